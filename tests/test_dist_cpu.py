@@ -210,6 +210,45 @@ def test_bench_stub_world_8_with_a_ragged_last_shard():
     assert doc["scaling"] == "weak" and doc["value"] > 0
 
 
+def test_bench_dump_outputs_layout_and_sample(tmp_path):
+    """bench.py --dump-outputs writes the last step's result arrays as float32 / float64 .npy files: slots past a frame's count are
+    id -1 and zeros whatever the device left there, and above the byte limit a seeded sample of whole frames (named by frame_index) is
+    written, the same sample on every run."""
+    import bench
+
+    rng = np.random.RandomState(5)
+    B, cap = 40, 64
+    m = np.zeros((B, cap), MARKER_DTYPE)
+    m["id"] = rng.randint(0, 1000, (B, cap))
+    m["corners"] = rng.rand(B, cap, 8) * 1000
+    m["ssize"], m["has_pose"] = rng.rand(B, cap), 1
+    m["rvec"], m["tvec"] = rng.randn(B, cap, 3), rng.randn(B, cap, 3)
+    counts = rng.randint(-1, cap + 2, B).astype(np.int32)
+    boards = [{"n_markers": i, "has_pose": i % 2, "rvec": rng.randn(3), "tvec": rng.randn(3), "prob": 0.5} for i in range(B)]
+    bench.dump_outputs(str(tmp_path / "all"), 100 + np.arange(B), counts, m, boards)
+    d = {f[:-4]: np.load(str(tmp_path / "all" / f)) for f in os.listdir(str(tmp_path / "all"))}
+    assert all(v.dtype in (np.float32, np.float64) and len(v) == B for v in d.values())
+    assert d["corners"].shape == (B, cap, 4, 2) and d["rvec"].shape == (B, cap, 3) and d["board_tvec"].shape == (B, 3)
+    n = np.clip(counts, 0, cap)
+    for f in range(B):
+        assert np.array_equal(d["ids"][f, :n[f]], m["id"][f, :n[f]]) and (d["ids"][f, n[f]:] == -1).all()
+        assert np.array_equal(d["corners"][f, :n[f]].reshape(-1, 8), m["corners"][f, :n[f]]) and not d["corners"][f, n[f]:].any()
+        assert np.array_equal(d["tvec"][f, :n[f]], m["tvec"][f, :n[f]]) and not d["tvec"][f, n[f]:].any()
+    assert np.array_equal(d["frame_index"], 100 + np.arange(B)) and np.array_equal(d["counts"], counts)
+    limit = 150000                          # about half of the 40 frames
+    samples = []
+    for k in range(2):
+        out = tmp_path / ("s%d" % k)
+        bench.dump_outputs(str(out), 100 + np.arange(B), counts, m, boards, prefix="rank1_", limit=limit)
+        assert sum(os.path.getsize(str(out / f)) for f in os.listdir(str(out))) <= limit
+        samples.append({f: np.load(str(out / f)) for f in os.listdir(str(out))})
+    s = samples[0]
+    rows = (s["rank1_frame_index.npy"] - 100).astype(int)
+    assert 0 < len(rows) < B and (np.diff(rows) > 0).all()
+    assert np.array_equal(s["rank1_ids.npy"], d["ids"][rows]) and np.array_equal(s["rank1_board_rvec.npy"], d["board_rvec"][rows])
+    assert all(np.array_equal(s[k], samples[1][k]) for k in s)
+
+
 def test_bench_refuses_more_ranks_than_devices():
     """`--gpus N` with fewer than N visible HIP devices: a clear message and a non-zero exit code BEFORE any GPU call or rank is started
     (this container has no GPU at all; on a one-GPU box the same holds for --gpus 2)."""
