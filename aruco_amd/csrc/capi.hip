@@ -71,46 +71,72 @@ static const int kKernelStage[K_COUNT] = {STAGE_THRESHOLD, STAGE_RECTANGLES, STA
                                           STAGE_IDENTIFY, STAGE_IDENTIFY, STAGE_SUBPIXEL, STAGE_FILTERING, STAGE_FILTERING};
 constexpr int TSETS = 32;
 
+// Memory the handle owns: device memory, or pinned host memory for staging the host reads. reserve() replaces the allocation only when
+// `need` exceeds the capacity (exact size, no slack, never shrinks) and then bumps `epoch`, the handle's alloc_epoch: the single-frame
+// graph compares it with its capture's, since its launches carry the pointers by value. The destructor frees.
+template <typename T>
+struct Mem {
+    T* p = nullptr;
+    size_t bytes = 0;
+    bool pinned = false;
+    explicit Mem(bool pinned_ = false) : pinned(pinned_) {}
+    Mem(Mem&& o) noexcept : p(o.p), bytes(o.bytes), pinned(o.pinned) { o.p = nullptr, o.bytes = 0; }
+    ~Mem() { (void)release(); }
+    operator T*() const { return p; }
+    hipError_t reserve(size_t need, uint64_t& epoch) {
+        if (need <= bytes) return hipSuccess;
+        epoch++;
+        hipError_t e = release();
+        if (e == hipSuccess) e = pinned ? hipHostMalloc((void**)&p, need) : hipMalloc((void**)&p, need);
+        if (e == hipSuccess)
+            bytes = need;
+        else
+            p = nullptr;
+        return e;
+    }
+
+private:
+    hipError_t release() {
+        const hipError_t e = p ? (pinned ? hipHostFree(p) : hipFree(p)) : hipSuccess;
+        p = nullptr, bytes = 0;
+        return e;
+    }
+};
+
 struct arucohip_handle {
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
     arucohip_params_t params;
     arucohip_limits_t lim;
-    Buffers buf{};
-    uint8_t* d_gray = nullptr;        // staging for host frames (gray) and the converted BGR frames
-    size_t gray_bytes = 0;
-    uint8_t* d_bgr = nullptr;         // staging for host BGR frames
-    size_t bgr_bytes = 0;
+    Buffers buf{};                    // views: the create-time arrays live in `held`, walk_scratch and patches below
+    uint64_t alloc_epoch = 0;         // replacements of owned memory so far (Mem::reserve)
+    std::vector<Mem<void>> held;      // create-time memory, held for the handle's life: the Buffers arrays, zero_block, d_small_*, d_patch, pinned staging
+    Mem<uint32_t> walk_scratch;       // buf.walk_scratch
+    Mem<uint8_t> patches;             // buf.patches
+    Mem<uint8_t> d_gray;              // staging for host frames (gray) and the converted BGR frames
+    Mem<uint8_t> d_bgr;               // staging for host BGR frames
     arucohip_marker_t* wt_out = nullptr;   // set around detect_core by chunk_enqueue: finalize_kernel writes the results there too
     int32_t* wt_n = nullptr;
     int wt_cap = 0;
-    uint8_t* d_erode = nullptr;       // eroded planes (params.erode)
-    size_t erode_bytes = 0;
-    uint8_t* d_canny = nullptr;       // CANNY: survivor tiles, edge tiles, changed flag
-    size_t canny_bytes = 0;
-    // frame undistortion (arucohip_undistort): the map of the last camera is kept
-    short2* d_umap_xy = nullptr;
-    uint16_t* d_umap_f = nullptr;
-    size_t umap_px = 0;
+    Mem<uint8_t> d_erode;             // eroded planes (params.erode)
+    Mem<uint64_t> d_canny;            // CANNY: survivor tiles, edge tiles, changed flag
+    // frame undistortion (arucohip_undistort): the map of the last camera is kept (umap_nd = -1: none)
+    Mem<short2> d_umap_xy;
+    Mem<uint16_t> d_umap_f;
     int umap_w = 0, umap_h = 0, umap_nd = -1;
     float umap_K[9] = {}, umap_d[8] = {};
-    uint8_t* d_undist = nullptr;      // undistorted frames when the caller wants them on the host
-    size_t undist_bytes = 0;
+    Mem<uint8_t> d_undist;            // undistorted frames when the caller wants them on the host
     // highly reliable markers (arucohip_set_dictionary)
-    uint64_t* d_hrm = nullptr;
+    Mem<uint64_t> d_hrm;
     int hrm_n = 0, hrm_count = 0, hrm_tau0 = 0;
     float hrm_rate = 1.f;
     // caller's own decoder (arucohip_set_decoder_callback)
     arucohip_decoder_fn decoder_fn = nullptr;
     void* decoder_user = nullptr;
-    int2* d_user_dec = nullptr;       // [cap_flat] {id, nRotations} returned by the callback
-    uint32_t* hu_list = nullptr;      // pinned staging of the callback path: candidate list, decoder results, call order
-    size_t hu_list_bytes = 0;
-    uint8_t* hu_patches = nullptr;    // pinned staging: the canonical patches handed to the callback (+ one scratch patch)
-    size_t hu_patch_bytes = 0;
-    size_t scratch_words = 0;         // capacity of buf.walk_scratch
+    Mem<int2> d_user_dec;             // [cap_flat] {id, nRotations} returned by the callback
+    Mem<uint32_t> hu_list{true};      // pinned staging of the callback path: candidate list, decoder results, call order
+    Mem<uint8_t> hu_patches{true};    // pinned staging: the canonical patches handed to the callback (+ one scratch patch)
     size_t bits_bytes = 0;
-    size_t patch_bytes = 0;           // capacity of buf.patches
     int bits_w = 0, bits_h = 0;       // geometry the bit image was last written with (pad words depend on it)
     // pinned host staging
     arucohip_marker_t* h_markers = nullptr;
@@ -121,11 +147,10 @@ struct arucohip_handle {
     double* d_small_d = nullptr;      // 64 doubles
     int* d_small_i = nullptr;
     uint8_t* d_patch = nullptr;       // MAX_WARP^2
-    void* d_board = nullptr;          // batched board results + ids
+    Mem<arucohip_board_t> d_board;    // batched board results + ids
     uint32_t* zero_block = nullptr;   // counters, gen_cnt, trig_cnt, raw_cnt, ring_cnt: zeroed together at the start of a batch
     size_t zero_words = 0;
-    double* d_gl = nullptr;           // batched GL modelview matrices
-    size_t gl_bytes = 0;
+    Mem<double> d_gl;                 // batched GL modelview matrices
     // last call
     int last_w = 0, last_h = 0, last_frames = 0, last_nthr = 1;
     const uint8_t* last_gray = nullptr;
@@ -154,6 +179,8 @@ struct arucohip_handle {
         hipGraphExec_t exec = nullptr;
         uint64_t key = 0;          // digest of everything the captured launches carry by value
         uint64_t seen = 0;         // key of the previous eager call: the second call with the same key captures (buffers are sized by then)
+        uint64_t epoch = 0;        // alloc_epoch at the capture: the buffers the launches point into are still the captured ones while it holds
+        bool thres_bytes = false;  // what the captured threshold left in buf.thres (a replay sets thres_bytes to it)
         int disabled = 0;          // ARUCOHIP_GRAPH=0, or a capture failed once
     } fgraph;
     // Batches in flight (arucohip_set_pipeline_depth / _submit / _wait): every pipeline lane is a complete worker (own
@@ -202,6 +229,15 @@ static arucohip_handle* route(arucohip_handle* h, int frame, int* local) {
 static int fail(arucohip_handle* h, int code, const char* msg) {
     if (h) h->err = msg;
     return code;
+}
+
+// create-time memory: held by the handle for its whole life, `view` is the pointer the code uses
+template <typename T>
+static hipError_t hold(arucohip_handle* h, T*& view, size_t bytes, bool pinned = false) {
+    Mem<void>& m = h->held.emplace_back(pinned);
+    const hipError_t e = m.reserve(bytes, h->alloc_epoch);
+    view = (T*)m.p;
+    return e;
 }
 
 extern "C" {
@@ -261,6 +297,7 @@ static int validate_params(arucohip_handle* h, const arucohip_params_t* p) {
 }
 
 extern "C" void arucohip_destroy(arucohip_handle* h);
+// everything but the memory, which the handle's Mem members free when it is deleted
 static void free_all(arucohip_handle* h) {
     hipSetDevice(h->device);
     for (auto* k : h->kids) arucohip_destroy(k);
@@ -279,15 +316,6 @@ static void free_all(arucohip_handle* h) {
     if (h->side_stream) hipStreamDestroy(h->side_stream);
     for (auto& e : h->ev_join)
         if (e) hipEventDestroy(e);
-    hipFree(h->buf.thr_stamps), hipFree(h->buf.thr_acc), hipFree(h->buf.thres_edge);
-    hipFree(h->buf.thres), hipFree(h->buf.tiles), hipFree(h->buf.tile_bits), hipFree(h->buf.raw), hipFree(h->buf.trig), hipFree(h->buf.gen_buf), hipFree(h->zero_block), hipFree(h->buf.cdesc), hipFree(h->buf.pool);
-    hipFree(h->buf.quads), hipFree(h->buf.cands), hipFree(h->buf.ncands), hipFree(h->buf.cand_list), hipFree(h->buf.iM), hipFree(h->buf.hist), hipFree(h->buf.othr), hipFree(h->buf.markers), hipFree(h->buf.nmarkers), hipFree(h->buf.marker_list);
-    hipFree(h->buf.walk_scratch), hipFree(h->buf.node), hipFree(h->buf.skipn), hipFree(h->buf.stamp), hipFree(h->buf.hash), hipFree(h->buf.patches), hipFree(h->d_gray), hipFree(h->d_bgr), hipFree(h->d_erode), hipFree(h->d_canny), hipFree(h->d_umap_xy), hipFree(h->d_umap_f), hipFree(h->d_undist), hipFree(h->d_hrm), hipFree(h->d_user_dec), hipFree(h->d_small_f), hipFree(h->d_small_d), hipFree(h->d_small_i), hipFree(h->d_patch), hipFree(h->d_board), hipFree(h->d_gl);
-    if (h->hu_list) hipHostFree(h->hu_list);
-    if (h->hu_patches) hipHostFree(h->hu_patches);
-    if (h->h_markers) hipHostFree(h->h_markers);
-    if (h->h_n) hipHostFree(h->h_n);
-    if (h->h_counters) hipHostFree(h->h_counters);
     for (auto& set : h->ev)
         for (auto& e : set)
             if (e) hipEventDestroy(e);
@@ -363,7 +391,7 @@ int arucohip_create_ex(const arucohip_params_t* params, int device, const arucoh
     b.cap_quads = std::min(lim->candidates_per_frame * 2, 512);
     b.cap_cands = lim->candidates_per_frame;
     b.cap_markers = lim->markers_per_frame;
-#define ALLOC(ptr, bytes) if ((e = hipMalloc((void**)&(ptr), (bytes))) != hipSuccess) return bail(e)
+#define ALLOC(ptr, bytes) if ((e = hold(h, ptr, (bytes))) != hipSuccess) return bail(e)
     ALLOC(b.thres, P * px);
     ALLOC(b.thres_edge, P * thres_edge_stride(lim->max_width, lim->max_height));
     {   // timing stamps of the wide threshold kernel: its finest grid is one wave per 1024-px strip and 16 rows
@@ -431,9 +459,9 @@ int arucohip_create_ex(const arucohip_params_t* params, int device, const arucoh
     ALLOC(h->d_small_i, 64 * sizeof(int));
     ALLOC(h->d_patch, 128 * 128);
 #undef ALLOC
-    if ((e = hipHostMalloc((void**)&h->h_markers, (F * b.cap_markers + 1) * sizeof(arucohip_marker_t))) != hipSuccess) return bail(e);
-    if ((e = hipHostMalloc((void**)&h->h_n, F * sizeof(int32_t))) != hipSuccess) return bail(e);
-    if ((e = hipHostMalloc((void**)&h->h_counters, (CNT_FIXED + F) * sizeof(uint32_t))) != hipSuccess) return bail(e);
+    if ((e = hold(h, h->h_markers, (F * b.cap_markers + 1) * sizeof(arucohip_marker_t), true)) != hipSuccess) return bail(e);
+    if ((e = hold(h, h->h_n, F * sizeof(int32_t), true)) != hipSuccess) return bail(e);
+    if ((e = hold(h, h->h_counters, (CNT_FIXED + F) * sizeof(uint32_t), true)) != hipSuccess) return bail(e);
     for (auto& set : h->ev)
         for (auto& ev : set)
             if ((e = hipEventCreate(&ev)) != hipSuccess) return bail(e);
@@ -691,26 +719,24 @@ static int ensure_bits_geometry(arucohip_handle* h, int W, int H) {
     return ARUCOHIP_OK;
 }
 
-// canonical patches of the decode stage: cap_flat * warp_size^2 bytes
-static int ensure_patches(arucohip_handle* h, const DetectParams& dp) {
-    size_t need = (size_t)h->buf.cap_flat * dp.warp_size * dp.warp_size;
-    if (need <= h->patch_bytes) return ARUCOHIP_OK;
-    if (h->buf.patches) HIPCHK(h, hipFree(h->buf.patches));
-    h->buf.patches = nullptr, h->patch_bytes = 0;
-    HIPCHK(h, hipMalloc((void**)&h->buf.patches, need));
-    h->patch_bytes = need;
-    return ARUCOHIP_OK;
-}
-
 // the long walks keep their checkpoint rings in HBM; (re)size the space for this batch
 static int ensure_walk_scratch(arucohip_handle* h, int nplanes, const DetectParams& dp) {
     size_t need = walk_scratch_words(nplanes, dp, h->buf.long_cap);
     if (need > 0xFFFFFFF0ull) return fail(h, ARUCOHIP_E_CAPACITY, "batch too large for 32-bit checkpoint offsets: fewer frames per batch or a smaller max size");
-    if (need <= h->scratch_words) return ARUCOHIP_OK;
-    if (h->buf.walk_scratch) HIPCHK(h, hipFree(h->buf.walk_scratch));
-    h->buf.walk_scratch = nullptr, h->scratch_words = 0;
-    HIPCHK(h, hipMalloc((void**)&h->buf.walk_scratch, need * sizeof(uint32_t)));
-    h->scratch_words = need;
+    HIPCHK(h, h->walk_scratch.reserve(need * sizeof(uint32_t), h->alloc_epoch));
+    h->buf.walk_scratch = h->walk_scratch;
+    return ARUCOHIP_OK;
+}
+
+// Host-side work in front of a batch's enqueued work (detect_core), which a captured graph does not repeat: the eager path and every graph
+// replay run it first. In steady state it only compares integers.
+static int batch_prologue(arucohip_handle* h, const FrameGeom& g, int nframes, const DetectParams& dp) {
+    int rc;
+    if ((rc = ensure_walk_scratch(h, nframes * dp.nthr, dp))) return rc;
+    if ((rc = ensure_bits_geometry(h, g.width, g.height))) return rc;
+    // canonical patches of the decode stage: cap_flat * warp_size^2 bytes
+    HIPCHK(h, h->patches.reserve((size_t)h->buf.cap_flat * dp.warp_size * dp.warp_size, h->alloc_epoch));
+    h->buf.patches = h->patches;
     return ARUCOHIP_OK;
 }
 
@@ -722,16 +748,7 @@ static int user_decode_stage(arucohip_handle* h, const DetectParams& dp) {
     const Buffers& b = h->buf;
     // pinned staging owned by the handle, grown on demand: the steady state of a stream of calls allocates nothing
     const size_t npx = (size_t)dp.warp_size * dp.warp_size;
-    auto pinned = [&](void** p, size_t* have, size_t need) -> int {
-        if (need <= *have) return ARUCOHIP_OK;
-        if (*p) HIPCHK(h, hipHostFree(*p));
-        *p = nullptr, *have = 0;
-        HIPCHK(h, hipHostMalloc(p, need));
-        *have = need;
-        return ARUCOHIP_OK;
-    };
-    int rc;
-    if ((rc = pinned((void**)&h->hu_list, &h->hu_list_bytes, (size_t)b.cap_flat * (sizeof(uint32_t) + sizeof(int2) + sizeof(uint32_t)) + sizeof(uint32_t)))) return rc;
+    HIPCHK(h, h->hu_list.reserve((size_t)b.cap_flat * (sizeof(uint32_t) + sizeof(int2) + sizeof(uint32_t)) + sizeof(uint32_t), h->alloc_epoch));
     uint32_t* list = h->hu_list;                                   // [cap_flat] frame << 16 | index
     int2* dec = (int2*)(list + b.cap_flat);                        // [cap_flat] {id, nRotations}
     uint32_t* order = (uint32_t*)(dec + b.cap_flat);               // [cap_flat] + the candidate count behind it
@@ -740,7 +757,7 @@ static int user_decode_stage(arucohip_handle* h, const DetectParams& dp) {
     HIPCHK(h, hipStreamSynchronize(s));
     const uint32_t n = std::min(*ncand_p, b.cap_flat);
     if (!n) return ARUCOHIP_OK;
-    if ((rc = pinned((void**)&h->hu_patches, &h->hu_patch_bytes, (size_t)n * npx + npx))) return rc;
+    HIPCHK(h, h->hu_patches.reserve((size_t)n * npx + npx, h->alloc_epoch));
     uint8_t* patches = h->hu_patches;
     uint8_t* scratch = patches + (size_t)n * npx;
     HIPCHK(h, hipMemcpyAsync(list, b.cand_list, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -755,7 +772,7 @@ static int user_decode_stage(arucohip_handle* h, const DetectParams& dp) {
         const int id = h->decoder_fn(h->decoder_user, scratch, dp.warp_size, &nrot);
         dec[i] = make_int2(id < 0 ? -1 : id, nrot & 3);
     }
-    if (!h->d_user_dec) HIPCHK(h, hipMalloc((void**)&h->d_user_dec, (size_t)b.cap_flat * sizeof(int2)));   // once per handle
+    HIPCHK(h, h->d_user_dec.reserve((size_t)b.cap_flat * sizeof(int2), h->alloc_epoch));   // once per handle
     HIPCHK(h, hipMemcpyAsync(h->d_user_dec, dec, n * sizeof(int2), hipMemcpyHostToDevice, s));
     launch_set_decoded(s, b, n, h->d_user_dec);
     // no synchronise: the staging belongs to the handle, and the next call that touches it synchronises the stream first (the count above)
@@ -785,8 +802,6 @@ static void run_rectangles(arucohip_handle* h, const FrameGeom& g, int nframes, 
     launch_frame_candidates(h->stream, g, nframes, dp, h->buf);
 }
 
-static int grow(arucohip_handle* h, uint8_t** buf, size_t* have, size_t need);
-
 // threshold stage of any method into buf.thres / buf.tiles (+ bitmap). CANNY (markerdetector.cpp:667-676) blocks the host while its
 // hysteresis converges.
 // want_bytes: the caller reads buf.thres right away (stage entry point, erosion); otherwise the byte image may be left as tiles + border
@@ -800,9 +815,8 @@ static int run_threshold(arucohip_handle* h, hipStream_t s, const uint8_t* gray_
         return ARUCOHIP_OK;
     }
     const size_t ntiles = (size_t)nframes * dp.nthr * ((g.width + 7) / 8) * ((g.height + 7) / 8);
-    int rc = grow(h, &h->d_canny, &h->canny_bytes, 2 * ntiles * sizeof(uint64_t) + 64);
-    if (rc) return rc;
-    uint64_t* surv = (uint64_t*)h->d_canny;
+    HIPCHK(h, h->d_canny.reserve(2 * ntiles * sizeof(uint64_t) + 64, h->alloc_epoch));
+    uint64_t* surv = h->d_canny;
     uint64_t* edge = surv + ntiles;
     if (launch_canny(s, gray_dev, g, nframes, dp.nthr, b, surv, edge, (uint32_t*)(edge + ntiles))) return fail(h, ARUCOHIP_E_HIP, "CANNY kernels failed");
     FrameGeom tg = g;
@@ -814,12 +828,6 @@ static int run_threshold(arucohip_handle* h, hipStream_t s, const uint8_t* gray_
 static int detect_core(arucohip_handle* h, const uint8_t* gray_dev, const FrameGeom& g, int nframes, const DetectParams& dp, const CamModel& cam) {
     hipStream_t s = h->stream;
     Buffers& b = h->buf;
-    {
-        int rc_ = ensure_walk_scratch(h, nframes * dp.nthr, dp);
-        if (rc_) return rc_;
-        if ((rc_ = ensure_bits_geometry(h, g.width, g.height))) return rc_;
-        if ((rc_ = ensure_patches(h, dp))) return rc_;
-    }
     HIPCHK(h, hipMemsetAsync(h->zero_block, 0, h->zero_words * sizeof(uint32_t), s));
     hipEvent_t* ev = h->ev[h->tsets % TSETS];
     const bool tm = h->timing;
@@ -833,8 +841,7 @@ static int detect_core(arucohip_handle* h, const uint8_t* gray_dev, const FrameG
     if (h->params.erode) {
         // on the bit tiles where the byte image was left out (the default path), on the bytes otherwise
         const bool on_tiles = !h->thres_bytes;
-        int rc_ = grow(h, &h->d_erode, &h->erode_bytes, on_tiles ? erode_tiles_tmp_bytes(g, nframes * dp.nthr) : (size_t)nframes * dp.nthr * g.width * g.height);
-        if (rc_) return rc_;
+        HIPCHK(h, h->d_erode.reserve(on_tiles ? erode_tiles_tmp_bytes(g, nframes * dp.nthr) : (size_t)nframes * dp.nthr * g.width * g.height, h->alloc_epoch));
         if (on_tiles)
             launch_erode_tiles(s, g, nframes * dp.nthr, b, h->d_erode);
         else
@@ -892,31 +899,21 @@ static int detect_core(arucohip_handle* h, const uint8_t* gray_dev, const FrameG
     return ARUCOHIP_OK;
 }
 
-static int grow(arucohip_handle* h, uint8_t** buf, size_t* have, size_t need) {
-    if (need <= *have) return ARUCOHIP_OK;
-    if (*buf) HIPCHK(h, hipFree(*buf));
-    *buf = nullptr, *have = 0;
-    HIPCHK(h, hipMalloc((void**)buf, need));
-    *have = need;
-    return ARUCOHIP_OK;
-}
-
 // channels = 1: gray frames (device frames are used in place); channels = 3: B,G,R interleaved, converted into d_gray
 static int stage_frames(arucohip_handle* h, const uint8_t* frames, int nframes, int W, int H, size_t row_stride, size_t frame_stride,
                         int on_device, int channels, const uint8_t** gray_dev, FrameGeom* g) {
     g->width = W, g->height = H;
-    int rc;
     if (channels == 3) {
         const uint8_t* bgr = frames;
         size_t rs = row_stride, fs = frame_stride;
         if (!on_device) {
-            if ((rc = grow(h, &h->d_bgr, &h->bgr_bytes, (size_t)nframes * W * H * 3))) return rc;
+            HIPCHK(h, h->d_bgr.reserve((size_t)nframes * W * H * 3, h->alloc_epoch));
             for (int f = 0; f < nframes; f++)
                 HIPCHK(h, hipMemcpy2DAsync(h->d_bgr + (size_t)f * W * H * 3, (size_t)W * 3, frames + (size_t)f * frame_stride, row_stride, (size_t)W * 3, H,
                                            hipMemcpyHostToDevice, h->stream));
             bgr = h->d_bgr, rs = (size_t)W * 3, fs = (size_t)W * H * 3;
         }
-        if ((rc = grow(h, &h->d_gray, &h->gray_bytes, (size_t)nframes * W * H))) return rc;
+        HIPCHK(h, h->d_gray.reserve((size_t)nframes * W * H, h->alloc_epoch));
         launch_bgr2gray(h->stream, bgr, rs, fs, W, H, nframes, h->d_gray);
         HIPCHK(h, hipGetLastError());
         *gray_dev = h->d_gray;
@@ -928,7 +925,7 @@ static int stage_frames(arucohip_handle* h, const uint8_t* frames, int nframes, 
         g->row_stride = row_stride, g->frame_stride = frame_stride;
         return ARUCOHIP_OK;
     }
-    if ((rc = grow(h, &h->d_gray, &h->gray_bytes, (size_t)nframes * W * H))) return rc;
+    HIPCHK(h, h->d_gray.reserve((size_t)nframes * W * H, h->alloc_epoch));
     if (row_stride == (size_t)W && frame_stride == (size_t)W * H) {
         // tightly packed frames (a pinned ring of camera frames): ONE copy for the batch instead of one 2-D copy per frame
         HIPCHK(h, hipMemcpyAsync(h->d_gray, frames, (size_t)nframes * W * H, hipMemcpyHostToDevice, h->stream));
@@ -960,6 +957,7 @@ static int chunk_enqueue(arucohip_handle* w, const uint8_t* frames, int nframes,
     const uint8_t* gray_dev;
     FrameGeom g;
     if ((rc = stage_frames(w, frames, nframes, W, H, row_stride, frame_stride, frames_on_device, channels, &gray_dev, &g))) return rc;
+    if ((rc = batch_prologue(w, g, nframes, dp))) return rc;
     // results for device memory without poses: finalize_kernel stores them there itself
     const bool write_through = out_on_device && !(cam.has_K && cam.marker_size > 0) && cap > 0;
     w->wt_out = write_through ? out : nullptr, w->wt_cap = write_through ? cap : 0, w->wt_n = write_through ? n_out : nullptr;
@@ -1038,9 +1036,9 @@ static uint64_t digest(uint64_t hsh, const void* p, size_t n) {
 }
 
 // arucohip_detect on one host frame through a captured graph. *handled = false: the caller takes the eager path (first call of a
-// configuration, timing on, a decoder or threshold method that blocks the host, a failed capture). The frame's copy to the device is issued
-// eagerly in front of the graph; inside it: the counters' memset, every kernel of detect_core (with the fork to the side stream of the late
-// walker generations) and the three copies of the results into the handle's pinned staging.
+// configuration or after a buffer was replaced, timing on, a decoder or threshold method that blocks the host, a failed capture). The frame's
+// copy to the device and batch_prologue are issued eagerly in front of the graph; inside it: the counters' memset, every kernel of detect_core
+// (with the fork to the side stream of the late walker generations) and the copy of the results into the handle's pinned staging.
 static int detect_one_graphed(arucohip_handle* h, const uint8_t* frame, int W, int H, size_t row_stride, int channels, const DetectParams& dp, const CamModel& cam,
                               arucohip_marker_t* out, int cap, int32_t* n_out, bool* handled) {
     *handled = false;
@@ -1063,8 +1061,15 @@ static int detect_one_graphed(arucohip_handle* h, const uint8_t* frame, int W, i
     const uint8_t* gray_dev;
     FrameGeom g;
     if ((rc = stage_frames(h, frame, 1, W, H, row_stride, (size_t)H * row_stride, 0, channels, &gray_dev, &g))) return rc;   // H2D (+ BGR conversion), eager
+    if ((rc = batch_prologue(h, g, 1, dp))) return rc;   // also restores the bit-image geometry on the stream, ahead of the launch
     h->last_chunks = 1, h->last_per = 1;
+    if (h->fgraph.exec && h->fgraph.epoch != h->alloc_epoch) {   // a buffer was replaced since the capture: start over, like a new configuration
+        (void)hipGraphExecDestroy(h->fgraph.exec);
+        h->fgraph.exec = nullptr, h->fgraph.seen = key;
+        return ARUCOHIP_OK;   // the frame is staged; the eager path stages it again, which is harmless
+    }
     if (!h->fgraph.exec) {
+        const uint64_t epoch = h->alloc_epoch;
         hipGraph_t graph = nullptr;
         if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
             (void)hipGetLastError();
@@ -1079,17 +1084,19 @@ static int detect_one_graphed(arucohip_handle* h, const uint8_t* frame, int W, i
             e = hipMemcpyAsync(h->h_markers, b.markers, ((size_t)b.cap_markers + 1) * sizeof(arucohip_marker_t), hipMemcpyDeviceToHost, h->stream);
         }
         const hipError_t e2 = hipStreamEndCapture(h->stream, &graph);
-        if (rc != ARUCOHIP_OK || e != hipSuccess || e2 != hipSuccess || !graph || hipGraphInstantiate(&h->fgraph.exec, graph, nullptr, nullptr, 0) != hipSuccess) {
+        if (rc != ARUCOHIP_OK || e != hipSuccess || e2 != hipSuccess || !graph || h->alloc_epoch != epoch ||
+            hipGraphInstantiate(&h->fgraph.exec, graph, nullptr, nullptr, 0) != hipSuccess) {
             (void)hipGetLastError();
             if (graph) (void)hipGraphDestroy(graph);
             h->fgraph.exec = nullptr, h->fgraph.disabled = 1;   // this handle stays on the eager path
             return ARUCOHIP_OK;
         }
         (void)hipGraphDestroy(graph);
-        h->fgraph.key = key;
+        h->fgraph.key = key, h->fgraph.epoch = epoch, h->fgraph.thres_bytes = h->thres_bytes;
     }
     *handled = true;
     HIPCHK(h, hipGraphLaunch(h->fgraph.exec, h->stream));
+    h->thres_bytes = h->fgraph.thres_bytes;
     h->last_w = W, h->last_h = H, h->last_frames = 1, h->last_nthr = dp.nthr, h->last_gray = gray_dev, h->last_geom = g;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const int32_t* hdr = (const int32_t*)(h->h_markers + h->buf.cap_markers);
@@ -1190,18 +1197,13 @@ int arucohip_undistort(arucohip_handle* h, const uint8_t* src, int nframes, int 
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     // map of this camera: recomputed only when size, K or dist change
-    bool same = h->d_umap_xy && h->umap_w == W && h->umap_h == H && h->umap_nd == ndist && std::memcmp(h->umap_K, K, sizeof(h->umap_K)) == 0 &&
+    bool same = h->umap_w == W && h->umap_h == H && h->umap_nd == ndist && std::memcmp(h->umap_K, K, sizeof(h->umap_K)) == 0 &&
                 (ndist == 0 || std::memcmp(h->umap_d, dist, ndist * sizeof(float)) == 0);
     if (!same) {
         const size_t px = (size_t)W * H;
-        if (px > h->umap_px) {
-            if (h->d_umap_xy) HIPCHK(h, hipFree(h->d_umap_xy));
-            if (h->d_umap_f) HIPCHK(h, hipFree(h->d_umap_f));
-            h->d_umap_xy = nullptr, h->d_umap_f = nullptr, h->umap_px = 0;
-            HIPCHK(h, hipMalloc((void**)&h->d_umap_xy, px * sizeof(short2)));
-            HIPCHK(h, hipMalloc((void**)&h->d_umap_f, px * sizeof(uint16_t)));
-            h->umap_px = px;
-        }
+        h->umap_nd = -1;   // no valid map until this one is written
+        HIPCHK(h, h->d_umap_xy.reserve(px * sizeof(short2), h->alloc_epoch));
+        HIPCHK(h, h->d_umap_f.reserve(px * sizeof(uint16_t), h->alloc_epoch));
         launch_undist_map(s, W, H, K, dist, ndist, h->d_umap_xy, h->d_umap_f);
         HIPCHK(h, hipGetLastError());
         h->umap_w = W, h->umap_h = H, h->umap_nd = ndist;
@@ -1212,7 +1214,7 @@ int arucohip_undistort(arucohip_handle* h, const uint8_t* src, int nframes, int 
     const uint8_t* sdev = src;
     size_t rs = row_stride, fs = frame_stride;
     if (!src_on_device) {
-        if ((rc = grow(h, &h->d_bgr, &h->bgr_bytes, (size_t)nframes * fbytes))) return rc;
+        HIPCHK(h, h->d_bgr.reserve((size_t)nframes * fbytes, h->alloc_epoch));
         for (int f = 0; f < nframes; f++)
             HIPCHK(h, hipMemcpy2DAsync(h->d_bgr + (size_t)f * fbytes, (size_t)W * channels, src + (size_t)f * frame_stride, row_stride, (size_t)W * channels, H,
                                        hipMemcpyHostToDevice, s));
@@ -1220,7 +1222,7 @@ int arucohip_undistort(arucohip_handle* h, const uint8_t* src, int nframes, int 
     }
     uint8_t* ddev = dst;
     if (!dst_on_device) {
-        if ((rc = grow(h, &h->d_undist, &h->undist_bytes, (size_t)nframes * fbytes))) return rc;
+        HIPCHK(h, h->d_undist.reserve((size_t)nframes * fbytes, h->alloc_epoch));
         ddev = h->d_undist;
     }
     launch_remap(s, sdev, rs, fs, W, H, channels, nframes, h->d_umap_xy, h->d_umap_f, ddev);
@@ -1237,11 +1239,10 @@ int arucohip_set_dictionary(arucohip_handle* h, int n, int count, const uint64_t
     drop_retry(h);
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_hrm) HIPCHK(h, hipFree(h->d_hrm));
-    h->d_hrm = nullptr, h->hrm_count = 0, h->hrm_n = 0;
+    h->hrm_count = 0, h->hrm_n = 0;
     if (count > 0) {
         if (!codes || n < 2 || n > 8 || count > 4096) return fail(h, ARUCOHIP_E_UNSUPPORTED, "dictionary: 2 <= n <= 8, count <= 4096");
-        HIPCHK(h, hipMalloc((void**)&h->d_hrm, (size_t)count * sizeof(uint64_t)));
+        HIPCHK(h, h->d_hrm.reserve((size_t)count * sizeof(uint64_t), h->alloc_epoch));
         HIPCHK(h, hipMemcpy(h->d_hrm, codes, (size_t)count * sizeof(uint64_t), hipMemcpyHostToDevice));
         h->hrm_n = n, h->hrm_count = count, h->hrm_tau0 = tau0, h->hrm_rate = correction_rate;
     }
@@ -1633,9 +1634,8 @@ int arucohip_board_detect_batch(arucohip_handle* h, int nframes, const int32_t* 
         arucohip_handle* w = c == 0 ? h : h->kids[c - 1];
         const int off = c * per, cnt = std::min(per, nframes - off);
         if (cnt <= 0) break;
-        if (!w->d_board)
-            HIPCHK(h, hipMalloc((void**)&w->d_board, (size_t)w->cap_frames * (sizeof(arucohip_board_t) + sizeof(float)) + 8192 * sizeof(int32_t)));
-        arucohip_board_t* d_out = (arucohip_board_t*)w->d_board;
+        HIPCHK(h, w->d_board.reserve((size_t)w->cap_frames * (sizeof(arucohip_board_t) + sizeof(float)) + 8192 * sizeof(int32_t), w->alloc_epoch));
+        arucohip_board_t* d_out = w->d_board;
         float* d_prob = (float*)(d_out + w->cap_frames);
         int32_t* d_ids = (int32_t*)(d_prob + w->cap_frames);
         HIPCHK(h, hipMemcpyAsync(d_ids, ids, (size_t)nboard * sizeof(int32_t), hipMemcpyHostToDevice, w->stream));
@@ -1664,12 +1664,7 @@ int arucohip_gl_modelview_batch(arucohip_handle* h, int nframes, int cap, double
     if (nframes < 1 || nframes > h->last_frames) return fail(h, ARUCOHIP_E_INVALID, "nframes exceeds the last batch");
     HIPCHK(h, hipSetDevice(h->device));
     const size_t need = (size_t)nframes * cap * 16 * sizeof(double);
-    if (need > h->gl_bytes) {
-        if (h->d_gl) HIPCHK(h, hipFree(h->d_gl));
-        h->d_gl = nullptr, h->gl_bytes = 0;
-        HIPCHK(h, hipMalloc((void**)&h->d_gl, need));
-        h->gl_bytes = need;
-    }
+    HIPCHK(h, h->d_gl.reserve(need, h->alloc_epoch));
     launch_gl_modelview(h->stream, nframes, cap, h->buf, h->d_gl);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(modelview, h->d_gl, need, hipMemcpyDeviceToHost, h->stream));

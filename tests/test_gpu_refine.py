@@ -142,3 +142,54 @@ def test_single_frame_graph_path_returns_the_bytes_of_the_eager_path(case, monke
         assert graphed.detect(gray).tobytes() == graphed.detect(gray).tobytes() == graphed.detect(gray).tobytes()
     finally:
         eager.close(), graphed.close()
+
+
+@pytest.mark.parametrize("case,contours", [("synthetic_1080p", None), ("single", "segments")])
+def test_single_frame_graph_follows_batches_and_stage_calls_in_between(case, contours, monkeypatch):
+    """The single-frame graph carries device pointers and leaves the host-side prologue of a batch to its caller. On handles of max_batch=4 a
+    batch of 4 host frames replaces the frame staging and the checkpoint rings, and a threshold call at another width moves the bit image's
+    pad words and leaves a byte image behind. Eager handle (ARUCOHIP_GRAPH=0 at creation) against the default handle, the same calls on both:
+    detect x3 (eager, capture + launch, replay), a batch of 4, detect of another frame and of the first, threshold() at another width,
+    detect, thresholded(0) - identical bytes at every step. 1080p bench frames on the walkers (the default for batches), a still on the
+    waypoint segments."""
+    from aruco_amd import capi, synth
+
+    kw = {}
+    if case == "synthetic_1080p":
+        fr, _ = synth.make_stream(4, seed=4711, device="cpu")
+        frames = fr.numpy()
+    else:
+        gray, doc = load_case(case)
+        frames = np.stack([gray, gray[:, ::-1], gray[::-1], gray[::-1, ::-1]])
+        kw = dict(K=doc["intrinsics"]["K"], dist=doc["intrinsics"]["dist"], marker_size=1.0)
+    a, b = frames[0], frames[1]
+    hgt, wid = a.shape
+    narrow = np.ascontiguousarray(a[:, : wid - 64])
+    if contours:
+        monkeypatch.setenv("ARUCOHIP_CONTOURS", contours)
+    monkeypatch.setenv("ARUCOHIP_GRAPH", "0")
+    eager = capi.Handle(wid, hgt, max_batch=4)
+    monkeypatch.delenv("ARUCOHIP_GRAPH")
+    graphed = capi.Handle(wid, hgt, max_batch=4)
+    monkeypatch.delenv("ARUCOHIP_CONTOURS", raising=False)
+
+    def same(call):
+        want, got = call(eager), call(graphed)
+        if isinstance(want, list):
+            assert [x.tobytes() for x in got] == [x.tobytes() for x in want]
+        else:
+            assert got.tobytes() == want.tobytes()
+        return want
+
+    try:
+        assert len(same(lambda h: h.detect(a, **kw))) >= 1
+        for _ in range(2):
+            same(lambda h: h.detect(a, **kw))
+        same(lambda h: h.detect_batch_host(frames, **kw))
+        same(lambda h: h.detect(b, **kw))
+        same(lambda h: h.detect(a, **kw))
+        same(lambda h: h.threshold(narrow))
+        same(lambda h: h.detect(a, **kw))
+        same(lambda h: h.thresholded(0, (hgt, wid)))
+    finally:
+        eager.close(), graphed.close()
