@@ -17,6 +17,10 @@ OK, E_INVALID, E_CAPACITY, E_UNSUPPORTED, E_HIP, E_OVERFLOW, E_BOARD_CONFIG = ra
 THRES_FIXED, THRES_ADPT, THRES_CANNY = 0, 1, 2
 CORNER_NONE, CORNER_HARRIS, CORNER_SUBPIX, CORNER_LINES = 0, 1, 2, 3
 BOARD_NONE, BOARD_PIX, BOARD_METERS = -1, 0, 1
+# arucohip_calibrate_*: the values of cv::CALIB_*
+CALIB_USE_INTRINSIC_GUESS, CALIB_FIX_ASPECT_RATIO, CALIB_FIX_PRINCIPAL_POINT, CALIB_ZERO_TANGENT_DIST = 1, 2, 4, 8
+CALIB_FIX_FOCAL_LENGTH, CALIB_FIX_K1, CALIB_FIX_K2, CALIB_FIX_K3 = 16, 32, 64, 128
+CALIB_MAX_VIEW_POINTS = 512
 
 _ERR_NAMES = {1: "ARUCOHIP_E_INVALID", 2: "ARUCOHIP_E_CAPACITY", 3: "ARUCOHIP_E_UNSUPPORTED", 4: "ARUCOHIP_E_HIP",
               5: "ARUCOHIP_E_OVERFLOW", 6: "ARUCOHIP_E_BOARD_CONFIG"}
@@ -75,6 +79,7 @@ SYMBOLS = [
     "arucohip_mgpu_set_depth", "arucohip_mgpu_submit_batch", "arucohip_mgpu_submit_streams", "arucohip_mgpu_wait",
     "arucohip_compact_bytes", "arucohip_compact_markers", "arucohip_wait_event", "arucohip_detect_batch_retry_overflowed",
     "arucohip_refine_candidate_lines", "arucohip_mgpu_gather_mode", "arucohip_build_info",
+    "arucohip_calibrate_camera", "arucohip_calibrate_board_batch",
 ]
 
 _lib = None
@@ -135,6 +140,8 @@ def load():
     L.arucohip_kernel_name.argtypes = [i]
     L.arucohip_debug_counters.argtypes = [vp, vp]
     L.arucohip_board_detect_batch.argtypes = [vp, i, vp, vp, i, i, vp, vp, i, f, f, i, vp, vp]
+    L.arucohip_calibrate_camera.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp]
+    L.arucohip_calibrate_board_batch.argtypes = [vp, i, vp, vp, i, i, f, i, i, i, i, vp, vp, vp, vp, vp, vp]
     L.arucohip_detect_bgr.argtypes = [vp, vp, i, i, sz, vp, vp, i, f, i, vp, i, vp]
     L.arucohip_detect_batch_bgr.argtypes = [vp, vp, i, i, i, sz, sz, i, vp, vp, i, f, i, vp, i, vp, i]
     L.arucohip_bgr_to_gray.argtypes = [vp, vp, i, i, sz, vp]
@@ -566,6 +573,55 @@ class Handle:
                                                      int(bool(y_perp)), out, _ptr(prob)))
         return [{"n_markers": out[f].n_markers, "has_pose": out[f].has_pose, "rvec": np.array(out[f].rvec), "tvec": np.array(out[f].tvec),
                  "prob": float(prob[f])} for f in range(nframes)]
+
+    @staticmethod
+    def _calib_start(K, dist):
+        Ka = np.zeros(9) if K is None else np.array(K, dtype=np.float64).reshape(9)
+        da = np.zeros(5) if dist is None else np.array(dist, dtype=np.float64).reshape(-1)
+        if da.size != 5:
+            raise ValueError("dist must hold 5 coefficients (k1, k2, p1, p2, k3)")
+        return Ka, da
+
+    def calibrate_camera(self, obj_list, img_list, image_size, flags=0, K=None, dist=None):
+        """cv::calibrateCamera on planar views: obj_list[v] (n, 3), img_list[v] (n, 2); image_size = (width, height). K / dist: the
+        start with CALIB_USE_INTRINSIC_GUESS, K's fx / fy ratio with CALIB_FIX_ASPECT_RATIO."""
+        if len(obj_list) != len(img_list):
+            raise ValueError("obj_list and img_list differ in length")
+        objs = [np.asarray(o, np.float32).reshape(-1, 3) for o in obj_list]
+        imgs = [np.asarray(m, np.float32).reshape(-1, 2) for m in img_list]
+        if any(len(o) != len(m) for o, m in zip(objs, imgs)):
+            raise ValueError("a view has different numbers of object and image points")
+        npts = np.array([len(o) for o in objs], np.int32)
+        oa = np.ascontiguousarray(np.concatenate(objs) if objs else np.zeros((0, 3), np.float32))
+        ia = np.ascontiguousarray(np.concatenate(imgs) if imgs else np.zeros((0, 2), np.float32))
+        Ka, da = self._calib_start(K, dist)
+        V = len(objs)
+        rv, tv, pv, rms = np.zeros((V, 3)), np.zeros((V, 3)), np.zeros(V), C.c_double()
+        self._chk(self.L.arucohip_calibrate_camera(self.h, _ptr(oa), _ptr(ia), _ptr(npts), V, 0, int(image_size[0]), int(image_size[1]),
+                                                   int(flags), _ptr(Ka), _ptr(da), _ptr(rv), _ptr(tv), _ptr(pv), C.byref(rms)))
+        return {"rms": rms.value, "K": Ka.reshape(3, 3), "dist": da, "rvecs": rv, "tvecs": tv, "per_view_rms": pv}
+
+    def calibrate_camera_device(self, obj_ptr, img_ptr, npoints_ptr, nviews, image_size, flags=0, K=None, dist=None):
+        """calibrate_camera on device arrays (obj float32 [N,3], img float32 [N,2], npoints int32 [nviews], given as pointers)."""
+        Ka, da = self._calib_start(K, dist)
+        rv, tv, pv, rms = np.zeros((nviews, 3)), np.zeros((nviews, 3)), np.zeros(nviews), C.c_double()
+        self._chk(self.L.arucohip_calibrate_camera(self.h, obj_ptr, img_ptr, npoints_ptr, nviews, 1, int(image_size[0]), int(image_size[1]),
+                                                   int(flags), _ptr(Ka), _ptr(da), _ptr(rv), _ptr(tv), _ptr(pv), C.byref(rms)))
+        return {"rms": rms.value, "K": Ka.reshape(3, 3), "dist": da, "rvecs": rv, "tvecs": tv, "per_view_rms": pv}
+
+    def calibrate_board_batch(self, nframes, ids, obj, info_type, image_size, marker_size=-1.0, min_markers=4, flags=0, K=None, dist=None):
+        """calibrate_camera on the board detections of the last detect_batch call, left on the device: frames with at least
+        min_markers board markers are the views. rvecs / tvecs have one row per used frame; used[f] marks them."""
+        ida = np.ascontiguousarray(ids, dtype=np.int32)
+        oa = _f32(obj)
+        Ka, da = self._calib_start(K, dist)
+        used = np.zeros(nframes, np.int32)
+        rv, tv, rms = np.zeros((nframes, 3)), np.zeros((nframes, 3)), C.c_double()
+        self._chk(self.L.arucohip_calibrate_board_batch(self.h, nframes, _ptr(ida), _ptr(oa), len(ida), info_type, float(marker_size),
+                                                        int(min_markers), int(image_size[0]), int(image_size[1]), int(flags), _ptr(Ka),
+                                                        _ptr(da), _ptr(used), _ptr(rv), _ptr(tv), C.byref(rms)))
+        nv = int(used.sum())
+        return {"rms": rms.value, "K": Ka.reshape(3, 3), "dist": da, "rvecs": rv[:nv], "tvecs": tv[:nv], "used": used.astype(bool)}
 
 
 class MultiGpu:

@@ -258,4 +258,38 @@ void launch_marker_pose(hipStream_t s, arucohip_marker_t* markers, int n, const 
 void launch_board_pose(hipStream_t s, int nframes, const Buffers& b, const int32_t* ids, const float* obj, int nboard, int info_type,
                        float marker_size, float repj_thres, const CamModel& cam, arucohip_board_t* out, float* prob);
 
+// Camera calibration (k_calib.hip). Views: points obj (xyz) / img (xy) at off[v], npt[v] points each.
+constexpr int CALIB_MAX_POINTS = 512;   // points of one view (= the board kernels' MAX_BOARD_POINTS)
+constexpr int CALIB_RED = 100;          // doubles per view of the reduced system: S_i (81), diag A_i (9), rhs_i (9), pad
+constexpr int CALIB_BS = 60;            // doubles per view for the back-substitution: u (6), M (6 x 9)
+enum { CALIB_ERR_DEGENERATE = 1, CALIB_ERR_NONPLANAR = 2 };
+
+struct CalibState {
+    double intr[9];    // fx fy cx cy k1 k2 p1 p2 k3
+    double cand[9], delta[9];
+    double aspect;     // fx / fy under ARUCOHIP_CALIB_FIX_ASPECT_RATIO
+    double cost;       // sum of squared residuals at intr / pose[cur]
+    int32_t flags, free_mask, lg, cur, done, iters, max_iter, attempts, err, pad_;
+};
+
+struct CalibDev {
+    const float* obj;
+    const float* img;
+    const int32_t* off;
+    const int32_t* npt;
+    int nviews;
+    double* init;      // [V][6] rows of the focal-length least squares
+    double* red;       // [V][CALIB_RED]
+    double* bs;        // [V][CALIB_BS]
+    double* pose;      // [2][V][6] rvec, tvec (current / candidate, swapped by st->cur)
+    double* vcost;     // [2][V]
+    double* vchg;      // [V][2] |pose step|^2, |pose|^2
+    CalibState* st;
+};
+
+void launch_calib_init(hipStream_t s, const CalibDev& d, bool guess);
+void launch_calib_iteration(hipStream_t s, const CalibDev& d);
+void launch_calib_gather(hipStream_t s, int nframes, const Buffers& b, const int32_t* ids, const float* bobj, int nboard, double mpp,
+                         int first, float* obj, float* img, int32_t* npt, int32_t* nmark);
+
 }  // namespace ah

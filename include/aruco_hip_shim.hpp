@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <cassert>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -235,6 +236,27 @@ public:
         for (size_t i = 0; i < 5 && i < D.size(); i++) Df[i] = (float)D[i];
         setParams(Kf, Df, 5, cv::Size((int)w, (int)h));
     }
+    // cameraparameters.h:79: the OpenCV FileStorage YAML readFromXMLFile reads back (values printed exactly)
+    void saveToFile(const std::string& path, bool /*inXML*/ = true) const {
+        if (!isValid()) arucohip_throw_(ARUCOHIP_E_INVALID, "invalid camera parameters", nullptr);
+        std::ofstream f(path.c_str());
+        if (!f) arucohip_throw_(ARUCOHIP_E_INVALID, ("cannot write " + path).c_str(), nullptr);
+        char num[64];
+        auto block = [&](const char* key, int rows, int cols, const float* v) {
+            f << key << ": !!opencv-matrix\n   rows: " << rows << "\n   cols: " << cols << "\n   dt: d\n   data: [ ";
+            for (int i = 0; i < rows * cols; i++) {
+                std::snprintf(num, sizeof(num), "%.17g", (double)v[i]);
+                f << num << (i + 1 < rows * cols ? ", " : " ]\n");
+            }
+        };
+        float K[9], D[5] = {0, 0, 0, 0, 0};
+        for (int i = 0; i < 9; i++) K[i] = CameraMatrix(i / 3, i % 3);
+        for (int i = 0; i < 5 && i < (int)Distorsion.total(); i++) D[i] = Distorsion(i);
+        f << "%YAML:1.0\n---\nimage_width: " << CamSize.width << "\nimage_height: " << CamSize.height << "\n";
+        block("camera_matrix", 3, 3, K);
+        block("distortion_coefficients", 1, 5, D);
+        if (!f) arucohip_throw_(ARUCOHIP_E_INVALID, ("cannot write " + path).c_str(), nullptr);
+    }
     // cameraparameters.cpp:166-179
     void resize(cv::Size size) {
         if (!isValid()) arucohip_throw_(ARUCOHIP_E_INVALID, "invalid camera parameters", nullptr);
@@ -314,6 +336,53 @@ inline void undistort(const cv::Mat& src, cv::Mat& dst, const cv::Mat& cameraMat
     arucohip_throw_(arucohip_undistort(h, src.data, 1, src.cols, src.rows, src.step, (size_t)src.rows * src.step, cn, 0, K, nd ? d : nullptr, nd, out.data, 0),
                     "undistort", h);
     dst = out;
+}
+
+// cv::calibrateCamera(objectPoints, imagePoints, imageSize, cameraMatrix, distCoeffs, rvecs, tvecs, flags) for planar views
+// (utils/aruco_calibration.cpp's call) on the process-wide handle. flags: cv::CALIB_* values (ARUCOHIP_CALIB_*). Returns the RMS
+// reprojection error; cameraMatrix (3x3), distCoeffs (1x5), rvecs / tvecs (3x1 each) come back as CV_64F.
+inline double calibrateCamera(const std::vector<std::vector<cv::Point3f> >& objPointsV, const std::vector<std::vector<cv::Point2f> >& imgPointsV,
+                              cv::Size imageSize, cv::Mat& cameraMatrix, cv::Mat& distCoeffs, std::vector<cv::Mat>& rvecs,
+                              std::vector<cv::Mat>& tvecs, int flags = 0) {
+    if (objPointsV.size() != imgPointsV.size()) arucohip_throw_(ARUCOHIP_E_INVALID, "calibrateCamera: object and image point lists differ", nullptr);
+    const int nv = (int)objPointsV.size();
+    std::vector<float> obj, img;
+    std::vector<int32_t> np;
+    for (int v = 0; v < nv; v++) {
+        if (objPointsV[v].size() != imgPointsV[v].size()) arucohip_throw_(ARUCOHIP_E_INVALID, "calibrateCamera: a view's point counts differ", nullptr);
+        np.push_back((int32_t)objPointsV[v].size());
+        for (const cv::Point3f& p : objPointsV[v]) obj.push_back(p.x), obj.push_back(p.y), obj.push_back(p.z);
+        for (const cv::Point2f& p : imgPointsV[v]) img.push_back(p.x), img.push_back(p.y);
+    }
+    double K[9] = {0, 0, 0, 0, 0, 0, 0, 0, 1}, d[5] = {0, 0, 0, 0, 0};
+    if (!cameraMatrix.empty() && cameraMatrix.rows == 3 && cameraMatrix.cols == 3)
+        for (int i = 0; i < 9; i++)
+            K[i] = cameraMatrix.type() == CV_64FC1 ? cameraMatrix.at<double>(i / 3, i % 3) : cameraMatrix.at<float>(i / 3, i % 3);
+    for (int i = 0; i < 5 && !distCoeffs.empty() && i < (int)distCoeffs.total(); i++) {
+        const int r = distCoeffs.cols == 1 ? i : 0, c = distCoeffs.cols == 1 ? 0 : i;
+        d[i] = distCoeffs.type() == CV_64FC1 ? distCoeffs.at<double>(r, c) : distCoeffs.at<float>(r, c);
+    }
+    std::vector<double> rv((size_t)nv * 3), tv((size_t)nv * 3);
+    double rms = 0;
+    {
+        SharedHandle_& sh = SharedHandle_::get();
+        std::lock_guard<std::mutex> lock(sh.mu);
+        arucohip_handle* h = sh.ensure();
+        arucohip_throw_(arucohip_calibrate_camera(h, obj.data(), img.data(), np.data(), nv, 0, imageSize.width, imageSize.height, flags, K, d,
+                                                  rv.data(), tv.data(), nullptr, &rms),
+                        "calibrateCamera", h);
+    }
+    cameraMatrix = cv::Mat(3, 3, CV_64FC1);
+    for (int i = 0; i < 9; i++) cameraMatrix.at<double>(i / 3, i % 3) = K[i];
+    distCoeffs = cv::Mat(1, 5, CV_64FC1);
+    for (int i = 0; i < 5; i++) distCoeffs.at<double>(0, i) = d[i];
+    rvecs.clear(), tvecs.clear();
+    for (int v = 0; v < nv; v++) {
+        cv::Mat r(3, 1, CV_64FC1), t(3, 1, CV_64FC1);
+        for (int k = 0; k < 3; k++) r.at<double>(k, 0) = rv[3 * v + k], t.at<double>(k, 0) = tv[3 * v + k];
+        rvecs.push_back(r), tvecs.push_back(t);
+    }
+    return rms;
 }
 
 class Marker : public std::vector<cv::Point2f> {
@@ -954,5 +1023,11 @@ private:
 namespace cv {
 // the reference's apps spell it cv::undistort; without OpenCV the name resolves to the device implementation
 inline void undistort(const Mat& src, Mat& dst, const Mat& cameraMatrix, const Mat& distCoeffs) { aruco::undistort(src, dst, cameraMatrix, distCoeffs); }
+enum { CALIB_USE_INTRINSIC_GUESS = 1, CALIB_FIX_ASPECT_RATIO = 2, CALIB_FIX_PRINCIPAL_POINT = 4, CALIB_ZERO_TANGENT_DIST = 8,
+       CALIB_FIX_FOCAL_LENGTH = 16, CALIB_FIX_K1 = 32, CALIB_FIX_K2 = 64, CALIB_FIX_K3 = 128 };
+inline double calibrateCamera(const std::vector<std::vector<Point3f> >& objPointsV, const std::vector<std::vector<Point2f> >& imgPointsV, Size imageSize,
+                              Mat& cameraMatrix, Mat& distCoeffs, std::vector<Mat>& rvecs, std::vector<Mat>& tvecs, int flags = 0) {
+    return aruco::calibrateCamera(objPointsV, imgPointsV, imageSize, cameraMatrix, distCoeffs, rvecs, tvecs, flags);
+}
 }  // namespace cv
 #endif

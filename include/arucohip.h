@@ -288,6 +288,34 @@ int arucohip_board_detect_batch(arucohip_handle* h, int nframes, const int32_t* 
                                 const float* K, const float* dist, int ndist, float marker_size, float repj_err_thres,
                                 int y_perpendicular, arucohip_board_t* out, float* prob);
 
+/* cv::calibrateCamera for planar targets (pinhole model, dist = k1 k2 p1 p2 k3), solved on the device in double precision: start
+ * values as OpenCV's (homography per view, focal lengths from the vanishing points, principal point at the image centre, distortion
+ * 0, planar solvePnP per view), then Levenberg-Marquardt over the intrinsics and every view's pose with the poses eliminated
+ * per view (Schur complement); 30 iterations or a relative step below DBL_EPSILON. Views are reduced in view order: the result
+ * is bit-reproducible. flags: the values of cv::CALIB_*. */
+#define ARUCOHIP_CALIB_USE_INTRINSIC_GUESS 1   /* start from K and dist (else K only gives the FIX_ASPECT_RATIO ratio) */
+#define ARUCOHIP_CALIB_FIX_ASPECT_RATIO 2      /* fx / fy stays at the ratio of the given K (1 when K holds no focal lengths) */
+#define ARUCOHIP_CALIB_FIX_PRINCIPAL_POINT 4
+#define ARUCOHIP_CALIB_ZERO_TANGENT_DIST 8     /* p1 = p2 = 0 */
+#define ARUCOHIP_CALIB_FIX_FOCAL_LENGTH 16
+#define ARUCOHIP_CALIB_FIX_K1 32
+#define ARUCOHIP_CALIB_FIX_K2 64
+#define ARUCOHIP_CALIB_FIX_K3 128
+#define ARUCOHIP_CALIB_MAX_VIEW_POINTS 512     /* points of one view */
+/* obj: 3 floats per point, img: 2 floats per point, view after view (npoints[v] points each); on_device: obj, img and npoints are
+ * device pointers. Every view's obj must have one constant z (ARUCOHIP_E_UNSUPPORTED otherwise). K (row-major 3x3) and dist are
+ * in/out; rvecs / tvecs (3 doubles per view), per_view_rms (1 per view) may be NULL; *rms = sqrt(sum |r|^2 / sum npoints). */
+int arucohip_calibrate_camera(arucohip_handle* h, const float* obj, const float* img, const int32_t* npoints, int nviews, int on_device,
+                              int width, int height, int flags, double K[9], double dist[5], double* rvecs, double* tvecs,
+                              double* per_view_rms, double* rms);
+/* The same on the board detections of the LAST arucohip_detect_batch call, where they are (device-resident, every chunk): a frame
+ * is a view when it holds >= min_markers markers of the board (ids / obj / info_type / marker_size as arucohip_board_detect_batch;
+ * PIX boards are scaled to metres when marker_size > 0). used[f] (nframes entries, may be NULL) = 1 for the frames taken; rvecs /
+ * tvecs (may be NULL) hold 3 doubles per used frame, in frame order. ARUCOHIP_E_INVALID when no frame qualifies. */
+int arucohip_calibrate_board_batch(arucohip_handle* h, int nframes, const int32_t* ids, const float* obj, int nboard, int info_type,
+                                   float marker_size, int min_markers, int width, int height, int flags, double K[9], double dist[5],
+                                   int32_t* used, double* rvecs, double* tvecs, double* rms);
+
 /* Marker::calculateExtrinsics (marker.h:98-104 / marker.cpp:112-124) for n markers at once (batched solvePnP). */
 int arucohip_calculate_extrinsics(arucohip_handle* h, arucohip_marker_t* markers, int n, const float* K, const float* dist,
                                   int ndist, float marker_size, int y_perpendicular);
