@@ -80,6 +80,11 @@ SYMBOLS = [
     "arucohip_compact_bytes", "arucohip_compact_markers", "arucohip_wait_event", "arucohip_detect_batch_retry_overflowed",
     "arucohip_refine_candidate_lines", "arucohip_mgpu_gather_mode", "arucohip_build_info",
     "arucohip_calibrate_camera", "arucohip_calibrate_board_batch",
+    "arucohip_chromatic_board_corners", "arucohip_chromatic_create", "arucohip_chromatic_destroy", "arucohip_chromatic_train",
+    "arucohip_chromatic_classify", "arucohip_chromatic_update", "arucohip_chromatic_get_mask", "arucohip_chromatic_get_cell_map",
+    "arucohip_chromatic_is_valid", "arucohip_chromatic_get_model", "arucohip_chromatic_set_model", "arucohip_em_fit",
+    "arucohip_chromatic_debug_geometry", "arucohip_chromatic_debug_hist", "arucohip_chromatic_classify_batch", "arucohip_chromatic_grid",
+    "arucohip_chromatic_reset_mask",
 ]
 
 _lib = None
@@ -142,6 +147,24 @@ def load():
     L.arucohip_board_detect_batch.argtypes = [vp, i, vp, vp, i, i, vp, vp, i, f, f, i, vp, vp]
     L.arucohip_calibrate_camera.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp]
     L.arucohip_calibrate_board_batch.argtypes = [vp, i, vp, vp, i, i, f, i, i, i, i, vp, vp, vp, vp, vp, vp]
+    d = C.c_double
+    L.arucohip_chromatic_board_corners.argtypes = [vp, i, i, f, vp]
+    L.arucohip_chromatic_create.argtypes = [vp, i, i, d, vp, vp, i, i, i, vp, vp]
+    L.arucohip_chromatic_destroy.argtypes = [vp]
+    L.arucohip_chromatic_train.argtypes = [vp, vp, i, sz, vp, vp]
+    L.arucohip_chromatic_classify.argtypes = [vp, vp, i, sz, vp, vp, i]
+    L.arucohip_chromatic_update.argtypes = [vp, vp, i, sz]
+    L.arucohip_chromatic_grid.argtypes = [vp, vp, vp]
+    L.arucohip_chromatic_reset_mask.argtypes = [vp]
+    L.arucohip_chromatic_get_mask.argtypes = [vp, vp, i]
+    L.arucohip_chromatic_get_cell_map.argtypes = [vp, vp, i]
+    L.arucohip_chromatic_is_valid.argtypes = [vp]
+    L.arucohip_chromatic_get_model.argtypes = [vp, vp, vp]
+    L.arucohip_chromatic_set_model.argtypes = [vp, vp, vp]
+    L.arucohip_em_fit.argtypes = [vp, vp, d, vp, vp, vp]
+    L.arucohip_chromatic_debug_geometry.argtypes = [vp, i, vp, vp, vp]
+    L.arucohip_chromatic_debug_hist.argtypes = [vp, vp, vp, vp]
+    L.arucohip_chromatic_classify_batch.argtypes = [vp, vp, vp, i, i, i, sz, sz, i, i, f, vp, i, vp]
     L.arucohip_detect_bgr.argtypes = [vp, vp, i, i, sz, vp, vp, i, f, i, vp, i, vp]
     L.arucohip_detect_batch_bgr.argtypes = [vp, vp, i, i, i, sz, sz, i, vp, vp, i, f, i, vp, i, vp, i]
     L.arucohip_bgr_to_gray.argtypes = [vp, vp, i, i, sz, vp]
@@ -622,6 +645,157 @@ class Handle:
                                                         _ptr(da), _ptr(used), _ptr(rv), _ptr(tv), C.byref(rms)))
         nv = int(used.sum())
         return {"rms": rms.value, "K": Ka.reshape(3, 3), "dist": da, "rvecs": rv[:nv], "tvecs": tv[:nv], "used": used.astype(bool)}
+
+    def chromatic(self, mc, nc, thresh_prob, K, dist, width, height, corners):
+        """ChromaticMask::setParams(mc, nc, threshProb, CP, BC, corners) on this handle's device and stream: see Chromatic."""
+        return Chromatic(self, mc, nc, thresh_prob, K, dist, width, height, corners)
+
+    def em_fit(self, samples_hist, thresh_prob, prob=None):
+        """EMClassifier::train on one cell's raw-sample histogram (256 counts): (prob[256], inside[256], trained). prob starts at 0.5
+        (a fresh classifier) unless given; it is returned unchanged when fewer than 10 discretised samples remain."""
+        hist = np.ascontiguousarray(samples_hist, dtype=np.uint32).reshape(256)
+        p = np.full(256, 0.5) if prob is None else np.array(prob, dtype=np.float64).reshape(256)
+        inside = (p > thresh_prob).astype(np.uint8)
+        t = C.c_int()
+        self._chk(self.L.arucohip_em_fit(self.h, _ptr(hist), float(thresh_prob), _ptr(p), _ptr(inside), C.byref(t)))
+        return p, inside.astype(bool), bool(t.value)
+
+
+def chromatic_board_corners(obj, info_type, marker_size=-1.0):
+    """ChromaticMask::setParams(.., BC, markersize)'s board corners (4 x 3 float32) from obj[N][4][3]."""
+    oa = _f32(obj)
+    out = np.zeros(12, np.float32)
+    rc = load().arucohip_chromatic_board_corners(_ptr(oa), oa.size // 12, int(info_type), float(marker_size), _ptr(out))
+    if rc != OK:
+        raise ArucoHipError(rc, "arucohip_chromatic_board_corners")
+    return out.reshape(4, 3)
+
+
+class Chromatic:
+    """arucohip_chromatic: the reference's ChromaticMask (board occlusion mask) on the device. Planes are uint8 numpy arrays of the
+    create-time size, or device pointers (the *_device forms); poses are rvec / tvec in the corners' units."""
+
+    def __init__(self, handle, mc, nc, thresh_prob, K, dist, width, height, corners):
+        self.handle, self.L = handle, handle.L
+        self.mc, self.nc, self.width, self.height, self.thresh = mc, nc, width, height, thresh_prob
+        self.m = C.c_void_p()
+        Ka = _f32(np.asarray(K).reshape(9))
+        da = None if dist is None else _f32(np.asarray(dist).reshape(-1))
+        ca = _f32(np.asarray(corners).reshape(12))
+        handle._chk(self.L.arucohip_chromatic_create(handle.h, mc, nc, float(thresh_prob), _ptr(Ka), _ptr(da), 0 if da is None else da.size,
+                                                     width, height, _ptr(ca), C.byref(self.m)))
+
+    def close(self):
+        if self.m:
+            self.L.arucohip_chromatic_destroy(self.m)
+            self.m = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc):
+        return self.handle._chk(rc)
+
+    def _plane(self, img):
+        a = np.ascontiguousarray(img, dtype=np.uint8)
+        if a.shape != (self.height, self.width):
+            raise ValueError("plane must be %dx%d" % (self.height, self.width))
+        return a
+
+    @staticmethod
+    def _pose(rvec, tvec):
+        return np.array(rvec, np.float64).reshape(3), np.array(tvec, np.float64).reshape(3)
+
+    def train(self, img, rvec, tvec):
+        a, (r, t) = self._plane(img), self._pose(rvec, tvec)
+        self._chk(self.L.arucohip_chromatic_train(self.m, _ptr(a), 0, self.width, _ptr(r), _ptr(t)))
+
+    def classify(self, img, rvec, tvec, method=2):
+        """method 1: classify, 2: classify2. Returns the mask (0 / 1)."""
+        a, (r, t) = self._plane(img), self._pose(rvec, tvec)
+        self._chk(self.L.arucohip_chromatic_classify(self.m, _ptr(a), 0, self.width, _ptr(r), _ptr(t), int(method)))
+        return self.mask()
+
+    def calculate_grid_image(self, rvec, tvec):
+        r, t = self._pose(rvec, tvec)
+        self._chk(self.L.arucohip_chromatic_grid(self.m, _ptr(r), _ptr(t)))
+
+    def reset_mask(self):
+        self._chk(self.L.arucohip_chromatic_reset_mask(self.m))
+
+    def update(self, img):
+        a = self._plane(img)
+        self._chk(self.L.arucohip_chromatic_update(self.m, _ptr(a), 0, self.width))
+
+    def train_device(self, ptr, row_stride, rvec, tvec):
+        r, t = self._pose(rvec, tvec)
+        self._chk(self.L.arucohip_chromatic_train(self.m, ptr, 1, row_stride, _ptr(r), _ptr(t)))
+
+    def classify_device(self, ptr, row_stride, rvec, tvec, method=2):
+        r, t = self._pose(rvec, tvec)
+        self._chk(self.L.arucohip_chromatic_classify(self.m, ptr, 1, row_stride, _ptr(r), _ptr(t), int(method)))
+
+    def update_device(self, ptr, row_stride):
+        self._chk(self.L.arucohip_chromatic_update(self.m, ptr, 1, row_stride))
+
+    def mask(self):
+        out = np.zeros((self.height, self.width), np.uint8)
+        self._chk(self.L.arucohip_chromatic_get_mask(self.m, _ptr(out), 0))
+        return out
+
+    def cell_map(self):
+        out = np.zeros((self.height, self.width), np.uint8)
+        self._chk(self.L.arucohip_chromatic_get_cell_map(self.m, _ptr(out), 0))
+        return out
+
+    def is_valid(self):
+        return bool(self.L.arucohip_chromatic_is_valid(self.m))
+
+    def get_model(self):
+        """(prob[mc*nc][256] float64, trained[mc*nc] bool)"""
+        n = self.mc * self.nc
+        p, t = np.zeros((n, 256)), np.zeros(n, np.int32)
+        self._chk(self.L.arucohip_chromatic_get_model(self.m, _ptr(p), _ptr(t)))
+        return p, t.astype(bool)
+
+    def set_model(self, prob, trained):
+        p = np.ascontiguousarray(prob, dtype=np.float64).reshape(self.mc * self.nc, 256)
+        t = np.ascontiguousarray(trained, dtype=np.int32).reshape(self.mc * self.nc)
+        self._chk(self.L.arucohip_chromatic_set_model(self.m, _ptr(p), _ptr(t)))
+
+    def debug_geometry(self, frame=-1):
+        """(corners2d[4][2] float32, H_train[3][3], H_classify[3][3]) of the last single-frame call (frame < 0) or a batch frame"""
+        c, ht, hc = np.zeros(8, np.float32), np.zeros(9), np.zeros(9)
+        self._chk(self.L.arucohip_chromatic_debug_geometry(self.m, int(frame), _ptr(c), _ptr(ht), _ptr(hc)))
+        return c.reshape(4, 2), ht.reshape(3, 3), hc.reshape(3, 3)
+
+    def debug_hist(self):
+        """(raw[mc*nc][256], hist_count[mc*nc][256], fitted[mc*nc]) of the last train / update"""
+        n = self.mc * self.nc
+        raw, hc, fit = np.zeros((n, 256), np.uint32), np.zeros((n, 256), np.uint32), np.zeros(n, np.int32)
+        self._chk(self.L.arucohip_chromatic_debug_hist(self.m, _ptr(raw), _ptr(hc), _ptr(fit)))
+        return raw, hc, fit
+
+    def classify_batch(self, handle, frames, method=2, min_prob=0.0, npix=True):
+        """classify every frame of handle's last detect_batch at its last board_detect_batch poses: frames uint8 [N, H, W] on the host.
+        Returns (masks [N, H, W], npix [N] or None)."""
+        fa = np.ascontiguousarray(frames, dtype=np.uint8)
+        if fa.ndim != 3 or fa.shape[1:] != (self.height, self.width):
+            raise ValueError("frames must be [N, %d, %d]" % (self.height, self.width))
+        n = fa.shape[0]
+        masks = np.zeros((n, self.height, self.width), np.uint8)
+        cnt = np.zeros(n, np.int32) if npix else None
+        self._chk(self.L.arucohip_chromatic_classify_batch(self.m, handle.h, _ptr(fa), n, self.width, self.height, self.width,
+                                                           self.width * self.height, 0, int(method), float(min_prob), _ptr(masks), 0, _ptr(cnt)))
+        return masks, cnt
+
+    def classify_batch_device(self, handle, frames_ptr, nframes, row_stride, frame_stride, masks_ptr, method=2, min_prob=0.0, npix=None):
+        """device frames and masks (pointers); npix: a host int32 array of nframes, or None"""
+        self._chk(self.L.arucohip_chromatic_classify_batch(self.m, handle.h, frames_ptr, nframes, self.width, self.height, row_stride, frame_stride,
+                                                           1, int(method), float(min_prob), masks_ptr, 1, _ptr(npix)))
 
 
 class MultiGpu:

@@ -10,6 +10,74 @@
 
 namespace ah {
 
+// 8x8 dense solve, partial pivoting, on LDS arrays (lane 0).
+__device__ inline bool solve8(double* A, double* b) {
+    const int n = 8;
+    for (int c = 0; c < n; c++) {
+        int piv = c;
+        double best = fabs(A[c * n + c]);
+        for (int r = c + 1; r < n; r++) {
+            double v = fabs(A[r * n + c]);
+            if (v > best) best = v, piv = r;
+        }
+        if (best == 0) return false;
+        if (piv != c) {
+            for (int k = 0; k < n; k++) {
+                double t = A[c * n + k];
+                A[c * n + k] = A[piv * n + k];
+                A[piv * n + k] = t;
+            }
+            double t = b[c];
+            b[c] = b[piv];
+            b[piv] = t;
+        }
+        double inv = 1.0 / A[c * n + c];
+        for (int r = c + 1; r < n; r++) {
+            double f = A[r * n + c] * inv;
+            if (f == 0) continue;
+            for (int k = c; k < n; k++) A[r * n + k] -= f * A[c * n + k];
+            b[r] -= f * b[c];
+        }
+    }
+    for (int r = n - 1; r >= 0; r--) {
+        double s = b[r];
+        for (int k = r + 1; k < n; k++) s -= A[r * n + k] * b[k];
+        b[r] = s / A[r * n + r];
+    }
+    return true;
+}
+
+// cv::getPerspectiveTransform(src -> dst) (one lane, A / b: 64 + 8 doubles of scratch, LDS or private): the 8 coefficients are
+// left in b, M[8] = 1 is the caller's. OpenCV forms the products src * dst in float, from its Point2f corners: float_products = true
+// restates that; the decode stage forms them in double (identical for its integer corners, and what arucohip_warp has always computed
+// for a caller's sub-pixel quad). A singular system gives 0, as cv::solve leaves its result.
+__device__ inline void perspective_transform_solve(const float* src, const float* dst, double* A, double* b, bool float_products = false) {
+    for (int i = 0; i < 64; i++) A[i] = 0;
+    for (int i = 0; i < 4; i++) {
+        const float sx = src[2 * i], sy = src[2 * i + 1], dx = dst[2 * i], dy = dst[2 * i + 1];
+        double* r0 = A + i * 8;
+        double* r1 = A + (i + 4) * 8;
+        r0[0] = r1[3] = sx;
+        r0[1] = r1[4] = sy;
+        r0[2] = r1[5] = 1;
+        if (float_products) {
+            r0[6] = -sx * dx;
+            r0[7] = -sy * dx;
+            r1[6] = -sx * dy;
+            r1[7] = -sy * dy;
+        } else {
+            r0[6] = -(double)sx * dx;
+            r0[7] = -(double)sy * dx;
+            r1[6] = -(double)sx * dy;
+            r1[7] = -(double)sy * dy;
+        }
+        b[i] = dx;
+        b[i + 4] = dy;
+    }
+    if (!solve8(A, b))
+        for (int i = 0; i < 8; i++) b[i] = 0;
+}
+
 // The 8x8 systems of HOMOGRAPHY_GROUP lanes at a time live in LDS, element-major: element k of a lane's matrix at k * GROUP + (lane % GROUP), so the lanes
 // of a group never collide on a bank. A wave solves its 64 candidates group after group (round 3: all 64 at once took 37 KB, and with the batches in
 // flight a workgroup that wants a quarter of a CU's LDS waits for it: 0.61 ms in the stream against 0.07 alone).

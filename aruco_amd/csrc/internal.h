@@ -292,4 +292,42 @@ void launch_calib_iteration(hipStream_t s, const CalibDev& d);
 void launch_calib_gather(hipStream_t s, int nframes, const Buffers& b, const int32_t* ids, const float* bobj, int nboard, double mpp,
                          int first, float* obj, float* img, int32_t* npt, int32_t* nmark);
 
+// Board occlusion mask (k_chromatic.hip): ChromaticMask of the reference, src/chromaticmask.cpp.
+constexpr int CHROMA_CELL = 20;       // ChromaticMask::_cellSize
+constexpr int CHROMA_MIN_FIT = 10;    // EMClassifier::train fits only when the discretised histogram holds >= 10 samples
+constexpr int CHROMA_UPDATE_MIN = 50; // update() retrains the cells with more than 50 raw samples
+
+struct ChromaCam {
+    float K[9];
+    double k[8];           // k1 k2 p1 p2 k3 (zero padded)
+    float corners3d[12];   // the board corners of setParams
+    int mc, nc, W, H;
+};
+
+// The geometry of one frame (calculateGridImage / classify2), written by chroma_geometry_kernel.
+struct ChromaGeom {
+    float corners[8];           // projected board corners (projectPoints, float as _imgCornerPoints)
+    double Ht[9];               // corners -> (0,0) (20mc-1,0) (20mc-1,20nc-1) (0,20nc-1): calculateGridImage
+    double Hc[9];               // corners -> (0,0) (mc-1,0) (mc-1,nc-1) (0,nc-1): classify2, used as float
+    int32_t rx0, ry0, rx1, ry1; // classify2's rectangle after fitRectToSize: [rx0, rx1) x [ry0, ry1) (empty when rx1 <= rx0)
+    int32_t valid;              // the frame has a pose (and, in a batch, prob > min_prob)
+    int32_t pad_;
+};
+
+// boards == nullptr: one frame at the pose rvec / tvec; else frame f takes boards[f] (and prob[f] > min_prob when prob != nullptr)
+void launch_chroma_geometry(hipStream_t s, const ChromaCam& c, int nframes, const arucohip_board_t* boards, const float* prob, float min_prob,
+                            const double* rvec, const double* tvec, ChromaGeom* out);
+void launch_chroma_grid(hipStream_t s, const ChromaCam& c, const ChromaGeom* g, uint8_t* cellmap);
+// raw[cell][256] += samples of the pixels whose cell-map value (times mask, when given) is not 0; raw must be zeroed by the caller
+void launch_chroma_hist(hipStream_t s, int W, int H, const uint8_t* in, size_t row_stride, const uint8_t* cellmap, const uint8_t* mask,
+                        uint32_t* raw);
+// EMClassifier::train of every cell from its raw-sample histogram; cells with min_raw > 0 and at most min_raw samples are skipped.
+// hcount[cell][256]: the discretised histogram; fitted[cell]: 1 fitted, 0 fewer than 10 samples (model kept), -1 skipped.
+void launch_chroma_em(hipStream_t s, int ncell, const uint32_t* raw, uint32_t min_raw, double thresh, uint32_t* hcount, int32_t* fitted,
+                      double* prob, uint8_t* inside, int32_t* trained);
+// classify (method 1) / classify2 (method 2) of nframes frames at geom[f], 3x3 close fused; masks W x H per frame (frame after frame);
+// npix[f] += the 1 pixels of frame f (zeroed by the caller) when not null
+void launch_chroma_classify(hipStream_t s, const ChromaCam& c, int method, double thresh, int nframes, const uint8_t* frames, size_t row_stride,
+                            size_t frame_stride, const ChromaGeom* geom, const double* prob, const uint8_t* inside, uint8_t* masks, int32_t* npix);
+
 }  // namespace ah

@@ -16,64 +16,11 @@
 
 namespace ah {
 
-// 8x8 dense solve, partial pivoting, on LDS arrays (lane 0).
-__device__ static bool solve8(double* A, double* b) {
-    const int n = 8;
-    for (int c = 0; c < n; c++) {
-        int piv = c;
-        double best = fabs(A[c * n + c]);
-        for (int r = c + 1; r < n; r++) {
-            double v = fabs(A[r * n + c]);
-            if (v > best) best = v, piv = r;
-        }
-        if (best == 0) return false;
-        if (piv != c) {
-            for (int k = 0; k < n; k++) {
-                double t = A[c * n + k];
-                A[c * n + k] = A[piv * n + k];
-                A[piv * n + k] = t;
-            }
-            double t = b[c];
-            b[c] = b[piv];
-            b[piv] = t;
-        }
-        double inv = 1.0 / A[c * n + c];
-        for (int r = c + 1; r < n; r++) {
-            double f = A[r * n + c] * inv;
-            if (f == 0) continue;
-            for (int k = c; k < n; k++) A[r * n + k] -= f * A[c * n + k];
-            b[r] -= f * b[c];
-        }
-    }
-    for (int r = n - 1; r >= 0; r--) {
-        double s = b[r];
-        for (int k = r + 1; k < n; k++) s -= A[r * n + k] * b[k];
-        b[r] = s / A[r * n + r];
-    }
-    return true;
-}
-
 // inverse map of cv::getPerspectiveTransform(quad -> (0,0),(s-1,0),(s-1,s-1),(0,s-1)) into iM (lane 0, LDS scratch)
 __device__ static void inverse_homography(const float* quad, int size, double* A, double* b, double* iM) {
-    const double d = (double)(float)(size - 1);
-    const double dxs[4] = {0, d, d, 0}, dys[4] = {0, 0, d, d};
-    for (int i = 0; i < 64; i++) A[i] = 0;
-    for (int i = 0; i < 4; i++) {
-        double sx = quad[2 * i], sy = quad[2 * i + 1], dx = dxs[i], dy = dys[i];
-        double* r0 = A + i * 8;
-        double* r1 = A + (i + 4) * 8;
-        r0[0] = r1[3] = sx;
-        r0[1] = r1[4] = sy;
-        r0[2] = r1[5] = 1;
-        r0[6] = -sx * dx;
-        r0[7] = -sy * dx;
-        r1[6] = -sx * dy;
-        r1[7] = -sy * dy;
-        b[i] = dx;
-        b[i + 4] = dy;
-    }
-    if (!solve8(A, b))
-        for (int i = 0; i < 8; i++) b[i] = 0;
+    const float d = (float)(size - 1);
+    const float dst[8] = {0, 0, d, 0, d, d, 0, d};
+    perspective_transform_solve(quad, dst, A, b);
     double m[9];
     for (int i = 0; i < 8; i++) m[i] = b[i];
     m[8] = 1.0;

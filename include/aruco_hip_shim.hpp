@@ -1031,3 +1031,141 @@ inline double calibrateCamera(const std::vector<std::vector<Point3f> >& objPoint
 }
 }  // namespace cv
 #endif
+
+// ---- ChromaticMask / EMClassifier (src/chromaticmask.h:38-114) at global scope, as the reference declares them. The fit runs on the
+// device (arucohip_em_fit / arucohip_chromatic_*); a ChromaticMask owns a small handle of its own for its device and stream.
+class EMClassifier {
+public:
+    // the device fit discretises to the reference's default of 200 samples; another nelements is not supported
+    EMClassifier(unsigned int nelements = 200) : _threshProb(0.0001) {
+        if (nelements != 200) aruco::arucohip_throw_(ARUCOHIP_E_UNSUPPORTED, "EMClassifier: nelements other than 200", nullptr);
+        for (int i = 0; i < 256; i++) _prob[i] = 0.5, _inside[i] = 0.5 > _threshProb;
+    }
+    void addSample(unsigned char s) { _samples.push_back(s); }
+    void clearSamples() { _samples.clear(); }
+    void train() {
+        uint32_t hist[256] = {0};
+        for (unsigned char s : _samples) hist[s]++;
+        uint8_t inside[256];
+        for (int i = 0; i < 256; i++) inside[i] = _inside[i];
+        int trained = 0;
+        aruco::SharedHandle_& sh = aruco::SharedHandle_::get();
+        std::lock_guard<std::mutex> lock(sh.mu);
+        arucohip_handle* h = sh.ensure();
+        aruco::arucohip_throw_(arucohip_em_fit(h, hist, _threshProb, _prob, inside, &trained), "EMClassifier::train", h);
+        for (int i = 0; i < 256; i++) _inside[i] = inside[i] != 0;
+    }
+    bool classify(unsigned char s) { return _inside[s]; }
+    double getProb(unsigned char s) { return _prob[s]; }
+    unsigned int numsamples() { return (unsigned int)_samples.size(); }
+    void setProb(double p) { _threshProb = p; }
+
+private:
+    std::vector<unsigned char> _samples;
+    bool _inside[256];
+    double _prob[256];
+    double _threshProb;
+};
+
+class ChromaticMask {
+public:
+    ChromaticMask() : _isValid(false) {}
+
+    void setParams(unsigned int mc, unsigned int nc, double threshProb, aruco::CameraParameters CP, aruco::BoardConfiguration /*BC*/,
+                   std::vector<cv::Point3f> corners) {
+        if (corners.size() != 4) aruco::arucohip_throw_(ARUCOHIP_E_INVALID, "ChromaticMask::setParams: 4 corners", nullptr);
+        float K[9], d[8], c[12];
+        if (!aruco::mat_to_K_(CP.CameraMatrix, K)) aruco::arucohip_throw_(ARUCOHIP_E_INVALID, "ChromaticMask::setParams: camera matrix is empty", nullptr);
+        const int nd = aruco::mat_to_dist_(CP.Distorsion, d);
+        for (int i = 0; i < 4; i++) c[3 * i] = corners[i].x, c[3 * i + 1] = corners[i].y, c[3 * i + 2] = corners[i].z;
+        std::shared_ptr<State> st(new State());
+        const char* e = std::getenv("ARUCOHIP_DEVICE");
+        aruco::arucohip_throw_(arucohip_create(nullptr, e ? std::atoi(e) : 0, 32, 32, 1, &st->h), "arucohip_create", nullptr);
+        aruco::arucohip_throw_(arucohip_chromatic_create(st->h, (int)mc, (int)nc, threshProb, K, nd ? d : nullptr, nd, CP.CamSize.width,
+                                                         CP.CamSize.height, c, &st->m),
+                               "ChromaticMask::setParams", st->h);
+        _st = st, _size = CP.CamSize, _isValid = false;
+    }
+    void setParams(unsigned int mc, unsigned int nc, double threshProb, aruco::CameraParameters CP, aruco::BoardConfiguration BC,
+                   float markersize = -1.) {
+        if (BC.mInfoType != aruco::BoardConfiguration::METERS && markersize == -1) {
+            std::fprintf(stderr, "Invalid markersize in ChromaticMask::setParams\n");
+            return;
+        }
+        if (BC.objPoints.size() == 0) {
+            std::fprintf(stderr, "Invalid BoardConfiguration size in ChromaticMask::setParams\n");
+            return;
+        }
+        std::vector<float> obj;
+        for (const std::vector<cv::Point3f>& m : BC.objPoints)
+            for (int j = 0; j < 4; j++) obj.push_back(m[j].x), obj.push_back(m[j].y), obj.push_back(m[j].z);
+        float c[12];
+        aruco::arucohip_throw_(arucohip_chromatic_board_corners(obj.data(), (int)BC.objPoints.size(), BC.mInfoType, markersize, c),
+                               "ChromaticMask::setParams", nullptr);
+        std::vector<cv::Point3f> corners;
+        for (int i = 0; i < 4; i++) corners.push_back(cv::Point3f(c[3 * i], c[3 * i + 1], c[3 * i + 2]));
+        setParams(mc, nc, threshProb, CP, BC, corners);
+    }
+
+    void calculateGridImage(const aruco::Board& board) {
+        double r[3], t[3];
+        pose_(board, r, t);
+        aruco::arucohip_throw_(arucohip_chromatic_grid(st_(), r, t), "ChromaticMask::calculateGridImage", _st->h);
+    }
+    cv::Mat getCellMap() { return fetch_(arucohip_chromatic_get_cell_map); }
+    cv::Mat getMask() { return fetch_(arucohip_chromatic_get_mask); }
+
+    void train(const cv::Mat& in, const aruco::Board& board) {
+        double r[3], t[3];
+        pose_(board, r, t);
+        check_(in);
+        aruco::arucohip_throw_(arucohip_chromatic_train(st_(), in.data, 0, (size_t)in.step, r, t), "ChromaticMask::train", _st->h);
+        _isValid = true;
+    }
+    void classify(const cv::Mat& in, const aruco::Board& board) { classify_(in, board, 1); }
+    void classify2(const cv::Mat& in, const aruco::Board& board) { classify_(in, board, 2); }
+    void update(const cv::Mat& in) {
+        check_(in);
+        aruco::arucohip_throw_(arucohip_chromatic_update(st_(), in.data, 0, (size_t)in.step), "ChromaticMask::update", _st->h);
+    }
+
+    bool isValid() { return _isValid; }
+    void resetMask() { aruco::arucohip_throw_(arucohip_chromatic_reset_mask(st_()), "ChromaticMask::resetMask", _st->h); }
+
+private:
+    struct State {
+        arucohip_handle* h = nullptr;
+        arucohip_chromatic* m = nullptr;
+        ~State() {
+            arucohip_chromatic_destroy(m);
+            arucohip_destroy(h);
+        }
+    };
+    std::shared_ptr<State> _st;
+    cv::Size _size;
+    bool _isValid;
+
+    arucohip_chromatic* st_() {
+        if (!_st) aruco::arucohip_throw_(ARUCOHIP_E_INVALID, "ChromaticMask: setParams has not been called", nullptr);
+        return _st->m;
+    }
+    static void pose_(const aruco::Board& b, double r[3], double t[3]) {
+        if (b.Rvec.empty() || b.Tvec.empty()) aruco::arucohip_throw_(ARUCOHIP_E_INVALID, "ChromaticMask: the board has no pose", nullptr);
+        for (int k = 0; k < 3; k++) r[k] = b.Rvec(k), t[k] = b.Tvec(k);
+    }
+    void check_(const cv::Mat& in) const {
+        if (in.type() != CV_8UC1 || in.cols != _size.width || in.rows != _size.height)
+            aruco::arucohip_throw_(ARUCOHIP_E_INVALID, "ChromaticMask: one 8-bit plane of CamSize", nullptr);
+    }
+    void classify_(const cv::Mat& in, const aruco::Board& board, int method) {
+        double r[3], t[3];
+        pose_(board, r, t);
+        check_(in);
+        aruco::arucohip_throw_(arucohip_chromatic_classify(st_(), in.data, 0, (size_t)in.step, r, t, method), "ChromaticMask::classify", _st->h);
+    }
+    cv::Mat fetch_(int (*get)(arucohip_chromatic*, uint8_t*, int)) {
+        cv::Mat out(_size.height, _size.width, CV_8UC1);
+        aruco::arucohip_throw_(get(st_(), out.data, 0), "ChromaticMask::getMask", _st->h);
+        return out;
+    }
+};

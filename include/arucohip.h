@@ -316,6 +316,60 @@ int arucohip_calibrate_board_batch(arucohip_handle* h, int nframes, const int32_
                                    float marker_size, int min_markers, int width, int height, int flags, double K[9], double dist[5],
                                    int32_t* used, double* rvecs, double* tvecs, double* rms);
 
+/* Board occlusion mask: ChromaticMask / EMClassifier of the reference (src/chromaticmask.cpp). Each of the mc x nc cells of the board
+ * holds a 2-component Gaussian mixture over the 256 grey levels of one 8-bit plane; a pixel on the board is 1 when its level is
+ * "board colour" under the model, 0 where something in front of the board hides it. The reference's quirks are kept;
+ * the EM fit is this library's definition (cv::ml::EM cannot be checked here). A chromatic object uses its handle's device and
+ * stream but owns its own buffers: its calls never invalidate the handle's single-frame graph. Not thread-safe with its handle. */
+typedef struct arucohip_chromatic arucohip_chromatic;
+/* setParams(mc, nc, threshProb, CP, BC, markersize) (:122-165): the 4 board corners (x y z each) from the board's nboard markers
+ * (obj: 12 floats per marker, as arucohip_board_detect). A METERS board takes the length of its first edge as marker_size.
+ * ARUCOHIP_E_INVALID for an empty board, or marker_size == -1 on a board that is not METERS. */
+int arucohip_chromatic_board_corners(const float* obj, int nboard, int info_type, float marker_size, float corners[12]);
+/* setParams(mc, nc, threshProb, CP, BC, corners) (:167-216) for width x height frames with camera K (row-major 3x3) and dist (ndist
+ * 0..8). ARUCOHIP_E_UNSUPPORTED for mc or nc of 0, nc > mc or mc * nc > 255 (undefined in the reference). */
+int arucohip_chromatic_create(arucohip_handle* h, int mc, int nc, double thresh_prob, const float* K, const float* dist, int ndist, int width,
+                              int height, const float corners[12], arucohip_chromatic** out);
+void arucohip_chromatic_destroy(arucohip_chromatic* m);
+/* One frame: a width x height plane (host, or device with on_device), its row stride and the board pose rvec / tvec (same units as
+ * the corners). train (:271-313); classify with method 1 = classify (:317-354), 2 = classify2 (:372-438); update (:440-460) retrains
+ * the cells with more than 50 samples under the last mask and the cell map of the last train / method-1 classify. */
+int arucohip_chromatic_train(arucohip_chromatic* m, const uint8_t* plane, int on_device, size_t row_stride, const double rvec[3],
+                             const double tvec[3]);
+int arucohip_chromatic_classify(arucohip_chromatic* m, const uint8_t* plane, int on_device, size_t row_stride, const double rvec[3],
+                                const double tvec[3], int method);
+int arucohip_chromatic_update(arucohip_chromatic* m, const uint8_t* plane, int on_device, size_t row_stride);
+/* calculateGridImage (:222-268) alone: the cell map of the pose; resetMask: the mask to 0 */
+int arucohip_chromatic_grid(arucohip_chromatic* m, const double rvec[3], const double tvec[3]);
+int arucohip_chromatic_reset_mask(arucohip_chromatic* m);
+/* getMask / getCellMap: width x height bytes (mask 0 / 1, cell map 1 + cell or 0) into dst (host, or device with on_device) */
+int arucohip_chromatic_get_mask(arucohip_chromatic* m, uint8_t* dst, int on_device);
+int arucohip_chromatic_get_cell_map(arucohip_chromatic* m, uint8_t* dst, int on_device);
+/* isValid(): 1 after a train */
+int arucohip_chromatic_is_valid(arucohip_chromatic* m);
+/* The model: prob[cell][256] doubles (cell = j * mc + i) and trained[cell] (1 once a fit has run). Cells never fitted hold 0.5.
+ * set_model recomputes inside[cell][v] = prob > thresh_prob. */
+int arucohip_chromatic_get_model(arucohip_chromatic* m, double* prob, int32_t* trained);
+int arucohip_chromatic_set_model(arucohip_chromatic* m, const double* prob, const int32_t* trained);
+/* EMClassifier::train on one cell's raw samples (samples_hist[v] = samples of grey level v), by the device code of the object's fit.
+ * *trained = 0 when the discretised histogram holds fewer than 10 samples: prob / inside are left as they were. */
+int arucohip_em_fit(arucohip_handle* h, const uint32_t samples_hist[256], double thresh_prob, double prob[256], uint8_t inside[256], int* trained);
+/* Geometry of the last single-frame call (frame < 0) or of frame `frame` of the last batch: projected corners, calculateGridImage's
+ * and classify2's homographies (row-major, double). Any output may be NULL. */
+int arucohip_chromatic_debug_geometry(arucohip_chromatic* m, int frame, float corners2d[8], double H_train[9], double H_classify[9]);
+/* The raw-sample histograms and the discretised histograms (histCount) of the last train / update, ncell x 256 each (may be NULL),
+ * and per cell: 1 fitted, 0 fewer than 10 samples (model kept), -1 not retrained (update: 50 samples or fewer). */
+int arucohip_chromatic_debug_hist(arucohip_chromatic* m, uint32_t* raw, uint32_t* hist_count, int32_t* fitted);
+/* classify (method 1) or classify2 (method 2) of every frame of the last arucohip_detect_batch on handle h, at the board poses the last
+ * arucohip_board_detect_batch left on the device (every chunk), against the current model, frozen for the batch. The model is NOT
+ * updated between frames: the reference's update() makes frame f+1 depend on frame f, which a batch cannot honour. A frame without a
+ * pose or with prob <= min_prob gets an all-zero mask. frames: nframes planes (host or device), masks: nframes x width x height
+ * (host or device), npix[f] (may be NULL): the 1 pixels of frame f. The object's single-frame mask and cell map are not touched.
+ * ARUCOHIP_E_INVALID without a board batch of nframes frames on h. */
+int arucohip_chromatic_classify_batch(arucohip_chromatic* m, arucohip_handle* h, const uint8_t* frames, int nframes, int width, int height,
+                                      size_t row_stride, size_t frame_stride, int frames_on_device, int method, float min_prob, uint8_t* masks,
+                                      int masks_on_device, int32_t* npix);
+
 /* Marker::calculateExtrinsics (marker.h:98-104 / marker.cpp:112-124) for n markers at once (batched solvePnP). */
 int arucohip_calculate_extrinsics(arucohip_handle* h, arucohip_marker_t* markers, int n, const float* K, const float* dist,
                                   int ndist, float marker_size, int y_perpendicular);
