@@ -85,6 +85,8 @@ SYMBOLS = [
     "arucohip_chromatic_is_valid", "arucohip_chromatic_get_model", "arucohip_chromatic_set_model", "arucohip_em_fit",
     "arucohip_chromatic_debug_geometry", "arucohip_chromatic_debug_hist", "arucohip_chromatic_classify_batch", "arucohip_chromatic_grid",
     "arucohip_chromatic_reset_mask",
+    "arucohip_hrm_create_dictionary", "arucohip_hrm_board_size", "arucohip_hrm_board_image", "arucohip_debug_hrm_stream",
+    "arucohip_debug_hrm_counters",
 ]
 
 _lib = None
@@ -162,6 +164,11 @@ def load():
     L.arucohip_chromatic_get_model.argtypes = [vp, vp, vp]
     L.arucohip_chromatic_set_model.argtypes = [vp, vp, vp]
     L.arucohip_em_fit.argtypes = [vp, vp, d, vp, vp, vp]
+    L.arucohip_hrm_create_dictionary.argtypes = [vp, i, i, C.c_uint32, vp, vp, vp]
+    L.arucohip_hrm_board_size.argtypes = [i, i, i, i, vp, vp, vp]
+    L.arucohip_hrm_board_image.argtypes = [vp, i, i, vp, i, i, i, vp, sz, i, vp, vp]
+    L.arucohip_debug_hrm_stream.argtypes = [vp, C.c_uint32, C.c_uint64, i, vp]
+    L.arucohip_debug_hrm_counters.argtypes = [vp, vp]
     L.arucohip_chromatic_debug_geometry.argtypes = [vp, i, vp, vp, vp]
     L.arucohip_chromatic_debug_hist.argtypes = [vp, vp, vp, vp]
     L.arucohip_chromatic_classify_batch.argtypes = [vp, vp, vp, i, i, i, sz, sz, i, i, f, vp, i, vp]
@@ -659,6 +666,44 @@ class Handle:
         t = C.c_int()
         self._chk(self.L.arucohip_em_fit(self.h, _ptr(hist), float(thresh_prob), _ptr(p), _ptr(inside), C.byref(t)))
         return p, inside.astype(bool), bool(t.value)
+
+    def hrm_create_dictionary(self, n, size, seed):
+        """HighlyReliableMarkers::createDicitionary(size, n) right after srand(seed), on the device: (codes uint64 [size] in
+        arucohip_set_dictionary's bit layout, tau0, candidates examined)."""
+        codes = np.zeros(max(int(size), 1), np.uint64)
+        tau0, ex = C.c_int(), C.c_int64()
+        self._chk(self.L.arucohip_hrm_create_dictionary(self.h, int(n), int(size), int(seed) & 0xFFFFFFFF, _ptr(codes), C.byref(tau0),
+                                                        C.byref(ex)))
+        return codes, tau0.value, ex.value
+
+    def hrm_board_image(self, codes, n, grid, chromatic=False, ids=True):
+        """HighlyReliableMarkers::createBoardImage(Size(grid[0], grid[1]), D, BC, chromatic) on the device: (image [H][W] or
+        [H][W][3] BGR uint8, ids int32 (None for n >= 6 or ids=False), obj float32 [gw * gh][4][3])."""
+        gw, gh = int(grid[0]), int(grid[1])
+        c = np.ascontiguousarray(codes, dtype=np.uint64)
+        w, hh, ch = C.c_int(), C.c_int(), C.c_int()
+        rc = self.L.arucohip_hrm_board_size(int(n), gw, gh, int(bool(chromatic)), C.byref(w), C.byref(hh), C.byref(ch))
+        if rc != OK:
+            raise ArucoHipError(rc, "arucohip_hrm_board_size")
+        img = np.zeros((hh.value, w.value, ch.value), np.uint8)
+        want_ids = ids and int(n) <= 5
+        ida = np.zeros(gw * gh, np.int32) if want_ids else None
+        obj = np.zeros((gw * gh, 4, 3), np.float32)
+        self._chk(self.L.arucohip_hrm_board_image(self.h, int(n), c.size, _ptr(c), gw, gh, int(bool(chromatic)), _ptr(img), w.value * ch.value,
+                                                  0, _ptr(ida), _ptr(obj)))
+        return (img if chromatic else img[:, :, 0]), ida, obj
+
+    def debug_hrm_stream(self, seed, offset, count):
+        """glibc rand() outputs [offset, offset + count) after srand(seed), made on the device"""
+        out = np.zeros(max(int(count), 1), np.uint32)
+        self._chk(self.L.arucohip_debug_hrm_stream(self.h, int(seed) & 0xFFFFFFFF, int(offset), int(count), _ptr(out)))
+        return out[:int(count)]
+
+    def debug_hrm_counters(self):
+        """the last hrm_create_dictionary: dict(windows, syncs, accepted, decrements)"""
+        out = np.zeros(4, np.int32)
+        self._chk(self.L.arucohip_debug_hrm_counters(self.h, _ptr(out)))
+        return dict(zip(("windows", "syncs", "accepted", "decrements"), (int(x) for x in out)))
 
 
 def chromatic_board_corners(obj, info_type, marker_size=-1.0):

@@ -330,4 +330,44 @@ void launch_chroma_em(hipStream_t s, int ncell, const uint32_t* raw, uint32_t mi
 void launch_chroma_classify(hipStream_t s, const ChromaCam& c, int method, double thresh, int nframes, const uint8_t* frames, size_t row_stride,
                             size_t frame_stride, const ChromaGeom* geom, const double* prob, const uint8_t* inside, uint8_t* masks, int32_t* npix);
 
+// Highly reliable marker dictionaries and boards (k_hrm.hip): createDicitionary / createBoardImage of src/highlyreliablemarkers.cpp.
+constexpr int HRM_STATE = 31;           // words of glibc's rand() state (r[i] = r[i-3] + r[i-31])
+constexpr int HRM_WINDOW = 65536;       // candidates screened per window
+constexpr int HRM_LANE_CANDS = 16;      // consecutive candidates per generating lane
+constexpr int HRM_GEN_BLOCK = 256;
+constexpr int HRM_LANE_BITS = 12;       // lanes per window = 2^12
+constexpr int HRM_DECIDE_BLOCK = 1024;
+constexpr int HRM_LIMIT = 100000;       // MAX_UNPRODUCTIVE_ITERATIONS
+constexpr int HRM_DBG_RUN = 64;         // outputs per lane of arucohip_debug_hrm_stream
+constexpr int HRM_POW_BITS = 48;        // M^(2^b) for b < 48: stream offsets below 2^48
+static_assert(HRM_WINDOW == (HRM_LANE_CANDS * HRM_GEN_BLOCK) << (HRM_LANE_BITS - 8), "window = lanes x candidates per lane");
+enum { HRM_RUNNING = 0, HRM_DONE = 1, HRM_TAU_ZERO = 2, HRM_INTERNAL = 3 };
+
+// The sequential state of createDicitionary, carried from window to window on the device
+struct HrmCtl {
+    int32_t tau, count, limit, dsize;
+    int64_t base;        // index of the window's first candidate
+    int64_t examined;    // index of the last candidate that changed the state (acceptance or tau decrement), plus one
+    int32_t status;      // HRM_*
+    int32_t windows, accepted, decrements;
+};
+
+struct HrmBufs {
+    uint32_t* state;     // [31] the stream state at the window's first output
+    uint32_t* jumps;     // [HRM_LANE_BITS + 1][31 * 31]: M^(HRM_LANE_CANDS n^2 2^b); the last one advances a whole window
+    uint64_t* code;      // [HRM_WINDOW] rotation 0 of every candidate
+    uint8_t* selfd;      // [HRM_WINDOW] selfDistance
+    uint8_t* dmin;       // [HRM_WINDOW] distance to the dictionary
+    uint64_t* dict;      // [dict_size][4] the accepted markers' rotations
+    HrmCtl* ctl;
+};
+
+// one window: generate, screen against the dictionary, walk the sequential decisions, advance the state
+void launch_hrm_window(hipStream_t s, int n, int target, const HrmBufs& b);
+// count outputs from `offset` of the stream whose state at output 0 is state0 (pow2: HRM_POW_BITS matrices M^(2^b))
+void launch_hrm_stream(hipStream_t s, const uint32_t* state0, const uint32_t* pow2, uint64_t offset, int count, uint32_t* out);
+// the board image (gray, or BGR with chromatic) of gw x gh markers; rows of `stride` bytes, a multiple of 16
+void launch_hrm_board(hipStream_t s, const uint64_t* codes, int n, int gw, int gh, int chromatic, int W, int H, int channels, size_t stride,
+                      uint8_t* out);
+
 }  // namespace ah

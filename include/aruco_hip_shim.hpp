@@ -6,7 +6,8 @@
 //   aruco::BoardConfiguration, aruco::Board  /root/reference/src/board.h:54-137 (data, readFromFile, GL / Ogre pose)
 //   aruco::BoardDetector    /root/reference/src/boarddetector.h:40-148
 //   aruco::Dictionary, aruco::MarkerCode, aruco::HighlyReliableMarkers  /root/reference/src/highlyreliablemarkers.h:50-260
-//                           (dictionary files, loadDictionary, the decoder token for setMakerDetectorFunction)
+//                           (dictionary files, loadDictionary, the decoder token for setMakerDetectorFunction,
+//                           createDicitionary and createBoardImage on the device, MarkerCode's rotations and distances)
 //
 // Same member names, argument meaning and failure behaviour (CV_Assert -> cv::Exception) as the reference, so a caller
 // of the reference compiles against this header and links libarucohip.so instead of libaruco + OpenCV imgproc/calib3d.
@@ -509,6 +510,27 @@ public:
         }
         if ((int)ids.size() != (int)nm) arucohip_throw_(ARUCOHIP_E_INVALID, "BoardConfiguration: aruco_bc_nmarkers does not match the marker list", nullptr);
     }
+    // board.cpp:45-49 + src/serialization.cpp:60-92: the file readFromFile reads back (values printed exactly)
+    void saveToFile(const std::string& sfile) const {
+        std::ofstream f(sfile.c_str());
+        if (!f) arucohip_throw_(ARUCOHIP_E_INVALID, ("cannot write " + sfile).c_str(), nullptr);
+        char num[48];
+        f << "%YAML:1.0\naruco_bc_nmarkers: " << ids.size() << "\naruco_bc_mInfoType: " << mInfoType << "\naruco_bc_markers:\n";
+        for (size_t i = 0; i < ids.size(); i++) {
+            f << "   - { id:" << ids[i] << ", corners:[ ";
+            for (size_t c = 0; c < objPoints[i].size(); c++) {
+                const cv::Point3f& p = objPoints[i][c];
+                f << (c ? ", [ " : "[ ");
+                const float v[3] = {p.x, p.y, p.z};
+                for (int k = 0; k < 3; k++) {
+                    std::snprintf(num, sizeof(num), "%.9g", (double)v[k]);
+                    f << num << (k < 2 ? ", " : " ]");
+                }
+            }
+            f << " ] }\n";
+        }
+        if (!f) arucohip_throw_(ARUCOHIP_E_INVALID, ("cannot write " + sfile).c_str(), nullptr);
+    }
     bool isExpressedInMeters() const { return mInfoType == METERS; }
     bool isExpressedInPixels() const { return mInfoType == PIX; }
     const std::vector<cv::Point3f>& getMarkerInfo(int id) const {  // board.cpp:60-66
@@ -538,22 +560,115 @@ public:
     }
 };
 
-// highlyreliablemarkers.h:50-140 (the part the detection path needs: size and bits)
+// highlyreliablemarkers.h:50-140 / .cpp:120-260: an n x n code in its four rotations with their ids. Small host arithmetic.
 class MarkerCode {
 public:
-    explicit MarkerCode(unsigned int n = 0) : _n(n), _bits(n * n, '0') {}
-    void fromString(const std::string& s) { _bits = s; }
-    std::string toString() const { return _bits; }
+    explicit MarkerCode(unsigned int n = 0) : _n(n) {
+        for (int r = 0; r < 4; r++) _bits[r].assign((size_t)n * n, false), _ids[r] = 0;
+    }
+    // MarkerCode::set (:149-182): an n x n CV_8U matrix, non-zero = 1
+    void set(const cv::Mat& code) {
+        if (code.rows != (int)_n || code.cols != (int)_n) arucohip_throw_(ARUCOHIP_E_INVALID, "MarkerCode::set: the code must be n x n", nullptr);
+        uint64_t c = 0;
+        for (unsigned int y = 0; y < _n; y++)
+            for (unsigned int x = 0; x < _n; x++)
+                if (code.at<unsigned char>((int)y, (int)x)) c |= 1ull << (y * _n + x);
+        set_code_(c);
+    }
+    void fromString(const std::string& s) {
+        uint64_t c = 0;
+        for (size_t i = 0; i < s.size() && i < (size_t)_n * _n; i++)
+            if (s[i] == '1') c |= 1ull << i;
+        set_code_(c);
+    }
+    std::string toString() const {
+        std::string s(size(), '0');
+        for (unsigned int i = 0; i < size(); i++)
+            if (get(i)) s[i] = '1';
+        return s;
+    }
     unsigned int n() const { return _n; }
     unsigned int size() const { return _n * _n; }
-    bool get(unsigned int pos) const { return _bits[pos] == '1'; }
+    bool get(unsigned int pos) const { return _bits[0][pos]; }
+    // sum of 2 << pos over the 1 bits of rotation rot. For n >= 6 the reference's int shift passes 32 bits (undefined); here the bits
+    // past 32 are dropped.
+    unsigned int getId(unsigned int rot = 0) const { return _ids[rot]; }
+    const std::vector<bool>& getRotation(unsigned int rot) const { return _bits[rot]; }
+    // :184-194: min over rotations 1..3 of the Hamming distance to rotation 0
+    unsigned int selfDistance(unsigned int& minRot) const {
+        unsigned int res = size();
+        for (unsigned int i = 1; i < 4; i++) {
+            const unsigned int d = hamming_(_bits[0], _bits[i]);
+            if (d < res) minRot = i, res = d;
+        }
+        return res;
+    }
+    unsigned int selfDistance() const {
+        unsigned int r = 0;
+        return selfDistance(r);
+    }
+    // :198-208: min over the rotations of m of the Hamming distance to this code's rotation 0
+    unsigned int distance(const MarkerCode& m, unsigned int& minRot) const {
+        unsigned int res = size();
+        for (unsigned int i = 0; i < 4; i++) {
+            const unsigned int d = hamming_(_bits[0], m.getRotation(i));
+            if (d < res) minRot = i, res = d;
+        }
+        return res;
+    }
+    unsigned int distance(const MarkerCode& m) const {
+        unsigned int r = 0;
+        return distance(m, r);
+    }
+    // :234-260: pixSize rounded up to a multiple of n + 2, black border, white = bit 1
+    cv::Mat getImg(unsigned int pixSize) const {
+        const unsigned int nrows = _n + 2;
+        if (pixSize % nrows != 0) pixSize = pixSize + nrows - pixSize % nrows;
+        const unsigned int cell = pixSize / nrows;
+        cv::Mat img = cv::Mat::zeros((int)pixSize, (int)pixSize, CV_8UC1);
+        for (unsigned int i = 0; i < _n; i++)
+            for (unsigned int j = 0; j < _n; j++)
+                if (_bits[0][i * _n + j])
+                    for (unsigned int k = 0; k < cell; k++)
+                        for (unsigned int l = 0; l < cell; l++) img.at<unsigned char>((int)((i + 1) * cell + k), (int)((j + 1) * cell + l)) = 255;
+        return img;
+    }
+    // rotation 0 in arucohip_set_dictionary's layout (bit y * n + x)
+    uint64_t code_() const {
+        uint64_t c = 0;
+        for (unsigned int i = 0; i < size(); i++)
+            if (_bits[0][i]) c |= 1ull << i;
+        return c;
+    }
 
 private:
+    static unsigned int hamming_(const std::vector<bool>& a, const std::vector<bool>& b) {
+        unsigned int r = 0;
+        for (size_t i = 0; i < a.size(); i++) r += a[i] != b[i];
+        return r;
+    }
+    void set_code_(uint64_t c) {
+        for (int r = 0; r < 4; r++) _bits[r].assign((size_t)_n * _n, false), _ids[r] = 0;
+        for (unsigned int y = 0; y < _n; y++)
+            for (unsigned int x = 0; x < _n; x++) {
+                const bool v = (c >> (y * _n + x)) & 1;
+                for (int r = 0; r < 4; r++) {
+                    unsigned int ry = y, rx = x;
+                    if (r == 1) ry = x, rx = _n - y - 1;
+                    else if (r == 2) ry = _n - y - 1, rx = _n - x - 1;
+                    else if (r == 3) ry = _n - x - 1, rx = y;
+                    const unsigned int pos = ry * _n + rx;
+                    _bits[r][pos] = v;
+                    if (v) _ids[r] |= (unsigned int)(2ull << pos);
+                }
+            }
+    }
     unsigned int _n;
-    std::string _bits;
+    std::vector<bool> _bits[4];
+    unsigned int _ids[4];
 };
 
-// highlyreliablemarkers.h:170-190; fromFile reads the reference's dictionary files (src/serialization.cpp:123-150:
+// highlyreliablemarkers.h:150-190; fromFile / toFile: the reference's dictionary files (src/serialization.cpp:123-150:
 // nmarkers, markersize, tau0, marker_<i>: "<n*n bits>")
 class Dictionary : public std::vector<MarkerCode> {
 public:
@@ -587,9 +702,43 @@ public:
         }
         return true;
     }
+    // :268-274 (serialization.cpp:123-133): the file fromFile reads back
+    bool toFile(const std::string& filename) {
+        if (empty()) arucohip_throw_(ARUCOHIP_E_INVALID, "Dictionary::toFile: empty dictionary", nullptr);
+        std::ofstream f(filename.c_str());
+        if (!f) arucohip_throw_(ARUCOHIP_E_INVALID, ("cannot write " + filename).c_str(), nullptr);
+        f << "%YAML:1.0\nnmarkers: " << size() << "\nmarkersize: " << (*this)[0].n() << "\ntau0: " << tau0 << "\n";
+        for (size_t i = 0; i < size(); i++) f << "marker_" << i << ": \"" << (*this)[i].toString() << "\"\n";
+        if (!f) arucohip_throw_(ARUCOHIP_E_INVALID, ("cannot write " + filename).c_str(), nullptr);
+        return true;
+    }
+    // :277-289: min over the markers of MarkerCode::distance; m.size() when empty
+    unsigned int distance(const MarkerCode& m, unsigned int& minMarker, unsigned int& minRot) {
+        unsigned int res = m.size();
+        for (unsigned int i = 0; i < size(); i++) {
+            unsigned int r = 0;
+            const unsigned int d = (*this)[i].distance(m, r);
+            if (d < res) minMarker = i, minRot = r, res = d;
+        }
+        return res;
+    }
+    unsigned int distance(const MarkerCode& m) {
+        unsigned int a = 0, b = 0;
+        return distance(m, a, b);
+    }
+    // :293-308
+    unsigned int minimunDistance() {
+        if (empty()) return 0;
+        unsigned int best = (*this)[0].size();
+        for (size_t i = 0; i < size(); i++) {
+            best = std::min(best, (*this)[i].selfDistance());
+            for (size_t j = i + 1; j < size(); j++) best = std::min(best, (*this)[i].distance((*this)[j]));
+        }
+        return best;
+    }
 };
 
-// highlyreliablemarkers.h:196-260: static dictionary + decoder token
+// highlyreliablemarkers.h:196-260: static dictionary + decoder token, dictionary and board generation
 class HighlyReliableMarkers {
 public:
     static bool loadDictionary(Dictionary D, float correctionDistanceRate = 1) {  // highlyreliablemarkers.cpp:311-322
@@ -606,6 +755,62 @@ public:
     static int detect(const cv::Mat&, int&) {
         arucohip_throw_(ARUCOHIP_E_UNSUPPORTED, "HighlyReliableMarkers::detect runs on the device; pass it to setMakerDetectorFunction", nullptr);
         return -1;
+    }
+    // :567-608 on the device (arucohip_hrm_create_dictionary). The reference continues the caller's glibc rand() state; this one takes
+    // its seed from one std::rand() call. The three-argument form equals the reference run right after srand(seed).
+    static Dictionary createDicitionary(size_t dictSize, size_t n) { return createDicitionary(dictSize, n, (unsigned int)std::rand()); }
+    static Dictionary createDicitionary(size_t dictSize, size_t n, unsigned int seed) {
+        if (n < 3 || n > 8 || dictSize < 1 || dictSize > 4096)
+            arucohip_throw_(ARUCOHIP_E_INVALID, "createDicitionary: n must be 3..8 and dictSize 1..4096", nullptr);
+        std::vector<uint64_t> codes(dictSize);
+        int tau = 0;
+        SharedHandle_& sh = SharedHandle_::get();
+        {
+            std::lock_guard<std::mutex> lock(sh.mu);
+            arucohip_handle* h = sh.ensure();
+            arucohip_throw_(arucohip_hrm_create_dictionary(h, (int)n, (int)dictSize, seed, codes.data(), &tau, nullptr), "createDicitionary", h);
+        }
+        Dictionary D;
+        for (size_t i = 0; i < dictSize; i++) {
+            MarkerCode m((unsigned int)n);
+            std::string bits((size_t)n * n, '0');
+            for (size_t b = 0; b < bits.size(); b++)
+                if ((codes[i] >> b) & 1) bits[b] = '1';
+            m.fromString(bits);
+            D.push_back(m);
+        }
+        D.tau0 = tau;
+        return D;
+    }
+    // :498-565 on the device (arucohip_hrm_board_image): BC gets PIX, and the markers' ids (getId()) and corners appended, as in the
+    // reference. The ids are undefined there for n >= 6: cv::Exception here.
+    static cv::Mat createBoardImage(cv::Size gridSize, const Dictionary& D, BoardConfiguration& BC, bool chromatic = false) {
+        if (D.empty()) arucohip_throw_(ARUCOHIP_E_INVALID, "createBoardImage: empty dictionary", nullptr);
+        const int n = (int)D[0].n();
+        int w = 0, hgt = 0, ch = 0;
+        arucohip_throw_(arucohip_hrm_board_size(n, gridSize.width, gridSize.height, chromatic ? 1 : 0, &w, &hgt, &ch), "createBoardImage", nullptr);
+        const int nb = gridSize.width * gridSize.height;
+        std::vector<uint64_t> codes(D.size());
+        for (size_t i = 0; i < D.size(); i++) codes[i] = D[i].code_();
+        cv::Mat img(hgt, w, chromatic ? CV_8UC3 : CV_8UC1);
+        std::vector<int32_t> ids((size_t)nb);
+        std::vector<float> obj((size_t)nb * 12);
+        SharedHandle_& sh = SharedHandle_::get();
+        {
+            std::lock_guard<std::mutex> lock(sh.mu);
+            arucohip_handle* h = sh.ensure();
+            arucohip_throw_(arucohip_hrm_board_image(h, n, (int)codes.size(), codes.data(), gridSize.width, gridSize.height, chromatic ? 1 : 0,
+                                                     img.data, img.step, 0, ids.data(), obj.data()),
+                            "createBoardImage", h);
+        }
+        BC.mInfoType = BoardConfiguration::PIX;
+        for (int i = 0; i < nb; i++) {
+            BC.ids.push_back(ids[i]);
+            std::vector<cv::Point3f> MI(4);
+            for (int k = 0; k < 4; k++) MI[k] = cv::Point3f(obj[12 * i + 3 * k], obj[12 * i + 3 * k + 1], obj[12 * i + 3 * k + 2]);
+            BC.objPoints.push_back(MI);
+        }
+        return img;
     }
     struct State_ {
         Dictionary D;

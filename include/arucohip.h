@@ -162,6 +162,29 @@ int arucohip_detect_batch(arucohip_handle* h, const uint8_t* frames, int nframes
  * here for every n. */
 int arucohip_set_dictionary(arucohip_handle* h, int n, int count, const uint64_t* codes, int tau0, float correction_rate);
 
+/* HighlyReliableMarkers::createDicitionary (src/highlyreliablemarkers.cpp:567-608, MarkerGenerator::generateMarker :58-116) as the
+ * reference computes it right after srand(seed) with glibc's rand(): the same dict_size codes in the same order, in the layout of
+ * arucohip_set_dictionary (bit y * n + x = cell (y, x)), so a result loads straight into a detector; *tau0 = the final tau (D.tau0);
+ * *candidates_examined = index of the last candidate the sequential walk looked at, plus one (either may be NULL). Runs on the
+ * device a window of candidates at a time (DESIGN.md "HRM dictionary and board generation"); at most (dict_size + tau0) * 100000
+ * candidates. 3 <= n <= 8 (n = 2 divides by zero in the reference, n > 8 passes 64 bits) and 1 <= dict_size <= 4096, else
+ * ARUCOHIP_E_INVALID; ARUCOHIP_E_INVALID naming it too when tau reaches 0 (the reference's CV_Error). Uses its own scratch: the
+ * handle's single-frame graph stays valid. */
+int arucohip_hrm_create_dictionary(arucohip_handle* h, int n, int dict_size, uint32_t seed, uint64_t* codes_out, int* tau0,
+                                   int64_t* candidates_examined);
+/* HighlyReliableMarkers::createBoardImage (:498-565): the image size of a grid_w x grid_h board of n x n markers: marker size
+ * (n + 2) * 20, gap marker size / 5; chromatic adds a gap-wide margin and 3 channels (BGR). 3 <= n <= 8, grid 1..128 each. */
+int arucohip_hrm_board_size(int n, int grid_w, int grid_h, int chromatic, int* width, int* height, int* channels);
+/* The board image itself, made on the device: white background, getImg (:234-260) markers (white = bit 1, black border) of codes[0 ..
+ * grid_w * grid_h - 1] row by row; chromatic: (250,134,4) with the black pixels (0,255,0), B G R. image: height rows of row_stride
+ * bytes (host, or device with image_on_device). obj (may be NULL): grid_w * grid_h * 4 * 3 floats, BC.objPoints (pixels, centred,
+ * y up). ids (may be NULL): BC.ids = getId() = sum of 2 << pos over the 1 bits; ARUCOHIP_E_UNSUPPORTED for n >= 6, where that shifts
+ * past 32 bits (undefined in the reference). Note that HRM detection reports a marker's position in the dictionary, not getId(): to
+ * find the board with arucohip_board_detect use ids[i] = i. count < grid_w * grid_h is ARUCOHIP_E_INVALID (the
+ * reference reads past the dictionary). */
+int arucohip_hrm_board_image(arucohip_handle* h, int n, int count, const uint64_t* codes, int grid_w, int grid_h, int chromatic, uint8_t* image,
+                             size_t row_stride, int image_on_device, int32_t* ids, float* obj);
+
 /* SURVEY §8b, plugin boundary — MarkerDetector::setMakerDetectorFunction (src/markerdetector.h:243-245) with a function of
  * the caller's own: typedef int (*MarkerdetectorFunc)(const cv::Mat& in, int& nRotations) (:78; contract :65-77: `in` is
  * the square canonical view of a candidate, the return value is the marker id or -1, nRotations the number of 90-degree
@@ -272,6 +295,12 @@ int arucohip_debug_otsu(arucohip_handle* h, int frame, int32_t* thr, int cap, in
 /* Device list fill levels of the last batch: [0] border-start candidates, [1] borders kept, [2] contour points,
  * [3] overflow bits. For sizing arucohip_limits_t. */
 int arucohip_debug_counters(arucohip_handle* h, uint32_t* out8);
+
+/* glibc's rand() outputs [offset, offset + count) after srand(seed), as the device makes them for arucohip_hrm_create_dictionary
+ * (jump-ahead of the stream's state). count <= 2^24, offset + count < 2^48. */
+int arucohip_debug_hrm_stream(arucohip_handle* h, uint32_t seed, uint64_t offset, int count, uint32_t* out);
+/* The last arucohip_hrm_create_dictionary: [0] windows, [1] host synchronisations, [2] acceptances, [3] tau decrements. */
+int arucohip_debug_hrm_counters(arucohip_handle* h, int32_t out[4]);
 
 /* BoardDetector::detect (boarddetector.h:103-108). markers: output of arucohip_detect; ids/obj: BoardConfiguration
  * (board.h:56-69) as nboard ids and nboard*4*3 floats; returns likelihood in *prob (found / total).
