@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 _WORDS = (0x10, 0x17, 0x09, 0x0E)
+_NEXT = np.array([1, 2, 3, 0])           # row i -> row i + 1 of a quad's corners, cyclic
 
 
 def marker_bits(marker_id: int) -> np.ndarray:
@@ -53,7 +54,7 @@ def _paint_quad(img, quad, table, cells, lo, ss=3):
     src = [(lo, lo), (lo + cells, lo), (lo + cells, lo + cells), (lo, lo + cells)]
     Hinv = _homography([tuple(p) for p in q], src)  # image -> table coords
     dev = img.device
-    Hi = torch.tensor(Hinv, dtype=torch.float64, device=dev)
+    Hi = Hinv.tolist()      # Python floats: the products below are the same float64 ones, without a copy to the device that waits for it
     ys = torch.arange(y0, y1, device=dev, dtype=torch.float64)
     xs = torch.arange(x0, x1, device=dev, dtype=torch.float64)
     tab = torch.as_tensor(table, dtype=torch.float32, device=dev)
@@ -62,9 +63,9 @@ def _paint_quad(img, quad, table, cells, lo, ss=3):
     offs = (torch.arange(ss, device=dev, dtype=torch.float64) + 0.5) / ss - 0.5
     px = (xs[None, :] + offs[:, None]).reshape(ss, 1, 1, x1 - x0)   # [ss_x, 1, 1, w]
     py = (ys[None, :] + offs[:, None]).reshape(1, ss, y1 - y0, 1)   # [1, ss_y, h, 1]
-    w = Hi[2, 0] * px + Hi[2, 1] * py + Hi[2, 2]
-    u = (Hi[0, 0] * px + Hi[0, 1] * py + Hi[0, 2]) / w
-    v = (Hi[1, 0] * px + Hi[1, 1] * py + Hi[1, 2]) / w
+    w = Hi[2][0] * px + Hi[2][1] * py + Hi[2][2]
+    u = (Hi[0][0] * px + Hi[0][1] * py + Hi[0][2]) / w
+    v = (Hi[1][0] * px + Hi[1][1] * py + Hi[1][2]) / w
     inside = (u >= lo) & (u < lo + cells) & (v >= lo) & (v < lo + cells)
     ui = torch.clamp((u - lo).floor().long(), 0, n - 1)
     vi = torch.clamp((v - lo).floor().long(), 0, n - 1)
@@ -92,17 +93,19 @@ def _poly_mask(shape, quad, scale):
     y0 = int(max(0, math.floor(q[:, 1].min()) - 1)); y1 = int(min(h, math.ceil(q[:, 1].max()) + 2))
     if x1 <= x0 or y1 <= y0:
         return 0, 0, 0, 0, np.zeros((0, 0), bool)
-    ys, xs = np.mgrid[y0:y1, x0:x1]
+    # cell centres as a column and a row: each edge's two products are formed once per row / column and broadcast
+    ys = np.arange(y0, y1)[:, None] + 0.5
+    xs = np.arange(x0, x1)[None, :] + 0.5
     m = np.ones((y1 - y0, x1 - x0), bool)
     sign = 0
     for i in range(4):
         ax, ay = q[i]
         bx, by = q[(i + 1) % 4]
-        cr = (bx - ax) * (ys + 0.5 - ay) - (by - ay) * (xs + 0.5 - ax)
+        cr = (bx - ax) * (ys - ay) - (by - ay) * (xs - ax)
         if sign == 0:
             c = (q[:, 0].mean() - ax) * (by - ay) - (q[:, 1].mean() - ay) * (bx - ax)
             sign = -1 if c > 0 else 1
-        m &= (cr * sign) >= 0
+        m &= (cr <= 0) if sign < 0 else (cr >= 0)
     return y0, y1, x0, x1, m
 
 
@@ -123,10 +126,23 @@ def frame_layout(rng, width, height, n_markers=20, side_range=(90, 220), margin=
                 continue
             cx = rng.uniform(margin, width - margin)
             cy = rng.uniform(margin, height - margin)
+            corner_jitter = rng.uniform(-jitter, jitter, size=(4, 2))  # mild perspective
+            # that was the attempt's last draw: from here on the tests may reject in any order without changing the stream. The quad
+            # holds the disc of radius (0.5 - jitter) s around (cx, cy) (36 px at the least: s >= 86) and the grown quiet-zone quad holds
+            # the quad, so the (2k+1)^2 cells around (cx, cy) (centres at most (k + 1/2) sqrt(2) cells away, 8 px inside that disc) are
+            # all in the occupancy mask below: one of them occupied fails that test
+            k = math.floor(((0.5 - jitter) * s - 8) / (sc * 1.415) - 0.5)
+            if k >= 0:
+                ix, iy = int(cx) // sc, int(cy) // sc
+                if occ[max(iy - k, 0):iy + k + 1, max(ix - k, 0):ix + k + 1].any():
+                    continue
             R = np.array([[math.cos(th), -math.sin(th)], [math.sin(th), math.cos(th)]])
             base = np.array([[-0.5, -0.5], [0.5, -0.5], [0.5, 0.5], [-0.5, 0.5]]) * s
-            base = base + rng.uniform(-jitter, jitter, size=(4, 2)) * s  # mild perspective
+            base = base + corner_jitter * s
             quad = base @ R.T + np.array([cx, cy])
+            (qx0, qy0), (qx1, qy1) = quad.min(axis=0), quad.max(axis=0)
+            if qx0 < margin or qx1 > width - margin or qy0 < margin or qy1 > height - margin:
+                continue
             # quiet-zone quad: extend the marker's own projective frame by `quiet` cells
             Hm = _homography([(0, 0), (cells, 0), (cells, cells), (0, cells)], [tuple(p) for p in quad])
             qq = []
@@ -134,14 +150,13 @@ def frame_layout(rng, width, height, n_markers=20, side_range=(90, 220), margin=
                 p = Hm @ np.array([u, v, 1.0])
                 qq.append(p[:2] / p[2])
             qq = np.array(qq)
-            if quad[:, 0].min() < margin or quad[:, 0].max() > width - margin or quad[:, 1].min() < margin or \
-                    quad[:, 1].max() > height - margin:
-                continue
-            if qq[:, 0].min() < 2 or qq[:, 0].max() > width - 3 or qq[:, 1].min() < 2 or qq[:, 1].max() > height - 3:
+            (qx0, qy0), (qx1, qy1) = qq.min(axis=0), qq.max(axis=0)
+            if qx0 < 2 or qx1 > width - 3 or qy0 < 2 or qy1 > height - 3:
                 continue
             # is the quad convex / well formed?
-            d = np.roll(qq, -1, axis=0) - qq
-            cr = d[:, 0] * np.roll(d, -1, axis=0)[:, 1] - d[:, 1] * np.roll(d, -1, axis=0)[:, 0]
+            d = qq[_NEXT] - qq
+            dn = d[_NEXT]
+            cr = d[:, 0] * dn[:, 1] - d[:, 1] * dn[:, 0]
             if not (np.all(cr > 0) or np.all(cr < 0)):
                 continue
             # pad the occupancy test by a few pixels so quiet zones never touch
@@ -172,10 +187,15 @@ def render_frame(layout, width, height, rng, device="cpu", noise_sigma=1.5, quie
         field = torch.randn((1, 1, height // 24 + 3, width // 24 + 3), generator=g2).to(dev)
         field = torch.nn.functional.interpolate(field, size=(height, width), mode="bicubic", align_corners=False)[0, 0]
         img = torch.where(field > 0.25, img - rng.uniform(70, 110), img)
+    tables = []
     for mk in layout:
         black = rng.uniform(15, 45)
         white = rng.uniform(215, 245)
-        t = (table_fn or _marker_table)(mk["id"], quiet, black, white)
+        tables.append((table_fn or _marker_table)(mk["id"], quiet, black, white))
+    if tables:
+        # the frame's tables go to the device in one copy: a copy per marker would wait for every kernel queued before it
+        tables = torch.as_tensor(np.stack(tables), dtype=torch.float32, device=dev)
+    for mk, t in zip(layout, tables):
         _paint_quad(img, mk["quad_q"], t, cells + 2 * quiet, -quiet)
     if noise_sigma > 0:
         if gen is None:

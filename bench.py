@@ -12,6 +12,11 @@ per frame, threshold + contours + decode + LINES refinement, no pose) that are a
 in HBM. With N > 1 every rank owns its own camera stream (seed 4711 + rank, frames sharded one stream per GPU, no
 data-path collective) and the per-frame marker blocks are gathered to rank 0 over RCCL once per step (config 5).
 Prints ONE JSON line on rank 0.
+
+A plain run does what the headline needs and nothing more: it sets up, warms up, times the K steps, checks the last timed
+batch's ids against the rendered ones, writes --dump-outputs and prints the line. `--full` adds what the headline does not
+need: the replica and instrumented passes behind `roofline` and the per-kernel times, the CPU baseline, the latency and
+thread-scaling legs and the other configurations (`other_configs`, each a `--full` child run of its own).
 """
 import argparse
 import json
@@ -383,7 +388,7 @@ def run_leg(extra, timeout=420):
     import subprocess
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-cpu-baseline", "--no-latency", "--no-legs"] + extra
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-cpu-baseline", "--no-latency", "--no-legs"] + extra
     try:
         r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout)
     except subprocess.TimeoutExpired:
@@ -410,9 +415,12 @@ def main():
     ap.add_argument("--depth", type=int, default=0,
                     help="batches in flight (arucohip_detect_batch_submit / _wait); 1 = one synchronous-style batch at a time; default 5, "
                          "config 4: 6 (its 128-frame batches wait on a 5000-step border walk: more of them in flight fill the chip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-latency", action="store_true", help="skip the single-frame latency leg (extra keys of the JSON line)")
-    ap.add_argument("--no-legs", action="store_true", help="skip the short legs of configs 3 / 4 / pinned H2D / clutter (extra key other_configs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the bench measures: the replica and instrumented passes (roofline, per-kernel times, "
+                         "h2d, list fill), the CPU baseline, the latency and thread-scaling legs and the other configurations (other_configs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-latency", action="store_true", help="with --full: skip the single-frame latency leg (extra keys of the JSON line)")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the short legs of configs 3 / 4 / pinned H2D / clutter (extra key other_configs)")
     ap.add_argument("--profile-run", action="store_true",
                     help="for rocprofv3 (tools/profile.sh): warm-up + timed steps at the default depth only - no instrumented / isolated passes, no legs - "
                          "so that EVERY dispatch in the trace is an in-stream launch of the configuration the headline is measured on")
@@ -660,6 +668,36 @@ def main():
             dist.barrier()
             dist.destroy_process_group()
         return
+    # ---- the headline line: what the timed region and the guard above give, no further GPU work
+    fps = world * B * args.steps / elapsed
+    res = {
+        "metric": "frames/sec at %d×%d" % (W, H), "value": round(fps, 2), "unit": "frames/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+        "config": {"workload": ("3840x2160 6x4 board frames (24 markers), detect + batched BoardDetector solvePnP (config 4)" if board is not None else
+                                "1920x1080 synthetic stream, ~20 markers/frame, threshold+contour+decode+LINES"
+                                + (" + per-marker solvePnP (config 3)" if args.pose else ", no pose (config 2)"))
+                               + (", frames start in pinned host memory (PCIe inclusive)" if args.host_frames else "")
+                               + (", textured backgrounds (second headline: what camera frames look like)" if args.clutter else ""),
+                   "frames_per_step_per_gpu": B, "distinct_frames_per_gpu": args.frames, "markers_rendered_per_frame": 24 if board is not None else 20,
+                   "markers_detected_per_frame": round(found / B, 2), "batches_in_flight": depth, "build": build,
+                   "timed_region": "no per-kernel instrumentation; every batch's packed result block (%d bytes) leaves the GPU inside it, asynchronously: "
+                                   % (gp.bytes_per_step if gp is not None else 0)
+                                   + ("copied to pinned host memory" if world == 1 else "gathered to rank 0 over RCCL") + ", waited for `batches_in_flight` steps later",
+                   "thresholded_image": "written in the hot path" if os.environ.get("ARUCOHIP_THRES_BYTES", "0") not in ("", "0") else
+                   "kept as bit tiles + border lines, bytes on request (ARUCOHIP_THRES_BYTES=1 writes them in the hot path)", "gpu_max_hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]), "parallelism": "frames sharded 1 stream/GPU"
+                   + (", packed marker blocks gathered over RCCL per step, asynchronously (own stream and process group), %d bytes per rank" % gp.bytes_per_step
+                      if (gp is not None and world > 1) else "")},
+        "hbm_algorithmic_gbps": round(ALG_BYTES_PER_FRAME * fps / 1e9, 2),
+        "hbm_frac_of_peak": round(ALG_BYTES_PER_FRAME * fps / 1e9 / (HBM_PEAK_GBPS * world), 5),
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # ---- replica pass, outside the timed region: the timed loop once more (same steps, same batches in flight, same result copies) with nothing
     # but the threshold kernel's device-clock stamps on (no hipEvents between the kernels): the in-stream duration of its launches as
     # rocprofv3 --kernel-trace reports it for `bench.py --profile-run` (profiles/<tag>_kernel_stats.csv)
@@ -672,7 +710,7 @@ def main():
     handle.enable_timing(False)
     # ---- instrumented passes, outside the timed region: per-kernel hipEvent intervals and the threshold kernel's device-clock span with
     # the same batches in flight, then one batch at a time (what rocprofv3 shows per dispatch when nothing else runs)
-    gp_keep, gp = gp, None                      # the instrumented passes do not gather
+    gp = None                                   # the instrumented passes do not gather
     handle.enable_timing(True)
     nin = min(args.steps, 12)
     for i in range(nin):
@@ -696,8 +734,6 @@ def main():
     fill = handle.debug_counters() if args.clutter else None
 
     if rank == 0:
-        total_frames = world * B * args.steps
-        fps = total_frames / elapsed
         # The roofline object is about the pipeline's one HBM-streaming kernel, the adaptive threshold pass. `achieved` / `frac` price it in
         # ITS OWN algorithmic bytes (threshold_own_bytes: gray read + bit tiles + bitmap + border lines written) over the duration of its
         # launches IN THE STREAM (batches in flight); SURVEY 8d's 3 W H recipe is kept as frac_survey_recipe, with the reason it can
@@ -750,26 +786,7 @@ def main():
                                       "traffic_over_algorithmic": round(kk[k]["hbm_bytes_per_frame"] / v[0], 2), "algorithmic": v[1]} for k, v in alg.items() if k in kk}
             except Exception as e:   # a malformed file is reported, not replayed
                 traffic, traffic_src = None, "profiles/hbm_traffic.json unreadable: %r" % (e,)
-        res = {
-            "metric": "frames/sec at %d×%d" % (W, H), "value": round(fps, 2), "unit": "frames/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-            "config": {"workload": ("3840x2160 6x4 board frames (24 markers), detect + batched BoardDetector solvePnP (config 4)" if board is not None else
-                                    "1920x1080 synthetic stream, ~20 markers/frame, threshold+contour+decode+LINES"
-                                    + (" + per-marker solvePnP (config 3)" if args.pose else ", no pose (config 2)"))
-                                   + (", frames start in pinned host memory (PCIe inclusive)" if args.host_frames else "")
-                                   + (", textured backgrounds (second headline: what camera frames look like)" if args.clutter else ""),
-                       "frames_per_step_per_gpu": B, "distinct_frames_per_gpu": args.frames, "markers_rendered_per_frame": 24 if board is not None else 20,
-                       "markers_detected_per_frame": round(found / B, 2), "batches_in_flight": depth, "build": build,
-                       "timed_region": "no per-kernel instrumentation; every batch's packed result block (%d bytes) leaves the GPU inside it, asynchronously: "
-                                       % (gp_keep.bytes_per_step if gp_keep is not None else 0)
-                                       + ("copied to pinned host memory" if world == 1 else "gathered to rank 0 over RCCL") + ", waited for `batches_in_flight` steps later",
-                       "thresholded_image": "written in the hot path" if os.environ.get("ARUCOHIP_THRES_BYTES", "0") not in ("", "0") else
-                       "kept as bit tiles + border lines, bytes on request (ARUCOHIP_THRES_BYTES=1 writes them in the hot path)", "gpu_max_hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]), "parallelism": "frames sharded 1 stream/GPU"
-                       + (", packed marker blocks gathered over RCCL per step, asynchronously (own stream and process group), %d bytes per rank" % gp_keep.bytes_per_step
-                          if (gp_keep is not None and world > 1) else "")},
-            "hbm_algorithmic_gbps": round(ALG_BYTES_PER_FRAME * fps / 1e9, 2),
-            "hbm_frac_of_peak": round(ALG_BYTES_PER_FRAME * fps / 1e9 / (HBM_PEAK_GBPS * world), 5),
+        res.update({
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic, "traffic_source": traffic_src,
                          "algorithmic_bytes_per_launch": own * per_launch, "algorithmic_bytes_per_frame": own,
@@ -802,7 +819,7 @@ def main():
                          "longest_kernel_note": "a latency-bound chain of dependent border steps; SURVEY 8d defines no algorithmic bytes for it"},
             "kernel_ms_per_launch": {k: round(v, 4) for k, v in ktimes.items()},
             "kernel_ms_isolated": {k: round(v, 4) for k, v in ktimes_iso.items()},
-        }
+        })
         if args.host_frames and world == 1:
             # the link: what this box's plain pinned hipMemcpyAsync reaches, and what the detector's frame copies reach inside the step
             ceil_gbps = h2d_ceiling_gbps(torch, dev)

@@ -15,7 +15,7 @@ shift $((OPTIND - 1))
 for r in $(seq 1 $ROUNDS); do
   for setting in "$@"; do
     envs=${setting%% -- *}; args=""; [[ "$setting" == *" -- "* ]] && args=${setting#* -- }
-    env $envs python bench.py --no-latency --no-cpu-baseline --no-legs --steps $STEPS --warmup $WARM $ALL $args 2>/dev/null | python -c "
+    env $envs python bench.py --full --no-latency --no-cpu-baseline --no-legs --steps $STEPS --warmup $WARM $ALL $args 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1])
 print('round $r | $setting |', d['value'], 'fps', d['ms_per_step'], 'ms/step', {k: round(v, 3) for k, v in d.get('kernel_ms_isolated', {}).items() if v > 0.05})" || exit 1
