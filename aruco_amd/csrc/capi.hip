@@ -104,6 +104,42 @@ private:
     }
 };
 
+constexpr int MAX_WORKERS = 8;   // chunk workers of a handle, itself included (ARUCOHIP_STREAMS)
+
+// A batch as the workers hold it: chunk c of its frames ran on worker c (chunk_worker). The handle the caller holds keeps the last one
+// (arucohip_handle::last): every call that replaces the device lists sets it whole, from plan_batch, or clears it when they no longer
+// hold a batch; a waited ticket adopts its lane's. The getters, board poses, calibration and ChromaticMask read it and nothing else.
+struct Span { arucohip_handle* w; int first, count; };   // worker w holds frames [first, first + count)
+struct Batch {
+    int nspan = 0, frames = 0;
+    Span span[MAX_WORKERS] = {};
+    int W = 0, H = 0, nthr = 1;
+    int board_frames = 0;   // frames whose board poses arucohip_board_detect_batch left in the workers' d_board
+    const Span* begin() const { return span; }
+    const Span* end() const { return span + nspan; }
+    // the worker that holds frame `frame` and the frame's index there; nullptr: the batch has no such frame
+    arucohip_handle* holder(int frame, int* local) const {
+        for (const Span& s : *this)
+            if (frame >= s.first && frame < s.first + s.count) return *local = frame - s.first, s.w;
+        return nullptr;
+    }
+    // the spans of the first nframes frames
+    Batch cut(int nframes) const {
+        Batch b = *this;
+        b.nspan = 0, b.frames = std::min(frames, nframes);
+        for (const Span& s : *this)
+            if (s.first < nframes) b.span[b.nspan++] = {s.w, s.first, std::min(s.count, nframes - s.first)};
+        return b;
+    }
+};
+
+// highly reliable markers (arucohip_set_dictionary); count 0: none
+struct Dictionary {
+    int n = 0, count = 0, tau0 = 0;
+    float rate = 1.f;
+    std::vector<uint64_t> codes;   // kept on the host as well: a new child takes them without reading the device copy back
+};
+
 struct arucohip_handle {
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
@@ -127,10 +163,8 @@ struct arucohip_handle {
     int umap_w = 0, umap_h = 0, umap_nd = -1;
     float umap_K[9] = {}, umap_d[8] = {};
     Mem<uint8_t> d_undist;            // undistorted frames when the caller wants them on the host
-    // highly reliable markers (arucohip_set_dictionary)
-    Mem<uint64_t> d_hrm;
-    int hrm_n = 0, hrm_count = 0, hrm_tau0 = 0;
-    float hrm_rate = 1.f;
+    Dictionary hrm;
+    Mem<uint64_t> d_hrm;              // hrm.codes on the device
     // caller's own decoder (arucohip_set_decoder_callback)
     arucohip_decoder_fn decoder_fn = nullptr;
     void* decoder_user = nullptr;
@@ -154,29 +188,22 @@ struct arucohip_handle {
     Mem<double> d_gl;                 // batched GL modelview matrices
     Mem<uint8_t> d_calib;             // camera calibration: solver state, per-view systems and poses, correspondences (calib_carve)
     Mem<CalibState> hc_calib{true};   // pinned copy of the solver state, read once per iteration
-    // last call
-    int last_w = 0, last_h = 0, last_frames = 0, last_nthr = 1;
-    const uint8_t* last_gray = nullptr;
-    FrameGeom last_geom{};
+    Batch last;                       // the last batch (kept on the handle the caller holds)
     bool timing = false;
     hipEvent_t ev[TSETS][K_COUNT + 1] = {};
     int tsets = 0;                       // batches recorded since the last reset
     float kernel_ms[K_COUNT] = {};       // averages over the recorded batches
     // Sub-batch pipelining: a batch larger than cap_frames is cut into up to nsub chunks; chunk 0 runs on this handle and
-    // the caller's stream, chunk i on kids[i-1] and its own stream, so the latency-bound kernels of one chunk (border
+    // the caller's stream, chunk i on chunk worker i (chunk_worker) and its own stream, so the latency-bound kernels of one chunk (border
     // following, Otsu) overlap the bandwidth-bound ones of another and host frames are copied while earlier chunks compute.
     int nsub = 1, cap_frames = 1;        // workers, frames each worker's buffers hold
-    bool is_child = false;
     std::vector<arucohip_handle*> kids;
-    hipEvent_t ev_fork = nullptr, ev_join[8] = {};
+    hipEvent_t ev_fork = nullptr, ev_join[MAX_WORKERS] = {};
     hipStream_t side_stream = nullptr;   // late walker generations (k_contours.hip)
     hipEvent_t ev_wfork = nullptr, ev_wjoin = nullptr;
     hipEvent_t ev_thr = nullptr;         // this worker's threshold kernel has finished (staggers the chunks, see detect_batch)
     bool thres_bytes = true;             // buf.thres holds the last batch's byte image (else: tiles + buf.thres_edge, expanded on demand)
     hipEvent_t wait_thr = nullptr;       // set by detect_batch: event the next threshold kernel waits for
-    int last_chunks = 1, last_per = 0;   // chunks and frames per chunk of the last batch
-    int board_frames = 0;                // frames whose board poses arucohip_board_detect_batch left in the workers' d_board for the
-                                         // lists of the last detection; every call that replaces the lists sets it back to 0
     Mem<uint8_t> d_em;                   // arucohip_em_fit scratch, with its own allocation counter (not alloc_epoch)
     uint64_t em_epoch = 0;
     Mem<uint8_t> d_hrm_gen;              // HRM dictionary / board generation scratch (k_hrm.hip), its own counter too (not alloc_epoch)
@@ -198,31 +225,44 @@ struct arucohip_handle {
     // decoding) overlaps the bandwidth-bound head of batch t+1.
     std::vector<arucohip_handle*> lanes;
     int next_ticket = 0;
-    arucohip_handle* cur = nullptr;      // lane whose results the getters / board pose address (last waited ticket)
     arucohip_handle* retry = nullptr;    // one-frame handle with larger lists for frames that overflowed (arucohip_detect_batch_retry_overflowed)
     int retry_mult = 0;
     hipEvent_t ev_submit = nullptr;
     struct Pending {
         bool active = false;
-        int ticket = -1, nframes = 0, cap = 0, out_on_device = 0;
+        int ticket = -1, cap = 0, out_on_device = 0;
         arucohip_marker_t* out = nullptr;
         int32_t* n_out = nullptr;
     } pend;
     std::string err;
 };
 
-// the worker that holds the results of the last completed batch
-static arucohip_handle* active(arucohip_handle* h) { return (h && h->cur) ? h->cur : h; }
+// chunk c of a batch runs on worker c: the handle itself, then its chunk workers
+static arucohip_handle* chunk_worker(arucohip_handle* h, int c) { return c == 0 ? h : h->kids[c - 1]; }
 
-// worker that holds frame `frame` of the last batch (and the frame's index inside that worker)
-static arucohip_handle* route(arucohip_handle* h, int frame, int* local) {
-    if (h->last_chunks <= 1 || h->last_per <= 0) {
-        *local = frame;
-        return h;
-    }
-    const int c = std::min(frame / h->last_per, h->last_chunks - 1);
-    *local = frame - c * h->last_per;
-    return c == 0 ? h : h->kids[c - 1];
+// A batch of nframes frames on h's workers: chunks of equal size, as few as the workers' buffers allow but one per worker when the batch is
+// large enough to share
+static Batch plan_batch(arucohip_handle* h, int nframes, int W, int H, int nthr) {
+    int chunks = (nframes + h->cap_frames - 1) / h->cap_frames;
+    if (h->nsub > 1 && (size_t)nframes * W * H >= (size_t)h->nsub * 32 * 1024 * 1024) chunks = std::max(chunks, std::min(h->nsub, nframes));
+    const int per = (nframes + chunks - 1) / chunks;
+    chunks = (nframes + per - 1) / per;
+    Batch b;
+    b.nspan = chunks, b.frames = nframes, b.W = W, b.H = H, b.nthr = nthr;
+    for (int c = 0; c < chunks; c++) b.span[c] = {chunk_worker(h, c), c * per, std::min(per, nframes - c * per)};
+    return b;
+}
+
+// Visits every worker of h's tree: its chunk workers, each pipeline lane with the lane's chunk workers, then h itself (children first, so
+// that f may delete what it visits), and stops at the first error f returns. The retry handle is not part of the tree (drop_retry).
+template <class F>
+static int for_each_worker(arucohip_handle* h, const F& f) {
+    int rc = ARUCOHIP_OK;
+    for (auto* k : h->kids)
+        if (!rc) rc = f(k);
+    for (auto* l : h->lanes)
+        if (!rc) rc = for_each_worker(l, f);
+    return rc ? rc : f(h);
 }
 
 #define HIPCHK(h, expr)                                                                         \
@@ -306,18 +346,9 @@ static int validate_params(arucohip_handle* h, const arucohip_params_t* p) {
     return ARUCOHIP_OK;
 }
 
-extern "C" void arucohip_destroy(arucohip_handle* h);
-// everything but the memory, which the handle's Mem members free when it is deleted
-static void free_all(arucohip_handle* h) {
-    hipSetDevice(h->device);
-    for (auto* k : h->kids) arucohip_destroy(k);
-    h->kids.clear();
-    for (auto* l : h->lanes) arucohip_destroy(l);
-    h->lanes.clear();
-    if (h->retry) arucohip_destroy(h->retry);
-    h->retry = nullptr;
+// a worker's own graph, events and streams; its memory goes with its Mem members when it is deleted
+static void release(arucohip_handle* h) {
     if (h->fgraph.exec) hipGraphExecDestroy(h->fgraph.exec);
-    h->fgraph.exec = nullptr;
     if (h->ev_submit) hipEventDestroy(h->ev_submit);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ev_thr) hipEventDestroy(h->ev_thr);
@@ -332,8 +363,6 @@ static void free_all(arucohip_handle* h) {
     if (h->own_stream) hipStreamDestroy(h->own_stream);
 }
 
-static thread_local bool g_creating_child = false;
-
 // The one-frame handle of arucohip_detect_batch_retry_overflowed copies parameters, dictionary and decoder callback when it is made: whenever
 // one of them changes it is dropped and the next retry builds a fresh one (a stale copy would decode retried frames with the old dictionary).
 static void drop_retry(arucohip_handle* h) {
@@ -341,7 +370,54 @@ static void drop_retry(arucohip_handle* h) {
     h->retry = nullptr, h->retry_mult = 0;
 }
 
-int arucohip_create_ex(const arucohip_params_t* params, int device, const arucohip_limits_t* lim, arucohip_handle** out) {
+// device-clock stamps of the wide threshold kernel (k_threshold.hip): taken while `on`, the accumulators restart with them
+static void arm_stamps(arucohip_handle* w, bool on) {
+    w->buf.thr_stamp_on = on && w->buf.thr_stamps && w->buf.thr_acc;
+    if (on && w->buf.thr_acc) {
+        hipSetDevice(w->device);
+        (void)hipStreamSynchronize(w->stream);
+        (void)hipMemset(w->buf.thr_acc, 0, 2 * sizeof(uint64_t));
+    }
+}
+
+// worker w takes dictionary d once its batches in flight, which may still read the old one, are done; errors are reported on h
+static int load_dictionary(arucohip_handle* h, arucohip_handle* w, const Dictionary& d) {
+    HIPCHK(h, hipStreamSynchronize(w->stream));
+    w->hrm = Dictionary{};   // none until the device copy is complete
+    if (d.count > 0) {
+        HIPCHK(h, w->d_hrm.reserve((size_t)d.count * sizeof(uint64_t), w->alloc_epoch));
+        HIPCHK(h, hipMemcpy(w->d_hrm, d.codes.data(), (size_t)d.count * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    w->hrm = d;
+    return ARUCOHIP_OK;
+}
+
+// a new child (chunk worker, pipeline lane, retry handle) and its own chunk workers take the parent's parameters, decoder callback,
+// dictionary and timing
+static int inherit(arucohip_handle* parent, arucohip_handle* child) {
+    return for_each_worker(child, [&](arucohip_handle* w) {
+        w->params = parent->params;
+        w->decoder_fn = parent->decoder_fn, w->decoder_user = parent->decoder_user;
+        w->timing = parent->timing;
+        arm_stamps(w, parent->buf.thr_stamp_on != 0);
+        return load_dictionary(parent, w, parent->hrm);
+    });
+}
+
+// is_kid: the handle is one of another's chunk workers and gets none of its own
+static int create_handle(const arucohip_params_t* params, int device, const arucohip_limits_t* lim, bool is_kid, arucohip_handle** out);
+
+// a new child of `parent` with limits `lim`, holding the parent's settings (errors are reported on the parent)
+static int create_child(arucohip_handle* parent, const arucohip_limits_t& lim, bool is_kid, arucohip_handle** out) {
+    int rc = create_handle(&parent->params, parent->device, &lim, is_kid, out);
+    if (rc == ARUCOHIP_OK && (rc = inherit(parent, *out)) != ARUCOHIP_OK) {
+        arucohip_destroy(*out);
+        *out = nullptr;
+    }
+    return rc;
+}
+
+static int create_handle(const arucohip_params_t* params, int device, const arucohip_limits_t* lim, bool is_kid, arucohip_handle** out) {
     if (!out || !lim) return ARUCOHIP_E_INVALID;
     *out = nullptr;
     if (lim->max_width < 32 || lim->max_height < 32 || lim->max_width > 16383 || lim->max_height > 16383 || lim->max_batch < 1 ||
@@ -362,8 +438,7 @@ int arucohip_create_ex(const arucohip_params_t* params, int device, const arucoh
     }
     auto bail = [&](hipError_t e) {
         fprintf(stderr, "arucohip_create: %s\n", hipGetErrorString(e));
-        free_all(h);
-        delete h;
+        arucohip_destroy(h);
         return ARUCOHIP_E_HIP;
     };
     hipError_t e;
@@ -374,12 +449,9 @@ int arucohip_create_ex(const arucohip_params_t* params, int device, const arucoh
         // workers: one by default; ARUCOHIP_STREAMS = 2..8 cuts large batches into chunks on separate streams (copies of host
         // frames then overlap the kernels). With the late walker generations on their own side stream a second chunk stream
         // no longer gains anything for device-resident frames (1 stream 208 k fps, 2 streams 208 k at 1024 1080p frames).
-        const double mpx = (double)lim->max_batch * lim->max_width * lim->max_height / (128.0 * 1024 * 1024);
         int ns = 1;
-        (void)mpx;
-        if (const char* es = getenv("ARUCOHIP_STREAMS")) ns = std::min(8, std::max(1, atoi(es)));
-        if (g_creating_child) ns = 1;
-        h->is_child = g_creating_child;
+        if (const char* es = getenv("ARUCOHIP_STREAMS")) ns = std::min(MAX_WORKERS, std::max(1, atoi(es)));
+        if (is_kid) ns = 1;
         h->nsub = std::min(ns, lim->max_batch);
         h->cap_frames = (lim->max_batch + h->nsub - 1) / h->nsub;
     }
@@ -486,12 +558,9 @@ int arucohip_create_ex(const arucohip_params_t* params, int device, const arucoh
             arucohip_limits_t kl = *lim;
             kl.max_batch = h->cap_frames;
             arucohip_handle* kid = nullptr;
-            g_creating_child = true;
-            int krc = arucohip_create_ex(&h->params, device, &kl, &kid);
-            g_creating_child = false;
+            const int krc = create_child(h, kl, true, &kid);
             if (krc != ARUCOHIP_OK) {
-                free_all(h);
-                delete h;
+                arucohip_destroy(h);
                 return krc;
             }
             h->kids.push_back(kid);
@@ -499,6 +568,10 @@ int arucohip_create_ex(const arucohip_params_t* params, int device, const arucoh
     }
     *out = h;
     return ARUCOHIP_OK;
+}
+
+int arucohip_create_ex(const arucohip_params_t* params, int device, const arucohip_limits_t* lim, arucohip_handle** out) {
+    return create_handle(params, device, lim, false, out);
 }
 
 int arucohip_create(const arucohip_params_t* params, int device, int max_width, int max_height, int max_batch, arucohip_handle** out) {
@@ -510,8 +583,9 @@ int arucohip_create(const arucohip_params_t* params, int device, int max_width, 
 
 void arucohip_destroy(arucohip_handle* h) {
     if (!h) return;
-    free_all(h);
-    delete h;
+    hipSetDevice(h->device);
+    drop_retry(h);
+    for_each_worker(h, [](arucohip_handle* w) { release(w); delete w; return ARUCOHIP_OK; });
 }
 
 int arucohip_set_params(arucohip_handle* h, const arucohip_params_t* p) {
@@ -520,12 +594,7 @@ int arucohip_set_params(arucohip_handle* h, const arucohip_params_t* p) {
     if (rc != ARUCOHIP_OK) return rc;
     if (2 * p->thres_param1_range + 1 > h->lim.max_thres_planes)
         return fail(h, ARUCOHIP_E_INVALID, "threshold range exceeds the planes this handle was created with");
-    h->params = *p;
-    for (auto* k : h->kids) k->params = *p;
-    for (auto* l : h->lanes) {
-        l->params = *p;
-        for (auto* k : l->kids) k->params = *p;
-    }
+    for_each_worker(h, [&](arucohip_handle* w) { w->params = *p; return ARUCOHIP_OK; });
     drop_retry(h);
     return ARUCOHIP_OK;
 }
@@ -562,22 +631,13 @@ int arucohip_wait_event(arucohip_handle* h, void* ev) {
 
 int arucohip_enable_timing(arucohip_handle* h, int on) {
     if (!h) return ARUCOHIP_E_INVALID;
-    h->timing = on == 1;      // on == 2: only the threshold kernel's device-clock stamps, no hipEvents between the kernels (the launches then overlap
-                              // with the other batches exactly as in an uninstrumented run: bench.py's replica pass)
-    h->tsets = 0;
-    for (auto* k : h->kids) k->timing = h->timing, k->tsets = 0;
-    // device-clock stamps of the wide threshold kernel (k_threshold.hip): taken while timing is on, accumulators restart with it
-    auto arm = [&](arucohip_handle* x) {
-        x->buf.thr_stamp_on = on != 0 && x->buf.thr_stamps && x->buf.thr_acc;
-        if (on && x->buf.thr_acc) {
-            hipSetDevice(x->device);
-            (void)hipStreamSynchronize(x->stream);
-            (void)hipMemset(x->buf.thr_acc, 0, 2 * sizeof(uint64_t));
-        }
-    };
-    arm(h);
-    for (auto* k : h->kids) arm(k);
-    for (auto* l : h->lanes) arucohip_enable_timing(l, on);
+    // on == 2: only the threshold kernel's device-clock stamps, no hipEvents between the kernels (the launches then overlap with the other
+    // batches exactly as in an uninstrumented run: bench.py's replica pass)
+    for_each_worker(h, [&](arucohip_handle* w) {
+        w->timing = on == 1, w->tsets = 0;
+        arm_stamps(w, on != 0);
+        return ARUCOHIP_OK;
+    });
     return ARUCOHIP_OK;
 }
 // synchronises the stream and averages the per-kernel event intervals of the batches since enable/reset
@@ -586,23 +646,17 @@ static void collect_times(arucohip_handle* h) {
     for (int k = 0; k < K_COUNT; k++) h->kernel_ms[k] = 0;
     hipSetDevice(h->device);
     int total = 0;
-    auto add = [&](arucohip_handle* w) {
-        int n = std::min(w->tsets, TSETS);
-        if (n <= 0) return;
-        if (hipStreamSynchronize(w->stream) != hipSuccess) return;
+    for_each_worker(h, [&](arucohip_handle* w) {
+        const int n = std::min(w->tsets, TSETS);
+        if (n <= 0 || hipStreamSynchronize(w->stream) != hipSuccess) return ARUCOHIP_OK;
         for (int s = 0; s < n; s++)
             for (int k = 0; k < K_COUNT; k++) {
                 float ms = 0;
                 if (hipEventElapsedTime(&ms, w->ev[s][k], w->ev[s][k + 1]) == hipSuccess) h->kernel_ms[k] += ms;
             }
         total += n;
-    };
-    add(h);
-    for (auto* k : h->kids) add(k);
-    for (auto* l : h->lanes) {
-        add(l);
-        for (auto* k : l->kids) add(k);
-    }
+        return ARUCOHIP_OK;
+    });
     if (total > 0)
         for (int k = 0; k < K_COUNT; k++) h->kernel_ms[k] /= total;
 }
@@ -622,20 +676,14 @@ int arucohip_threshold_exec_ms(arucohip_handle* h, double* total_ms, int* launch
     int khz = 0;
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, h->device) != hipSuccess || khz <= 0) return fail(h, ARUCOHIP_E_HIP, "no wall clock rate");
     unsigned long long ticks = 0, n = 0;
-    auto add = [&](arucohip_handle* w) -> int {
+    const int rc = for_each_worker(h, [&](arucohip_handle* w) {
         if (!w->buf.thr_acc) return ARUCOHIP_OK;
         unsigned long long v[2] = {0, 0};
         HIPCHK(h, hipStreamSynchronize(w->stream));
         HIPCHK(h, hipMemcpy(v, w->buf.thr_acc, sizeof(v), hipMemcpyDeviceToHost));
         ticks += v[0], n += v[1];
         return ARUCOHIP_OK;
-    };
-    int rc = add(h);
-    for (auto* k : h->kids) if (rc == ARUCOHIP_OK) rc = add(k);
-    for (auto* l : h->lanes) {
-        if (rc == ARUCOHIP_OK) rc = add(l);
-        for (auto* k : l->kids) if (rc == ARUCOHIP_OK) rc = add(k);
-    }
+    });
     if (rc != ARUCOHIP_OK) return rc;
     *total_ms = (double)ticks / (double)khz, *launches = (int)n;
     return ARUCOHIP_OK;
@@ -685,10 +733,11 @@ static int make_detect_params(arucohip_handle* h, int W, int H, DetectParams* dp
     dp->locked = p.use_locked_corners != 0, dp->locked_wsize = (int)p.thres_param1;   // findCornerMaxima(Corners, grey, _thresParam1)
     dp->decoder = p.decoder_kind;
     if (p.decoder_kind == ARUCOHIP_DECODER_HRM) {
-        if (!h->d_hrm || h->hrm_count <= 0) return fail(h, ARUCOHIP_E_INVALID, "decoder HRM without a dictionary (arucohip_set_dictionary)");
-        if (p.warp_size < 2 * (h->hrm_n + 2)) return fail(h, ARUCOHIP_E_INVALID, "warp size too small for the dictionary's markers");
-        dp->hrm_n = h->hrm_n, dp->hrm_count = h->hrm_count, dp->hrm_codes = h->d_hrm;
-        dp->hrm_correction = (uint32_t)(h->hrm_rate * (float)((h->hrm_tau0 - 1) / 2));   // highlyreliablemarkers.cpp:318
+        const Dictionary& d = h->hrm;
+        if (!h->d_hrm || d.count <= 0) return fail(h, ARUCOHIP_E_INVALID, "decoder HRM without a dictionary (arucohip_set_dictionary)");
+        if (p.warp_size < 2 * (d.n + 2)) return fail(h, ARUCOHIP_E_INVALID, "warp size too small for the dictionary's markers");
+        dp->hrm_n = d.n, dp->hrm_count = d.count, dp->hrm_codes = h->d_hrm;
+        dp->hrm_correction = (uint32_t)(d.rate * (float)((d.tau0 - 1) / 2));   // highlyreliablemarkers.cpp:318
     }
     if (p.decoder_kind == ARUCOHIP_DECODER_USER && !h->decoder_fn)
         return fail(h, ARUCOHIP_E_INVALID, "decoder USER without a callback (arucohip_set_decoder_callback)");
@@ -904,9 +953,6 @@ static int detect_core(arucohip_handle* h, const uint8_t* gray_dev, const FrameG
 #undef MARK
     if (tm) h->tsets++;
     HIPCHK(h, hipGetLastError());
-    h->last_w = g.width, h->last_h = g.height, h->last_frames = nframes, h->last_nthr = dp.nthr;
-    h->last_gray = gray_dev, h->last_geom = g;
-    h->board_frames = 0;
     return ARUCOHIP_OK;
 }
 
@@ -1008,32 +1054,30 @@ static int chunk_collect_host(arucohip_handle* h, arucohip_handle* w, int nframe
     return ret;
 }
 
-// fork: the workers' streams wait for what the caller's stream has queued so far
-static int fork_workers(arucohip_handle* h, int chunks) {
-    if (chunks <= 1) return ARUCOHIP_OK;
-    HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
-    for (int c = 1; c < chunks; c++) HIPCHK(h, hipStreamWaitEvent(h->kids[c - 1]->stream, h->ev_fork, 0));
+// fork: the other workers' streams wait for what the first worker's stream (the batch's own) has queued so far; errors are reported on h
+static int fork_workers(arucohip_handle* h, const Batch& b) {
+    if (b.nspan <= 1) return ARUCOHIP_OK;
+    arucohip_handle* o = b.span[0].w;
+    HIPCHK(h, hipEventRecord(o->ev_fork, o->stream));
+    for (int c = 1; c < b.nspan; c++) HIPCHK(h, hipStreamWaitEvent(b.span[c].w->stream, o->ev_fork, 0));
     return ARUCOHIP_OK;
 }
-// join: the caller's stream waits for the workers
-static int join_workers(arucohip_handle* h, int chunks) {
-    for (int c = 1; c < chunks; c++) {
-        HIPCHK(h, hipEventRecord(h->ev_join[c - 1], h->kids[c - 1]->stream));
-        HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join[c - 1], 0));
+// join: the first worker's stream waits for the others
+static int join_workers(arucohip_handle* h, const Batch& b) {
+    arucohip_handle* o = b.span[0].w;
+    for (int c = 1; c < b.nspan; c++) {
+        HIPCHK(h, hipEventRecord(o->ev_join[c - 1], b.span[c].w->stream));
+        HIPCHK(h, hipStreamWaitEvent(o->stream, o->ev_join[c - 1], 0));
     }
     return ARUCOHIP_OK;
 }
 
-// the batch's stream has been filled: wait for it and copy every chunk's markers from the pinned staging to the caller
-static int collect_batch_host(arucohip_handle* h, int nframes, arucohip_marker_t* out, int cap, int32_t* n_out) {
+// h's last batch has been enqueued on h's stream: wait for it and copy every chunk's markers from the pinned staging to the caller
+static int collect_batch_host(arucohip_handle* h, arucohip_marker_t* out, int cap, int32_t* n_out) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    const int chunks = std::max(h->last_chunks, 1), per = chunks > 1 ? h->last_per : nframes;
     int ret = ARUCOHIP_OK;
-    for (int c = 0; c < chunks; c++) {
-        arucohip_handle* w = c == 0 ? h : h->kids[c - 1];
-        const int off = c * per, cnt = std::min(per, nframes - off);
-        if (cnt <= 0) break;
-        int r = chunk_collect_host(h, w, cnt, out + (size_t)off * cap, cap, n_out + off);
+    for (const Span& s : h->last) {
+        int r = chunk_collect_host(h, s.w, s.count, out + (size_t)s.first * cap, cap, n_out + s.first);
         if (ret == ARUCOHIP_OK) ret = r;
     }
     return ret;
@@ -1073,7 +1117,6 @@ static int detect_one_graphed(arucohip_handle* h, const uint8_t* frame, int W, i
     FrameGeom g;
     if ((rc = stage_frames(h, frame, 1, W, H, row_stride, (size_t)H * row_stride, 0, channels, &gray_dev, &g))) return rc;   // H2D (+ BGR conversion), eager
     if ((rc = batch_prologue(h, g, 1, dp))) return rc;   // also restores the bit-image geometry on the stream, ahead of the launch
-    h->last_chunks = 1, h->last_per = 1, h->board_frames = 0;
     if (h->fgraph.exec && h->fgraph.epoch != h->alloc_epoch) {   // a buffer was replaced since the capture: start over, like a new configuration
         (void)hipGraphExecDestroy(h->fgraph.exec);
         h->fgraph.exec = nullptr, h->fgraph.seen = key;
@@ -1108,11 +1151,11 @@ static int detect_one_graphed(arucohip_handle* h, const uint8_t* frame, int W, i
     *handled = true;
     HIPCHK(h, hipGraphLaunch(h->fgraph.exec, h->stream));
     h->thres_bytes = h->fgraph.thres_bytes;
-    h->last_w = W, h->last_h = H, h->last_frames = 1, h->last_nthr = dp.nthr, h->last_gray = gray_dev, h->last_geom = g;
+    h->last = plan_batch(h, 1, W, H, dp.nthr);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const int32_t* hdr = (const int32_t*)(h->h_markers + h->buf.cap_markers);
     h->h_n[0] = hdr[0], h->h_counters[CNT_STATUS] = (uint32_t)hdr[1];
-    return collect_batch_host(h, 1, out, cap, n_out);
+    return collect_batch_host(h, out, cap, n_out);
 }
 
 static int detect_batch_impl(arucohip_handle* h, const uint8_t* frames, int nframes, int W, int H, size_t row_stride, size_t frame_stride,
@@ -1131,36 +1174,32 @@ static int detect_batch_impl(arucohip_handle* h, const uint8_t* frames, int nfra
         rc = detect_one_graphed(h, frames, W, H, row_stride, channels, dp, cam, out, cap, n_out, &handled);
         if (handled) return rc;
     }
-    // chunks of equal size, as few as the workers' buffers allow but one per worker when the batch is large enough to share
-    int chunks = (nframes + h->cap_frames - 1) / h->cap_frames;
-    if (h->nsub > 1 && (size_t)nframes * W * H >= (size_t)h->nsub * 32 * 1024 * 1024) chunks = std::max(chunks, std::min(h->nsub, nframes));
-    const int per = (nframes + chunks - 1) / chunks;
-    chunks = (nframes + per - 1) / per;
-    h->last_chunks = chunks, h->last_per = per, h->board_frames = 0;
-    if ((rc = fork_workers(h, chunks))) return rc;
-    for (int c = 0; c < chunks; c++) {
-        arucohip_handle* w = c == 0 ? h : h->kids[c - 1];
-        const int off = c * per, cnt = std::min(per, nframes - off);
+    h->last = plan_batch(h, nframes, W, H, dp.nthr);
+    const Batch& plan = h->last;
+    if ((rc = fork_workers(h, plan))) return rc;
+    for (int c = 0; c < plan.nspan; c++) {
+        const Span& s = plan.span[c];
         // optional stagger (ARUCOHIP_CHAIN=1): the bandwidth-bound threshold kernels of the chunks run one after the other,
         // so that chunk c's threshold overlaps the latency-bound border following / decoding of chunk c-1. Helps with 4
         // streams on some boxes and hurts on others, hence off by default.
         const bool chain = h->buf.tune.chain != 0;
-        w->wait_thr = (chain && c > 0) ? (c == 1 ? h : h->kids[c - 2])->ev_thr : nullptr;
-        rc = chunk_enqueue(w, frames + (size_t)off * frame_stride, cnt, W, H, row_stride, frame_stride, frames_on_device, channels, dp, cam,
-                           out ? out + (size_t)off * cap : nullptr, cap, n_out + off, out_on_device);
+        s.w->wait_thr = (chain && c > 0) ? plan.span[c - 1].w->ev_thr : nullptr;
+        rc = chunk_enqueue(s.w, frames + (size_t)s.first * frame_stride, s.count, W, H, row_stride, frame_stride, frames_on_device, channels, dp, cam,
+                           out ? out + (size_t)s.first * cap : nullptr, cap, n_out + s.first, out_on_device);
         if (rc) {
-            if (w != h) h->err = w->err;
+            if (s.w != h) h->err = s.w->err;
             // the workers that already have queued work still have to rejoin the caller's stream
             const std::string keep = h->err;
-            (void)join_workers(h, chunks);
-            for (int k = 0; k < chunks; k++) (k == 0 ? h : h->kids[k - 1])->wait_thr = nullptr;
+            (void)join_workers(h, plan);
+            for (const Span& x : plan) x.w->wait_thr = nullptr;
             h->err = keep;
+            h->last = Batch{};   // the lists hold part of a batch
             return rc;
         }
     }
-    if ((rc = join_workers(h, chunks))) return rc;
+    if ((rc = join_workers(h, plan))) return rc;
     if (out_on_device || defer) return ARUCOHIP_OK;
-    return collect_batch_host(h, nframes, out, cap, n_out);
+    return collect_batch_host(h, out, cap, n_out);
 }
 
 int arucohip_detect_batch(arucohip_handle* h, const uint8_t* frames, int nframes, int W, int H, size_t row_stride, size_t frame_stride,
@@ -1247,37 +1286,24 @@ int arucohip_undistort(arucohip_handle* h, const uint8_t* src, int nframes, int 
 
 int arucohip_set_dictionary(arucohip_handle* h, int n, int count, const uint64_t* codes, int tau0, float correction_rate) {
     if (!h) return ARUCOHIP_E_INVALID;
-    drop_retry(h);
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->hrm_count = 0, h->hrm_n = 0;
+    Dictionary d;
     if (count > 0) {
         if (!codes || n < 2 || n > 8 || count > 4096) return fail(h, ARUCOHIP_E_UNSUPPORTED, "dictionary: 2 <= n <= 8, count <= 4096");
-        HIPCHK(h, h->d_hrm.reserve((size_t)count * sizeof(uint64_t), h->alloc_epoch));
-        HIPCHK(h, hipMemcpy(h->d_hrm, codes, (size_t)count * sizeof(uint64_t), hipMemcpyHostToDevice));
-        h->hrm_n = n, h->hrm_count = count, h->hrm_tau0 = tau0, h->hrm_rate = correction_rate;
+        d.n = n, d.count = count, d.tau0 = tau0, d.rate = correction_rate, d.codes.assign(codes, codes + count);
     }
-    for (auto* k : h->kids) {
-        int rc = arucohip_set_dictionary(k, n, count, codes, tau0, correction_rate);
-        if (rc) return rc;
-    }
-    for (auto* l : h->lanes) {
-        int rc = arucohip_set_dictionary(l, n, count, codes, tau0, correction_rate);
-        if (rc) return rc;
-    }
-    return ARUCOHIP_OK;
+    drop_retry(h);
+    HIPCHK(h, hipSetDevice(h->device));
+    return for_each_worker(h, [&](arucohip_handle* w) { return load_dictionary(h, w, d); });
 }
 
 int arucohip_set_decoder_callback(arucohip_handle* h, arucohip_decoder_fn fn, void* user) {
     if (!h) return ARUCOHIP_E_INVALID;
     drop_retry(h);
-    h->decoder_fn = fn, h->decoder_user = user;
-    for (auto* k : h->kids) k->decoder_fn = fn, k->decoder_user = user;
-    for (auto* l : h->lanes) arucohip_set_decoder_callback(l, fn, user);
-    if (!fn && h->params.decoder_kind == ARUCOHIP_DECODER_USER) {
-        h->params.decoder_kind = ARUCOHIP_DECODER_FIDUCIAL_5X5;
-        for (auto* k : h->kids) k->params.decoder_kind = ARUCOHIP_DECODER_FIDUCIAL_5X5;
-    }
+    for_each_worker(h, [&](arucohip_handle* w) {
+        w->decoder_fn = fn, w->decoder_user = user;
+        if (!fn && w->params.decoder_kind == ARUCOHIP_DECODER_USER) w->params.decoder_kind = ARUCOHIP_DECODER_FIDUCIAL_5X5;
+        return ARUCOHIP_OK;
+    });
     return ARUCOHIP_OK;
 }
 
@@ -1285,8 +1311,8 @@ int arucohip_batch_status(arucohip_handle* h) {
     if (!h) return ARUCOHIP_E_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
     uint32_t st = 0;
-    for (int c = 0; c < std::max(h->last_chunks, 1); c++) {
-        arucohip_handle* w = c == 0 ? h : h->kids[c - 1];
+    for (const Span& s : h->last) {
+        arucohip_handle* w = s.w;
         HIPCHK(h, hipMemcpyAsync(w->h_counters, w->buf.counters, CNT_FIXED * sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
         HIPCHK(h, hipStreamSynchronize(w->stream));
         st |= w->h_counters[CNT_STATUS];
@@ -1297,9 +1323,8 @@ int arucohip_batch_status(arucohip_handle* h) {
 
 int arucohip_batch_chunks(arucohip_handle* h, int* frames_per_chunk) {
     if (!h) return 0;
-    h = active(h);
-    if (frames_per_chunk) *frames_per_chunk = h->last_chunks > 1 ? h->last_per : h->last_frames;
-    return std::max(h->last_chunks, 1);
+    if (frames_per_chunk) *frames_per_chunk = h->last.nspan ? h->last.span[0].count : 0;
+    return std::max(h->last.nspan, 1);
 }
 
 int arucohip_detect(arucohip_handle* h, const uint8_t* gray, int W, int H, size_t row_stride, const float* K, const float* dist, int ndist,
@@ -1311,16 +1336,16 @@ int arucohip_detect(arucohip_handle* h, const uint8_t* gray, int W, int H, size_
 }
 
 int arucohip_get_thresholded(arucohip_handle* h0, int frame, uint8_t* dst) {
-    if (!h0 || !dst || frame < 0) return ARUCOHIP_E_INVALID;
-    h0 = active(h0);
-    arucohip_handle* h = route(h0, frame, &frame);
-    if (frame >= h->last_frames) return ARUCOHIP_E_INVALID;
+    if (!h0 || !dst) return ARUCOHIP_E_INVALID;
+    const Batch& r = h0->last;
+    arucohip_handle* h = r.holder(frame, &frame);
+    if (!h) return ARUCOHIP_E_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
-    size_t px = (size_t)h->last_w * h->last_h;
-    int plane = frame * h->last_nthr + h->last_nthr / 2;   // thres = thres_images[n_param1 / 2]
+    size_t px = (size_t)r.W * r.H;
+    int plane = frame * r.nthr + r.nthr / 2;   // thres = thres_images[n_param1 / 2]
     if (!h->thres_bytes) {   // the batch kept the image as tiles + border lines: rebuild this plane's bytes
         FrameGeom g;
-        g.width = h->last_w, g.height = h->last_h, g.row_stride = (size_t)h->last_w, g.frame_stride = px;
+        g.width = r.W, g.height = r.H, g.row_stride = (size_t)r.W, g.frame_stride = px;
         launch_expand_thres(h->stream, g, plane, h->buf);
         HIPCHK(h, hipGetLastError());
     }
@@ -1330,10 +1355,9 @@ int arucohip_get_thresholded(arucohip_handle* h0, int frame, uint8_t* dst) {
 }
 
 static int fetch_cands(arucohip_handle* h0, int frame, std::vector<Cand>* v) {
-    if (!h0 || frame < 0) return ARUCOHIP_E_INVALID;
-    h0 = active(h0);
-    arucohip_handle* h = route(h0, frame, &frame);
-    if (frame >= h->last_frames) return ARUCOHIP_E_INVALID;
+    if (!h0) return ARUCOHIP_E_INVALID;
+    arucohip_handle* h = h0->last.holder(frame, &frame);
+    if (!h) return ARUCOHIP_E_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
     int32_t n = 0;
     HIPCHK(h, hipMemcpyAsync(&n, h->buf.ncands + frame, sizeof(n), hipMemcpyDeviceToHost, h->stream));
@@ -1363,10 +1387,9 @@ int arucohip_get_candidates(arucohip_handle* h, int frame, float* quads, int cap
 
 // Otsu threshold of every candidate of a frame (candidate order of arucohip_debug_candidates): what otsu_kernel left in the flat list's threshold slots
 int arucohip_debug_otsu(arucohip_handle* h0, int frame, int32_t* thr, int cap, int* n) {
-    if (!h0 || frame < 0 || !thr || !n) return ARUCOHIP_E_INVALID;
-    h0 = active(h0);
-    arucohip_handle* h = route(h0, frame, &frame);
-    if (frame >= h->last_frames) return ARUCOHIP_E_INVALID;
+    if (!h0 || !thr || !n) return ARUCOHIP_E_INVALID;
+    arucohip_handle* h = h0->last.holder(frame, &frame);
+    if (!h) return ARUCOHIP_E_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
     uint32_t cnt[CNT_FIXED];
     int32_t nc = 0;
@@ -1407,16 +1430,16 @@ int arucohip_debug_candidates(arucohip_handle* h, int frame, float* quads0, int3
 
 // contours of one frame in reference (RETR_LIST) order: planes ascending, raster key descending
 static int fetch_contours(arucohip_handle* h0, int frame, std::vector<ContourDesc>* out, arucohip_handle** owner = nullptr) {
-    if (!h0 || frame < 0) return ARUCOHIP_E_INVALID;
-    h0 = active(h0);
-    arucohip_handle* h = route(h0, frame, &frame);
+    if (!h0) return ARUCOHIP_E_INVALID;
+    const int nthr = h0->last.nthr;
+    arucohip_handle* h = h0->last.holder(frame, &frame);
+    if (!h) return ARUCOHIP_E_INVALID;
     if (owner) *owner = h;
-    if (frame >= h->last_frames) return ARUCOHIP_E_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
     // the frame's planes are consecutive; every plane owns cap_cdesc descriptor slots
     std::vector<ContourDesc> all;
-    for (int t = 0; t < h->last_nthr; t++) {
-        const int plane = frame * h->last_nthr + t;
+    for (int t = 0; t < nthr; t++) {
+        const int plane = frame * nthr + t;
         uint32_t n = 0;
         HIPCHK(h, hipMemcpyAsync(&n, h->buf.trig_cnt + (size_t)plane * TRIG_CNT_STRIDE + TC_CDESC, sizeof(n), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1467,15 +1490,15 @@ int arucohip_debug_contour(arucohip_handle* h0, int frame, int index, int* is_ho
 
 int arucohip_debug_counters(arucohip_handle* h, uint32_t* out8) {
     if (!h || !out8) return ARUCOHIP_E_INVALID;
-    h = active(h);
     HIPCHK(h, hipSetDevice(h->device));
+    const Batch& r = h->last;
     uint64_t acc[CNT_FIXED] = {};
     uint64_t ntrig = 0, nraw = 0, nlong = 0;
-    for (int c = 0; c < std::max(h->last_chunks, 1); c++) {
-        arucohip_handle* w = c == 0 ? h : h->kids[c - 1];
+    for (const Span& s : r) {
+        arucohip_handle* w = s.w;
         uint32_t cnt[CNT_FIXED];
         HIPCHK(h, hipMemcpyAsync(cnt, w->buf.counters, sizeof(cnt), hipMemcpyDeviceToHost, w->stream));
-        int planes = std::max(w->last_frames * w->last_nthr, 1);
+        const int planes = s.count * r.nthr;
         std::vector<uint32_t> tc((size_t)planes * TRIG_CNT_STRIDE), rc_((size_t)planes * TRIG_CNT_STRIDE), rg((size_t)planes * TRIG_CNT_STRIDE);
         HIPCHK(h, hipMemcpyAsync(tc.data(), w->buf.trig_cnt, tc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
         HIPCHK(h, hipMemcpyAsync(rc_.data(), w->buf.raw_cnt, rc_.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
@@ -1492,7 +1515,8 @@ int arucohip_debug_counters(arucohip_handle* h, uint32_t* out8) {
     }
     for (int i = 0; i < CNT_FIXED; i++) out8[i] = (uint32_t)std::min<uint64_t>(acc[i], 0xFFFFFFFFu);
     out8[0] = (uint32_t)std::min<uint64_t>(ntrig, 0xFFFFFFFFu);   // start candidates after the run rule (all planes)
-    out8[4] = (uint32_t)std::min<uint64_t>(h->buf.seg_mode ? nraw : nlong, 0xFFFFFFFFu);   // waypoint records (segment mode) / long walks = checkpoint rings handed out
+    const bool seg = r.nspan > 0 && r.span[0].w->buf.seg_mode;
+    out8[4] = (uint32_t)std::min<uint64_t>(seg ? nraw : nlong, 0xFFFFFFFFu);   // waypoint records (segment mode) / long walks = checkpoint rings handed out
     return ARUCOHIP_OK;
 }
 
@@ -1523,7 +1547,7 @@ int arucohip_threshold(arucohip_handle* h, int method, const uint8_t* gray, int 
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(dst, h->buf.thres, (size_t)W * H, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->last_w = W, h->last_h = H, h->last_frames = 1, h->last_nthr = 1, h->last_chunks = 1, h->board_frames = 0;
+    h->last = plan_batch(h, 1, W, H, 1);
     return ARUCOHIP_OK;
 }
 
@@ -1547,7 +1571,7 @@ int arucohip_detect_rectangles(arucohip_handle* h, const uint8_t* thres, int W, 
     launch_binary_planes(h->stream, dev, g, 1, h->buf);
     run_rectangles(h, g, 1, dp);
     HIPCHK(h, hipGetLastError());
-    h->last_w = W, h->last_h = H, h->last_frames = 1, h->last_nthr = 1, h->last_chunks = 1, h->board_frames = 0;
+    h->last = plan_batch(h, 1, W, H, 1);
     std::vector<Cand> v;
     if ((rc = fetch_cands(h, 0, &v))) return rc;
     HIPCHK(h, hipMemcpy(h->h_counters, h->buf.counters, CNT_FIXED * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -1619,7 +1643,7 @@ int arucohip_refine_candidate_lines(arucohip_handle* h, const int32_t* contour_x
     HIPCHK(h, hipMemcpyAsync(&c, b.cands, sizeof(c), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
     for (int k = 0; k < 8; k++) corners[k] = c.c[k];
-    h->last_frames = 0, h->board_frames = 0;   // the lists no longer hold a batch
+    h->last = Batch{};   // the lists no longer hold a batch
     return ARUCOHIP_OK;
 }
 
@@ -1627,11 +1651,7 @@ int arucohip_board_detect_batch(arucohip_handle* h, int nframes, const int32_t* 
                                 const float* dist, int ndist, float marker_size, float repj_err_thres, int y_perp, arucohip_board_t* out, float* prob) {
     if (!h || !out || !prob) return ARUCOHIP_E_INVALID;
     if (nboard <= 0 || !ids || !obj) return fail(h, ARUCOHIP_E_BOARD_CONFIG, "invalid BoardConfig that is empty");
-    h = active(h);   // with batches in flight: the lane of the last ticket waited for
-    const int chunks = std::max(h->last_chunks, 1), per = chunks > 1 ? h->last_per : h->last_frames;
-    int have = 0;
-    for (int c = 0; c < chunks; c++) have += (c == 0 ? h : h->kids[c - 1])->last_frames;
-    if (nframes < 1 || nframes > have) return fail(h, ARUCOHIP_E_INVALID, "nframes exceeds the last batch");
+    if (nframes < 1 || nframes > h->last.frames) return fail(h, ARUCOHIP_E_INVALID, "nframes exceeds the last batch");
     if (nboard * 12 > 8192) return fail(h, ARUCOHIP_E_CAPACITY, "board with too many markers");
     HIPCHK(h, hipSetDevice(h->device));
     float zeros[4] = {0, 0, 0, 0};
@@ -1640,31 +1660,30 @@ int arucohip_board_detect_batch(arucohip_handle* h, int nframes, const int32_t* 
     int rc = make_cam(h, K, dist, ndist, marker_size, y_perp, &cam);
     if (rc) return rc;
     // every worker solves the boards of the frames it detected, on its own stream
-    if ((rc = fork_workers(h, chunks))) return rc;
-    for (int c = 0; c < chunks; c++) {
-        arucohip_handle* w = c == 0 ? h : h->kids[c - 1];
-        const int off = c * per, cnt = std::min(per, nframes - off);
-        if (cnt <= 0) break;
+    const Batch b = h->last.cut(nframes);
+    if ((rc = fork_workers(h, b))) return rc;
+    for (const Span& s : b) {
+        arucohip_handle* w = s.w;
         HIPCHK(h, w->d_board.reserve((size_t)w->cap_frames * (sizeof(arucohip_board_t) + sizeof(float)) + 8192 * sizeof(int32_t), w->alloc_epoch));
         arucohip_board_t* d_out = w->d_board;
         float* d_prob = (float*)(d_out + w->cap_frames);
         int32_t* d_ids = (int32_t*)(d_prob + w->cap_frames);
         HIPCHK(h, hipMemcpyAsync(d_ids, ids, (size_t)nboard * sizeof(int32_t), hipMemcpyHostToDevice, w->stream));
         HIPCHK(h, hipMemcpyAsync(w->d_small_f, obj, (size_t)nboard * 12 * sizeof(float), hipMemcpyHostToDevice, w->stream));
-        launch_board_pose(w->stream, cnt, w->buf, d_ids, w->d_small_f, nboard, info_type, marker_size, repj_err_thres, cam, d_out, d_prob);
+        launch_board_pose(w->stream, s.count, w->buf, d_ids, w->d_small_f, nboard, info_type, marker_size, repj_err_thres, cam, d_out, d_prob);
         HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(out + off, d_out, (size_t)cnt * sizeof(arucohip_board_t), hipMemcpyDeviceToHost, w->stream));
-        HIPCHK(h, hipMemcpyAsync(prob + off, d_prob, (size_t)cnt * sizeof(float), hipMemcpyDeviceToHost, w->stream));
+        HIPCHK(h, hipMemcpyAsync(out + s.first, d_out, (size_t)s.count * sizeof(arucohip_board_t), hipMemcpyDeviceToHost, w->stream));
+        HIPCHK(h, hipMemcpyAsync(prob + s.first, d_prob, (size_t)s.count * sizeof(float), hipMemcpyDeviceToHost, w->stream));
     }
-    if ((rc = join_workers(h, chunks))) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if ((rc = join_workers(h, b))) return rc;
+    HIPCHK(h, hipStreamSynchronize(b.span[0].w->stream));
     // a frame with more member markers than the kernel's correspondence array holds is reported, not truncated silently
-    for (int c = 0; c < chunks; c++) {
-        arucohip_handle* w = c == 0 ? h : h->kids[c - 1];
+    for (const Span& s : h->last) {
+        arucohip_handle* w = s.w;
         HIPCHK(h, hipMemcpy(w->h_counters, w->buf.counters, CNT_FIXED * sizeof(uint32_t), hipMemcpyDeviceToHost));
         if (w->h_counters[CNT_STATUS] & ST_MARKER_OVERFLOW) return fail(h, ARUCOHIP_E_CAPACITY, "a frame has more than 128 board markers");
     }
-    h->board_frames = nframes;
+    h->last.board_frames = nframes;
     return ARUCOHIP_OK;
 }
 
@@ -1808,42 +1827,37 @@ int arucohip_calibrate_board_batch(arucohip_handle* h, int nframes, const int32_
     if (!h) return ARUCOHIP_E_INVALID;
     if (!K || !dist || W <= 0 || H <= 0) return fail(h, ARUCOHIP_E_INVALID, "calibrate_board_batch: NULL K / dist or an empty image size");
     if (nboard <= 0 || !ids || !obj) return fail(h, ARUCOHIP_E_BOARD_CONFIG, "invalid BoardConfig that is empty");
-    h = active(h);   // with batches in flight: the lane of the last ticket waited for
-    const int chunks = std::max(h->last_chunks, 1), per = chunks > 1 ? h->last_per : h->last_frames;
-    int have = 0;
-    for (int c = 0; c < chunks; c++) have += (c == 0 ? h : h->kids[c - 1])->last_frames;
-    if (nframes < 1 || nframes > have) return fail(h, ARUCOHIP_E_INVALID, "nframes exceeds the last batch");
+    if (nframes < 1 || nframes > h->last.frames) return fail(h, ARUCOHIP_E_INVALID, "nframes exceeds the last batch");
     HIPCHK(h, hipSetDevice(h->device));
+    const Batch b = h->last.cut(nframes);
+    arucohip_handle* o = b.span[0].w;   // the worker of the batch's first chunk: the calibration runs on its stream, in its scratch
     // the metres-per-unit factor of board_pose_kernel for PIX boards (marker side from the first edge of marker 0)
     const float dx = obj[0] - obj[3], dy = obj[1] - obj[4], dz = obj[2] - obj[5];
     const double side = std::sqrt((double)dx * dx + (double)dy * dy + (double)dz * dz);
     const double mpp = (info_type == ARUCOHIP_BOARD_PIX && marker_size > 0) ? (double)marker_size / side : 1.0;
     const CalibCarve c = calib_carve(nframes, (size_t)nframes * CALIB_MAX_POINTS, nframes, nboard);
-    HIPCHK(h, h->d_calib.reserve(c.total, h->alloc_epoch));
-    uint8_t* base = h->d_calib;
+    HIPCHK(h, o->d_calib.reserve(c.total, o->alloc_epoch));
+    uint8_t* base = o->d_calib;
     float* dobj = (float*)(base + c.obj);
     float* dimg = (float*)(base + c.img);
     int32_t* dnpt = (int32_t*)(base + c.npt);
     int32_t* dnmark = (int32_t*)(base + c.nmark);
     int32_t* dids = (int32_t*)(base + c.bids);
     float* dbobj = (float*)(base + c.bobj);
-    HIPCHK(h, hipMemcpyAsync(dids, ids, (size_t)nboard * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(dbobj, obj, (size_t)nboard * 12 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dids, ids, (size_t)nboard * sizeof(int32_t), hipMemcpyHostToDevice, o->stream));
+    HIPCHK(h, hipMemcpyAsync(dbobj, obj, (size_t)nboard * 12 * sizeof(float), hipMemcpyHostToDevice, o->stream));
     // every worker lays out the correspondences of the frames it detected, on its own stream
     int rc;
-    if ((rc = fork_workers(h, chunks))) return rc;
-    for (int ch = 0; ch < chunks; ch++) {
-        arucohip_handle* w = ch == 0 ? h : h->kids[ch - 1];
-        const int first = ch * per, cnt = std::min(per, nframes - first);
-        if (cnt <= 0) break;
-        launch_calib_gather(w->stream, cnt, w->buf, dids, dbobj, nboard, mpp, first, dobj, dimg, dnpt, dnmark);
+    if ((rc = fork_workers(h, b))) return rc;
+    for (const Span& s : b) {
+        launch_calib_gather(s.w->stream, s.count, s.w->buf, dids, dbobj, nboard, mpp, s.first, dobj, dimg, dnpt, dnmark);
         HIPCHK(h, hipGetLastError());
     }
-    if ((rc = join_workers(h, chunks))) return rc;
+    if ((rc = join_workers(h, b))) return rc;
     std::vector<int32_t> fnpt((size_t)nframes), fnmark((size_t)nframes);
-    HIPCHK(h, hipMemcpyAsync(fnpt.data(), dnpt, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(fnmark.data(), dnmark, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpyAsync(fnpt.data(), dnpt, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, o->stream));
+    HIPCHK(h, hipMemcpyAsync(fnmark.data(), dnmark, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, o->stream));
+    HIPCHK(h, hipStreamSynchronize(o->stream));
     std::vector<int32_t> off, npt;
     for (int f = 0; f < nframes; f++) {
         const bool take = fnmark[f] >= std::max(min_markers, 1) && fnpt[f] != 0;
@@ -1855,7 +1869,9 @@ int arucohip_calibrate_board_batch(arucohip_handle* h, int nframes, const int32_
     CalibDev d{};
     d.nviews = (int)off.size(), d.obj = dobj, d.img = dimg;
     // the per-view arrays are carved for nframes >= views; the off / npt arrays are rewritten with the views
-    return calib_solve(h, d, c, off, npt, W, H, flags, K, dist, rvecs, tvecs, nullptr, rms);
+    rc = calib_solve(o, d, c, off, npt, W, H, flags, K, dist, rvecs, tvecs, nullptr, rms);
+    if (rc && o != h) h->err = o->err;
+    return rc;
 }
 
 // ---- board occlusion mask (k_chromatic.hip) ----
@@ -2147,8 +2163,7 @@ int arucohip_chromatic_classify_batch(arucohip_chromatic* m, arucohip_handle* h,
         return fail(mh, ARUCOHIP_E_INVALID, "chromatic_classify_batch: frame size differs from the object's, or strides too small");
     if (method != 1 && method != 2) return fail(mh, ARUCOHIP_E_INVALID, "chromatic_classify_batch: method is 1 (classify) or 2 (classify2)");
     if (h->device != mh->device) return fail(mh, ARUCOHIP_E_INVALID, "chromatic_classify_batch: the handle is on another device");
-    h = active(h);
-    if (h->board_frames != nframes) return fail(mh, ARUCOHIP_E_INVALID, "chromatic_classify_batch: no arucohip_board_detect_batch of nframes frames before");
+    if (h->last.board_frames != nframes) return fail(mh, ARUCOHIP_E_INVALID, "chromatic_classify_batch: no arucohip_board_detect_batch of nframes frames before");
     HIPCHK(mh, hipSetDevice(mh->device));
     hipStream_t s = mh->stream;
     const size_t px = (size_t)W * H;
@@ -2157,15 +2172,10 @@ int arucohip_chromatic_classify_batch(arucohip_chromatic* m, arucohip_handle* h,
         HIPCHK(mh, m->d_npix.reserve((size_t)nframes * sizeof(int32_t), m->epoch));
         HIPCHK(mh, hipMemsetAsync(m->d_npix, 0, (size_t)nframes * sizeof(int32_t), s));
     }
-    // the poses where the board batch left them: worker c holds frames [c * per, c * per + cnt)
-    const int chunks = std::max(h->last_chunks, 1), per = chunks > 1 ? h->last_per : h->last_frames;
-    if ((long long)chunks * per < nframes) return fail(mh, ARUCOHIP_E_INVALID, "chromatic_classify_batch: the last batch holds fewer frames");
-    for (int c = 0; c < chunks; c++) {
-        arucohip_handle* w = c == 0 ? h : h->kids[c - 1];
-        const int first = c * per, cnt = std::min(per, nframes - first);
-        if (cnt <= 0) break;
-        const arucohip_board_t* boards = w->d_board;
-        launch_chroma_geometry(s, m->cam, cnt, boards, (const float*)(boards + w->cap_frames), min_prob, nullptr, nullptr, m->d_bgeom + first);
+    // the poses where the board batch left them: each worker holds its own frames' boards
+    for (const Span& sp : h->last.cut(nframes)) {
+        const arucohip_board_t* boards = sp.w->d_board;
+        launch_chroma_geometry(s, m->cam, sp.count, boards, (const float*)(boards + sp.w->cap_frames), min_prob, nullptr, nullptr, m->d_bgeom + sp.first);
     }
     HIPCHK(mh, hipGetLastError());
     m->last_batch = nframes;
@@ -2197,18 +2207,19 @@ int arucohip_chromatic_classify_batch(arucohip_chromatic* m, arucohip_handle* h,
 // SURVEY §8 row f4, batched: Marker::glGetModelViewMatrix (src/marker.h:90) for every marker of the last batch in one launch
 int arucohip_gl_modelview_batch(arucohip_handle* h, int nframes, int cap, double* modelview, int32_t* n_out) {
     if (!h || !modelview || !n_out || cap < 1) return ARUCOHIP_E_INVALID;
-    h = active(h);
-    if (h->last_chunks > 1) return fail(h, ARUCOHIP_E_UNSUPPORTED, "not available for batches split over chunk streams");
-    if (nframes < 1 || nframes > h->last_frames) return fail(h, ARUCOHIP_E_INVALID, "nframes exceeds the last batch");
+    const Batch& r = h->last;
+    if (r.nspan > 1) return fail(h, ARUCOHIP_E_UNSUPPORTED, "not available for batches split over chunk streams");
+    if (nframes < 1 || nframes > r.frames) return fail(h, ARUCOHIP_E_INVALID, "nframes exceeds the last batch");
+    arucohip_handle* w = r.span[0].w;
     HIPCHK(h, hipSetDevice(h->device));
     const size_t need = (size_t)nframes * cap * 16 * sizeof(double);
-    HIPCHK(h, h->d_gl.reserve(need, h->alloc_epoch));
-    launch_gl_modelview(h->stream, nframes, cap, h->buf, h->d_gl);
+    HIPCHK(h, w->d_gl.reserve(need, w->alloc_epoch));
+    launch_gl_modelview(w->stream, nframes, cap, w->buf, w->d_gl);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(modelview, h->d_gl, need, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(n_out, h->buf.nmarkers, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int f = 0; f < nframes; f++) n_out[f] = std::min(std::min(n_out[f], cap), h->buf.cap_markers);
+    HIPCHK(h, hipMemcpyAsync(modelview, w->d_gl, need, hipMemcpyDeviceToHost, w->stream));
+    HIPCHK(h, hipMemcpyAsync(n_out, w->buf.nmarkers, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, w->stream));
+    HIPCHK(h, hipStreamSynchronize(w->stream));
+    for (int f = 0; f < nframes; f++) n_out[f] = std::min(std::min(n_out[f], cap), w->buf.cap_markers);
     return ARUCOHIP_OK;
 }
 
@@ -2341,30 +2352,19 @@ int arucohip_set_pipeline_depth(arucohip_handle* h, int depth) {
     HIPCHK(h, hipSetDevice(h->device));
     for (auto* l : h->lanes) arucohip_destroy(l);
     h->lanes.clear();
-    h->cur = nullptr, h->next_ticket = 0;
+    if (h->last.nspan && h->last.span[0].w != h) h->last = Batch{};   // it was a lane's
+    h->next_ticket = 0;
     if (depth == 0) return ARUCOHIP_OK;
     if (!h->ev_submit) HIPCHK(h, hipEventCreateWithFlags(&h->ev_submit, hipEventDisableTiming));
     for (int i = 0; i < depth; i++) {
         arucohip_handle* l = nullptr;
-        int rc = arucohip_create_ex(&h->params, h->device, &h->lim, &l);
+        const int rc = create_child(h, h->lim, false, &l);
         if (rc != ARUCOHIP_OK) {   // all or nothing: a later submit must not run at a smaller depth than the caller asked for
             for (auto* made : h->lanes) arucohip_destroy(made);
             h->lanes.clear();
             return fail(h, rc, "creating a pipeline lane failed (no lanes kept)");
         }
-        l->decoder_fn = h->decoder_fn, l->decoder_user = h->decoder_user;
-        for (auto* k : l->kids) k->decoder_fn = h->decoder_fn, k->decoder_user = h->decoder_user;
-        l->timing = h->timing;
         h->lanes.push_back(l);
-        if (h->d_hrm && h->hrm_count > 0) {
-            std::vector<uint64_t> codes(h->hrm_count);
-            HIPCHK(h, hipMemcpy(codes.data(), h->d_hrm, codes.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-            if ((rc = arucohip_set_dictionary(l, h->hrm_n, h->hrm_count, codes.data(), h->hrm_tau0, h->hrm_rate))) {
-                for (auto* made : h->lanes) arucohip_destroy(made);
-                h->lanes.clear();
-                return rc;
-            }
-        }
     }
     return ARUCOHIP_OK;
 }
@@ -2386,7 +2386,7 @@ int arucohip_detect_batch_submit(arucohip_handle* h, const uint8_t* frames, int 
         h->err = l->err;
         return rc;
     }
-    l->pend.active = true, l->pend.ticket = h->next_ticket, l->pend.nframes = nframes, l->pend.cap = cap, l->pend.out_on_device = out_on_device;
+    l->pend.active = true, l->pend.ticket = h->next_ticket, l->pend.cap = cap, l->pend.out_on_device = out_on_device;
     l->pend.out = out, l->pend.n_out = n_out;
     *ticket = h->next_ticket++;
     return ARUCOHIP_OK;
@@ -2417,25 +2417,17 @@ int arucohip_detect_batch_retry_overflowed(arucohip_handle* h, const uint8_t* fr
             const int want = h->retry ? std::min(64, attempt == 0 ? h->retry_mult : h->retry_mult * 4) : 4;
             if (attempt > 0 && h->retry && want == h->retry_mult) break;   // already at the cap
             if (!h->retry || want != h->retry_mult) {
-                if (h->retry) arucohip_destroy(h->retry);
-                h->retry = nullptr;
+                drop_retry(h);
                 arucohip_limits_t l = h->lim;
                 l.max_batch = 1;
                 auto grow = [&](int32_t v, long top) { return (int32_t)std::min<long>((long)v * want, top); };
                 l.triggers_per_frame = grow(l.triggers_per_frame, 1L << 22), l.contours_per_frame = grow(l.contours_per_frame, 1L << 18);
                 l.points_per_frame = grow(l.points_per_frame, 1L << 24), l.long_walks_per_plane = grow(l.long_walks_per_plane, 1L << 16);
                 l.candidates_per_frame = std::min(512, l.candidates_per_frame * 2);
-                int crc = arucohip_create_ex(&h->params, h->device, &l, &h->retry);
+                const int crc = create_child(h, l, false, &h->retry);
                 if (crc != ARUCOHIP_OK) return fail(h, crc, "creating the retry handle failed");
                 h->retry_mult = want;
-                h->retry->decoder_fn = h->decoder_fn, h->retry->decoder_user = h->decoder_user;
-                if (h->d_hrm && h->hrm_count > 0) {
-                    std::vector<uint64_t> codes(h->hrm_count);
-                    HIPCHK(h, hipMemcpy(codes.data(), h->d_hrm, codes.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-                    if ((crc = arucohip_set_dictionary(h->retry, h->hrm_n, h->hrm_count, codes.data(), h->hrm_tau0, h->hrm_rate))) return crc;
-                }
             }
-            h->retry->params = h->params;
             rc = arucohip_detect_batch(h->retry, frames + (size_t)f * frame_stride, 1, W, H, row_stride, frame_stride, frames_on_device, K, dist, ndist, marker_size,
                                        y_perp, tmp.data(), cap, &got, 0);
         }
@@ -2462,9 +2454,9 @@ int arucohip_detect_batch_wait(arucohip_handle* h, int ticket) {
     arucohip_handle* l = h->lanes[ticket % (int)h->lanes.size()];
     if (!l->pend.active || l->pend.ticket != ticket) return fail(h, ARUCOHIP_E_INVALID, "no such batch in flight");
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = l->pend.out_on_device ? arucohip_batch_status(l) : collect_batch_host(l, l->pend.nframes, l->pend.out, l->pend.cap, l->pend.n_out);
+    int rc = l->pend.out_on_device ? arucohip_batch_status(l) : collect_batch_host(l, l->pend.out, l->pend.cap, l->pend.n_out);
     l->pend.active = false;
-    h->cur = l;
+    h->last = l->last;
     if (rc) h->err = l->err;
     return rc;
 }

@@ -245,8 +245,8 @@ int arucohip_batch_chunks(arucohip_handle* h, int* frames_per_chunk);
  * far and returns at once; arucohip_detect_batch_wait(ticket) returns when that batch is complete (its status code: overflow /
  * capacity conditions as arucohip_detect_batch / arucohip_batch_status would report them), host outputs are filled then.
  * At most `depth` tickets can be outstanding (ARUCOHIP_E_CAPACITY otherwise); getters and arucohip_board_detect_batch
- * address the batch of the last ticket waited for. Input frames and output arrays of a ticket must stay untouched until
- * its wait returns. */
+ * address the batch that finished last, a synchronous call's or the last ticket waited for. Input frames and output
+ * arrays of a ticket must stay untouched until its wait returns. */
 int arucohip_set_pipeline_depth(arucohip_handle* h, int depth);
 int arucohip_detect_batch_submit(arucohip_handle* h, const uint8_t* frames, int nframes, int width, int height, size_t row_stride,
                                  size_t frame_stride, int frames_on_device, const float* K, const float* dist, int ndist,

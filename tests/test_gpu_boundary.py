@@ -378,6 +378,96 @@ def test_batches_in_flight_equal_synchronous_batches(env):
         h.close()
 
 
+def test_synchronous_batch_after_a_waited_ticket_is_the_last_batch(env):
+    """Depth 2, one ticket submitted and waited for, then a synchronous batch of other frames on the same handle: the getters and the
+    batched board pose address the synchronous batch, the one that finished last, exactly as on a handle without lanes."""
+    capi = env["capi"]
+    _, doc = load_case("board")
+    bc = doc["board_conf"]
+    K = np.array([[1700.0, 0, 955.0], [0, 1690.0, 545.0], [0, 0, 1]], np.float32)
+    frames, _ = env["synth"].make_board_stream(8, bc["ids"], bc["obj"], K.reshape(-1), width=1920, height=1080, seed=31, device="cuda")
+    fr = frames.cpu().numpy()
+    h = capi.Handle(1920, 1080, max_batch=4)
+    ref = capi.Handle(1920, 1080, max_batch=4)
+    try:
+        h.set_pipeline_depth(2)
+        out, n = np.zeros((4, 64), capi.MARKER_DTYPE), np.zeros(4, np.int32)
+        h.wait(h.submit_host(np.ascontiguousarray(fr[0:4]), out, n, K=K, dist=[0.0] * 5, marker_size=0.039))
+        got = h.detect_batch_host(fr[4:8], K=K, dist=[0.0] * 5, marker_size=0.039)
+        want = ref.detect_batch_host(fr[4:8], K=K, dist=[0.0] * 5, marker_size=0.039)
+        for f in range(4):
+            assert got[f].tobytes() == want[f].tobytes()
+            assert np.array_equal(h.thresholded(f, (1080, 1920)), ref.thresholded(f, (1080, 1920)))
+            ca, cb = h.debug_contours(f), ref.debug_contours(f)
+            assert len(ca) == len(cb) and all(np.array_equal(x["pts"], y["pts"]) for x, y in zip(ca, cb))
+        ba = h.board_detect_batch(4, bc["ids"], bc["obj"], bc["info_type"], K=K, dist=[0.0] * 5, marker_size=0.039)
+        bb = ref.board_detect_batch(4, bc["ids"], bc["obj"], bc["info_type"], K=K, dist=[0.0] * 5, marker_size=0.039)
+        assert sum(a["has_pose"] for a in ba) >= 2
+        for a, b in zip(ba, bb):
+            assert a["n_markers"] == b["n_markers"] and a["has_pose"] == b["has_pose"] and a["prob"] == b["prob"]
+            assert np.array_equal(a["rvec"], b["rvec"]) and np.array_equal(a["tvec"], b["tvec"])
+    finally:
+        h.close()
+        ref.close()
+
+
+def test_lanes_take_settings_made_before_and_after_the_depth(env, monkeypatch):
+    """ARUCOHIP_STREAMS=3 and two pipeline lanes, each with chunk workers of its own: an HRM dictionary, a decoder callback and parameters
+    set before arucohip_set_pipeline_depth are taken by the lanes when they are made, and new ones set afterwards reach every lane and its
+    chunk workers. The tickets' results equal those of a plain handle with the same settings."""
+    capi = env["capi"]
+    gray, doc = load_case("hrm")
+    st, dic = doc["settings"], doc["dictionary"]
+    fr = np.ascontiguousarray(np.stack([np.roll(gray, 9 * i, axis=1) for i in range(6)]))
+    FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.POINTER(C.c_int))
+    every_candidate_is_5 = FN(lambda user, patch, size, nrot: 5)
+    rejects_all = FN(lambda user, patch, size, nrot: -1)
+    L = capi.load()
+    L.arucohip_set_decoder_callback.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    bad = list(dic["markers"])
+    bad[3] = ("0" if bad[3][0] == "1" else "1") + bad[3][1:]
+
+    def configure(x, markers, fn, min_size, decoder_kind):
+        x.set_dictionary(markers, dic["tau0"])
+        assert L.arucohip_set_decoder_callback(x.h, C.cast(fn, C.c_void_p), None) == 0
+        p = x.get_params()
+        p.thres_param1, p.thres_param2, p.max_size, p.warp_size = st["thres_param1"], st["thres_param2"], st["max_size"], st["warp_size"]
+        p.min_size, p.decoder_kind = min_size, decoder_kind
+        x.set_params(p)
+
+    def tickets(x):
+        out, n = np.zeros((6, 64), capi.MARKER_DTYPE), np.zeros(6, np.int32)
+        x.wait(x.submit_host(fr, out, n))
+        assert x.batch_chunks() == (3, 2)
+        return [out[f, :n[f]].copy() for f in range(6)]
+
+    def plain(*settings):
+        x = capi.Handle(640, 640, max_batch=6)
+        try:
+            configure(x, *settings)
+            return x.detect_batch_host(fr, cap=64)
+        finally:
+            x.close()
+
+    monkeypatch.setenv("ARUCOHIP_STREAMS", "3")   # read when the handle and its lanes are made
+    h = capi.Handle(640, 640, max_batch=6)
+    try:
+        before = (dic["markers"], rejects_all, st["min_size"], 1)
+        configure(h, *before)
+        h.set_pipeline_depth(2)
+        monkeypatch.delenv("ARUCOHIP_STREAMS")
+        for settings in (before, (bad, every_candidate_is_5, 0.02, 1), (bad, every_candidate_is_5, 0.02, 2)):
+            if settings is not before:
+                configure(h, *settings)
+            got, want = tickets(h), plain(*settings)
+            assert sum(len(g) for g in got) >= 6
+            for a, b in zip(got, want):
+                assert a.tobytes() == b.tobytes()
+        assert all(int(m["id"]) == 5 for g in got for m in g)
+    finally:
+        h.close()
+
+
 def test_gl_modelviews_of_hip_detected_poses(env):
     """SURVEY §8 row f4 with poses that come from the HIP path (reference test Aruco.GL_Conversion, test/core_tests.cpp:
     230-283 <-> testdata/board/expected_gl.yml): detect the board image with intrinsics and marker size 1, board pose from

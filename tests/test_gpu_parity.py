@@ -442,6 +442,34 @@ def test_chunk_streams(env, monkeypatch):
         ref.close()
 
 
+def test_stage_call_after_a_chunked_batch_clears_the_last_batch(env, monkeypatch):
+    """ARUCOHIP_STREAMS=3: a batch in three chunks, then arucohip_refine_candidate_lines, which borrows the lists of the handle's first
+    worker. The last batch is gone for every frame, not only for the frames of the first chunk: every frame getter refuses."""
+    capi, synth = env["capi"], env["synth"]
+    fr, _ = synth.make_stream(7, seed=99, device="cuda")
+    frames = fr.cpu().numpy()
+    monkeypatch.setenv("ARUCOHIP_STREAMS", "3")
+    h = capi.Handle(1920, 1080, max_batch=7)
+    monkeypatch.delenv("ARUCOHIP_STREAMS")
+    try:
+        h.detect_batch_host(frames)
+        assert h.batch_chunks() == (3, 3)
+        for f in range(7):
+            assert h.thresholded(f, frames[f].shape).any()
+        edge = np.arange(100, 200)
+        contour = np.concatenate([np.stack([edge, np.full(100, 100)], 1), np.stack([np.full(100, 200), edge], 1),
+                                  np.stack([edge[::-1] + 1, np.full(100, 200)], 1), np.stack([np.full(100, 100), edge[::-1] + 1], 1)])
+        h.refine_candidate_lines(contour, [[100, 100], [200, 100], [200, 200], [100, 200]])
+        getters = [lambda f: h.thresholded(f, frames[f].shape), h.candidates, h.debug_otsu, h.debug_candidates, h.debug_contours]
+        for f in range(7):
+            for get in getters:
+                with pytest.raises(capi.ArucoHipError) as e:
+                    get(f)
+                assert e.value.code == capi.E_INVALID
+    finally:
+        h.close()
+
+
 def test_hrm_decoder(env):
     """highly reliable markers (reference test Aruco.HRM_Single, test/core_tests.cpp:310-353) through
     the HIP path: dictionary d4x4_100, the test's detector settings; equals the CPU restatement and the reference's golden."""
