@@ -1,4 +1,5 @@
-// Host side of libarucohip: handle, device buffers, launch order. Implements include/arucohip.h.
+// Host side of libarucohip: handle, device buffers, launch order. Implements include/arucohip.h together with capi_calib.hip,
+// capi_chromatic.hip and capi_hrm.hip (handle.h holds what they share).
 //
 // Launch order of one batch (all on the handle's stream, no host round trip until the final D2H of the markers):
 //   memset counters -> threshold(+masks+start candidates) -> walkers -> contour/quad -> frame candidates ->
@@ -10,12 +11,11 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <memory>
 #include <string>
 #include <vector>
 
 #include "bits_tiles.h"
-#include "internal.h"
+#include "handle.h"
 
 namespace ah {
 void launch_rotate_x(hipStream_t s, double* rt);
@@ -57,185 +57,13 @@ Tuning read_tuning() {
 }
 }  // namespace ah
 
-using namespace ah;
-
 enum { STAGE_THRESHOLD = 0, STAGE_RECTANGLES, STAGE_IDENTIFY, STAGE_SUBPIXEL, STAGE_FILTERING, STAGE_COUNT };
 static const char* kStageNames[STAGE_COUNT] = {"Threshold", "Rectangles", "Identify", "Subpixel", "Filtering"};
-// one event after every kernel of a batch; a ring of TSETS batches so that asynchronous steps can be averaged
-// slot k = the interval between mark k and mark k + 1. walker_long = the generations of long walks up to the fork of the side
-// stream; contour_quad = both passes including the wait for the side stream's late generations.
-enum { K_THRESHOLD = 0, K_FILTER, K_WALKERS, K_WALKERS_LONG, K_CONTOUR_QUADS, K_FRAME_CANDS, K_DECODE, K_REFINE_LINES, K_REFINE_PIXELS, K_FINALIZE, K_POSE, K_COUNT };
 static const char* kKernelNames[K_COUNT] = {"threshold_kernel", "candidates_kernel", "walker_kernel", "walker_long_kernel", "contour_quad_kernel",
                                             "frame_candidates_kernel", "decode_kernel", "refine_lines_kernel", "refine_pixels_kernel", "finalize_kernel",
                                             "pose_kernel"};
 static const int kKernelStage[K_COUNT] = {STAGE_THRESHOLD, STAGE_RECTANGLES, STAGE_RECTANGLES, STAGE_RECTANGLES, STAGE_RECTANGLES, STAGE_RECTANGLES,
                                           STAGE_IDENTIFY, STAGE_IDENTIFY, STAGE_SUBPIXEL, STAGE_FILTERING, STAGE_FILTERING};
-constexpr int TSETS = 32;
-
-// Memory the handle owns: device memory, or pinned host memory for staging the host reads. reserve() replaces the allocation only when
-// `need` exceeds the capacity (exact size, no slack, never shrinks) and then bumps `epoch`, the handle's alloc_epoch: the single-frame
-// graph compares it with its capture's, since its launches carry the pointers by value. The destructor frees.
-template <typename T>
-struct Mem {
-    T* p = nullptr;
-    size_t bytes = 0;
-    bool pinned = false;
-    explicit Mem(bool pinned_ = false) : pinned(pinned_) {}
-    Mem(Mem&& o) noexcept : p(o.p), bytes(o.bytes), pinned(o.pinned) { o.p = nullptr, o.bytes = 0; }
-    ~Mem() { (void)release(); }
-    operator T*() const { return p; }
-    hipError_t reserve(size_t need, uint64_t& epoch) {
-        if (need <= bytes) return hipSuccess;
-        epoch++;
-        hipError_t e = release();
-        if (e == hipSuccess) e = pinned ? hipHostMalloc((void**)&p, need) : hipMalloc((void**)&p, need);
-        if (e == hipSuccess)
-            bytes = need;
-        else
-            p = nullptr;
-        return e;
-    }
-
-private:
-    hipError_t release() {
-        const hipError_t e = p ? (pinned ? hipHostFree(p) : hipFree(p)) : hipSuccess;
-        p = nullptr, bytes = 0;
-        return e;
-    }
-};
-
-constexpr int MAX_WORKERS = 8;   // chunk workers of a handle, itself included (ARUCOHIP_STREAMS)
-
-// A batch as the workers hold it: chunk c of its frames ran on worker c (chunk_worker). The handle the caller holds keeps the last one
-// (arucohip_handle::last): every call that replaces the device lists sets it whole, from plan_batch, or clears it when they no longer
-// hold a batch; a waited ticket adopts its lane's. The getters, board poses, calibration and ChromaticMask read it and nothing else.
-struct Span { arucohip_handle* w; int first, count; };   // worker w holds frames [first, first + count)
-struct Batch {
-    int nspan = 0, frames = 0;
-    Span span[MAX_WORKERS] = {};
-    int W = 0, H = 0, nthr = 1;
-    int board_frames = 0;   // frames whose board poses arucohip_board_detect_batch left in the workers' d_board
-    const Span* begin() const { return span; }
-    const Span* end() const { return span + nspan; }
-    // the worker that holds frame `frame` and the frame's index there; nullptr: the batch has no such frame
-    arucohip_handle* holder(int frame, int* local) const {
-        for (const Span& s : *this)
-            if (frame >= s.first && frame < s.first + s.count) return *local = frame - s.first, s.w;
-        return nullptr;
-    }
-    // the spans of the first nframes frames
-    Batch cut(int nframes) const {
-        Batch b = *this;
-        b.nspan = 0, b.frames = std::min(frames, nframes);
-        for (const Span& s : *this)
-            if (s.first < nframes) b.span[b.nspan++] = {s.w, s.first, std::min(s.count, nframes - s.first)};
-        return b;
-    }
-};
-
-// highly reliable markers (arucohip_set_dictionary); count 0: none
-struct Dictionary {
-    int n = 0, count = 0, tau0 = 0;
-    float rate = 1.f;
-    std::vector<uint64_t> codes;   // kept on the host as well: a new child takes them without reading the device copy back
-};
-
-struct arucohip_handle {
-    int device = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
-    arucohip_params_t params;
-    arucohip_limits_t lim;
-    Buffers buf{};                    // views: the create-time arrays live in `held`, walk_scratch and patches below
-    uint64_t alloc_epoch = 0;         // replacements of owned memory so far (Mem::reserve)
-    std::vector<Mem<void>> held;      // create-time memory, held for the handle's life: the Buffers arrays, zero_block, d_small_*, d_patch, pinned staging
-    Mem<uint32_t> walk_scratch;       // buf.walk_scratch
-    Mem<uint8_t> patches;             // buf.patches
-    Mem<uint8_t> d_gray;              // staging for host frames (gray) and the converted BGR frames
-    Mem<uint8_t> d_bgr;               // staging for host BGR frames
-    arucohip_marker_t* wt_out = nullptr;   // set around detect_core by chunk_enqueue: finalize_kernel writes the results there too
-    int32_t* wt_n = nullptr;
-    int wt_cap = 0;
-    Mem<uint8_t> d_erode;             // eroded planes (params.erode)
-    Mem<uint64_t> d_canny;            // CANNY: survivor tiles, edge tiles, changed flag
-    // frame undistortion (arucohip_undistort): the map of the last camera is kept (umap_nd = -1: none)
-    Mem<short2> d_umap_xy;
-    Mem<uint16_t> d_umap_f;
-    int umap_w = 0, umap_h = 0, umap_nd = -1;
-    float umap_K[9] = {}, umap_d[8] = {};
-    Mem<uint8_t> d_undist;            // undistorted frames when the caller wants them on the host
-    Dictionary hrm;
-    Mem<uint64_t> d_hrm;              // hrm.codes on the device
-    // caller's own decoder (arucohip_set_decoder_callback)
-    arucohip_decoder_fn decoder_fn = nullptr;
-    void* decoder_user = nullptr;
-    Mem<int2> d_user_dec;             // [cap_flat] {id, nRotations} returned by the callback
-    Mem<uint32_t> hu_list{true};      // pinned staging of the callback path: candidate list, decoder results, call order
-    Mem<uint8_t> hu_patches{true};    // pinned staging: the canonical patches handed to the callback (+ one scratch patch)
-    size_t bits_bytes = 0;
-    int bits_w = 0, bits_h = 0;       // geometry the bit image was last written with (pad words depend on it)
-    // pinned host staging
-    arucohip_marker_t* h_markers = nullptr;
-    int32_t* h_n = nullptr;
-    uint32_t* h_counters = nullptr;
-    // small device scratch for the stage-level calls
-    float* d_small_f = nullptr;       // 4096 floats
-    double* d_small_d = nullptr;      // 64 doubles
-    int* d_small_i = nullptr;
-    uint8_t* d_patch = nullptr;       // MAX_WARP^2
-    Mem<arucohip_board_t> d_board;    // batched board results + ids
-    uint32_t* zero_block = nullptr;   // counters, gen_cnt, trig_cnt, raw_cnt, ring_cnt: zeroed together at the start of a batch
-    size_t zero_words = 0;
-    Mem<double> d_gl;                 // batched GL modelview matrices
-    Mem<uint8_t> d_calib;             // camera calibration: solver state, per-view systems and poses, correspondences (calib_carve)
-    Mem<CalibState> hc_calib{true};   // pinned copy of the solver state, read once per iteration
-    Batch last;                       // the last batch (kept on the handle the caller holds)
-    bool timing = false;
-    hipEvent_t ev[TSETS][K_COUNT + 1] = {};
-    int tsets = 0;                       // batches recorded since the last reset
-    float kernel_ms[K_COUNT] = {};       // averages over the recorded batches
-    // Sub-batch pipelining: a batch larger than cap_frames is cut into up to nsub chunks; chunk 0 runs on this handle and
-    // the caller's stream, chunk i on chunk worker i (chunk_worker) and its own stream, so the latency-bound kernels of one chunk (border
-    // following, Otsu) overlap the bandwidth-bound ones of another and host frames are copied while earlier chunks compute.
-    int nsub = 1, cap_frames = 1;        // workers, frames each worker's buffers hold
-    std::vector<arucohip_handle*> kids;
-    hipEvent_t ev_fork = nullptr, ev_join[MAX_WORKERS] = {};
-    hipStream_t side_stream = nullptr;   // late walker generations (k_contours.hip)
-    hipEvent_t ev_wfork = nullptr, ev_wjoin = nullptr;
-    hipEvent_t ev_thr = nullptr;         // this worker's threshold kernel has finished (staggers the chunks, see detect_batch)
-    bool thres_bytes = true;             // buf.thres holds the last batch's byte image (else: tiles + buf.thres_edge, expanded on demand)
-    hipEvent_t wait_thr = nullptr;       // set by detect_batch: event the next threshold kernel waits for
-    Mem<uint8_t> d_em;                   // arucohip_em_fit scratch, with its own allocation counter (not alloc_epoch)
-    uint64_t em_epoch = 0;
-    Mem<uint8_t> d_hrm_gen;              // HRM dictionary / board generation scratch (k_hrm.hip), its own counter too (not alloc_epoch)
-    uint64_t hrm_epoch = 0;
-    int32_t hrm_stats[4] = {};           // the last arucohip_hrm_create_dictionary: windows, host synchronisations, acceptances, tau decrements
-    // One frame per call (the reference's call shape, arucohip_detect): the chain of ~20 dependent dispatches of a frame is captured once per
-    // (geometry, parameters, camera) into a hipGraph and replayed with ONE launch per call; the frame's H2D copy stays outside (its source
-    // pointer changes with every call), the results land in the handle's pinned staging inside the graph.
-    struct FrameGraph {
-        hipGraphExec_t exec = nullptr;
-        uint64_t key = 0;          // digest of everything the captured launches carry by value
-        uint64_t seen = 0;         // key of the previous eager call: the second call with the same key captures (buffers are sized by then)
-        uint64_t epoch = 0;        // alloc_epoch at the capture: the buffers the launches point into are still the captured ones while it holds
-        bool thres_bytes = false;  // what the captured threshold left in buf.thres (a replay sets thres_bytes to it)
-        int disabled = 0;          // ARUCOHIP_GRAPH=0, or a capture failed once
-    } fgraph;
-    // Batches in flight (arucohip_set_pipeline_depth / _submit / _wait): every pipeline lane is a complete worker (own
-    // buffers, own stream); ticket t runs on lane t mod depth, so the latency-bound tail of batch t (border following,
-    // decoding) overlaps the bandwidth-bound head of batch t+1.
-    std::vector<arucohip_handle*> lanes;
-    int next_ticket = 0;
-    arucohip_handle* retry = nullptr;    // one-frame handle with larger lists for frames that overflowed (arucohip_detect_batch_retry_overflowed)
-    int retry_mult = 0;
-    hipEvent_t ev_submit = nullptr;
-    struct Pending {
-        bool active = false;
-        int ticket = -1, cap = 0, out_on_device = 0;
-        arucohip_marker_t* out = nullptr;
-        int32_t* n_out = nullptr;
-    } pend;
-    std::string err;
-};
 
 // chunk c of a batch runs on worker c: the handle itself, then its chunk workers
 static arucohip_handle* chunk_worker(arucohip_handle* h, int c) { return c == 0 ? h : h->kids[c - 1]; }
@@ -265,27 +93,11 @@ static int for_each_worker(arucohip_handle* h, const F& f) {
     return rc ? rc : f(h);
 }
 
-#define HIPCHK(h, expr)                                                                         \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) {                                                                 \
-            char buf_[256];                                                                     \
-            snprintf(buf_, sizeof(buf_), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            (h)->err = buf_;                                                                    \
-            return ARUCOHIP_E_HIP;                                                              \
-        }                                                                                       \
-    } while (0)
-
-static int fail(arucohip_handle* h, int code, const char* msg) {
-    if (h) h->err = msg;
-    return code;
-}
-
 // create-time memory: held by the handle for its whole life, `view` is the pointer the code uses
 template <typename T>
 static hipError_t hold(arucohip_handle* h, T*& view, size_t bytes, bool pinned = false) {
     Mem<void>& m = h->held.emplace_back(pinned);
-    const hipError_t e = m.reserve(bytes, h->alloc_epoch);
+    const hipError_t e = m.reserve(bytes);
     view = (T*)m.p;
     return e;
 }
@@ -385,7 +197,7 @@ static int load_dictionary(arucohip_handle* h, arucohip_handle* w, const Diction
     HIPCHK(h, hipStreamSynchronize(w->stream));
     w->hrm = Dictionary{};   // none until the device copy is complete
     if (d.count > 0) {
-        HIPCHK(h, w->d_hrm.reserve((size_t)d.count * sizeof(uint64_t), w->alloc_epoch));
+        HIPCHK(h, w->d_hrm.reserve((size_t)d.count * sizeof(uint64_t)));
         HIPCHK(h, hipMemcpy(w->d_hrm, d.codes.data(), (size_t)d.count * sizeof(uint64_t), hipMemcpyHostToDevice));
     }
     w->hrm = d;
@@ -782,7 +594,7 @@ static int ensure_bits_geometry(arucohip_handle* h, int W, int H) {
 static int ensure_walk_scratch(arucohip_handle* h, int nplanes, const DetectParams& dp) {
     size_t need = walk_scratch_words(nplanes, dp, h->buf.long_cap);
     if (need > 0xFFFFFFF0ull) return fail(h, ARUCOHIP_E_CAPACITY, "batch too large for 32-bit checkpoint offsets: fewer frames per batch or a smaller max size");
-    HIPCHK(h, h->walk_scratch.reserve(need * sizeof(uint32_t), h->alloc_epoch));
+    HIPCHK(h, h->walk_scratch.reserve(need * sizeof(uint32_t)));
     h->buf.walk_scratch = h->walk_scratch;
     return ARUCOHIP_OK;
 }
@@ -794,7 +606,7 @@ static int batch_prologue(arucohip_handle* h, const FrameGeom& g, int nframes, c
     if ((rc = ensure_walk_scratch(h, nframes * dp.nthr, dp))) return rc;
     if ((rc = ensure_bits_geometry(h, g.width, g.height))) return rc;
     // canonical patches of the decode stage: cap_flat * warp_size^2 bytes
-    HIPCHK(h, h->patches.reserve((size_t)h->buf.cap_flat * dp.warp_size * dp.warp_size, h->alloc_epoch));
+    HIPCHK(h, h->patches.reserve((size_t)h->buf.cap_flat * dp.warp_size * dp.warp_size));
     h->buf.patches = h->patches;
     return ARUCOHIP_OK;
 }
@@ -807,7 +619,7 @@ static int user_decode_stage(arucohip_handle* h, const DetectParams& dp) {
     const Buffers& b = h->buf;
     // pinned staging owned by the handle, grown on demand: the steady state of a stream of calls allocates nothing
     const size_t npx = (size_t)dp.warp_size * dp.warp_size;
-    HIPCHK(h, h->hu_list.reserve((size_t)b.cap_flat * (sizeof(uint32_t) + sizeof(int2) + sizeof(uint32_t)) + sizeof(uint32_t), h->alloc_epoch));
+    HIPCHK(h, h->hu_list.reserve((size_t)b.cap_flat * (sizeof(uint32_t) + sizeof(int2) + sizeof(uint32_t)) + sizeof(uint32_t)));
     uint32_t* list = h->hu_list;                                   // [cap_flat] frame << 16 | index
     int2* dec = (int2*)(list + b.cap_flat);                        // [cap_flat] {id, nRotations}
     uint32_t* order = (uint32_t*)(dec + b.cap_flat);               // [cap_flat] + the candidate count behind it
@@ -816,7 +628,7 @@ static int user_decode_stage(arucohip_handle* h, const DetectParams& dp) {
     HIPCHK(h, hipStreamSynchronize(s));
     const uint32_t n = std::min(*ncand_p, b.cap_flat);
     if (!n) return ARUCOHIP_OK;
-    HIPCHK(h, h->hu_patches.reserve((size_t)n * npx + npx, h->alloc_epoch));
+    HIPCHK(h, h->hu_patches.reserve((size_t)n * npx + npx));
     uint8_t* patches = h->hu_patches;
     uint8_t* scratch = patches + (size_t)n * npx;
     HIPCHK(h, hipMemcpyAsync(list, b.cand_list, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -831,34 +643,43 @@ static int user_decode_stage(arucohip_handle* h, const DetectParams& dp) {
         const int id = h->decoder_fn(h->decoder_user, scratch, dp.warp_size, &nrot);
         dec[i] = make_int2(id < 0 ? -1 : id, nrot & 3);
     }
-    HIPCHK(h, h->d_user_dec.reserve((size_t)b.cap_flat * sizeof(int2), h->alloc_epoch));   // once per handle
+    HIPCHK(h, h->d_user_dec.reserve((size_t)b.cap_flat * sizeof(int2)));   // once per handle
     HIPCHK(h, hipMemcpyAsync(h->d_user_dec, dec, n * sizeof(int2), hipMemcpyHostToDevice, s));
     launch_set_decoded(s, b, n, h->d_user_dec);
     // no synchronise: the staging belongs to the handle, and the next call that touches it synchronises the stream first (the count above)
     return ARUCOHIP_OK;
 }
 
-static void run_walkers_and_quads(arucohip_handle* h, hipStream_t s, const FrameGeom& g, int nframes, const DetectParams& dp) {
-    WalkFork fk{h->buf.tune.walk_fork ? h->side_stream : nullptr, h->ev_wfork, h->ev_wjoin, nullptr};
-    const bool forked = launch_walkers(s, fk, g, nframes * dp.nthr, dp, h->buf);
-    launch_contour_quads(s, g, nframes, dp, h->buf, forked ? 1 : 0);
-    if (forked) {
-        (void)hipStreamWaitEvent(s, h->ev_wjoin, 0);
-        launch_contour_quads(s, g, nframes, dp, h->buf, 2);
-    }
-}
+// per-kernel timing on stream s: ev = the batch's events (h->ev), nullptr when timing is off
+#define MARK(i) do { if (ev) (void)hipEventRecord(ev[i], s); } while (0)
 
-// runs kernels 2..8 after the masks and start candidates exist
-static void run_rectangles(arucohip_handle* h, const FrameGeom& g, int nframes, const DetectParams& dp) {
-    if (h->buf.seg_mode) {
-        launch_start_candidates(h->stream, g, nframes * dp.nthr, h->buf);   // also clears the planes' key -> node tables
-        launch_segments(h->stream, g, nframes * dp.nthr, dp, h->buf);
+// Rectangles stage on the planes' bit tiles: start candidates, border following, quads, frame candidates (detect_core, and without timing
+// events arucohip_detect_rectangles)
+static int run_rectangles(arucohip_handle* h, hipStream_t s, const FrameGeom& g, int nframes, const DetectParams& dp, hipEvent_t* ev) {
+    const Buffers& b = h->buf;
+    if (b.seg_mode) {
+        launch_start_candidates(s, g, nframes * dp.nthr, b);   // also clears the planes' key -> node tables
+        MARK(K_WALKERS);
+        launch_segments(s, g, nframes * dp.nthr, dp, b);
+        MARK(K_WALKERS_LONG);
+        MARK(K_CONTOUR_QUADS);
+        launch_contour_quads(s, g, nframes, dp, b);
     } else {
-        launch_start_candidates(h->stream, g, nframes * dp.nthr, h->buf, dp.min_contour);
-        run_walkers_and_quads(h, h->stream, g, nframes, dp);
+        if (RUN_STAGE(b.tune, 1)) launch_start_candidates(s, g, nframes * dp.nthr, b, dp.min_contour);
+        MARK(K_WALKERS);
+        // walkers; their late generations run on the side stream under the first quad pass (the contour_quad mark sits at the fork)
+        WalkFork fk{b.tune.walk_fork ? h->side_stream : nullptr, h->ev_wfork, h->ev_wjoin, ev ? ev[K_WALKERS_LONG] : nullptr};
+        const bool forked = RUN_STAGE(b.tune, 2) ? launch_walkers(s, fk, g, nframes * dp.nthr, dp, b) : false;
+        MARK(K_CONTOUR_QUADS);
+        if (RUN_STAGE(b.tune, 4)) launch_contour_quads(s, g, nframes, dp, b, forked ? 1 : 0);
+        if (forked) {
+            HIPCHK(h, hipStreamWaitEvent(s, h->ev_wjoin, 0));
+            if (RUN_STAGE(b.tune, 4)) launch_contour_quads(s, g, nframes, dp, b, 2);
+        }
     }
-    if (h->buf.seg_mode) launch_contour_quads(h->stream, g, nframes, dp, h->buf);
-    launch_frame_candidates(h->stream, g, nframes, dp, h->buf);
+    MARK(K_FRAME_CANDS);
+    if (RUN_STAGE(b.tune, 5)) launch_frame_candidates(s, g, nframes, dp, b);
+    return ARUCOHIP_OK;
 }
 
 // threshold stage of any method into buf.thres / buf.tiles (+ bitmap). CANNY (markerdetector.cpp:667-676) blocks the host while its
@@ -874,7 +695,7 @@ static int run_threshold(arucohip_handle* h, hipStream_t s, const uint8_t* gray_
         return ARUCOHIP_OK;
     }
     const size_t ntiles = (size_t)nframes * dp.nthr * ((g.width + 7) / 8) * ((g.height + 7) / 8);
-    HIPCHK(h, h->d_canny.reserve(2 * ntiles * sizeof(uint64_t) + 64, h->alloc_epoch));
+    HIPCHK(h, h->d_canny.reserve(2 * ntiles * sizeof(uint64_t) + 64));
     uint64_t* surv = h->d_canny;
     uint64_t* edge = surv + ntiles;
     if (launch_canny(s, gray_dev, g, nframes, dp.nthr, b, surv, edge, (uint32_t*)(edge + ntiles))) return fail(h, ARUCOHIP_E_HIP, "CANNY kernels failed");
@@ -888,9 +709,7 @@ static int detect_core(arucohip_handle* h, const uint8_t* gray_dev, const FrameG
     hipStream_t s = h->stream;
     Buffers& b = h->buf;
     HIPCHK(h, hipMemsetAsync(h->zero_block, 0, h->zero_words * sizeof(uint32_t), s));
-    hipEvent_t* ev = h->ev[h->tsets % TSETS];
-    const bool tm = h->timing;
-#define MARK(i) do { if (tm) (void)hipEventRecord(ev[i], s); } while (0)
+    hipEvent_t* ev = h->timing ? h->ev[h->tsets % TSETS] : nullptr;
     if (h->wait_thr) HIPCHK(h, hipStreamWaitEvent(s, h->wait_thr, 0));   // threshold kernels of the lanes run one after the other
     MARK(K_THRESHOLD);   // after that wait: the interval is this batch's own threshold kernel
     {
@@ -900,7 +719,7 @@ static int detect_core(arucohip_handle* h, const uint8_t* gray_dev, const FrameG
     if (h->params.erode) {
         // on the bit tiles where the byte image was left out (the default path), on the bytes otherwise
         const bool on_tiles = !h->thres_bytes;
-        HIPCHK(h, h->d_erode.reserve(on_tiles ? erode_tiles_tmp_bytes(g, nframes * dp.nthr) : (size_t)nframes * dp.nthr * g.width * g.height, h->alloc_epoch));
+        HIPCHK(h, h->d_erode.reserve(on_tiles ? erode_tiles_tmp_bytes(g, nframes * dp.nthr) : (size_t)nframes * dp.nthr * g.width * g.height));
         if (on_tiles)
             launch_erode_tiles(s, g, nframes * dp.nthr, b, h->d_erode);
         else
@@ -908,28 +727,10 @@ static int detect_core(arucohip_handle* h, const uint8_t* gray_dev, const FrameG
     }
     if (h->ev_thr) HIPCHK(h, hipEventRecord(h->ev_thr, s));
     MARK(K_FILTER);
-    if (b.seg_mode) {
-        launch_start_candidates(s, g, nframes * dp.nthr, b);   // also clears the planes' key -> node tables
-        MARK(K_WALKERS);
-        launch_segments(s, g, nframes * dp.nthr, dp, b);
-        MARK(K_WALKERS_LONG);
-        MARK(K_CONTOUR_QUADS);
-        launch_contour_quads(s, g, nframes, dp, b);
-    } else {
-        if (RUN_STAGE(b.tune, 1)) launch_start_candidates(s, g, nframes * dp.nthr, b, dp.min_contour);
-        MARK(K_WALKERS);
-        // walkers; their late generations run on the side stream under the first quad pass (the contour_quad mark sits at the fork)
-        WalkFork fk{b.tune.walk_fork ? h->side_stream : nullptr, h->ev_wfork, h->ev_wjoin, tm ? ev[K_WALKERS_LONG] : nullptr};
-        const bool forked = RUN_STAGE(b.tune, 2) ? launch_walkers(s, fk, g, nframes * dp.nthr, dp, b) : false;
-        MARK(K_CONTOUR_QUADS);
-        if (RUN_STAGE(b.tune, 4)) launch_contour_quads(s, g, nframes, dp, b, forked ? 1 : 0);
-        if (forked) {
-            HIPCHK(h, hipStreamWaitEvent(s, h->ev_wjoin, 0));
-            if (RUN_STAGE(b.tune, 4)) launch_contour_quads(s, g, nframes, dp, b, 2);
-        }
+    {
+        const int rc_ = run_rectangles(h, s, g, nframes, dp, ev);
+        if (rc_) return rc_;
     }
-    MARK(K_FRAME_CANDS);
-    if (RUN_STAGE(b.tune, 5)) launch_frame_candidates(s, g, nframes, dp, b);
     MARK(K_DECODE);
     // built-in 5x5 decoder: the cell votes and the Hamming decode of a candidate are the head of its refinement wave (one dispatch less)
     const bool fused_cells = dp.decoder == ARUCOHIP_DECODER_FIDUCIAL_5X5;
@@ -951,7 +752,7 @@ static int detect_core(arucohip_handle* h, const uint8_t* gray_dev, const FrameG
     if (RUN_STAGE(b.tune, 8) && cam.has_K && cam.marker_size > 0) launch_pose(s, nframes, cam, b);
     MARK(K_COUNT);
 #undef MARK
-    if (tm) h->tsets++;
+    if (ev) h->tsets++;
     HIPCHK(h, hipGetLastError());
     return ARUCOHIP_OK;
 }
@@ -964,13 +765,13 @@ static int stage_frames(arucohip_handle* h, const uint8_t* frames, int nframes, 
         const uint8_t* bgr = frames;
         size_t rs = row_stride, fs = frame_stride;
         if (!on_device) {
-            HIPCHK(h, h->d_bgr.reserve((size_t)nframes * W * H * 3, h->alloc_epoch));
+            HIPCHK(h, h->d_bgr.reserve((size_t)nframes * W * H * 3));
             for (int f = 0; f < nframes; f++)
                 HIPCHK(h, hipMemcpy2DAsync(h->d_bgr + (size_t)f * W * H * 3, (size_t)W * 3, frames + (size_t)f * frame_stride, row_stride, (size_t)W * 3, H,
                                            hipMemcpyHostToDevice, h->stream));
             bgr = h->d_bgr, rs = (size_t)W * 3, fs = (size_t)W * H * 3;
         }
-        HIPCHK(h, h->d_gray.reserve((size_t)nframes * W * H, h->alloc_epoch));
+        HIPCHK(h, h->d_gray.reserve((size_t)nframes * W * H));
         launch_bgr2gray(h->stream, bgr, rs, fs, W, H, nframes, h->d_gray);
         HIPCHK(h, hipGetLastError());
         *gray_dev = h->d_gray;
@@ -982,7 +783,7 @@ static int stage_frames(arucohip_handle* h, const uint8_t* frames, int nframes, 
         g->row_stride = row_stride, g->frame_stride = frame_stride;
         return ARUCOHIP_OK;
     }
-    HIPCHK(h, h->d_gray.reserve((size_t)nframes * W * H, h->alloc_epoch));
+    HIPCHK(h, h->d_gray.reserve((size_t)nframes * W * H));
     if (row_stride == (size_t)W && frame_stride == (size_t)W * H) {
         // tightly packed frames (a pinned ring of camera frames): ONE copy for the batch instead of one 2-D copy per frame
         HIPCHK(h, hipMemcpyAsync(h->d_gray, frames, (size_t)nframes * W * H, hipMemcpyHostToDevice, h->stream));
@@ -1003,8 +804,6 @@ static int check_geometry(arucohip_handle* h, int nframes, int W, int H, size_t 
     if (row_stride < (size_t)W * channels) return fail(h, ARUCOHIP_E_INVALID, "row_stride < width * channels");
     return ARUCOHIP_OK;
 }
-
-extern "C" {
 
 // enqueue one chunk on worker w (its buffers, its stream); results go to device memory or to w's pinned staging
 static int chunk_enqueue(arucohip_handle* w, const uint8_t* frames, int nframes, int W, int H, size_t row_stride, size_t frame_stride,
@@ -1054,16 +853,14 @@ static int chunk_collect_host(arucohip_handle* h, arucohip_handle* w, int nframe
     return ret;
 }
 
-// fork: the other workers' streams wait for what the first worker's stream (the batch's own) has queued so far; errors are reported on h
-static int fork_workers(arucohip_handle* h, const Batch& b) {
+int fork_workers(arucohip_handle* h, const Batch& b) {
     if (b.nspan <= 1) return ARUCOHIP_OK;
     arucohip_handle* o = b.span[0].w;
     HIPCHK(h, hipEventRecord(o->ev_fork, o->stream));
     for (int c = 1; c < b.nspan; c++) HIPCHK(h, hipStreamWaitEvent(b.span[c].w->stream, o->ev_fork, 0));
     return ARUCOHIP_OK;
 }
-// join: the first worker's stream waits for the others
-static int join_workers(arucohip_handle* h, const Batch& b) {
+int join_workers(arucohip_handle* h, const Batch& b) {
     arucohip_handle* o = b.span[0].w;
     for (int c = 1; c < b.nspan; c++) {
         HIPCHK(h, hipEventRecord(o->ev_join[c - 1], b.span[c].w->stream));
@@ -1099,7 +896,7 @@ static int detect_one_graphed(arucohip_handle* h, const uint8_t* frame, int W, i
     *handled = false;
     if (h->fgraph.disabled || h->timing || dp.decoder == ARUCOHIP_DECODER_USER || dp.thres_method == ARUCOHIP_THRES_CANNY || h->params.erode) return ARUCOHIP_OK;
     uint64_t key = 1469598103934665603ull;
-    const int geo[4] = {W, H, channels, (int)h->buf.seg_mode};
+    const int geo[5] = {W, H, channels, (int)h->buf.seg_mode, h->buf.thr_stamp_on};
     key = digest(key, geo, sizeof(geo));
     key = digest(key, &dp, sizeof(dp));
     key = digest(key, &cam, sizeof(cam));
@@ -1117,13 +914,13 @@ static int detect_one_graphed(arucohip_handle* h, const uint8_t* frame, int W, i
     FrameGeom g;
     if ((rc = stage_frames(h, frame, 1, W, H, row_stride, (size_t)H * row_stride, 0, channels, &gray_dev, &g))) return rc;   // H2D (+ BGR conversion), eager
     if ((rc = batch_prologue(h, g, 1, dp))) return rc;   // also restores the bit-image geometry on the stream, ahead of the launch
-    if (h->fgraph.exec && h->fgraph.epoch != h->alloc_epoch) {   // a buffer was replaced since the capture: start over, like a new configuration
+    const std::array<const void*, 3> addrs = {gray_dev, h->buf.walk_scratch, h->buf.patches};   // what may move between calls (FrameGraph)
+    if (h->fgraph.exec && h->fgraph.addrs != addrs) {   // a buffer was replaced since the capture: start over, like a new configuration
         (void)hipGraphExecDestroy(h->fgraph.exec);
         h->fgraph.exec = nullptr, h->fgraph.seen = key;
         return ARUCOHIP_OK;   // the frame is staged; the eager path stages it again, which is harmless
     }
     if (!h->fgraph.exec) {
-        const uint64_t epoch = h->alloc_epoch;
         hipGraph_t graph = nullptr;
         if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
             (void)hipGetLastError();
@@ -1138,7 +935,8 @@ static int detect_one_graphed(arucohip_handle* h, const uint8_t* frame, int W, i
             e = hipMemcpyAsync(h->h_markers, b.markers, ((size_t)b.cap_markers + 1) * sizeof(arucohip_marker_t), hipMemcpyDeviceToHost, h->stream);
         }
         const hipError_t e2 = hipStreamEndCapture(h->stream, &graph);
-        if (rc != ARUCOHIP_OK || e != hipSuccess || e2 != hipSuccess || !graph || h->alloc_epoch != epoch ||
+        const std::array<const void*, 3> captured = {gray_dev, h->buf.walk_scratch, h->buf.patches};
+        if (rc != ARUCOHIP_OK || e != hipSuccess || e2 != hipSuccess || !graph || captured != addrs ||
             hipGraphInstantiate(&h->fgraph.exec, graph, nullptr, nullptr, 0) != hipSuccess) {
             (void)hipGetLastError();
             if (graph) (void)hipGraphDestroy(graph);
@@ -1146,7 +944,7 @@ static int detect_one_graphed(arucohip_handle* h, const uint8_t* frame, int W, i
             return ARUCOHIP_OK;
         }
         (void)hipGraphDestroy(graph);
-        h->fgraph.key = key, h->fgraph.epoch = epoch, h->fgraph.thres_bytes = h->thres_bytes;
+        h->fgraph.key = key, h->fgraph.addrs = addrs, h->fgraph.thres_bytes = h->thres_bytes;
     }
     *handled = true;
     HIPCHK(h, hipGraphLaunch(h->fgraph.exec, h->stream));
@@ -1202,6 +1000,8 @@ static int detect_batch_impl(arucohip_handle* h, const uint8_t* frames, int nfra
     return collect_batch_host(h, out, cap, n_out);
 }
 
+extern "C" {
+
 int arucohip_detect_batch(arucohip_handle* h, const uint8_t* frames, int nframes, int W, int H, size_t row_stride, size_t frame_stride,
                           int frames_on_device, const float* K, const float* dist, int ndist, float marker_size, int y_perp,
                           arucohip_marker_t* out, int cap, int32_t* n_out, int out_on_device) {
@@ -1252,8 +1052,8 @@ int arucohip_undistort(arucohip_handle* h, const uint8_t* src, int nframes, int 
     if (!same) {
         const size_t px = (size_t)W * H;
         h->umap_nd = -1;   // no valid map until this one is written
-        HIPCHK(h, h->d_umap_xy.reserve(px * sizeof(short2), h->alloc_epoch));
-        HIPCHK(h, h->d_umap_f.reserve(px * sizeof(uint16_t), h->alloc_epoch));
+        HIPCHK(h, h->d_umap_xy.reserve(px * sizeof(short2)));
+        HIPCHK(h, h->d_umap_f.reserve(px * sizeof(uint16_t)));
         launch_undist_map(s, W, H, K, dist, ndist, h->d_umap_xy, h->d_umap_f);
         HIPCHK(h, hipGetLastError());
         h->umap_w = W, h->umap_h = H, h->umap_nd = ndist;
@@ -1264,7 +1064,7 @@ int arucohip_undistort(arucohip_handle* h, const uint8_t* src, int nframes, int 
     const uint8_t* sdev = src;
     size_t rs = row_stride, fs = frame_stride;
     if (!src_on_device) {
-        HIPCHK(h, h->d_bgr.reserve((size_t)nframes * fbytes, h->alloc_epoch));
+        HIPCHK(h, h->d_bgr.reserve((size_t)nframes * fbytes));
         for (int f = 0; f < nframes; f++)
             HIPCHK(h, hipMemcpy2DAsync(h->d_bgr + (size_t)f * fbytes, (size_t)W * channels, src + (size_t)f * frame_stride, row_stride, (size_t)W * channels, H,
                                        hipMemcpyHostToDevice, s));
@@ -1272,7 +1072,7 @@ int arucohip_undistort(arucohip_handle* h, const uint8_t* src, int nframes, int 
     }
     uint8_t* ddev = dst;
     if (!dst_on_device) {
-        HIPCHK(h, h->d_undist.reserve((size_t)nframes * fbytes, h->alloc_epoch));
+        HIPCHK(h, h->d_undist.reserve((size_t)nframes * fbytes));
         ddev = h->d_undist;
     }
     launch_remap(s, sdev, rs, fs, W, H, channels, nframes, h->d_umap_xy, h->d_umap_f, ddev);
@@ -1569,7 +1369,7 @@ int arucohip_detect_rectangles(arucohip_handle* h, const uint8_t* thres, int W, 
     if ((rc = ensure_walk_scratch(h, 1, dp))) return rc;
     if ((rc = ensure_bits_geometry(h, W, H))) return rc;
     launch_binary_planes(h->stream, dev, g, 1, h->buf);
-    run_rectangles(h, g, 1, dp);
+    if ((rc = run_rectangles(h, h->stream, g, 1, dp, nullptr))) return rc;
     HIPCHK(h, hipGetLastError());
     h->last = plan_batch(h, 1, W, H, 1);
     std::vector<Cand> v;
@@ -1664,7 +1464,7 @@ int arucohip_board_detect_batch(arucohip_handle* h, int nframes, const int32_t* 
     if ((rc = fork_workers(h, b))) return rc;
     for (const Span& s : b) {
         arucohip_handle* w = s.w;
-        HIPCHK(h, w->d_board.reserve((size_t)w->cap_frames * (sizeof(arucohip_board_t) + sizeof(float)) + 8192 * sizeof(int32_t), w->alloc_epoch));
+        HIPCHK(h, w->d_board.reserve((size_t)w->cap_frames * (sizeof(arucohip_board_t) + sizeof(float)) + 8192 * sizeof(int32_t)));
         arucohip_board_t* d_out = w->d_board;
         float* d_prob = (float*)(d_out + w->cap_frames);
         int32_t* d_ids = (int32_t*)(d_prob + w->cap_frames);
@@ -1687,523 +1487,6 @@ int arucohip_board_detect_batch(arucohip_handle* h, int nframes, const int32_t* 
     return ARUCOHIP_OK;
 }
 
-// ---- camera calibration (k_calib.hip) ----
-// Byte offsets into h->d_calib for V views, npts points, nframes gather slots and a board of nboard markers.
-struct CalibCarve {
-    size_t st, off, npt, init, red, bs, pose, vcost, vchg, obj, img, nmark, bids, bobj, total;
-};
-static CalibCarve calib_carve(int V, size_t npts, int nframes, int nboard) {
-    CalibCarve c;
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t here = at;
-        at += (bytes + 255) & ~(size_t)255;
-        return here;
-    };
-    c.st = take(sizeof(CalibState));
-    c.off = take((size_t)V * sizeof(int32_t)), c.npt = take((size_t)std::max(V, nframes) * sizeof(int32_t));
-    c.init = take((size_t)V * 6 * sizeof(double)), c.red = take((size_t)V * CALIB_RED * sizeof(double));
-    c.bs = take((size_t)V * CALIB_BS * sizeof(double)), c.pose = take((size_t)V * 12 * sizeof(double));
-    c.vcost = take((size_t)V * 2 * sizeof(double)), c.vchg = take((size_t)V * 2 * sizeof(double));
-    c.obj = take(npts * 3 * sizeof(float)), c.img = take(npts * 2 * sizeof(float));
-    c.nmark = take((size_t)nframes * sizeof(int32_t));
-    c.bids = take((size_t)nboard * sizeof(int32_t)), c.bobj = take((size_t)nboard * 12 * sizeof(float));
-    c.total = at;
-    return c;
-}
-
-// Levenberg-Marquardt on views whose points are already on the device (d.obj / d.img, offsets off[], counts npt[]): start values, then
-// one host synchronisation per iteration for the stop flag.
-static int calib_solve(arucohip_handle* h, CalibDev d, const CalibCarve& c, const std::vector<int32_t>& off, const std::vector<int32_t>& npt,
-                       int W, int H, int flags, double* K, double* dist, double* rvecs, double* tvecs, double* per_view_rms, double* rms) {
-    const int V = d.nviews;
-    uint8_t* base = h->d_calib;
-    d.off = (const int32_t*)(base + c.off), d.npt = (const int32_t*)(base + c.npt);
-    d.init = (double*)(base + c.init), d.red = (double*)(base + c.red), d.bs = (double*)(base + c.bs);
-    d.pose = (double*)(base + c.pose), d.vcost = (double*)(base + c.vcost), d.vchg = (double*)(base + c.vchg);
-    d.st = (CalibState*)(base + c.st);
-    const bool guess = flags & ARUCOHIP_CALIB_USE_INTRINSIC_GUESS;
-    CalibState st;
-    std::memset(&st, 0, sizeof(st));
-    st.flags = flags, st.max_iter = 30, st.lg = -3;
-    st.aspect = (K[0] > 0 && K[4] > 0) ? K[0] / K[4] : 1.0;
-    if (guess) {
-        const double g[9] = {K[0], K[4], K[2], K[5], dist[0], dist[1], dist[2], dist[3], dist[4]};
-        for (int i = 0; i < 9; i++) st.intr[i] = g[i];
-        if (!(g[0] > 0 && g[1] > 0)) return fail(h, ARUCOHIP_E_INVALID, "USE_INTRINSIC_GUESS needs positive focal lengths");
-        if (flags & ARUCOHIP_CALIB_FIX_ASPECT_RATIO) st.intr[0] = st.aspect * st.intr[1];
-    } else {
-        st.intr[2] = (W - 1) * 0.5, st.intr[3] = (H - 1) * 0.5;
-    }
-    if (flags & ARUCOHIP_CALIB_ZERO_TANGENT_DIST) st.intr[6] = st.intr[7] = 0;
-    int mask = 0x1FF;
-    if (flags & ARUCOHIP_CALIB_FIX_ASPECT_RATIO) mask &= ~1;
-    if (flags & ARUCOHIP_CALIB_FIX_FOCAL_LENGTH) mask &= ~3;
-    if (flags & ARUCOHIP_CALIB_FIX_PRINCIPAL_POINT) mask &= ~(4 | 8);
-    if (flags & ARUCOHIP_CALIB_ZERO_TANGENT_DIST) mask &= ~(64 | 128);
-    if (flags & ARUCOHIP_CALIB_FIX_K1) mask &= ~16;
-    if (flags & ARUCOHIP_CALIB_FIX_K2) mask &= ~32;
-    if (flags & ARUCOHIP_CALIB_FIX_K3) mask &= ~256;
-    st.free_mask = mask;
-    hipStream_t s = h->stream;
-    HIPCHK(h, h->hc_calib.reserve(sizeof(CalibState), h->alloc_epoch));
-    CalibState* hs = h->hc_calib;
-    *hs = st;
-    HIPCHK(h, hipMemcpyAsync(d.st, hs, sizeof(st), hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync((void*)d.off, off.data(), (size_t)V * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync((void*)d.npt, npt.data(), (size_t)V * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    launch_calib_init(s, d, guess);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(hs, d.st, sizeof(st), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    if (hs->err & CALIB_ERR_NONPLANAR) return fail(h, ARUCOHIP_E_UNSUPPORTED, "calibration views must be planar (constant z per view)");
-    if (hs->err) return fail(h, ARUCOHIP_E_INVALID, "degenerate calibration views: no start values");
-    // at most 30 accepted steps; every rejected step raises lambda tenfold, and lambda above 1e16 stops
-    for (int it = 0; it < 256 && !hs->done; it++) {
-        launch_calib_iteration(s, d);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(hs, d.st, sizeof(st), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-    }
-    st = *hs;
-    std::vector<double> pose((size_t)V * 6), vcost((size_t)V);
-    HIPCHK(h, hipMemcpyAsync(pose.data(), d.pose + (size_t)st.cur * V * 6, pose.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(vcost.data(), d.vcost + (size_t)st.cur * V, vcost.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    const double* in = st.intr;
-    const double Ko[9] = {in[0], 0, in[2], 0, in[1], in[3], 0, 0, 1};
-    for (int i = 0; i < 9; i++) K[i] = Ko[i];
-    for (int i = 0; i < 5; i++) dist[i] = in[4 + i];
-    double e2 = 0, np = 0;
-    for (int v = 0; v < V; v++) {
-        e2 += vcost[v], np += npt[v];
-        if (per_view_rms) per_view_rms[v] = std::sqrt(vcost[v] / npt[v]);
-        for (int k = 0; k < 3; k++) {
-            if (rvecs) rvecs[3 * v + k] = pose[6 * v + k];
-            if (tvecs) tvecs[3 * v + k] = pose[6 * v + 3 + k];
-        }
-    }
-    if (rms) *rms = std::sqrt(e2 / np);
-    return ARUCOHIP_OK;
-}
-
-int arucohip_calibrate_camera(arucohip_handle* h, const float* obj, const float* img, const int32_t* npoints, int nviews, int on_device, int W,
-                              int H, int flags, double* K, double* dist, double* rvecs, double* tvecs, double* per_view_rms, double* rms) {
-    if (!h) return ARUCOHIP_E_INVALID;
-    if (!obj || !img || !npoints || !K || !dist || nviews < 1 || W <= 0 || H <= 0)
-        return fail(h, ARUCOHIP_E_INVALID, "calibrate_camera: NULL argument, no views or an empty image size");
-    HIPCHK(h, hipSetDevice(h->device));
-    std::vector<int32_t> npt((size_t)nviews), off((size_t)nviews);
-    if (on_device)
-        HIPCHK(h, hipMemcpy(npt.data(), npoints, (size_t)nviews * sizeof(int32_t), hipMemcpyDeviceToHost));
-    else
-        std::memcpy(npt.data(), npoints, (size_t)nviews * sizeof(int32_t));
-    size_t total = 0;
-    for (int v = 0; v < nviews; v++) {
-        if (npt[v] < 4) return fail(h, ARUCOHIP_E_INVALID, "a calibration view has fewer than 4 points");
-        if (npt[v] > CALIB_MAX_POINTS) return fail(h, ARUCOHIP_E_CAPACITY, "a calibration view has more than ARUCOHIP_CALIB_MAX_VIEW_POINTS points");
-        off[v] = (int32_t)total, total += (size_t)npt[v];
-    }
-    if (total > (size_t)INT32_MAX) return fail(h, ARUCOHIP_E_CAPACITY, "too many calibration points");
-    const CalibCarve c = calib_carve(nviews, on_device ? 0 : total, 0, 0);
-    HIPCHK(h, h->d_calib.reserve(c.total, h->alloc_epoch));
-    CalibDev d{};
-    d.nviews = nviews;
-    if (on_device) {
-        d.obj = obj, d.img = img;
-    } else {
-        float* dobj = (float*)((uint8_t*)h->d_calib + c.obj);
-        float* dimg = (float*)((uint8_t*)h->d_calib + c.img);
-        HIPCHK(h, hipMemcpyAsync(dobj, obj, total * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(dimg, img, total * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        d.obj = dobj, d.img = dimg;
-    }
-    return calib_solve(h, d, c, off, npt, W, H, flags, K, dist, rvecs, tvecs, per_view_rms, rms);
-}
-
-int arucohip_calibrate_board_batch(arucohip_handle* h, int nframes, const int32_t* ids, const float* obj, int nboard, int info_type,
-                                   float marker_size, int min_markers, int W, int H, int flags, double* K, double* dist, int32_t* used,
-                                   double* rvecs, double* tvecs, double* rms) {
-    if (!h) return ARUCOHIP_E_INVALID;
-    if (!K || !dist || W <= 0 || H <= 0) return fail(h, ARUCOHIP_E_INVALID, "calibrate_board_batch: NULL K / dist or an empty image size");
-    if (nboard <= 0 || !ids || !obj) return fail(h, ARUCOHIP_E_BOARD_CONFIG, "invalid BoardConfig that is empty");
-    if (nframes < 1 || nframes > h->last.frames) return fail(h, ARUCOHIP_E_INVALID, "nframes exceeds the last batch");
-    HIPCHK(h, hipSetDevice(h->device));
-    const Batch b = h->last.cut(nframes);
-    arucohip_handle* o = b.span[0].w;   // the worker of the batch's first chunk: the calibration runs on its stream, in its scratch
-    // the metres-per-unit factor of board_pose_kernel for PIX boards (marker side from the first edge of marker 0)
-    const float dx = obj[0] - obj[3], dy = obj[1] - obj[4], dz = obj[2] - obj[5];
-    const double side = std::sqrt((double)dx * dx + (double)dy * dy + (double)dz * dz);
-    const double mpp = (info_type == ARUCOHIP_BOARD_PIX && marker_size > 0) ? (double)marker_size / side : 1.0;
-    const CalibCarve c = calib_carve(nframes, (size_t)nframes * CALIB_MAX_POINTS, nframes, nboard);
-    HIPCHK(h, o->d_calib.reserve(c.total, o->alloc_epoch));
-    uint8_t* base = o->d_calib;
-    float* dobj = (float*)(base + c.obj);
-    float* dimg = (float*)(base + c.img);
-    int32_t* dnpt = (int32_t*)(base + c.npt);
-    int32_t* dnmark = (int32_t*)(base + c.nmark);
-    int32_t* dids = (int32_t*)(base + c.bids);
-    float* dbobj = (float*)(base + c.bobj);
-    HIPCHK(h, hipMemcpyAsync(dids, ids, (size_t)nboard * sizeof(int32_t), hipMemcpyHostToDevice, o->stream));
-    HIPCHK(h, hipMemcpyAsync(dbobj, obj, (size_t)nboard * 12 * sizeof(float), hipMemcpyHostToDevice, o->stream));
-    // every worker lays out the correspondences of the frames it detected, on its own stream
-    int rc;
-    if ((rc = fork_workers(h, b))) return rc;
-    for (const Span& s : b) {
-        launch_calib_gather(s.w->stream, s.count, s.w->buf, dids, dbobj, nboard, mpp, s.first, dobj, dimg, dnpt, dnmark);
-        HIPCHK(h, hipGetLastError());
-    }
-    if ((rc = join_workers(h, b))) return rc;
-    std::vector<int32_t> fnpt((size_t)nframes), fnmark((size_t)nframes);
-    HIPCHK(h, hipMemcpyAsync(fnpt.data(), dnpt, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, o->stream));
-    HIPCHK(h, hipMemcpyAsync(fnmark.data(), dnmark, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, o->stream));
-    HIPCHK(h, hipStreamSynchronize(o->stream));
-    std::vector<int32_t> off, npt;
-    for (int f = 0; f < nframes; f++) {
-        const bool take = fnmark[f] >= std::max(min_markers, 1) && fnpt[f] != 0;
-        if (take && fnpt[f] < 0) return fail(h, ARUCOHIP_E_CAPACITY, "a frame has more board points than ARUCOHIP_CALIB_MAX_VIEW_POINTS");
-        if (used) used[f] = take ? 1 : 0;
-        if (take) off.push_back(f * CALIB_MAX_POINTS), npt.push_back(fnpt[f]);
-    }
-    if (off.empty()) return fail(h, ARUCOHIP_E_INVALID, "no frame holds min_markers board markers");
-    CalibDev d{};
-    d.nviews = (int)off.size(), d.obj = dobj, d.img = dimg;
-    // the per-view arrays are carved for nframes >= views; the off / npt arrays are rewritten with the views
-    rc = calib_solve(o, d, c, off, npt, W, H, flags, K, dist, rvecs, tvecs, nullptr, rms);
-    if (rc && o != h) h->err = o->err;
-    return rc;
-}
-
-// ---- board occlusion mask (k_chromatic.hip) ----
-// The object's buffers are its own (Mem with its own counter, never the handle's alloc_epoch): a chromatic call cannot invalidate the
-// handle's single-frame graph. Calls run on the handle's current stream and return after it has drained.
-struct arucohip_chromatic {
-    arucohip_handle* h = nullptr;
-    int device = 0;           // destroy() may run after the handle's
-    ChromaCam cam{};
-    int ncell = 0;
-    double thresh = 0;
-    bool valid = false;       // isValid(): a train has run
-    int last_batch = 0;       // frames of the last classify_batch (debug_geometry)
-    uint64_t epoch = 0;       // the object's own allocation counter
-    Mem<uint8_t> d_frame, d_cellmap, d_mask, d_inside, d_bframes, d_bmasks;
-    Mem<uint32_t> d_raw, d_hcount;
-    Mem<int32_t> d_fitted, d_trained, d_npix;
-    Mem<double> d_prob;
-    Mem<ChromaGeom> d_geom, d_bgeom;
-};
-
-// setParams(mc, nc, threshProb, CP, BC, markersize), src/chromaticmask.cpp:122-165: the min / max scan (x <= min.x && y <= min.y), the
-// pixel size from the first edge of marker 0, then min and max scaled in x and y (z as found)
-int arucohip_chromatic_board_corners(const float* obj, int nboard, int info_type, float marker_size, float corners[12]) {
-    if (!obj || !corners || nboard < 1) return ARUCOHIP_E_INVALID;
-    if (info_type != ARUCOHIP_BOARD_METERS && marker_size == -1) return ARUCOHIP_E_INVALID;
-    auto P = [&](int i, int j) { return obj + ((size_t)i * 4 + j) * 3; };
-    if (info_type == ARUCOHIP_BOARD_METERS) {   // cv::norm(objPoints[0][0] - objPoints[0][1])
-        const float dx = P(0, 0)[0] - P(0, 1)[0], dy = P(0, 0)[1] - P(0, 1)[1], dz = P(0, 0)[2] - P(0, 1)[2];
-        marker_size = (float)std::sqrt((double)dx * dx + (double)dy * dy + (double)dz * dz);
-    }
-    float mn[3], mx[3];
-    for (int k = 0; k < 3; k++) mn[k] = mx[k] = P(0, 0)[k];
-    for (int i = 0; i < nboard; i++)
-        for (int j = 0; j < 4; j++) {
-            const float* p = P(i, j);
-            if (p[0] <= mn[0] && p[1] <= mn[1]) mn[0] = p[0], mn[1] = p[1], mn[2] = p[2];
-            if (p[0] >= mx[0] && p[1] >= mx[1]) mx[0] = p[0], mx[1] = p[1], mx[2] = p[2];
-        }
-    const double pix = std::fabs(marker_size / (P(0, 1)[0] - P(0, 0)[0]));
-    mn[0] = (float)(mn[0] * pix), mn[1] = (float)(mn[1] * pix);
-    mx[0] = (float)(mx[0] * pix), mx[1] = (float)(mx[1] * pix);
-    const float c[12] = {mn[0], mn[1], mn[2], mn[0], mx[1], 0, mx[0], mx[1], mx[2], mx[0], mn[1], 0};
-    for (int i = 0; i < 12; i++) corners[i] = c[i];
-    return ARUCOHIP_OK;
-}
-
-int arucohip_chromatic_create(arucohip_handle* h, int mc, int nc, double thresh_prob, const float* K, const float* dist, int ndist, int W, int H,
-                              const float corners[12], arucohip_chromatic** out) {
-    if (!h) return ARUCOHIP_E_INVALID;
-    if (!out || !K || !corners || W <= 0 || H <= 0 || ndist < 0 || ndist > 8 || (ndist > 0 && !dist))
-        return fail(h, ARUCOHIP_E_INVALID, "chromatic_create: NULL argument, empty frame size or ndist outside 0..8");
-    *out = nullptr;
-    if (mc <= 0 || nc <= 0 || nc > mc || mc * nc > 255)
-        return fail(h, ARUCOHIP_E_UNSUPPORTED, "chromatic_create: needs 1 <= nc <= mc and mc * nc <= 255 (other grids are undefined in the reference)");
-    HIPCHK(h, hipSetDevice(h->device));
-    std::unique_ptr<arucohip_chromatic> m(new arucohip_chromatic());
-    m->h = h, m->device = h->device, m->ncell = mc * nc, m->thresh = thresh_prob;
-    ChromaCam& c = m->cam;
-    for (int i = 0; i < 9; i++) c.K[i] = K[i];
-    for (int i = 0; i < 8; i++) c.k[i] = i < ndist ? (double)dist[i] : 0.0;
-    for (int i = 0; i < 12; i++) c.corners3d[i] = corners[i];
-    c.mc = mc, c.nc = nc, c.W = W, c.H = H;
-    const size_t px = (size_t)W * H, tab = (size_t)m->ncell * 256;
-    uint64_t& e = m->epoch;
-    HIPCHK(h, m->d_frame.reserve(px, e));
-    HIPCHK(h, m->d_cellmap.reserve(px, e));
-    HIPCHK(h, m->d_mask.reserve(px, e));
-    HIPCHK(h, m->d_raw.reserve(tab * sizeof(uint32_t), e));
-    HIPCHK(h, m->d_hcount.reserve(tab * sizeof(uint32_t), e));
-    HIPCHK(h, m->d_fitted.reserve(m->ncell * sizeof(int32_t), e));
-    HIPCHK(h, m->d_trained.reserve(m->ncell * sizeof(int32_t), e));
-    HIPCHK(h, m->d_prob.reserve(tab * sizeof(double), e));
-    HIPCHK(h, m->d_inside.reserve(tab, e));
-    HIPCHK(h, m->d_geom.reserve(sizeof(ChromaGeom), e));
-    // a fresh EMClassifier: _prob = 0.5, and _inside (uninitialised in the reference) = 0.5 > threshProb
-    std::vector<double> p(tab, 0.5);
-    std::vector<uint8_t> in(tab, 0.5 > thresh_prob ? 1 : 0);
-    hipStream_t s = h->stream;
-    HIPCHK(h, hipMemsetAsync(m->d_cellmap, 0, px, s));
-    HIPCHK(h, hipMemsetAsync(m->d_mask, 0, px, s));
-    HIPCHK(h, hipMemsetAsync(m->d_raw, 0, tab * sizeof(uint32_t), s));
-    HIPCHK(h, hipMemsetAsync(m->d_hcount, 0, tab * sizeof(uint32_t), s));
-    HIPCHK(h, hipMemsetAsync(m->d_fitted, 0, m->ncell * sizeof(int32_t), s));
-    HIPCHK(h, hipMemsetAsync(m->d_trained, 0, m->ncell * sizeof(int32_t), s));
-    HIPCHK(h, hipMemsetAsync(m->d_geom, 0, sizeof(ChromaGeom), s));
-    HIPCHK(h, hipMemcpyAsync(m->d_prob, p.data(), tab * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(m->d_inside, in.data(), tab, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    *out = m.release();
-    return ARUCOHIP_OK;
-}
-
-void arucohip_chromatic_destroy(arucohip_chromatic* m) {
-    if (!m) return;
-    (void)hipSetDevice(m->device);
-    delete m;
-}
-
-// the plane on the device: the caller's, or a copy into the object's staging
-static int chroma_plane(arucohip_chromatic* m, const uint8_t* plane, int on_device, size_t row_stride, const uint8_t** dev, size_t* dev_stride) {
-    arucohip_handle* h = m->h;
-    if (!plane || row_stride < (size_t)m->cam.W) return fail(h, ARUCOHIP_E_INVALID, "chromatic: NULL plane or row stride below the width");
-    HIPCHK(h, hipSetDevice(h->device));
-    if (on_device) {
-        *dev = plane, *dev_stride = row_stride;
-        return ARUCOHIP_OK;
-    }
-    HIPCHK(h, hipMemcpy2DAsync(m->d_frame, m->cam.W, plane, row_stride, m->cam.W, m->cam.H, hipMemcpyHostToDevice, h->stream));
-    *dev = m->d_frame, *dev_stride = m->cam.W;
-    return ARUCOHIP_OK;
-}
-
-// one frame's raw-sample histograms (under the mask for update) and the EM of every cell
-static int chroma_fit(arucohip_chromatic* m, const uint8_t* in, size_t stride, const uint8_t* mask, uint32_t min_raw) {
-    arucohip_handle* h = m->h;
-    hipStream_t s = h->stream;
-    HIPCHK(h, hipMemsetAsync(m->d_raw, 0, (size_t)m->ncell * 256 * sizeof(uint32_t), s));
-    launch_chroma_hist(s, m->cam.W, m->cam.H, in, stride, m->d_cellmap, mask, m->d_raw);
-    launch_chroma_em(s, m->ncell, m->d_raw, min_raw, m->thresh, m->d_hcount, m->d_fitted, m->d_prob, m->d_inside, m->d_trained);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(s));
-    return ARUCOHIP_OK;
-}
-
-int arucohip_chromatic_train(arucohip_chromatic* m, const uint8_t* plane, int on_device, size_t row_stride, const double rvec[3], const double tvec[3]) {
-    if (!m) return ARUCOHIP_E_INVALID;
-    if (!rvec || !tvec) return fail(m->h, ARUCOHIP_E_INVALID, "chromatic_train: NULL pose");
-    const uint8_t* in;
-    size_t stride;
-    int rc = chroma_plane(m, plane, on_device, row_stride, &in, &stride);
-    if (rc) return rc;
-    hipStream_t s = m->h->stream;
-    launch_chroma_geometry(s, m->cam, 1, nullptr, nullptr, 0.f, rvec, tvec, m->d_geom);
-    launch_chroma_grid(s, m->cam, m->d_geom, m->d_cellmap);
-    if ((rc = chroma_fit(m, in, stride, nullptr, 0))) return rc;
-    m->valid = true;
-    return ARUCOHIP_OK;
-}
-
-int arucohip_chromatic_classify(arucohip_chromatic* m, const uint8_t* plane, int on_device, size_t row_stride, const double rvec[3], const double tvec[3],
-                                int method) {
-    if (!m) return ARUCOHIP_E_INVALID;
-    arucohip_handle* h = m->h;
-    if (!rvec || !tvec) return fail(h, ARUCOHIP_E_INVALID, "chromatic_classify: NULL pose");
-    if (method != 1 && method != 2) return fail(h, ARUCOHIP_E_INVALID, "chromatic_classify: method is 1 (classify) or 2 (classify2)");
-    const uint8_t* in;
-    size_t stride;
-    int rc = chroma_plane(m, plane, on_device, row_stride, &in, &stride);
-    if (rc) return rc;
-    hipStream_t s = h->stream;
-    launch_chroma_geometry(s, m->cam, 1, nullptr, nullptr, 0.f, rvec, tvec, m->d_geom);
-    if (method == 1) launch_chroma_grid(s, m->cam, m->d_geom, m->d_cellmap);   // classify refreshes the cell map, classify2 does not
-    launch_chroma_classify(s, m->cam, method, m->thresh, 1, in, stride, 0, m->d_geom, m->d_prob, m->d_inside, m->d_mask, nullptr);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(s));
-    return ARUCOHIP_OK;
-}
-
-int arucohip_chromatic_update(arucohip_chromatic* m, const uint8_t* plane, int on_device, size_t row_stride) {
-    if (!m) return ARUCOHIP_E_INVALID;
-    const uint8_t* in;
-    size_t stride;
-    int rc = chroma_plane(m, plane, on_device, row_stride, &in, &stride);
-    if (rc) return rc;
-    return chroma_fit(m, in, stride, m->d_mask, CHROMA_UPDATE_MIN);
-}
-
-// calculateGridImage(board) on its own (:222-268): the geometry of the pose and the cell map
-int arucohip_chromatic_grid(arucohip_chromatic* m, const double rvec[3], const double tvec[3]) {
-    if (!m) return ARUCOHIP_E_INVALID;
-    arucohip_handle* h = m->h;
-    if (!rvec || !tvec) return fail(h, ARUCOHIP_E_INVALID, "chromatic_grid: NULL pose");
-    HIPCHK(h, hipSetDevice(h->device));
-    launch_chroma_geometry(h->stream, m->cam, 1, nullptr, nullptr, 0.f, rvec, tvec, m->d_geom);
-    launch_chroma_grid(h->stream, m->cam, m->d_geom, m->d_cellmap);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ARUCOHIP_OK;
-}
-
-int arucohip_chromatic_reset_mask(arucohip_chromatic* m) {
-    if (!m) return ARUCOHIP_E_INVALID;
-    arucohip_handle* h = m->h;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemsetAsync(m->d_mask, 0, (size_t)m->cam.W * m->cam.H, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ARUCOHIP_OK;
-}
-
-static int chroma_copy_out(arucohip_chromatic* m, const void* src, void* dst, size_t bytes, int on_device) {
-    arucohip_handle* h = m->h;
-    if (!dst) return fail(h, ARUCOHIP_E_INVALID, "chromatic: NULL destination");
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemcpyAsync(dst, src, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ARUCOHIP_OK;
-}
-
-int arucohip_chromatic_get_mask(arucohip_chromatic* m, uint8_t* dst, int on_device) {
-    if (!m) return ARUCOHIP_E_INVALID;
-    return chroma_copy_out(m, m->d_mask, dst, (size_t)m->cam.W * m->cam.H, on_device);
-}
-
-int arucohip_chromatic_get_cell_map(arucohip_chromatic* m, uint8_t* dst, int on_device) {
-    if (!m) return ARUCOHIP_E_INVALID;
-    return chroma_copy_out(m, m->d_cellmap, dst, (size_t)m->cam.W * m->cam.H, on_device);
-}
-
-int arucohip_chromatic_is_valid(arucohip_chromatic* m) { return m && m->valid ? 1 : 0; }
-
-int arucohip_chromatic_get_model(arucohip_chromatic* m, double* prob, int32_t* trained) {
-    if (!m) return ARUCOHIP_E_INVALID;
-    if (!prob || !trained) return fail(m->h, ARUCOHIP_E_INVALID, "chromatic_get_model: NULL argument");
-    int rc = chroma_copy_out(m, m->d_prob, prob, (size_t)m->ncell * 256 * sizeof(double), 0);
-    return rc ? rc : chroma_copy_out(m, m->d_trained, trained, (size_t)m->ncell * sizeof(int32_t), 0);
-}
-
-int arucohip_chromatic_set_model(arucohip_chromatic* m, const double* prob, const int32_t* trained) {
-    if (!m) return ARUCOHIP_E_INVALID;
-    arucohip_handle* h = m->h;
-    if (!prob || !trained) return fail(h, ARUCOHIP_E_INVALID, "chromatic_set_model: NULL argument");
-    const size_t tab = (size_t)m->ncell * 256;
-    std::vector<uint8_t> in(tab);
-    for (size_t i = 0; i < tab; i++) in[i] = prob[i] > m->thresh ? 1 : 0;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemcpyAsync(m->d_prob, prob, tab * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(m->d_inside, in.data(), tab, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(m->d_trained, trained, (size_t)m->ncell * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ARUCOHIP_OK;
-}
-
-// EMClassifier::train of one cell by chroma_em_kernel, in a small scratch of the handle's that is outside alloc_epoch
-int arucohip_em_fit(arucohip_handle* h, const uint32_t samples_hist[256], double thresh_prob, double prob[256], uint8_t inside[256], int* trained) {
-    if (!h) return ARUCOHIP_E_INVALID;
-    if (!samples_hist || !prob || !inside || !trained) return fail(h, ARUCOHIP_E_INVALID, "em_fit: NULL argument");
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t o_hc = 1024, o_fit = 2048, o_tr = 2056, o_prob = 2064, o_in = o_prob + 2048, total = o_in + 256;
-    HIPCHK(h, h->d_em.reserve(total, h->em_epoch));   // kept for the handle's life; never moves alloc_epoch
-    uint8_t* b = h->d_em;
-    hipStream_t s = h->stream;
-    HIPCHK(h, hipMemcpyAsync(b, samples_hist, 1024, hipMemcpyHostToDevice, s));
-    launch_chroma_em(s, 1, (const uint32_t*)b, 0, thresh_prob, (uint32_t*)(b + o_hc), (int32_t*)(b + o_fit), (double*)(b + o_prob), b + o_in,
-                     (int32_t*)(b + o_tr));
-    HIPCHK(h, hipGetLastError());
-    int32_t fitted = 0;
-    HIPCHK(h, hipMemcpyAsync(&fitted, b + o_fit, sizeof(fitted), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    *trained = fitted == 1;
-    if (fitted == 1) {
-        HIPCHK(h, hipMemcpyAsync(prob, b + o_prob, 256 * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(inside, b + o_in, 256, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-    }
-    return ARUCOHIP_OK;
-}
-
-int arucohip_chromatic_debug_geometry(arucohip_chromatic* m, int frame, float corners2d[8], double H_train[9], double H_classify[9]) {
-    if (!m) return ARUCOHIP_E_INVALID;
-    if (frame >= m->last_batch) return fail(m->h, ARUCOHIP_E_INVALID, "chromatic_debug_geometry: frame outside the last batch");
-    ChromaGeom g;
-    int rc = chroma_copy_out(m, frame < 0 ? (const ChromaGeom*)m->d_geom : (const ChromaGeom*)m->d_bgeom + frame, &g, sizeof(g), 0);
-    if (rc) return rc;
-    for (int i = 0; i < 9; i++) {
-        if (corners2d && i < 8) corners2d[i] = g.corners[i];
-        if (H_train) H_train[i] = g.Ht[i];
-        if (H_classify) H_classify[i] = g.Hc[i];
-    }
-    return ARUCOHIP_OK;
-}
-
-int arucohip_chromatic_debug_hist(arucohip_chromatic* m, uint32_t* raw, uint32_t* hist_count, int32_t* fitted) {
-    if (!m) return ARUCOHIP_E_INVALID;
-    const size_t tab = (size_t)m->ncell * 256;
-    int rc = raw ? chroma_copy_out(m, m->d_raw, raw, tab * sizeof(uint32_t), 0) : 0;
-    if (!rc && hist_count) rc = chroma_copy_out(m, m->d_hcount, hist_count, tab * sizeof(uint32_t), 0);
-    if (!rc && fitted) rc = chroma_copy_out(m, m->d_fitted, fitted, (size_t)m->ncell * sizeof(int32_t), 0);
-    return rc;
-}
-
-int arucohip_chromatic_classify_batch(arucohip_chromatic* m, arucohip_handle* h, const uint8_t* frames, int nframes, int W, int H, size_t row_stride,
-                                      size_t frame_stride, int frames_on_device, int method, float min_prob, uint8_t* masks, int masks_on_device,
-                                      int32_t* npix) {
-    if (!m) return ARUCOHIP_E_INVALID;
-    arucohip_handle* mh = m->h;
-    if (!h || !frames || !masks || nframes < 1) return fail(mh, ARUCOHIP_E_INVALID, "chromatic_classify_batch: NULL argument or no frames");
-    if (W != m->cam.W || H != m->cam.H || row_stride < (size_t)W || frame_stride < row_stride * (H - 1) + W)
-        return fail(mh, ARUCOHIP_E_INVALID, "chromatic_classify_batch: frame size differs from the object's, or strides too small");
-    if (method != 1 && method != 2) return fail(mh, ARUCOHIP_E_INVALID, "chromatic_classify_batch: method is 1 (classify) or 2 (classify2)");
-    if (h->device != mh->device) return fail(mh, ARUCOHIP_E_INVALID, "chromatic_classify_batch: the handle is on another device");
-    if (h->last.board_frames != nframes) return fail(mh, ARUCOHIP_E_INVALID, "chromatic_classify_batch: no arucohip_board_detect_batch of nframes frames before");
-    HIPCHK(mh, hipSetDevice(mh->device));
-    hipStream_t s = mh->stream;
-    const size_t px = (size_t)W * H;
-    HIPCHK(mh, m->d_bgeom.reserve((size_t)nframes * sizeof(ChromaGeom), m->epoch));
-    if (npix) {
-        HIPCHK(mh, m->d_npix.reserve((size_t)nframes * sizeof(int32_t), m->epoch));
-        HIPCHK(mh, hipMemsetAsync(m->d_npix, 0, (size_t)nframes * sizeof(int32_t), s));
-    }
-    // the poses where the board batch left them: each worker holds its own frames' boards
-    for (const Span& sp : h->last.cut(nframes)) {
-        const arucohip_board_t* boards = sp.w->d_board;
-        launch_chroma_geometry(s, m->cam, sp.count, boards, (const float*)(boards + sp.w->cap_frames), min_prob, nullptr, nullptr, m->d_bgeom + sp.first);
-    }
-    HIPCHK(mh, hipGetLastError());
-    m->last_batch = nframes;
-    // frames and masks where they are; host sides go through staging, 64 MB of frames at a time (and at most 65535 per launch)
-    const bool direct = frames_on_device && masks_on_device;
-    const int piece = direct ? 65535 : (int)std::max<size_t>(1, std::min<size_t>(65535, ((size_t)64 << 20) / px));
-    if (!frames_on_device) HIPCHK(mh, m->d_bframes.reserve(std::min(nframes, piece) * px, m->epoch));
-    if (!masks_on_device) HIPCHK(mh, m->d_bmasks.reserve(std::min(nframes, piece) * px, m->epoch));
-    for (int first = 0; first < nframes; first += piece) {
-        const int cnt = std::min(piece, nframes - first);
-        const uint8_t* src = frames + (size_t)first * frame_stride;
-        size_t rs = row_stride, fs = frame_stride;
-        if (!frames_on_device) {
-            for (int f = 0; f < cnt; f++)
-                HIPCHK(mh, hipMemcpy2DAsync(m->d_bframes + (size_t)f * px, W, src + (size_t)f * frame_stride, row_stride, W, H, hipMemcpyHostToDevice, s));
-            src = m->d_bframes, rs = W, fs = px;
-        }
-        uint8_t* dst = masks_on_device ? masks + (size_t)first * px : (uint8_t*)m->d_bmasks;
-        launch_chroma_classify(s, m->cam, method, m->thresh, cnt, src, rs, fs, m->d_bgeom + first, m->d_prob, m->d_inside, dst,
-                               npix ? (int32_t*)m->d_npix + first : nullptr);
-        HIPCHK(mh, hipGetLastError());
-        if (!masks_on_device) HIPCHK(mh, hipMemcpyAsync(masks + (size_t)first * px, dst, (size_t)cnt * px, hipMemcpyDeviceToHost, s));
-    }
-    if (npix) HIPCHK(mh, hipMemcpyAsync(npix, m->d_npix, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(mh, hipStreamSynchronize(s));
-    return ARUCOHIP_OK;
-}
-
 // SURVEY §8 row f4, batched: Marker::glGetModelViewMatrix (src/marker.h:90) for every marker of the last batch in one launch
 int arucohip_gl_modelview_batch(arucohip_handle* h, int nframes, int cap, double* modelview, int32_t* n_out) {
     if (!h || !modelview || !n_out || cap < 1) return ARUCOHIP_E_INVALID;
@@ -2213,7 +1496,7 @@ int arucohip_gl_modelview_batch(arucohip_handle* h, int nframes, int cap, double
     arucohip_handle* w = r.span[0].w;
     HIPCHK(h, hipSetDevice(h->device));
     const size_t need = (size_t)nframes * cap * 16 * sizeof(double);
-    HIPCHK(h, w->d_gl.reserve(need, w->alloc_epoch));
+    HIPCHK(h, w->d_gl.reserve(need));
     launch_gl_modelview(w->stream, nframes, cap, w->buf, w->d_gl);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(modelview, w->d_gl, need, hipMemcpyDeviceToHost, w->stream));
@@ -2459,212 +1742,6 @@ int arucohip_detect_batch_wait(arucohip_handle* h, int ticket) {
     h->last = l->last;
     if (rc) h->err = l->err;
     return rc;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------
-// Highly reliable marker dictionaries and boards (k_hrm.hip): HighlyReliableMarkers::createDicitionary and createBoardImage
-// (src/highlyreliablemarkers.cpp:498-608). The scratch is the handle's d_hrm_gen, outside alloc_epoch: these calls never invalidate the
-// single-frame graph.
-// ---------------------------------------------------------------------------------------------
-namespace {
-constexpr int S31 = ah::HRM_STATE;
-typedef std::vector<uint32_t> M31;   // 31 x 31, row-major, mod 2^32 (uint32 arithmetic wraps)
-
-M31 m31_mul(const M31& A, const M31& B) {
-    M31 C(S31 * S31, 0);
-    for (int i = 0; i < S31; i++)
-        for (int k = 0; k < S31; k++) {
-            const uint32_t a = A[i * S31 + k];
-            if (!a) continue;
-            for (int j = 0; j < S31; j++) C[i * S31 + j] += a * B[k * S31 + j];
-        }
-    return C;
-}
-
-// M^k, M the step (r[i-31] .. r[i-1]) -> (r[i-30] .. r[i])
-M31 m31_pow(uint64_t k) {
-    M31 R(S31 * S31, 0), P(S31 * S31, 0);
-    for (int i = 0; i < S31; i++) R[i * S31 + i] = 1;
-    for (int j = 0; j + 1 < S31; j++) P[j * S31 + j + 1] = 1;
-    P[30 * S31 + 0] = P[30 * S31 + 28] = 1;
-    for (; k; k >>= 1) {
-        if (k & 1) R = m31_mul(R, P);
-        if (k > 1) P = m31_mul(P, P);
-    }
-    return R;
-}
-
-// srand(seed): r[0] = seed as int32 (0 -> 1), r[1..30] by the 16807 LCG (Schrage, C division), r[31..33] = r[0..2], then the recurrence
-// up to r[343]. The state at output 0 is r[313..343].
-void hrm_state0(uint32_t seed, uint32_t out[S31]) {
-    int64_t r0 = (int32_t)seed;
-    if (r0 == 0) r0 = 1;
-    std::vector<uint32_t> r(344);
-    r[0] = (uint32_t)r0;
-    int64_t word = r0;
-    for (int i = 1; i < 31; i++) {
-        const int64_t hi = word / 127773, lo = word % 127773;
-        word = 16807 * lo - 2836 * hi;
-        if (word < 0) word += 2147483647;
-        r[i] = (uint32_t)word;
-    }
-    for (int i = 31; i < 34; i++) r[i] = r[i - 31];
-    for (int i = 34; i < 344; i++) r[i] = r[i - 31] + r[i - 3];
-    for (int i = 0; i < S31; i++) out[i] = r[313 + i];
-}
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-}  // namespace
-
-extern "C" {
-
-int arucohip_hrm_create_dictionary(arucohip_handle* h, int n, int dict_size, uint32_t seed, uint64_t* codes_out, int* tau0,
-                                   int64_t* candidates_examined) {
-    if (!h) return ARUCOHIP_E_INVALID;
-    if (n < 3 || n > 8) return fail(h, ARUCOHIP_E_INVALID, "hrm_create_dictionary: n must be 3..8 (n = 2 divides by zero in the reference)");
-    if (dict_size < 1 || dict_size > 4096) return fail(h, ARUCOHIP_E_INVALID, "hrm_create_dictionary: dict_size must be 1..4096");
-    if (!codes_out) return fail(h, ARUCOHIP_E_INVALID, "hrm_create_dictionary: NULL codes_out");
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t jbytes = (size_t)(HRM_LANE_BITS + 1) * S31 * S31 * sizeof(uint32_t);
-    const size_t o_state = align256(jbytes), o_ctl = o_state + 256, o_code = o_ctl + 256, o_self = o_code + (size_t)HRM_WINDOW * 8,
-                 o_dmin = o_self + HRM_WINDOW, o_dict = o_dmin + HRM_WINDOW, total = o_dict + (size_t)4096 * 4 * sizeof(uint64_t);
-    HIPCHK(h, h->d_hrm_gen.reserve(total, h->hrm_epoch));
-    uint8_t* b = h->d_hrm_gen;
-    HrmBufs bufs{(uint32_t*)(b + o_state), (uint32_t*)b, (uint64_t*)(b + o_code), b + o_self, b + o_dmin, (uint64_t*)(b + o_dict),
-                 (HrmCtl*)(b + o_ctl)};
-    // J_b = M^(HRM_LANE_CANDS n^2 2^b): lane l starts at J applied for the bits of l; the last one is a whole window
-    std::vector<uint32_t> jumps;
-    M31 J = m31_pow((uint64_t)HRM_LANE_CANDS * n * n);
-    for (int bit = 0; bit <= HRM_LANE_BITS; bit++) {
-        jumps.insert(jumps.end(), J.begin(), J.end());
-        if (bit < HRM_LANE_BITS) J = m31_mul(J, J);
-    }
-    uint32_t st[S31];
-    hrm_state0(seed, st);
-    const int tau_init = 2 * ((4 * ((n * n) / 4)) / 3);
-    HrmCtl c{};
-    c.tau = tau_init, c.count = 0, c.limit = HRM_LIMIT, c.dsize = 0, c.base = 0, c.status = HRM_RUNNING;
-    hipStream_t s = h->stream;
-    HIPCHK(h, hipMemcpyAsync(bufs.jumps, jumps.data(), jbytes, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(bufs.state, st, sizeof(st), hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(bufs.ctl, &c, sizeof(c), hipMemcpyHostToDevice, s));
-    // the reference examines at most (dict_size + tau) * 100000 candidates: every acceptance and every decrement resets the count
-    const int64_t max_windows = ((int64_t)(dict_size + tau_init) * HRM_LIMIT + HRM_WINDOW - 1) / HRM_WINDOW + 1;
-    int syncs = 0;
-    for (int64_t w = 0; w < max_windows; w++) {
-        launch_hrm_window(s, n, dict_size, bufs);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(&c, bufs.ctl, sizeof(c), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));   // the one host synchronisation of a window
-        syncs++;
-        if (c.status != HRM_RUNNING) break;
-    }
-    h->hrm_stats[0] = c.windows, h->hrm_stats[1] = syncs, h->hrm_stats[2] = c.accepted, h->hrm_stats[3] = c.decrements;
-    if (c.status == HRM_TAU_ZERO)
-        return fail(h, ARUCOHIP_E_INVALID, "hrm_create_dictionary: tau reached 0 (too many markers for this marker size; CV_Error in the reference)");
-    if (c.status != HRM_DONE) return fail(h, ARUCOHIP_E_HIP, "hrm_create_dictionary: the window walk did not finish");
-    std::vector<uint64_t> rot((size_t)dict_size * 4);
-    HIPCHK(h, hipMemcpyAsync(rot.data(), bufs.dict, rot.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    for (int i = 0; i < dict_size; i++) codes_out[i] = rot[(size_t)i * 4];
-    if (tau0) *tau0 = c.tau;
-    if (candidates_examined) *candidates_examined = c.examined;
-    return ARUCOHIP_OK;
-}
-
-int arucohip_debug_hrm_counters(arucohip_handle* h, int32_t out[4]) {
-    if (!h || !out) return ARUCOHIP_E_INVALID;
-    for (int i = 0; i < 4; i++) out[i] = h->hrm_stats[i];
-    return ARUCOHIP_OK;
-}
-
-int arucohip_debug_hrm_stream(arucohip_handle* h, uint32_t seed, uint64_t offset, int count, uint32_t* out) {
-    if (!h) return ARUCOHIP_E_INVALID;
-    if (!out || count < 0 || count > (1 << 24) || offset + (uint64_t)count >= (1ull << HRM_POW_BITS))
-        return fail(h, ARUCOHIP_E_INVALID, "debug_hrm_stream: count must be 0..2^24 and offset + count below 2^48");
-    if (count == 0) return ARUCOHIP_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t pbytes = (size_t)HRM_POW_BITS * S31 * S31 * sizeof(uint32_t), o_state = align256(pbytes), o_out = o_state + 256,
-                 total = o_out + (size_t)count * sizeof(uint32_t);
-    HIPCHK(h, h->d_hrm_gen.reserve(total, h->hrm_epoch));
-    uint8_t* b = h->d_hrm_gen;
-    std::vector<uint32_t> pow2;
-    M31 P = m31_pow(1);
-    for (int bit = 0; bit < HRM_POW_BITS; bit++) {
-        pow2.insert(pow2.end(), P.begin(), P.end());
-        P = m31_mul(P, P);
-    }
-    uint32_t st[S31];
-    hrm_state0(seed, st);
-    hipStream_t s = h->stream;
-    HIPCHK(h, hipMemcpyAsync(b, pow2.data(), pbytes, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(b + o_state, st, sizeof(st), hipMemcpyHostToDevice, s));
-    launch_hrm_stream(s, (const uint32_t*)(b + o_state), (const uint32_t*)b, offset, count, (uint32_t*)(b + o_out));
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out, b + o_out, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return ARUCOHIP_OK;
-}
-
-int arucohip_hrm_board_size(int n, int grid_w, int grid_h, int chromatic, int* width, int* height, int* channels) {
-    if (n < 3 || n > 8 || grid_w < 1 || grid_h < 1 || grid_w > 128 || grid_h > 128 || !width || !height || !channels) return ARUCOHIP_E_INVALID;
-    const int ms = (n + 2) * 20, gap = ms / 5, margin = chromatic ? 2 * gap : 0;
-    *width = grid_w * ms + (grid_w - 1) * gap + margin;
-    *height = grid_h * ms + (grid_h - 1) * gap + margin;
-    *channels = chromatic ? 3 : 1;
-    return ARUCOHIP_OK;
-}
-
-int arucohip_hrm_board_image(arucohip_handle* h, int n, int count, const uint64_t* codes, int grid_w, int grid_h, int chromatic, uint8_t* image,
-                             size_t row_stride, int image_on_device, int32_t* ids, float* obj) {
-    if (!h) return ARUCOHIP_E_INVALID;
-    int W = 0, H = 0, ch = 0;
-    if (arucohip_hrm_board_size(n, grid_w, grid_h, chromatic, &W, &H, &ch) != ARUCOHIP_OK)
-        return fail(h, ARUCOHIP_E_INVALID, "hrm_board_image: n must be 3..8 and the grid 1..128 x 1..128");
-    const int nb = grid_w * grid_h;
-    if (!codes || !image || row_stride < (size_t)W * ch) return fail(h, ARUCOHIP_E_INVALID, "hrm_board_image: NULL codes / image or row_stride too small");
-    if (count < nb) return fail(h, ARUCOHIP_E_INVALID, "hrm_board_image: fewer codes than grid cells (the reference reads past the dictionary)");
-    if (ids && n >= 6)
-        return fail(h, ARUCOHIP_E_UNSUPPORTED, "hrm_board_image: getId() shifts past 32 bits for n >= 6 (undefined in the reference); pass ids = NULL");
-    const uint64_t valid = n == 8 ? ~0ull : (1ull << (n * n)) - 1;
-    for (int i = 0; i < nb; i++)
-        if (codes[i] & ~valid) return fail(h, ARUCOHIP_E_INVALID, "hrm_board_image: a code has bits past n * n");
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t stride = ((size_t)W * ch + 15) & ~(size_t)15, o_img = align256((size_t)nb * sizeof(uint64_t)), total = o_img + stride * H;
-    HIPCHK(h, h->d_hrm_gen.reserve(total, h->hrm_epoch));
-    uint8_t* b = h->d_hrm_gen;
-    hipStream_t s = h->stream;
-    HIPCHK(h, hipMemcpyAsync(b, codes, (size_t)nb * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    launch_hrm_board(s, (const uint64_t*)b, n, grid_w, grid_h, chromatic ? 1 : 0, W, H, ch, stride, b + o_img);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpy2DAsync(image, row_stride, b + o_img, stride, (size_t)W * ch, H, image_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-    // BC.ids (getId(): sum of 2 << pos) and BC.objPoints, on the host in the reference's float arithmetic
-    const unsigned ms = (unsigned)(n + 2) * 20, gap = ms / 5;
-    const int sx = grid_w * (int)ms + (grid_w - 1) * (int)gap, sy = grid_h * (int)ms + (grid_h - 1) * (int)gap;
-    const float cx = (float)(sx / 2.), cy = (float)(sy / 2.);
-    for (int y = 0, idp = 0; y < grid_h; y++)
-        for (int x = 0; x < grid_w; x++, idp++) {
-            if (ids) {
-                uint32_t id = 0;
-                for (int p = 0; p < n * n; p++)
-                    if ((codes[idp] >> p) & 1) id |= 2u << p;
-                ids[idp] = (int32_t)id;
-            }
-            if (obj) {
-                const unsigned ox = (unsigned)x * (gap + ms), oy = (unsigned)y * (gap + ms);
-                const unsigned px[4] = {ox, ox + ms, ox + ms, ox}, py[4] = {oy, oy, oy + ms, oy + ms};
-                for (int k = 0; k < 4; k++) {
-                    float* o = obj + (size_t)idp * 12 + 3 * k;
-                    o[0] = (float)px[k] - cx;
-                    o[1] = -((float)py[k] - cy);
-                    o[2] = 0.f;
-                }
-            }
-        }
-    HIPCHK(h, hipStreamSynchronize(s));
-    return ARUCOHIP_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,209 @@
+// Private host-side header of libarucohip's C ABI (capi*.hip): the handle, the memory it owns and the helpers those files share.
+// Kernel files never include it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <array>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "internal.h"
+
+using namespace ah;
+
+// one event after every kernel of a batch; a ring of TSETS batches so that asynchronous steps can be averaged
+// slot k = the interval between mark k and mark k + 1. walker_long = the generations of long walks up to the fork of the side
+// stream; contour_quad = both passes including the wait for the side stream's late generations.
+enum { K_THRESHOLD = 0, K_FILTER, K_WALKERS, K_WALKERS_LONG, K_CONTOUR_QUADS, K_FRAME_CANDS, K_DECODE, K_REFINE_LINES, K_REFINE_PIXELS, K_FINALIZE, K_POSE, K_COUNT };
+constexpr int TSETS = 32;
+
+// Memory the handle owns: device memory, or pinned host memory for staging the host reads. reserve() replaces the allocation only when
+// `need` exceeds the capacity (exact size, no slack, never shrinks). The destructor frees.
+template <typename T>
+struct Mem {
+    T* p = nullptr;
+    size_t bytes = 0;
+    bool pinned = false;
+    explicit Mem(bool pinned_ = false) : pinned(pinned_) {}
+    Mem(Mem&& o) noexcept : p(o.p), bytes(o.bytes), pinned(o.pinned) { o.p = nullptr, o.bytes = 0; }
+    ~Mem() { (void)release(); }
+    operator T*() const { return p; }
+    hipError_t reserve(size_t need) {
+        if (need <= bytes) return hipSuccess;
+        hipError_t e = release();
+        if (e == hipSuccess) e = pinned ? hipHostMalloc((void**)&p, need) : hipMalloc((void**)&p, need);
+        if (e == hipSuccess)
+            bytes = need;
+        else
+            p = nullptr;
+        return e;
+    }
+
+private:
+    hipError_t release() {
+        const hipError_t e = p ? (pinned ? hipHostFree(p) : hipFree(p)) : hipSuccess;
+        p = nullptr, bytes = 0;
+        return e;
+    }
+};
+
+constexpr int MAX_WORKERS = 8;   // chunk workers of a handle, itself included (ARUCOHIP_STREAMS)
+
+// A batch as the workers hold it: chunk c of its frames ran on worker c (chunk_worker). The handle the caller holds keeps the last one
+// (arucohip_handle::last): every call that replaces the device lists sets it whole, from plan_batch, or clears it when they no longer
+// hold a batch; a waited ticket adopts its lane's. The getters, board poses, calibration and ChromaticMask read it and nothing else.
+struct Span { arucohip_handle* w; int first, count; };   // worker w holds frames [first, first + count)
+struct Batch {
+    int nspan = 0, frames = 0;
+    Span span[MAX_WORKERS] = {};
+    int W = 0, H = 0, nthr = 1;
+    int board_frames = 0;   // frames whose board poses arucohip_board_detect_batch left in the workers' d_board
+    const Span* begin() const { return span; }
+    const Span* end() const { return span + nspan; }
+    // the worker that holds frame `frame` and the frame's index there; nullptr: the batch has no such frame
+    arucohip_handle* holder(int frame, int* local) const {
+        for (const Span& s : *this)
+            if (frame >= s.first && frame < s.first + s.count) return *local = frame - s.first, s.w;
+        return nullptr;
+    }
+    // the spans of the first nframes frames
+    Batch cut(int nframes) const {
+        Batch b = *this;
+        b.nspan = 0, b.frames = std::min(frames, nframes);
+        for (const Span& s : *this)
+            if (s.first < nframes) b.span[b.nspan++] = {s.w, s.first, std::min(s.count, nframes - s.first)};
+        return b;
+    }
+};
+
+// highly reliable markers (arucohip_set_dictionary); count 0: none
+struct Dictionary {
+    int n = 0, count = 0, tau0 = 0;
+    float rate = 1.f;
+    std::vector<uint64_t> codes;   // kept on the host as well: a new child takes them without reading the device copy back
+};
+
+struct arucohip_handle {
+    int device = 0;
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    arucohip_params_t params;
+    arucohip_limits_t lim;
+    Buffers buf{};                    // views: the create-time arrays live in `held`, walk_scratch and patches below
+    std::vector<Mem<void>> held;      // create-time memory, held for the handle's life: the Buffers arrays, zero_block, d_small_*, d_patch, pinned staging
+    Mem<uint32_t> walk_scratch;       // buf.walk_scratch
+    Mem<uint8_t> patches;             // buf.patches
+    Mem<uint8_t> d_gray;              // staging for host frames (gray) and the converted BGR frames
+    Mem<uint8_t> d_bgr;               // staging for host BGR frames
+    arucohip_marker_t* wt_out = nullptr;   // set around detect_core by chunk_enqueue: finalize_kernel writes the results there too
+    int32_t* wt_n = nullptr;
+    int wt_cap = 0;
+    Mem<uint8_t> d_erode;             // eroded planes (params.erode)
+    Mem<uint64_t> d_canny;            // CANNY: survivor tiles, edge tiles, changed flag
+    // frame undistortion (arucohip_undistort): the map of the last camera is kept (umap_nd = -1: none)
+    Mem<short2> d_umap_xy;
+    Mem<uint16_t> d_umap_f;
+    int umap_w = 0, umap_h = 0, umap_nd = -1;
+    float umap_K[9] = {}, umap_d[8] = {};
+    Mem<uint8_t> d_undist;            // undistorted frames when the caller wants them on the host
+    Dictionary hrm;
+    Mem<uint64_t> d_hrm;              // hrm.codes on the device
+    // caller's own decoder (arucohip_set_decoder_callback)
+    arucohip_decoder_fn decoder_fn = nullptr;
+    void* decoder_user = nullptr;
+    Mem<int2> d_user_dec;             // [cap_flat] {id, nRotations} returned by the callback
+    Mem<uint32_t> hu_list{true};      // pinned staging of the callback path: candidate list, decoder results, call order
+    Mem<uint8_t> hu_patches{true};    // pinned staging: the canonical patches handed to the callback (+ one scratch patch)
+    size_t bits_bytes = 0;
+    int bits_w = 0, bits_h = 0;       // geometry the bit image was last written with (pad words depend on it)
+    // pinned host staging
+    arucohip_marker_t* h_markers = nullptr;
+    int32_t* h_n = nullptr;
+    uint32_t* h_counters = nullptr;
+    // small device scratch for the stage-level calls
+    float* d_small_f = nullptr;       // 4096 floats
+    double* d_small_d = nullptr;      // 64 doubles
+    int* d_small_i = nullptr;
+    uint8_t* d_patch = nullptr;       // MAX_WARP^2
+    Mem<arucohip_board_t> d_board;    // batched board results + ids
+    uint32_t* zero_block = nullptr;   // counters, gen_cnt, trig_cnt, raw_cnt, ring_cnt: zeroed together at the start of a batch
+    size_t zero_words = 0;
+    Mem<double> d_gl;                 // batched GL modelview matrices
+    Mem<uint8_t> d_calib;             // camera calibration: solver state, per-view systems and poses, correspondences (calib_carve)
+    Mem<CalibState> hc_calib{true};   // pinned copy of the solver state, read once per iteration
+    Batch last;                       // the last batch (kept on the handle the caller holds)
+    bool timing = false;
+    hipEvent_t ev[TSETS][K_COUNT + 1] = {};
+    int tsets = 0;                       // batches recorded since the last reset
+    float kernel_ms[K_COUNT] = {};       // averages over the recorded batches
+    // Sub-batch pipelining: a batch larger than cap_frames is cut into up to nsub chunks; chunk 0 runs on this handle and
+    // the caller's stream, chunk i on chunk worker i (chunk_worker) and its own stream, so the latency-bound kernels of one chunk (border
+    // following, Otsu) overlap the bandwidth-bound ones of another and host frames are copied while earlier chunks compute.
+    int nsub = 1, cap_frames = 1;        // workers, frames each worker's buffers hold
+    std::vector<arucohip_handle*> kids;
+    hipEvent_t ev_fork = nullptr, ev_join[MAX_WORKERS] = {};
+    hipStream_t side_stream = nullptr;   // late walker generations (k_contours.hip)
+    hipEvent_t ev_wfork = nullptr, ev_wjoin = nullptr;
+    hipEvent_t ev_thr = nullptr;         // this worker's threshold kernel has finished (staggers the chunks, see detect_batch)
+    bool thres_bytes = true;             // buf.thres holds the last batch's byte image (else: tiles + buf.thres_edge, expanded on demand)
+    hipEvent_t wait_thr = nullptr;       // set by detect_batch: event the next threshold kernel waits for
+    Mem<uint8_t> d_em;                   // arucohip_em_fit scratch
+    Mem<uint8_t> d_hrm_gen;              // HRM dictionary / board generation scratch (k_hrm.hip)
+    int32_t hrm_stats[4] = {};           // the last arucohip_hrm_create_dictionary: windows, host synchronisations, acceptances, tau decrements
+    // One frame per call (the reference's call shape, arucohip_detect): the chain of ~20 dependent dispatches of a frame is captured once per
+    // (geometry, parameters, camera) into a hipGraph and replayed with ONE launch per call; the frame's H2D copy stays outside (its source
+    // pointer changes with every call), the results land in the handle's pinned staging inside the graph.
+    // The captured launches carry device addresses by value; a replay needs every one of them to be live and as large as at the capture:
+    // - in the value key: dp.hrm_codes (d_hrm), and buf.thr_stamp_on, which picks the threshold kernel's stamp pointer;
+    // - compared with `addrs` before a replay and after a capture: gray_dev (d_gray for host gray and BGR frames), buf.walk_scratch and
+    //   buf.patches, which calls of other shapes grow. An equal address is enough, since reserve() never shrinks;
+    // - neither: the other Buffers arrays, zero_block and h_markers are create-time memory (`held`); d_erode, d_canny and the user decoder's
+    //   staging belong to configurations that are not graphed; wt_out is set only inside chunk_enqueue and wait_thr only on chunk workers
+    //   after the first, neither of which runs this path. Memory no captured launch reads (d_bgr, undistortion, calibration, board and GL
+    //   batches, EM, HRM and ChromaticMask scratch) may be replaced at any time.
+    struct FrameGraph {
+        hipGraphExec_t exec = nullptr;
+        uint64_t key = 0;          // digest of everything the captured launches carry by value
+        uint64_t seen = 0;         // key of the previous eager call: the second call with the same key captures (buffers are sized by then)
+        std::array<const void*, 3> addrs{};   // gray_dev, buf.walk_scratch and buf.patches at the capture
+        bool thres_bytes = false;  // what the captured threshold left in buf.thres (a replay sets thres_bytes to it)
+        int disabled = 0;          // ARUCOHIP_GRAPH=0, or a capture failed once
+    } fgraph;
+    // Batches in flight (arucohip_set_pipeline_depth / _submit / _wait): every pipeline lane is a complete worker (own
+    // buffers, own stream); ticket t runs on lane t mod depth, so the latency-bound tail of batch t (border following,
+    // decoding) overlaps the bandwidth-bound head of batch t+1.
+    std::vector<arucohip_handle*> lanes;
+    int next_ticket = 0;
+    arucohip_handle* retry = nullptr;    // one-frame handle with larger lists for frames that overflowed (arucohip_detect_batch_retry_overflowed)
+    int retry_mult = 0;
+    hipEvent_t ev_submit = nullptr;
+    struct Pending {
+        bool active = false;
+        int ticket = -1, cap = 0, out_on_device = 0;
+        arucohip_marker_t* out = nullptr;
+        int32_t* n_out = nullptr;
+    } pend;
+    std::string err;
+};
+
+#define HIPCHK(h, expr)                                                                         \
+    do {                                                                                        \
+        hipError_t e_ = (expr);                                                                 \
+        if (e_ != hipSuccess) {                                                                 \
+            char buf_[256];                                                                     \
+            snprintf(buf_, sizeof(buf_), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+            (h)->err = buf_;                                                                    \
+            return ARUCOHIP_E_HIP;                                                              \
+        }                                                                                       \
+    } while (0)
+
+inline int fail(arucohip_handle* h, int code, const char* msg) {
+    if (h) h->err = msg;
+    return code;
+}
+
+// fork: the other workers' streams wait for what the first worker's stream (the batch's own) has queued so far; errors are reported on h
+int fork_workers(arucohip_handle* h, const Batch& b);
+// join: the first worker's stream waits for the others
+int join_workers(arucohip_handle* h, const Batch& b);

@@ -209,8 +209,8 @@ def test_board_stream_end_to_end(monkeypatch, streams):
 
 
 def test_detect_graph_after_calibration(monkeypatch):
-    """detect x3 (the third replays the captured single-frame graph), a calibration that allocates (alloc_epoch rises), detect: the
-    bytes of every result equal an ARUCOHIP_GRAPH=0 handle's."""
+    """detect x3 (the third replays the captured single-frame graph), a calibration that allocates scratch no captured launch reads, detect:
+    the bytes of every result equal an ARUCOHIP_GRAPH=0 handle's."""
     from aruco_amd import capi
     from tests.util import load_case
 

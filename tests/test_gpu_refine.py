@@ -193,3 +193,43 @@ def test_single_frame_graph_follows_batches_and_stage_calls_in_between(case, con
         same(lambda h: h.thresholded(0, (hgt, wid)))
     finally:
         eager.close(), graphed.close()
+
+
+def test_single_frame_graph_follows_bgr_batches_and_survives_undistort(monkeypatch):
+    """The graph of a BGR frame reads the converted frame in d_gray. A batch of 4 BGR host frames regrows d_gray, so the next detect_bgr
+    must drop the graph and capture again; an undistort of 4 gray frames grows only staging no captured launch reads (d_bgr, d_undist), so
+    the graph is kept. Eager handle (ARUCOHIP_GRAPH=0 at creation) against the default handle, the same calls on both: detect_bgr x3, a
+    BGR batch of 4, detect_bgr x2, undistort, detect_bgr x2 - identical bytes at every step."""
+    from aruco_amd import capi
+
+    gray, doc = load_case("single")
+    K, dist = doc["intrinsics"]["K"], doc["intrinsics"]["dist"]
+    grays = np.stack([gray, gray[:, ::-1], gray[::-1], gray[::-1, ::-1]])
+    bgrs = np.ascontiguousarray(np.stack([grays, grays, grays], axis=-1))
+    hgt, wid = gray.shape
+    kw = dict(K=K, dist=dist, marker_size=1.0)
+    monkeypatch.setenv("ARUCOHIP_GRAPH", "0")
+    eager = capi.Handle(wid, hgt, max_batch=4)
+    monkeypatch.delenv("ARUCOHIP_GRAPH")
+    graphed = capi.Handle(wid, hgt, max_batch=4)
+
+    def same(call):
+        want, got = call(eager), call(graphed)
+        if isinstance(want, list):
+            assert [x.tobytes() for x in got] == [x.tobytes() for x in want]
+        else:
+            assert got.tobytes() == want.tobytes()
+        return want
+
+    try:
+        assert len(same(lambda h: h.detect_bgr(bgrs[0], **kw))) >= 1
+        for _ in range(2):
+            same(lambda h: h.detect_bgr(bgrs[0], **kw))
+        same(lambda h: h.detect_batch_bgr_host(bgrs, **kw))
+        for _ in range(2):
+            same(lambda h: h.detect_bgr(bgrs[1], **kw))
+        same(lambda h: h.undistort(grays, K, dist))
+        for _ in range(2):
+            same(lambda h: h.detect_bgr(bgrs[0], **kw))
+    finally:
+        eager.close(), graphed.close()
