@@ -21,41 +21,25 @@ namespace ah {
 void launch_rotate_x(hipStream_t s, double* rt);
 }
 
-namespace ah {
-Tuning read_tuning() {
-    Tuning t;
+// the environment's switches, read when the caller creates a handle (every getenv of the handle is here)
+static EnvSettings read_env() {
+    EnvSettings v;
     auto geti = [](const char* name, int dflt) {
         const char* e = getenv(name);
         return (e && *e) ? atoi(e) : dflt;
     };
-    t.walk_fork = geti("ARUCOHIP_WALK_FORK", 1) != 0;
-    t.chain = geti("ARUCOHIP_CHAIN", 0) != 0;
-    t.cand_sparse = geti("ARUCOHIP_CAND_SPARSE", 1) != 0;
-    t.cand_waves = std::max(1, geti("ARUCOHIP_CAND_WAVES", 32));
-    t.cand_chunks = std::max(1, geti("ARUCOHIP_CAND_CHUNKS", 16));
-    t.leash = geti("ARUCOHIP_LEASH", 0);
-    t.fork_after = geti("ARUCOHIP_FORK_AFTER", 3);
-    t.quad_blocks = std::max(1, geti("ARUCOHIP_QUAD_BLOCKS", 12));
-    t.quad_dual = geti("ARUCOHIP_QUAD_DUAL", 1) != 0;
-    t.seg_skip = geti("ARUCOHIP_SEG_SKIP", 1) != 0;
-    t.gen_xcd = geti("ARUCOHIP_GEN_XCD", 1) != 0;
-    t.threshold_wide = geti("ARUCOHIP_THRESHOLD_WIDE", 1) != 0;
-    t.threshold_eo = geti("ARUCOHIP_THRESHOLD_EO", 1) != 0;
+    if (const char* e = getenv("ARUCOHIP_STREAMS")) v.streams = std::min(MAX_WORKERS, std::max(1, atoi(e)));
+    v.graph = geti("ARUCOHIP_GRAPH", 1) != 0;
+    if (const char* e = getenv("ARUCOHIP_CONTOURS")) v.contours = std::string(e) == "segments";
+    if (const char* e = getenv("ARUCOHIP_GRID")) v.grid = atoi(e);
+    if (v.grid != 1 && v.grid != 2 && v.grid != 4 && v.grid != 8 && v.grid != 16 && v.grid != 32) v.grid = 8;
+    v.thres_lazy = geti("ARUCOHIP_THRES_BYTES", 0) == 0;
+    v.quad_dual = geti("ARUCOHIP_QUAD_DUAL", 1) != 0;
 #ifdef ARUCOHIP_STAGE_EXPERIMENT
-    t.stop_after = geti("ARUCOHIP_STOP_AFTER", 99);   // truncates the pipeline: results are meaningless, only the step time is
+    v.stop_after = geti("ARUCOHIP_STOP_AFTER", 99);   // truncates the pipeline: results are meaningless, only the step time is
 #endif
-    t.thres_lazy = geti("ARUCOHIP_THRES_BYTES", 0) == 0;
-    if (const char* e = getenv("ARUCOHIP_GENS")) {
-        for (const char* q = e; *q && t.ngens < 32;) {
-            const int v = atoi(q);
-            if (v > 0) t.gens[t.ngens++] = v;
-            while (*q && *q != ',') q++;
-            if (*q == ',') q++;
-        }
-    }
-    return t;
+    return v;
 }
-}  // namespace ah
 
 enum { STAGE_THRESHOLD = 0, STAGE_RECTANGLES, STAGE_IDENTIFY, STAGE_SUBPIXEL, STAGE_FILTERING, STAGE_COUNT };
 static const char* kStageNames[STAGE_COUNT] = {"Threshold", "Rectangles", "Identify", "Subpixel", "Filtering"};
@@ -163,7 +147,6 @@ static void release(arucohip_handle* h) {
     if (h->fgraph.exec) hipGraphExecDestroy(h->fgraph.exec);
     if (h->ev_submit) hipEventDestroy(h->ev_submit);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
-    if (h->ev_thr) hipEventDestroy(h->ev_thr);
     if (h->ev_wfork) hipEventDestroy(h->ev_wfork);
     if (h->ev_wjoin) hipEventDestroy(h->ev_wjoin);
     if (h->side_stream) hipStreamDestroy(h->side_stream);
@@ -216,12 +199,13 @@ static int inherit(arucohip_handle* parent, arucohip_handle* child) {
     });
 }
 
-// is_kid: the handle is one of another's chunk workers and gets none of its own
-static int create_handle(const arucohip_params_t* params, int device, const arucohip_limits_t* lim, bool is_kid, arucohip_handle** out);
+// is_kid: the handle is one of another's chunk workers and gets none of its own; env: the switches of the handle the caller creates
+static int create_handle(const arucohip_params_t* params, int device, const arucohip_limits_t* lim, bool is_kid, const EnvSettings& env,
+                         arucohip_handle** out);
 
-// a new child of `parent` with limits `lim`, holding the parent's settings (errors are reported on the parent)
+// a new child of `parent` with limits `lim`, holding the parent's settings and environment switches (errors are reported on the parent)
 static int create_child(arucohip_handle* parent, const arucohip_limits_t& lim, bool is_kid, arucohip_handle** out) {
-    int rc = create_handle(&parent->params, parent->device, &lim, is_kid, out);
+    int rc = create_handle(&parent->params, parent->device, &lim, is_kid, parent->buf.env, out);
     if (rc == ARUCOHIP_OK && (rc = inherit(parent, *out)) != ARUCOHIP_OK) {
         arucohip_destroy(*out);
         *out = nullptr;
@@ -229,7 +213,8 @@ static int create_child(arucohip_handle* parent, const arucohip_limits_t& lim, b
     return rc;
 }
 
-static int create_handle(const arucohip_params_t* params, int device, const arucohip_limits_t* lim, bool is_kid, arucohip_handle** out) {
+static int create_handle(const arucohip_params_t* params, int device, const arucohip_limits_t* lim, bool is_kid, const EnvSettings& env,
+                         arucohip_handle** out) {
     if (!out || !lim) return ARUCOHIP_E_INVALID;
     *out = nullptr;
     if (lim->max_width < 32 || lim->max_height < 32 || lim->max_width > 16383 || lim->max_height > 16383 || lim->max_batch < 1 ||
@@ -257,23 +242,15 @@ static int create_handle(const arucohip_params_t* params, int device, const aruc
     if ((e = hipSetDevice(device)) != hipSuccess) return bail(e);
     if ((e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking)) != hipSuccess) return bail(e);
     h->stream = h->own_stream;
-    {
-        // workers: one by default; ARUCOHIP_STREAMS = 2..8 cuts large batches into chunks on separate streams (copies of host
-        // frames then overlap the kernels). With the late walker generations on their own side stream a second chunk stream
-        // no longer gains anything for device-resident frames (1 stream 208 k fps, 2 streams 208 k at 1024 1080p frames).
-        int ns = 1;
-        if (const char* es = getenv("ARUCOHIP_STREAMS")) ns = std::min(MAX_WORKERS, std::max(1, atoi(es)));
-        if (is_kid) ns = 1;
-        h->nsub = std::min(ns, lim->max_batch);
-        h->cap_frames = (lim->max_batch + h->nsub - 1) / h->nsub;
-    }
-    const size_t F = h->cap_frames, P = F * lim->max_thres_planes, px = (size_t)lim->max_width * lim->max_height;
     Buffers& b = h->buf;
-    b.tune = read_tuning();
-    {
-        const char* eg = getenv("ARUCOHIP_GRAPH");
-        h->fgraph.disabled = (eg && *eg && atoi(eg) == 0) ? 1 : 0;
-    }
+    b.env = env;
+    h->fgraph.disabled = env.graph ? 0 : 1;
+    // workers: one by default; ARUCOHIP_STREAMS = 2..8 cuts large batches into chunks on separate streams (copies of host frames then
+    // overlap the kernels), chunk workers have none of their own. With the late walker generations on their own side stream a second
+    // chunk stream no longer gains anything for device-resident frames (1 stream 208 k fps, 2 streams 208 k at 1024 1080p frames).
+    h->nsub = std::min(is_kid ? 1 : env.streams, lim->max_batch);
+    h->cap_frames = (lim->max_batch + h->nsub - 1) / h->nsub;
+    const size_t F = h->cap_frames, P = F * lim->max_thres_planes, px = (size_t)lim->max_width * lim->max_height;
     b.cap_raw = (uint32_t)lim->triggers_per_frame;
     b.cap_trig = (uint32_t)std::max(lim->triggers_per_frame, 8192);   // two halves: outer starts, hole starts
     b.long_cap = (uint32_t)std::min(std::max(lim->long_walks_per_plane, 64), 1 << 16);
@@ -305,12 +282,8 @@ static int create_handle(const arucohip_params_t* params, int device, const aruc
         // batches; a single small frame is a chain of up to max-contour dependent border steps for them, which the waypoint
         // segments cut (bench.py latency leg, 1000 calls: 640x480 stills 0.67-0.72 ms vs 0.49-0.52 ms; one 1080p frame 0.80 vs 0.51 since round 4:
         // per-plane workgroup counts scaled for one frame, the run rule read from the lane's block)
-        const char* mode = getenv("ARUCOHIP_CONTOURS");
-        b.seg_mode = mode ? std::string(mode) == "segments" : (lim->max_batch == 1 && (long)lim->max_width * lim->max_height <= 2048L * 1536L);
-        const char* gs = getenv("ARUCOHIP_GRID");
-        int grid = gs ? atoi(gs) : 16;
-        if (grid != 1 && grid != 2 && grid != 4 && grid != 8 && grid != 16 && grid != 32) grid = 8;
-        b.grid_mask = grid - 1;
+        b.seg_mode = env.contours >= 0 ? env.contours : (lim->max_batch == 1 && (long)lim->max_width * lim->max_height <= 2048L * 1536L);
+        b.grid_mask = env.grid - 1;
         uint32_t hs = 1;
         while (hs < 2u * b.cap_raw) hs <<= 1;
         b.hash_mask = hs - 1;
@@ -359,7 +332,6 @@ static int create_handle(const arucohip_params_t* params, int device, const aruc
     for (auto& set : h->ev)
         for (auto& ev : set)
             if ((e = hipEventCreate(&ev)) != hipSuccess) return bail(e);
-    if ((e = hipEventCreateWithFlags(&h->ev_thr, hipEventDisableTiming)) != hipSuccess) return bail(e);
     if ((e = hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking)) != hipSuccess) return bail(e);
     if ((e = hipEventCreateWithFlags(&h->ev_wfork, hipEventDisableTiming)) != hipSuccess) return bail(e);
     if ((e = hipEventCreateWithFlags(&h->ev_wjoin, hipEventDisableTiming)) != hipSuccess) return bail(e);
@@ -383,7 +355,7 @@ static int create_handle(const arucohip_params_t* params, int device, const aruc
 }
 
 int arucohip_create_ex(const arucohip_params_t* params, int device, const arucohip_limits_t* lim, arucohip_handle** out) {
-    return create_handle(params, device, lim, false, out);
+    return create_handle(params, device, lim, false, read_env(), out);
 }
 
 int arucohip_create(const arucohip_params_t* params, int device, int max_width, int max_height, int max_batch, arucohip_handle** out) {
@@ -665,20 +637,20 @@ static int run_rectangles(arucohip_handle* h, hipStream_t s, const FrameGeom& g,
         MARK(K_CONTOUR_QUADS);
         launch_contour_quads(s, g, nframes, dp, b);
     } else {
-        if (RUN_STAGE(b.tune, 1)) launch_start_candidates(s, g, nframes * dp.nthr, b, dp.min_contour);
+        if (RUN_STAGE(b.env, 1)) launch_start_candidates(s, g, nframes * dp.nthr, b, dp.min_contour);
         MARK(K_WALKERS);
         // walkers; their late generations run on the side stream under the first quad pass (the contour_quad mark sits at the fork)
-        WalkFork fk{b.tune.walk_fork ? h->side_stream : nullptr, h->ev_wfork, h->ev_wjoin, ev ? ev[K_WALKERS_LONG] : nullptr};
-        const bool forked = RUN_STAGE(b.tune, 2) ? launch_walkers(s, fk, g, nframes * dp.nthr, dp, b) : false;
+        WalkFork fk{h->side_stream, h->ev_wfork, h->ev_wjoin, ev ? ev[K_WALKERS_LONG] : nullptr};
+        const bool forked = RUN_STAGE(b.env, 2) ? launch_walkers(s, fk, g, nframes * dp.nthr, dp, b) : false;
         MARK(K_CONTOUR_QUADS);
-        if (RUN_STAGE(b.tune, 4)) launch_contour_quads(s, g, nframes, dp, b, forked ? 1 : 0);
+        if (RUN_STAGE(b.env, 4)) launch_contour_quads(s, g, nframes, dp, b, forked ? 1 : 0);
         if (forked) {
             HIPCHK(h, hipStreamWaitEvent(s, h->ev_wjoin, 0));
-            if (RUN_STAGE(b.tune, 4)) launch_contour_quads(s, g, nframes, dp, b, 2);
+            if (RUN_STAGE(b.env, 4)) launch_contour_quads(s, g, nframes, dp, b, 2);
         }
     }
     MARK(K_FRAME_CANDS);
-    if (RUN_STAGE(b.tune, 5)) launch_frame_candidates(s, g, nframes, dp, b);
+    if (RUN_STAGE(b.env, 5)) launch_frame_candidates(s, g, nframes, dp, b);
     return ARUCOHIP_OK;
 }
 
@@ -690,7 +662,7 @@ static int run_threshold(arucohip_handle* h, hipStream_t s, const uint8_t* gray_
     const Buffers& b = h->buf;
     h->thres_bytes = true;
     if (dp.thres_method != ARUCOHIP_THRES_CANNY) {
-        const bool lazy = launch_threshold(s, gray_dev, g, nframes, dp, b, b.tune.thres_lazy && !want_bytes);
+        const bool lazy = launch_threshold(s, gray_dev, g, nframes, dp, b, b.env.thres_lazy && !want_bytes);
         h->thres_bytes = !lazy;
         return ARUCOHIP_OK;
     }
@@ -710,8 +682,7 @@ static int detect_core(arucohip_handle* h, const uint8_t* gray_dev, const FrameG
     Buffers& b = h->buf;
     HIPCHK(h, hipMemsetAsync(h->zero_block, 0, h->zero_words * sizeof(uint32_t), s));
     hipEvent_t* ev = h->timing ? h->ev[h->tsets % TSETS] : nullptr;
-    if (h->wait_thr) HIPCHK(h, hipStreamWaitEvent(s, h->wait_thr, 0));   // threshold kernels of the lanes run one after the other
-    MARK(K_THRESHOLD);   // after that wait: the interval is this batch's own threshold kernel
+    MARK(K_THRESHOLD);
     {
         const int rc_ = run_threshold(h, s, gray_dev, g, nframes, dp, false);
         if (rc_) return rc_;
@@ -725,7 +696,6 @@ static int detect_core(arucohip_handle* h, const uint8_t* gray_dev, const FrameG
         else
             launch_erode(s, g, nframes * dp.nthr, b, h->d_erode);
     }
-    if (h->ev_thr) HIPCHK(h, hipEventRecord(h->ev_thr, s));
     MARK(K_FILTER);
     {
         const int rc_ = run_rectangles(h, s, g, nframes, dp, ev);
@@ -734,22 +704,22 @@ static int detect_core(arucohip_handle* h, const uint8_t* gray_dev, const FrameG
     MARK(K_DECODE);
     // built-in 5x5 decoder: the cell votes and the Hamming decode of a candidate are the head of its refinement wave (one dispatch less)
     const bool fused_cells = dp.decoder == ARUCOHIP_DECODER_FIDUCIAL_5X5;
-    if (RUN_STAGE(b.tune, 6)) launch_decode(s, gray_dev, g, nframes, dp, b, fused_cells);
+    if (RUN_STAGE(b.env, 6)) launch_decode(s, gray_dev, g, nframes, dp, b, fused_cells);
     if (dp.decoder == ARUCOHIP_DECODER_USER) {
         const int rc_ = user_decode_stage(h, dp);
         if (rc_) return rc_;
     }
     MARK(K_REFINE_LINES);
-    if (RUN_STAGE(b.tune, 7)) launch_refine_lines(s, g, nframes, dp, cam, b, fused_cells);
+    if (RUN_STAGE(b.env, 7)) launch_refine_lines(s, g, nframes, dp, cam, b, fused_cells);
     MARK(K_REFINE_PIXELS);
     if (dp.corner_method == ARUCOHIP_CORNER_HARRIS || dp.corner_method == ARUCOHIP_CORNER_SUBPIX) {
         if (dp.locked) launch_locked_corners(s, gray_dev, g, nframes, dp, b);   // markerdetector.cpp:398-399
         launch_refine_pixels(s, gray_dev, g, nframes, dp, b);
     }
     MARK(K_FINALIZE);
-    if (RUN_STAGE(b.tune, 8)) launch_finalize(s, g, nframes, dp, cam, b, h->wt_out, h->wt_cap, h->wt_n);
+    if (RUN_STAGE(b.env, 8)) launch_finalize(s, g, nframes, dp, cam, b, h->wt_out, h->wt_cap, h->wt_n);
     MARK(K_POSE);
-    if (RUN_STAGE(b.tune, 8) && cam.has_K && cam.marker_size > 0) launch_pose(s, nframes, cam, b);
+    if (RUN_STAGE(b.env, 8) && cam.has_K && cam.marker_size > 0) launch_pose(s, nframes, cam, b);
     MARK(K_COUNT);
 #undef MARK
     if (ev) h->tsets++;
@@ -977,11 +947,6 @@ static int detect_batch_impl(arucohip_handle* h, const uint8_t* frames, int nfra
     if ((rc = fork_workers(h, plan))) return rc;
     for (int c = 0; c < plan.nspan; c++) {
         const Span& s = plan.span[c];
-        // optional stagger (ARUCOHIP_CHAIN=1): the bandwidth-bound threshold kernels of the chunks run one after the other,
-        // so that chunk c's threshold overlaps the latency-bound border following / decoding of chunk c-1. Helps with 4
-        // streams on some boxes and hurts on others, hence off by default.
-        const bool chain = h->buf.tune.chain != 0;
-        s.w->wait_thr = (chain && c > 0) ? plan.span[c - 1].w->ev_thr : nullptr;
         rc = chunk_enqueue(s.w, frames + (size_t)s.first * frame_stride, s.count, W, H, row_stride, frame_stride, frames_on_device, channels, dp, cam,
                            out ? out + (size_t)s.first * cap : nullptr, cap, n_out + s.first, out_on_device);
         if (rc) {
@@ -989,7 +954,6 @@ static int detect_batch_impl(arucohip_handle* h, const uint8_t* frames, int nfra
             // the workers that already have queued work still have to rejoin the caller's stream
             const std::string keep = h->err;
             (void)join_workers(h, plan);
-            for (const Span& x : plan) x.w->wait_thr = nullptr;
             h->err = keep;
             h->last = Batch{};   // the lists hold part of a batch
             return rc;

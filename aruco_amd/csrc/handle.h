@@ -145,9 +145,7 @@ struct arucohip_handle {
     hipEvent_t ev_fork = nullptr, ev_join[MAX_WORKERS] = {};
     hipStream_t side_stream = nullptr;   // late walker generations (k_contours.hip)
     hipEvent_t ev_wfork = nullptr, ev_wjoin = nullptr;
-    hipEvent_t ev_thr = nullptr;         // this worker's threshold kernel has finished (staggers the chunks, see detect_batch)
     bool thres_bytes = true;             // buf.thres holds the last batch's byte image (else: tiles + buf.thres_edge, expanded on demand)
-    hipEvent_t wait_thr = nullptr;       // set by detect_batch: event the next threshold kernel waits for
     Mem<uint8_t> d_em;                   // arucohip_em_fit scratch
     Mem<uint8_t> d_hrm_gen;              // HRM dictionary / board generation scratch (k_hrm.hip)
     int32_t hrm_stats[4] = {};           // the last arucohip_hrm_create_dictionary: windows, host synchronisations, acceptances, tau decrements
@@ -159,9 +157,9 @@ struct arucohip_handle {
     // - compared with `addrs` before a replay and after a capture: gray_dev (d_gray for host gray and BGR frames), buf.walk_scratch and
     //   buf.patches, which calls of other shapes grow. An equal address is enough, since reserve() never shrinks;
     // - neither: the other Buffers arrays, zero_block and h_markers are create-time memory (`held`); d_erode, d_canny and the user decoder's
-    //   staging belong to configurations that are not graphed; wt_out is set only inside chunk_enqueue and wait_thr only on chunk workers
-    //   after the first, neither of which runs this path. Memory no captured launch reads (d_bgr, undistortion, calibration, board and GL
-    //   batches, EM, HRM and ChromaticMask scratch) may be replaced at any time.
+    //   staging belong to configurations that are not graphed; wt_out is set only inside chunk_enqueue, which does not run this path.
+    //   Memory no captured launch reads (d_bgr, undistortion, calibration, board and GL batches, EM, HRM and ChromaticMask scratch) may
+    //   be replaced at any time.
     struct FrameGraph {
         hipGraphExec_t exec = nullptr;
         uint64_t key = 0;          // digest of everything the captured launches carry by value

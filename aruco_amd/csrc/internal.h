@@ -113,40 +113,28 @@ struct DetectParams {
     const uint64_t* hrm_codes;      // device
 };
 
-// Tuning / A-B knobs. They are environment variables (INTEGRATION.md lists them), read ONCE when a handle is created and
-// kept with it: a handle behaves the same for its whole life whatever the environment does later, and no kernel launcher
-// touches the environment.
-struct Tuning {
-    int walk_fork = 1;         // ARUCOHIP_WALK_FORK: late walker generations on a side stream
-    int chain = 0;             // ARUCOHIP_CHAIN: threshold kernels of chunk streams one after the other
-    int cand_sparse = 1;       // ARUCOHIP_CAND_SPARSE: bitmap-driven start candidates
-    int cand_waves = 32;       // ARUCOHIP_CAND_WAVES: waves per plane of that kernel (4 0.25, 8 0.18, 16 0.13, 32 0.13 ms per 512 frames)
-    int cand_chunks = 16;      // ARUCOHIP_CAND_CHUNKS: workgroups per plane of the lane-per-tile kernel
-    int leash = 0;             // ARUCOHIP_LEASH: steps of the first walker pass (0 = default)
-    int gens[32] = {};         // ARUCOHIP_GENS: steps per generation of long walks
-    int ngens = 0;
-    int fork_after = 3;        // ARUCOHIP_FORK_AFTER: generations on the main stream
-    int gen_xcd = 1;           // ARUCOHIP_GEN_XCD=0: one generation list for the whole chip (rounds 1-3) instead of one per XCD
-    int seg_skip = 1;          // ARUCOHIP_SEG_SKIP=0: the laps of the segment pipeline take one segment per hop also for one frame per call
-    int quad_dual = 1;         // ARUCOHIP_QUAD_DUAL=0: one border per wave in contour_quad (round 3), 1: two borders of <= 512 points per wave
-    int quad_blocks = 12;      // ARUCOHIP_QUAD_BLOCKS: workgroups per plane of contour_quad. One border per wave (rounds 1-3): 8: 0.93 ms, 16: 0.68, 24: 0.60, 32: 0.72 -> 24.
-                               // Two borders per wave (round 4): a workgroup needs an even number of short borders to pair them all, so fewer, longer lists:
-                               // 24 / 16 / 12 = 467.7k / 471.1k / 480.0k frames/s (flat stream), 273.1k / 276.2k / 276.2k (cluttered), same box
-    int thres_lazy = 1;        // ARUCOHIP_THRES_BYTES=1 clears it: the threshold kernel always writes the byte image
-    int threshold_wide = 1;    // ARUCOHIP_THRESHOLD_WIDE: 16-pixel-per-lane threshold kernel where it applies
+// Environment switches (INTEGRATION.md "Environment knobs"). read_env() (capi.hip) reads them once, when the caller creates a handle;
+// its chunk workers, pipeline lanes and retry handle take that record instead of reading the environment again, so a handle and
+// everything made for it behave the same for their whole life whatever the environment does later. Each switch stays because
+// callers or tests need it; no kernel launcher touches the environment.
+struct EnvSettings {
+    int streams = 1;       // ARUCOHIP_STREAMS: chunk workers per handle
+    int graph = 1;         // ARUCOHIP_GRAPH=0: no single-frame graph (the eager reference of the graph path)
+    int contours = -1;     // ARUCOHIP_CONTOURS: 0 walkers, 1 waypoint segments, -1 by handle shape (create_handle)
+    int grid = 16;         // ARUCOHIP_GRID: waypoint spacing of the segment pipeline
+    int thres_lazy = 1;    // ARUCOHIP_THRES_BYTES=1 clears it: the threshold kernel always writes the byte image
+    int quad_dual = 1;     // ARUCOHIP_QUAD_DUAL=0: one border per wave in contour_quad (round 3), the reference of two borders of <= 512 points per wave
 #ifdef ARUCOHIP_STAGE_EXPERIMENT
-    int stop_after = 99;       // stage-cost experiment (tools/stage_cost.sh builds a variant library with this flag and reads ARUCOHIP_STOP_AFTER):
-                               // 1 threshold, 2 start candidates, 3 first walker pass, 4 generations, 5 contour_quad, 6 frame_candidates, 7 warp + Otsu, 8 LINES
+    int stop_after = 99;   // stage-cost experiment (tools/stage_cost.sh builds a variant library with this flag and reads ARUCOHIP_STOP_AFTER):
+                           // 1 threshold, 2 start candidates, 3 first walker pass, 4 generations, 5 contour_quad, 6 frame_candidates, 7 warp + Otsu, 8 LINES
 #endif
-    int threshold_eo = 1;      // ARUCOHIP_THRESHOLD_EO: its round-3 form for 7x7 blocks (unpacked row ring, folded constants); 0 = the round-2 kernel
 };
-Tuning read_tuning();          // capi.hip
-// RUN_STAGE(tune, n): does the pipeline run past stage n? Always, except in the stage-cost experiment's variant build, where the pipeline is cut
+// RUN_STAGE(env, n): does the pipeline run past stage n? Always, except in the stage-cost experiment's variant build, where the pipeline is cut
 // behind the stage ARUCOHIP_STOP_AFTER names (results are then meaningless; arucohip_build_info() names the flag and bench.py prints no headline).
 #ifdef ARUCOHIP_STAGE_EXPERIMENT
-#define RUN_STAGE(tune, n) ((tune).stop_after > (n))
+#define RUN_STAGE(env, n) ((env).stop_after > (n))
 #else
-#define RUN_STAGE(tune, n) true
+#define RUN_STAGE(env, n) true
 #endif
 
 // Border lines of a thresholded plane kept beside the bit tiles (lazy byte image): row 0 at 0, row H-1 at Wp, column 0 at 2 Wp, column W-1
@@ -158,7 +146,7 @@ __host__ __device__ inline size_t thres_edge_stride(int W, int H) { return 2 * t
 
 // device pointers + capacities handed to kernels
 struct Buffers {
-    Tuning tune;
+    EnvSettings env;
     uint8_t* thres;
     uint64_t* tiles;       // [P][tiles_y(H)][tiles_x(W)] binary image in 8x8-pixel tiles (bits_tiles.h)
     uint64_t* tile_bits;   // [P][tiles_y(H)][2 * tile_strips(W)] non-empty-tile bitmap: per 128-tile strip one word for the even
@@ -231,7 +219,7 @@ void launch_tile_bitmap(hipStream_t s, const FrameGeom& g, int nplanes, const Bu
 void launch_binary_planes(hipStream_t s, const uint8_t* thres_in, const FrameGeom& g, int nframes, const Buffers& b);
 void launch_start_candidates(hipStream_t s, const FrameGeom& g, int nplanes, const Buffers& b, int min_contour = 0);
 struct WalkFork {
-    hipStream_t side;            // stream of the late walker generations (nullptr: everything on the main stream)
+    hipStream_t side;            // stream of the late walker generations
     hipEvent_t forked, joined;
     hipEvent_t after_first;      // recorded behind the first pass (per-kernel timing), may be null
 };

@@ -6,7 +6,7 @@
 //
 // cv::findContours is a sequential raster scan that relabels pixels while it follows borders. The point sequence
 // of a border depends only on the binary image, its start pixel and whether it is a hole border, so the scan is
-// replaced by (a) local start candidates found on the tiled image, thinned by the run rule (candidates_kernel: the start of a
+// replaced by (a) local start candidates found on the tiled image, thinned by the run rule (candidates_sparse_kernel: the start of a
 // border is the first pixel of a horizontal run with nothing connected in the row above) and (b) one walker per candidate that follows the border
 // with OpenCV's step rule and drops itself as soon as it proves it is not the scan's start:
 //   outer border: a visited pixel precedes the start in raster order
@@ -54,76 +54,58 @@ __device__ __forceinline__ bool run_rule_tiles(const uint64_t* __restrict__ tile
 }
 
 // ---------------------------------------------------------------------------------------------
-// Kernel 1b: border-start candidates from the tiled binary image. One lane per 8x8 tile evaluates the 3x3 start rule
-// of cv::findContours' raster scan for its 64 pixels with 64-bit logic on the tile and its W / N / NW / NE neighbours
+// Kernel 1b, segment mode (k_segments.hip): the waypoint cracks of the tiled binary image. One lane per 8x8 tile evaluates the
+// 3x3 start rule of cv::findContours' raster scan for its 64 pixels with 64-bit logic on the tile and its W / N / NW / NE neighbours
 //   outer: pixel set,  W, NW, N, NE clear         hole: pixel clear, W and N set (pixel inside the 1-px frame)
-// and then the run rule for every hit: a candidate survives only if it can be the first pixel of its component / hole
-// in raster order (outer - no set pixel 8-adjacent to its run of set pixels in the row above; hole - no clear pixel
-// directly above its run of clear pixels). Survivors go to two lists per plane (outer starts in the first half of
-// trig[plane], hole starts in the second half) so that a walker wavefront follows only one kind of border.
-// Segment mode (k_segments.hip) instead gets the waypoint cracks of every tile: W / E cracks on grid rows, N / S cracks
-// on grid columns plus every start-candidate crack, as records {candidate flag, pos << 2 | code}.
+// and emits W / E cracks on grid rows, N / S cracks on grid columns plus every start-candidate crack, as records
+// {candidate flag, pos << 2 | code}, to the plane's raw list.
 // ---------------------------------------------------------------------------------------------
 struct CandArgs {
     const uint64_t* tiles;
     int tnx, tny;
     int width, height;
-    uint2* trig;
-    uint32_t* trig_cnt;
+    uint32_t* trig_cnt;      // per-plane counter lines: the overflow bits
     uint2* raw;
     uint32_t* raw_cnt;
     uint32_t* counters;
-    uint32_t cap_raw, cap_trig;
-    int seg_mode, grid_mask;
-    uint32_t* hash;          // segment mode: the plane's key -> node table, cleared here (segment_kernel fills it: one memset node less per call)
+    uint32_t cap_raw;
+    int grid_mask;
+    uint32_t* hash;          // the plane's key -> node table, cleared here (segment_kernel fills it: one memset node less per call)
     uint32_t hash_size;
 };
 
 constexpr int CAND_THREADS = 256;
-constexpr int CAND_STAGE = 512;   // staged records per list and round
+constexpr int CAND_STAGE = 512;   // staged records per round
 
 __global__ __launch_bounds__(CAND_THREADS) void candidates_kernel(CandArgs a) {
     throughput_bound_priority();
-    __shared__ uint2 s_keep[2][CAND_STAGE];
-    __shared__ uint2 s_long[CAND_STAGE];
-    __shared__ uint32_t s_n[2], s_base[2], s_nlong;
+    __shared__ uint2 s_keep[CAND_STAGE];
+    __shared__ uint32_t s_n, s_base;
     const int plane = blockIdx.y;
     const uint64_t* __restrict__ tiles = a.tiles + (size_t)plane * a.tnx * a.tny;
     const int ntx = a.tnx - 1, nty = a.tny - 1;          // real tiles (the pad column / row holds no pixel)
     const int ntiles = ntx * nty;
     const uint64_t COL0 = 0x0101010101010101ull, COL7 = 0x8080808080808080ull;
-    const uint32_t half = a.seg_mode ? a.cap_raw : a.cap_trig / 2;
-    if (a.hash)
-        for (uint32_t i = blockIdx.x * CAND_THREADS + threadIdx.x; i < a.hash_size; i += gridDim.x * CAND_THREADS) a.hash[(size_t)plane * a.hash_size + i] = 0xFFFFFFFFu;
-    uint2* const out = a.seg_mode ? a.raw + (size_t)plane * a.cap_raw : a.trig + (size_t)plane * a.cap_trig;
-    uint32_t* const out_cnt = (a.seg_mode ? a.raw_cnt : a.trig_cnt) + plane * TRIG_CNT_STRIDE;
+    for (uint32_t i = blockIdx.x * CAND_THREADS + threadIdx.x; i < a.hash_size; i += gridDim.x * CAND_THREADS) a.hash[(size_t)plane * a.hash_size + i] = 0xFFFFFFFFu;
+    uint2* const out = a.raw + (size_t)plane * a.cap_raw;
+    uint32_t* const out_cnt = a.raw_cnt + plane * TRIG_CNT_STRIDE;
 
-    // a record either enters the staging list of its kind or, when the round's list is full, goes straight to the plane's list
-    auto stage = [&](int kind, uint2 rec) {
-        const uint32_t ls = atomicAdd(&s_n[kind], 1u);
+    // a record either enters the staging list or, when the round's list is full, goes straight to the plane's list
+    auto stage = [&](uint2 rec) {
+        const uint32_t ls = atomicAdd(&s_n, 1u);
         if (ls < CAND_STAGE) {
-            s_keep[kind][ls] = rec;
+            s_keep[ls] = rec;
         } else {
-            const uint32_t slot = atomicAdd(&out_cnt[kind], 1u);
-            if (slot < half)
-                out[(size_t)kind * half + slot] = rec;
+            const uint32_t slot = atomicAdd(out_cnt, 1u);
+            if (slot < a.cap_raw)
+                out[slot] = rec;
             else
                 flag_overflow(a.counters, a.trig_cnt, plane, ST_TRIG_OVERFLOW);
         }
     };
 
-    // a candidate whose run outlasts the pixels at hand waits for the 64-pixel test (or takes it at once if the list is full)
-    auto defer = [&](uint2 rec) {
-        const uint32_t ls = atomicAdd(&s_nlong, 1u);
-        if (ls < CAND_STAGE)
-            s_long[ls] = rec;
-        else if (run_rule_tiles(tiles, a.tnx, (int)(rec.y & 0xFFFFu), (int)(rec.y >> 16), (int)rec.x))
-            stage((int)rec.x, rec);
-    };
-
     for (int i0 = blockIdx.x * CAND_THREADS; i0 < ntiles; i0 += gridDim.x * CAND_THREADS) {
-        if (threadIdx.x < 2) s_n[threadIdx.x] = 0;
-        if (threadIdx.x == 2) s_nlong = 0;
+        if (threadIdx.x == 0) s_n = 0;
         __syncthreads();
         const int i = i0 + threadIdx.x;
         if (i < ntiles) {
@@ -145,95 +127,59 @@ __global__ __launch_bounds__(CAND_THREADS) void candidates_kernel(CandArgs a) {
                 const uint64_t outer = T & ~(Wn | NW | N | NE);
                 const uint64_t hole = ~T & Wn & N & colm & rowm;
                 const uint32_t base = ((uint32_t)(8 * ty) << 16) | (uint32_t)(8 * tx);
-                if (!a.seg_mode) {
-                    // run rule on the 16 - (x & 7) pixels at hand (this tile and its right neighbour, rows y and y-1); only a
-                    // run that leaves them undecided takes the 64-pixel test after the tile pass
-                    const uint64_t both = outer | hole;
-                    uint64_t m = both;
+                // waypoint cracks (pixel p set, 4-neighbour clear). Record: y = (pos(p) << 2) | code (E=0,N=1,W=2,S=3),
+                // x = 1 if the crack is a border-start candidate.
+                uint64_t rsel = 0, csel = 0;
+#pragma unroll
+                for (int q = 0; q < 8; q++) {
+                    if (((8 * ty + q) & a.grid_mask) == 0) rsel |= 0xFFull << (8 * q);
+                    if (((8 * tx + q) & a.grid_mask) == 0) csel |= COL0 << q;
+                }
+                const uint64_t crW = T & ~Wn & (rsel | outer);          // W crack of the set pixel
+                const uint64_t crE = ~T & Wn & (rsel | hole);           // E crack of p, seen from the clear pixel z = p + 1
+                const uint64_t crN = T & ~N & csel;                     // N crack of the set pixel
+                const uint64_t crS = N & ~T & csel;                     // S crack of the pixel above, seen from the clear pixel
+                for (int kind = 0; kind < 4; kind++) {
+                    uint64_t m = kind == 0 ? crW : kind == 1 ? crE : kind == 2 ? crN : crS;
                     while (m) {
                         const int b = __builtin_ctzll(m);
                         m &= m - 1;
-                        const int q = b >> 3, j = b & 7;
-                        const uint32_t kind = (uint32_t)(hole >> b) & 1u;
-                        const uint32_t mid = ((((uint32_t)(T >> (8 * q)) & 0xFFu) | (((uint32_t)(Rt >> (8 * q)) & 0xFFu) << 8)) >> j);
-                        const uint32_t up = ((((uint32_t)(N >> (8 * q)) & 0xFFu) | (((uint32_t)(NRt >> (8 * q)) & 0xFFu) << 8)) >> j);
-                        const int avail = 16 - j;
-                        const uint32_t pos = base + ((uint32_t)q << 16) + (uint32_t)j;
-                        // outer: run of set pixels from x, blockers = set pixels above columns x+2 .. x+L
-                        // hole : run of clear pixels from x, blockers = clear pixels above columns x+1 .. x+L-1
-                        const uint32_t runbits = (kind ? mid : ~mid) | (1u << avail);
-                        const int Lr = __builtin_ctz(runbits);                       // run length inside the window
-                        const int hi = kind ? min(Lr - 1, avail - 1) : min(Lr, avail - 1);
-                        const uint32_t span = ((2u << hi) - 1u) & (kind ? ~1u : ~3u);
-                        const bool blocked = ((kind ? ~up : up) & span) != 0;
-                        if (blocked) continue;
-                        if (Lr < avail)
-                            stage((int)kind, make_uint2(kind, pos));
-                        else
-                            defer(make_uint2(kind, pos));
-                    }
-                } else {
-                    // waypoint cracks (pixel p set, 4-neighbour clear). Record: y = (pos(p) << 2) | code (E=0,N=1,W=2,S=3),
-                    // x = 1 if the crack is a border-start candidate.
-                    uint64_t rsel = 0, csel = 0;
-#pragma unroll
-                    for (int q = 0; q < 8; q++) {
-                        if (((8 * ty + q) & a.grid_mask) == 0) rsel |= 0xFFull << (8 * q);
-                        if (((8 * tx + q) & a.grid_mask) == 0) csel |= COL0 << q;
-                    }
-                    const uint64_t crW = T & ~Wn & (rsel | outer);          // W crack of the set pixel
-                    const uint64_t crE = ~T & Wn & (rsel | hole);           // E crack of p, seen from the clear pixel z = p + 1
-                    const uint64_t crN = T & ~N & csel;                     // N crack of the set pixel
-                    const uint64_t crS = N & ~T & csel;                     // S crack of the pixel above, seen from the clear pixel
-                    for (int kind = 0; kind < 4; kind++) {
-                        uint64_t m = kind == 0 ? crW : kind == 1 ? crE : kind == 2 ? crN : crS;
-                        while (m) {
-                            const int b = __builtin_ctzll(m);
-                            m &= m - 1;
-                            const uint32_t z = base + ((uint32_t)(b >> 3) << 16) + (uint32_t)(b & 7);
-                            uint32_t pos, code, cand = 0;
-                            if (kind == 0) pos = z, code = 2u, cand = (uint32_t)(outer >> b) & 1u;
-                            else if (kind == 1) pos = z - 1u, code = 0u, cand = (uint32_t)(hole >> b) & 1u;
-                            else if (kind == 2) pos = z, code = 1u;
-                            else pos = z - 65536u, code = 3u;
-                            stage(0, make_uint2(cand, (pos << 2) | code));
-                        }
+                        const uint32_t z = base + ((uint32_t)(b >> 3) << 16) + (uint32_t)(b & 7);
+                        uint32_t pos, code, cand = 0;
+                        if (kind == 0) pos = z, code = 2u, cand = (uint32_t)(outer >> b) & 1u;
+                        else if (kind == 1) pos = z - 1u, code = 0u, cand = (uint32_t)(hole >> b) & 1u;
+                        else if (kind == 2) pos = z, code = 1u;
+                        else pos = z - 65536u, code = 3u;
+                        stage(make_uint2(cand, (pos << 2) | code));
                     }
                 }
             }
         }
         __syncthreads();
-        {
-            const uint32_t nlong = min(s_nlong, (uint32_t)CAND_STAGE);
-            for (uint32_t j = threadIdx.x; j < nlong; j += CAND_THREADS) {
-                const uint2 rec = s_long[j];
-                if (run_rule_tiles(tiles, a.tnx, (int)(rec.y & 0xFFFFu), (int)(rec.y >> 16), (int)rec.x)) stage((int)rec.x, rec);
-            }
-        }
+        if (threadIdx.x == 0 && s_n) s_base = atomicAdd(out_cnt, min(s_n, (uint32_t)CAND_STAGE));
         __syncthreads();
-        if (threadIdx.x < 2 && s_n[threadIdx.x]) s_base[threadIdx.x] = atomicAdd(&out_cnt[threadIdx.x], min(s_n[threadIdx.x], (uint32_t)CAND_STAGE));
-        __syncthreads();
-        for (int kind = 0; kind < 2; kind++) {
-            const uint32_t n = min(s_n[kind], (uint32_t)CAND_STAGE);
-            for (uint32_t j = threadIdx.x; j < n; j += CAND_THREADS) {
-                const uint32_t slot = s_base[kind] + j;
-                if (slot < half)
-                    out[(size_t)kind * half + slot] = s_keep[kind][j];
-                else
-                    flag_overflow(a.counters, a.trig_cnt, plane, ST_TRIG_OVERFLOW);
-            }
+        const uint32_t n = min(s_n, (uint32_t)CAND_STAGE);
+        for (uint32_t j = threadIdx.x; j < n; j += CAND_THREADS) {
+            const uint32_t slot = s_base + j;
+            if (slot < a.cap_raw)
+                out[slot] = s_keep[j];
+            else
+                flag_overflow(a.counters, a.trig_cnt, plane, ST_TRIG_OVERFLOW);
         }
         __syncthreads();
     }
 }
 
 // ---------------------------------------------------------------------------------------------
-// Kernel 1b, sparse form (walker mode): nine tiles in ten are empty and cannot hold a start (a start needs a set pixel in the
+// Kernel 1b, walker mode: border-start candidates. Nine tiles in ten are empty and cannot hold a start (a start needs a set pixel in the
 // tile, or in its left or upper neighbour). The threshold kernel leaves a non-empty-tile bitmap (two words per 128-tile
 // strip: even tiles, odd tiles); a wave walks its share of the tile rows on those words alone, queues the tiles that can
 // hold a start and evaluates 64 queued tiles at a time with all lanes busy: the start rule, the run rule on the 16 pixels at
-// hand and — for the few runs that leave them — the 64-pixel run rule at once. Survivors are staged per wave and appended to
-// the plane's lists with one atomic per list and flush.
+// hand and — for the few runs that leave them — the 64-pixel run rule at once. A candidate survives only if it can be the first
+// pixel of its component / hole in raster order (outer - no set pixel 8-adjacent to its run of set pixels in the row above; hole -
+// no clear pixel directly above its run of clear pixels). Survivors are staged per wave and appended to two lists per plane (outer
+// starts in the first half of trig[plane], hole starts in the second half, so that a walker wavefront follows only one kind of
+// border) with one atomic per list and flush.
 // ---------------------------------------------------------------------------------------------
 constexpr int CQ_CAP = 192;       // queued tile ids per wave (a round consumes 64; at most 128 join per strip)
 constexpr int CS_CAP = 256;       // staged survivors per list and wave
@@ -413,26 +359,27 @@ __global__ __launch_bounds__(64) void candidates_sparse_kernel(SparseArgs a) {
 }
 
 void launch_start_candidates(hipStream_t s, const FrameGeom& g, int nplanes, const Buffers& b, int min_contour) {
-    if (!b.seg_mode && b.tune.cand_sparse) {
+    if (!b.seg_mode) {
+        constexpr int kWaves = 32;   // waves per plane (4 0.25, 8 0.18, 16 0.13, 32 0.13 ms per 512 frames)
         SparseArgs a;
         a.drop_single = min_contour >= 1;
         a.tiles = b.tiles, a.tile_bits = b.tile_bits, a.tnx = tiles_x(g.width), a.tny = tiles_y(g.height), a.nstrips = tile_strips(g.width);
         a.width = g.width, a.height = g.height, a.trig = b.trig, a.trig_cnt = b.trig_cnt, a.counters = b.counters, a.cap_trig = b.cap_trig;
         const int nty = a.tny - 1;
-        const int waves = b.tune.cand_waves;
-        hipLaunchKernelGGL(candidates_sparse_kernel, dim3(std::min(waves, nty), nplanes), dim3(64), 0, s, a);
+        hipLaunchKernelGGL(candidates_sparse_kernel, dim3(std::min(kWaves, nty), nplanes), dim3(64), 0, s, a);
         return;
     }
+    constexpr int kChunks = 16;   // workgroups per plane of a batch
     CandArgs a;
     a.tiles = b.tiles, a.tnx = tiles_x(g.width), a.tny = tiles_y(g.height);
     a.width = g.width, a.height = g.height;
-    a.trig = b.trig, a.trig_cnt = b.trig_cnt, a.raw = b.raw, a.raw_cnt = b.raw_cnt, a.counters = b.counters;
-    a.cap_raw = b.cap_raw, a.cap_trig = b.cap_trig;
-    a.seg_mode = b.seg_mode, a.grid_mask = b.grid_mask;
-    a.hash = b.seg_mode ? b.hash : nullptr, a.hash_size = b.hash_mask + 1;
+    a.trig_cnt = b.trig_cnt, a.raw = b.raw, a.raw_cnt = b.raw_cnt, a.counters = b.counters;
+    a.cap_raw = b.cap_raw;
+    a.grid_mask = b.grid_mask;
+    a.hash = b.hash, a.hash_size = b.hash_mask + 1;
     const int ntiles = (a.tnx - 1) * (a.tny - 1);
-    // a single frame has the chip to itself: a tile per thread; a batch of planes: four tiles per thread, at most cand_chunks workgroups per plane
-    const int maxchunks = nplanes <= 2 ? 256 : b.tune.cand_chunks;
+    // a single frame has the chip to itself: a tile per thread; a batch of planes: four tiles per thread, at most kChunks workgroups per plane
+    const int maxchunks = nplanes <= 2 ? 256 : kChunks;
     const int per = nplanes <= 2 ? CAND_THREADS : 4 * CAND_THREADS;
     const int chunks = std::max(1, std::min(maxchunks, (ntiles + per - 1) / per));
     hipLaunchKernelGGL(candidates_kernel, dim3(chunks, nplanes), dim3(CAND_THREADS), 0, s, a);
@@ -440,7 +387,7 @@ void launch_start_candidates(hipStream_t s, const FrameGeom& g, int nplanes, con
 
 constexpr int CK = 16;        // border steps between two checkpoints
 constexpr int LEASH_MAX = 96;     // most steps a candidate can get in the first pass (sizes the LDS checkpoint array)
-constexpr int LEASH_DEFAULT = 64; // a multiple of CK; ARUCOHIP_LEASH overrides for tuning
+constexpr int LEASH_DEFAULT = 64; // a multiple of CK
 constexpr int PROBE = 10;     // steps of the reverse probe: stays inside the 32x32 block loaded around the start
 constexpr int GEN_MAX = 30;           // generations of the long walks (kernel launches after the first pass)
 constexpr int GEN_CNT_STRIDE = 32;    // uint32 words between two generation counters (one 128-byte line each)
@@ -850,15 +797,12 @@ bool launch_walkers(hipStream_t s, const WalkFork& fk, const FrameGeom& g, int n
     // hold more walks than rings exist
     a.long_cap = b.long_cap;
     // one sublist per XCD when the batch gives every XCD planes to work on; a few planes (one frame per call with the walkers) keep one list for the whole chip
-    a.gen_nx = (nplanes >= 64 && b.tune.gen_xcd) ? GEN_NX_MAX : 1;
+    a.gen_nx = nplanes >= 64 ? GEN_NX_MAX : 1;
     a.gen_cap = (uint32_t)((size_t)((nplanes + 7) / 8 * 8) * b.long_cap);
     a.gen_state = (uint4*)b.gen_buf;
     a.gen_ring = (uint32_t*)(a.gen_state + 4 * (size_t)a.gen_cap);
     a.gen = 0, a.gen_steps = 0;
-    {
-        const int v = b.tune.leash > 0 ? b.tune.leash : LEASH_DEFAULT;
-        a.leash = (v >= CK && v <= LEASH_MAX && v % CK == 0) ? v : LEASH_DEFAULT;
-    }
+    a.leash = LEASH_DEFAULT;
     const int planes8 = ((nplanes + 7) / 8) * 8;
     // a 64-thread workgroup per wave keeps the divergent walks of one wave from holding other waves' slots
     hipLaunchKernelGGL(walker_kernel, dim3(planes8 * WALK_BLOCKS), dim3(64), 0, s, a);
@@ -867,25 +811,16 @@ bool launch_walkers(hipStream_t s, const WalkFork& fk, const FrameGeom& g, int n
     // walks and are pure latency (a border of n pixels is a chain of n dependent steps), so they run on the side stream
     // while the main stream already turns the borders found so far into quads (launch_contour_quads pass 1); the per-plane
     // descriptor counts at the fork are snapshotted for that.
-    // schedule: ARUCOHIP_GENS="64,64,128,..." overrides for tuning; after the listed generations the length stays 1024
-    int kSteps[GEN_MAX], nsched = 0;
-    {
-        for (int i = 0; i < b.tune.ngens && nsched < GEN_MAX; i++) {   // ARUCOHIP_GENS="64,64,128,..."; after the listed generations the length stays 1024
-            const int v = b.tune.gens[i];
-            if (v >= CHUNK && v % CHUNK == 0 && v % CK == 0) kSteps[nsched++] = v;
-        }
-        // round 2 (every lane re-centres its own block): few long generations beat many short ones; the side stream takes over
-        // after 128 + 256 + 512 steps, borders of up to 960 points are in contour_quad's first pass (profiles/r02_kernel_experiments.txt)
-        static const int kDefault[] = {128, 256, 512, 1024};
-        if (nsched == 0)
-            for (int v : kDefault) kSteps[nsched++] = v;
-    }
-    const int kForkAfter = b.tune.fork_after;
+    // Round 2 (every lane re-centres its own block): few long generations beat many short ones; the side stream takes over
+    // after 128 + 256 + 512 steps, borders of up to 960 points are in contour_quad's first pass (profiles/r02_kernel_experiments.txt).
+    // After the listed generations the length stays 1024.
+    static const int kSteps[] = {128, 256, 512, 1024};
+    constexpr int nsched = 4, kForkAfter = 3;   // kForkAfter: generations on the main stream
     int done = a.leash;
     bool forked = false;
     hipStream_t cur = s;
-    for (int g = 1; g <= GEN_MAX && done < p.max_contour && RUN_STAGE(b.tune, 3); g++) {
-        if (g == kForkAfter + 1 && fk.side) {
+    for (int g = 1; g <= GEN_MAX && done < p.max_contour && RUN_STAGE(b.env, 3); g++) {
+        if (g == kForkAfter + 1) {
             hipLaunchKernelGGL(snapshot_kernel, dim3((nplanes + 255) / 256), dim3(256), 0, s, b.trig_cnt, nplanes);
             (void)hipEventRecord(fk.forked, s);
             (void)hipStreamWaitEvent(fk.side, fk.forked, 0);
@@ -1415,9 +1350,13 @@ void launch_contour_quads(hipStream_t s, const FrameGeom& g, int nframes, const 
     a.cap_cdesc = b.cap_cdesc, a.cap_quads = b.cap_quads, a.nthr = p.nthr, a.width = g.width, a.height = g.height;
     a.trig_cnt = b.trig_cnt, a.walk_scratch = b.walk_scratch;
     a.nplanes = nframes * p.nthr;
-    a.dual = b.tune.quad_dual && a.nplanes > 8;   // a single frame has a wave per kept border anyway: all 64 lanes on one border are faster there
+    a.dual = b.env.quad_dual && a.nplanes > 8;   // a single frame has a wave per kept border anyway: all 64 lanes on one border are faster there
+    // workgroups per plane of a batch. One border per wave (rounds 1-3): 8: 0.93 ms, 16: 0.68, 24: 0.60, 32: 0.72 -> 24. Two borders per wave
+    // (round 4): a workgroup needs an even number of short borders to pair them all, so fewer, longer lists: 24 / 16 / 12 = 467.7k / 471.1k /
+    // 480.0k frames/s (flat stream), 273.1k / 276.2k / 276.2k (cluttered), same box
+    constexpr int kBlocks = 12;
     // a handful of planes (one detect() per frame): a wave per kept border instead of a few waves that take the borders one after the other
-    const int qb = a.nplanes <= 2 ? 128 : a.nplanes <= 8 ? 48 : b.tune.quad_blocks;
+    const int qb = a.nplanes <= 2 ? 128 : a.nplanes <= 8 ? 48 : kBlocks;
     a.qblocks = pass == 2 ? std::max(1, qb / 2) : qb;
     const int planes8 = ((a.nplanes + 7) / 8) * 8;
     hipLaunchKernelGGL(contour_quad_kernel, dim3(planes8 * a.qblocks), dim3(64), 0, s, a);

@@ -82,7 +82,7 @@ static void seg_chunks_for(int nplanes, int* seg, int* cyc) {
 
 __device__ __forceinline__ uint32_t hash_key(uint32_t key, uint32_t mask) { return (key * 2654435761u >> 7) & mask; }
 
-// run rule for a start-candidate crack (same test as candidates_kernel in k_contours.hip)
+// run rule for a start-candidate crack (same test as run_rule_tiles in k_contours.hip)
 __device__ __forceinline__ bool run_rule(const uint64_t* __restrict__ tiles, int tnx, uint32_t pos, int e) {
     const int hole = e == 0;
     const uint32_t zpos = pos + (hole ? 1u : 0u);            // outer: the pixel itself; hole: the clear pixel right of p
@@ -452,7 +452,7 @@ static void fill_seg_args(SegArgs& a, const FrameGeom& g, int nplanes, const Det
     a.cdesc = b.cdesc, a.pool = b.pool, a.counters = b.counters, a.cap_cdesc = b.cap_cdesc, a.cap_pool = b.cap_pool, a.trig_cnt = b.trig_cnt;
     a.min_contour = p.min_contour, a.max_contour = p.max_contour;
     seg_chunks_for(nplanes, &a.seg_chunks, &a.cyc_chunks);
-    a.skipn = (nplanes <= 2 && b.tune.seg_skip) ? b.skipn : nullptr;
+    a.skipn = nplanes <= 2 ? b.skipn : nullptr;
 }
 
 void launch_segments(hipStream_t s, const FrameGeom& g, int nplanes, const DetectParams& p, const Buffers& b) {

@@ -37,8 +37,6 @@ struct ThrArgs {
     int tnx, tny;         // tiles per row / column of the tiled binary image
     int fast;             // width, strides and base address are multiples of 4: dword loads and stores (template FAST)
     int fast16;           // ... multiples of 16 and width >= 16: the 16-pixel-per-lane kernel applies
-    int wide_ok;          // Tuning::threshold_wide
-    int eo_ok;            // Tuning::threshold_eo
     int eo_strips, eo_segs, eo_frames;   // the round-3 kernel's 1-D grid: strips per row, row segments per frame, frames
     uint8_t* thres;
     uint64_t* tiles;
@@ -793,7 +791,7 @@ static bool launch_adpt(hipStream_t s, const ThrArgs& a, int nframes, unsigned l
     constexpr bool CAN16 = R <= 5;
     const long lim = (long)(256 + abs(a.idelta)) * a.n + a.n_half;
     if constexpr (R <= 4) {
-        if (a.fast16 && lim < 32768 && a.wide_ok) {
+        if (a.fast16 && lim < 32768) {
             // prefetch depth 3 rows, 128-row segments: the best of the sweep (PF 2..5, segments 64 / 128 / 256, forced register
             // budgets; profiles/r02_threshold_sweep.txt: 0.53 ms per 512 frames, everything else 0.54 .. 1.6)
             // A wave walks down its segment row by row: a launch of few frames gets shorter segments so that it still spreads over
@@ -803,7 +801,7 @@ static bool launch_adpt(hipStream_t s, const ThrArgs& a, int nframes, unsigned l
             const long waves128 = (long)strips * ((a.height + 127) / 128) * nframes;
             int segs;
             if constexpr (R == 3) {
-                if (a.eo_ok && abs(a.idelta) <= 200) {   // the round-3 form of this pass (7x7 blocks; its folded constants want a moderate C)
+                if (abs(a.idelta) <= 200) {   // the round-3 form of this pass (7x7 blocks; its folded constants want a moderate C)
                     const dim3 blk(64);
 #define EO_LAUNCH(SEG_)                                                                                                               \
     do {                                                                                                                              \
@@ -854,7 +852,7 @@ static void fill_args(ThrArgs& a, const uint8_t* gray, const FrameGeom& g, const
     a.gray = gray, a.row_stride = g.row_stride, a.frame_stride = g.frame_stride;
     a.width = g.width, a.height = g.height, a.nthr = nthr, a.t = t;
     a.tnx = tiles_x(g.width), a.tny = tiles_y(g.height);
-    a.thres = b.thres, a.tiles = b.tiles, a.tile_bits = b.tile_bits, a.nstrips = tile_strips(g.width), a.wide_ok = b.tune.threshold_wide, a.eo_ok = b.tune.threshold_eo;
+    a.thres = b.thres, a.tiles = b.tiles, a.tile_bits = b.tile_bits, a.nstrips = tile_strips(g.width);
     a.idelta = 0, a.n = 1, a.n_half = 0;
     a.stamps = b.thr_stamp_on ? b.thr_stamps : nullptr;
     a.edge = nullptr;
@@ -869,7 +867,7 @@ bool launch_threshold(hipStream_t s, const uint8_t* gray, const FrameGeom& g, in
     if (lazy) {   // all planes or none
         ThrArgs a;
         fill_args(a, gray, g, b, p.nthr, 0);
-        lazy = p.thres_method == ARUCOHIP_THRES_ADPT && a.fast16 && a.wide_ok && b.thres_edge != nullptr;
+        lazy = p.thres_method == ARUCOHIP_THRES_ADPT && a.fast16 && b.thres_edge != nullptr;
         for (int t = 0; t < p.nthr && lazy; t++) {
             const long n = (long)p.block[t] * p.block[t];
             lazy = p.block[t] / 2 >= 1 && p.block[t] / 2 <= 4 && (long)(256 + abs(p.idelta)) * n + n / 2 < 32768;

@@ -414,7 +414,8 @@ def test_synchronous_batch_after_a_waited_ticket_is_the_last_batch(env):
 def test_lanes_take_settings_made_before_and_after_the_depth(env, monkeypatch):
     """ARUCOHIP_STREAMS=3 and two pipeline lanes, each with chunk workers of its own: an HRM dictionary, a decoder callback and parameters
     set before arucohip_set_pipeline_depth are taken by the lanes when they are made, and new ones set afterwards reach every lane and its
-    chunk workers. The tickets' results equal those of a plain handle with the same settings."""
+    chunk workers. The tickets' results equal those of a plain handle with the same settings. Lanes take the environment switches the
+    handle was created with: lanes made after ARUCOHIP_STREAMS is gone still cut a batch into three chunks."""
     capi = env["capi"]
     gray, doc = load_case("hrm")
     st, dic = doc["settings"], doc["dictionary"]
@@ -464,6 +465,9 @@ def test_lanes_take_settings_made_before_and_after_the_depth(env, monkeypatch):
             for a, b in zip(got, want):
                 assert a.tobytes() == b.tobytes()
         assert all(int(m["id"]) == 5 for g in got for m in g)
+        h.set_pipeline_depth(2)   # new lanes, made without ARUCOHIP_STREAMS in the environment
+        for a, b in zip(tickets(h), want):
+            assert a.tobytes() == b.tobytes()
     finally:
         h.close()
 
