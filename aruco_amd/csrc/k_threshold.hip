@@ -1,25 +1,29 @@
-// Kernel 1 — adaptive threshold + tiled binary image, one streaming pass per frame.
+// Threshold stage: adaptive (or FIXED) threshold + tiled binary image, one streaming pass per frame.
 //
 // Reference: MarkerDetector::thresHold -> cv::adaptiveThreshold(MEAN_C, BINARY_INV, b, C)
-//            (/root/reference/src/markerdetector.cpp:643-677); the binary image feeds cv::findContours (:511).
+//            (the reference's src/markerdetector.cpp:643-677); the binary image feeds cv::findContours (:511).
 //
-// One wavefront owns a vertical strip of 256 pixels: lane l holds 4 horizontally adjacent pixels (one dword of the gray
-// row), so a row is one aligned 256-byte load and one aligned 256-byte store per wave; lanes 0 and 63 also fetch the
-// ceil(R/4) dwords left / right of the strip that the horizontal sums need (they enter the DPP lane shifts as the value
-// shifted into the wave). The wave walks down its row segment keeping, in registers only,
-//   * a ring of the last 2R+1 gray rows and of their horizontal box sums (two u16 per dword, pixel pairs (0,2) and (1,3)),
-//   * the running vertical sums V (added row in, row out),
-// so every gray byte is read from HBM/L2 once (plus the halo overlap); there is no LDS tile and no re-read. The slot of
-// the ring that held the centre row is refilled at once with the row R+1 ahead, so R+1 loads are always in flight.
+// Three kernel families; thr_plan() (thr_plan.h) chooses one per plane, and nothing in this file repeats its conditions:
+//   threshold_strip_kernel<R, MODE, P16, FAST>  the general path: any width and alignment, blocks up to 31x31, the FIXED method, a
+//       caller-supplied binary image. 4 pixels per lane. Always writes the byte image; writes no non-empty-tile bitmap
+//       (launch_tile_bitmap follows). Chosen when the conditions below fail; FAST with 4-byte aligned rows, P16 with blocks up to
+//       11x11 whose packed compare fits 16 bits.
+//   threshold_wide_kernel<R, PF, SEG>  16 pixels per lane, writes the bitmap, byte image optional. Blocks up to 9x9, width, strides
+//       and both images 16-byte aligned, compare in 16 bits.
+//   threshold_eo_kernel<PF, SEG, LAZY>  the same pass rebuilt on measured instruction costs for 7x7 blocks with |C| <= 200: the
+//       default configuration.
+// The byte image is left out (tiles + four border lines instead, expand_thres_kernel rebuilds a plane) only if the caller allows it
+// and no plane runs the strip kernel.
 // mean = round(S / b^2) is never formed: src - mean <= -C  <=>  (src + C) * b^2 <= S + b^2/2 (exact in integers); for
 // blocks up to 11x11 both sides fit 16 bits and the four comparisons are two packed 16-bit multiply-adds and subtracts.
-// Per output row the wave stores one dword of threshold bytes per lane; every 8 rows it stores the 8x8-pixel tiles
-// (one uint64 each) of the binary image with the 1-px frame cleared — the image cv::findContours binarises.
-// HBM traffic per frame: read W*H, write W*H + W*H/8. Border-start candidates come from the tiles (k_contours.hip).
+// Border-start candidates come from the tiles (k_contours.hip).
 #include <stdlib.h>
+
+#include <utility>
 
 #include "bits_tiles.h"
 #include "internal.h"
+#include "thr_plan.h"
 
 namespace ah {
 
@@ -56,6 +60,17 @@ __device__ __forceinline__ uint32_t from_right(uint32_t v) { return (uint32_t)__
 
 constexpr int STRIP = 256;       // pixels per wave and row: one aligned 256-byte load and store per row
 
+// One wavefront owns a vertical strip of 256 pixels: lane l holds 4 horizontally adjacent pixels (one dword of the gray
+// row), so a row is one aligned 256-byte load and one aligned 256-byte store per wave; lanes 0 and 63 also fetch the
+// ceil(R/4) dwords left / right of the strip that the horizontal sums need (they enter the DPP lane shifts as the value
+// shifted into the wave). The wave walks down its row segment keeping, in registers only,
+//   * a ring of the last 2R+1 gray rows and of their horizontal box sums (two u16 per dword, pixel pairs (0,2) and (1,3)),
+//   * the running vertical sums V (added row in, row out),
+// so every gray byte is read from HBM/L2 once (plus the halo overlap); there is no LDS tile and no re-read. The slot of
+// the ring that held the centre row is refilled at once with the row R+1 ahead, so R+1 loads are always in flight.
+// Per output row the wave stores one dword of threshold bytes per lane; every 8 rows it stores the 8x8-pixel tiles
+// (one uint64 each) of the binary image with the 1-px frame cleared - the image cv::findContours binarises.
+// HBM traffic per frame: read W*H, write W*H + W*H/8.
 // P16: (255 + |C| + 1) * b^2 + b^2/2 < 32768, checked by the host. FAST: width, strides and base address are multiples
 // of 4 (dword loads and stores).
 template <int R, int MODE, bool P16, bool FAST>
@@ -784,68 +799,45 @@ void launch_tile_bitmap(hipStream_t s, const FrameGeom& g, int nplanes, const Bu
     hipLaunchKernelGGL(tile_bitmap_kernel, dim3(ns, tny, nplanes), dim3(64), 0, s, b.tiles, b.tile_bits, tnx, tny, ns);
 }
 
-// returns true if the kernel that ran also wrote the non-empty-tile bitmap
-template <int R>
-static bool launch_adpt(hipStream_t s, const ThrArgs& a, int nframes, unsigned long long* stamp_acc) {
-    dim3 grid((a.width + STRIP - 1) / STRIP, (a.height + SEG - 1) / SEG, nframes);
-    constexpr bool CAN16 = R <= 5;
-    const long lim = (long)(256 + abs(a.idelta)) * a.n + a.n_half;
-    if constexpr (R <= 4) {
-        if (a.fast16 && lim < 32768) {
-            // prefetch depth 3 rows, 128-row segments: the best of the sweep (PF 2..5, segments 64 / 128 / 256, forced register
-            // budgets; profiles/r02_threshold_sweep.txt: 0.53 ms per 512 frames, everything else 0.54 .. 1.6)
-            // A wave walks down its segment row by row: a launch of few frames gets shorter segments so that it still spreads over
-            // the chip (one 640x480 frame: 4 waves of 128 rows took 91 us; 2R extra rows per segment are re-read, which only small
-            // launches can afford)
-            const int strips = (a.width + WSTRIP - 1) / WSTRIP;
-            const long waves128 = (long)strips * ((a.height + 127) / 128) * nframes;
-            int segs;
-            if constexpr (R == 3) {
-                if (abs(a.idelta) <= 200) {   // the round-3 form of this pass (7x7 blocks; its folded constants want a moderate C)
-                    const dim3 blk(64);
-#define EO_LAUNCH(SEG_)                                                                                                               \
-    do {                                                                                                                              \
-        segs = (a.height + (SEG_) - 1) / (SEG_);                                                                                      \
-        ThrArgs e = a;                                                                                                                \
-        e.eo_strips = strips, e.eo_segs = segs, e.eo_frames = nframes;                                                                \
-        const long nb = (((long)strips * segs * nframes + 8L * strips - 1) / (8L * strips)) * (8L * strips);                          \
-        if (a.thres)                                                                                                                  \
-            hipLaunchKernelGGL((threshold_eo_kernel<THR_PF, SEG_, false>), dim3((unsigned)nb), blk, 0, s, e);                         \
-        else                                                                                                                          \
-            hipLaunchKernelGGL((threshold_eo_kernel<THR_PF, SEG_, true>), dim3((unsigned)nb), blk, 0, s, e);                          \
-    } while (0)
-                    if (waves128 >= 512)
-                        EO_LAUNCH(128);
-                    else if (waves128 * 4 >= 512)
-                        EO_LAUNCH(32);
-                    else
-                        EO_LAUNCH(16);
-#undef EO_LAUNCH
-                    if (a.stamps) hipLaunchKernelGGL(stamp_reduce_kernel, dim3(1), dim3(1024), 0, s, a.stamps, (size_t)strips * segs * nframes, stamp_acc);
-                    return true;
-                }
-            }
-            if (waves128 >= 512) {
-                segs = (a.height + 127) / 128;
-                hipLaunchKernelGGL((threshold_wide_kernel<R, THR_PF, 128>), dim3(strips, segs, nframes), dim3(64), 0, s, a);
-            } else if (waves128 * 4 >= 512) {
-                segs = (a.height + 31) / 32;
-                hipLaunchKernelGGL((threshold_wide_kernel<R, THR_PF, 32>), dim3(strips, segs, nframes), dim3(64), 0, s, a);
-            } else {
-                segs = (a.height + 15) / 16;
-                hipLaunchKernelGGL((threshold_wide_kernel<R, THR_PF, 16>), dim3(strips, segs, nframes), dim3(64), 0, s, a);
-            }
-            if (a.stamps) hipLaunchKernelGGL(stamp_reduce_kernel, dim3(1), dim3(1024), 0, s, a.stamps, (size_t)strips * segs * nframes, stamp_acc);
-            return true;
-        }
-    }
-    if (!a.fast)
-        hipLaunchKernelGGL((threshold_strip_kernel<R, MODE_ADPT, false, false>), grid, dim3(64), 0, s, a);
-    else if (CAN16 && lim < 32768)
-        hipLaunchKernelGGL((threshold_strip_kernel<R, MODE_ADPT, CAN16, true>), grid, dim3(64), 0, s, a);
+// calls f(std::integral_constant<int, V>) for the V of the list that equals v
+template <int... Vs, class F>
+static void for_value(int v, std::integer_sequence<int, Vs...>, F&& f) {
+    (void)((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+
+// the strip kernel of <R, MODE> with the FAST / P16 the plan chose (P16 exists for adaptive blocks up to 11x11 only)
+template <int R, int MODE>
+static void launch_strip(hipStream_t s, const ThrArgs& a, int nframes, bool fast, bool p16) {
+    const dim3 grid((a.width + STRIP - 1) / STRIP, (a.height + SEG - 1) / SEG, nframes), blk(64);
+    constexpr bool CAN16 = MODE == MODE_ADPT && R <= 5;
+    if (!fast)
+        hipLaunchKernelGGL((threshold_strip_kernel<R, MODE, false, false>), grid, blk, 0, s, a);
+    else if (CAN16 && p16)
+        hipLaunchKernelGGL((threshold_strip_kernel<R, MODE, CAN16, true>), grid, blk, 0, s, a);
     else
-        hipLaunchKernelGGL((threshold_strip_kernel<R, MODE_ADPT, false, true>), grid, dim3(64), 0, s, a);
-    return false;
+        hipLaunchKernelGGL((threshold_strip_kernel<R, MODE, false, true>), grid, blk, 0, s, a);
+}
+
+// a wide / eo plane of the plan: the kernel of <R, q.seg>, then the span of its waves' stamps when timing is on
+template <int R>
+static void launch_16px(hipStream_t s, ThrArgs a, int nframes, const ThrPlan& pl, const ThrPlanePlan& q, unsigned long long* stamp_acc) {
+    static_assert(WSTRIP == THR_WSTRIP, "the plan's strips are the wide kernels' strips");
+    const int strips = pl.strips, segs = (a.height + q.seg - 1) / q.seg;
+    for_value(q.seg, std::integer_sequence<int, 16, 32, 128>{}, [&](auto seg) {
+        constexpr int SEGW = decltype(seg)::value;
+        if constexpr (R == 3)
+            if (q.family == THR_EO) {   // 1-D grid padded to whole groups of 8 x strips (threshold_eo_body unpacks it)
+                a.eo_strips = strips, a.eo_segs = segs, a.eo_frames = nframes;
+                const dim3 grid((unsigned)((((long)strips * segs * nframes + 8L * strips - 1) / (8L * strips)) * (8L * strips)));
+                if (pl.no_bytes)
+                    hipLaunchKernelGGL((threshold_eo_kernel<THR_PF, SEGW, true>), grid, dim3(64), 0, s, a);
+                else
+                    hipLaunchKernelGGL((threshold_eo_kernel<THR_PF, SEGW, false>), grid, dim3(64), 0, s, a);
+                return;
+            }
+        hipLaunchKernelGGL((threshold_wide_kernel<R, THR_PF, SEGW>), dim3(strips, segs, nframes), dim3(64), 0, s, a);
+    });
+    if (a.stamps) hipLaunchKernelGGL(stamp_reduce_kernel, dim3(1), dim3(1024), 0, s, a.stamps, (size_t)strips * segs * nframes, stamp_acc);
 }
 
 static void fill_args(ThrArgs& a, const uint8_t* gray, const FrameGeom& g, const Buffers& b, int nthr, int t) {
@@ -856,58 +848,35 @@ static void fill_args(ThrArgs& a, const uint8_t* gray, const FrameGeom& g, const
     a.idelta = 0, a.n = 1, a.n_half = 0;
     a.stamps = b.thr_stamp_on ? b.thr_stamps : nullptr;
     a.edge = nullptr;
-    a.fast = ((g.width | (int)(g.row_stride & 3) | (int)(g.frame_stride & 3) | (int)((uintptr_t)gray & 3)) & 3) == 0;
-    a.fast16 = g.width >= 16 && ((g.width | (int)(g.row_stride & 15) | (int)(g.frame_stride & 15) | (int)((uintptr_t)gray & 15) | (int)((uintptr_t)b.thres & 15)) & 15) == 0;
+    a.fast = thr_fast(g.width, g.row_stride, g.frame_stride, (uintptr_t)gray);
+    a.fast16 = thr_fast16(g.width, g.row_stride, g.frame_stride, (uintptr_t)gray, (uintptr_t)b.thres);
 }
 
-// lazy: the caller does not need the byte image now. Returns true if it was left out (every plane ran the 16-pixel-per-lane kernel,
-// which keeps the border lines instead: launch_expand_thres rebuilds a plane on demand).
+// lazy: the caller does not need the byte image now. Returns true if it was left out (every plane ran a 16-pixel-per-lane kernel,
+// which keeps the border lines instead: launch_expand_thres rebuilds a plane on demand). Executes thr_plan() and decides nothing itself.
 bool launch_threshold(hipStream_t s, const uint8_t* gray, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b, bool lazy) {
-    bool bitmap_done = true;
-    if (lazy) {   // all planes or none
-        ThrArgs a;
-        fill_args(a, gray, g, b, p.nthr, 0);
-        lazy = p.thres_method == ARUCOHIP_THRES_ADPT && a.fast16 && b.thres_edge != nullptr;
-        for (int t = 0; t < p.nthr && lazy; t++) {
-            const long n = (long)p.block[t] * p.block[t];
-            lazy = p.block[t] / 2 >= 1 && p.block[t] / 2 <= 4 && (long)(256 + abs(p.idelta)) * n + n / 2 < 32768;
-        }
-    }
+    const ThrPlan pl = thr_plan({g.width, g.height, g.row_stride, g.frame_stride, (uintptr_t)gray, (uintptr_t)b.thres, p.thres_method, p.nthr, p.block,
+                                 p.idelta, nframes, b.thres_edge != nullptr, lazy});
     for (int t = 0; t < p.nthr; t++) {
+        const ThrPlanePlan& q = pl.plane[t];
         ThrArgs a;
         fill_args(a, gray, g, b, p.nthr, t);
-        if (lazy) a.thres = nullptr, a.edge = b.thres_edge;
+        if (pl.no_bytes) a.thres = nullptr, a.edge = b.thres_edge;
         if (p.thres_method == ARUCOHIP_THRES_FIXED) {
             a.idelta = (int)floor(p.p1[t]);
-            dim3 grid((g.width + STRIP - 1) / STRIP, (g.height + SEG - 1) / SEG, nframes);
-            if (a.fast)
-                hipLaunchKernelGGL((threshold_strip_kernel<0, MODE_FIXED, false, true>), grid, dim3(64), 0, s, a);
-            else
-                hipLaunchKernelGGL((threshold_strip_kernel<0, MODE_FIXED, false, false>), grid, dim3(64), 0, s, a);
-            bitmap_done = false;
+            launch_strip<0, MODE_FIXED>(s, a, nframes, q.fast, false);
             continue;
         }
         a.n = p.block[t] * p.block[t], a.n_half = a.n / 2, a.idelta = p.idelta;
-        switch (p.block[t] / 2) {
-            case 1: bitmap_done &= launch_adpt<1>(s, a, nframes, (unsigned long long*)b.thr_acc); break;
-            case 2: bitmap_done &= launch_adpt<2>(s, a, nframes, (unsigned long long*)b.thr_acc); break;
-            case 3: bitmap_done &= launch_adpt<3>(s, a, nframes, (unsigned long long*)b.thr_acc); break;
-            case 4: bitmap_done &= launch_adpt<4>(s, a, nframes, (unsigned long long*)b.thr_acc); break;
-            case 5: bitmap_done &= launch_adpt<5>(s, a, nframes, (unsigned long long*)b.thr_acc); break;
-            case 6: bitmap_done &= launch_adpt<6>(s, a, nframes, (unsigned long long*)b.thr_acc); break;
-            case 7: bitmap_done &= launch_adpt<7>(s, a, nframes, (unsigned long long*)b.thr_acc); break;
-            case 8: bitmap_done &= launch_adpt<8>(s, a, nframes, (unsigned long long*)b.thr_acc); break;
-            case 9: bitmap_done &= launch_adpt<9>(s, a, nframes, (unsigned long long*)b.thr_acc); break;
-            case 10: bitmap_done &= launch_adpt<10>(s, a, nframes, (unsigned long long*)b.thr_acc); break;
-            case 11: bitmap_done &= launch_adpt<11>(s, a, nframes, (unsigned long long*)b.thr_acc); break;
-            case 12: bitmap_done &= launch_adpt<12>(s, a, nframes, (unsigned long long*)b.thr_acc); break;
-            case 13: bitmap_done &= launch_adpt<13>(s, a, nframes, (unsigned long long*)b.thr_acc); break;
-            case 14: bitmap_done &= launch_adpt<14>(s, a, nframes, (unsigned long long*)b.thr_acc); break;
-            default: bitmap_done &= launch_adpt<15>(s, a, nframes, (unsigned long long*)b.thr_acc); break;
-        }
+        for_value(q.R, std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>{}, [&](auto r) {
+            constexpr int R = decltype(r)::value;
+            if constexpr (R <= 4)
+                if (q.family != THR_STRIP) return launch_16px<R>(s, a, nframes, pl, q, (unsigned long long*)b.thr_acc);
+            launch_strip<R, MODE_ADPT>(s, a, nframes, q.fast, q.p16);
+        });
     }
-    if (!bitmap_done) launch_tile_bitmap(s, g, nframes * p.nthr, b);
-    return lazy;
+    if (pl.bitmap_pass) launch_tile_bitmap(s, g, nframes * p.nthr, b);
+    return pl.no_bytes;
 }
 
 // Optional erosion (north_star; off by default, no reference counterpart in this snapshot): 3x3 minimum of the thresholded
@@ -1038,13 +1007,9 @@ void launch_erode_tiles(hipStream_t s, const FrameGeom& g, int nplanes, const Bu
 
 // detectRectangles on a caller-supplied thresholded image (markerdetector.h:261): only the tiled binary image.
 void launch_binary_planes(hipStream_t s, const uint8_t* thres_in, const FrameGeom& g, int nframes, const Buffers& b) {
-    dim3 grid((g.width + STRIP - 1) / STRIP, (g.height + SEG - 1) / SEG, nframes);
     ThrArgs a;
     fill_args(a, thres_in, g, b, 1, 0);
-    if (a.fast)
-        hipLaunchKernelGGL((threshold_strip_kernel<0, MODE_BINARY, false, true>), grid, dim3(64), 0, s, a);
-    else
-        hipLaunchKernelGGL((threshold_strip_kernel<0, MODE_BINARY, false, false>), grid, dim3(64), 0, s, a);
+    launch_strip<0, MODE_BINARY>(s, a, nframes, a.fast, false);
     launch_tile_bitmap(s, g, nframes, b);
 }
 

@@ -138,3 +138,16 @@ def test_reference_apps_compile_against_the_shim():
     for exe in apps:
         r = subprocess.run([exe], capture_output=True, text=True)
         assert r.returncode == 0 and "Usage" in r.stderr
+
+
+def test_threshold_plan_never_leaves_the_byte_image_out_under_a_strip_kernel(tmp_path):
+    """aruco_amd/csrc/thr_plan.h decides, per threshold plane, which kernel family runs and whether the byte image is left out; it is
+    plain C++ so that tests/cpp/thr_plan_check.cpp can walk it with the host compiler over widths, strides, alignments, block sizes, C,
+    batch sizes and plane counts. The strip kernel stores through the byte image's pointer without a test: a plan that leaves the image
+    out while a plane runs that kernel would fault the device, which no GPU test may provoke. The program also checks the conditions of
+    the eo / wide kernels, of P16 / FAST, the segment-height rule and when the bitmap pass runs."""
+    exe = str(tmp_path / "thr_plan_check")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tests", "cpp", "thr_plan_check.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr[-3000:]
+    assert " 0 failures" in r.stdout
