@@ -66,6 +66,7 @@ SYMBOLS = [
     "arucohip_get_stream", "arucohip_synchronize", "arucohip_detect", "arucohip_detect_batch", "arucohip_batch_status", "arucohip_batch_chunks",
     "arucohip_get_thresholded", "arucohip_get_candidates", "arucohip_threshold", "arucohip_detect_rectangles",
     "arucohip_warp", "arucohip_debug_num_contours", "arucohip_debug_contour", "arucohip_debug_candidates", "arucohip_debug_otsu",
+    "arucohip_debug_cells",
     "arucohip_board_detect", "arucohip_calculate_extrinsics", "arucohip_stage_times", "arucohip_stage_name",
     "arucohip_enable_timing", "arucohip_kernel_times", "arucohip_threshold_exec_ms", "arucohip_kernel_name",
     "arucohip_debug_counters", "arucohip_board_detect_batch",
@@ -501,6 +502,13 @@ class Handle:
         n = C.c_int(0)
         self._chk(self.L.arucohip_debug_otsu(self.h, frame, _ptr(t), cap, C.byref(n)))
         return t[:n.value].copy()
+
+    def debug_cells(self, frame=0, cap=512):
+        """Cell medians (7 x 7, the 33rd-largest of each cell's 64 pixels) of every candidate's 56x56 patch, candidate order of debug_candidates."""
+        c = np.zeros((cap, 7, 7), np.uint8)
+        n = C.c_int(0)
+        self._chk(self.L.arucohip_debug_cells(self.h, frame, _ptr(c), cap, C.byref(n)))
+        return c[:n.value].copy()
 
     def debug_contours(self, frame=0):
         n = C.c_int(0)

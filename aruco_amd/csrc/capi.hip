@@ -306,6 +306,7 @@ static int create_handle(const arucohip_params_t* params, int device, const aruc
     ALLOC(b.iM, (size_t)b.cap_flat * 9 * sizeof(double));
     ALLOC(b.hist, (size_t)b.cap_flat * 256 * sizeof(uint16_t));
     ALLOC(b.othr, (size_t)b.cap_flat * sizeof(int32_t));
+    ALLOC(b.cells, (size_t)b.cap_flat * 64);
     ALLOC(b.markers, (F * b.cap_markers + 1) * sizeof(arucohip_marker_t));   // + the header slot of a one-frame call (k_finalize.hip: write_hdr)
     ALLOC(b.nmarkers, F * sizeof(int32_t));
     ALLOC(b.marker_list, F * (size_t)b.cap_markers * sizeof(uint32_t));
@@ -577,9 +578,11 @@ static int batch_prologue(arucohip_handle* h, const FrameGeom& g, int nframes, c
     int rc;
     if ((rc = ensure_walk_scratch(h, nframes * dp.nthr, dp))) return rc;
     if ((rc = ensure_bits_geometry(h, g.width, g.height))) return rc;
-    // canonical patches of the decode stage: cap_flat * warp_size^2 bytes
-    HIPCHK(h, h->patches.reserve((size_t)h->buf.cap_flat * dp.warp_size * dp.warp_size));
-    h->buf.patches = h->patches;
+    // canonical patches of the decode stage: cap_flat * warp_size^2 bytes, for the configurations whose kernels store and read them
+    if (!decode_from_cells(g, nframes, dp)) {
+        HIPCHK(h, h->patches.reserve((size_t)h->buf.cap_flat * dp.warp_size * dp.warp_size));
+        h->buf.patches = h->patches;
+    }
     return ARUCOHIP_OK;
 }
 
@@ -702,8 +705,10 @@ static int detect_core(arucohip_handle* h, const uint8_t* gray_dev, const FrameG
         if (rc_) return rc_;
     }
     MARK(K_DECODE);
-    // built-in 5x5 decoder: the cell votes and the Hamming decode of a candidate are the head of its refinement wave (one dispatch less)
-    const bool fused_cells = dp.decoder == ARUCOHIP_DECODER_FIDUCIAL_5X5;
+    // built-in 5x5 decoder: a batch decodes from cell medians inside launch_decode; on a stored patch (one frame per call, other warp sizes) the cell
+    // votes and the Hamming decode of a candidate are the head of its refinement wave (one dispatch less)
+    h->cells_valid = decode_from_cells(g, nframes, dp);
+    const bool fused_cells = dp.decoder == ARUCOHIP_DECODER_FIDUCIAL_5X5 && !h->cells_valid;
     if (RUN_STAGE(b.env, 6)) launch_decode(s, gray_dev, g, nframes, dp, b, fused_cells);
     if (dp.decoder == ARUCOHIP_DECODER_USER) {
         const int rc_ = user_decode_stage(h, dp);
@@ -919,6 +924,7 @@ static int detect_one_graphed(arucohip_handle* h, const uint8_t* frame, int W, i
     *handled = true;
     HIPCHK(h, hipGraphLaunch(h->fgraph.exec, h->stream));
     h->thres_bytes = h->fgraph.thres_bytes;
+    h->cells_valid = false;   // one frame per call stores the patch
     h->last = plan_batch(h, 1, W, H, dp.nthr);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const int32_t* hdr = (const int32_t*)(h->h_markers + h->buf.cap_markers);
@@ -1172,6 +1178,36 @@ int arucohip_debug_otsu(arucohip_handle* h0, int frame, int32_t* thr, int cap, i
     for (int i = 0; i < std::min(*n, cap); i++) thr[i] = -1;
     for (uint32_t i = 0; i < nflat; i++)
         if ((int)(list[i] >> 16) == frame && (int)(list[i] & 0xFFFFu) < cap) thr[list[i] & 0xFFFFu] = othr[i];
+    return *n > cap ? ARUCOHIP_E_CAPACITY : ARUCOHIP_OK;
+}
+
+// Cell medians of every candidate of a frame (same order): what warp_hist_kernel<ROWS, true> left for otsu_kernel<true> in the last batch
+int arucohip_debug_cells(arucohip_handle* h0, int frame, uint8_t* cells49, int cap, int* n) {
+    if (!h0 || !cells49 || !n) return ARUCOHIP_E_INVALID;
+    arucohip_handle* h = h0->last.holder(frame, &frame);
+    if (!h) return ARUCOHIP_E_INVALID;
+    if (!h->cells_valid) return fail(h, ARUCOHIP_E_INVALID, "the last batch did not decode from cell medians");
+    HIPCHK(h, hipSetDevice(h->device));
+    uint32_t cnt[CNT_FIXED];
+    int32_t nc = 0;
+    HIPCHK(h, hipMemcpyAsync(cnt, h->buf.counters, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&nc, h->buf.ncands + frame, sizeof(nc), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const uint32_t nflat = std::min(cnt[CNT_NCAND], h->buf.cap_flat);
+    std::vector<uint32_t> list(nflat);
+    std::vector<uint8_t> cells((size_t)nflat * 64);
+    if (nflat) {
+        HIPCHK(h, hipMemcpyAsync(list.data(), h->buf.cand_list, nflat * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(cells.data(), h->buf.cells, cells.size(), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    *n = std::max(nc, 0);
+    for (uint32_t i = 0; i < nflat; i++) {
+        const int ci = (int)(list[i] & 0xFFFFu);
+        if ((int)(list[i] >> 16) != frame || ci >= cap) continue;
+        for (int cy = 0; cy < 7; cy++)
+            for (int cx = 0; cx < 7; cx++) cells49[(size_t)ci * 49 + cy * 7 + cx] = cells[(size_t)i * 64 + cy * 8 + cx];
+    }
     return *n > cap ? ARUCOHIP_E_CAPACITY : ARUCOHIP_OK;
 }
 

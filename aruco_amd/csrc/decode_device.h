@@ -1,8 +1,9 @@
 // Device pieces of the decode stage that two kernels share (round 3: fewer, fatter dispatches in the chain).
 //   homography_lane   : inverse of cv::getPerspectiveTransform(quad -> patch corners), one candidate per LANE (the 8x8 system of every
 //                       lane lives in LDS, element-major) — the tail of frame_candidates_kernel since round 3, its own kernel before
-//   cells_decode_wave : FiducidalMarkers::detect on the Otsu-thresholded patch, one candidate per WAVEFRONT — the head of
-//                       refine_lines_kernel for the built-in 5x5 decoder since round 3, its own kernel for the other entry points
+//   fiducial_decode_word : FiducidalMarkers::detect on the 49 cell votes of a candidate, one candidate per LANE — the tail of otsu_kernel on the
+//                       default path (votes from the cell medians warp_hist_kernel kept), lane 0 of cells_decode_wave otherwise
+//   cells_decode_wave : the cell votes on a stored, Otsu-thresholded patch, one candidate per WAVEFRONT (cells_decode_kernel: warp sizes other than 56)
 // Reference: MarkerDetector::warp src/markerdetector.cpp:684-697, FiducidalMarkers::detect src/arucofidmarkers.cpp:438-452 with
 // analyzeMarkerImage :100-137, checkBorders :168-184, getMarkerCode :189-204, hammDistMarker :74-98, rotate :63-72.
 #pragma once
@@ -185,10 +186,55 @@ __device__ __forceinline__ int hamm_rows(const uint32_t v[5]) {
     return dist;
 }
 
+// Cell votes of a 7x7 patch as a word (bit cy * 7 + cx = cell is white) -> FiducidalMarkers::detect: checkBorders, then the 5x5 code's Hamming distance
+// in its four rotations; id = -1: not a marker. One lane's work: lane 0 of cells_decode_wave, every lane of otsu_kernel's cell-median variant.
+__device__ __forceinline__ void fiducial_decode_word(unsigned long long m, int* id_out, int* nrot_out) {
+    int id = -1, nrot = 0;
+    // checkBorders: all 24 frame cells must be black
+    unsigned long long border = 0x7Full | (0x7Full << 42);
+#pragma unroll
+    for (int y = 1; y < 6; y++) border |= (1ull << (7 * y)) | (1ull << (7 * y + 6));
+    if ((m & border) == 0) {
+        uint32_t cur[5], best[5];
+#pragma unroll
+        for (int y = 0; y < 5; y++) cur[y] = (uint32_t)(m >> (7 * (y + 1) + 1)) & 31u, best[y] = cur[y];
+        int min_dist = hamm_rows(cur);
+#pragma unroll
+        for (int r = 1; r < 4; r++) {
+            uint32_t nxt[5];   // rotate: new[i][j] = old[4-j][i]
+#pragma unroll
+            for (int i = 0; i < 5; i++) {
+                nxt[i] = 0;
+#pragma unroll
+                for (int j = 0; j < 5; j++) nxt[i] |= ((cur[4 - j] >> i) & 1u) << j;
+            }
+#pragma unroll
+            for (int i = 0; i < 5; i++) cur[i] = nxt[i];
+            const int dd = hamm_rows(cur);
+            if (dd < min_dist) {
+                min_dist = dd, nrot = r;
+#pragma unroll
+                for (int i = 0; i < 5; i++) best[i] = cur[i];
+            }
+        }
+        if (min_dist == 0) {
+            id = 0;
+#pragma unroll
+            for (int y = 0; y < 5; y++) id |= (int)((((best[y] >> 1) & 1u) << 1) | ((best[y] >> 3) & 1u)) << (2 * (4 - y));
+        }
+    }
+    *id_out = id, *nrot_out = nrot;
+}
+
+// Cells per candidate row of Buffers::cells: the 7 x 7 cell medians at byte cy * CELLS_PITCH + cx, one 64-byte row per candidate
+constexpr int CELLS_PITCH = 8;
+// A cell's vote "more than half of its pixels exceed thr" is "its (half + 1)-th largest pixel exceeds thr": the rank warp_hist_kernel selects
+constexpr int cell_vote_rank(int sw) { return (sw * sw) / 2 + 1; }
+
 // all 64 lanes call it; *id / *nrot are valid on lane 0 (id = -1: not a marker)
 __device__ __forceinline__ void cells_decode_wave(const uint8_t* patch, int ws, int thr, int lane, int* id_out, int* nrot_out) {
     const int sw = ws / 7;
-    const int half = (sw * sw) / 2;
+    const int half = cell_vote_rank(sw) - 1;
     bool white = false;
     if (lane < 49) {   // cell (cy,cx): white iff more than half of its pixels exceed the Otsu threshold
         const int cy = lane / 7, cx = lane - cy * 7;
@@ -208,41 +254,7 @@ __device__ __forceinline__ void cells_decode_wave(const uint8_t* patch, int ws, 
     }
     const unsigned long long m = __ballot(white);   // bit cy*7+cx
     int id = -1, nrot = 0;
-    if (lane == 0) {
-        // checkBorders: all 24 frame cells must be black
-        unsigned long long border = 0x7Full | (0x7Full << 42);
-#pragma unroll
-        for (int y = 1; y < 6; y++) border |= (1ull << (7 * y)) | (1ull << (7 * y + 6));
-        if ((m & border) == 0) {
-            uint32_t cur[5], best[5];
-#pragma unroll
-            for (int y = 0; y < 5; y++) cur[y] = (uint32_t)(m >> (7 * (y + 1) + 1)) & 31u, best[y] = cur[y];
-            int min_dist = hamm_rows(cur);
-#pragma unroll
-            for (int r = 1; r < 4; r++) {
-                uint32_t nxt[5];   // rotate: new[i][j] = old[4-j][i]
-#pragma unroll
-                for (int i = 0; i < 5; i++) {
-                    nxt[i] = 0;
-#pragma unroll
-                    for (int j = 0; j < 5; j++) nxt[i] |= ((cur[4 - j] >> i) & 1u) << j;
-                }
-#pragma unroll
-                for (int i = 0; i < 5; i++) cur[i] = nxt[i];
-                const int dd = hamm_rows(cur);
-                if (dd < min_dist) {
-                    min_dist = dd, nrot = r;
-#pragma unroll
-                    for (int i = 0; i < 5; i++) best[i] = cur[i];
-                }
-            }
-            if (min_dist == 0) {
-                id = 0;
-#pragma unroll
-                for (int y = 0; y < 5; y++) id |= (int)((((best[y] >> 1) & 1u) << 1) | ((best[y] >> 3) & 1u)) << (2 * (4 - y));
-            }
-        }
-    }
+    if (lane == 0) fiducial_decode_word(m, &id, &nrot);
     *id_out = id, *nrot_out = nrot;
 }
 

@@ -94,6 +94,7 @@ struct arucohip_handle {
     std::vector<Mem<void>> held;      // create-time memory, held for the handle's life: the Buffers arrays, zero_block, d_small_*, d_patch, pinned staging
     Mem<uint32_t> walk_scratch;       // buf.walk_scratch
     Mem<uint8_t> patches;             // buf.patches
+    bool cells_valid = false;         // buf.cells holds the last batch's cell medians (decode_from_cells; arucohip_debug_cells)
     Mem<uint8_t> d_gray;              // staging for host frames (gray) and the converted BGR frames
     Mem<uint8_t> d_bgr;               // staging for host BGR frames
     arucohip_marker_t* wt_out = nullptr;   // set around detect_core by chunk_enqueue: finalize_kernel writes the results there too
@@ -155,7 +156,9 @@ struct arucohip_handle {
     // The captured launches carry device addresses by value; a replay needs every one of them to be live and as large as at the capture:
     // - in the value key: dp.hrm_codes (d_hrm), and buf.thr_stamp_on, which picks the threshold kernel's stamp pointer;
     // - compared with `addrs` before a replay and after a capture: gray_dev (d_gray for host gray and BGR frames), buf.walk_scratch and
-    //   buf.patches, which calls of other shapes grow. An equal address is enough, since reserve() never shrinks;
+    //   buf.patches, which calls of other shapes grow. An equal address is enough, since reserve() never shrinks. The captured chain is that of
+    //   ONE frame, which always stores its patches (decode_from_cells is false below three frames), so batch_prologue reserves them before every
+    //   capture and replay; batches that decode from cell medians neither touch nor move buf.patches, and buf.cells is create-time memory;
     // - neither: the other Buffers arrays, zero_block and h_markers are create-time memory (`held`); d_erode, d_canny and the user decoder's
     //   staging belong to configurations that are not graphed; wt_out is set only inside chunk_enqueue, which does not run this path.
     //   Memory no captured launch reads (d_bgr, undistortion, calibration, board and GL batches, EM, HRM and ChromaticMask scratch) may

@@ -177,7 +177,8 @@ struct Buffers {
     double* iM;            // [cap_flat][9] inverse homographies
     uint16_t* hist;        // [cap_flat][256] patch histograms
     int32_t* othr;         // [cap_flat] Otsu thresholds
-    uint8_t* patches;      // [cap_flat][warp_size^2] canonical patches
+    uint8_t* patches;      // [cap_flat][warp_size^2] canonical patches, where something reads them (decode_from_cells: nothing does)
+    uint8_t* cells;        // [cap_flat][64] medians of the 7 x 7 cells of a 56 x 56 patch, 8 to a row (decode_from_cells)
     uint32_t cap_flat;
     arucohip_marker_t* markers;
     int32_t* nmarkers;     // [F]
@@ -229,7 +230,11 @@ constexpr size_t GEN_CNT_WORDS = 2 * 32 * 32 * 8;                 // words of Bu
 void launch_segments(hipStream_t s, const FrameGeom& g, int nplanes, const DetectParams& p, const Buffers& b);
 void launch_contour_quads(hipStream_t s, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b, int pass = 0);
 void launch_frame_candidates(hipStream_t s, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b);
-// fused_cells: the built-in 5x5 decoder runs as the head of refine_lines_kernel (launch_refine_lines with the same flag) instead of a kernel of its own
+// warp + histogram, Otsu threshold, id / rotation of every candidate (left in Cand; the caller's decoder: warp only). decode_from_cells: the batch
+// takes the variant that keeps 49 cell medians per candidate instead of the stored patch and decodes in otsu_kernel (k_decode.hip).
+// fused_cells: the built-in 5x5 decoder on a stored patch runs as the head of refine_lines_kernel (launch_refine_lines with the same flag) instead of
+// a kernel of its own; never together with decode_from_cells
+bool decode_from_cells(const FrameGeom& g, int nframes, const DetectParams& p);
 void launch_decode(hipStream_t s, const uint8_t* gray, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b, bool fused_cells = false);
 void launch_set_decoded(hipStream_t s, const Buffers& b, uint32_t n, const int2* id_nrot_dev);
 void launch_refine_lines(hipStream_t s, const FrameGeom& g, int nframes, const DetectParams& p, const CamModel& cam, const Buffers& b, bool fused_cells = false);

@@ -66,7 +66,8 @@ struct DecodeArgs {
     double* iM;                  // [cap_flat][9]
     uint16_t* hist;              // [cap_flat][256]
     int32_t* othr;               // [cap_flat]
-    uint8_t* patches;            // [cap_flat][ws*ws]
+    uint8_t* patches;            // [cap_flat][ws*ws], written unless the kernel keeps cell medians instead (warp_hist_kernel<ROWS, true>)
+    uint8_t* cells;              // [cap_flat][64] cell medians of the 56 x 56 patch (decode_device.h: CELLS_PITCH)
 };
 
 // 5a (inverse homography, one candidate per lane) is the tail of frame_candidates_kernel since round 3: decode_device.h, k_contours.hip
@@ -130,14 +131,20 @@ __device__ __forceinline__ uint8_t warp_gather(const uint8_t* src, size_t row_st
 // WS = 56 (the reference's default markerWarpSize, src/markerdetector.cpp:246): a patch is 7 x 7 blocks, a step of the loop is one block row, so the
 // column terms of the seven blocks are formed once per candidate and the row terms once per block row, and no pixel needs a bounds test (round 3:
 // the stream is bound by vector-instruction issue, and these were a third of the kernel's). WS = 0: any size, everything per pixel.
-template <int WS, int ROWS>
+// CELLS (WS = 56, built-in 5x5 decoder): the patch is not stored. All the decoder asks of it is, per 8x8 cell, whether more than half of the pixels
+// exceed the Otsu threshold, that is whether the cell's 33rd-largest pixel does - and a wave-gather IS one cell, so the wave selects that order
+// statistic while it holds the 64 samples (radix select from the top bit down: a compare and a ballot's population count per bit) and the
+// candidate leaves 49 bytes behind instead of 3136. otsu_kernel compares them with the threshold it has just found and decodes in the same lane.
+template <int WS, int ROWS, bool CELLS>
 __device__ __forceinline__ void warp_hist_candidate(const DecodeArgs& a, const uint32_t idx, uint32_t* hist, const double* siM, const int lane) {
     const uint32_t e = a.cand_list[idx];
     const uint8_t* src = a.gray + (size_t)(e >> 16) * a.frame_stride;
     const int W = a.width, H = a.height;
     const int ws = WS ? WS : a.ws, npx = ws * ws;
     const bool bytes = HLANES * ((ws + 7) / 8) * ((ws + 7) / 8) < 256;   // pixels a copy can see: a byte counter must hold them
-    uint8_t* patch = a.patches + (size_t)idx * npx;
+    static_assert(!CELLS || (WS == 8 * GQ && WS / 7 == 8 && GQ <= CELLS_PITCH), "a wave-gather must be a cell of the 7 x 7 grid");
+    uint8_t* patch = CELLS ? nullptr : a.patches + (size_t)idx * npx;
+    uint32_t mycell = 0;   // CELLS: lane CELLS_PITCH * cy + cx keeps the median of cell (cy, cx)
     uint32_t* myhist = bytes ? hist + (lane / HLANES) * HPITCH : hist + (lane & (HWCOPIES - 1)) * HWPITCH;
     const double m0 = siM[0], m1 = siM[1], m2 = siM[2], m3 = siM[3], m4 = siM[4], m5 = siM[5], m6 = siM[6], m7 = siM[7], m8 = siM[8];
     // The 64 lanes of a gather take an 8x8 block of patch pixels (lane = 8 * row + column inside the block), GQ blocks in
@@ -169,12 +176,24 @@ __device__ __forceinline__ void warp_hist_candidate(const DecodeArgs& a, const u
             for (int rr = 0; rr < ROWS; rr++) {
                 const int BY = BY0 + rr;
                 if (BY < GQ) {
+                    uint32_t rowcells[2] = {0, 0};   // CELLS: the medians of this block row's cells, a byte each (wave-uniform)
 #pragma unroll
                     for (int q = 0; q < GQ; q++) {
-                        prow[BY * 8 * WS + q * 8] = v[rr][q];
+                        if (CELLS) {
+                            uint32_t t = 0;   // the largest t with at least `rank` samples >= t
+#pragma unroll
+                            for (int bit = 7; bit >= 0; bit--) {
+                                const uint32_t c = t | (1u << bit);
+                                if (__popcll(__ballot((uint32_t)v[rr][q] >= c)) >= cell_vote_rank(8)) t = c;
+                            }
+                            rowcells[q >> 2] |= t << (8 * (q & 3));
+                        } else {
+                            prow[BY * 8 * WS + q * 8] = v[rr][q];
+                        }
                         psum += v[rr][q];
                         atomicAdd(&myhist[v[rr][q] >> 2], 1u << (8 * (v[rr][q] & 3)));
                     }
+                    if (CELLS && byl == BY) mycell = ((bxl < 4 ? rowcells[0] : rowcells[1]) >> (8 * (bxl & 3))) & 0xFFu;
                 }
             }
         }
@@ -221,6 +240,7 @@ __device__ __forceinline__ void warp_hist_candidate(const DecodeArgs& a, const u
             for (int q = 0; q < 4; q++) hsum[q] += hist[c * HWPITCH + 4 * lane + q];
     }
     ((uint2*)(a.hist + (size_t)idx * 256))[lane] = make_uint2(hsum[0] | (hsum[1] << 16), hsum[2] | (hsum[3] << 16));
+    if (CELLS) a.cells[(size_t)idx * 64 + lane] = (uint8_t)mycell;
     // the pixel sum travels in the candidate's threshold slot: otsu_kernel reads it there and puts the threshold in its place
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) psum += (uint32_t)__shfl_xor((int)psum, o, 64);
@@ -230,8 +250,10 @@ __device__ __forceinline__ void warp_hist_candidate(const DecodeArgs& a, const u
 #ifndef WARP_WAVES_N
 #define WARP_WAVES_N 2   // waves per SIMD the register allocator aims at (170 VGPRs unconstrained = 2)
 #endif
-template <int ROWS>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WARP_WAVES_N, WARP_WAVES_N))) void warp_hist_kernel(DecodeArgs a) {
+constexpr int WARP_WAVES_CELLS = 4;   // the cell-median kernel has neither the any-size path nor the patch addresses: 112 VGPRs unconstrained
+// CELLS: launch_decode has checked what the patch-storing kernel tests per candidate below (56 x 56 patch, frame below 4 GB)
+template <int ROWS, bool CELLS>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CELLS ? WARP_WAVES_CELLS : WARP_WAVES_N, CELLS ? WARP_WAVES_CELLS : WARP_WAVES_N))) void warp_hist_kernel(DecodeArgs a) {
     throughput_bound_priority();
     __shared__ uint32_t hist[HCOPIES * HPITCH];
     __shared__ double siM[9];
@@ -252,10 +274,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WARP_WAVES_N
         for (int i = lane; i < HCOPIES * HPITCH; i += WAVE) hist[i] = 0;
         if (lane < 9) siM[lane] = a.iM[(size_t)idx * 9 + lane];
         __syncthreads();
-        if (a.ws == 8 * GQ && a.row_stride * (size_t)a.height < ((size_t)1 << 32))
-            warp_hist_candidate<8 * GQ, ROWS>(a, idx, hist, siM, lane);
+        if (CELLS)
+            warp_hist_candidate<8 * GQ, ROWS, true>(a, idx, hist, siM, lane);
+        else if (a.ws == 8 * GQ && a.row_stride * (size_t)a.height < ((size_t)1 << 32))
+            warp_hist_candidate<8 * GQ, ROWS, false>(a, idx, hist, siM, lane);
         else
-            warp_hist_candidate<0, 1>(a, idx, hist, siM, lane);
+            warp_hist_candidate<0, 1, false>(a, idx, hist, siM, lane);
     }
 }
 
@@ -268,6 +292,9 @@ constexpr int OTSU_PITCH = 66;   // halfwords per bin row: 64 candidates + paddi
 constexpr int OTSU_BINS = 64;    // bins staged at a time
 // Round 4 measured a sweep that skips runs of empty bins once mu1 has reached its fixed point (bit-identical, a third of the divisions): the lane's
 // branches cost more than the divisions save - 93-106 us against 50 us for the 15 candidates of a 640x480 still, 0.43 against 0.41 ms per 1024-frame batch. Not kept.
+// DECODE: warp_hist_kernel left the candidate's cell medians; the lane that has found the threshold compares the 49 of them with it and runs
+// FiducidalMarkers::detect on the word (what lane 0 of cells_decode_wave does for a stored patch): 64 candidates decode per wave instead of one.
+template <bool DECODE>
 __global__ __launch_bounds__(64) void otsu_kernel(DecodeArgs a) {
     latency_bound_priority();
     __shared__ uint16_t sh[OTSU_BINS * OTSU_PITCH];
@@ -357,11 +384,33 @@ __global__ __launch_bounds__(64) void otsu_kernel(DecodeArgs a) {
             }
         }
     }
-    if (lane < cnt) a.othr[idx] = (int)max_val;
+    if (lane < cnt) {
+        const int thr = (int)max_val;
+        a.othr[idx] = thr;
+        if (DECODE) {
+            const uint2* row = (const uint2*)(a.cells + (size_t)idx * 64);
+            unsigned long long m = 0;   // bit cy * 7 + cx: the cell is white
+#pragma unroll
+            for (int cy = 0; cy < 7; cy++) {
+                const uint2 w = row[cy];
+#pragma unroll
+                for (int cx = 0; cx < 7; cx++) {
+                    const int px = (int)(((cx < 4 ? w.x : w.y) >> (8 * (cx & 3))) & 0xFFu);
+                    m |= (unsigned long long)(px > thr) << (cy * 7 + cx);
+                }
+            }
+            int id, nrot;
+            fiducial_decode_word(m, &id, &nrot);
+            const uint32_t e = a.cand_list[idx];
+            Cand* cand = a.cands + (size_t)(e >> 16) * a.cap_cands + (e & 0xFFFFu);
+            cand->id = id, cand->nrot = nrot;
+        }
+    }
 }
 
-// 5d: one wavefront per candidate — 7x7 cell votes on the binarised patch and the 5x5 Hamming decode (decode_device.h). Since round 3 the
-// default pipeline runs it as the head of refine_lines_kernel; this kernel remains for callers that want the ids without the refinement.
+// 5d: one wavefront per candidate — 7x7 cell votes on the binarised patch and the 5x5 Hamming decode (decode_device.h), for the built-in decoder
+// on a stored patch (one frame per call, a warp size other than 56, a frame of 4 GB or more). The pipeline runs it as the head of refine_lines_kernel
+// there; this kernel remains for callers that want the ids without the refinement. Batches decode from the cell medians in otsu_kernel<true>.
 __global__ __launch_bounds__(64) void cells_decode_kernel(DecodeArgs a) {
     latency_bound_priority();
     const uint32_t n = min(a.counters[CNT_NCAND], a.cap_flat);
@@ -440,23 +489,34 @@ __global__ __launch_bounds__(64) void hrm_decode_kernel(DecodeArgs a, HrmArgs d)
     }
 }
 
+// Does the batch decode from cell medians (no stored patch)? The built-in 5x5 decoder on the 56 x 56 patch of a frame the fast sampler takes.
+// Everything that reads Buffers::patches - the caller's decoder, a dictionary (hrm_decode_kernel), cells_decode_wave - keeps the stored patch.
+// So does one frame per call (the ROWS = 2 kernel): there a candidate's wave has its SIMD to itself and the kernel's time is its chain of
+// dependent instructions, which the select lengthens - measured 0.01-0.03 ms per call slower on the latency cases (profiles/decode_cells_ab.txt).
+bool decode_from_cells(const FrameGeom& g, int nframes, const DetectParams& p) {
+    return nframes > 2 && p.decoder == ARUCOHIP_DECODER_FIDUCIAL_5X5 && p.warp_size == 8 * GQ && g.row_stride * (size_t)g.height < ((size_t)1 << 32);
+}
+
 void launch_decode(hipStream_t s, const uint8_t* gray, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b, bool fused_cells) {
     DecodeArgs a;
     a.gray = gray, a.row_stride = g.row_stride, a.frame_stride = g.frame_stride, a.width = g.width, a.height = g.height;
     a.ws = p.warp_size, a.cands = b.cands, a.cap_cands = b.cap_cands;
-    a.cand_list = b.cand_list, a.counters = b.counters, a.cap_flat = b.cap_flat, a.iM = b.iM, a.hist = b.hist, a.othr = b.othr, a.patches = b.patches;
+    a.cand_list = b.cand_list, a.counters = b.counters, a.cap_flat = b.cap_flat, a.iM = b.iM, a.hist = b.hist, a.othr = b.othr, a.patches = b.patches, a.cells = b.cells;
+    const bool cells = decode_from_cells(g, nframes, p);
     const int lane_blocks = (int)((b.cap_flat + 63) / 64);
     const int wave_blocks = (int)std::min<uint32_t>(b.cap_flat, (uint32_t)nframes * 48u);
     // the inverse homographies are there already: frame_candidates_kernel solved them (b.iM)
     // one frame per call: the XCD-run unpacking sends list entries 0..47 to the slots of XCD 0 only - with 48 workgroups six of them took all the
     // candidates, eight one after the other (47 us for a 1080p frame); a workgroup per slot of the first run instead
     const int warp_blocks = nframes <= 2 ? (int)std::min<uint32_t>(b.cap_flat, 8u * XCD_RUN) : wave_blocks;
-    if (nframes <= 2)
-        hipLaunchKernelGGL(warp_hist_kernel<2>, dim3(warp_blocks), dim3(64), 0, s, a);
-    else
-        hipLaunchKernelGGL(warp_hist_kernel<1>, dim3(warp_blocks), dim3(64), 0, s, a);
+    auto* const warp_hist = cells ? warp_hist_kernel<1, true> : nframes <= 2 ? warp_hist_kernel<2, false> : warp_hist_kernel<1, false>;
+    hipLaunchKernelGGL(warp_hist, dim3(warp_blocks), dim3(64), 0, s, a);
     if (p.decoder == ARUCOHIP_DECODER_USER) return;   // the host callback decodes the patches (capi.hip: user_decode_stage)
-    hipLaunchKernelGGL(otsu_kernel, dim3(lane_blocks), dim3(64), 0, s, a);
+    if (cells) {
+        hipLaunchKernelGGL(otsu_kernel<true>, dim3(lane_blocks), dim3(64), 0, s, a);   // threshold, then id and rotation in the same lane
+        return;
+    }
+    hipLaunchKernelGGL(otsu_kernel<false>, dim3(lane_blocks), dim3(64), 0, s, a);
     if (p.decoder == 1) {
         HrmArgs d{p.hrm_n, p.hrm_count, p.hrm_correction, p.hrm_codes};
         hipLaunchKernelGGL(hrm_decode_kernel, dim3(wave_blocks), dim3(64), 0, s, a, d);

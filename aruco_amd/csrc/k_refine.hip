@@ -48,7 +48,8 @@ struct LinesArgs {
     const uint32_t* cand_list;   // frame << 16 | index, counters[CNT_NCAND] entries
     const uint32_t* counters;
     uint32_t cap_flat;
-    // round 3: the built-in 5x5 decoder as the head of this kernel (decode_device.h: cells_decode_wave)
+    // the built-in 5x5 decoder on a STORED patch as the head of this kernel (decode_device.h: cells_decode_wave): one frame per call, warp sizes
+    // other than 56. Batches decode upstream from cell medians (otsu_kernel<true>) and come here with the flag off, like every other decoder.
     int fused_cells, ws;
     const uint8_t* patches;      // [cap_flat][ws * ws]
     const int32_t* othr;         // [cap_flat] Otsu thresholds

@@ -291,6 +291,9 @@ int arucohip_debug_candidates(arucohip_handle* h, int frame, float* quads0, int3
 /* Otsu threshold (cv::threshold THRESH_OTSU inside the decoders, arucofidmarkers.cpp:169 / highlyreliablemarkers.cpp:346) of every candidate's patch,
  * same order; -1 where the decode stage did not run for the candidate. */
 int arucohip_debug_otsu(arucohip_handle* h, int frame, int32_t* thr, int cap, int* n);
+/* Cell medians of every candidate's patch, same order: cells49[49 * i + 7 * cy + cx] = the 33rd-largest of the 64 pixels of cell (cy, cx) of candidate
+ * i's 56x56 patch. The last batch must have decoded from them (built-in 5x5 decoder, warp size 56, three frames or more); ARUCOHIP_E_INVALID otherwise. */
+int arucohip_debug_cells(arucohip_handle* h, int frame, uint8_t* cells49, int cap, int* n);
 
 /* Device list fill levels of the last batch: [0] border-start candidates, [1] borders kept, [2] contour points,
  * [3] overflow bits. For sizing arucohip_limits_t. */
