@@ -590,7 +590,9 @@ class Handle:
         c = np.zeros(8, np.uint32)
         self._chk(self.L.arucohip_debug_counters(self.h, _ptr(c)))
         return {"raw": int(c[4]), "triggers": int(c[0]), "contours": int(c[1]), "points": int(c[2]), "status": int(c[3]),
-                "long_walks": int(c[4])}   # walker mode: [4] = long walks (checkpoint rings handed out)
+                "long_walks": int(c[4]),   # walker mode: [4] = long walks (checkpoint rings handed out)
+                "late_walks": int(c[6]),   # of them: walks that reached the late generations (borders above 960 points)
+                "side_streams": int(c[7])}   # workers of the batch that own a side stream for those generations (a pipeline lane: 0)
 
     def gl_modelview_batch(self, nframes, cap=64):
         """Marker::glGetModelViewMatrix for every marker of the last batch (device kernel): list per frame of [n][16]."""

@@ -199,13 +199,14 @@ static int inherit(arucohip_handle* parent, arucohip_handle* child) {
     });
 }
 
-// is_kid: the handle is one of another's chunk workers and gets none of its own; env: the switches of the handle the caller creates
-static int create_handle(const arucohip_params_t* params, int device, const arucohip_limits_t* lim, bool is_kid, const EnvSettings& env,
+// is_kid: the handle is one of another's chunk workers and gets none of its own; in_lane: it is a pipeline lane or a lane's chunk worker, whose
+// batches run with other batches in flight: no side stream (WalkFork); env: the switches of the handle the caller creates
+static int create_handle(const arucohip_params_t* params, int device, const arucohip_limits_t* lim, bool is_kid, bool in_lane, const EnvSettings& env,
                          arucohip_handle** out);
 
 // a new child of `parent` with limits `lim`, holding the parent's settings and environment switches (errors are reported on the parent)
-static int create_child(arucohip_handle* parent, const arucohip_limits_t& lim, bool is_kid, arucohip_handle** out) {
-    int rc = create_handle(&parent->params, parent->device, &lim, is_kid, parent->buf.env, out);
+static int create_child(arucohip_handle* parent, const arucohip_limits_t& lim, bool is_kid, bool in_lane, arucohip_handle** out) {
+    int rc = create_handle(&parent->params, parent->device, &lim, is_kid, in_lane, parent->buf.env, out);
     if (rc == ARUCOHIP_OK && (rc = inherit(parent, *out)) != ARUCOHIP_OK) {
         arucohip_destroy(*out);
         *out = nullptr;
@@ -213,7 +214,7 @@ static int create_child(arucohip_handle* parent, const arucohip_limits_t& lim, b
     return rc;
 }
 
-static int create_handle(const arucohip_params_t* params, int device, const arucohip_limits_t* lim, bool is_kid, const EnvSettings& env,
+static int create_handle(const arucohip_params_t* params, int device, const arucohip_limits_t* lim, bool is_kid, bool in_lane, const EnvSettings& env,
                          arucohip_handle** out) {
     if (!out || !lim) return ARUCOHIP_E_INVALID;
     *out = nullptr;
@@ -223,6 +224,7 @@ static int create_handle(const arucohip_params_t* params, int device, const aruc
         return ARUCOHIP_E_INVALID;
     arucohip_handle* h = new arucohip_handle();
     h->device = device;
+    h->in_lane = in_lane;
     h->lim = *lim;
     if (params)
         h->params = *params;
@@ -333,9 +335,11 @@ static int create_handle(const arucohip_params_t* params, int device, const aruc
     for (auto& set : h->ev)
         for (auto& ev : set)
             if ((e = hipEventCreate(&ev)) != hipSuccess) return bail(e);
-    if ((e = hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking)) != hipSuccess) return bail(e);
-    if ((e = hipEventCreateWithFlags(&h->ev_wfork, hipEventDisableTiming)) != hipSuccess) return bail(e);
-    if ((e = hipEventCreateWithFlags(&h->ev_wjoin, hipEventDisableTiming)) != hipSuccess) return bail(e);
+    if (!in_lane) {   // the one place that decides whether a handle's batches fork their late walker generations (run_rectangles, launch_walkers)
+        if ((e = hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking)) != hipSuccess) return bail(e);
+        if ((e = hipEventCreateWithFlags(&h->ev_wfork, hipEventDisableTiming)) != hipSuccess) return bail(e);
+        if ((e = hipEventCreateWithFlags(&h->ev_wjoin, hipEventDisableTiming)) != hipSuccess) return bail(e);
+    }
     if (h->nsub > 1) {
         if ((e = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming)) != hipSuccess) return bail(e);
         for (int i = 0; i < h->nsub - 1; i++) {
@@ -343,7 +347,7 @@ static int create_handle(const arucohip_params_t* params, int device, const aruc
             arucohip_limits_t kl = *lim;
             kl.max_batch = h->cap_frames;
             arucohip_handle* kid = nullptr;
-            const int krc = create_child(h, kl, true, &kid);
+            const int krc = create_child(h, kl, true, in_lane, &kid);
             if (krc != ARUCOHIP_OK) {
                 arucohip_destroy(h);
                 return krc;
@@ -356,7 +360,7 @@ static int create_handle(const arucohip_params_t* params, int device, const aruc
 }
 
 int arucohip_create_ex(const arucohip_params_t* params, int device, const arucohip_limits_t* lim, arucohip_handle** out) {
-    return create_handle(params, device, lim, false, read_env(), out);
+    return create_handle(params, device, lim, false, false, read_env(), out);
 }
 
 int arucohip_create(const arucohip_params_t* params, int device, int max_width, int max_height, int max_batch, arucohip_handle** out) {
@@ -642,7 +646,8 @@ static int run_rectangles(arucohip_handle* h, hipStream_t s, const FrameGeom& g,
     } else {
         if (RUN_STAGE(b.env, 1)) launch_start_candidates(s, g, nframes * dp.nthr, b, dp.min_contour);
         MARK(K_WALKERS);
-        // walkers; their late generations run on the side stream under the first quad pass (the contour_quad mark sits at the fork)
+        // walkers; where the handle has a side stream their late generations run there under the first quad pass (the contour_quad mark sits at
+        // the fork); a pipeline lane has none and runs every generation, then the one quad pass, on s
         WalkFork fk{h->side_stream, h->ev_wfork, h->ev_wjoin, ev ? ev[K_WALKERS_LONG] : nullptr};
         const bool forked = RUN_STAGE(b.env, 2) ? launch_walkers(s, fk, g, nframes * dp.nthr, dp, b) : false;
         MARK(K_CONTOUR_QUADS);
@@ -1293,7 +1298,7 @@ int arucohip_debug_counters(arucohip_handle* h, uint32_t* out8) {
     HIPCHK(h, hipSetDevice(h->device));
     const Batch& r = h->last;
     uint64_t acc[CNT_FIXED] = {};
-    uint64_t ntrig = 0, nraw = 0, nlong = 0;
+    uint64_t ntrig = 0, nraw = 0, nlong = 0, nlate = 0, nside = 0;
     for (const Span& s : r) {
         arucohip_handle* w = s.w;
         uint32_t cnt[CNT_FIXED];
@@ -1303,7 +1308,16 @@ int arucohip_debug_counters(arucohip_handle* h, uint32_t* out8) {
         HIPCHK(h, hipMemcpyAsync(tc.data(), w->buf.trig_cnt, tc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
         HIPCHK(h, hipMemcpyAsync(rc_.data(), w->buf.raw_cnt, rc_.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
         HIPCHK(h, hipMemcpyAsync(rg.data(), w->buf.ring_cnt, rg.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
+        // walks that entered the first generation behind the fork point (both kinds, every sublist), forked or not
+        uint32_t late[2][8] = {};
+        if (!w->buf.seg_mode)
+            for (int kind = 0; kind < 2; kind++)
+                HIPCHK(h, hipMemcpy2DAsync(late[kind], sizeof(uint32_t), w->buf.gen_cnt + gen_cnt_word(kind, GEN_FORK_AFTER + 1, 0),
+                                           (gen_cnt_word(kind, GEN_FORK_AFTER + 1, 1) - gen_cnt_word(kind, GEN_FORK_AFTER + 1, 0)) * sizeof(uint32_t),
+                                           sizeof(uint32_t), 8, hipMemcpyDeviceToHost, w->stream));
         HIPCHK(h, hipStreamSynchronize(w->stream));
+        for (int i = 0; i < 16; i++) nlate += late[i / 8][i % 8];
+        nside += w->side_stream ? 1 : 0;
         for (int i = 0; i < CNT_FIXED; i++)
             if (i != 1 && i != 2) acc[i] = (i == CNT_STATUS) ? (acc[i] | cnt[i]) : acc[i] + cnt[i];   // [1], [2] come from the planes' own counters below
         for (int p = 0; p < planes; p++) {
@@ -1317,6 +1331,8 @@ int arucohip_debug_counters(arucohip_handle* h, uint32_t* out8) {
     out8[0] = (uint32_t)std::min<uint64_t>(ntrig, 0xFFFFFFFFu);   // start candidates after the run rule (all planes)
     const bool seg = r.nspan > 0 && r.span[0].w->buf.seg_mode;
     out8[4] = (uint32_t)std::min<uint64_t>(seg ? nraw : nlong, 0xFFFFFFFFu);   // waypoint records (segment mode) / long walks = checkpoint rings handed out
+    out8[6] = (uint32_t)std::min<uint64_t>(nlate, 0xFFFFFFFFu);   // long walks that reached the late generations (the ones a side stream carries)
+    out8[7] = (uint32_t)nside;                                    // side streams among the workers that hold the batch (a pipeline lane: 0)
     return ARUCOHIP_OK;
 }
 
@@ -1641,7 +1657,7 @@ int arucohip_set_pipeline_depth(arucohip_handle* h, int depth) {
     if (!h->ev_submit) HIPCHK(h, hipEventCreateWithFlags(&h->ev_submit, hipEventDisableTiming));
     for (int i = 0; i < depth; i++) {
         arucohip_handle* l = nullptr;
-        const int rc = create_child(h, h->lim, false, &l);
+        const int rc = create_child(h, h->lim, false, true, &l);
         if (rc != ARUCOHIP_OK) {   // all or nothing: a later submit must not run at a smaller depth than the caller asked for
             for (auto* made : h->lanes) arucohip_destroy(made);
             h->lanes.clear();
@@ -1707,7 +1723,7 @@ int arucohip_detect_batch_retry_overflowed(arucohip_handle* h, const uint8_t* fr
                 l.triggers_per_frame = grow(l.triggers_per_frame, 1L << 22), l.contours_per_frame = grow(l.contours_per_frame, 1L << 18);
                 l.points_per_frame = grow(l.points_per_frame, 1L << 24), l.long_walks_per_plane = grow(l.long_walks_per_plane, 1L << 16);
                 l.candidates_per_frame = std::min(512, l.candidates_per_frame * 2);
-                const int crc = create_child(h, l, false, &h->retry);
+                const int crc = create_child(h, l, false, false, &h->retry);
                 if (crc != ARUCOHIP_OK) return fail(h, crc, "creating the retry handle failed");
                 h->retry_mult = want;
             }

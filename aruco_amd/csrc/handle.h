@@ -14,8 +14,9 @@
 using namespace ah;
 
 // one event after every kernel of a batch; a ring of TSETS batches so that asynchronous steps can be averaged
-// slot k = the interval between mark k and mark k + 1. walker_long = the generations of long walks up to the fork of the side
-// stream; contour_quad = both passes including the wait for the side stream's late generations.
+// slot k = the interval between mark k and mark k + 1. With a side stream: walker_long = the generations of long walks up to the fork,
+// contour_quad = both passes including the wait for the side stream's late generations. On a pipeline lane (no side stream):
+// walker_long = every generation, contour_quad = its one pass.
 enum { K_THRESHOLD = 0, K_FILTER, K_WALKERS, K_WALKERS_LONG, K_CONTOUR_QUADS, K_FRAME_CANDS, K_DECODE, K_REFINE_LINES, K_REFINE_PIXELS, K_FINALIZE, K_POSE, K_COUNT };
 constexpr int TSETS = 32;
 
@@ -144,7 +145,10 @@ struct arucohip_handle {
     int nsub = 1, cap_frames = 1;        // workers, frames each worker's buffers hold
     std::vector<arucohip_handle*> kids;
     hipEvent_t ev_fork = nullptr, ev_join[MAX_WORKERS] = {};
-    hipStream_t side_stream = nullptr;   // late walker generations (k_contours.hip)
+    // Late walker generations (k_contours.hip, WalkFork). A pipeline lane and its chunk workers (in_lane) have neither the stream nor
+    // the events: their batch runs on `stream` alone, so `depth` lanes are `depth` streams.
+    bool in_lane = false;
+    hipStream_t side_stream = nullptr;
     hipEvent_t ev_wfork = nullptr, ev_wjoin = nullptr;
     bool thres_bytes = true;             // buf.thres holds the last batch's byte image (else: tiles + buf.thres_edge, expanded on demand)
     Mem<uint8_t> d_em;                   // arucohip_em_fit scratch
@@ -172,7 +176,7 @@ struct arucohip_handle {
         int disabled = 0;          // ARUCOHIP_GRAPH=0, or a capture failed once
     } fgraph;
     // Batches in flight (arucohip_set_pipeline_depth / _submit / _wait): every pipeline lane is a complete worker (own
-    // buffers, own stream); ticket t runs on lane t mod depth, so the latency-bound tail of batch t (border following,
+    // buffers, ONE stream: no side stream); ticket t runs on lane t mod depth, so the latency-bound tail of batch t (border following,
     // decoding) overlaps the bandwidth-bound head of batch t+1.
     std::vector<arucohip_handle*> lanes;
     int next_ticket = 0;

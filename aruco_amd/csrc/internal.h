@@ -219,13 +219,18 @@ void launch_erode_tiles(hipStream_t s, const FrameGeom& g, int nplanes, const Bu
 void launch_tile_bitmap(hipStream_t s, const FrameGeom& g, int nplanes, const Buffers& b);
 void launch_binary_planes(hipStream_t s, const uint8_t* thres_in, const FrameGeom& g, int nframes, const Buffers& b);
 void launch_start_candidates(hipStream_t s, const FrameGeom& g, int nplanes, const Buffers& b, int min_contour = 0);
+// Where a batch's late walker generations run. A handle that has the GPU to itself while its batch runs (a synchronous call, one frame per call and
+// its graph, a chunk worker) owns a side stream and forks them onto it; a pipeline lane owns none (create_handle decides, once per handle): the
+// other lanes' batches fill the chip while its chain runs, and its whole batch stays on the lane's one stream.
 struct WalkFork {
-    hipStream_t side;            // stream of the late walker generations
-    hipEvent_t forked, joined;
+    hipStream_t side;            // stream of the late walker generations; null: no fork, every generation on the batch's stream
+    hipEvent_t forked, joined;   // used only with a side stream
     hipEvent_t after_first;      // recorded behind the first pass (per-kernel timing), may be null
 };
 bool launch_walkers(hipStream_t s, const WalkFork& fk, const FrameGeom& g, int nplanes, const DetectParams& p, const Buffers& b);
 size_t walk_scratch_words(int nplanes, const DetectParams& p, uint32_t long_cap);   // capacity launch_walkers needs in Buffers::walk_scratch
+constexpr int GEN_FORK_AFTER = 3;   // generations in front of the fork; a walk that enters generation GEN_FORK_AFTER + 1 is a "late" one
+size_t gen_cnt_word(int kind, int gen, int sublist);   // index into Buffers::gen_cnt of the entry count of a generation list (kind 0 outer, 1 hole; sublist 0..7)
 constexpr size_t GEN_CNT_WORDS = 2 * 32 * 32 * 8;                 // words of Buffers::gen_cnt: [2 kinds][GEN_MAX + 2 generations][8 sublists] lines of 32 words
 void launch_segments(hipStream_t s, const FrameGeom& g, int nplanes, const DetectParams& p, const Buffers& b);
 void launch_contour_quads(hipStream_t s, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b, int pass = 0);

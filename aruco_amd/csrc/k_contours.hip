@@ -774,6 +774,8 @@ __global__ __launch_bounds__(64) void walker_long_kernel(WalkArgs a) {
         walk_generation<true>(a, blockIdx.x - a.gen_blocks, rows);
 }
 
+size_t gen_cnt_word(int kind, int gen, int sublist) { return ((size_t)(kind * (GEN_MAX + 2) + gen) * GEN_NX_MAX + sublist) * GEN_CNT_STRIDE; }
+
 size_t walk_scratch_words(int nplanes, const DetectParams& p, uint32_t long_cap) {
     return (size_t)((nplanes + 7) / 8) * 8 * 2 * long_cap * ((p.max_contour + CK - 1) / CK);
 }
@@ -784,7 +786,8 @@ __global__ void snapshot_kernel(uint32_t* trig_cnt, int nplanes) {
 }
 
 // returns true if the late generations were forked to fk.side: the caller runs launch_contour_quads pass 1, waits for
-// fk.joined on its stream and runs pass 2
+// fk.joined on its stream and runs pass 2. Without a side stream (a pipeline lane) every generation runs on s, nothing is
+// snapshotted and the caller runs the one pass 0.
 bool launch_walkers(hipStream_t s, const WalkFork& fk, const FrameGeom& g, int nplanes, const DetectParams& p, const Buffers& b) {
     WalkArgs a;
     a.tiles = b.tiles, a.tnx = tiles_x(g.width), a.tny = tiles_y(g.height), a.nplanes = nplanes;
@@ -810,17 +813,19 @@ bool launch_walkers(hipStream_t s, const WalkFork& fk, const FrameGeom& g, int n
     // Generations: 64-step ones while many walks are alive, then doubling. The late generations hold a handful of very long
     // walks and are pure latency (a border of n pixels is a chain of n dependent steps), so they run on the side stream
     // while the main stream already turns the borders found so far into quads (launch_contour_quads pass 1); the per-plane
-    // descriptor counts at the fork are snapshotted for that.
+    // descriptor counts at the fork are snapshotted for that. A pipeline lane brings no side stream: with other batches in flight
+    // the chip is busy while the chain runs, and the fork's two event hops only tie a second stream into the shared hardware
+    // queues (profiles/lane_single_stream_ab.txt).
     // Round 2 (every lane re-centres its own block): few long generations beat many short ones; the side stream takes over
     // after 128 + 256 + 512 steps, borders of up to 960 points are in contour_quad's first pass (profiles/r02_kernel_experiments.txt).
     // After the listed generations the length stays 1024.
     static const int kSteps[] = {128, 256, 512, 1024};
-    constexpr int nsched = 4, kForkAfter = 3;   // kForkAfter: generations on the main stream
+    constexpr int nsched = 4, kForkAfter = GEN_FORK_AFTER;   // kForkAfter: generations on the main stream when there is a side stream
     int done = a.leash;
     bool forked = false;
     hipStream_t cur = s;
     for (int g = 1; g <= GEN_MAX && done < p.max_contour && RUN_STAGE(b.env, 3); g++) {
-        if (g == kForkAfter + 1) {
+        if (g == kForkAfter + 1 && fk.side) {
             hipLaunchKernelGGL(snapshot_kernel, dim3((nplanes + 255) / 256), dim3(256), 0, s, b.trig_cnt, nplanes);
             (void)hipEventRecord(fk.forked, s);
             (void)hipStreamWaitEvent(fk.side, fk.forked, 0);

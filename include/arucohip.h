@@ -296,7 +296,9 @@ int arucohip_debug_otsu(arucohip_handle* h, int frame, int32_t* thr, int cap, in
 int arucohip_debug_cells(arucohip_handle* h, int frame, uint8_t* cells49, int cap, int* n);
 
 /* Device list fill levels of the last batch: [0] border-start candidates, [1] borders kept, [2] contour points,
- * [3] overflow bits. For sizing arucohip_limits_t. */
+ * [3] overflow bits, [4] long walks (waypoint records in segment mode). For sizing arucohip_limits_t. For tests: [6] the long walks that
+ * reached the late generations (borders of more than 960 points), [7] how many of the workers that hold the batch own a side stream for
+ * those generations (a pipeline lane, arucohip_set_pipeline_depth, owns none: its batch runs on one stream). */
 int arucohip_debug_counters(arucohip_handle* h, uint32_t* out8);
 
 /* glibc's rand() outputs [offset, offset + count) after srand(seed), as the device makes them for arucohip_hrm_create_dictionary
