@@ -88,6 +88,9 @@ SYMBOLS = [
     "arucohip_chromatic_reset_mask",
     "arucohip_hrm_create_dictionary", "arucohip_hrm_board_size", "arucohip_hrm_board_image", "arucohip_debug_hrm_stream",
     "arucohip_debug_hrm_counters",
+    "arucohip_fiducial_marker_images", "arucohip_fiducial_marker_side", "arucohip_fiducial_marker_mat", "arucohip_fiducial_shuffle_ids",
+    "arucohip_fiducial_board_size", "arucohip_fiducial_board_image", "arucohip_board_pix_to_meters", "arucohip_fiducial_distances",
+    "arucohip_fiducial_select",
 ]
 
 _lib = None
@@ -170,6 +173,15 @@ def load():
     L.arucohip_hrm_board_image.argtypes = [vp, i, i, vp, i, i, i, vp, sz, i, vp, vp]
     L.arucohip_debug_hrm_stream.argtypes = [vp, C.c_uint32, C.c_uint64, i, vp]
     L.arucohip_debug_hrm_counters.argtypes = [vp, vp]
+    L.arucohip_fiducial_marker_images.argtypes = [vp, vp, i, i, i, vp, sz, sz, i]
+    L.arucohip_fiducial_marker_side.argtypes = [i, i]
+    L.arucohip_fiducial_marker_mat.argtypes = [i, vp]
+    L.arucohip_fiducial_shuffle_ids.argtypes = [vp, i, vp, i, vp]
+    L.arucohip_fiducial_board_size.argtypes = [i, i, i, i, i, vp, vp, vp, vp]
+    L.arucohip_fiducial_board_image.argtypes = [vp, i, i, i, i, i, i, vp, i, vp, sz, i, vp]
+    L.arucohip_board_pix_to_meters.argtypes = [vp, i, f, vp]
+    L.arucohip_fiducial_distances.argtypes = [vp, vp, i]
+    L.arucohip_fiducial_select.argtypes = [vp, i, i, vp, vp, vp]
     L.arucohip_chromatic_debug_geometry.argtypes = [vp, i, vp, vp, vp]
     L.arucohip_chromatic_debug_hist.argtypes = [vp, vp, vp, vp]
     L.arucohip_chromatic_classify_batch.argtypes = [vp, vp, vp, i, i, i, sz, sz, i, i, f, vp, i, vp]
@@ -242,6 +254,54 @@ def default_params():
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+FIDUCIAL_PANEL, FIDUCIAL_CHESSBOARD, FIDUCIAL_FRAME = 0, 1, 2
+
+
+def fiducial_marker_mat(marker_id):
+    """FiducidalMarkers::getMarkerMat: the 5 x 5 cells of a marker as uint8 0 / 1 (host arithmetic, no handle)."""
+    out = np.zeros((5, 5), np.uint8)
+    rc = load().arucohip_fiducial_marker_mat(int(marker_id), _ptr(out))
+    if rc != OK:
+        raise ArucoHipError(rc, "arucohip_fiducial_marker_mat")
+    return out
+
+
+def fiducial_marker_side(size, locked=False):
+    """Side of createMarkerImage(id, size, ., locked); 0 for a size the library refuses."""
+    return int(load().arucohip_fiducial_marker_side(int(size), int(bool(locked))))
+
+
+def fiducial_shuffle_ids(rng_state, n, excluded=()):
+    """getListOfValidMarkersIds_random on cv::theRNG() with state rng_state: (ids int32 [n], the state afterwards)."""
+    st = C.c_uint64(int(rng_state) & 0xFFFFFFFFFFFFFFFF)
+    ex = np.ascontiguousarray(excluded, dtype=np.int32).reshape(-1)
+    out = np.zeros(max(int(n), 1), np.int32)
+    rc = load().arucohip_fiducial_shuffle_ids(C.byref(st), int(n), _ptr(ex) if ex.size else None, ex.size, _ptr(out))
+    if rc != OK:
+        raise ArucoHipError(rc, "arucohip_fiducial_shuffle_ids")
+    return out[:max(int(n), 0)], int(st.value)
+
+
+def fiducial_board_size(board_type, grid, marker_size, marker_distance=0):
+    """(width, height, ids the reference draws from the shuffle, markers placed) of a board layout (FIDUCIAL_*)."""
+    w, hh, drawn, nm = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    rc = load().arucohip_fiducial_board_size(int(board_type), int(grid[0]), int(grid[1]), int(marker_size), int(marker_distance), C.byref(w),
+                                             C.byref(hh), C.byref(drawn), C.byref(nm))
+    if rc != OK:
+        raise ArucoHipError(rc, "arucohip_fiducial_board_size")
+    return w.value, hh.value, drawn.value, nm.value
+
+
+def board_pix_to_meters(obj, marker_size_m):
+    """aruco_board_pix2meters: objPoints in pixels [n][4][3] -> metres, float32 arithmetic (host, no handle)."""
+    o = np.ascontiguousarray(obj, dtype=np.float32).reshape(-1, 4, 3)
+    out = np.zeros_like(o)
+    rc = load().arucohip_board_pix_to_meters(_ptr(o), o.shape[0], float(marker_size_m), _ptr(out))
+    if rc != OK:
+        raise ArucoHipError(rc, "arucohip_board_pix_to_meters")
+    return out
 
 
 def _f32(a):
@@ -702,6 +762,46 @@ class Handle:
         self._chk(self.L.arucohip_hrm_board_image(self.h, int(n), c.size, _ptr(c), gw, gh, int(bool(chromatic)), _ptr(img), w.value * ch.value,
                                                   0, _ptr(ida), _ptr(obj)))
         return (img if chromatic else img[:, :, 0]), ida, obj
+
+    def fiducial_marker_images(self, ids, size, locked=False):
+        """FiducidalMarkers::createMarkerImage(id, size, false, locked) for every id, one launch: uint8 [len(ids)][side][side]."""
+        a = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        side = max(fiducial_marker_side(size, locked), 1)
+        out = np.zeros((max(a.size, 1), side, side), np.uint8)
+        self._chk(self.L.arucohip_fiducial_marker_images(self.h, _ptr(a), a.size, int(size), int(bool(locked)), _ptr(out), side, side * side, 0))
+        return out[:a.size]
+
+    def fiducial_board_image(self, board_type, grid, marker_size, marker_distance, ids, centered=True):
+        """createBoardImage / _ChessBoard / _Frame (board_type FIDUCIAL_*) with the caller's ids: (image uint8 [H][W], the ids the
+        layout used int32 [markers], objPoints float32 [markers][4][3] in pixels)."""
+        a = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        try:
+            w, hh, _, nm = fiducial_board_size(board_type, grid, marker_size, marker_distance)
+        except ArucoHipError:
+            w, hh, nm = 1, 1, 1   # the call below reports the error with its message
+        img = np.zeros((hh, w), np.uint8)
+        obj = np.zeros((nm, 4, 3), np.float32)
+        self._chk(self.L.arucohip_fiducial_board_image(self.h, int(board_type), int(grid[0]), int(grid[1]), int(marker_size), int(marker_distance),
+                                                       int(bool(centered)), _ptr(a), a.size, _ptr(img), w, 0, _ptr(obj)))
+        return img, a[:nm].copy(), obj
+
+    def fiducial_distances(self):
+        """the 1024 x 1024 int32 matrix of aruco_selectoptimalmarkers: rotation-minimal Hamming distance of every pair of markers"""
+        out = np.zeros((1024, 1024), np.int32)
+        self._chk(self.L.arucohip_fiducial_distances(self.h, _ptr(out), 0))
+        return out
+
+    def fiducial_select(self, n_markers, min_entropy=0):
+        """aruco_selectoptimalmarkers: (ids int32 ascending, smallest pairwise distance). Raises ArucoHipError (E_INVALID) where the
+        reference gives up; the exception's `partial` holds the ids found until then."""
+        out = np.zeros(max(int(n_markers), 1), np.int32)
+        n, md = C.c_int(), C.c_int()
+        rc = self.L.arucohip_fiducial_select(self.h, int(n_markers), int(min_entropy), _ptr(out), C.byref(n), C.byref(md))
+        if rc != OK:
+            e = ArucoHipError(rc, (self.L.arucohip_last_error_string(self.h) or b"").decode())
+            e.partial = out[:n.value].copy()
+            raise e
+        return out[:n.value].copy(), md.value
 
     def debug_hrm_stream(self, seed, offset, count):
         """glibc rand() outputs [offset, offset + count) after srand(seed), made on the device"""

@@ -154,6 +154,7 @@ struct arucohip_handle {
     Mem<uint8_t> d_em;                   // arucohip_em_fit scratch
     Mem<uint8_t> d_hrm_gen;              // HRM dictionary / board generation scratch (k_hrm.hip)
     int32_t hrm_stats[4] = {};           // the last arucohip_hrm_create_dictionary: windows, host synchronisations, acceptances, tau decrements
+    Mem<uint8_t> d_fiducial;             // 5x5 marker / board images, distance matrix and selection scratch (k_fiducial.hip)
     // One frame per call (the reference's call shape, arucohip_detect): the chain of ~20 dependent dispatches of a frame is captured once per
     // (geometry, parameters, camera) into a hipGraph and replayed with ONE launch per call; the frame's H2D copy stays outside (its source
     // pointer changes with every call), the results land in the handle's pinned staging inside the graph.
@@ -165,7 +166,7 @@ struct arucohip_handle {
     //   capture and replay; batches that decode from cell medians neither touch nor move buf.patches, and buf.cells is create-time memory;
     // - neither: the other Buffers arrays, zero_block and h_markers are create-time memory (`held`); d_erode, d_canny and the user decoder's
     //   staging belong to configurations that are not graphed; wt_out is set only inside chunk_enqueue, which does not run this path.
-    //   Memory no captured launch reads (d_bgr, undistortion, calibration, board and GL batches, EM, HRM and ChromaticMask scratch) may
+    //   Memory no captured launch reads (d_bgr, undistortion, calibration, board and GL batches, EM, HRM, fiducial generation and ChromaticMask scratch) may
     //   be replaced at any time.
     struct FrameGraph {
         hipGraphExec_t exec = nullptr;

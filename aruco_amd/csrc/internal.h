@@ -368,4 +368,19 @@ void launch_hrm_stream(hipStream_t s, const uint32_t* state0, const uint32_t* po
 void launch_hrm_board(hipStream_t s, const uint64_t* codes, int n, int gw, int gh, int chromatic, int W, int H, int channels, size_t stride,
                       uint8_t* out);
 
+// The default 5x5 markers, their boards and marker sets (k_fiducial.hip): src/arucofidmarkers.cpp:214-430, utils/aruco_selectoptimalmarkers.cpp.
+// One image of fid_paint_kernel: a gw x gh grid of markers of M pixels (cells of sw = M / 7) at `pitch` on white, GW x GH pixels large,
+// at (off, off) of a W x H image. off = 0: the grid is the image (boards, plain markers). off > 0: the "locked" marker, white around the
+// grid with a black off x off square in every corner.
+struct FidLayout {
+    int W, H, GW, GH, off;
+    int gw, gh, M, pitch, sw;
+};
+// n images of layout L; slots: [n][gh * gw] marker ids, -1 = the cell stays white. Any row_stride >= W, any alignment.
+void launch_fid_paint(hipStream_t s, const FidLayout& L, const int32_t* slots, int nimages, uint8_t* out, size_t row_stride, size_t image_stride);
+// dist[1024][1024]: the selection utility's distance of every pair of markers
+void launch_fid_distances(hipStream_t s, int32_t* dist);
+// the greedy selection of n_markers markers; sel [n_markers] ascending, res [4]: selected, complete, smallest pairwise distance, largest entropy
+void launch_fid_select(hipStream_t s, int n_markers, int min_entropy, int32_t* sel, int32_t* res);
+
 }  // namespace ah

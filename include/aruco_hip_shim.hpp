@@ -8,6 +8,8 @@
 //   aruco::Dictionary, aruco::MarkerCode, aruco::HighlyReliableMarkers  /root/reference/src/highlyreliablemarkers.h:50-260
 //                           (dictionary files, loadDictionary, the decoder token for setMakerDetectorFunction,
 //                           createDicitionary and createBoardImage on the device, MarkerCode's rotations and distances)
+//   aruco::FiducidalMarkers src/arucofidmarkers.h:82-130 (the decoder token; createMarkerImage, getMarkerMat and the three
+//                           createBoardImage* layouts on the device, their ids from cv::theRNG())
 //
 // Same member names, argument meaning and failure behaviour (CV_Assert -> cv::Exception) as the reference, so a caller
 // of the reference compiles against this header and links libarucohip.so instead of libaruco + OpenCV imgproc/calib3d.
@@ -120,6 +122,21 @@ public:
 };
 typedef const Mat& InputArray;
 typedef Mat& OutputArray;
+}  // namespace cv
+#endif
+#ifndef CV_VERSION
+// cv::theRNG(): the generator FiducidalMarkers::createBoardImage* shuffle the marker ids with. Every OpenCV has it (and CV_VERSION);
+// without OpenCV only its public state exists (callers assign it: cv::theRNG().state = 4711), and arucohip_fiducial_shuffle_ids
+// advances it as cv::RNG would.
+namespace cv {
+struct RNG {
+    unsigned long long state;
+    RNG(unsigned long long s = 0xffffffff) : state(s) {}
+};
+inline RNG& theRNG() {
+    static RNG r;
+    return r;
+}
 }  // namespace cv
 #endif
 
@@ -557,6 +574,72 @@ public:
     static int detect(const cv::Mat&, int&) {
         arucohip_throw_(ARUCOHIP_E_UNSUPPORTED, "FiducidalMarkers::detect runs on the device; pass it to setMakerDetectorFunction", nullptr);
         return -1;
+    }
+    // arucofidmarkers.h:82-130 / .cpp:214-430 on the device (arucohip_fiducial_*), through the process-wide handle.
+    // createMarkerImage: writeIdWaterMark is accepted and ignored, the "#id" text is not drawn.
+    static cv::Mat createMarkerImage(int id, int size, bool writeIdWaterMark = true, bool locked = false) {
+        (void)writeIdWaterMark;
+        const int side = arucohip_fiducial_marker_side(size, locked ? 1 : 0);
+        if (!side || id < 0 || id >= 1024) arucohip_throw_(ARUCOHIP_E_INVALID, "createMarkerImage: 0 <= id < 1024, 7 <= size, side <= 16383", nullptr);
+        cv::Mat img(side, side, CV_8UC1);
+        const int32_t id32 = id;
+        SharedHandle_& sh = SharedHandle_::get();
+        std::lock_guard<std::mutex> lock(sh.mu);
+        arucohip_handle* h = sh.ensure();
+        arucohip_throw_(arucohip_fiducial_marker_images(h, &id32, 1, size, locked ? 1 : 0, img.data, img.step, 0, 0), "createMarkerImage", h);
+        return img;
+    }
+    static cv::Mat getMarkerMat(int id) {   // 5 x 5 CV_8UC1 of 0 / 1
+        unsigned char cells[25];
+        arucohip_throw_(arucohip_fiducial_marker_mat(id, cells), "getMarkerMat: invalid marker id", nullptr);
+        cv::Mat m(5, 5, CV_8UC1);
+        for (int y = 0; y < 5; y++)
+            for (int x = 0; x < 5; x++) m.at<unsigned char>(y, x) = cells[5 * y + x];
+        return m;
+    }
+    // The ids come from cv::theRNG() as in the reference: consecutive calls continue one stream. The panel form resizes TInfo.objPoints
+    // and assigns TInfo.ids; the other two append to what TInfo held.
+    static cv::Mat createBoardImage(cv::Size gridSize, int MarkerSize, int MarkerDistance, BoardConfiguration& TInfo,
+                                    const std::vector<int>& excludedIds = std::vector<int>()) {
+        return board_(0, gridSize, MarkerSize, MarkerDistance, TInfo, true, excludedIds);
+    }
+    static cv::Mat createBoardImage_ChessBoard(cv::Size gridSize, int MarkerSize, BoardConfiguration& TInfo, bool setDataCentered = true,
+                                               const std::vector<int>& excludedIds = std::vector<int>()) {
+        return board_(1, gridSize, MarkerSize, 0, TInfo, setDataCentered, excludedIds);
+    }
+    static cv::Mat createBoardImage_Frame(cv::Size gridSize, int MarkerSize, int MarkerDistance, BoardConfiguration& TInfo, bool setDataCentered = true,
+                                          const std::vector<int>& excludedIds = std::vector<int>()) {
+        return board_(2, gridSize, MarkerSize, MarkerDistance, TInfo, setDataCentered, excludedIds);
+    }
+
+private:
+    static cv::Mat board_(int type, cv::Size grid, int size, int dist, BoardConfiguration& TInfo, bool centered, const std::vector<int>& excluded) {
+        int w = 0, hgt = 0, drawn = 0, nm = 0;
+        arucohip_throw_(arucohip_fiducial_board_size(type, grid.width, grid.height, size, dist, &w, &hgt, &drawn, &nm), "createBoardImage", nullptr);
+        std::vector<int32_t> ex(excluded.begin(), excluded.end()), ids((size_t)drawn);
+        uint64_t state = (uint64_t)cv::theRNG().state;
+        arucohip_throw_(arucohip_fiducial_shuffle_ids(&state, drawn, ex.data(), (int)ex.size(), ids.data()),
+                        "createBoardImage: number of possible markers is exceeded", nullptr);
+        cv::theRNG().state = state;
+        cv::Mat img(hgt, w, CV_8UC1);
+        std::vector<float> obj((size_t)nm * 12);
+        {
+            SharedHandle_& sh = SharedHandle_::get();
+            std::lock_guard<std::mutex> lock(sh.mu);
+            arucohip_handle* h = sh.ensure();
+            arucohip_throw_(arucohip_fiducial_board_image(h, type, grid.width, grid.height, size, dist, centered ? 1 : 0, ids.data(), drawn, img.data,
+                                                          img.step, 0, obj.data()),
+                            "createBoardImage", h);
+        }
+        TInfo.mInfoType = BoardConfiguration::PIX;
+        if (type == 0) TInfo.ids.clear(), TInfo.objPoints.clear();
+        for (int i = 0; i < nm; i++) {
+            TInfo.ids.push_back(ids[i]);
+            std::vector<cv::Point3f> c(4);
+            for (int k = 0; k < 4; k++) c[k] = cv::Point3f(obj[12 * i + 3 * k], obj[12 * i + 3 * k + 1], obj[12 * i + 3 * k + 2]);
+            TInfo.objPoints.push_back(c);
+        }
+        return img;
     }
 };
 

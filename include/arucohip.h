@@ -185,6 +185,56 @@ int arucohip_hrm_board_size(int n, int grid_w, int grid_h, int chromatic, int* w
 int arucohip_hrm_board_image(arucohip_handle* h, int n, int count, const uint64_t* codes, int grid_w, int grid_h, int chromatic, uint8_t* image,
                              size_t row_stride, int image_on_device, int32_t* ids, float* obj);
 
+/* ---- The default 5x5 Hamming markers: images, boards and marker sets (DESIGN.md "Fiducial marker, board and marker-set generation").
+ * The image calls paint on the device with scratch of their own: the handle's single-frame graph stays valid. Ids are 0..1023.
+ *
+ * FiducidalMarkers::createMarkerImage(id, size, false, locked) (src/arucofidmarkers.cpp:214-260) for n ids in one launch. An image is
+ * side x side bytes, side = arucohip_fiducial_marker_side(size, locked): `size`, or size + 2 * int(float(size) * 0.25f) for the locked
+ * form (white, a black square of that quarter in every corner, the marker in the middle). Cells are size / 7 wide (integer); the
+ * remainder at the right and the bottom stays black. Image i starts at images + i * image_stride, its rows are row_stride bytes apart
+ * (any value >= side, no alignment needed), in host memory or, with images_on_device, device memory. The "#id" watermark of
+ * addWaterMark is not drawn. 7 <= size, side <= 16383, 1 <= n <= 1024, and for a host destination at most 2^30 bytes
+ * of images (rows padded to 16) per call; else ARUCOHIP_E_INVALID, as for an id outside 0..1023 (CV_Assert in the reference). */
+int arucohip_fiducial_marker_images(arucohip_handle* h, const int32_t* ids, int n, int size, int locked, uint8_t* images, size_t row_stride,
+                                    size_t image_stride, int images_on_device);
+/* The side of such an image; 0 when size < 7 or the side would pass 16383. Host arithmetic. */
+int arucohip_fiducial_marker_side(int size, int locked);
+/* FiducidalMarkers::getMarkerMat (:264-282): out25[5 * y + x] = cell (y, x) as 0 / 1. Host arithmetic. */
+int arucohip_fiducial_marker_mat(int id, uint8_t* out25);
+/* getListOfValidMarkersIds_random (:40-61): the first n entries that are not excluded of the list 0..1023 after
+ * std::random_shuffle(list, list + 1024, cv::theRNG()) as libstdc++ runs it on cv::RNG (multiply with carry, 4164903690).
+ * *rng_state is cv::theRNG().state, read and written, so consecutive calls continue one stream as consecutive createBoardImage*
+ * calls do in the reference. n + nexcluded > 1024 or an excluded id outside 0..1023 is ARUCOHIP_E_INVALID. Host arithmetic. */
+int arucohip_fiducial_shuffle_ids(uint64_t* rng_state, int n, const int32_t* excluded, int nexcluded, int32_t* ids_out);
+/* The three board layouts (:290-430). type 0: createBoardImage (a panel of grid_w x grid_h markers, marker_distance apart);
+ * 1: createBoardImage_ChessBoard (markers on every other cell, no distance: marker_distance is ignored); 2: createBoardImage_Frame
+ * (the outermost ring of the panel's cells). *width / *height: the image; *ids_drawn: how many ids the reference takes from the
+ * shuffle for it (w h, 3 (w h) / 4, 2 h 2 w); *markers: how many it places - it uses the first *markers of the drawn ids, in
+ * row-major order of the cells. Any output may be NULL. grid 1..128 each, 7 <= marker_size, 0 <= marker_distance, image at most
+ * 16383 x 16383, at most 1024 markers; a chessboard that places more markers than it draws (1 x 1, for one) trips a CV_Assert in the
+ * reference (:362): all ARUCOHIP_E_INVALID. Host arithmetic. */
+int arucohip_fiducial_board_size(int type, int grid_w, int grid_h, int marker_size, int marker_distance, int* width, int* height, int* ids_drawn,
+                                 int* markers);
+/* The board image, painted by one launch: white, marker k of the layout = createMarkerImage(ids[k], marker_size). image: *height rows
+ * of row_stride bytes (>= *width, no alignment needed), host or device. obj (may be NULL): markers * 4 * 3 floats, TInfo.objPoints in
+ * pixels (mInfoType PIX), y down; the panel is always centred on (width / 2, height / 2) (integer halves), the other two when
+ * `centered`. nids below the layout's marker count is ARUCOHIP_E_INVALID. */
+int arucohip_fiducial_board_image(arucohip_handle* h, int type, int grid_w, int grid_h, int marker_size, int marker_distance, int centered,
+                                  const int32_t* ids, int nids, uint8_t* image, size_t row_stride, int image_on_device, float* obj);
+/* utils/aruco_board_pix2meters.cpp:54-63: obj_out = obj * (marker_size_m / float(int(norm of the first marker's first side))), float
+ * products. obj_out may be obj. A first side shorter than one pixel is ARUCOHIP_E_INVALID (the reference divides by zero). Host. */
+int arucohip_board_pix_to_meters(const float* obj, int nmarkers, float marker_size_m, float* obj_out);
+/* utils/aruco_selectoptimalmarkers.cpp:53-74, :128-131: dist[1024 * i + j] = the minimum over the four rotations of marker i of its
+ * 25-cell Hamming distance to marker j (symmetric, zero diagonal). dist: 1024 * 1024 int32, host or device. */
+int arucohip_fiducial_distances(arucohip_handle* h, int32_t* dist, int on_device);
+/* The selection of that utility (:76-205) without its files: the first marker of the largest entropy (:76-95), then n_markers - 1
+ * rounds that each take, among the markers of entropy >= min_entropy, the one whose smallest distance to the selected set is largest
+ * (the lowest id on ties). ids_out (n_markers entries): the selection in ascending order; *n_selected its size; *min_dist the smallest
+ * pairwise distance in it (INT_MAX for a single marker, as the reference prints). One launch, no host round trip per round. When a
+ * round finds no marker at a distance above 1 the reference prints "COUDL NOT ADD ANY MARKER" and exits: ARUCOHIP_E_INVALID here,
+ * with the markers found so far in ids_out / *n_selected. 1 <= n_markers <= 1024. */
+int arucohip_fiducial_select(arucohip_handle* h, int n_markers, int min_entropy, int32_t* ids_out, int* n_selected, int* min_dist);
+
 /* SURVEY §8b, plugin boundary — MarkerDetector::setMakerDetectorFunction (src/markerdetector.h:243-245) with a function of
  * the caller's own: typedef int (*MarkerdetectorFunc)(const cv::Mat& in, int& nRotations) (:78; contract :65-77: `in` is
  * the square canonical view of a candidate, the return value is the marker id or -1, nRotations the number of 90-degree
