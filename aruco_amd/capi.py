@@ -48,6 +48,12 @@ class BoardOut(C.Structure):
     _fields_ = [("n_markers", C.c_int32), ("has_pose", C.c_int32), ("rvec", C.c_double * 3), ("tvec", C.c_double * 3)]
 
 
+class PlanarPoses(C.Structure):
+    """arucohip_planar_poses_t: both pose solutions of one marker, rms[0] <= rms[1]; n_solutions is 0 or 2."""
+    _fields_ = [("rvec", (C.c_double * 3) * 2), ("tvec", (C.c_double * 3) * 2), ("rms", C.c_double * 2), ("n_solutions", C.c_int32),
+                ("pad_", C.c_int32)]
+
+
 class Limits(C.Structure):
     _fields_ = [("max_width", C.c_int32), ("max_height", C.c_int32), ("max_batch", C.c_int32),
                 ("max_thres_planes", C.c_int32), ("triggers_per_frame", C.c_int32), ("contours_per_frame", C.c_int32),
@@ -58,6 +64,9 @@ class Limits(C.Structure):
 MARKER_DTYPE = np.dtype([("id", "<i4"), ("corners", "<f4", (8,)), ("ssize", "<f4"), ("has_pose", "<i4"),
                          ("pad_", "<i4"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,))])
 assert MARKER_DTYPE.itemsize == 96 and C.sizeof(Marker) == 96
+# numpy view of a PlanarPoses array: np.frombuffer(array, PLANAR_DTYPE)
+PLANAR_DTYPE = np.dtype([("rvec", "<f8", (2, 3)), ("tvec", "<f8", (2, 3)), ("rms", "<f8", (2,)), ("n_solutions", "<i4"), ("pad_", "<i4")])
+assert PLANAR_DTYPE.itemsize == 120 and C.sizeof(PlanarPoses) == 120
 
 # every symbol include/arucohip.h declares
 SYMBOLS = [
@@ -81,6 +90,7 @@ SYMBOLS = [
     "arucohip_compact_bytes", "arucohip_compact_markers", "arucohip_wait_event", "arucohip_detect_batch_retry_overflowed",
     "arucohip_refine_candidate_lines", "arucohip_mgpu_gather_mode", "arucohip_build_info",
     "arucohip_calibrate_camera", "arucohip_calibrate_board_batch",
+    "arucohip_planar_poses", "arucohip_planar_poses_batch",
     "arucohip_chromatic_board_corners", "arucohip_chromatic_create", "arucohip_chromatic_destroy", "arucohip_chromatic_train",
     "arucohip_chromatic_classify", "arucohip_chromatic_update", "arucohip_chromatic_get_mask", "arucohip_chromatic_get_cell_map",
     "arucohip_chromatic_is_valid", "arucohip_chromatic_get_model", "arucohip_chromatic_set_model", "arucohip_em_fit",
@@ -153,6 +163,8 @@ def load():
     L.arucohip_board_detect_batch.argtypes = [vp, i, vp, vp, i, i, vp, vp, i, f, f, i, vp, vp]
     L.arucohip_calibrate_camera.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp]
     L.arucohip_calibrate_board_batch.argtypes = [vp, i, vp, vp, i, i, f, i, i, i, i, vp, vp, vp, vp, vp, vp]
+    L.arucohip_planar_poses.argtypes = [vp, vp, i, i, vp, vp, i, f, i, i, vp]
+    L.arucohip_planar_poses_batch.argtypes = [vp, i, vp, vp, i, f, i, i, vp, i, i]
     d = C.c_double
     L.arucohip_chromatic_board_corners.argtypes = [vp, i, i, f, vp]
     L.arucohip_chromatic_create.argtypes = [vp, i, i, d, vp, vp, i, i, i, vp, vp]
@@ -612,6 +624,38 @@ class Handle:
         self._chk(self.L.arucohip_calculate_extrinsics(self.h, _ptr(m), len(m), _ptr(Ka), _ptr(da), 0 if da is None else da.size,
                                                        float(marker_size), int(bool(y_perp))))
         return m
+
+    def planar_poses(self, markers, K, dist, marker_size, refine=True, y_perp=False):
+        """Both planar pose solutions of every marker (only the corners are read), each refined by the library's Levenberg-Marquardt
+        unless refine is False: a PlanarPoses array, one entry per marker, the solution with the smaller reprojection error first."""
+        m = np.ascontiguousarray(markers, dtype=MARKER_DTYPE)
+        Ka, da = _f32(K), _f32(dist)
+        out = (PlanarPoses * len(m))()
+        self._chk(self.L.arucohip_planar_poses(self.h, _ptr(m) if len(m) else None, len(m), 0, _ptr(Ka), _ptr(da), 0 if da is None else da.size,
+                                               float(marker_size), int(bool(refine)), int(bool(y_perp)), out))
+        return out
+
+    def planar_poses_device(self, markers_ptr, n, out_ptr, K, dist, marker_size, refine=True, y_perp=False):
+        """planar_poses on device arrays (arucohip_marker_t [n] in, arucohip_planar_poses_t [n] out, given as pointers)."""
+        Ka, da = _f32(K), _f32(dist)
+        self._chk(self.L.arucohip_planar_poses(self.h, markers_ptr, int(n), 1, _ptr(Ka), _ptr(da), 0 if da is None else da.size,
+                                               float(marker_size), int(bool(refine)), int(bool(y_perp)), out_ptr))
+
+    def planar_poses_batch(self, nframes, K, dist, marker_size, refine=True, y_perp=False, cap=64, fill=0):
+        """planar_poses on the device-resident markers of the last detect_batch call: a PlanarPoses array of nframes * cap entries,
+        entry f * cap + i for marker i of frame f; the entries beyond a frame's markers keep the byte `fill`."""
+        Ka, da = _f32(K), _f32(dist)
+        out = (PlanarPoses * (nframes * cap))()
+        C.memset(out, int(fill), C.sizeof(out))
+        self._chk(self.L.arucohip_planar_poses_batch(self.h, int(nframes), _ptr(Ka), _ptr(da), 0 if da is None else da.size, float(marker_size),
+                                                     int(bool(refine)), int(bool(y_perp)), out, int(cap), 0))
+        return out
+
+    def planar_poses_batch_device(self, nframes, out_ptr, cap, K, dist, marker_size, refine=True, y_perp=False):
+        """planar_poses_batch into a device array of nframes * cap arucohip_planar_poses_t, given as a pointer."""
+        Ka, da = _f32(K), _f32(dist)
+        self._chk(self.L.arucohip_planar_poses_batch(self.h, int(nframes), _ptr(Ka), _ptr(da), 0 if da is None else da.size, float(marker_size),
+                                                     int(bool(refine)), int(bool(y_perp)), out_ptr, int(cap), 1))
 
     def board_detect(self, markers, ids, obj, info_type, K=None, dist=None, marker_size=-1.0, repj_err_thres=-1.0, y_perp=False):
         m = np.ascontiguousarray(markers, dtype=MARKER_DTYPE)

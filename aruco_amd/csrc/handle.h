@@ -54,7 +54,7 @@ constexpr int MAX_WORKERS = 8;   // chunk workers of a handle, itself included (
 
 // A batch as the workers hold it: chunk c of its frames ran on worker c (chunk_worker). The handle the caller holds keeps the last one
 // (arucohip_handle::last): every call that replaces the device lists sets it whole, from plan_batch, or clears it when they no longer
-// hold a batch; a waited ticket adopts its lane's. The getters, board poses, calibration and ChromaticMask read it and nothing else.
+// hold a batch; a waited ticket adopts its lane's. The getters, board poses, planar poses, calibration and ChromaticMask read it and nothing else.
 struct Span { arucohip_handle* w; int first, count; };   // worker w holds frames [first, first + count)
 struct Batch {
     int nspan = 0, frames = 0;
@@ -134,6 +134,7 @@ struct arucohip_handle {
     Mem<double> d_gl;                 // batched GL modelview matrices
     Mem<uint8_t> d_calib;             // camera calibration: solver state, per-view systems and poses, correspondences (calib_carve)
     Mem<CalibState> hc_calib{true};   // pinned copy of the solver state, read once per iteration
+    Mem<uint8_t> d_planar;            // arucohip_planar_poses: results and staged markers of one call
     Batch last;                       // the last batch (kept on the handle the caller holds)
     bool timing = false;
     hipEvent_t ev[TSETS][K_COUNT + 1] = {};
@@ -166,7 +167,7 @@ struct arucohip_handle {
     //   capture and replay; batches that decode from cell medians neither touch nor move buf.patches, and buf.cells is create-time memory;
     // - neither: the other Buffers arrays, zero_block and h_markers are create-time memory (`held`); d_erode, d_canny and the user decoder's
     //   staging belong to configurations that are not graphed; wt_out is set only inside chunk_enqueue, which does not run this path.
-    //   Memory no captured launch reads (d_bgr, undistortion, calibration, board and GL batches, EM, HRM, fiducial generation and ChromaticMask scratch) may
+    //   Memory no captured launch reads (d_bgr, undistortion, calibration, board and GL batches, planar poses, EM, HRM, fiducial generation and ChromaticMask scratch) may
     //   be replaced at any time.
     struct FrameGraph {
         hipGraphExec_t exec = nullptr;

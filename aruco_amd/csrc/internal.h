@@ -256,6 +256,12 @@ void launch_marker_pose(hipStream_t s, arucohip_marker_t* markers, int n, const 
 void launch_board_pose(hipStream_t s, int nframes, const Buffers& b, const int32_t* ids, const float* obj, int nboard, int info_type,
                        float marker_size, float repj_thres, const CamModel& cam, arucohip_board_t* out, float* prob);
 
+// Both planar pose solutions per marker (k_planar.hip): markers[0 .. n) -> out[0 .. n), or the markers of the first nframes of the list_frames
+// frames a worker's lists hold -> out[(first + f) * cap_out + i]
+void launch_planar_poses(hipStream_t s, const arucohip_marker_t* markers, int n, const CamModel& cam, int refine, arucohip_planar_poses_t* out);
+void launch_planar_poses_list(hipStream_t s, int list_frames, int nframes, int first, const Buffers& b, const CamModel& cam, int refine,
+                              arucohip_planar_poses_t* out, int cap_out);
+
 // Camera calibration (k_calib.hip). Views: points obj (xyz) / img (xy) at off[v], npt[v] points each.
 constexpr int CALIB_MAX_POINTS = 512;   // points of one view (= the board kernels' MAX_BOARD_POINTS)
 constexpr int CALIB_RED = 100;          // doubles per view of the reduced system: S_i (81), diag A_i (9), rhs_i (9), pad

@@ -140,7 +140,9 @@ __device__ inline void orthonormalise(double* R) {
     }
 }
 
-// Rodrigues vector -> matrix, optional dR/dr (J[j*9+k] = dR[k]/dr[j])
+// Rodrigues vector -> matrix, optional dR/dr (J[j*9+k] = dR[k]/dr[j]). WITH_J: the caller states that J is there, so that no test of
+// the pointer is left in the code (a private array whose address is compared cannot be kept in registers)
+template <bool WITH_J = false>
 __device__ inline void rodrigues_vec2mat(const double* r, double* R, double* J) {
     double rx = r[0], ry = r[1], rz = r[2];
     double theta = sqrt(rx * rx + ry * ry + rz * rz);
@@ -148,7 +150,7 @@ __device__ inline void rodrigues_vec2mat(const double* r, double* R, double* J) 
     const double dRX[27] = {0, 0, 0, 0, 0, -1, 0, 1, 0, 0, 0, 1, 0, 0, 0, -1, 0, 0, 0, -1, 0, 1, 0, 0, 0, 0, 0};
     if (theta < DBL_EPSILON) {
         for (int k = 0; k < 9; k++) R[k] = I[k];
-        if (J)
+        if (WITH_J || J)
             for (int k = 0; k < 27; k++) J[k] = dRX[k];
         return;
     }
@@ -157,7 +159,7 @@ __device__ inline void rodrigues_vec2mat(const double* r, double* R, double* J) 
     double rrt[9] = {rx * rx, rx * ry, rx * rz, rx * ry, ry * ry, ry * rz, rx * rz, ry * rz, rz * rz};
     double rx_[9] = {0, -rz, ry, rz, 0, -rx, -ry, rx, 0};
     for (int k = 0; k < 9; k++) R[k] = c * I[k] + c1 * rrt[k] + s * rx_[k];
-    if (J) {
+    if (WITH_J || J) {
         double drrt[27] = {rx + rx, ry, rz, ry, 0, 0, rz, 0, 0, 0, rx, 0, rx, ry + ry, rz, 0, rz, 0,
                            0, 0, rx, 0, 0, ry, rx, ry, rz + rz};
         for (int i = 0; i < 3; i++) {
@@ -438,41 +440,36 @@ __device__ inline void wave_sum_arr(double* a, int n) {
     for (int i = 0; i < n; i++) a[i] = wave_sum_d<G>(a[i]);
 }
 
-template <int G>
-__device__ inline bool solve_pnp_planar_wave(const float* obj, const float* img, int n, const CamModel& cam, double* rvec, double* tvec, int lane) {
-    if (n < 4) return false;
+// Least-squares homography (8 unknowns, H22 = 1) from the plane of the object points, shifted by -Mc, to the normalised image:
+// the normalised DLT of cv::findHomography. RF: the inputs are rounded to float first, as cv::findHomography takes them from
+// solvePnP; the planar two-solution code (planar_device.h) keeps them in double. False: degenerate points (a spread below DBL_EPSILON,
+// a singular system or a homography that is not finite).
+template <bool RF>
+__device__ inline double homography_input(double v) {
+    return RF ? (double)(float)v : v;
+}
+template <int G, bool RF>
+__device__ inline bool planar_homography_wave(const float* obj, const float* img, int n, const CamModel& cam, int lane, const double* Mc, double* H) {
     const float* K = cam.K;
     const double* k = cam.k;
-    double Mc[2] = {0, 0};
-    bool nonplanar = false;
-    for (int i = lane; i < n; i += G) {
-        if (obj[3 * i + 2] != 0.f) nonplanar = true;
-        Mc[0] += (double)obj[3 * i], Mc[1] += (double)obj[3 * i + 1];
-    }
-    if (wave_sum_d<G>(nonplanar ? 1.0 : 0.0) > 0) return false;
-    wave_sum_arr<G>(Mc, 2);
-    Mc[0] /= n, Mc[1] /= n;
-    // ---- homography plane -> normalised image (inputs rounded to float as cv::findHomography does)
     double cM[2] = {0, 0}, cm[2] = {0, 0}, sM[2] = {0, 0}, sm[2] = {0, 0};
     for (int i = lane; i < n; i += G) {
         double ux, uy;
         undistort_point(img[2 * i], img[2 * i + 1], K, k, &ux, &uy);
-        cM[0] += (double)(float)((double)obj[3 * i] - Mc[0]), cM[1] += (double)(float)((double)obj[3 * i + 1] - Mc[1]);
-        cm[0] += (double)(float)ux, cm[1] += (double)(float)uy;
+        cM[0] += homography_input<RF>((double)obj[3 * i] - Mc[0]), cM[1] += homography_input<RF>((double)obj[3 * i + 1] - Mc[1]);
+        cm[0] += homography_input<RF>(ux), cm[1] += homography_input<RF>(uy);
     }
     wave_sum_arr<G>(cM, 2), wave_sum_arr<G>(cm, 2);
     cM[0] /= n, cM[1] /= n, cm[0] /= n, cm[1] /= n;
     for (int i = lane; i < n; i += G) {
         double ux, uy;
         undistort_point(img[2 * i], img[2 * i + 1], K, k, &ux, &uy);
-        sM[0] += fabs((double)(float)((double)obj[3 * i] - Mc[0]) - cM[0]);
-        sM[1] += fabs((double)(float)((double)obj[3 * i + 1] - Mc[1]) - cM[1]);
-        sm[0] += fabs((double)(float)ux - cm[0]), sm[1] += fabs((double)(float)uy - cm[1]);
+        sM[0] += fabs(homography_input<RF>((double)obj[3 * i] - Mc[0]) - cM[0]);
+        sM[1] += fabs(homography_input<RF>((double)obj[3 * i + 1] - Mc[1]) - cM[1]);
+        sm[0] += fabs(homography_input<RF>(ux) - cm[0]), sm[1] += fabs(homography_input<RF>(uy) - cm[1]);
     }
     wave_sum_arr<G>(sM, 2), wave_sum_arr<G>(sm, 2);
-    double r[3] = {0, 0, 0}, t[3] = {0, 0, 0};
     bool hok = !(fabs(sM[0]) < DBL_EPSILON || fabs(sM[1]) < DBL_EPSILON || fabs(sm[0]) < DBL_EPSILON || fabs(sm[1]) < DBL_EPSILON);
-    double H[9];
     if (hok) {
         sM[0] = n / sM[0], sM[1] = n / sM[1], sm[0] = n / sm[0], sm[1] = n / sm[1];
         double A[64], b[8];
@@ -481,9 +478,9 @@ __device__ inline bool solve_pnp_planar_wave(const float* obj, const float* img,
         for (int i = lane; i < n; i += G) {
             double ux, uy;
             undistort_point(img[2 * i], img[2 * i + 1], K, k, &ux, &uy);
-            double x = ((double)(float)ux - cm[0]) * sm[0], y = ((double)(float)uy - cm[1]) * sm[1];
-            double X = ((double)(float)((double)obj[3 * i] - Mc[0]) - cM[0]) * sM[0];
-            double Y = ((double)(float)((double)obj[3 * i + 1] - Mc[1]) - cM[1]) * sM[1];
+            double x = (homography_input<RF>(ux) - cm[0]) * sm[0], y = (homography_input<RF>(uy) - cm[1]) * sm[1];
+            double X = (homography_input<RF>((double)obj[3 * i] - Mc[0]) - cM[0]) * sM[0];
+            double Y = (homography_input<RF>((double)obj[3 * i + 1] - Mc[1]) - cM[1]) * sM[1];
             double Lx[8] = {X, Y, 1, 0, 0, 0, -x * X, -x * Y};
             double Ly[8] = {0, 0, 0, X, Y, 1, -y * X, -y * Y};
             for (int j = 0; j < 8; j++) {
@@ -507,18 +504,49 @@ __device__ inline bool solve_pnp_planar_wave(const float* obj, const float* img,
             }
         }
     }
-    if (hok) {
-        double h1n = sqrt(H[0] * H[0] + H[3] * H[3] + H[6] * H[6]);
-        double h2n = sqrt(H[1] * H[1] + H[4] * H[4] + H[7] * H[7]);
-        double s1 = 1. / fmax(h1n, DBL_EPSILON), s2 = 1. / fmax(h2n, DBL_EPSILON), st = 2. / fmax(h1n + h2n, DBL_EPSILON);
-        double h1[3] = {H[0] * s1, H[3] * s1, H[6] * s1}, h2[3] = {H[1] * s2, H[4] * s2, H[7] * s2};
-        t[0] = H[2] * st, t[1] = H[5] * st, t[2] = H[8] * st;
-        double h3[3] = {h1[1] * h2[2] - h1[2] * h2[1], h1[2] * h2[0] - h1[0] * h2[2], h1[0] * h2[1] - h1[1] * h2[0]};
-        double R[9] = {h1[0], h2[0], h3[0], h1[1], h2[1], h3[1], h1[2], h2[2], h3[2]};
-        rodrigues_mat2vec(R, r);
-        rodrigues_vec2mat(r, R, nullptr);
-        for (int i = 0; i < 3; i++) t[i] += R[i * 3] * (-Mc[0]) + R[i * 3 + 1] * (-Mc[1]);
-        rodrigues_mat2vec(R, r);
+    return hok;
+}
+
+// START: the homography start is left out and the Levenberg-Marquardt loop begins at the pose the caller put into rvec / tvec (the
+// planar two-solution code refines each of its analytic solutions this way). The loop stays in this function, not in one of its own:
+// with the loop as a separate inline function the compiler optimises it before it inlines it here, and the register allocation of the
+// pose kernels, which sit at the 256-register limit, came out differently.
+template <int G, bool START = false>
+__device__ inline bool solve_pnp_planar_wave(const float* obj, const float* img, int n, const CamModel& cam, double* rvec, double* tvec, int lane) {
+    if (n < 4) return false;
+    const float* K = cam.K;
+    const double* k = cam.k;
+    double Mc[2] = {0, 0};
+    if constexpr (!START) {
+        bool nonplanar = false;
+        for (int i = lane; i < n; i += G) {
+            if (obj[3 * i + 2] != 0.f) nonplanar = true;
+            Mc[0] += (double)obj[3 * i], Mc[1] += (double)obj[3 * i + 1];
+        }
+        if (wave_sum_d<G>(nonplanar ? 1.0 : 0.0) > 0) return false;
+        wave_sum_arr<G>(Mc, 2);
+        Mc[0] /= n, Mc[1] /= n;
+    }
+    // ---- homography plane -> normalised image (inputs rounded to float as cv::findHomography does)
+    double r[3] = {0, 0, 0}, t[3] = {0, 0, 0};
+    if constexpr (START) {
+        for (int i = 0; i < 3; i++) r[i] = rvec[i], t[i] = tvec[i];
+    } else {
+        double H[9];
+        const bool hok = planar_homography_wave<G, true>(obj, img, n, cam, lane, Mc, H);
+        if (hok) {
+            double h1n = sqrt(H[0] * H[0] + H[3] * H[3] + H[6] * H[6]);
+            double h2n = sqrt(H[1] * H[1] + H[4] * H[4] + H[7] * H[7]);
+            double s1 = 1. / fmax(h1n, DBL_EPSILON), s2 = 1. / fmax(h2n, DBL_EPSILON), st = 2. / fmax(h1n + h2n, DBL_EPSILON);
+            double h1[3] = {H[0] * s1, H[3] * s1, H[6] * s1}, h2[3] = {H[1] * s2, H[4] * s2, H[7] * s2};
+            t[0] = H[2] * st, t[1] = H[5] * st, t[2] = H[8] * st;
+            double h3[3] = {h1[1] * h2[2] - h1[2] * h2[1], h1[2] * h2[0] - h1[0] * h2[2], h1[0] * h2[1] - h1[1] * h2[0]};
+            double R[9] = {h1[0], h2[0], h3[0], h1[1], h2[1], h3[1], h1[2], h2[2], h3[2]};
+            rodrigues_mat2vec(R, r);
+            rodrigues_vec2mat(r, R, nullptr);
+            for (int i = 0; i < 3; i++) t[i] += R[i * 3] * (-Mc[0]) + R[i * 3 + 1] * (-Mc[1]);
+            rodrigues_mat2vec(R, r);
+        }
     }
     // ---- CvLevMarq
     double param[6] = {r[0], r[1], r[2], t[0], t[1], t[2]}, prev[6];
@@ -527,7 +555,7 @@ __device__ inline bool solve_pnp_planar_wave(const float* obj, const float* img,
     double prevErrNorm = DBL_MAX;
     for (;;) {
         double R[9], dRdr[27];
-        rodrigues_vec2mat(param, R, dRdr);
+        rodrigues_vec2mat<START>(param, R, dRdr);
         for (int i = 0; i < 36; i++) JtJ[i] = 0;
         for (int i = 0; i < 6; i++) JtErr[i] = 0;
         double e2 = 0;

@@ -403,6 +403,14 @@ inline double calibrateCamera(const std::vector<std::vector<cv::Point3f> >& objP
     return rms;
 }
 
+// Both pose solutions of a planar marker (Marker::calculateExtrinsicsBoth): solution j is Rvec[j] / Tvec[j] (3x1 double like
+// Marker::Rvec) with reprojection error rms[j] in pixels, rms[0] <= rms[1]; nSolutions is 2, or 0 for degenerate corners (empty Mats).
+struct PlanarPoses {
+    cv::Mat Rvec[2], Tvec[2];
+    double rms[2];
+    int nSolutions;
+};
+
 class Marker : public std::vector<cv::Point2f> {
 public:
     int id;
@@ -455,6 +463,40 @@ public:
         Rvec = cv::Mat_<double>(3, 1), Tvec = cv::Mat_<double>(3, 1);
         for (int k = 0; k < 3; k++) Rvec(k) = m.rvec[k], Tvec(k) = m.tvec[k];
         ssize = markerSize;
+    }
+    // No reference counterpart: the two poses a square has under weak perspective (arucohip_planar_poses on the process-wide handle), each
+    // refined by the library's Levenberg-Marquardt when refine is set. The marker itself is not changed: its Rvec / Tvec stay the pose
+    // calculateExtrinsics gave it. Throws where calculateExtrinsics throws.
+    PlanarPoses calculateExtrinsicsBoth(float markerSize, cv::Mat CameraMatrix, cv::Mat Distorsion = cv::Mat(), bool refine = true,
+                                        bool setYPerpendicular = false) const {
+        if (!(markerSize > 0 && isValid())) arucohip_throw_(ARUCOHIP_E_INVALID, "invalid marker. It is not possible to calculate extrinsics", nullptr);
+        float K[9], d[8];
+        if (!mat_to_K_(CameraMatrix, K)) arucohip_throw_(ARUCOHIP_E_INVALID, "CameraMatrix is empty", nullptr);
+        const int nd = mat_to_dist_(Distorsion, d);
+        arucohip_marker_t m;
+        to_abi(&m);
+        arucohip_planar_poses_t pp;
+        {
+            SharedHandle_& sh = SharedHandle_::get();
+            std::lock_guard<std::mutex> lock(sh.mu);
+            arucohip_handle* h = sh.ensure();
+            arucohip_throw_(arucohip_planar_poses(h, &m, 1, 0, K, nd ? d : nullptr, nd, markerSize, refine ? 1 : 0, setYPerpendicular ? 1 : 0, &pp),
+                            "Marker::calculateExtrinsicsBoth", h);
+        }
+        PlanarPoses out;
+        out.nSolutions = pp.n_solutions;
+        for (int j = 0; j < 2; j++) {
+            out.rms[j] = pp.rms[j];
+            if (!pp.n_solutions) continue;
+            cv::Mat_<double> r(3, 1), t(3, 1);
+            for (int k = 0; k < 3; k++) r(k) = pp.rvec[j][k], t(k) = pp.tvec[j][k];
+            out.Rvec[j] = r, out.Tvec[j] = t;
+        }
+        return out;
+    }
+    PlanarPoses calculateExtrinsicsBoth(float markerSize, const CameraParameters& CP, bool refine = true, bool setYPerpendicular = false) const {
+        if (!CP.isValid()) arucohip_throw_(ARUCOHIP_E_INVALID, "!CP.isValid(): invalid camera parameters. It is not possible to calculate extrinsics", nullptr);
+        return calculateExtrinsicsBoth(markerSize, CP.CameraMatrix, CP.Distorsion, refine, setYPerpendicular);
     }
     void glGetModelViewMatrix(double modelview_matrix[16]) const { arucohip_gl_modelview_(Rvec, Tvec, modelview_matrix); }              // marker.h:90
     void OgreGetPoseParameters(double position[3], double orientation[4]) const { arucohip_ogre_pose_(Rvec, Tvec, position, orientation); }  // marker.h:104

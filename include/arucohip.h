@@ -84,6 +84,14 @@ typedef struct arucohip_board {
     double tvec[3];
 } arucohip_board_t;
 
+/* Both pose solutions of one marker (arucohip_planar_poses): solution j is rvec[j] / tvec[j] with reprojection error rms[j]. 120 bytes. */
+typedef struct arucohip_planar_poses {
+    double rvec[2][3], tvec[2][3];
+    double rms[2];                        /* pixels, rms[0] <= rms[1] */
+    int32_t n_solutions;                  /* 0 or 2 */
+    int32_t pad_;
+} arucohip_planar_poses_t;
+
 /* device-side limits of one handle */
 typedef struct arucohip_limits {
     int32_t max_width, max_height;
@@ -457,6 +465,25 @@ int arucohip_chromatic_classify_batch(arucohip_chromatic* m, arucohip_handle* h,
 /* Marker::calculateExtrinsics (marker.h:98-104 / marker.cpp:112-124) for n markers at once (batched solvePnP). */
 int arucohip_calculate_extrinsics(arucohip_handle* h, arucohip_marker_t* markers, int n, const float* K, const float* dist,
                                   int ndist, float marker_size, int y_perpendicular);
+
+/* Both pose solutions of a planar marker. A square seen under weak perspective has two poses that explain its four corners almost
+ * equally well; arucohip_calculate_extrinsics and the detect calls report the one solvePnP(ITERATIVE) converges to and are unchanged.
+ * Here both come out of the homography in closed form (infinitesimal plane-based pose estimation, Collins and Bartoli 2014), in double
+ * precision on the device; with refine != 0 each is then refined by the library's Levenberg-Marquardt (<= 20 iterations, eps
+ * FLT_EPSILON) started from it. rms[j] is the root-mean-square distance in pixels between the four given corners and the projection
+ * of solution j through K and dist; the solutions are ordered by it. Degenerate corners (coincident, on one line, a homography that
+ * cannot be fitted, a solution behind the camera) give n_solutions = 0 and all doubles 0.
+ * Only `corners` of each marker is read; on_device: markers and out are both device pointers. K is required, ndist is 0, 4, 5 or 8,
+ * marker_size > 0 (ARUCOHIP_E_INVALID otherwise); y_perpendicular applies rotateXAxis to both rotations. The call returns when the
+ * results are complete, and never touches the single-frame graph or the last batch. */
+int arucohip_planar_poses(arucohip_handle* h, const arucohip_marker_t* markers, int n, int on_device, const float* K, const float* dist,
+                          int ndist, float marker_size, int refine, int y_perpendicular, arucohip_planar_poses_t* out);
+/* The same for the device-resident markers of the first nframes frames of the LAST arucohip_detect_batch call (every chunk; the batch
+ * need not have been run with a pose): out[f * cap + i] belongs to marker i of frame f as that batch returned it, entries beyond a
+ * frame's count are left untouched. out: host, or device with out_on_device. ARUCOHIP_E_CAPACITY when a frame holds more than cap
+ * markers (nothing is written), ARUCOHIP_E_INVALID without a batch of nframes frames. */
+int arucohip_planar_poses_batch(arucohip_handle* h, int nframes, const float* K, const float* dist, int ndist, float marker_size,
+                                int refine, int y_perpendicular, arucohip_planar_poses_t* out, int cap, int out_on_device);
 
 /* Execution time of the dominant streaming kernel (the 16-pixel-per-lane adaptive threshold kernel) from the device's constant-rate
  * clock: every wave leaves its first and last reading, *total_ms = sum over the launches since arucohip_enable_timing(h, 1) of
