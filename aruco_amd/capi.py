@@ -54,6 +54,16 @@ class PlanarPoses(C.Structure):
                 ("pad_", C.c_int32)]
 
 
+class Overlay(C.Structure):
+    """arucohip_overlay_t: what arucohip_draw_markers_batch draws (DRAW_* flags), the outline's width and its colour (B, G, R)."""
+    _fields_ = [("flags", C.c_int32), ("line_width", C.c_int32), ("color", C.c_uint8 * 4)]
+
+
+DRAW_OUTLINE, DRAW_IDS, DRAW_AXIS, DRAW_CUBE, DRAW_Y_PERPENDICULAR = 1, 2, 4, 8, 16
+BOARD_DTYPE = np.dtype([("n_markers", "<i4"), ("has_pose", "<i4"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,))])
+assert C.sizeof(Overlay) == 12 and BOARD_DTYPE.itemsize == 56
+
+
 class Limits(C.Structure):
     _fields_ = [("max_width", C.c_int32), ("max_height", C.c_int32), ("max_batch", C.c_int32),
                 ("max_thres_planes", C.c_int32), ("triggers_per_frame", C.c_int32), ("contours_per_frame", C.c_int32),
@@ -101,6 +111,7 @@ SYMBOLS = [
     "arucohip_fiducial_marker_images", "arucohip_fiducial_marker_side", "arucohip_fiducial_marker_mat", "arucohip_fiducial_shuffle_ids",
     "arucohip_fiducial_board_size", "arucohip_fiducial_board_image", "arucohip_board_pix_to_meters", "arucohip_fiducial_distances",
     "arucohip_fiducial_select",
+    "arucohip_draw_markers_batch", "arucohip_draw_boards_batch",
 ]
 
 _lib = None
@@ -165,6 +176,8 @@ def load():
     L.arucohip_calibrate_board_batch.argtypes = [vp, i, vp, vp, i, i, f, i, i, i, i, vp, vp, vp, vp, vp, vp]
     L.arucohip_planar_poses.argtypes = [vp, vp, i, i, vp, vp, i, f, i, i, vp]
     L.arucohip_planar_poses_batch.argtypes = [vp, i, vp, vp, i, f, i, i, vp, i, i]
+    L.arucohip_draw_markers_batch.argtypes = [vp, vp, i, i, i, i, sz, sz, i, vp, i, vp, i, vp, vp, i, vp]
+    L.arucohip_draw_boards_batch.argtypes = [vp, vp, i, i, i, i, sz, sz, i, vp, i, f, vp, vp, i, i]
     d = C.c_double
     L.arucohip_chromatic_board_corners.argtypes = [vp, i, i, f, vp]
     L.arucohip_chromatic_create.argtypes = [vp, i, i, d, vp, vp, i, i, i, vp, vp]
@@ -656,6 +669,65 @@ class Handle:
         Ka, da = _f32(K), _f32(dist)
         self._chk(self.L.arucohip_planar_poses_batch(self.h, int(nframes), _ptr(Ka), _ptr(da), 0 if da is None else da.size, float(marker_size),
                                                      int(bool(refine)), int(bool(y_perp)), out_ptr, int(cap), 1))
+
+    # ---- overlays: frames and markers are numpy arrays (host) or torch tensors on the handle's device, painted in place
+    @staticmethod
+    def _buf(a):
+        """(pointer, on_device) of a numpy array or a torch tensor; both must be contiguous."""
+        if isinstance(a, np.ndarray):
+            assert a.flags.c_contiguous
+            return a.ctypes.data_as(C.c_void_p), 0
+        assert a.is_contiguous()
+        return C.c_void_p(a.data_ptr()), int(a.is_cuda)
+
+    @classmethod
+    def _frames(cls, frames, width, channels):
+        """Frame arguments of the draw calls. frames: uint8 [N][H][W] (gray) or [N][H][W][3] (B G R); with `width` (and `channels`) given
+        instead [N][H][row_stride bytes], rows padded."""
+        assert str(frames.dtype).endswith("uint8")
+        if width is None:
+            assert frames.ndim in (3, 4)
+            ch = 1 if frames.ndim == 3 else int(frames.shape[3])
+            n, hgt, wid = (int(v) for v in frames.shape[:3])
+            rs = wid * ch
+        else:
+            assert frames.ndim == 3
+            n, hgt, rs = (int(v) for v in frames.shape)
+            wid, ch = int(width), int(channels)
+        ptr, dev = cls._buf(frames)
+        return ptr, n, wid, hgt, ch, rs, rs * hgt, dev
+
+    def draw_markers(self, frames, markers, counts, K=None, dist=None, flags=DRAW_OUTLINE | DRAW_IDS, line_width=1, color=(0, 0, 255), width=None,
+                     channels=1):
+        """arucohip_draw_markers_batch, in place. markers: [N][cap] MARKER_DTYPE (numpy) or the device array detect_batch_device filled
+        (any tensor of N * cap * 96 bytes), counts: N int32 of the same kind. Device frames with device markers: asynchronous."""
+        ptr, n, wid, hgt, ch, rs, fs, dev = self._frames(frames, width, channels)
+        if isinstance(markers, np.ndarray):
+            assert markers.dtype == MARKER_DTYPE and counts.dtype == np.int32
+            total = markers.size
+        else:
+            total = markers.numel() * markers.element_size() // MARKER_DTYPE.itemsize
+        assert total % n == 0 and total >= n and len(counts) == n
+        mptr, mdev = self._buf(markers)
+        cptr, cdev = self._buf(counts)
+        assert mdev == cdev
+        Ka, da = _f32(K), _f32(dist)
+        st = Overlay(int(flags), int(line_width), (C.c_uint8 * 4)(*[int(c) for c in color][:3], 0))
+        self._chk(self.L.arucohip_draw_markers_batch(self.h, ptr, n, wid, hgt, ch, rs, fs, dev, mptr, total // n, cptr, mdev, _ptr(Ka), _ptr(da),
+                                                     0 if da is None else da.size, C.byref(st)))
+        return frames
+
+    def draw_boards(self, frames, boards, marker_size, K, dist=None, flags=DRAW_AXIS | DRAW_CUBE, width=None, channels=1):
+        """arucohip_draw_boards_batch, in place. boards: N BOARD_DTYPE entries (numpy; board_detect_batch's first result converts with
+        np.frombuffer) or a device tensor of N * 56 bytes."""
+        ptr, n, wid, hgt, ch, rs, fs, dev = self._frames(frames, width, channels)
+        if isinstance(boards, np.ndarray):
+            assert boards.dtype == BOARD_DTYPE and boards.size == n
+        bptr, bdev = self._buf(boards)
+        Ka, da = _f32(K), _f32(dist)
+        self._chk(self.L.arucohip_draw_boards_batch(self.h, ptr, n, wid, hgt, ch, rs, fs, dev, bptr, bdev, float(marker_size), _ptr(Ka), _ptr(da),
+                                                    0 if da is None else da.size, int(flags)))
+        return frames
 
     def board_detect(self, markers, ids, obj, info_type, K=None, dist=None, marker_size=-1.0, repj_err_thres=-1.0, y_perp=False):
         m = np.ascontiguousarray(markers, dtype=MARKER_DTYPE)

@@ -262,6 +262,18 @@ void launch_planar_poses(hipStream_t s, const arucohip_marker_t* markers, int n,
 void launch_planar_poses_list(hipStream_t s, int list_frames, int nframes, int first, const Buffers& b, const CamModel& cam, int refine,
                               arucohip_planar_poses_t* out, int cap_out);
 
+// Overlays (k_overlay.hip). Scratch of one call: a 32-byte record per marker slot (the box of its primitives and their number), then
+// OV_SLOTS primitives of 32 bytes per slot, in painting order. A marker needs at most 16 (outline) + 14 ("id=" and eleven characters) +
+// 6 (axis) + 12 (cube) = 48 of them; a board takes one slot.
+constexpr int OV_SLOTS = 48;
+constexpr size_t OV_REC_BYTES = 32, OV_PRIM_BYTES = 32 * OV_SLOTS;
+void launch_overlay_build_markers(hipStream_t s, const arucohip_marker_t* markers, const int32_t* counts, int nframes, int cap, const CamModel& cam,
+                                  int flags, int line_width, uint32_t color, void* recs, void* prims);
+void launch_overlay_build_boards(hipStream_t s, const arucohip_board_t* boards, int nframes, const CamModel& cam, int flags, float marker_size, void* recs,
+                                 void* prims);
+void launch_overlay_raster(hipStream_t s, uint8_t* frames, int nframes, int width, int height, int channels, size_t row_stride, size_t frame_stride,
+                           const void* recs, const void* prims, int cap);
+
 // Camera calibration (k_calib.hip). Views: points obj (xyz) / img (xy) at off[v], npt[v] points each.
 constexpr int CALIB_MAX_POINTS = 512;   // points of one view (= the board kernels' MAX_BOARD_POINTS)
 constexpr int CALIB_RED = 100;          // doubles per view of the reduced system: S_i (81), diag A_i (9), rhs_i (9), pad

@@ -501,9 +501,9 @@ public:
     void glGetModelViewMatrix(double modelview_matrix[16]) const { arucohip_gl_modelview_(Rvec, Tvec, modelview_matrix); }              // marker.h:90
     void OgreGetPoseParameters(double position[3], double orientation[4]) const { arucohip_ogre_pose_(Rvec, Tvec, position, orientation); }  // marker.h:104
 #if ARUCOHIP_HAVE_OPENCV
-    // marker.h:69. Drawing is outside the detection path: the member is DECLARED so that the reference's callers compile
-    // (utils/aruco_simple.cpp:82); its definition stays the reference's own cv::line / cv::putText code (src/marker.cpp:54-81), which needs
-    // nothing but OpenCV imgproc and this class - INTEGRATION.md "drawing".
+    // marker.h:69. The member is DECLARED so that the reference's callers compile (utils/aruco_simple.cpp:82). Its definition is the
+    // includer's choice: the reference's own cv::line / cv::putText code (src/marker.cpp:54-81), or, with ARUCOHIP_SHIM_DEFINE_DRAWING
+    // defined before this header, the device overlay below (aruco::DeviceDrawing) - INTEGRATION.md "drawing".
     void draw(cv::Mat& in, cv::Scalar color, int lineWidth = 1, bool writeId = true) const;
 #endif
     friend bool operator<(const Marker& a, const Marker& b) { return a.id < b.id; }
@@ -606,7 +606,98 @@ public:
     cv::Mat_<double> Rvec, Tvec;
     void glGetModelViewMatrix(double modelview_matrix[16]) const { arucohip_gl_modelview_(Rvec, Tvec, modelview_matrix); }              // board.h:109
     void OgreGetPoseParameters(double position[3], double orientation[4]) const { arucohip_ogre_pose_(Rvec, Tvec, position, orientation); }  // board.h:123
+    // board.h:99 Board::draw: Marker::draw of every member marker, on the device (DeviceDrawing::draw); colour as B, G, R
+    inline void draw(cv::Mat& im, unsigned char b, unsigned char g, unsigned char r, int lineWidth = 1, bool writeId = true) const;
+#if ARUCOHIP_HAVE_OPENCV
+    void draw(cv::Mat& im, cv::Scalar color, int lineWidth = 1, bool writeId = true) const {
+        draw(im, (unsigned char)color[0], (unsigned char)color[1], (unsigned char)color[2], lineWidth, writeId);
+    }
+#endif
 };
+
+// Marker::draw, Board::draw and CvDrawingUtils::draw3dAxis / draw3dCube through the device overlay pass (arucohip_draw_markers_batch /
+// arucohip_draw_boards_batch on the process-wide handle): the frame goes up, is painted and comes back. The reference's primitives, order,
+// colours and geometry; lines are not antialiased and the text uses the library's bitmap font (INTEGRATION.md "drawing"). 8-bit frames
+// with 1 or 3 (B G R) channels. A caller that keeps its frames on the device calls the C ABI directly and copies nothing.
+class DeviceDrawing {
+public:
+    // flags: ARUCOHIP_DRAW_*; CP is needed for AXIS / CUBE
+    static void draw(cv::Mat& image, const std::vector<Marker>& markers, int flags = ARUCOHIP_DRAW_OUTLINE | ARUCOHIP_DRAW_IDS, int lineWidth = 1,
+                     unsigned char b = 0, unsigned char g = 0, unsigned char r = 255, const CameraParameters* CP = nullptr) {
+        if (markers.empty()) return;
+        std::vector<arucohip_marker_t> m(markers.size());
+        for (size_t i = 0; i < markers.size(); i++) markers[i].to_abi(&m[i]);
+        const int32_t n = (int32_t)m.size();
+        const arucohip_overlay_t st = {flags, lineWidth, {b, g, r, 0}};
+        float K[9], d[8];
+        const bool hasK = CP && mat_to_K_(CP->CameraMatrix, K);
+        const int nd = CP ? mat_to_dist_(CP->Distorsion, d) : 0;
+        SharedHandle_& sh = SharedHandle_::get();
+        std::lock_guard<std::mutex> lock(sh.mu);
+        arucohip_handle* h = sh.ensure(image.cols, image.rows);
+        arucohip_throw_(arucohip_draw_markers_batch(h, image.data, 1, image.cols, image.rows, channels_(image), (size_t)image.step,
+                                                    (size_t)image.step * image.rows, 0, m.data(), n, &n, 0, hasK ? K : nullptr, nd ? d : nullptr, nd, &st),
+                        "DeviceDrawing::draw", h);
+    }
+    static void draw3dAxis(cv::Mat& image, const Marker& m, const CameraParameters& CP) {
+        draw(image, std::vector<Marker>(1, m), ARUCOHIP_DRAW_AXIS, 1, 0, 0, 255, &CP);
+    }
+    static void draw3dCube(cv::Mat& image, const Marker& m, const CameraParameters& CP, bool setYperpendicular = false) {
+        draw(image, std::vector<Marker>(1, m), ARUCOHIP_DRAW_CUBE | (setYperpendicular ? ARUCOHIP_DRAW_Y_PERPENDICULAR : 0), 1, 0, 0, 255, &CP);
+    }
+    static void draw3dAxis(cv::Mat& image, const Board& B, const CameraParameters& CP) { board_(image, B, CP, ARUCOHIP_DRAW_AXIS); }
+    static void draw3dCube(cv::Mat& image, const Board& B, const CameraParameters& CP, bool setYperpendicular = false) {
+        board_(image, B, CP, ARUCOHIP_DRAW_CUBE | (setYperpendicular ? ARUCOHIP_DRAW_Y_PERPENDICULAR : 0));
+    }
+
+private:
+    static int channels_(const cv::Mat& image) {
+        if (image.type() != CV_8UC1 && image.type() != CV_8UC3) arucohip_throw_(ARUCOHIP_E_INVALID, "drawing: CV_8UC1 or CV_8UC3 frames", nullptr);
+        return image.type() == CV_8UC3 ? 3 : 1;
+    }
+    static void board_(cv::Mat& image, const Board& B, const CameraParameters& CP, int flags) {
+        if (B.empty()) arucohip_throw_(ARUCOHIP_E_INVALID, "drawing: the board holds no marker (B[0].ssize is its scale)", nullptr);
+        arucohip_board_t b;
+        std::memset(&b, 0, sizeof(b));
+        b.n_markers = (int32_t)B.size();
+        if (!B.Rvec.empty() && !B.Tvec.empty()) {
+            b.has_pose = 1;
+            for (int k = 0; k < 3; k++) b.rvec[k] = B.Rvec(k), b.tvec[k] = B.Tvec(k);
+        }
+        float K[9], d[8];
+        const bool hasK = mat_to_K_(CP.CameraMatrix, K);
+        const int nd = mat_to_dist_(CP.Distorsion, d);
+        SharedHandle_& sh = SharedHandle_::get();
+        std::lock_guard<std::mutex> lock(sh.mu);
+        arucohip_handle* h = sh.ensure(image.cols, image.rows);
+        arucohip_throw_(arucohip_draw_boards_batch(h, image.data, 1, image.cols, image.rows, channels_(image), (size_t)image.step,
+                                                   (size_t)image.step * image.rows, 0, &b, 0, B[0].ssize, hasK ? K : nullptr, nd ? d : nullptr, nd, flags),
+                        "DeviceDrawing::draw3d (board)", h);
+    }
+};
+inline void Board::draw(cv::Mat& im, unsigned char b, unsigned char g, unsigned char r, int lineWidth, bool writeId) const {
+    DeviceDrawing::draw(im, *this, ARUCOHIP_DRAW_OUTLINE | (writeId ? ARUCOHIP_DRAW_IDS : 0), lineWidth, b, g, r);
+}
+#if ARUCOHIP_HAVE_OPENCV && defined(ARUCOHIP_SHIM_DEFINE_DRAWING)
+// The reference's drawing names, defined through the device overlay. Off by default: an integration that keeps the reference's own
+// src/marker.cpp / src/cvdrawingutils.{h,cpp} (or any other definition of these names) must not define the macro.
+inline void Marker::draw(cv::Mat& in, cv::Scalar color, int lineWidth, bool writeId) const {
+    if (size() != 4) return;
+    DeviceDrawing::draw(in, std::vector<Marker>(1, *this), ARUCOHIP_DRAW_OUTLINE | (writeId ? ARUCOHIP_DRAW_IDS : 0), lineWidth, (unsigned char)color[0],
+                        (unsigned char)color[1], (unsigned char)color[2]);
+}
+class CvDrawingUtils {
+public:
+    static void draw3dAxis(cv::Mat& Image, Marker& m, const CameraParameters& CP) { DeviceDrawing::draw3dAxis(Image, m, CP); }
+    static void draw3dCube(cv::Mat& Image, Marker& m, const CameraParameters& CP, bool setYperpendicular = false) {
+        DeviceDrawing::draw3dCube(Image, m, CP, setYperpendicular);
+    }
+    static void draw3dAxis(cv::Mat& Image, Board& B, const CameraParameters& CP) { DeviceDrawing::draw3dAxis(Image, B, CP); }
+    static void draw3dCube(cv::Mat& Image, Board& B, const CameraParameters& CP, bool setYperpendicular = false) {
+        DeviceDrawing::draw3dCube(Image, B, CP, setYperpendicular);
+    }
+};
+#endif
 
 // ---- marker-id decoders (markerdetector.h:248 setMakerDetectorFunction). On the accelerated path the decoders run on the
 // device; the static functions below are the tokens a caller passes to MarkerDetector::setMakerDetectorFunction.

@@ -485,6 +485,44 @@ int arucohip_planar_poses(arucohip_handle* h, const arucohip_marker_t* markers, 
 int arucohip_planar_poses_batch(arucohip_handle* h, int nframes, const float* K, const float* dist, int ndist, float marker_size,
                                 int refine, int y_perpendicular, arucohip_planar_poses_t* out, int cap, int out_on_device);
 
+/* ---- Overlays: Marker::draw (marker.cpp:54-81), Board::draw and CvDrawingUtils::draw3dAxis / draw3dCube (cvdrawingutils.cpp:41-255) painted
+ * into 8-bit frames where they lie (DESIGN.md "Overlay"). Primitives, order, colours (B G R) and geometry are the reference's; the pixel
+ * coverage is this library's: lines are not antialiased, text uses a 5 x 7 bitmap font. Within a frame the result is that
+ * of painting the primitives one after another, markers in array order; identical on every run. */
+enum {
+    ARUCOHIP_DRAW_OUTLINE = 1,          /* the four edges in `color`, then small squares at corners 0, 1, 2 in red, green, blue */
+    ARUCOHIP_DRAW_IDS = 2,              /* "id=<id>" in 255 - color at the integer centroid */
+    ARUCOHIP_DRAW_AXIS = 4,             /* markers with a pose: draw3dAxis, length 3 * ssize */
+    ARUCOHIP_DRAW_CUBE = 8,             /* markers with a pose: draw3dCube */
+    ARUCOHIP_DRAW_Y_PERPENDICULAR = 16  /* the cube's setYperpendicular form */
+};
+typedef struct arucohip_overlay {
+    int32_t flags;      /* ARUCOHIP_DRAW_* */
+    int32_t line_width; /* 1..7, of the outline */
+    uint8_t color[4];   /* B, G, R of the outline; [3] is ignored */
+} arucohip_overlay_t;
+/* frames: nframes frames of height rows of width pixels with `channels` (1 or 3, B G R) interleaved bytes, rows row_stride and frames
+ * frame_stride bytes apart; on a one-channel frame only component 0 of a colour is written. Bytes between width * channels and
+ * row_stride are never written, and a 64 x 16 tile that nothing touches is neither read nor written. markers (nframes * cap) and
+ * counts (nframes) have the layout arucohip_detect_batch writes with out_on_device: frame f draws its first min(counts[f], cap)
+ * markers, none when counts[f] <= 0. markers_on_device covers both arrays. With device frames AND device markers the call is
+ * asynchronous on the handle's stream, behind whatever detection is queued there (a detect -> draw chain needs no host round trip);
+ * otherwise it returns when the frames are done (host frames are copied up, drawn and copied back). K (9 floats) is required for AXIS /
+ * CUBE, dist: ndist (0, 4, 5, 8) floats. A primitive with an endpoint that is not finite, lies in the camera's plane or beyond +-2^20
+ * is dropped whole. style NULL: OUTLINE | IDS, width 1, red (0, 0, 255), the reference's defaults. ARUCOHIP_E_INVALID: channels not 1
+ * or 3, line_width outside 1..7, AXIS / CUBE without K, row_stride < width * channels, frames that overlap; ARUCOHIP_E_UNSUPPORTED:
+ * frames wider or taller than the handle, cap above 65535. Uses scratch of its own: the single-frame graph and the last batch stay valid. */
+int arucohip_draw_markers_batch(arucohip_handle* h, uint8_t* frames, int nframes, int width, int height, int channels, size_t row_stride,
+                                size_t frame_stride, int frames_on_device, const arucohip_marker_t* markers, int cap, const int32_t* counts,
+                                int markers_on_device, const float* K, const float* dist, int ndist, const arucohip_overlay_t* style);
+/* CvDrawingUtils::draw3dAxis / draw3dCube for boards: boards[f] (rvec / tvec; nothing is drawn without has_pose) goes into frame f. The
+ * axis has length 2 * marker_size and width 2 with labels X Y Z, the cube has edge marker_size (B[0].ssize in the reference). flags:
+ * ARUCOHIP_DRAW_AXIS | ARUCOHIP_DRAW_CUBE | ARUCOHIP_DRAW_Y_PERPENDICULAR. K is required. Board::draw is arucohip_draw_markers_batch on
+ * the board's markers. */
+int arucohip_draw_boards_batch(arucohip_handle* h, uint8_t* frames, int nframes, int width, int height, int channels, size_t row_stride,
+                               size_t frame_stride, int frames_on_device, const arucohip_board_t* boards, int boards_on_device, float marker_size,
+                               const float* K, const float* dist, int ndist, int flags);
+
 /* Execution time of the dominant streaming kernel (the 16-pixel-per-lane adaptive threshold kernel) from the device's constant-rate
  * clock: every wave leaves its first and last reading, *total_ms = sum over the launches since arucohip_enable_timing(h, 1) of
  * (last wave's end - first wave's start), *launches = their number (0 when another threshold kernel ran: use the event times).
