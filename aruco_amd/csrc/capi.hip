@@ -647,14 +647,18 @@ static int run_rectangles(arucohip_handle* h, hipStream_t s, const FrameGeom& g,
         if (RUN_STAGE(b.env, 1)) launch_start_candidates(s, g, nframes * dp.nthr, b, dp.min_contour);
         MARK(K_WALKERS);
         // walkers; where the handle has a side stream their late generations run there under the first quad pass (the contour_quad mark sits at
-        // the fork); a pipeline lane has none and runs every generation, then the one quad pass, on s
+        // the fork); a pipeline lane has none: its late walks run inside the launch of the first quad pass, on s, and a small pass takes their borders
         WalkFork fk{h->side_stream, h->ev_wfork, h->ev_wjoin, ev ? ev[K_WALKERS_LONG] : nullptr};
-        const bool forked = RUN_STAGE(b.env, 2) ? launch_walkers(s, fk, g, nframes * dp.nthr, dp, b) : false;
+        const int tail = RUN_STAGE(b.env, 2) ? launch_walkers(s, fk, g, nframes * dp.nthr, dp, b) : WALKS_DONE;
         MARK(K_CONTOUR_QUADS);
-        if (RUN_STAGE(b.env, 4)) launch_contour_quads(s, g, nframes, dp, b, forked ? 1 : 0);
-        if (forked) {
-            HIPCHK(h, hipStreamWaitEvent(s, h->ev_wjoin, 0));
-            if (RUN_STAGE(b.env, 4)) launch_contour_quads(s, g, nframes, dp, b, 2);
+        if (tail == WALKS_LATE) {
+            launch_late_quads(s, g, nframes, dp, b);
+        } else {
+            if (RUN_STAGE(b.env, 4)) launch_contour_quads(s, g, nframes, dp, b, tail == WALKS_FORKED ? 1 : 0);
+            if (tail == WALKS_FORKED) {
+                HIPCHK(h, hipStreamWaitEvent(s, h->ev_wjoin, 0));
+                if (RUN_STAGE(b.env, 4)) launch_contour_quads(s, g, nframes, dp, b, 2);
+            }
         }
     }
     MARK(K_FRAME_CANDS);
@@ -1245,14 +1249,17 @@ static int fetch_contours(arucohip_handle* h0, int frame, std::vector<ContourDes
     std::vector<ContourDesc> all;
     for (int t = 0; t < nthr; t++) {
         const int plane = frame * nthr + t;
-        uint32_t n = 0;
-        HIPCHK(h, hipMemcpyAsync(&n, h->buf.trig_cnt + (size_t)plane * TRIG_CNT_STRIDE + TC_CDESC, sizeof(n), hipMemcpyDeviceToHost, h->stream));
+        uint32_t line[TC_LATE + 1] = {};
+        HIPCHK(h, hipMemcpyAsync(line, h->buf.trig_cnt + (size_t)plane * TRIG_CNT_STRIDE, sizeof(line), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        n = std::min(n, h->buf.cap_cdesc);
-        if (!n) continue;
+        const uint32_t n = std::min(line[TC_CDESC], h->buf.cap_cdesc);
+        const uint32_t nlate = std::min(line[TC_LATE], h->buf.cap_cdesc - n);   // a lane's late list: the last nlate slots of the plane's array
+        if (!n && !nlate) continue;
         const size_t at = all.size();
-        all.resize(at + n);
-        HIPCHK(h, hipMemcpyAsync(all.data() + at, h->buf.cdesc + (size_t)plane * h->buf.cap_cdesc, n * sizeof(ContourDesc), hipMemcpyDeviceToHost, h->stream));
+        all.resize(at + n + nlate);
+        const ContourDesc* base = h->buf.cdesc + (size_t)plane * h->buf.cap_cdesc;
+        if (n) HIPCHK(h, hipMemcpyAsync(all.data() + at, base, n * sizeof(ContourDesc), hipMemcpyDeviceToHost, h->stream));
+        if (nlate) HIPCHK(h, hipMemcpyAsync(all.data() + at + n, base + (h->buf.cap_cdesc - nlate), nlate * sizeof(ContourDesc), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     out->clear();
@@ -1322,7 +1329,7 @@ int arucohip_debug_counters(arucohip_handle* h, uint32_t* out8) {
             if (i != 1 && i != 2) acc[i] = (i == CNT_STATUS) ? (acc[i] | cnt[i]) : acc[i] + cnt[i];   // [1], [2] come from the planes' own counters below
         for (int p = 0; p < planes; p++) {
             ntrig += tc[(size_t)p * TRIG_CNT_STRIDE] + tc[(size_t)p * TRIG_CNT_STRIDE + 1];
-            acc[1] += tc[(size_t)p * TRIG_CNT_STRIDE + TC_CDESC], acc[2] += tc[(size_t)p * TRIG_CNT_STRIDE + TC_POOL];
+            acc[1] += tc[(size_t)p * TRIG_CNT_STRIDE + TC_CDESC] + tc[(size_t)p * TRIG_CNT_STRIDE + TC_LATE], acc[2] += tc[(size_t)p * TRIG_CNT_STRIDE + TC_POOL];
             nraw += rc_[(size_t)p * TRIG_CNT_STRIDE];
             nlong += rg[(size_t)p * TRIG_CNT_STRIDE] + rg[(size_t)p * TRIG_CNT_STRIDE + 1];
         }

@@ -24,6 +24,8 @@ constexpr int TC_CDESC = 2;           // words of a plane's trig_cnt line: 0 / 1
 constexpr int TC_POOL = 3;
 constexpr int TC_STATUS = 5;          // 5 = overflow bits (StatusBits) of THIS plane: a frame whose planes carry any is reported with n = -1
 constexpr int TC_SNAP = 4;            // 4 = descriptors that existed when the late walker generations were forked            // 2 = contour descriptors, 3 = contour points allocated (per plane: no global hot counter)
+constexpr int TC_LATE = 6;            // 6 = descriptors of the plane's late list (from the top of its cdesc array downwards): the borders a pipeline
+                                      //     lane's late walks keep while contour_quad's first pass runs (k_contours.hip: late_quad_kernel)
 constexpr int WALK_BLOCKS = 16;       // 64-lane walker workgroups per plane
 
 
@@ -227,13 +229,15 @@ struct WalkFork {
     hipEvent_t forked, joined;   // used only with a side stream
     hipEvent_t after_first;      // recorded behind the first pass (per-kernel timing), may be null
 };
-bool launch_walkers(hipStream_t s, const WalkFork& fk, const FrameGeom& g, int nplanes, const DetectParams& p, const Buffers& b);
+enum WalkTail { WALKS_DONE = 0, WALKS_FORKED = 1, WALKS_LATE = 2 };   // what launch_walkers leaves to its caller (k_contours.hip)
+int launch_walkers(hipStream_t s, const WalkFork& fk, const FrameGeom& g, int nplanes, const DetectParams& p, const Buffers& b);
 size_t walk_scratch_words(int nplanes, const DetectParams& p, uint32_t long_cap);   // capacity launch_walkers needs in Buffers::walk_scratch
 constexpr int GEN_FORK_AFTER = 3;   // generations in front of the fork; a walk that enters generation GEN_FORK_AFTER + 1 is a "late" one
 size_t gen_cnt_word(int kind, int gen, int sublist);   // index into Buffers::gen_cnt of the entry count of a generation list (kind 0 outer, 1 hole; sublist 0..7)
 constexpr size_t GEN_CNT_WORDS = 2 * 32 * 32 * 8;                 // words of Buffers::gen_cnt: [2 kinds][GEN_MAX + 2 generations][8 sublists] lines of 32 words
 void launch_segments(hipStream_t s, const FrameGeom& g, int nplanes, const DetectParams& p, const Buffers& b);
 void launch_contour_quads(hipStream_t s, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b, int pass = 0);
+void launch_late_quads(hipStream_t s, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b);   // behind WALKS_LATE: late walks + every quad pass
 void launch_frame_candidates(hipStream_t s, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b);
 // warp + histogram, Otsu threshold, id / rotation of every candidate (left in Cand; the caller's decoder: warp only). decode_from_cells: the batch
 // takes the variant that keeps 49 cell medians per candidate instead of the stored patch and decodes in otsu_kernel (k_decode.hip).

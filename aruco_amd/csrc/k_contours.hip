@@ -586,14 +586,19 @@ __device__ __forceinline__ int walk_run(const uint64_t* __restrict__ tiles, int 
 
 // A closed border that passes the size filter: descriptor slot and point range from the plane's own counters (a global
 // counter would serialise every kept border). Returns the descriptor's pool offset for the checkpoints / points.
+// LATE: the border goes to the plane's late list - counted in TC_LATE, descriptors from the top of the plane's array downwards - so that a contour_quad
+// pass running beside the walk (late_quad_kernel) never sees it; TC_CDESC is final by then, and the two lists share the array's cap_cdesc slots.
+template <bool LATE = false>
 __device__ __forceinline__ bool keep_border(const WalkArgs& a, int plane, bool hole, uint32_t tkey, uint32_t pos0, uint32_t n, uint32_t nck_in_pool,
                                             uint32_t ck_off, uint32_t* pool_at) {
-    const uint32_t slot = atomicAdd(&a.trig_cnt[plane * TRIG_CNT_STRIDE + TC_CDESC], 1u);
+    uint32_t slot = atomicAdd(&a.trig_cnt[plane * TRIG_CNT_STRIDE + (LATE ? TC_LATE : TC_CDESC)], 1u);
     uint32_t off = atomicAdd(&a.trig_cnt[plane * TRIG_CNT_STRIDE + TC_POOL], n + nck_in_pool);
-    if (slot >= a.cap_cdesc) {
+    const uint32_t room = LATE ? a.cap_cdesc - min(a.trig_cnt[plane * TRIG_CNT_STRIDE + TC_CDESC], a.cap_cdesc) : a.cap_cdesc;
+    if (slot >= room) {
         flag_overflow(a.counters, a.trig_cnt, plane, ST_CDESC_OVERFLOW);
         return false;
     }
+    if (LATE) slot = a.cap_cdesc - 1u - slot;
     bool ok = true;
     if (off + n + nck_in_pool > a.cap_pool) {
         flag_overflow(a.counters, a.trig_cnt, plane, ST_POOL_OVERFLOW);
@@ -724,7 +729,9 @@ __global__ __launch_bounds__(64) void walker_kernel(WalkArgs a) {
 // Round 4 measured the alternative "a wave owns 64 q walks and its lanes take over the next one when theirs ends" (lane utilisation of the generations
 // 60 % -> 69 % / 80 % for q = 2 / 4, and the stage 0.64 -> 0.84 / 1.07 ms: every generation wave is resident at once, the time is the iterations of the
 // longest walk times the latency of an iteration, not lane-step slots). Step counts and the A/B: profiles/r04_walker_steps.txt. Not kept.
-template <bool HOLE>
+// FINISH (late_quad_kernel's walker workgroups): every walk of the list runs to its end in one go - closed, proven bad or max_contour steps - instead of
+// gen_steps steps and a hand-over to the next list, and the closed borders go to the planes' late lists (keep_border<true>).
+template <bool HOLE, bool FINISH = false>
 __device__ __forceinline__ void walk_generation(const WalkArgs& a, int chunk, uint32_t* rows) {
     const int kind = HOLE ? 1 : 0, lane = threadIdx.x;
     // gen_blocks is a multiple of 8: workgroup b of this kind runs on XCD b % 8 and takes sublist b % 8 (gen_nx = 8) with the other gen_blocks / 8 - 1 of its XCD
@@ -744,12 +751,13 @@ __device__ __forceinline__ void walk_generation(const WalkArgs& a, int chunk, ui
         const int plane = (int)(ring / (2u * a.long_cap));
         const uint64_t* __restrict__ tiles = a.tiles + (size_t)plane * plane_tiles;
         uint32_t* ck = a.scratch + (size_t)ring * a.maxck;
-        const uint32_t lim = min(n + (uint32_t)a.gen_steps, nmax);
+        const uint32_t lim = FINISH ? nmax : min(n + (uint32_t)a.gen_steps, nmax);
         const int res = walk_run<HOLE, 64>(tiles, a.tnx, a.tny, rows, lane, live, tkey, pos0, pos1, lim, nmax, pos, n, s, [&](uint32_t q) { return ck + q; });
         if (live && res == WR_CLOSED && n < nmax && (int)n > a.min_contour) {
             uint32_t at;
-            keep_border(a, plane, HOLE, tkey, pos0, n, 0u, (uint32_t)((size_t)ring * a.maxck), &at);
+            keep_border<FINISH>(a, plane, HOLE, tkey, pos0, n, 0u, (uint32_t)((size_t)ring * a.maxck), &at);
         }
+        if (FINISH) continue;   // a walk that is still open has taken max_contour steps: dropped, like one that reaches the limit in the last generation
         const bool again = live && res == WR_LIMIT && n < nmax;
         const unsigned long long bal = __ballot(again);
         if (bal) {
@@ -785,10 +793,7 @@ __global__ void snapshot_kernel(uint32_t* trig_cnt, int nplanes) {
     if (p < nplanes) trig_cnt[p * TRIG_CNT_STRIDE + TC_SNAP] = trig_cnt[p * TRIG_CNT_STRIDE + TC_CDESC];
 }
 
-// returns true if the late generations were forked to fk.side: the caller runs launch_contour_quads pass 1, waits for
-// fk.joined on its stream and runs pass 2. Without a side stream (a pipeline lane) every generation runs on s, nothing is
-// snapshotted and the caller runs the one pass 0.
-bool launch_walkers(hipStream_t s, const WalkFork& fk, const FrameGeom& g, int nplanes, const DetectParams& p, const Buffers& b) {
+static WalkArgs walk_args(const FrameGeom& g, int nplanes, const DetectParams& p, const Buffers& b) {
     WalkArgs a;
     a.tiles = b.tiles, a.tnx = tiles_x(g.width), a.tny = tiles_y(g.height), a.nplanes = nplanes;
     a.trig = b.trig, a.trig_cnt = b.trig_cnt, a.cdesc = b.cdesc, a.counters = b.counters;
@@ -804,27 +809,47 @@ bool launch_walkers(hipStream_t s, const WalkFork& fk, const FrameGeom& g, int n
     a.gen_cap = (uint32_t)((size_t)((nplanes + 7) / 8 * 8) * b.long_cap);
     a.gen_state = (uint4*)b.gen_buf;
     a.gen_ring = (uint32_t*)(a.gen_state + 4 * (size_t)a.gen_cap);
-    a.gen = 0, a.gen_steps = 0;
+    a.gen = 0, a.gen_steps = 0, a.gen_blocks = 0;
     a.leash = LEASH_DEFAULT;
+    return a;
+}
+
+// Generations: 64-step ones while many walks are alive, then doubling; after the listed generations the length stays 1024.
+static const int kGenSteps[] = {128, 256, 512, 1024};
+static int gen_steps_of(int gen, const DetectParams& p) { return gen == GEN_MAX ? p.max_contour /* whatever is left */ : gen <= 4 ? kGenSteps[gen - 1] : 1024; }
+// 64-lane workgroups per kind for a generation whose walks have `before` steps behind them: enough that every wave-load of walks runs at once while
+// many walks are alive (about a fifth of a plane's ~1000 candidates reach generation 1), fewer for the thin late generations; surplus workgroups
+// exit at once. A multiple of 8 (walk_generation's sublists).
+static int gen_blocks_of(int nplanes, int before) {
+    const int per_plane_x16 = before < 200 ? 64 : before < 450 ? 40 : before < 1100 ? 24 : 4;   // walks per plane and kind / 4, rough upper bounds
+    return (std::max(64, std::min(8192, (nplanes * per_plane_x16 * 4 + 63) / 64 / 2)) + 7) / 8 * 8;
+}
+
+// What launch_walkers leaves to its caller:
+//   WALKS_DONE     every generation has run on s: one contour_quad pass (launch_contour_quads pass 0)
+//   WALKS_FORKED   the late generations run on fk.side: pass 1, wait for fk.joined on s, pass 2
+//   WALKS_LATE     no side stream (a pipeline lane): generations 1..GEN_FORK_AFTER have run on s and the late walks are still open;
+//                  launch_late_quads finishes them and turns every border into quads
+int launch_walkers(hipStream_t s, const WalkFork& fk, const FrameGeom& g, int nplanes, const DetectParams& p, const Buffers& b) {
+    WalkArgs a = walk_args(g, nplanes, p, b);
     const int planes8 = ((nplanes + 7) / 8) * 8;
     // a 64-thread workgroup per wave keeps the divergent walks of one wave from holding other waves' slots
     hipLaunchKernelGGL(walker_kernel, dim3(planes8 * WALK_BLOCKS), dim3(64), 0, s, a);
     if (fk.after_first) (void)hipEventRecord(fk.after_first, s);
-    // Generations: 64-step ones while many walks are alive, then doubling. The late generations hold a handful of very long
-    // walks and are pure latency (a border of n pixels is a chain of n dependent steps), so they run on the side stream
-    // while the main stream already turns the borders found so far into quads (launch_contour_quads pass 1); the per-plane
-    // descriptor counts at the fork are snapshotted for that. A pipeline lane brings no side stream: with other batches in flight
-    // the chip is busy while the chain runs, and the fork's two event hops only tie a second stream into the shared hardware
-    // queues (profiles/lane_single_stream_ab.txt).
-    // Round 2 (every lane re-centres its own block): few long generations beat many short ones; the side stream takes over
+    // The late generations hold a handful of very long walks and are pure latency (a border of n pixels is a chain of n dependent steps), so they
+    // run beside contour_quad's pass over the borders found so far. A handle with a side stream forks them onto it (the per-plane descriptor counts
+    // at the fork are snapshotted for pass 1). A pipeline lane brings no side stream - the fork's two event hops only tie a second stream into the
+    // shared hardware queues (profiles/lane_single_stream_ab.txt) - and gets the same overlap inside ONE launch on its own stream: late_quad_kernel
+    // (profiles/late_walks_fused_ab.txt).
+    // Round 2 (every lane re-centres its own block): few long generations beat many short ones; the late walks begin
     // after 128 + 256 + 512 steps, borders of up to 960 points are in contour_quad's first pass (profiles/r02_kernel_experiments.txt).
-    // After the listed generations the length stays 1024.
-    static const int kSteps[] = {128, 256, 512, 1024};
-    constexpr int nsched = 4, kForkAfter = GEN_FORK_AFTER;   // kForkAfter: generations on the main stream when there is a side stream
+    constexpr int kForkAfter = GEN_FORK_AFTER;   // generations every batch runs on its own stream
+    const bool fuse = !fk.side && RUN_STAGE(b.env, 4);
     int done = a.leash;
     bool forked = false;
     hipStream_t cur = s;
     for (int g = 1; g <= GEN_MAX && done < p.max_contour && RUN_STAGE(b.env, 3); g++) {
+        if (g == kForkAfter + 1 && fuse) return WALKS_LATE;
         if (g == kForkAfter + 1 && fk.side) {
             hipLaunchKernelGGL(snapshot_kernel, dim3((nplanes + 255) / 256), dim3(256), 0, s, b.trig_cnt, nplanes);
             (void)hipEventRecord(fk.forked, s);
@@ -832,18 +857,13 @@ bool launch_walkers(hipStream_t s, const WalkFork& fk, const FrameGeom& g, int n
             cur = fk.side, forked = true;
         }
         a.gen = g;
-        a.gen_steps = g <= nsched ? kSteps[g - 1] : 1024;
-        if (g == GEN_MAX) a.gen_steps = p.max_contour;   // whatever is left
+        a.gen_steps = gen_steps_of(g, p);
+        a.gen_blocks = gen_blocks_of(nplanes, done);   // done: steps every walk of this generation has behind it
         done += a.gen_steps;
-        // enough workgroups that every wave-load of walks runs at once while many walks are alive (about a fifth of a
-        // plane's ~1000 candidates reach generation 1), fewer for the thin late generations; surplus workgroups exit at once
-        const int before = done - a.gen_steps;   // steps every walk of this generation has behind it
-        const int per_plane_x16 = before < 200 ? 64 : before < 450 ? 40 : before < 1100 ? 24 : 4;   // walks per plane and kind / 4, rough upper bounds
-        a.gen_blocks = (std::max(64, std::min(8192, (nplanes * per_plane_x16 * 4 + 63) / 64 / 2)) + 7) / 8 * 8;
         hipLaunchKernelGGL(walker_long_kernel, dim3(2 * a.gen_blocks), dim3(64), 0, cur, a);
     }
     if (forked) (void)hipEventRecord(fk.joined, fk.side);
-    return forked;
+    return forked ? WALKS_FORKED : WALKS_DONE;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1301,29 +1321,24 @@ __device__ __forceinline__ void border_pair_to_quads(const QuadArgs& a, const Co
     if (hl == 0 && !reject && outn >= 4) polygon_to_quad(a, cd, ci, s_out[h], outn, eps);
 }
 
-__global__ __launch_bounds__(64) void contour_quad_kernel(QuadArgs a) {
-    throughput_bound_priority();
-    __shared__ __align__(16) short2 Plds[QP_LDS];   // contour points (two borders of up to DUAL_MAX points, or one of up to QP_LDS)
-    __shared__ uint32_t rows[TB_ROWS * EMIT_LANES];  // one 32x32-pixel block per emitting lane
-    __shared__ int s_stack[2][16][2];
-    __shared__ short2 s_out[2][12];
-    __shared__ int s_outn;
-    static_assert(QP_LDS >= 2 * DUAL_MAX && EMIT_LANES == 64, "the two-borders-per-wave path uses the whole point buffer and a block per lane");
-    // 1-D grid dealt round-robin over the 8 XCDs: all workgroups of a plane land on one XCD, whose L2 then serves the plane's tiles,
-    // descriptors and checkpoints to all of them (same unpacking as walker_kernel)
-    const int xcd = blockIdx.x & 7, rest = blockIdx.x >> 3;
+// contour_quad's work of workgroup `bid` of planes8 * qblocks. 1-D grid dealt round-robin over the 8 XCDs: all workgroups of a plane land on one XCD,
+// whose L2 then serves the plane's tiles, descriptors and checkpoints to all of them (same unpacking as walker_kernel).
+// pass 0: all borders of TC_CDESC; pass 1: those that existed when the late walker generations were forked; pass 2: the rest; pass 3: the planes' late
+// lists (keep_border<true>: TC_LATE descriptors from the top of the plane's array downwards).
+__device__ __forceinline__ void quad_blocks(const QuadArgs& a, const int bid, short2* Plds, uint32_t* rows, int (*s_stack)[16][2], short2 (*s_out)[12], int& s_outn) {
+    const int xcd = bid & 7, rest = bid >> 3;
     const int chunk = rest % a.qblocks, plane = (rest / a.qblocks) * 8 + xcd;
     if (plane >= a.nplanes) return;
-    // pass 0: all borders; pass 1: those that existed when the late walker generations were forked; pass 2: the rest
     const uint32_t nall = min(a.trig_cnt[plane * TRIG_CNT_STRIDE + TC_CDESC], a.cap_cdesc);
     const uint32_t nsnap = min(a.trig_cnt[plane * TRIG_CNT_STRIDE + TC_SNAP], a.cap_cdesc);
-    const uint32_t lo = a.pass == 2 ? nsnap : 0u, ncd = a.pass == 1 ? nsnap : nall;
+    const uint32_t nlate = a.pass == 3 ? min(a.trig_cnt[plane * TRIG_CNT_STRIDE + TC_LATE], a.cap_cdesc - nall) : 0u;
+    const uint32_t lo = a.pass == 2 ? nsnap : 0u, ncd = a.pass == 3 ? nlate : a.pass == 1 ? nsnap : nall;
     const bool upper = threadIdx.x >= 32;
     ContourDesc pend;   // a short border waiting for a partner
     uint32_t pend_ci = 0;
     bool has_pend = false;
     for (uint32_t cslot = lo + (uint32_t)chunk; cslot < ncd; cslot += (uint32_t)a.qblocks) {
-        const uint32_t ci = (uint32_t)plane * a.cap_cdesc + cslot;
+        const uint32_t ci = (uint32_t)plane * a.cap_cdesc + (a.pass == 3 ? a.cap_cdesc - 1u - cslot : cslot);
         const ContourDesc cd = a.cdesc[ci];
         if (cd.n <= 0) continue;
         if (a.dual && cd.n <= DUAL_MAX) {
@@ -1348,7 +1363,57 @@ __global__ __launch_bounds__(64) void contour_quad_kernel(QuadArgs a) {
     }
 }
 
-void launch_contour_quads(hipStream_t s, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b, int pass) {
+__global__ __launch_bounds__(64) void contour_quad_kernel(QuadArgs a) {
+    throughput_bound_priority();
+    __shared__ __align__(16) short2 Plds[QP_LDS];   // contour points (two borders of up to DUAL_MAX points, or one of up to QP_LDS)
+    __shared__ uint32_t rows[TB_ROWS * EMIT_LANES];  // one 32x32-pixel block per emitting lane
+    __shared__ int s_stack[2][16][2];
+    __shared__ short2 s_out[2][12];
+    __shared__ int s_outn;
+    static_assert(QP_LDS >= 2 * DUAL_MAX && EMIT_LANES == 64, "the two-borders-per-wave path uses the whole point buffer and a block per lane");
+    quad_blocks(a, blockIdx.x, Plds, rows, s_stack, s_out, s_outn);
+}
+
+// A pipeline lane's late walks and contour_quad's pass over the borders known when the launch starts, in ONE launch (launch_late_quads): one stream
+// cannot overlap two launches, one launch can hold both kinds of workgroups. The first 2 * w.gen_blocks workgroups - dispatched first, so the chain of
+// dependent border steps starts at once - take generation GEN_FORK_AFTER + 1's lists and walk every walk to its end (walk_generation<FINISH>); the others
+// are contour_quad_kernel's workgroups of pass 0. 2 * gen_blocks is a multiple of 8, so both roles keep their workgroup -> XCD mapping. The walker's
+// per-lane blocks are the array the quad role emits points from: no LDS beyond contour_quad_kernel's, whose residency bounds the stage.
+struct LateQuadArgs {
+    WalkArgs w;
+    QuadArgs q;
+};
+__global__ __launch_bounds__(64) void late_quad_kernel(LateQuadArgs a) {
+    __shared__ __align__(16) short2 Plds[QP_LDS];
+    __shared__ uint32_t rows[TB_ROWS * EMIT_LANES];   // walker role: one 32x32-pixel block per walking lane
+    __shared__ int s_stack[2][16][2];
+    __shared__ short2 s_out[2][12];
+    __shared__ int s_outn;
+    static_assert(EMIT_LANES == 64, "the late walks use the quad role's blocks: one per lane");
+    const int nwalk = 2 * a.w.gen_blocks;
+    if ((int)blockIdx.x < nwalk) {
+        latency_bound_priority();   // the priority is a wave's own: each role sets its kernel's
+        if ((int)blockIdx.x < a.w.gen_blocks)
+            walk_generation<false, true>(a.w, blockIdx.x, rows);
+        else
+            walk_generation<true, true>(a.w, blockIdx.x - a.w.gen_blocks, rows);
+        return;
+    }
+    throughput_bound_priority();
+    quad_blocks(a.q, (int)blockIdx.x - nwalk, Plds, rows, s_stack, s_out, s_outn);
+}
+
+// workgroups per plane of contour_quad's passes 0 and 1
+static int quad_blocks_per_plane(int nplanes) {
+    // workgroups per plane of a batch. One border per wave (rounds 1-3): 8: 0.93 ms, 16: 0.68, 24: 0.60, 32: 0.72 -> 24. Two borders per wave
+    // (round 4): a workgroup needs an even number of short borders to pair them all, so fewer, longer lists: 24 / 16 / 12 = 467.7k / 471.1k /
+    // 480.0k frames/s (flat stream), 273.1k / 276.2k / 276.2k (cluttered), same box
+    constexpr int kBlocks = 12;
+    // a handful of planes (one detect() per frame): a wave per kept border instead of a few waves that take the borders one after the other
+    return nplanes <= 2 ? 128 : nplanes <= 8 ? 48 : kBlocks;
+}
+
+static QuadArgs quad_args(const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b, int pass) {
     QuadArgs a;
     a.pass = pass;
     a.tiles = b.tiles, a.tnx = tiles_x(g.width), a.tny = tiles_y(g.height), a.from_pool = b.seg_mode, a.cdesc = b.cdesc, a.pool = b.pool, a.quads = b.quads, a.counters = b.counters;
@@ -1356,15 +1421,34 @@ void launch_contour_quads(hipStream_t s, const FrameGeom& g, int nframes, const 
     a.trig_cnt = b.trig_cnt, a.walk_scratch = b.walk_scratch;
     a.nplanes = nframes * p.nthr;
     a.dual = b.env.quad_dual && a.nplanes > 8;   // a single frame has a wave per kept border anyway: all 64 lanes on one border are faster there
-    // workgroups per plane of a batch. One border per wave (rounds 1-3): 8: 0.93 ms, 16: 0.68, 24: 0.60, 32: 0.72 -> 24. Two borders per wave
-    // (round 4): a workgroup needs an even number of short borders to pair them all, so fewer, longer lists: 24 / 16 / 12 = 467.7k / 471.1k /
-    // 480.0k frames/s (flat stream), 273.1k / 276.2k / 276.2k (cluttered), same box
-    constexpr int kBlocks = 12;
-    // a handful of planes (one detect() per frame): a wave per kept border instead of a few waves that take the borders one after the other
-    const int qb = a.nplanes <= 2 ? 128 : a.nplanes <= 8 ? 48 : kBlocks;
+    const int qb = quad_blocks_per_plane(a.nplanes);
+    // pass 3: the late borders, each of more than 960 points (one border per wave, never a pair) and 100-200 us of one wave's time. The bench's
+    // frames keep a handful per plane, a 4K board frame dozens (every marker's own borders): 4 workgroups per plane cost config 4 2.4 % against
+    // the parent, whose single pass took them 12 at a time (profiles/late_walks_fused_ab.txt), so pass 3 keeps pass 0's grid; a workgroup whose
+    // share of the late list is empty exits at once
     a.qblocks = pass == 2 ? std::max(1, qb / 2) : qb;
+    return a;
+}
+
+void launch_contour_quads(hipStream_t s, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b, int pass) {
+    const QuadArgs a = quad_args(g, nframes, p, b, pass);
     const int planes8 = ((a.nplanes + 7) / 8) * 8;
     hipLaunchKernelGGL(contour_quad_kernel, dim3(planes8 * a.qblocks), dim3(64), 0, s, a);
+}
+
+// behind launch_walkers' WALKS_LATE: the late walks beside contour_quad's pass over the early borders (late_quad_kernel), then the small pass over the
+// borders the late walks kept
+void launch_late_quads(hipStream_t s, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b) {
+    LateQuadArgs a;
+    a.w = walk_args(g, nframes * p.nthr, p, b);
+    a.w.gen = GEN_FORK_AFTER + 1, a.w.gen_steps = p.max_contour;
+    int before = a.w.leash;
+    for (int gen = 1; gen <= GEN_FORK_AFTER; gen++) before += gen_steps_of(gen, p);
+    a.w.gen_blocks = gen_blocks_of(a.w.nplanes, before);   // what generation GEN_FORK_AFTER + 1 gets as a launch of its own
+    a.q = quad_args(g, nframes, p, b, 0);
+    const int planes8 = ((a.q.nplanes + 7) / 8) * 8;
+    hipLaunchKernelGGL(late_quad_kernel, dim3(2 * a.w.gen_blocks + planes8 * a.q.qblocks), dim3(64), 0, s, a);
+    launch_contour_quads(s, g, nframes, p, b, 3);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -11,4 +11,5 @@ timeout -k 10 400 rocprofv3 --kernel-trace --kernel-include-regex "ah::" --outpu
 cp /tmp/p_ov/*/*kernel_trace.csv $OUT/kernel_trace.csv
 python3 tools/overlap_summarize.py $OUT/kernel_trace.csv | tee $OUT/summary.txt
 python3 tools/fork_gap_summarize.py $OUT/kernel_trace.csv | tee $OUT/fork_gaps.txt   # the walker fork's event hops and the in-stream gaps
+python3 tools/late_span_summarize.py $OUT/kernel_trace.csv | tee $OUT/late_span.txt   # the late walker generations of a lane and what runs beside them
 rm -f $OUT/kernel_trace.csv
