@@ -124,7 +124,7 @@ struct arucohip_handle {
     int32_t* h_n = nullptr;
     uint32_t* h_counters = nullptr;
     // small device scratch for the stage-level calls
-    float* d_small_f = nullptr;       // 4096 floats
+    float* d_small_f = nullptr;       // 8192 floats
     double* d_small_d = nullptr;      // 64 doubles
     int* d_small_i = nullptr;
     uint8_t* d_patch = nullptr;       // MAX_WARP^2

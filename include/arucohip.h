@@ -367,7 +367,8 @@ int arucohip_debug_hrm_counters(arucohip_handle* h, int32_t out[4]);
 
 /* BoardDetector::detect (boarddetector.h:103-108). markers: output of arucohip_detect; ids/obj: BoardConfiguration
  * (board.h:56-69) as nboard ids and nboard*4*3 floats; returns likelihood in *prob (found / total).
- * out_markers (cap n) receives the board's member markers (Board : vector<Marker>). */
+ * out_markers (cap n) receives the board's member markers (Board : vector<Marker>). Up to 1168 correspondences (292 member
+ * markers) are solved; more give ARUCOHIP_E_CAPACITY. */
 int arucohip_board_detect(arucohip_handle* h, const arucohip_marker_t* markers, int n, const int32_t* ids, const float* obj,
                           int nboard, int info_type, const float* K, const float* dist, int ndist, float marker_size,
                           float repj_err_thres, int y_perpendicular, arucohip_marker_t* out_markers, arucohip_board_t* out,
