@@ -1143,7 +1143,12 @@ __device__ __forceinline__ void border_to_quad(const QuadArgs& a, const ContourD
     }
     __syncthreads();
     while (top > 0) {
-        if (outn + top > 8) {  // cannot end as 4 vertices (clean-up removes at most every other vertex)
+        // outn + top never falls and ends as the vertex count, so this refuses the borders that approxPolyDP's recursion leaves with more than 8
+        // vertices. That none of them ends as 4 is EMPIRICAL and thinly supported: the clean-up pass can take five vertices off nine (it steps over the
+        // one behind every removal). A seeded search (tests/quad_ref.py search_early_reject) drew 12711 shapes, of which only 57 borders had
+        // more than 8 vertices here (9 or 10, never more), and none of those ended as a quad; borders of 7 and 8 vertices do end as quads.
+        // tests/test_gpu_quad_edges.py pins quads kept at 7 and 8 against shapes refused at 8, 9 and more.
+        if (outn + top > 8) {
             reject = true;
             break;
         }
@@ -1274,7 +1279,7 @@ __device__ __forceinline__ void border_pair_to_quads(const QuadArgs& a, const Co
     __syncthreads();
     for (;;) {
         bool act = !reject && top > 0;
-        if (act && outn + top > 8) reject = true, act = false;   // cannot end as 4 vertices (clean-up removes at most every other vertex)
+        if (act && outn + top > 8) reject = true, act = false;   // more than 8 vertices: see border_to_quad (empirical)
         if (!__any(act)) break;
         int sl_start = 0, sl_end = 0, len = 0;
         short2 ep = make_short2(0, 0), sp = make_short2(0, 0);

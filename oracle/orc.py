@@ -197,6 +197,11 @@ def approx_poly(pts, eps, inner_product_rule=1, cap=4096):
     return out[:n].copy()
 
 
+def is_contour_convex(poly):
+    p = np.ascontiguousarray(poly, dtype=np.int32)
+    return bool(lib().orc_is_convex(p.ctypes.data_as(C.c_void_p), len(p)))
+
+
 def warp(gray, quad, size=56):
     g, gp = _u8(gray)
     h, w = g.shape
