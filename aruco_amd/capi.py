@@ -112,6 +112,7 @@ SYMBOLS = [
     "arucohip_fiducial_board_size", "arucohip_fiducial_board_image", "arucohip_board_pix_to_meters", "arucohip_fiducial_distances",
     "arucohip_fiducial_select",
     "arucohip_draw_markers_batch", "arucohip_draw_boards_batch",
+    "arucohip_set_pyr_down", "arucohip_get_pyr_down", "arucohip_pyr_down",
 ]
 
 _lib = None
@@ -215,6 +216,9 @@ def load():
     L.arucohip_bgr_to_gray.argtypes = [vp, vp, i, i, sz, vp]
     L.arucohip_set_dictionary.argtypes = [vp, i, i, vp, i, f]
     L.arucohip_undistort.argtypes = [vp, vp, i, i, i, sz, sz, i, i, vp, vp, i, vp, i]
+    L.arucohip_set_pyr_down.argtypes = [vp, i]
+    L.arucohip_get_pyr_down.argtypes = [vp]
+    L.arucohip_pyr_down.argtypes = [vp, vp, i, i, i, sz, sz, i, i, vp, i]
     L.arucohip_gl_modelview.argtypes = [vp, vp, vp]
     L.arucohip_gl_modelview_n.argtypes = [vp, i, vp]
     L.arucohip_gl_modelview_batch.argtypes = [vp, i, i, vp, vp]
@@ -450,6 +454,34 @@ class Handle:
         self._chk(self.L.arucohip_undistort(self.h, _ptr(a), n, wid, hgt, wid * cn, wid * hgt * cn, cn, 0, _ptr(Ka), _ptr(da),
                                             0 if da is None else da.size, _ptr(out), 0))
         return out
+
+    def set_pyr_down(self, level):
+        """MarkerDetector::pyrDown(level): threshold, contours and quads on the frame reduced `level` times (0..3), the rest on the frame."""
+        self._chk(self.L.arucohip_set_pyr_down(self.h, int(level)))
+
+    @property
+    def pyr_down(self):
+        return self.L.arucohip_get_pyr_down(self.h)
+
+    def pyr_down_image(self, frames, levels=1):
+        """cv::pyrDown, `levels` times, of host frames [H][W] or [N][H][W] -> [Ho][Wo] or [N][Ho][Wo]."""
+        a = np.ascontiguousarray(frames, dtype=np.uint8)
+        one = a.ndim == 2
+        if one:
+            a = a[None]
+        n, hgt, wid = a.shape
+        wo, ho = wid, hgt
+        for _ in range(int(levels)):
+            wo, ho = (wo + 1) // 2, (ho + 1) // 2
+        out = np.empty((n, ho, wo), np.uint8)
+        self._chk(self.L.arucohip_pyr_down(self.h, _ptr(a), n, wid, hgt, wid, wid * hgt, 0, int(levels), _ptr(out), 0))
+        return out[0] if one else out
+
+    def pyr_down_device(self, src_ptr, nframes, width, height, levels, dst_ptr, row_stride=None, frame_stride=None):
+        """arucohip_pyr_down on device frames (plain integer pointers), the result left on the device, tightly packed."""
+        rs = width if row_stride is None else row_stride
+        fs = rs * height if frame_stride is None else frame_stride
+        self._chk(self.L.arucohip_pyr_down(self.h, C.c_void_p(src_ptr), nframes, width, height, rs, fs, 1, int(levels), C.c_void_p(dst_ptr), 1))
 
     def refine_candidate_lines(self, contour, corners, K=None, dist=None):
         """MarkerDetector::refineCandidateLines: contour = n x 2 integer points, corners = 4 x 2; returns the refined corners (4 x 2)."""

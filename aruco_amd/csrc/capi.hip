@@ -192,6 +192,7 @@ static int load_dictionary(arucohip_handle* h, arucohip_handle* w, const Diction
 static int inherit(arucohip_handle* parent, arucohip_handle* child) {
     return for_each_worker(child, [&](arucohip_handle* w) {
         w->params = parent->params;
+        w->pyr = parent->pyr;
         w->decoder_fn = parent->decoder_fn, w->decoder_user = parent->decoder_user;
         w->timing = parent->timing;
         arm_stamps(w, parent->buf.thr_stamp_on != 0);
@@ -488,9 +489,11 @@ int arucohip_kernel_times(arucohip_handle* h, float* ms, int cap) {
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------
-static int make_detect_params(arucohip_handle* h, int W, int H, DetectParams* dp) {
+// level: the pyramid level the rectangle stage runs at (detection: the handle's; the stage entry points work on the image they are given: 0)
+static int make_detect_params(arucohip_handle* h, int W, int H, DetectParams* dp, int level = 0) {
     const arucohip_params_t& p = h->params;
     std::memset(dp, 0, sizeof(*dp));
+    dp->pyr = level;
     dp->thres_method = p.thres_method;
     dp->nthr = 2 * p.thres_param1_range + 1;
     if (dp->nthr > h->lim.max_thres_planes) return fail(h, ARUCOHIP_E_INVALID, "threshold range exceeds handle planes");
@@ -510,8 +513,12 @@ static int make_detect_params(arucohip_handle* h, int W, int H, DetectParams* dp
     dp->idelta = (int)std::floor(p.thres_param2);
     dp->corner_method = p.corner_method;
     dp->warp_size = p.warp_size;
-    dp->min_contour = (int)(p.min_size * std::max(W, H) * 4);   // :500-501, float arithmetic
-    dp->max_contour = (int)(p.max_size * std::max(W, H) * 4);
+    // the contour bounds come from the image the contours are found on (the reference measured thres.cols / rows), the border filter
+    // below from the frame
+    int Wr = W, Hr = H;
+    for (int l = 0; l < level; l++) Wr = (Wr + 1) / 2, Hr = (Hr + 1) / 2;
+    dp->min_contour = (int)(p.min_size * std::max(Wr, Hr) * 4);   // :500-501, float arithmetic
+    dp->max_contour = (int)(p.max_size * std::max(Wr, Hr) * 4);
     if (dp->max_contour > 16383) dp->max_contour = 16383;       // offsets inside a border are 14-bit fields
     // :433-434 Rect(Point(size)*t, Point(size)*(1-t)) with cvRound
     int x1 = (int)lrintf((float)W * p.border_dist), y1 = (int)lrintf((float)H * p.border_dist);
@@ -576,12 +583,54 @@ static int ensure_walk_scratch(arucohip_handle* h, int nplanes, const DetectPara
     return ARUCOHIP_OK;
 }
 
+// The pyramid of a batch: level l (1 .. levels) is w[l] x h[l]; the levels below the last one have rows padded to 8 bytes (pyr_down_kernel's
+// 8-byte loads) and alternate between the two halves of d_pyr, the last one is tightly packed, in d_pyr or where the caller wants it.
+struct PyrPlan {
+    int levels = 0;
+    int w[4] = {}, h[4] = {};
+    size_t row[4] = {}, frame[4] = {}, off[4] = {};   // off: byte offset of level l in d_pyr
+    size_t bytes = 0;
+    FrameGeom reduced() const { return FrameGeom{w[levels], h[levels], row[levels], frame[levels]}; }
+};
+static PyrPlan plan_pyramid(const FrameGeom& g, int nframes, int levels) {
+    PyrPlan p;
+    p.levels = levels, p.w[0] = g.width, p.h[0] = g.height;
+    size_t half[2] = {0, 0};
+    for (int l = 1; l <= levels; l++) {
+        p.w[l] = (p.w[l - 1] + 1) / 2, p.h[l] = (p.h[l - 1] + 1) / 2;
+        p.row[l] = l == levels ? (size_t)p.w[l] : ((size_t)p.w[l] + 7) & ~(size_t)7;
+        p.frame[l] = l == levels ? p.row[l] * p.h[l] : (p.row[l] * p.h[l] + 7) & ~(size_t)7;
+        half[l & 1] = std::max(half[l & 1], ((size_t)nframes * p.frame[l] + 255) & ~(size_t)255);
+    }
+    for (int l = 1; l <= levels; l++) p.off[l] = (l & 1) ? 0 : half[1];
+    p.bytes = half[0] + half[1];
+    return p;
+}
+// level after level on stream s; the last one goes to `last` (the caller's device memory) or, when null, to its place in d_pyr (reserved by the caller)
+static const uint8_t* run_pyramid(arucohip_handle* h, hipStream_t s, const uint8_t* src, const FrameGeom& g, int nframes, const PyrPlan& p, uint8_t* last) {
+    const uint8_t* from = src;
+    size_t row = g.row_stride, frame = g.frame_stride;
+    for (int l = 1; l <= p.levels; l++) {
+        uint8_t* to = (l == p.levels && last) ? last : h->d_pyr + p.off[l];
+        launch_pyr_down(s, from, row, frame, p.w[l - 1], p.h[l - 1], nframes, to, p.row[l], p.frame[l]);
+        from = to, row = p.row[l], frame = p.frame[l];
+    }
+    return from;
+}
+
 // Host-side work in front of a batch's enqueued work (detect_core), which a captured graph does not repeat: the eager path and every graph
-// replay run it first. In steady state it only compares integers.
+// replay run it first. In steady state it only compares integers. g: the frames; with a pyramid level the walk scratch and the bit tiles are
+// sized for the reduced image, which is also reserved here.
 static int batch_prologue(arucohip_handle* h, const FrameGeom& g, int nframes, const DetectParams& dp) {
     int rc;
     if ((rc = ensure_walk_scratch(h, nframes * dp.nthr, dp))) return rc;
-    if ((rc = ensure_bits_geometry(h, g.width, g.height))) return rc;
+    FrameGeom gr = g;
+    if (dp.pyr > 0) {
+        const PyrPlan pp = plan_pyramid(g, nframes, dp.pyr);
+        HIPCHK(h, h->d_pyr.reserve(pp.bytes));
+        gr = pp.reduced();
+    }
+    if ((rc = ensure_bits_geometry(h, gr.width, gr.height))) return rc;
     // canonical patches of the decode stage: cap_flat * warp_size^2 bytes, for the configurations whose kernels store and read them
     if (!decode_from_cells(g, nframes, dp)) {
         HIPCHK(h, h->patches.reserve((size_t)h->buf.cap_flat * dp.warp_size * dp.warp_size));
@@ -689,14 +738,24 @@ static int run_threshold(arucohip_handle* h, hipStream_t s, const uint8_t* gray_
     return ARUCOHIP_OK;
 }
 
-static int detect_core(arucohip_handle* h, const uint8_t* gray_dev, const FrameGeom& g, int nframes, const DetectParams& dp, const CamModel& cam) {
+// gf: the frames at gray_dev. With a pyramid level (dp.pyr > 0) threshold, erosion and the rectangle stage work on the reduced frames (gr, in
+// d_pyr, reserved by batch_prologue); what they found is lifted to full-frame coordinates, and decoding, corner refinement and the border filter
+// work on the frames themselves.
+static int detect_core(arucohip_handle* h, const uint8_t* gray_dev, const FrameGeom& gf, int nframes, const DetectParams& dp, const CamModel& cam) {
     hipStream_t s = h->stream;
     Buffers& b = h->buf;
     HIPCHK(h, hipMemsetAsync(h->zero_block, 0, h->zero_words * sizeof(uint32_t), s));
     hipEvent_t* ev = h->timing ? h->ev[h->tsets % TSETS] : nullptr;
     MARK(K_THRESHOLD);
+    FrameGeom g = gf;   // of the rectangle stage
+    const uint8_t* small_dev = gray_dev;
+    if (dp.pyr > 0) {
+        const PyrPlan pp = plan_pyramid(gf, nframes, dp.pyr);
+        small_dev = run_pyramid(h, s, gray_dev, gf, nframes, pp, nullptr);
+        g = pp.reduced();
+    }
     {
-        const int rc_ = run_threshold(h, s, gray_dev, g, nframes, dp, false);
+        const int rc_ = run_threshold(h, s, small_dev, g, nframes, dp, false);
         if (rc_) return rc_;
     }
     if (h->params.erode) {
@@ -713,25 +772,26 @@ static int detect_core(arucohip_handle* h, const uint8_t* gray_dev, const FrameG
         const int rc_ = run_rectangles(h, s, g, nframes, dp, ev);
         if (rc_) return rc_;
     }
+    if (dp.pyr > 0) launch_lift(s, nframes, dp, b);
     MARK(K_DECODE);
     // built-in 5x5 decoder: a batch decodes from cell medians inside launch_decode; on a stored patch (one frame per call, other warp sizes) the cell
     // votes and the Hamming decode of a candidate are the head of its refinement wave (one dispatch less)
-    h->cells_valid = decode_from_cells(g, nframes, dp);
+    h->cells_valid = decode_from_cells(gf, nframes, dp);
     const bool fused_cells = dp.decoder == ARUCOHIP_DECODER_FIDUCIAL_5X5 && !h->cells_valid;
-    if (RUN_STAGE(b.env, 6)) launch_decode(s, gray_dev, g, nframes, dp, b, fused_cells);
+    if (RUN_STAGE(b.env, 6)) launch_decode(s, gray_dev, gf, nframes, dp, b, fused_cells);
     if (dp.decoder == ARUCOHIP_DECODER_USER) {
         const int rc_ = user_decode_stage(h, dp);
         if (rc_) return rc_;
     }
     MARK(K_REFINE_LINES);
-    if (RUN_STAGE(b.env, 7)) launch_refine_lines(s, g, nframes, dp, cam, b, fused_cells);
+    if (RUN_STAGE(b.env, 7)) launch_refine_lines(s, gf, nframes, dp, cam, b, fused_cells);
     MARK(K_REFINE_PIXELS);
     if (dp.corner_method == ARUCOHIP_CORNER_HARRIS || dp.corner_method == ARUCOHIP_CORNER_SUBPIX) {
-        if (dp.locked) launch_locked_corners(s, gray_dev, g, nframes, dp, b);   // markerdetector.cpp:398-399
-        launch_refine_pixels(s, gray_dev, g, nframes, dp, b);
+        if (dp.locked) launch_locked_corners(s, gray_dev, gf, nframes, dp, b);   // markerdetector.cpp:398-399
+        launch_refine_pixels(s, gray_dev, gf, nframes, dp, b);
     }
     MARK(K_FINALIZE);
-    if (RUN_STAGE(b.env, 8)) launch_finalize(s, g, nframes, dp, cam, b, h->wt_out, h->wt_cap, h->wt_n);
+    if (RUN_STAGE(b.env, 8)) launch_finalize(s, gf, nframes, dp, cam, b, h->wt_out, h->wt_cap, h->wt_n);
     MARK(K_POSE);
     if (RUN_STAGE(b.env, 8) && cam.has_K && cam.marker_size > 0) launch_pose(s, nframes, cam, b);
     MARK(K_COUNT);
@@ -878,7 +938,7 @@ static uint64_t digest(uint64_t hsh, const void* p, size_t n) {
 static int detect_one_graphed(arucohip_handle* h, const uint8_t* frame, int W, int H, size_t row_stride, int channels, const DetectParams& dp, const CamModel& cam,
                               arucohip_marker_t* out, int cap, int32_t* n_out, bool* handled) {
     *handled = false;
-    if (h->fgraph.disabled || h->timing || dp.decoder == ARUCOHIP_DECODER_USER || dp.thres_method == ARUCOHIP_THRES_CANNY || h->params.erode) return ARUCOHIP_OK;
+    if (h->fgraph.disabled || h->timing || dp.decoder == ARUCOHIP_DECODER_USER || dp.thres_method == ARUCOHIP_THRES_CANNY || h->params.erode || dp.pyr > 0) return ARUCOHIP_OK;
     uint64_t key = 1469598103934665603ull;
     const int geo[5] = {W, H, channels, (int)h->buf.seg_mode, h->buf.thr_stamp_on};
     key = digest(key, geo, sizeof(geo));
@@ -950,7 +1010,7 @@ static int detect_batch_impl(arucohip_handle* h, const uint8_t* frames, int nfra
     HIPCHK(h, hipSetDevice(h->device));
     DetectParams dp;
     CamModel cam;
-    if ((rc = make_detect_params(h, W, H, &dp))) return rc;
+    if ((rc = make_detect_params(h, W, H, &dp, h->pyr))) return rc;
     if ((rc = make_cam(h, K, dist, ndist, marker_size, y_perp, &cam))) return rc;
     if (nframes == 1 && !frames_on_device && !out_on_device && !defer && h->nsub == 1) {
         bool handled = false;
@@ -958,6 +1018,7 @@ static int detect_batch_impl(arucohip_handle* h, const uint8_t* frames, int nfra
         if (handled) return rc;
     }
     h->last = plan_batch(h, nframes, W, H, dp.nthr);
+    for (int l = 0; l < dp.pyr; l++) h->last.W = (h->last.W + 1) / 2, h->last.H = (h->last.H + 1) / 2;   // of the thresholded image
     const Batch& plan = h->last;
     if ((rc = fork_workers(h, plan))) return rc;
     for (int c = 0; c < plan.nspan; c++) {
@@ -1058,6 +1119,41 @@ int arucohip_undistort(arucohip_handle* h, const uint8_t* src, int nframes, int 
     HIPCHK(h, hipGetLastError());
     if (!dst_on_device) {
         HIPCHK(h, hipMemcpyAsync(dst, ddev, (size_t)nframes * fbytes, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+    }
+    return ARUCOHIP_OK;
+}
+
+// MarkerDetector::pyrDown(level): the level is a property of the whole tree of workers, like the parameters
+int arucohip_set_pyr_down(arucohip_handle* h, int level) {
+    if (!h) return ARUCOHIP_E_INVALID;
+    if (level < 0 || level > 3) return fail(h, ARUCOHIP_E_INVALID, "pyrDown: level outside 0..3");
+    for (auto* l : h->lanes)
+        if (l->pend.active) return fail(h, ARUCOHIP_E_INVALID, "a submitted batch has not been waited for");
+    for_each_worker(h, [&](arucohip_handle* w) { w->pyr = level; return ARUCOHIP_OK; });
+    drop_retry(h);
+    return ARUCOHIP_OK;
+}
+
+int arucohip_get_pyr_down(const arucohip_handle* h) { return h ? h->pyr : 0; }
+
+int arucohip_pyr_down(arucohip_handle* h, const uint8_t* src, int nframes, int W, int H, size_t row_stride, size_t frame_stride, int src_on_device,
+                      int levels, uint8_t* dst, int dst_on_device) {
+    if (!h || !src || !dst) return ARUCOHIP_E_INVALID;
+    if (levels < 1 || levels > 3) return fail(h, ARUCOHIP_E_INVALID, "pyr_down: levels outside 1..3");
+    int rc = check_geometry(h, nframes, W, H, row_stride);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const uint8_t* sdev;
+    FrameGeom g;
+    if ((rc = stage_frames(h, src, nframes, W, H, row_stride, frame_stride, src_on_device, 1, &sdev, &g))) return rc;
+    const PyrPlan pp = plan_pyramid(g, nframes, levels);
+    HIPCHK(h, h->d_pyr.reserve(pp.bytes));
+    const uint8_t* out = run_pyramid(h, s, sdev, g, nframes, pp, dst_on_device ? dst : nullptr);
+    HIPCHK(h, hipGetLastError());
+    if (!dst_on_device) {
+        HIPCHK(h, hipMemcpyAsync(dst, out, (size_t)nframes * pp.frame[levels], hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipStreamSynchronize(s));
     }
     return ARUCOHIP_OK;

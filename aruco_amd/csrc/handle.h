@@ -103,6 +103,8 @@ struct arucohip_handle {
     int wt_cap = 0;
     Mem<uint8_t> d_erode;             // eroded planes (params.erode)
     Mem<uint64_t> d_canny;            // CANNY: survivor tiles, edge tiles, changed flag
+    int pyr = 0;                      // MarkerDetector::pyrDown level (arucohip_set_pyr_down), the same on every worker of the tree
+    Mem<uint8_t> d_pyr;               // the reduced frames of a level above 0: two halves, the levels go to and fro between them (PyrPlan)
     // frame undistortion (arucohip_undistort): the map of the last camera is kept (umap_nd = -1: none)
     Mem<short2> d_umap_xy;
     Mem<uint16_t> d_umap_f;
@@ -168,7 +170,7 @@ struct arucohip_handle {
     //   ONE frame, which always stores its patches (decode_from_cells is false below three frames), so batch_prologue reserves them before every
     //   capture and replay; batches that decode from cell medians neither touch nor move buf.patches, and buf.cells is create-time memory;
     // - neither: the other Buffers arrays, zero_block and h_markers are create-time memory (`held`); d_erode, d_canny and the user decoder's
-    //   staging belong to configurations that are not graphed; wt_out is set only inside chunk_enqueue, which does not run this path.
+    //   staging and d_pyr belong to configurations that are not graphed; wt_out is set only inside chunk_enqueue, which does not run this path.
     //   Memory no captured launch reads (d_bgr, undistortion, calibration, board and GL batches, planar poses, overlays, EM, HRM, fiducial generation and ChromaticMask scratch) may
     //   be replaced at any time.
     struct FrameGraph {

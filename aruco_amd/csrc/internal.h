@@ -113,6 +113,7 @@ struct DetectParams {
     int hrm_n, hrm_count;
     uint32_t hrm_correction;        // largest Hamming distance that is still corrected
     const uint64_t* hrm_codes;      // device
+    int pyr;                        // MarkerDetector::pyrDown level: threshold, contours and quads run on the frame reduced pyr times (0: on the frame itself)
 };
 
 // Environment switches (INTEGRATION.md "Environment knobs"). read_env() (capi.hip) reads them once, when the caller creates a handle;
@@ -209,6 +210,9 @@ __device__ __forceinline__ void throughput_bound_priority() { if (LBP_PRIO_HEAVY
 
 // ---- kernel launchers (host side, defined in the .hip files)
 void launch_bgr2gray(hipStream_t s, const uint8_t* bgr, size_t row_stride, size_t frame_stride, int width, int height, int nframes, uint8_t* gray);
+// cv::pyrDown of nframes 8-bit frames (k_pyrdown.hip): W x H at src_row / src_frame -> (W + 1) / 2 x (H + 1) / 2 at dst_row / dst_frame
+void launch_pyr_down(hipStream_t s, const uint8_t* src, size_t src_row, size_t src_frame, int W, int H, int nframes, uint8_t* dst, size_t dst_row,
+                     size_t dst_frame);
 bool launch_threshold(hipStream_t s, const uint8_t* gray, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b, bool lazy);
 void launch_expand_thres(hipStream_t s, const FrameGeom& g, int plane, const Buffers& b);
 void launch_undist_map(hipStream_t s, int W, int H, const float* K, const float* dist, int ndist, short2* xy, uint16_t* fxy);
@@ -239,6 +243,8 @@ void launch_segments(hipStream_t s, const FrameGeom& g, int nplanes, const Detec
 void launch_contour_quads(hipStream_t s, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b, int pass = 0);
 void launch_late_quads(hipStream_t s, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b);   // behind WALKS_LATE: late walks + every quad pass
 void launch_frame_candidates(hipStream_t s, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b);
+// p.pyr > 0, behind launch_frame_candidates: kept borders (points, start pixels) and candidates (integer quads, corners) times 1 << p.pyr, in place
+void launch_lift(hipStream_t s, int nframes, const DetectParams& p, const Buffers& b);
 // warp + histogram, Otsu threshold, id / rotation of every candidate (left in Cand; the caller's decoder: warp only). decode_from_cells: the batch
 // takes the variant that keeps 49 cell medians per candidate instead of the stored patch and decodes in otsu_kernel (k_decode.hip).
 // fused_cells: the built-in 5x5 decoder on a stored patch runs as the head of refine_lines_kernel (launch_refine_lines with the same flag) instead of

@@ -1461,6 +1461,8 @@ void launch_late_quads(hipStream_t s, const FrameGeom& g, int nframes, const Det
 // ---------------------------------------------------------------------------------------------
 struct FrameArgs {
     double* iM;           // [cap_flat][9] inverse homographies of the flat candidate list (round 3: solved here, one candidate per lane)
+    int lift;             // pyramid level of the image the quads were found on: the homographies are those of the quads times 1 << lift, which the
+                          // decode stage warps from the full frame (the candidates themselves are scaled by lift_contours_kernel, k_pyrdown.hip)
     int ws;               // patch size of MarkerDetector::warp
     const Quad* quads;
     Cand* cands;
@@ -1588,7 +1590,7 @@ __global__ __launch_bounds__(64) void frame_candidates_kernel(FrameArgs a) {
         const int k = r * WAVE + lane;
         if (k < n) {
             const int i = s_map[k];
-            for (int c = 0; c < 4; c++) qx[r][c] = sx[i][c], qy[r][c] = sy[i][c];
+            for (int c = 0; c < 4; c++) qx[r][c] = (int16_t)(sx[i][c] << a.lift), qy[r][c] = (int16_t)(sy[i][c] << a.lift);
         } else {
             for (int c = 0; c < 4; c++) qx[r][c] = 0, qy[r][c] = 0;
         }
@@ -1612,7 +1614,7 @@ void launch_frame_candidates(hipStream_t s, const FrameGeom& g, int nframes, con
     a.quads = b.quads, a.cands = b.cands, a.ncands = b.ncands, a.counters = b.counters, a.trig_cnt = b.trig_cnt, a.nthr = p.nthr;
     a.cand_list = b.cand_list, a.cap_flat = b.cap_flat;
     a.cap_quads = b.cap_quads, a.cap_cands = b.cap_cands;
-    a.iM = b.iM, a.ws = p.warp_size;
+    a.iM = b.iM, a.ws = p.warp_size, a.lift = p.pyr;
     if (nframes <= 2)
         hipLaunchKernelGGL(frame_candidates_kernel<64>, dim3(nframes), dim3(64), 0, s, a);
     else

@@ -1133,9 +1133,18 @@ public:
         if (enable) p_.corner_method = SUBPIX;
         push_();
     }
-    const cv::Mat& getThresholdedImage() {  // markerdetector.h:183
+    // MarkerDetector::pyrDown(level) of ArUco 1.2 (this snapshot of the reference keeps the call as a no-op, PortingManual.md): threshold, contours
+    // and quads run on the frame reduced `level` times (0..3), everything else on the frame itself; arucohip_set_pyr_down
+    void pyrDown(unsigned int level) {
+        if (level > 3) arucohip_throw_(ARUCOHIP_E_INVALID, "pyrDown: level outside 0..3", nullptr);
+        if (h_) arucohip_throw_(arucohip_set_pyr_down(h_, (int)level), "pyrDown", h_);
+        pyr_ = (int)level;
+    }
+    const cv::Mat& getThresholdedImage() {  // markerdetector.h:183; with pyrDown(level) the reduced image
         if (!thres_valid_ && h_ && frame_size_.width > 0) {
-            thres_ = cv::Mat(frame_size_.height, frame_size_.width, CV_8UC1);
+            int tw = frame_size_.width, th = frame_size_.height;
+            for (int l = 0; l < arucohip_get_pyr_down(h_); l++) tw = (tw + 1) / 2, th = (th + 1) / 2;
+            thres_ = cv::Mat(th, tw, CV_8UC1);
             arucohip_throw_(arucohip_get_thresholded(h_, 0, thres_.data), "getThresholdedImage", h_);
             thres_valid_ = true;
         }
@@ -1277,6 +1286,7 @@ private:
         lim.candidates_per_frame = 512, lim.markers_per_frame = 256;
         arucohip_throw_(arucohip_create_ex(&p_, device_, &lim, &h_), "arucohip_create", nullptr);
         cap_w_ = w, cap_h_ = hh;
+        if (pyr_) arucohip_throw_(arucohip_set_pyr_down(h_, pyr_), "pyrDown", h_);
         hrm_version_ = -1;
         if (hrm_ || user_fn_) apply_decoder_();
     }
@@ -1309,6 +1319,7 @@ private:
     arucohip_handle* h_;
     int device_, cap_w_, cap_h_;
     int grow_ = 0;   // doublings of the device list limits after overflows
+    int pyr_ = 0;    // pyrDown level, set again on every handle ensure_ creates
     arucohip_params_t p_;
     int speed_ = 0;
     bool hrm_ = false;

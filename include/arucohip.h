@@ -278,6 +278,24 @@ int arucohip_bgr_to_gray(arucohip_handle* h, const uint8_t* bgr, int width, int 
  * and kept in the handle. */
 int arucohip_undistort(arucohip_handle* h, const uint8_t* src, int nframes, int width, int height, size_t row_stride, size_t frame_stride,
                        int channels, int src_on_device, const float* K, const float* dist, int ndist, uint8_t* dst, int dst_on_device);
+/* MarkerDetector::pyrDown(level) of ArUco 1.2 (this snapshot of the reference dropped it as a no-op, PortingManual.md): detect on a
+ * reduced image. With level > 0 every detection call of the handle reduces the gray frame `level` times (cv::pyrDown: 5x5 Gaussian,
+ * BORDER_REFLECT_101, half the size rounded up; BGR input reduces the converted gray image) and runs threshold, erosion, contours and
+ * quads on the reduced image; min / max contour length are measured on the reduced size. Corners and contour points are then multiplied
+ * by 2^level, and decoding (warp + Otsu), HARRIS / SUBPIX refinement, the border filter and the poses work on the full-resolution frame;
+ * LINES fits its lines to the scaled contour. From then on every getter (arucohip_get_candidates, arucohip_debug_contour,
+ * arucohip_debug_candidates) reports full-frame coordinates, while arucohip_get_thresholded returns the reduced image (the size of the
+ * last level, tightly packed). 0 <= level <= 3 (ARUCOHIP_E_INVALID otherwise, the level stays as it was); nothing may be in flight
+ * (arucohip_detect_batch_submit). Level 0, the default, is the path without the option, launch for launch. With a level above 0 a
+ * one-frame call takes the eager path: the reduced path is not captured in the frame graph. The level is a property of the handle beside
+ * arucohip_params_t (arucohip_get_params does not report it); a multi-GPU detector sets it per slot through arucohip_mgpu_handle. */
+int arucohip_set_pyr_down(arucohip_handle* h, int level);
+int arucohip_get_pyr_down(const arucohip_handle* h);
+/* The reduction as a stage of its own: nframes 8-bit gray frames, in host or device memory, reduced `levels` (1..3) times; dst is tightly
+ * packed (nframes x Ho x Wo of the last level, Wo = (W + 1) / 2 per level), in host or device memory; with dst_on_device the call is
+ * asynchronous on the handle's stream, like arucohip_undistort. */
+int arucohip_pyr_down(arucohip_handle* h, const uint8_t* src, int nframes, int width, int height, size_t row_stride, size_t frame_stride,
+                      int src_on_device, int levels, uint8_t* dst, int dst_on_device);
 /* After an asynchronous batch: synchronise and report device-side overflow / capacity conditions. */
 int arucohip_batch_status(arucohip_handle* h);
 /* Device lists are finite (arucohip_limits_t), the reference's vectors are not (src/markerdetector.cpp:496-635). When a list overflows
