@@ -59,6 +59,12 @@ class Overlay(C.Structure):
     _fields_ = [("flags", C.c_int32), ("line_width", C.c_int32), ("color", C.c_uint8 * 4)]
 
 
+class Recover(C.Structure):
+    """arucohip_recover_t: what board_recover_batch accepts (corner distance in pixels, differing cells of the 7 x 7 grid, board members a
+    frame must already hold) and whether the recovered markers get their own pose."""
+    _fields_ = [("max_corner_dist", C.c_float), ("max_cell_errors", C.c_int32), ("min_markers", C.c_int32), ("pose_markers", C.c_int32)]
+
+
 DRAW_OUTLINE, DRAW_IDS, DRAW_AXIS, DRAW_CUBE, DRAW_Y_PERPENDICULAR = 1, 2, 4, 8, 16
 BOARD_DTYPE = np.dtype([("n_markers", "<i4"), ("has_pose", "<i4"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,))])
 assert C.sizeof(Overlay) == 12 and BOARD_DTYPE.itemsize == 56
@@ -113,6 +119,7 @@ SYMBOLS = [
     "arucohip_fiducial_select",
     "arucohip_draw_markers_batch", "arucohip_draw_boards_batch",
     "arucohip_set_pyr_down", "arucohip_get_pyr_down", "arucohip_pyr_down",
+    "arucohip_default_recover", "arucohip_board_recover_batch",
 ]
 
 _lib = None
@@ -173,6 +180,9 @@ def load():
     L.arucohip_kernel_name.argtypes = [i]
     L.arucohip_debug_counters.argtypes = [vp, vp]
     L.arucohip_board_detect_batch.argtypes = [vp, i, vp, vp, i, i, vp, vp, i, f, f, i, vp, vp]
+    L.arucohip_default_recover.argtypes = [vp]
+    L.arucohip_default_recover.restype = None
+    L.arucohip_board_recover_batch.argtypes = [vp, i, vp, vp, i, i, vp, vp, i, f, f, i, vp, vp, i, vp, i, vp, vp, vp]
     L.arucohip_calibrate_camera.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp]
     L.arucohip_calibrate_board_batch.argtypes = [vp, i, vp, vp, i, i, f, i, i, i, i, vp, vp, vp, vp, vp, vp]
     L.arucohip_planar_poses.argtypes = [vp, vp, i, i, vp, vp, i, f, i, i, vp]
@@ -279,6 +289,12 @@ def default_params():
     p = Params()
     load().arucohip_default_params(C.byref(p))
     return p
+
+
+def default_recover():
+    o = Recover()
+    load().arucohip_default_recover(C.byref(o))
+    return o
 
 
 def _ptr(a):
@@ -821,6 +837,40 @@ class Handle:
                                                      int(bool(y_perp)), out, _ptr(prob)))
         return [{"n_markers": out[f].n_markers, "has_pose": out[f].has_pose, "rvec": np.array(out[f].rvec), "tvec": np.array(out[f].tvec),
                  "prob": float(prob[f])} for f in range(nframes)]
+
+    def board_recover_batch(self, nframes, ids, obj, info_type, K, dist=None, marker_size=-1.0, repj_err_thres=-1.0, y_perp=False, opt=None,
+                            cap=64, allow=()):
+        """arucohip_board_recover_batch on the last batch: the board's markers that the decoder rejected are taken back from the frames'
+        rejected candidates, in place. opt: a Recover (None: the defaults). Returns (markers per frame, counts, recovered per frame,
+        boards as board_detect_batch returns them); counts[f] = -1 for a frame the batch gave up. cap = 0: the marker lists are not
+        fetched (empty lists, counts None)."""
+        ida = np.ascontiguousarray(ids, dtype=np.int32)
+        oa = _f32(obj)
+        Ka, da = _f32(K), _f32(dist)
+        out = np.zeros((nframes, cap), MARKER_DTYPE)
+        n = np.zeros(nframes, np.int32)
+        rec = np.zeros(nframes, np.int32)
+        boards = (BoardOut * nframes)()
+        prob = np.zeros(nframes, np.float32)
+        self._chk(self.L.arucohip_board_recover_batch(self.h, int(nframes), _ptr(ida), _ptr(oa), len(ida), int(info_type), _ptr(Ka), _ptr(da),
+                                                      0 if da is None else da.size, float(marker_size), float(repj_err_thres), int(bool(y_perp)),
+                                                      None if opt is None else C.cast(C.byref(opt), C.c_void_p), _ptr(out) if cap else None, int(cap),
+                                                      _ptr(n) if cap else None, 0, _ptr(rec), boards, _ptr(prob)), allow=allow)
+        bl = [{"n_markers": boards[f].n_markers, "has_pose": boards[f].has_pose, "rvec": np.array(boards[f].rvec), "tvec": np.array(boards[f].tvec),
+               "prob": float(prob[f])} for f in range(nframes)]
+        return [out[f, :max(min(int(n[f]), cap), 0)].copy() for f in range(nframes)], n if cap else None, rec, bl
+
+    def board_recover_batch_device(self, nframes, ids, obj, info_type, out_ptr, cap, n_out_ptr, K, dist=None, marker_size=-1.0, repj_err_thres=-1.0,
+                                   y_perp=False, opt=None):
+        """board_recover_batch with the marker lists written to device arrays (arucohip_marker_t [nframes][cap], int32 [nframes], given as
+        pointers): asynchronous on the handle's stream, for a detect -> recover -> draw chain."""
+        ida = np.ascontiguousarray(ids, dtype=np.int32)
+        oa = _f32(obj)
+        Ka, da = _f32(K), _f32(dist)
+        self._chk(self.L.arucohip_board_recover_batch(self.h, int(nframes), _ptr(ida), _ptr(oa), len(ida), int(info_type), _ptr(Ka), _ptr(da),
+                                                      0 if da is None else da.size, float(marker_size), float(repj_err_thres), int(bool(y_perp)),
+                                                      None if opt is None else C.cast(C.byref(opt), C.c_void_p), C.c_void_p(out_ptr), int(cap),
+                                                      C.c_void_p(n_out_ptr), 1, None, None, None))
 
     @staticmethod
     def _calib_start(K, dist):

@@ -60,7 +60,7 @@ static Batch plan_batch(arucohip_handle* h, int nframes, int W, int H, int nthr)
     const int per = (nframes + chunks - 1) / chunks;
     chunks = (nframes + per - 1) / per;
     Batch b;
-    b.nspan = chunks, b.frames = nframes, b.W = W, b.H = H, b.nthr = nthr;
+    b.nspan = chunks, b.frames = nframes, b.W = W, b.H = H, b.nthr = nthr, b.frame_w = W, b.frame_h = H;
     for (int c = 0; c < chunks; c++) b.span[c] = {chunk_worker(h, c), c * per, std::min(per, nframes - c * per)};
     return b;
 }
@@ -520,11 +520,9 @@ static int make_detect_params(arucohip_handle* h, int W, int H, DetectParams* dp
     dp->min_contour = (int)(p.min_size * std::max(Wr, Hr) * 4);   // :500-501, float arithmetic
     dp->max_contour = (int)(p.max_size * std::max(Wr, Hr) * 4);
     if (dp->max_contour > 16383) dp->max_contour = 16383;       // offsets inside a border are 14-bit fields
-    // :433-434 Rect(Point(size)*t, Point(size)*(1-t)) with cvRound
-    int x1 = (int)lrintf((float)W * p.border_dist), y1 = (int)lrintf((float)H * p.border_dist);
-    int x2 = (int)lrintf((float)W * (1.0f - p.border_dist)), y2 = (int)lrintf((float)H * (1.0f - p.border_dist));
-    dp->bx0 = std::min(x1, x2), dp->by0 = std::min(y1, y2);
-    dp->bx1 = std::max(x1, x2), dp->by1 = std::max(y1, y2);
+    int rect[4];
+    border_rect(p.border_dist, W, H, rect);
+    dp->bx0 = rect[0], dp->by0 = rect[1], dp->bx1 = rect[2], dp->by1 = rect[3];
     dp->subpix_win = (int)p.thres_param1;
     dp->locked = p.use_locked_corners != 0, dp->locked_wsize = (int)p.thres_param1;   // findCornerMaxima(Corners, grey, _thresParam1)
     dp->decoder = p.decoder_kind;

@@ -1,0 +1,155 @@
+// Host side of the board marker recovery (k_recover.hip).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "handle.h"
+
+extern "C" {
+
+void arucohip_default_recover(arucohip_recover_t* o) {
+    if (!o) return;
+    o->max_corner_dist = 10.f, o->max_cell_errors = 3, o->min_markers = 2, o->pose_markers = 0;
+}
+
+// Byte offsets into a worker's d_recover for F frames of cap_markers markers and a board of nboard markers
+struct RecoverCarve {
+    size_t base, nrec, recovered, status, rec, rlist, plist, ids, obj, total;
+};
+static RecoverCarve recover_carve(int F, int cap_markers, int nboard) {
+    RecoverCarve c;
+    size_t at = 0;
+    auto take = [&](size_t bytes) {
+        const size_t here = at;
+        at += (bytes + 255) & ~(size_t)255;
+        return here;
+    };
+    const size_t slots = (size_t)F * cap_markers;
+    c.base = take((size_t)F * sizeof(int32_t)), c.nrec = take((size_t)F * sizeof(int32_t)), c.recovered = take((size_t)F * sizeof(int32_t));
+    c.status = take(sizeof(uint32_t));
+    c.rec = take(slots * sizeof(RecoverRec)), c.rlist = take(slots * sizeof(uint32_t)), c.plist = take(slots * sizeof(uint32_t));
+    c.ids = take((size_t)nboard * sizeof(int32_t)), c.obj = take((size_t)nboard * 12 * sizeof(float));
+    c.total = at;
+    return c;
+}
+
+int arucohip_board_recover_batch(arucohip_handle* h, int nframes, const int32_t* ids, const float* obj, int nboard, int info_type, const float* K,
+                                 const float* dist, int ndist, float marker_size, float repj_err_thres, int y_perp, const arucohip_recover_t* opt,
+                                 arucohip_marker_t* out, int cap, int32_t* n_out, int out_on_device, int32_t* recovered, arucohip_board_t* boards,
+                                 float* prob) {
+    if (!h) return ARUCOHIP_E_INVALID;
+    if (nboard <= 0 || !ids || !obj) return fail(h, ARUCOHIP_E_BOARD_CONFIG, "invalid BoardConfig that is empty");
+    if (nboard * 12 > 8192) return fail(h, ARUCOHIP_E_CAPACITY, "board with too many markers");
+    if (nframes < 1 || nframes > h->last.frames) return fail(h, ARUCOHIP_E_INVALID, "nframes exceeds the last batch");
+    if ((out == nullptr) != (n_out == nullptr) || (out && cap < 1)) return fail(h, ARUCOHIP_E_INVALID, "board_recover_batch: out and n_out go together, with cap >= 1");
+    if (!K) return fail(h, ARUCOHIP_E_INVALID, "board_recover_batch: K is required");
+    if (info_type != ARUCOHIP_BOARD_PIX && info_type != ARUCOHIP_BOARD_METERS) return fail(h, ARUCOHIP_E_INVALID, "board_recover_batch: info_type is neither PIX nor METERS");
+    if (info_type == ARUCOHIP_BOARD_PIX && !(marker_size > 0)) return fail(h, ARUCOHIP_E_INVALID, "board_recover_batch: a PIX board needs marker_size > 0");
+    arucohip_recover_t o;
+    arucohip_default_recover(&o);
+    if (opt) o = *opt;
+    if (!(o.max_corner_dist > 0)) return fail(h, ARUCOHIP_E_INVALID, "board_recover_batch: max_corner_dist must be positive");
+    if (o.max_cell_errors < 0 || o.max_cell_errors > 49) return fail(h, ARUCOHIP_E_INVALID, "board_recover_batch: max_cell_errors outside 0..49");
+    if (o.min_markers < 1) return fail(h, ARUCOHIP_E_INVALID, "board_recover_batch: min_markers must be at least 1");
+    if (o.pose_markers && !(marker_size > 0)) return fail(h, ARUCOHIP_E_INVALID, "board_recover_batch: pose_markers needs marker_size > 0");
+    const arucohip_params_t& p = h->params;
+    if (p.corner_method != ARUCOHIP_CORNER_LINES && p.corner_method != ARUCOHIP_CORNER_NONE)
+        return fail(h, ARUCOHIP_E_UNSUPPORTED, "board_recover_batch: HARRIS / SUBPIX corners need the frames, which the handle does not hold");
+    if (p.use_locked_corners) return fail(h, ARUCOHIP_E_UNSUPPORTED, "board_recover_batch: locked corners are not supported");
+    if (p.decoder_kind != ARUCOHIP_DECODER_FIDUCIAL_5X5) return fail(h, ARUCOHIP_E_UNSUPPORTED, "board_recover_batch: only the built-in 5x5 decoder is supported (not HRM / USER)");
+    if (ndist < 0 || ndist > 8 || (ndist > 0 && !dist)) return fail(h, ARUCOHIP_E_INVALID, "ndist must be 0..8, with dist");
+    HIPCHK(h, hipSetDevice(h->device));
+    // cam: the refinement's and the markers' own poses; bcam: the board solves, which always carry a distortion vector (board_detect_batch)
+    CamModel cam, bcam;
+    std::memset(&cam, 0, sizeof(cam));
+    cam.has_K = 1, cam.has_dist = dist != nullptr && ndist > 0, cam.marker_size = marker_size, cam.y_perp = y_perp;
+    for (int i = 0; i < 9; i++) cam.K[i] = K[i];
+    for (int i = 0; i < (cam.has_dist ? ndist : 0); i++) cam.k[i] = (double)dist[i];
+    bcam = cam, bcam.has_dist = 1;
+    RecoverArgs a;
+    a.nboard = nboard, a.info_type = info_type, a.marker_size = marker_size, a.repj_thres = repj_err_thres;
+    a.max_corner_dist = o.max_corner_dist, a.max_cell_errors = o.max_cell_errors, a.min_markers = o.min_markers;
+    a.ws = p.warp_size;
+    int rect[4];
+    border_rect(p.border_dist, h->last.frame_w, h->last.frame_h, rect);
+    a.bx0 = rect[0], a.by0 = rect[1], a.bx1 = rect[2], a.by1 = rect[3];
+    const bool wait = !out_on_device || recovered || boards || prob;
+
+    const Batch b = h->last.cut(nframes);
+    int rc;
+    std::vector<std::vector<arucohip_marker_t>> stage((size_t)b.nspan);
+    std::vector<uint32_t> status((size_t)b.nspan, 0u);
+    std::vector<int32_t> n_host;
+    if (out && !out_on_device) n_host.resize((size_t)nframes);
+    if ((rc = fork_workers(h, b))) return rc;
+    for (int c = 0; c < b.nspan; c++) {
+        const Span& s = b.span[c];
+        arucohip_handle* w = s.w;
+        const Buffers& wb = w->buf;
+        const int capM = wb.cap_markers;
+        const RecoverCarve cv = recover_carve(w->cap_frames, capM, nboard);
+        HIPCHK(h, w->d_recover.reserve(cv.total));
+        uint8_t* base = w->d_recover;
+        RecoverBufs r;
+        r.base = (int32_t*)(base + cv.base), r.nrec = (int32_t*)(base + cv.nrec), r.recovered = (int32_t*)(base + cv.recovered);
+        r.status = (uint32_t*)(base + cv.status), r.rec = (RecoverRec*)(base + cv.rec), r.rlist = (uint32_t*)(base + cv.rlist);
+        r.plist = (uint32_t*)(base + cv.plist);
+        a.ids = (const int32_t*)(base + cv.ids), a.obj = (const float*)(base + cv.obj);
+        a.cells_valid = w->cells_valid ? 1 : 0;
+        HIPCHK(h, w->d_board.reserve((size_t)w->cap_frames * (sizeof(arucohip_board_t) + sizeof(float)) + 8192 * sizeof(int32_t)));
+        arucohip_board_t* d_boards = w->d_board;
+        float* d_prob = (float*)(d_boards + w->cap_frames);
+        hipStream_t st = w->stream;
+        HIPCHK(h, hipMemsetAsync(r.base, 0xFF, (size_t)w->cap_frames * sizeof(int32_t), st));
+        HIPCHK(h, hipMemsetAsync(r.status, 0, sizeof(uint32_t), st));
+        HIPCHK(h, hipMemcpyAsync(base + cv.ids, ids, (size_t)nboard * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(base + cv.obj, obj, (size_t)nboard * 12 * sizeof(float), hipMemcpyHostToDevice, st));
+        launch_recover_match(st, h->last.span[c].count, s.count, wb, a, bcam, r);
+        launch_refine_recovered(st, s.count, p.corner_method, cam, wb, r.rlist, r.nrec, capM);
+        launch_recover_insert(st, s.count, wb, a, bcam, r, d_boards, d_prob);
+        if (o.pose_markers) launch_pose_sparse(st, wb, r.plist, (uint32_t)s.count * (uint32_t)capM, cam);
+        HIPCHK(h, hipGetLastError());
+        if (out && out_on_device) {
+            HIPCHK(h, hipMemcpy2DAsync(out + (size_t)s.first * cap, (size_t)cap * sizeof(arucohip_marker_t), wb.markers, (size_t)capM * sizeof(arucohip_marker_t),
+                                       (size_t)std::min(cap, capM) * sizeof(arucohip_marker_t), (size_t)s.count, hipMemcpyDeviceToDevice, st));
+            HIPCHK(h, hipMemcpyAsync(n_out + s.first, wb.nmarkers, (size_t)s.count * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        } else if (out) {
+            stage[c].resize((size_t)s.count * capM);
+            HIPCHK(h, hipMemcpyAsync(stage[c].data(), wb.markers, stage[c].size() * sizeof(arucohip_marker_t), hipMemcpyDeviceToHost, st));
+            HIPCHK(h, hipMemcpyAsync(n_host.data() + s.first, wb.nmarkers, (size_t)s.count * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        }
+        if (recovered) HIPCHK(h, hipMemcpyAsync(recovered + s.first, r.recovered, (size_t)s.count * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (boards) HIPCHK(h, hipMemcpyAsync(boards + s.first, d_boards, (size_t)s.count * sizeof(arucohip_board_t), hipMemcpyDeviceToHost, st));
+        if (prob) HIPCHK(h, hipMemcpyAsync(prob + s.first, d_prob, (size_t)s.count * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (wait) HIPCHK(h, hipMemcpyAsync(&status[c], r.status, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    if ((rc = join_workers(h, b))) return rc;
+    h->last.board_frames = nframes;
+    if (!wait) return ARUCOHIP_OK;
+    HIPCHK(h, hipStreamSynchronize(b.span[0].w->stream));
+    int ret = ARUCOHIP_OK;
+    for (int c = 0; c < b.nspan; c++) {
+        const Span& s = b.span[c];
+        arucohip_handle* w = s.w;
+        HIPCHK(h, hipMemcpy(w->h_counters, w->buf.counters, CNT_FIXED * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (w->h_counters[CNT_STATUS] & ST_MARKER_OVERFLOW) ret = fail(h, ARUCOHIP_E_CAPACITY, "a frame has more than 128 board markers");
+        if (status[c] & 1u) ret = fail(h, ARUCOHIP_E_CAPACITY, "board_recover_batch: a frame's marker list is full (markers_per_frame)");
+        if (!out || out_on_device) continue;
+        const int capM = w->buf.cap_markers;
+        for (int f = 0; f < s.count; f++) {
+            int n = n_host[s.first + f];
+            n_out[s.first + f] = n;
+            if (n > cap) {
+                if (ret == ARUCOHIP_OK) ret = fail(h, ARUCOHIP_E_CAPACITY, "marker output array too small");
+                n = cap;
+            }
+            n = std::min(n, capM);
+            if (n > 0) std::memcpy(out + (size_t)(s.first + f) * cap, stage[c].data() + (size_t)f * capM, (size_t)n * sizeof(arucohip_marker_t));
+        }
+    }
+    return ret;
+}
+
+}  // extern "C"

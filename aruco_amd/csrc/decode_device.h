@@ -231,8 +231,8 @@ constexpr int CELLS_PITCH = 8;
 // A cell's vote "more than half of its pixels exceed thr" is "its (half + 1)-th largest pixel exceeds thr": the rank warp_hist_kernel selects
 constexpr int cell_vote_rank(int sw) { return (sw * sw) / 2 + 1; }
 
-// all 64 lanes call it; *id / *nrot are valid on lane 0 (id = -1: not a marker)
-__device__ __forceinline__ void cells_decode_wave(const uint8_t* patch, int ws, int thr, int lane, int* id_out, int* nrot_out) {
+// all 64 lanes call it: the 49 cell votes of a stored patch as a word, bit cy * 7 + cx = the cell is white (the same on every lane)
+__device__ __forceinline__ unsigned long long cells_votes_wave(const uint8_t* patch, int ws, int thr, int lane) {
     const int sw = ws / 7;
     const int half = cell_vote_rank(sw) - 1;
     bool white = false;
@@ -252,7 +252,12 @@ __device__ __forceinline__ void cells_decode_wave(const uint8_t* patch, int ws, 
         }
         white = cnt > half;
     }
-    const unsigned long long m = __ballot(white);   // bit cy*7+cx
+    return __ballot(white);   // bit cy*7+cx
+}
+
+// all 64 lanes call it; *id / *nrot are valid on lane 0 (id = -1: not a marker)
+__device__ __forceinline__ void cells_decode_wave(const uint8_t* patch, int ws, int thr, int lane, int* id_out, int* nrot_out) {
+    const unsigned long long m = cells_votes_wave(patch, ws, thr, lane);
     int id = -1, nrot = 0;
     if (lane == 0) fiducial_decode_word(m, &id, &nrot);
     *id_out = id, *nrot_out = nrot;

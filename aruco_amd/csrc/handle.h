@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdio>
 #include <string>
 #include <vector>
@@ -59,7 +60,8 @@ struct Span { arucohip_handle* w; int first, count; };   // worker w holds frame
 struct Batch {
     int nspan = 0, frames = 0;
     Span span[MAX_WORKERS] = {};
-    int W = 0, H = 0, nthr = 1;
+    int W = 0, H = 0, nthr = 1;   // W x H: the thresholded image (the frame reduced by the pyrDown level)
+    int frame_w = 0, frame_h = 0;   // the frames themselves
     int board_frames = 0;   // frames whose board poses arucohip_board_detect_batch left in the workers' d_board
     const Span* begin() const { return span; }
     const Span* end() const { return span + nspan; }
@@ -139,6 +141,7 @@ struct arucohip_handle {
     Mem<uint8_t> d_planar;            // arucohip_planar_poses: results and staged markers of one call
     Mem<uint8_t> d_overlay;           // arucohip_draw_*_batch: primitive lists of one chunk of frames, staged host markers / boards
     Mem<uint8_t> d_overlay_frames;    // arucohip_draw_*_batch: staged host frames
+    Mem<uint8_t> d_recover;           // arucohip_board_recover_batch: the board, adoption records and work lists of one call (recover_carve)
     Batch last;                       // the last batch (kept on the handle the caller holds)
     bool timing = false;
     hipEvent_t ev[TSETS][K_COUNT + 1] = {};
@@ -171,7 +174,7 @@ struct arucohip_handle {
     //   capture and replay; batches that decode from cell medians neither touch nor move buf.patches, and buf.cells is create-time memory;
     // - neither: the other Buffers arrays, zero_block and h_markers are create-time memory (`held`); d_erode, d_canny and the user decoder's
     //   staging and d_pyr belong to configurations that are not graphed; wt_out is set only inside chunk_enqueue, which does not run this path.
-    //   Memory no captured launch reads (d_bgr, undistortion, calibration, board and GL batches, planar poses, overlays, EM, HRM, fiducial generation and ChromaticMask scratch) may
+    //   Memory no captured launch reads (d_bgr, undistortion, calibration, board and GL batches, planar poses, marker recovery, overlays, EM, HRM, fiducial generation and ChromaticMask scratch) may
     //   be replaced at any time.
     struct FrameGraph {
         hipGraphExec_t exec = nullptr;
@@ -212,6 +215,13 @@ struct arucohip_handle {
 inline int fail(arucohip_handle* h, int code, const char* msg) {
     if (h) h->err = msg;
     return code;
+}
+
+// the border filter's rectangle [r[0], r[2]) x [r[1], r[3]) of a W x H frame: markerdetector.cpp:433-434, Rect(Point(size) * t, Point(size) * (1 - t)) with cvRound
+inline void border_rect(float border_dist, int W, int H, int r[4]) {
+    const int x1 = (int)lrintf((float)W * border_dist), y1 = (int)lrintf((float)H * border_dist);
+    const int x2 = (int)lrintf((float)W * (1.0f - border_dist)), y2 = (int)lrintf((float)H * (1.0f - border_dist));
+    r[0] = std::min(x1, x2), r[1] = std::min(y1, y2), r[2] = std::max(x1, x2), r[3] = std::max(y1, y2);
 }
 
 // fork: the other workers' streams wait for what the first worker's stream (the batch's own) has queued so far; errors are reported on h

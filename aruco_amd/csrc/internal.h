@@ -266,6 +266,39 @@ void launch_marker_pose(hipStream_t s, arucohip_marker_t* markers, int n, const 
 void launch_board_pose(hipStream_t s, int nframes, const Buffers& b, const int32_t* ids, const float* obj, int nboard, int info_type,
                        float marker_size, float repj_thres, const CamModel& cam, arucohip_board_t* out, float* prob);
 
+// Board marker recovery (k_recover.hip; arucohip_board_recover_batch). A worker's scratch: per frame the first entry of its block in the flat
+// candidate list, the adoptions of the matching pass, and the lists the refinement and the per-marker solver walk.
+struct RecoverRec {
+    int32_t board, cand, nrot, old_nrot;   // board entry, candidate index in the frame, rotation adopted, the rotation the decoder had left
+};
+struct RecoverBufs {
+    int32_t* base;        // [F] index in Buffers::cand_list of the frame's candidate 0
+    int32_t* nrec;        // [F] adoptions of the matching pass
+    RecoverRec* rec;      // [F][cap_markers]
+    uint32_t* rlist;      // [F][cap_markers] frame << 16 | candidate: what launch_refine_recovered walks
+    uint32_t* plist;      // [F][cap_markers] frame << 16 | marker index of the recovered markers, 0xFFFFFFFF: none (launch_pose_sparse)
+    int32_t* recovered;   // [F] markers inserted
+    uint32_t* status;     // bit 0: a frame's marker list was full
+};
+struct RecoverArgs {
+    const int32_t* ids;   // device: the board
+    const float* obj;
+    int nboard, info_type;
+    float marker_size, repj_thres;
+    float max_corner_dist;
+    int max_cell_errors, min_markers;
+    int cells_valid, ws;             // votes from Buffers::cells, else from the stored patches of side ws
+    int bx0, by0, bx1, by1;          // finalize_kernel's border rectangle
+};
+void launch_recover_match(hipStream_t s, int list_frames, int nframes, const Buffers& b, const RecoverArgs& a, const CamModel& cam, const RecoverBufs& r);
+void launch_recover_insert(hipStream_t s, int nframes, const Buffers& b, const RecoverArgs& a, const CamModel& cam, const RecoverBufs& r,
+                           arucohip_board_t* boards, float* prob);
+// refine_one (k_refine.hip) on the candidates of r.rlist, with this call's camera
+void launch_refine_recovered(hipStream_t s, int nframes, int corner_method, const CamModel& cam, const Buffers& b, const uint32_t* rlist,
+                             const int32_t* nrec, int stride);
+// the per-marker solver (k_finalize.hip) over a list with holes: nlist entries frame << 16 | index, 0xFFFFFFFF = none
+void launch_pose_sparse(hipStream_t s, const Buffers& b, const uint32_t* list, uint32_t nlist, const CamModel& cam);
+
 // Both planar pose solutions per marker (k_planar.hip): markers[0 .. n) -> out[0 .. n), or the markers of the first nframes of the list_frames
 // frames a worker's lists hold -> out[(first + f) * cap_out + i]
 void launch_planar_poses(hipStream_t s, const arucohip_marker_t* markers, int n, const CamModel& cam, int refine, arucohip_planar_poses_t* out);

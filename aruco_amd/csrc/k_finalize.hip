@@ -6,6 +6,7 @@
 // BoardDetector pose (src/boarddetector.cpp:157-198).
 #include "internal.h"
 #include "pnp_device.h"
+#include "board_device.h"
 
 namespace ah {
 
@@ -180,6 +181,22 @@ void launch_pose(hipStream_t s, int nframes, const CamModel& cam, const Buffers&
     hipLaunchKernelGGL(pose_kernel, dim3((cap_list + 15) / 16), dim3(64), 0, s, b.markers, b.marker_list, b.counters, cap_list, b.cap_markers, 0, cam);
 }
 
+// the markers a sparse list names (board marker recovery): entry frame << 16 | index, 0xFFFFFFFF = none
+__global__ __launch_bounds__(64) void pose_sparse_kernel(arucohip_marker_t* markers, const uint32_t* list, uint32_t nlist, int cap_markers, CamModel cam) {
+    latency_bound_priority();
+    __shared__ float s_obj[16][12], s_img[16][8];
+    const int grp = threadIdx.x / POSE_G, sub = threadIdx.x % POSE_G;
+    const uint32_t gid = blockIdx.x * (64 / POSE_G) + grp;
+    if (gid >= nlist) return;   // uniform within the group of four
+    const uint32_t e = list[gid];
+    if (e == 0xFFFFFFFFu) return;
+    marker_pose4(markers + (size_t)(e >> 16) * cap_markers + (e & 0xFFFFu), cam, s_obj[grp], s_img[grp], sub);
+}
+
+void launch_pose_sparse(hipStream_t s, const Buffers& b, const uint32_t* list, uint32_t nlist, const CamModel& cam) {
+    if (nlist) hipLaunchKernelGGL(pose_sparse_kernel, dim3((nlist + 15) / 16), dim3(64), 0, s, b.markers, list, nlist, b.cap_markers, cam);
+}
+
 void launch_marker_pose(hipStream_t s, arucohip_marker_t* markers, int n, const CamModel& cam) {
     hipLaunchKernelGGL(pose_kernel, dim3((n + 15) / 16), dim3(64), 0, s, markers, (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0u, 0, n, cam);
 }
@@ -218,19 +235,13 @@ void launch_project_points(hipStream_t s, const float* obj, int npts, const doub
 
 // ---------------------------------------------------------------------------------------------
 // Batched BoardDetector::detect (boarddetector.cpp:90-205): one wavefront per frame on the device-resident markers of the
-// last batch. Lane 0 filters the markers by board id and lays out the 3-D / 2-D correspondences in LDS, then the 64 lanes
-// share the points of the planar solvePnP (wave sums for J^T J); optional reprojection filter and second solve.
+// last batch: board_solve_wave (board_device.h).
 // ---------------------------------------------------------------------------------------------
-constexpr int MAX_BOARD_POINTS = 512;
-
 struct BoardArgs {
     const arucohip_marker_t* markers;
     const int32_t* nmarkers;
     int cap_markers;
-    const int32_t* ids;
-    const float* obj;      // nboard * 4 * 3
-    int nboard, info_type;
-    float marker_size, repj_thres;
+    BoardDef bd;
     CamModel cam;
     arucohip_board_t* out;
     float* prob;
@@ -239,78 +250,22 @@ struct BoardArgs {
 
 __global__ __launch_bounds__(64) void board_pose_kernel(BoardArgs a) {
     latency_bound_priority();
-    __shared__ float s_obj[MAX_BOARD_POINTS * 3], s_img[MAX_BOARD_POINTS * 2], s_obj2[MAX_BOARD_POINTS * 3], s_img2[MAX_BOARD_POINTS * 2];
-    __shared__ int s_npts, s_nmark, s_n2;
+    __shared__ BoardLds s;
     const int frame = blockIdx.x, lane = threadIdx.x;
     const arucohip_marker_t* M = a.markers + (size_t)frame * a.cap_markers;
     const int nm = min(a.nmarkers[frame], a.cap_markers);
-    if (lane == 0) {
-        const float dx = a.obj[0] - a.obj[3], dy = a.obj[1] - a.obj[4], dz = a.obj[2] - a.obj[5];
-        const double side = sqrt((double)dx * dx + (double)dy * dy + (double)dz * dz);
-        const double mpp = a.info_type == ARUCOHIP_BOARD_PIX ? (double)a.marker_size / side : 1.0;
-        int np = 0, nk = 0;
-        for (int i = 0; i < nm; i++) {
-            int slot = -1;
-            for (int j = 0; j < a.nboard; j++)
-                if (a.ids[j] == M[i].id) {
-                    slot = j;
-                    break;
-                }
-            if (slot < 0) continue;
-            nk++;
-            if (np + 4 > MAX_BOARD_POINTS) {   // more correspondences than the kernel holds: reported, never silent
-                atomicOr(&a.counters[CNT_STATUS], (uint32_t)ST_MARKER_OVERFLOW);
-                continue;
-            }
-            for (int p = 0; p < 4; p++, np++) {
-                s_img[2 * np] = M[i].corners[2 * p], s_img[2 * np + 1] = M[i].corners[2 * p + 1];
-                const float* q = a.obj + ((size_t)slot * 4 + p) * 3;
-                for (int c = 0; c < 3; c++) s_obj[3 * np + c] = (float)(q[c] * mpp);
-            }
-        }
-        s_npts = np, s_nmark = nk;
-    }
-    __syncthreads();
-    const int np = s_npts, nk = s_nmark;
+    double r[3], t[3];
+    int nk;
+    const int st = board_solve_wave(M, nm, a.bd, a.cam, a.counters, s, lane, r, t, &nk);
     arucohip_board_t res;
     res.n_markers = nk, res.has_pose = 0;
     for (int k = 0; k < 3; k++) res.rvec[k] = res.tvec[k] = 0;
     float prob = 0;
-    const bool enough = (a.marker_size > 0 && a.info_type == ARUCOHIP_BOARD_PIX) || a.info_type == ARUCOHIP_BOARD_METERS;
-    if (nk > 0 && a.cam.has_K && enough) {
-        double r[3] = {0, 0, 0}, t[3] = {0, 0, 0};
-        bool ok = solve_pnp_planar_wave<64>(s_obj, s_img, np, a.cam, r, t, lane);
-        if (a.repj_thres > 0 && ok) {
-            double R[9];
-            rodrigues_vec2mat(r, R, nullptr);
-            if (lane == 0) s_n2 = 0;
-            __syncthreads();
-            for (int base = 0; base < np; base += 64) {   // order-preserving compaction of the points that pass
-                const int i = base + lane;
-                bool keep = false;
-                if (i < np) {
-                    double mx, my;
-                    project_point(s_obj[3 * i], s_obj[3 * i + 1], s_obj[3 * i + 2], R, nullptr, t, a.cam.K, a.cam.k, &mx, &my, nullptr, nullptr);
-                    const float ex = (float)mx - s_img[2 * i], ey = (float)my - s_img[2 * i + 1];
-                    keep = (float)sqrt((double)ex * ex + (double)ey * ey) < a.repj_thres;
-                }
-                const unsigned long long bal = __ballot(keep);
-                const int dst = s_n2 + __popcll(bal & ((1ull << lane) - 1ull));
-                if (keep) {
-                    for (int c = 0; c < 3; c++) s_obj2[3 * dst + c] = s_obj[3 * i + c];
-                    s_img2[2 * dst] = s_img[2 * i], s_img2[2 * dst + 1] = s_img[2 * i + 1];
-                }
-                __syncthreads();
-                if (lane == 0) s_n2 += __popcll(bal);
-                __syncthreads();
-            }
-            // fewer than 4 surviving points: the reference's second solvePnP would throw; keep the first pose, flag no pose
-            ok = s_n2 >= 4 && solve_pnp_planar_wave<64>(s_obj2, s_img2, s_n2, a.cam, r, t, lane);
-        }
-        if (ok && a.cam.y_perp) rotate_x_axis(r);
-        res.has_pose = ok ? 1 : 0;
+    if (st != BOARD_NOT_TRIED) {
+        if (st == BOARD_POSE && a.cam.y_perp) rotate_x_axis(r);
+        res.has_pose = st == BOARD_POSE ? 1 : 0;
         for (int k = 0; k < 3; k++) res.rvec[k] = r[k], res.tvec[k] = t[k];
-        prob = (float)nk / (float)a.nboard;
+        prob = (float)nk / (float)a.bd.nboard;
     }
     if (lane == 0) a.out[frame] = res, a.prob[frame] = prob;
 }
@@ -319,7 +274,7 @@ void launch_board_pose(hipStream_t s, int nframes, const Buffers& b, const int32
                        float marker_size, float repj_thres, const CamModel& cam, arucohip_board_t* out, float* prob) {
     BoardArgs a;
     a.markers = b.markers, a.nmarkers = b.nmarkers, a.cap_markers = b.cap_markers;
-    a.ids = ids, a.obj = obj, a.nboard = nboard, a.info_type = info_type, a.marker_size = marker_size, a.repj_thres = repj_thres;
+    a.bd.ids = ids, a.bd.obj = obj, a.bd.nboard = nboard, a.bd.info_type = info_type, a.bd.marker_size = marker_size, a.bd.repj_thres = repj_thres;
     a.cam = cam, a.out = out, a.prob = prob, a.counters = b.counters;
     hipLaunchKernelGGL(board_pose_kernel, dim3(nframes), dim3(64), 0, s, a);
 }

@@ -242,6 +242,27 @@ void launch_refine_lines(hipStream_t s, const FrameGeom& g, int nframes, const D
     hipLaunchKernelGGL(refine_lines_kernel, dim3(blocks), dim3(64), 0, s, a);
 }
 
+// Board marker recovery (k_recover.hip): the candidates a frame's matching pass adopted, rlist[frame * stride + k] for k < nrec[frame], are refined
+// and turned to canonical order as the launch above would have done had the decoder accepted them. One workgroup per frame: a frame adopts few.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LINES_WAVES_N, LINES_WAVES_N))) void refine_recovered_kernel(LinesArgs a, const int32_t* nrec,
+                                                                                                                          int stride) {
+    latency_bound_priority();
+    const int lane = threadIdx.x, frame = blockIdx.x;
+    const int n = min(nrec[frame], stride);
+    for (int k = 0; k < n; k++) refine_one(a, a.cand_list[(size_t)frame * stride + k], lane, 0u);
+}
+
+void launch_refine_recovered(hipStream_t s, int nframes, int corner_method, const CamModel& cam, const Buffers& b, const uint32_t* rlist,
+                             const int32_t* nrec, int stride) {
+    LinesArgs a;
+    a.fused_cells = 0, a.ws = 0, a.patches = nullptr, a.othr = nullptr;   // the ids are set: no cell decode
+    a.cands = b.cands, a.ncands = b.ncands, a.cdesc = b.cdesc, a.pool = b.pool, a.cap_cands = b.cap_cands;
+    a.do_lines = corner_method == ARUCOHIP_CORNER_LINES;
+    a.cam = cam;
+    a.cand_list = rlist, a.counters = b.counters, a.cap_flat = b.cap_flat;
+    hipLaunchKernelGGL(refine_recovered_kernel, dim3(nframes), dim3(64), 0, s, a, nrec, stride);
+}
+
 // ---------------------------------------------------------------------------------------------
 // SUBPIX / HARRIS: one wavefront per corner of a decoded candidate
 // ---------------------------------------------------------------------------------------------

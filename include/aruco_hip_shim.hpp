@@ -1430,6 +1430,36 @@ public:
         BD.detect(Image);
         return BD.getDetectedBoard();
     }
+    // No counterpart in the reference (OpenCV's aruco module: refineDetectedMarkers). The board's markers that the decoder rejected in the
+    // last detect(im) are taken back from that frame's rejected candidates on the device (arucohip_board_recover_batch): a candidate within
+    // maxCornerDist pixels of where the board's pose puts the marker, showing it in all but maxCellErrors cells. Replaces the detector's
+    // marker vector and board; returns the number of markers recovered.
+    int recoverMarkers(const BoardConfiguration& BConf, const CameraParameters& cp, float markerSizeMeters = -1, float maxCornerDist = 10,
+                       int maxCellErrors = 3) {
+        float K[9], d[8];
+        bool hasK = mat_to_K_(cp.CameraMatrix, K);
+        int nd = mat_to_dist_(cp.Distorsion, d);
+        std::vector<int32_t> ids(BConf.ids.begin(), BConf.ids.end());
+        std::vector<float> obj;
+        for (size_t i = 0; i < BConf.objPoints.size(); i++)
+            for (int p = 0; p < 4 && p < (int)BConf.objPoints[i].size(); p++)
+                obj.push_back(BConf.objPoints[i][p].x), obj.push_back(BConf.objPoints[i][p].y), obj.push_back(BConf.objPoints[i][p].z);
+        arucohip_recover_t o;
+        arucohip_default_recover(&o);
+        o.max_corner_dist = maxCornerDist, o.max_cell_errors = maxCellErrors, o.pose_markers = markerSizeMeters > 0 ? 1 : 0;
+        const int cap = 512;
+        std::vector<arucohip_marker_t> out(cap);
+        int32_t n = 0, recovered = 0;
+        arucohip_handle* h = _mdetector.handle();
+        int rc = arucohip_board_recover_batch(h, 1, ids.data(), obj.data(), (int)ids.size(), BConf.mInfoType, hasK ? K : nullptr, nd ? d : nullptr, nd,
+                                              markerSizeMeters, repj_err_thres, _setYPerpendicular ? 1 : 0, &o, out.data(), cap, &n, 0, &recovered,
+                                              nullptr, nullptr);
+        arucohip_throw_(rc, "BoardDetector::recoverMarkers", h);
+        _vmarkers.clear();
+        for (int i = 0; i < n && i < cap; i++) _vmarkers.push_back(Marker::from_abi(out[i]));
+        detect(_vmarkers, BConf, _boardDetected, cp.CameraMatrix, cp.Distorsion, markerSizeMeters);
+        return recovered;
+    }
     Board& getDetectedBoard() { return _boardDetected; }
     MarkerDetector& getMarkerDetector() { return _mdetector; }
     std::vector<Marker>& getDetectedMarkers() { return _vmarkers; }

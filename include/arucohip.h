@@ -399,6 +399,49 @@ int arucohip_board_detect_batch(arucohip_handle* h, int nframes, const int32_t* 
                                 const float* K, const float* dist, int ndist, float marker_size, float repj_err_thres,
                                 int y_perpendicular, arucohip_board_t* out, float* prob);
 
+/* Board marker recovery. A marker of a board is lost when one of its cells reads wrong (a highlight, a fingertip, motion blur): the
+ * decoder accepts only Hamming distance 0 with a clean border. Its quad is still among the frame's rejected candidates, and the board's
+ * other markers say where it must be and what it must show. No counterpart in the reference (OpenCV's aruco module has
+ * refineDetectedMarkers). */
+typedef struct arucohip_recover {
+    float   max_corner_dist;  /* pixels: largest distance between a candidate corner and the projected corner it is matched to.
+                                 Default 10 (OpenCV's minRepDistance; taken over, not measured here) */
+    int32_t max_cell_errors;  /* 0..49: cells of the 7 x 7 grid (24 border + 25 code) that may differ from the expected marker. Default 3 */
+    int32_t min_markers;      /* board members a frame must already hold (>= 1). Default 2 */
+    int32_t pose_markers;     /* != 0: recovered markers get ssize and their own pose from this call's camera, as
+                                 arucohip_calculate_extrinsics would give; 0: has_pose = 0, ssize = -1 */
+} arucohip_recover_t;
+void arucohip_default_recover(arucohip_recover_t* o);
+
+/* Works on the first nframes frames of the LAST batch (a synchronous call, a waited ticket or a one-frame arucohip_detect; every chunk
+ * worker), entirely on the device, frame by frame:
+ *  1. the board pose from the frame's markers whose id is in `ids`, as arucohip_board_detect_batch solves it, before rotateXAxis. A frame
+ *     without a pose, with fewer than min_markers members or given up by the batch (n = -1) is left untouched;
+ *  2. for every board entry the frame lacks, in board order: its four corners are projected, and over the rejected candidates no earlier
+ *     entry took and their four cyclic rotations the smallest "largest corner distance" to the integer quad is found (ties: lower
+ *     candidate, then lower rotation). The entry stays missing unless that is < max_corner_dist;
+ *  3. the candidate's 49 cell votes (the decoder's) are compared with the expected marker in the candidate's orientation; more than
+ *     max_cell_errors differing cells leave the entry missing and the candidate free;
+ *  4. the candidate gets id and rotation, its corners are refined as detection refines them with this call's camera (LINES or NONE) and
+ *     turned to canonical order; a marker with a corner outside the border rectangle (border_dist) is not adopted;
+ *  5. the adopted markers enter the frame's marker list at their place in id order (pose_markers: with their own pose). A full list
+ *     (markers_per_frame) stops the frame's recovery: the call completes and returns ARUCOHIP_E_CAPACITY;
+ *  6. the board is solved again over all members: boards[f] / prob[f] (host, may be NULL), rotated with y_perpendicular. The poses stay
+ *     on the device as after arucohip_board_detect_batch (arucohip_chromatic_classify_batch may follow).
+ * Every later reader of the last batch sees the recovered markers; a second call recovers nothing. out / n_out (both NULL, or both
+ * given) receive each frame's whole marker list as arucohip_detect_batch lays it out (cap per frame; n_out[f] = -1 stays -1; a frame
+ * with more than cap markers gives its count and ARUCOHIP_E_CAPACITY): host arrays, or device arrays with out_on_device. With
+ * out_on_device and recovered, boards and prob all NULL the call is asynchronous on the handle's stream and reports no capacity
+ * condition. recovered (host, nframes, may be NULL): markers recovered per frame.
+ * Supported: the built-in 5 x 5 decoder, corner methods LINES and NONE, any threshold range, any pyrDown level.
+ * ARUCOHIP_E_UNSUPPORTED: HARRIS / SUBPIX (the handle does not hold the frames), locked corners, the HRM and USER decoders.
+ * ARUCOHIP_E_INVALID: no K, marker_size <= 0 on a PIX board, max_corner_dist <= 0, max_cell_errors outside 0..49, min_markers < 1,
+ * nframes beyond the last batch. ARUCOHIP_E_BOARD_CONFIG: an empty board. ARUCOHIP_E_CAPACITY: a board of more than 682 markers. */
+int arucohip_board_recover_batch(arucohip_handle* h, int nframes, const int32_t* ids, const float* obj, int nboard, int info_type,
+                                 const float* K, const float* dist, int ndist, float marker_size, float repj_err_thres,
+                                 int y_perpendicular, const arucohip_recover_t* opt, arucohip_marker_t* out, int cap, int32_t* n_out,
+                                 int out_on_device, int32_t* recovered, arucohip_board_t* boards, float* prob);
+
 /* cv::calibrateCamera for planar targets (pinhole model, dist = k1 k2 p1 p2 k3), solved on the device in double precision: start
  * values as OpenCV's (homography per view, focal lengths from the vanishing points, principal point at the image centre, distortion
  * 0, planar solvePnP per view), then Levenberg-Marquardt over the intrinsics and every view's pose with the poses eliminated
