@@ -104,7 +104,7 @@ SYMBOLS = [
     "arucohip_mgpu_set_params", "arucohip_mgpu_last_error_string", "arucohip_mgpu_detect_batch", "arucohip_mgpu_detect_streams",
     "arucohip_mgpu_set_depth", "arucohip_mgpu_submit_batch", "arucohip_mgpu_submit_streams", "arucohip_mgpu_wait",
     "arucohip_compact_bytes", "arucohip_compact_markers", "arucohip_wait_event", "arucohip_detect_batch_retry_overflowed",
-    "arucohip_refine_candidate_lines", "arucohip_mgpu_gather_mode", "arucohip_build_info",
+    "arucohip_refine_candidate_lines", "arucohip_debug_refine_pixels", "arucohip_mgpu_gather_mode", "arucohip_build_info",
     "arucohip_calibrate_camera", "arucohip_calibrate_board_batch",
     "arucohip_planar_poses", "arucohip_planar_poses_batch",
     "arucohip_chromatic_board_corners", "arucohip_chromatic_create", "arucohip_chromatic_destroy", "arucohip_chromatic_train",
@@ -261,6 +261,7 @@ def load():
     L.arucohip_wait_event.argtypes = [vp, vp]
     L.arucohip_detect_batch_retry_overflowed.argtypes = [vp, vp, i, i, i, sz, sz, i, vp, vp, i, f, i, vp, i, vp, i, vp]
     L.arucohip_refine_candidate_lines.argtypes = [vp, vp, i, vp, vp, vp, i]
+    L.arucohip_debug_refine_pixels.argtypes = [vp, vp, i, i, C.c_size_t, vp, i, i, i, i]
     L.arucohip_default_params.argtypes = [vp]
     L.arucohip_default_limits.argtypes = [vp, i, i, i]
     _lib = L
@@ -506,6 +507,17 @@ class Handle:
         Ka, da = _f32(K), _f32(dist)
         self._chk(self.L.arucohip_refine_candidate_lines(self.h, _ptr(xy), len(xy), _ptr(c), _ptr(Ka), _ptr(da), 0 if da is None else da.size))
         return c.reshape(4, 2)
+
+    def debug_refine_pixels(self, gray, corners, method, win=0, locked_wsize=0, width=None):
+        """The locked-corner pre-pass (locked_wsize > 0) and the SUBPIX / HARRIS refinement (method CORNER_SUBPIX with `win`, CORNER_HARRIS;
+        CORNER_NONE: the pre-pass alone) on `corners` (n x 2) of one gray frame [H][stride]; `width` < stride gives a padded frame, whose row
+        stride is kept on the device. Returns the refined corners (n x 2, float32)."""
+        g = np.ascontiguousarray(gray, dtype=np.uint8)
+        hgt, stride = g.shape
+        c = np.ascontiguousarray(corners, dtype=np.float32).reshape(-1, 2).copy()
+        self._chk(self.L.arucohip_debug_refine_pixels(self.h, _ptr(g), stride if width is None else int(width), hgt, stride, _ptr(c), len(c), int(method),
+                                                      int(win), int(locked_wsize)))
+        return c
 
     def bgr_to_gray(self, bgr):
         b = np.ascontiguousarray(bgr, dtype=np.uint8)

@@ -1564,6 +1564,63 @@ int arucohip_refine_candidate_lines(arucohip_handle* h, const int32_t* contour_x
     return ARUCOHIP_OK;
 }
 
+// Test hook: the locked-corner pre-pass (findCornerMaxima) and the SUBPIX / HARRIS refinement on caller-supplied corners. The corners become
+// candidates of frame 0 (four a candidate, id 0; a partly filled last one repeats its last corner) and the two launches of detect_core do
+// what they do for a batch's decoded candidates. Unlike stage_frames the frame keeps its row stride on the device, so that the kernels'
+// row indexing is part of what runs.
+int arucohip_debug_refine_pixels(arucohip_handle* h, const uint8_t* gray, int W, int H, size_t row_stride, float* corners_xy, int ncorners, int method,
+                                 int win, int locked_wsize) {
+    if (!h || !gray || !corners_xy) return ARUCOHIP_E_INVALID;
+    int rc = check_geometry(h, 1, W, H, row_stride);
+    if (rc) return rc;
+    if (row_stride > 4 * (size_t)h->lim.max_width) return fail(h, ARUCOHIP_E_INVALID, "row_stride beyond four times the handle's width");
+    if (method != ARUCOHIP_CORNER_NONE && method != ARUCOHIP_CORNER_HARRIS && method != ARUCOHIP_CORNER_SUBPIX)
+        return fail(h, ARUCOHIP_E_INVALID, "refine_pixels: method is not NONE, HARRIS or SUBPIX");
+    if (locked_wsize < 0) return fail(h, ARUCOHIP_E_INVALID, "locked-corner window < 0");
+    if (locked_wsize > 31) return fail(h, ARUCOHIP_E_UNSUPPORTED, "locked corners: window outside 1..31");
+    if (method == ARUCOHIP_CORNER_NONE && locked_wsize == 0) return fail(h, ARUCOHIP_E_INVALID, "refine_pixels: nothing to run");
+    if (method == ARUCOHIP_CORNER_SUBPIX && win > 15) return fail(h, ARUCOHIP_E_UNSUPPORTED, "SUBPIX window > 15");
+    if (method == ARUCOHIP_CORNER_SUBPIX && win < 1) return fail(h, ARUCOHIP_E_INVALID, "SUBPIX window < 1");
+    const Buffers& b = h->buf;
+    if (ncorners < 1) return fail(h, ARUCOHIP_E_INVALID, "ncorners < 1");
+    if (ncorners > 4 * b.cap_cands) return fail(h, ARUCOHIP_E_CAPACITY, "more corners than four times the handle's candidates per frame");
+    for (int i = 0; i < 2 * ncorners; i++)
+        if (!(std::fabs(corners_xy[i]) <= 65534.f)) return fail(h, ARUCOHIP_E_INVALID, "corner not finite or outside +-65534");   // NaN fails the comparison
+    HIPCHK(h, hipSetDevice(h->device));
+    const int nc = (ncorners + 3) / 4;
+    std::vector<Cand> v((size_t)nc);
+    for (int k = 0; k < nc; k++) {
+        Cand c{};
+        for (int j = 0; j < 4; j++) {
+            const int i = std::min(4 * k + j, ncorners - 1);
+            c.c[2 * j] = corners_xy[2 * i], c.c[2 * j + 1] = corners_xy[2 * i + 1];
+        }
+        c.cdesc = 0, c.swapped = 0, c.id = 0, c.nrot = 0;
+        v[k] = c;
+    }
+    DetectParams dp;
+    std::memset(&dp, 0, sizeof(dp));
+    dp.nthr = 1, dp.corner_method = method, dp.subpix_win = win, dp.locked = locked_wsize > 0, dp.locked_wsize = locked_wsize;
+    hipStream_t s = h->stream;
+    const size_t bytes = (size_t)(H - 1) * row_stride + (size_t)W;   // the last row need not be padded
+    HIPCHK(h, h->d_gray.reserve(bytes));
+    HIPCHK(h, hipMemcpyAsync(h->d_gray, gray, bytes, hipMemcpyHostToDevice, s));
+    FrameGeom g{};
+    g.width = W, g.height = H, g.row_stride = row_stride, g.frame_stride = (size_t)H * row_stride;
+    const int32_t n32 = nc;
+    HIPCHK(h, hipMemsetAsync(h->zero_block, 0, h->zero_words * sizeof(uint32_t), s));
+    HIPCHK(h, hipMemcpyAsync(b.cands, v.data(), v.size() * sizeof(Cand), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(b.ncands, &n32, sizeof(n32), hipMemcpyHostToDevice, s));
+    if (dp.locked) launch_locked_corners(s, h->d_gray, g, 1, dp, b);
+    if (method != ARUCOHIP_CORNER_NONE) launch_refine_pixels(s, h->d_gray, g, 1, dp, b);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(v.data(), b.cands, v.size() * sizeof(Cand), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    for (int i = 0; i < ncorners; i++) corners_xy[2 * i] = v[i / 4].c[2 * (i % 4)], corners_xy[2 * i + 1] = v[i / 4].c[2 * (i % 4) + 1];
+    h->last = Batch{};   // the lists no longer hold a batch
+    return ARUCOHIP_OK;
+}
+
 int arucohip_board_detect_batch(arucohip_handle* h, int nframes, const int32_t* ids, const float* obj, int nboard, int info_type, const float* K,
                                 const float* dist, int ndist, float marker_size, float repj_err_thres, int y_perp, arucohip_board_t* out, float* prob) {
     if (!h || !out || !prob) return ARUCOHIP_E_INVALID;

@@ -377,6 +377,14 @@ int arucohip_debug_cells(arucohip_handle* h, int frame, uint8_t* cells49, int ca
  * those generations (a pipeline lane, arucohip_set_pipeline_depth, owns none: its batch runs on one stream). */
 int arucohip_debug_counters(arucohip_handle* h, uint32_t* out8);
 
+/* Test hook: the pixel-domain corner kernels on corners of the caller's. gray: one host frame with its row stride (kept on the device,
+ * at most four times the handle's width); corners_xy: ncorners x,y pairs, refined in place. locked_wsize > 0 runs findCornerMaxima with that
+ * window (at most 31) first; method ARUCOHIP_CORNER_SUBPIX (win 1..15) or _HARRIS (win unused) runs the refinement; _NONE with locked_wsize > 0
+ * runs the pre-pass alone. ncorners is 1..4 * candidates_per_frame; every coordinate finite and within +-65534. Everything is checked before
+ * anything runs (ARUCOHIP_E_INVALID / _E_UNSUPPORTED / _E_CAPACITY). Uses the handle's candidate list: results of the last batch are gone afterwards. */
+int arucohip_debug_refine_pixels(arucohip_handle* h, const uint8_t* gray, int width, int height, size_t row_stride, float* corners_xy,
+                                 int ncorners, int method, int win, int locked_wsize);
+
 /* glibc's rand() outputs [offset, offset + count) after srand(seed), as the device makes them for arucohip_hrm_create_dictionary
  * (jump-ahead of the stream's state). count <= 2^24, offset + count < 2^48. */
 int arucohip_debug_hrm_stream(arucohip_handle* h, uint32_t seed, uint64_t offset, int count, uint32_t* out);

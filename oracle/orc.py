@@ -254,19 +254,22 @@ def refine_lines(contour, corners, K=None, dist=None):
     return c.reshape(4, 2)
 
 
-def corner_subpix(gray, pts, win=7, max_iter=8, eps=0.005):
+def corner_subpix(gray, pts, win=7, max_iter=8, eps=0.005, width=None):
+    """`width`: the frame's width where gray's rows are longer than it (a padded frame [H][stride]); the same for the three calls below."""
     g, gp = _u8(gray)
-    h, w = g.shape
+    h, st = g.shape
+    w = st if width is None else int(width)
     p = np.ascontiguousarray(pts, dtype=np.float32).copy()
-    lib().orc_corner_subpix(gp, w, h, w, p.ctypes.data_as(C.c_void_p), len(p.reshape(-1, 2)), win, max_iter, C.c_double(eps))
+    lib().orc_corner_subpix(gp, w, h, st, p.ctypes.data_as(C.c_void_p), len(p.reshape(-1, 2)), win, max_iter, C.c_double(eps))
     return p
 
 
-def corner_harris(gray, pts):
+def corner_harris(gray, pts, width=None):
     g, gp = _u8(gray)
-    h, w = g.shape
+    h, st = g.shape
+    w = st if width is None else int(width)
     p = np.ascontiguousarray(pts, dtype=np.float32).copy()
-    lib().orc_corner_harris(gp, w, h, w, p.ctypes.data_as(C.c_void_p), len(p.reshape(-1, 2)))
+    lib().orc_corner_harris(gp, w, h, st, p.ctypes.data_as(C.c_void_p), len(p.reshape(-1, 2)))
     return p
 
 
@@ -291,19 +294,21 @@ def canny(gray, low=10, high=220):
     return out
 
 
-def find_corner_maxima(gray, pts, wsize):
+def find_corner_maxima(gray, pts, wsize, width=None):
     g, gp = _u8(gray)
-    h, w = g.shape
+    h, st = g.shape
+    w = st if width is None else int(width)
     p = np.ascontiguousarray(pts, dtype=np.float32).copy()
-    lib().orc_find_corner_maxima(gp, w, h, w, p.ctypes.data_as(C.c_void_p), len(p.reshape(-1, 2)), int(wsize))
+    lib().orc_find_corner_maxima(gp, w, h, st, p.ctypes.data_as(C.c_void_p), len(p.reshape(-1, 2)), int(wsize))
     return p
 
 
-def corner_harris_window(gray, x0, y0, x1, y1):
+def corner_harris_window(gray, x0, y0, x1, y1, width=None):
     g, gp = _u8(gray)
-    h, w = g.shape
+    h, st = g.shape
+    w = st if width is None else int(width)
     out = np.zeros((y1 - y0, x1 - x0), np.float32)
-    lib().orc_corner_harris_window(gp, w, h, w, x0, y0, x1, y1, out.ctypes.data_as(C.c_void_p))
+    lib().orc_corner_harris_window(gp, w, h, st, x0, y0, x1, y1, out.ctypes.data_as(C.c_void_p))
     return out
 
 
