@@ -91,7 +91,7 @@ SYMBOLS = [
     "arucohip_get_stream", "arucohip_synchronize", "arucohip_detect", "arucohip_detect_batch", "arucohip_batch_status", "arucohip_batch_chunks",
     "arucohip_get_thresholded", "arucohip_get_candidates", "arucohip_threshold", "arucohip_detect_rectangles",
     "arucohip_warp", "arucohip_debug_num_contours", "arucohip_debug_contour", "arucohip_debug_candidates", "arucohip_debug_otsu",
-    "arucohip_debug_cells",
+    "arucohip_debug_cells", "arucohip_debug_start_candidates",
     "arucohip_board_detect", "arucohip_calculate_extrinsics", "arucohip_stage_times", "arucohip_stage_name",
     "arucohip_enable_timing", "arucohip_kernel_times", "arucohip_threshold_exec_ms", "arucohip_kernel_name",
     "arucohip_debug_counters", "arucohip_board_detect_batch",
@@ -179,6 +179,7 @@ def load():
     L.arucohip_threshold_exec_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]
     L.arucohip_kernel_name.argtypes = [i]
     L.arucohip_debug_counters.argtypes = [vp, vp]
+    L.arucohip_debug_start_candidates.argtypes = [vp, i, i, vp, i, vp]
     L.arucohip_board_detect_batch.argtypes = [vp, i, vp, vp, i, i, vp, vp, i, f, f, i, vp, vp]
     L.arucohip_default_recover.argtypes = [vp]
     L.arucohip_default_recover.restype = None
@@ -654,6 +655,15 @@ class Handle:
         n = C.c_int(0)
         self._chk(self.L.arucohip_debug_cells(self.h, frame, _ptr(c), cap, C.byref(n)))
         return c[:n.value].copy()
+
+    def debug_start_candidates(self, frame=0, kind=0):
+        """Border-start candidates of a frame after the run rule, walker mode only: the transition pixels y << 16 | x of the outer (kind 0)
+        or hole (kind 1) list, in the order the device appended them."""
+        n = C.c_int(0)
+        self._chk(self.L.arucohip_debug_start_candidates(self.h, int(frame), int(kind), None, 0, C.byref(n)), allow=(E_CAPACITY,))
+        out = np.zeros(max(n.value, 1), np.uint32)
+        self._chk(self.L.arucohip_debug_start_candidates(self.h, int(frame), int(kind), _ptr(out), n.value, C.byref(n)))
+        return out[:n.value].copy()
 
     def debug_contours(self, frame=0):
         n = C.c_int(0)

@@ -1394,6 +1394,34 @@ int arucohip_debug_contour(arucohip_handle* h0, int frame, int index, int* is_ho
     return ARUCOHIP_OK;
 }
 
+// start candidates of one frame and kind as candidates_sparse_kernel left them: the filled part of each plane's half of buf.trig
+int arucohip_debug_start_candidates(arucohip_handle* h0, int frame, int kind, uint32_t* yx, int cap, int* n) {
+    if (!h0 || !n || (!yx && cap > 0) || cap < 0 || kind < 0 || kind > 1) return ARUCOHIP_E_INVALID;
+    const int nthr = h0->last.nthr;
+    arucohip_handle* h = h0->last.holder(frame, &frame);
+    if (!h) return ARUCOHIP_E_INVALID;
+    if (h->buf.seg_mode) return fail(h0, ARUCOHIP_E_INVALID, "debug_start_candidates: this handle follows borders by waypoint segments and keeps no start-candidate lists");
+    HIPCHK(h, hipSetDevice(h->device));
+    const uint32_t half = h->buf.cap_trig / 2;
+    std::vector<uint2> recs;
+    int k = 0;
+    for (int t = 0; t < nthr; t++) {
+        const size_t plane = (size_t)frame * nthr + t;
+        uint32_t cnt = 0;
+        HIPCHK(h, hipMemcpyAsync(&cnt, h->buf.trig_cnt + plane * TRIG_CNT_STRIDE + kind, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        cnt = std::min(cnt, half);   // a list that overflowed holds its first half-capacity records (ST_TRIG_OVERFLOW is set)
+        if (!cnt) continue;
+        recs.resize(cnt);
+        HIPCHK(h, hipMemcpyAsync(recs.data(), h->buf.trig + plane * h->buf.cap_trig + (size_t)kind * half, cnt * sizeof(uint2), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (uint32_t i = 0; i < cnt; i++, k++)
+            if (k < cap) yx[k] = recs[i].y;
+    }
+    *n = k;
+    return k > cap ? ARUCOHIP_E_CAPACITY : ARUCOHIP_OK;
+}
+
 int arucohip_debug_counters(arucohip_handle* h, uint32_t* out8) {
     if (!h || !out8) return ARUCOHIP_E_INVALID;
     HIPCHK(h, hipSetDevice(h->device));

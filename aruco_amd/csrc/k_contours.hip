@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "bits_tiles.h"
+#include "cand_rule.h"
 #include "internal.h"
 #include "decode_device.h"
 
@@ -171,18 +172,38 @@ __global__ __launch_bounds__(CAND_THREADS) void candidates_kernel(CandArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Kernel 1b, walker mode: border-start candidates. Nine tiles in ten are empty and cannot hold a start (a start needs a set pixel in the
-// tile, or in its left or upper neighbour). The threshold kernel leaves a non-empty-tile bitmap (two words per 128-tile
-// strip: even tiles, odd tiles); a wave walks its share of the tile rows on those words alone, queues the tiles that can
-// hold a start and evaluates 64 queued tiles at a time with all lanes busy: the start rule, the run rule on the 16 pixels at
-// hand and — for the few runs that leave them — the 64-pixel run rule at once. A candidate survives only if it can be the first
-// pixel of its component / hole in raster order (outer - no set pixel 8-adjacent to its run of set pixels in the row above; hole -
+// Kernel 1b, walker mode: border-start candidates. Nine tiles in ten are empty. The threshold kernel leaves a non-empty-tile bitmap (two
+// words per 128-tile strip: even tiles, odd tiles); a wave walks its share of the tile rows on those words alone and queues the tiles that
+// can hold a start: a tile that holds a pixel, or an empty tile whose left AND upper neighbours both hold one. (An outer start is a set pixel
+// of the tile itself. A hole start is a clear pixel whose W and N neighbours are set; in a tile without a set pixel only column 0 has a W
+// neighbour that can be set - column 7 of the left tile - and only row 0 such an N neighbour - row 7 of the upper tile - so pixel (0, 0) is the
+// only one that can start anything, and only with the left tile's (row 0, column 7) and the upper tile's (row 7, column 0) set.)
+// 64 queued tiles are evaluated at a time, in two steps. One tile per lane: the start rule with 64-bit logic on the tile and its five
+// neighbours; the tile's rows -1 .. 7, joined with its right neighbour's to 16 pixels each, go to LDS. Then one start-rule pixel per lane:
+// the pixels of the round's tiles are dealt to the lanes densely (a wave prefix sum of the per-tile counts gives every tile its range of slots;
+// a tile writes (tile, bit) into its slots) and every lane runs the run rule for one of them on the 16 pixels at hand (cand_rule.h) and - for
+// the few runs that leave them - the 64-pixel run rule at once. A tile holds one start-rule pixel on average but up to 32, so a pass over the dealt pixels has nearly
+// every lane busy where a loop over each lane's own tile ran as long as the fullest tile of the round. A candidate survives only if it can be
+// the first pixel of its component / hole in raster order (outer - no set pixel 8-adjacent to its run of set pixels in the row above; hole -
 // no clear pixel directly above its run of clear pixels). Survivors are staged per wave and appended to two lists per plane (outer
 // starts in the first half of trig[plane], hole starts in the second half, so that a walker wavefront follows only one kind of
 // border) with one atomic per list and flush.
 // ---------------------------------------------------------------------------------------------
 constexpr int CQ_CAP = 192;       // queued tile ids per wave (a round consumes 64; at most 128 join per strip)
 constexpr int CS_CAP = 256;       // staged survivors per list and wave
+constexpr int CR_WORDS = 5;       // words of a tile's rows in LDS: rows -1 .. 7 at 16 pixels (the tile's byte | its right neighbour's << 8), two per word
+constexpr int CD_CAP = 112;       // dealt start-rule pixels per window (a round holds 60-80 on camera frames, up to 2048; further windows follow)
+
+// inclusive prefix sum over the 64 lanes, all of them active: four shifts inside each row of 16 lanes, then the row totals to the rows behind
+__device__ __forceinline__ uint32_t wave_prefix_sum(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);   // row_shr:1 (a lane without a source keeps 0)
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);   // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);   // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);   // row_shr:8
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);   // row_bcast:15 into rows 1 and 3
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);   // row_bcast:31 into rows 2 and 3
+    return v;
+}
 
 struct SparseArgs {
     const uint64_t* tiles;
@@ -201,13 +222,15 @@ __global__ __launch_bounds__(64) void candidates_sparse_kernel(SparseArgs a) {
     __shared__ uint32_t s_q[CQ_CAP];
     __shared__ uint2 s_keep[2][CS_CAP];
     __shared__ uint32_t s_n[2];
+    __shared__ uint32_t s_rows[WAVE * CR_WORDS];
+    __shared__ uint16_t s_deal[CD_CAP];
     const int plane = blockIdx.y, lane = threadIdx.x;
     const uint64_t* __restrict__ tiles = a.tiles + (size_t)plane * a.tnx * a.tny;
     const uint64_t* __restrict__ bits = a.tile_bits + (size_t)plane * a.tny * (2 * a.nstrips);
     const int ntx = a.tnx - 1, nty = a.tny - 1;          // real tiles
     const uint32_t half = a.cap_trig / 2;
     uint2* const out = a.trig + (size_t)plane * a.cap_trig;
-    uint32_t* const out_cnt = a.trig_cnt + plane * TRIG_CNT_STRIDE;
+    uint32_t* const out_cnt = a.trig_cnt + plane * TRIG_CNT_STRIDE;   // the plane's counter line (flag_overflow takes it as plane 0 of its own array)
     const uint64_t COL0 = 0x0101010101010101ull, COL7 = 0x8080808080808080ull;
     if (lane < 2) s_n[lane] = 0;
     __syncthreads();
@@ -225,7 +248,7 @@ __global__ __launch_bounds__(64) void candidates_sparse_kernel(SparseArgs a) {
                 if (base + j < half)
                     out[(size_t)kind * half + base + j] = s_keep[kind][j];
                 else
-                    flag_overflow(a.counters, a.trig_cnt, plane, ST_TRIG_OVERFLOW);
+                    flag_overflow(a.counters, out_cnt, 0, ST_TRIG_OVERFLOW);
             }
         }
         __syncthreads();
@@ -241,7 +264,7 @@ __global__ __launch_bounds__(64) void candidates_sparse_kernel(SparseArgs a) {
             if (slot < half)
                 out[(size_t)kind * half + slot] = rec;
             else
-                flag_overflow(a.counters, a.trig_cnt, plane, ST_TRIG_OVERFLOW);
+                flag_overflow(a.counters, out_cnt, 0, ST_TRIG_OVERFLOW);
         }
     };
     // one queued tile per lane: the tile and its five neighbours (loads only; two sets are put in flight before either is used)
@@ -262,7 +285,9 @@ __global__ __launch_bounds__(64) void candidates_sparse_kernel(SparseArgs a) {
         }
         return q;
     };
-    auto evaluate = [&](bool live, const TileSet& q) {
+    // a round: the tiles whose ids are s_q[qoff .. qoff + 63], one per live lane (all lanes call it)
+    auto evaluate = [&](bool live, const TileSet& q, uint32_t qoff) {
+        uint64_t m = 0;   // the tile's start-rule pixels, both kinds
         if (live) {
             const int ty = q.ty, tx = q.tx;
             const uint64_t T = q.T, L = q.L, U = q.U, UL = q.UL, UR = q.UR, Rt = q.Rt;
@@ -283,27 +308,45 @@ __global__ __launch_bounds__(64) void candidates_sparse_kernel(SparseArgs a) {
                 const uint64_t lower = (T >> 8) | (Wn >> 8) | (E >> 8);            // S, SW, SE of rows 0..6
                 outer &= ~(~(E | lower) & 0x00FFFFFFFFFFFFFFull);
             }
-            const uint32_t base = ((uint32_t)(8 * ty) << 16) | (uint32_t)(8 * tx);
-            uint64_t m = outer | hole;
-            while (m) {
-                const int b = __builtin_ctzll(m);
-                m &= m - 1;
-                const int qr = b >> 3, j = b & 7;
-                const uint32_t kind = (uint32_t)(hole >> b) & 1u;
-                const uint32_t mid = ((((uint32_t)(T >> (8 * qr)) & 0xFFu) | (((uint32_t)(Rt >> (8 * qr)) & 0xFFu) << 8)) >> j);
-                const uint32_t up = ((((uint32_t)(N >> (8 * qr)) & 0xFFu) | (((uint32_t)(NRt >> (8 * qr)) & 0xFFu) << 8)) >> j);
-                const int avail = 16 - j;
-                const uint32_t pos = base + ((uint32_t)qr << 16) + (uint32_t)j;
-                const uint32_t runbits = (kind ? mid : ~mid) | (1u << avail);
-                const int Lr = __builtin_ctz(runbits);
-                const int hi = kind ? min(Lr - 1, avail - 1) : min(Lr, avail - 1);
-                const uint32_t span = ((2u << hi) - 1u) & (kind ? ~1u : ~3u);
-                if (((kind ? ~up : up) & span) != 0) continue;
-                // a run that leaves the 16 pixels at hand takes the 64-pixel test at once (rare)
-                if (Lr < avail || run_rule_tiles(tiles, a.tnx, (int)(pos & 0xFFFFu), (int)(pos >> 16), (int)kind)) stage((int)kind, make_uint2(kind, pos));
-            }
+            m = outer | hole;
+            // The bytes of N are rows -1 .. 6 of the tile's columns, those of NRt the same rows of the right neighbour's: interleaved they are the
+            // 16-pixel rows -1 .. 6, and row 7 comes from T and Rt. Row r sits at half-word r + 1, so a pixel's row above and its own row are neighbours.
+            const uint32_t nl = (uint32_t)N, nh = (uint32_t)(N >> 32), rl = (uint32_t)NRt, rh = (uint32_t)(NRt >> 32);
+            uint32_t* w = s_rows + lane * CR_WORDS;
+            w[0] = __builtin_amdgcn_perm(rl, nl, 0x05010400u);
+            w[1] = __builtin_amdgcn_perm(rl, nl, 0x07030602u);
+            w[2] = __builtin_amdgcn_perm(rh, nh, 0x05010400u);
+            w[3] = __builtin_amdgcn_perm(rh, nh, 0x07030602u);
+            w[4] = __builtin_amdgcn_perm((uint32_t)(Rt >> 32), (uint32_t)(T >> 32), 0x0C0C0703u);
         }
-        __syncthreads();
+        // deal the round's start-rule pixels to the lanes: tile `lane` owns the slots [p, p + popcount(m))
+        const uint32_t cnt = (uint32_t)__popcll(m);
+        const uint32_t incl = wave_prefix_sum(cnt);
+        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, WAVE - 1);
+        uint32_t p = incl - cnt;
+        for (uint32_t w0 = 0; w0 < total; w0 += CD_CAP) {       // wave-uniform
+            while (m && p - w0 < (uint32_t)CD_CAP) {            // a lane with pixels left has p >= w0
+                s_deal[p - w0] = (uint16_t)(((uint32_t)lane << 6) | (uint32_t)__builtin_ctzll(m));
+                m &= m - 1;
+                p++;
+            }
+            __syncthreads();
+            const uint32_t wn = min(total - w0, (uint32_t)CD_CAP);
+            for (uint32_t k = lane; k < wn; k += WAVE) {
+                const uint32_t e = s_deal[k];
+                const uint32_t t = e >> 6, qr = (e >> 3) & 7u, j = e & 7u;
+                const uint32_t* rw = s_rows + t * CR_WORDS + (qr >> 1);
+                const uint32_t x = (uint32_t)(((uint64_t)rw[0] | ((uint64_t)rw[1] << 32)) >> (16 * (qr & 1u)));   // row above | own row << 16
+                uint32_t kind;
+                const int verdict = cand_rule16(x, j, &kind);
+                if (verdict != CAND_DROP) {
+                    const uint32_t pos = (s_q[qoff + t] << 3) + (qr << 16) + j;   // the tile id is ty << 16 | tx
+                    // a run that leaves the 16 pixels at hand takes the 64-pixel test at once (rare)
+                    if (verdict == CAND_KEEP || run_rule_tiles(tiles, a.tnx, (int)(pos & 0xFFFFu), (int)(pos >> 16), (int)kind)) stage((int)kind, make_uint2(kind, pos));
+                }
+            }
+            __syncthreads();
+        }
         if (max(s_n[0], s_n[1]) > CS_CAP - 64) flush();   // wave-uniform: room for another round's typical yield
     };
 
@@ -326,13 +369,15 @@ __global__ __launch_bounds__(64) void candidates_sparse_kernel(SparseArgs a) {
             const uint64_t A = word_of(curw, 2 * st), Bm = word_of(curw, 2 * st + 1);
             const uint64_t UA = word_of(curw, nw + 2 * st), UB = word_of(curw, nw + 2 * st + 1);
             const uint64_t carry = st > 0 ? (word_of(curw, 2 * st - 1) >> 63) : 0ull;          // the previous strip's last (odd) tile
-            // a tile can hold a start if it, its left or its upper neighbour holds a pixel
-            const uint64_t needA = A | (Bm << 1) | carry | UA, needB = Bm | A | UB;
-#pragma unroll
+            // a tile can hold a start if it holds a pixel, or if its left and its upper neighbour both do (pixel (0, 0) of an empty tile: see above).
+            // The left neighbour of even tile i is odd tile i - 1 (the previous strip's last one for i = 0), that of odd tile i is even tile i.
+            const uint64_t needA = A | (((Bm << 1) | carry) & UA), needB = Bm | (A & UB);
+            const int tx0 = 128 * st + 2 * lane;
+            const bool actA = ((needA >> lane) & 1ull) && tx0 < ntx, actB = ((needB >> lane) & 1ull) && tx0 + 1 < ntx;
+#pragma unroll 1   // one copy of the two rounds below instead of two: the kernel stays inside its scalar registers
             for (int odd = 0; odd < 2; odd++) {
-                const uint64_t need = odd ? needB : needA;
-                const int tx = 128 * st + 2 * lane + odd;
-                const bool act = ((need >> lane) & 1ull) && tx < ntx;
+                const int tx = tx0 + odd;
+                const bool act = odd ? actB : actA;
                 const unsigned long long bal = __ballot(act);
                 if (bal) {
                     if (act) s_q[qn + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = ((uint32_t)ty << 16) | (uint32_t)tx;
@@ -341,8 +386,8 @@ __global__ __launch_bounds__(64) void candidates_sparse_kernel(SparseArgs a) {
                     if (qn >= 128) {   // keep room for the next 64 joins; two rounds' loads are in flight together
                         qn -= 128;
                         const TileSet q0 = fetch(true, s_q[qn + 64 + lane]), q1 = fetch(true, s_q[qn + lane]);
-                        evaluate(true, q0);
-                        evaluate(true, q1);
+                        evaluate(true, q0, qn + 64);
+                        evaluate(true, q1, qn);
                     }
                 }
             }
@@ -352,15 +397,18 @@ __global__ __launch_bounds__(64) void candidates_sparse_kernel(SparseArgs a) {
         const bool l0 = qn >= 64 ? true : (uint32_t)lane < qn;
         const bool l1 = qn >= 64 && (uint32_t)lane < qn - 64;
         const TileSet q0 = fetch(l0, l0 ? s_q[lane] : 0u), q1 = fetch(l1, l1 ? s_q[64 + lane] : 0u);
-        if (qn > 0) evaluate(l0, q0);
-        if (qn > 64) evaluate(l1, q1);
+        if (qn > 0) evaluate(l0, q0, 0);
+        if (qn > 64) evaluate(l1, q1, 64);
     }
     flush();
 }
 
 void launch_start_candidates(hipStream_t s, const FrameGeom& g, int nplanes, const Buffers& b, int min_contour) {
     if (!b.seg_mode) {
-        constexpr int kWaves = 32;   // waves per plane (4 0.25, 8 0.18, 16 0.13, 32 0.13 ms per 512 frames)
+        // waves per plane. A batch's planes fill the chip on their own: 16 (round 2, a lane per tile's own pixels: 4 0.25, 8 0.18, 16 0.13, 32 0.13 ms per
+        // 512 frames; with one candidate per lane the headline is 457.5-458.1 k frames/s at 16 against 450.9-456.7 k at 32, profiles/start_candidates_ab.txt).
+        // A few planes (one frame per call on a walker handle) are a serial chain on an empty chip: they keep 32, each wave half as many tile rows.
+        const int kWaves = nplanes >= 64 ? 16 : 32;
         SparseArgs a;
         a.drop_single = min_contour >= 1;
         a.tiles = b.tiles, a.tile_bits = b.tile_bits, a.tnx = tiles_x(g.width), a.tny = tiles_y(g.height), a.nstrips = tile_strips(g.width);

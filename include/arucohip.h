@@ -362,6 +362,11 @@ int arucohip_refine_candidate_lines(arucohip_handle* h, const int32_t* contour_x
 int arucohip_debug_num_contours(arucohip_handle* h, int frame, int* n);
 int arucohip_debug_contour(arucohip_handle* h, int frame, int index, int* is_hole, int* start_x, int* start_y, int16_t* xy,
                            int cap_points, int* n_points);
+/* Border-start candidates of a frame after the run rule (walker mode only: a handle whose borders go through the waypoint segments returns
+ * ARUCOHIP_E_INVALID): the transition pixels y << 16 | x of the outer (kind 0: the first pixel of a run of set pixels) or hole (kind 1: the clear
+ * pixel right of a set one) list, the frame's threshold planes one after the other, in the order the device appended them (any). *n is the list's
+ * length; ARUCOHIP_E_CAPACITY when it exceeds cap. */
+int arucohip_debug_start_candidates(arucohip_handle* h, int frame, int kind, uint32_t* yx, int cap, int* n);
 /* Candidates after detectRectangles in reference order: integer quad, decoded id (-1 none), nRotations. */
 int arucohip_debug_candidates(arucohip_handle* h, int frame, float* quads0, int32_t* ids, int32_t* nrot, int cap, int* n);
 /* Otsu threshold (cv::threshold THRESH_OTSU inside the decoders, arucofidmarkers.cpp:169 / highlyreliablemarkers.cpp:346) of every candidate's patch,
