@@ -917,61 +917,51 @@ int launch_walkers(hipStream_t s, const WalkFork& fk, const FrameGeom& g, int np
 // ---------------------------------------------------------------------------------------------
 // Kernel 3: one wave per surviving border: emit points, approxPolyDP, convexity, min side -> Quad
 // ---------------------------------------------------------------------------------------------
-// Wave reductions on the DPP network (no LDS crossbar trips): butterfly inside each row of 16 lanes, then row
-// broadcasts; the result is read from lane 63.
-// max / min of the wave on the DPP network with the shuffle folded into the operation (v_max_u32_dpp: one instruction per step; written as
-// "move with DPP, then max" the compiler keeps two). Rows that a row_bcast step does not address keep their value.
-#define DPP_FOLD(op, v)                                                                                         \
-    asm volatile("s_nop 4\n\t" /* the compiler does not see a DPP read here: cover the VGPR-write (2) and VALU-EXEC-write (5) wait states */ \
-                 op " %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"                            \
-                 "s_nop 1\n\t" op " %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"             \
-                 "s_nop 1\n\t" op " %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"                 \
-                 "s_nop 1\n\t" op " %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"                      \
-                 "s_nop 1\n\t" op " %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"                    \
-                 "s_nop 1\n\t" op " %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"                    \
-                 "s_nop 1"                                                                                      \
-                 : "+v"(v))
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-    DPP_FOLD("v_max_u32_dpp", v);
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+// Reductions on the DPP network (no LDS crossbar trips) over the G lanes that serve one border: the whole wave (G = 64) or each of its halves on its
+// own (G = 32). The shuffle is folded into the operation (v_max_u32_dpp: one instruction per step; written as "move with DPP, then max" the compiler
+// keeps two). Butterfly inside each row of 16 lanes, then row broadcasts; rows that a row_bcast step does not address keep their value. After
+// row_bcast:15 row 1 ends with the result of lanes 0..31 and row 3 with that of lanes 32..63, and no step has read across the halves; row_bcast:31
+// (G = 64 only) joins the two in row 3. The result is read from the group's last lane: for G = 64 that is one readlane, which the compiler knows to
+// be uniform, so the control flow that hangs on it stays on the scalar unit.
+#define DPP_FOLD_ROWS(op)                                                                                                          \
+    "s_nop 4\n\t" /* the compiler does not see a DPP read here: cover the VGPR-write (2) and VALU-EXEC-write (5) wait states */ \
+    op " %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"                                                            \
+    "s_nop 1\n\t" op " %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"                                             \
+    "s_nop 1\n\t" op " %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"                                                 \
+    "s_nop 1\n\t" op " %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"                                                      \
+    "s_nop 1\n\t" op " %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+#define DPP_FOLD(G, op, v)                                                                                                                      \
+    do {                                                                                                                                        \
+        if constexpr ((G) == WAVE)                                                                                                              \
+            asm volatile(DPP_FOLD_ROWS(op) "s_nop 1\n\t" op " %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t" "s_nop 1" : "+v"(v)); \
+        else                                                                                                                                    \
+            asm volatile(DPP_FOLD_ROWS(op) "s_nop 1" : "+v"(v));                                                                              \
+    } while (0)
+template <int G>
+__device__ __forceinline__ uint32_t group_result(uint32_t v, bool upper) {
+    static_assert(G == WAVE || G == WAVE / 2, "a border has the wave or one of its halves");
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+    if constexpr (G == WAVE) return hi;
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)v, 31);
+    return upper ? hi : lo;
 }
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-    DPP_FOLD("v_min_u32_dpp", v);
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+template <int G>
+__device__ __forceinline__ uint32_t group_max_u32(uint32_t v, bool upper) {
+    DPP_FOLD(G, "v_max_u32_dpp", v);
+    return group_result<G>(v, upper);
+}
+template <int G>
+__device__ __forceinline__ uint32_t group_min_u32(uint32_t v, bool upper) {
+    DPP_FOLD(G, "v_min_u32_dpp", v);
+    return group_result<G>(v, upper);
 }
 // argmax with first-maximum tie break: every lane brings its best (value, position), positions are unique; a lane whose elements are all zero
 // (or that has none) brings (0, 0xFFFFFFFF), so a maximum of zero comes back with position 0xFFFFFFFF
-__device__ __forceinline__ void wave_argmax_first(uint32_t val, uint32_t idx, uint32_t* max_val, uint32_t* first_idx) {
-    const uint32_t mv = wave_max_u32(val);
+template <int G>
+__device__ __forceinline__ void group_argmax_first(uint32_t val, uint32_t idx, bool upper, uint32_t* max_val, uint32_t* first_idx) {
+    const uint32_t mv = group_max_u32<G>(val, upper);
     *max_val = mv;
-    *first_idx = wave_min_u32(val == mv ? idx : 0xFFFFFFFFu);
-}
-
-// The same reductions for the two halves of a wave at once (round 4: two borders per wave, one per half): the butterfly inside the rows of 16 lanes and
-// the first row broadcast leave the maximum of lanes 0..31 in row 1 and that of lanes 32..63 in row 3; no step reads across the halves.
-#define DPP_FOLD_HALF(op, v)                                                                                    \
-    asm volatile("s_nop 4\n\t"                                                                                  \
-                 op " %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"                            \
-                 "s_nop 1\n\t" op " %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"             \
-                 "s_nop 1\n\t" op " %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"                 \
-                 "s_nop 1\n\t" op " %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"                      \
-                 "s_nop 1\n\t" op " %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"                    \
-                 "s_nop 1"                                                                                      \
-                 : "+v"(v))
-__device__ __forceinline__ uint32_t half_max_u32(uint32_t v, bool upper) {
-    DPP_FOLD_HALF("v_max_u32_dpp", v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)v, 31), hi = (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-    return upper ? hi : lo;
-}
-__device__ __forceinline__ uint32_t half_min_u32(uint32_t v, bool upper) {
-    DPP_FOLD_HALF("v_min_u32_dpp", v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)v, 31), hi = (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-    return upper ? hi : lo;
-}
-__device__ __forceinline__ void half_argmax_first(uint32_t val, uint32_t idx, bool upper, uint32_t* max_val, uint32_t* first_idx) {
-    const uint32_t mv = half_max_u32(val, upper);
-    *max_val = mv;
-    *first_idx = half_min_u32(val == mv ? idx : 0xFFFFFFFFu, upper);
+    *first_idx = group_min_u32<G>(val == mv ? idx : 0xFFFFFFFFu, upper);
 }
 
 // The "farthest point" scans of approxPolyDP over the cyclic index range first, first + 1, ... (len entries, first < count, len <= count) as two
@@ -988,7 +978,7 @@ __device__ __forceinline__ uint32_t scan_value(uint32_t pt, uint32_t anchor, uin
     const int cr = __builtin_amdgcn_sdot2(d, as_s2(w), 0, false);
     return (uint32_t)max(cr, -cr);
 }
-template <bool CROSS, int STRIDE = WAVE>
+template <bool CROSS, int STRIDE>
 __device__ __forceinline__ void scan_cyclic(const uint32_t* P32, int count, int first, int len, int lane, uint32_t anchor, uint32_t w, uint32_t& bd, uint32_t& bk) {
     bd = 0, bk = 0xFFFFFFFFu;
     const int lenA = min(len, count - first);
@@ -1004,15 +994,14 @@ __device__ __forceinline__ void scan_cyclic(const uint32_t* P32, int count, int 
     }
 }
 
-#ifndef EMIT_LANES_N
-#define EMIT_LANES_N 64   // round 3: the whole wave emits. Round 2 kept 32 (less LDS, more waves: 0.58 against 0.67 ms one batch at a time); with the
-                          // batches in flight the vector-instruction count is what counts: 446.3k / 447.6k against 443.2k / 442.5k fps, same box, alternating
-#endif
-constexpr int EMIT_LANES = EMIT_LANES_N;   // lanes that emit points at a time (each needs a 32x32 block in LDS)
 #ifndef QP_LDS_N
 #define QP_LDS_N 1024
 #endif
 constexpr int QP_LDS = QP_LDS_N;   // points of a border kept in LDS; longer borders are scanned in HBM (their pool range)
+#ifndef DUAL_MAX_N
+#define DUAL_MAX_N 512
+#endif
+constexpr int DUAL_MAX = DUAL_MAX_N;   // points of a border that shares its wave with another; 1024 (with QP_LDS_N=2048) measured: see profiles/r04_experiments.txt
 
 struct QuadArgs {
     const uint64_t* tiles;
@@ -1100,16 +1089,26 @@ __device__ __forceinline__ void polygon_to_quad(const QuadArgs& a, const Contour
     }
 }
 
-// One border -> at most one quad. P holds the border's points: LDS (LDSP, up to QP_LDS points) or the border's own pool range.
-template <bool LDSP>
-__device__ __forceinline__ void border_to_quad(const QuadArgs& a, const ContourDesc& cd, const uint32_t ci, short2* P, int (*s_stack)[2], short2* s_out,
-                                               int& s_outn, uint32_t* rows) {
-    const int lane = threadIdx.x;
+// One border -> at most one quad, with G lanes on the border. G = 64: one border per wave, its points in LDS (LDSP, up to QP_LDS points) or in the
+// border's own pool range. G = 32: TWO borders of at most DUAL_MAX points per wave, one per half (lanes 0..31 / 32..63; the median kept border has
+// 460 points); cd and ci are then each half's own. One border per wave leaves half the emitting lanes idle (29 checkpoints for 64 lanes) and pays
+// the fixed cost of every approxPolyDP iteration - stack traffic, two reductions on the DPP network, the fp64 test, the barriers; about 150
+// instructions against 10 per 64 points scanned - per border; with two, the halves run the same instruction stream on their own border. Every
+// quantity below is uniform per group of G lanes: for G = 64 wave-uniform, so that instantiation's control flow is scalar.
+template <int G, bool LDSP>
+__device__ __forceinline__ void border_to_quad(const QuadArgs& a, const ContourDesc& cd, const uint32_t ci, short2* Plds, int (*s_stack)[16][2], short2 (*s_out)[12],
+                                               uint32_t* rows) {
+    static_assert(G == WAVE || (G == WAVE / 2 && LDSP), "a half wave's border is one of at most DUAL_MAX points in LDS");
+    // h = lane / G, with the 0 of G = 64 written out: the compiler does not conclude lane < 64 from the launch bounds, and an h it takes to differ
+    // between lanes turns that instantiation's stack and vertex accesses, and every branch behind them, divergent
+    const int lane = threadIdx.x, h = G == WAVE ? 0 : lane / G, hl = lane - h * G;
+    const bool upper = h != 0;
+    short2* P = LDSP ? Plds + h * DUAL_MAX : a.pool + cd.pool_off;
     const int count = cd.n;
     // ---- points: already emitted (segment pipeline) or every lane resumes the walk at one checkpoint and records CK points
     if (a.from_pool) {
         if (LDSP)
-            for (int i = lane; i < count; i += WAVE) P[i] = a.pool[cd.pool_off + i];
+            for (int i = hl; i < count; i += G) P[i] = a.pool[cd.pool_off + i];
     } else {
         const uint64_t* tiles = a.tiles + (size_t)cd.plane * a.tnx * a.tny;
         const int ncp = (count + CK - 1) / CK;
@@ -1119,16 +1118,14 @@ __device__ __forceinline__ void border_to_quad(const QuadArgs& a, const ContourD
         // whole stretch because both of its ends are known - this checkpoint and the next one (the border's start for the last stretch): a path
         // of L steps from A to B cannot leave their bounding box by more than (L - |dx|) / 2 columns or (L - |dy|) / 2 rows (a pixel further
         // out would need more than L steps to be reached from A and left towards B), so with the ring of neighbours the stretch spans at most
-        // 19 pixels each way and a tile-aligned block of 32 that holds it always exists. (Until round 3 the block was placed by the heading at
-        // the checkpoint and re-centred after 8 steps where needed - almost always for some lane: a second load per round, a fifth of the
-        // kernel's vector instructions.)
-        // EMIT_LANES lanes at a time: the kernel's speed follows its occupancy (12 KB of LDS per wave = 12 waves per CU measured
-        // 0.67 ms, 24 KB 1.08 ms), and the blocks of a half wave cost 4 KB instead of 8
+        // 19 pixels each way and a tile-aligned block of 32 that holds it always exists.
+        // The trip count is wave-uniform: a border's own number of rounds for G = 64, the one round that DUAL_MAX points need for G = 32.
         uint32_t* P32 = (uint32_t*)P;
-        const uint32_t* rb = rows + lane - EMIT_LANES;
-        for (int k0 = 0; k0 < ncp; k0 += EMIT_LANES) {
-            const int k = k0 + lane;
-            if (lane >= EMIT_LANES || k >= ncp) continue;
+        const uint32_t* rb = rows + lane - WAVE;
+        const int kend = G == WAVE ? ncp : (DUAL_MAX + CK - 1) / CK;
+        for (int k0 = 0; k0 < kend; k0 += G) {
+            const int k = k0 + hl;
+            if (k >= ncp) continue;
             const uint32_t c = ckp[k];
             const uint32_t pos = (c & 0x3FFFu) | (((c >> 14) & 0x3FFFu) << 16);
             const int n0 = k * CK, n1 = min(n0 + CK, count);
@@ -1143,24 +1140,24 @@ __device__ __forceinline__ void border_to_quad(const QuadArgs& a, const ContourD
             const int ex = (L - abs(bx - ax)) >> 1, ey = (L - abs(by - ay)) >> 1;
             const int tx0 = min(max((min(ax, bx) - ex - 1) >> 3, 0), a.tnx - 4), ty0 = min(max((min(ay, by) - ey - 1) >> 3, 0), a.tny - 4);
             TileBlock blk;
-            tb_load_at<EMIT_LANES>(tiles, a.tnx, tx0, ty0, rows, lane, blk);
+            tb_load_at<WAVE>(tiles, a.tnx, tx0, ty0, rows, lane, blk);
             const uint32_t base1 = tb_base1(blk);
             uint32_t lp = pos - base1, s1c = tb_s1c((int)(c >> 28));
 #pragma unroll
             for (int j = 0; j < CK; j++) {
                 if (n0 + j < n1) {
                     P32[n0 + j] = lp + base1;
-                    tb_step<EMIT_LANES>(rb, lp, s1c);
+                    tb_step<WAVE>(rb, lp, s1c);
                 }
             }
         }
     }
     __syncthreads();
     if (LDSP && !a.from_pool)
-        for (int i = lane; i < count; i += WAVE) a.pool[cd.pool_off + i] = P[i];
+        for (int i = hl; i < count; i += G) a.pool[cd.pool_off + i] = P[i];
 
-    // ---- cv::approxPolyDP(closed), restated for a wavefront: every "farthest point" scan is a 64-lane argmax with
-    // first-maximum tie break (lowest scan position), control flow is wave-uniform.
+    // ---- cv::approxPolyDP(closed), restated for G lanes: every "farthest point" scan is a G-lane argmax with first-maximum tie break (lowest scan
+    // position)
     double eps = (double)count * 0.05;
     eps *= eps;
     int pos = 0, rs_start = 0;
@@ -1169,149 +1166,13 @@ __device__ __forceinline__ void border_to_quad(const QuadArgs& a, const ContourD
     for (int it = 0; it < 3; it++) {
         pos = (pos + rs_start) % count;
         uint32_t bd, bk, maxd, kmax;
-        scan_cyclic<false>(PW, count, pos + 1 == count ? 0 : pos + 1, count - 1, lane, PW[pos], 0u, bd, bk);   // j = 1 .. count-1 at scan position j - 1
-        wave_argmax_first(bd, bk, &maxd, &kmax);
+        scan_cyclic<false, G>(PW, count, pos + 1 == count ? 0 : pos + 1, count - 1, hl, PW[pos], 0u, bd, bk);   // j = 1 .. count-1 at scan position j - 1
+        group_argmax_first<G>(bd, bk, upper, &maxd, &kmax);
         if (maxd > 0) rs_start = (int)kmax + 1;
         le_eps = (double)maxd <= eps;
     }
     int top = 0, outn = 0;
     bool reject = false;
-    if (lane == 0) s_outn = 0;
-    if (!le_eps) {
-        int sl_start = pos % count;
-        int sl_end = (rs_start + sl_start) % count;
-        if (lane == 0) {
-            s_stack[0][0] = sl_end, s_stack[0][1] = sl_start;   // right_slice
-            s_stack[1][0] = sl_start, s_stack[1][1] = sl_end;   // slice
-        }
-        top = 2;
-    } else {
-        if (lane == 0) s_out[0] = P[pos];
-        outn = 1;
-    }
-    __syncthreads();
-    while (top > 0) {
-        // outn + top never falls and ends as the vertex count, so this refuses the borders that approxPolyDP's recursion leaves with more than 8
-        // vertices. That none of them ends as 4 is EMPIRICAL and thinly supported: the clean-up pass can take five vertices off nine (it steps over the
-        // one behind every removal). A seeded search (tests/quad_ref.py search_early_reject; DESIGN.md) drew 12711 shapes, of which only 57 borders had
-        // more than 8 vertices here (9 or 10, never more), and none of those ended as a quad; borders of 7 and 8 vertices do end as quads.
-        // tests/test_gpu_quad_edges.py pins quads kept at 7 and 8 against shapes refused at 8, 9 and more.
-        if (outn + top > 8) {
-            reject = true;
-            break;
-        }
-        --top;
-        const int sl_start = s_stack[top][0], sl_end = s_stack[top][1];
-        __syncthreads();
-        const short2 ep = P[sl_end], sp = P[sl_start];
-        int len = sl_end - sl_start;
-        if (len <= 0) len += count;
-        bool small;
-        int split = 0;
-        if (len > 1) {
-            const int dx = ep.x - sp.x, dy = ep.y - sp.y;
-            // |(pt.y - sp.y) * dx - (pt.x - sp.x) * dy| = |(pt - sp) . (-dy, dx)|
-            const uint32_t w = ((uint32_t)(-dy) & 0xFFFFu) | ((uint32_t)dx << 16);
-            uint32_t bd, bq, maxd_u, qmax;
-            scan_cyclic<true>(PW, count, sl_start + 1 == count ? 0 : sl_start + 1, len - 1, lane, PW[sl_start], w, bd, bq);
-            wave_argmax_first(bd, bq, &maxd_u, &qmax);
-            double maxd = (double)maxd_u;
-            int q = qmax == 0xFFFFFFFFu ? 0 : (int)qmax;
-            split = sl_start + 1 + q;
-            if (split >= count) split -= count;
-            small = maxd * maxd <= eps * ((double)dx * (double)dx + (double)dy * (double)dy);
-        } else {
-            small = true;
-        }
-        if (small) {
-            if (lane == 0) s_out[outn] = sp;
-            outn++;
-        } else {
-            if (lane == 0) {
-                s_stack[top][0] = split, s_stack[top][1] = sl_end;
-                s_stack[top + 1][0] = sl_start, s_stack[top + 1][1] = split;
-            }
-            top += 2;
-        }
-        __syncthreads();
-    }
-    if (reject || outn < 4) return;
-    if (lane == 0) polygon_to_quad(a, cd, ci, s_out, outn, eps);
-}
-
-// Round 4: TWO borders per wave, one per half (lanes 0..31 / 32..63), for borders of at most DUAL_MAX points - the median kept border has 460. One
-// border per wave left half the emitting lanes idle (29 checkpoints for 64 lanes) and paid the fixed cost of every approxPolyDP iteration - stack
-// traffic, two reductions on the DPP network, the fp64 test, the barriers; about 150 instructions against 10 per 64 points scanned - per border; here
-// the two halves run the same instruction stream on their own border. Every quantity that was wave-uniform is uniform per half; `valid` is false
-// for a half without a border. Same arithmetic, same scan order, same tie breaks as border_to_quad.
-#ifndef DUAL_MAX_N
-#define DUAL_MAX_N 512
-#endif
-constexpr int DUAL_MAX = DUAL_MAX_N;   // 1024 (with QP_LDS_N=2048) measured: see profiles/r04_experiments.txt
-__device__ __forceinline__ void border_pair_to_quads(const QuadArgs& a, const ContourDesc& cd, const uint32_t ci, const bool valid, short2* Pbase, int (*s_stack)[16][2],
-                                                     short2 (*s_out)[12], uint32_t* rows) {
-    const int lane = threadIdx.x, h = lane >> 5, hl = lane & 31;
-    const bool upper = h != 0;
-    short2* P = Pbase + h * DUAL_MAX;
-    uint32_t* P32 = (uint32_t*)P;
-    const int count = valid ? cd.n : 1;
-    if (a.from_pool) {
-        if (valid)
-            for (int i = hl; i < count; i += 32) P[i] = a.pool[cd.pool_off + i];
-    } else {
-        // a lane per checkpoint (at most 32 per border): resume the walk there and record CK points from the lane's own block (border_to_quad)
-        const uint64_t* tiles = a.tiles + (size_t)cd.plane * a.tnx * a.tny;
-        const int ncp = (count + CK - 1) / CK;
-        const uint32_t* ckp = cd.ck_off == 0xFFFFFFFFu ? (const uint32_t*)(a.pool + cd.pool_off) - ncp : a.walk_scratch + cd.ck_off;
-        const uint32_t* rb = rows + lane - 64;
-        for (int k = hl; k < (DUAL_MAX + CK - 1) / CK; k += 32) {   // one round for borders of up to 512 points
-            if (!(valid && k < ncp)) continue;
-            const uint32_t c = ckp[k];
-            const uint32_t pos = (c & 0x3FFFu) | (((c >> 14) & 0x3FFFu) << 16);
-            const int n0 = k * CK, n1 = min(n0 + CK, count);
-            int bx, by;   // where the stretch ends
-            if (k + 1 < ncp) {
-                const uint32_t cn = ckp[k + 1];
-                bx = (int)(cn & 0x3FFFu), by = (int)((cn >> 14) & 0x3FFFu);
-            } else {
-                bx = cd.x0, by = cd.y0;
-            }
-            const int ax = (int)(pos & 0xFFFFu), ay = (int)(pos >> 16), L = n1 - n0;
-            const int ex = (L - abs(bx - ax)) >> 1, ey = (L - abs(by - ay)) >> 1;
-            const int tx0 = min(max((min(ax, bx) - ex - 1) >> 3, 0), a.tnx - 4), ty0 = min(max((min(ay, by) - ey - 1) >> 3, 0), a.tny - 4);
-            TileBlock blk;
-            tb_load_at<64>(tiles, a.tnx, tx0, ty0, rows, lane, blk);
-            const uint32_t base1 = tb_base1(blk);
-            uint32_t lp = pos - base1, s1c = tb_s1c((int)(c >> 28));
-#pragma unroll
-            for (int j = 0; j < CK; j++) {
-                if (n0 + j < n1) {
-                    P32[n0 + j] = lp + base1;
-                    tb_step<64>(rb, lp, s1c);
-                }
-            }
-        }
-    }
-    __syncthreads();
-    if (!a.from_pool && valid)
-        for (int i = hl; i < count; i += 32) a.pool[cd.pool_off + i] = P[i];
-
-    // ---- cv::approxPolyDP(closed) per half
-    double eps = (double)count * 0.05;
-    eps *= eps;
-    int pos = 0, rs_start = 0;
-    bool le_eps = false;
-    const uint32_t* PW = (const uint32_t*)P;
-    for (int it = 0; it < 3; it++) {
-        pos = (pos + rs_start) % count;
-        uint32_t bd, bk, maxd, kmax;
-        scan_cyclic<false, 32>(PW, count, pos + 1 == count ? 0 : pos + 1, count - 1, hl, PW[pos], 0u, bd, bk);
-        half_argmax_first(bd, bk, upper, &maxd, &kmax);
-        if (maxd > 0) rs_start = (int)kmax + 1;
-        le_eps = (double)maxd <= eps;
-    }
-    int top = 0, outn = 0;
-    bool reject = !valid;
     if (!le_eps) {
         const int sl_start = pos % count;
         const int sl_end = (rs_start + sl_start) % count;
@@ -1326,28 +1187,38 @@ __device__ __forceinline__ void border_pair_to_quads(const QuadArgs& a, const Co
     }
     __syncthreads();
     for (;;) {
-        bool act = !reject && top > 0;
-        if (act && outn + top > 8) reject = true, act = false;   // more than 8 vertices: see border_to_quad (empirical)
-        if (!__any(act)) break;
+        bool act = !reject && top > 0;   // this border is still being split
+        // outn + top never falls and ends as the vertex count, so this refuses the borders that approxPolyDP's recursion leaves with more than 8
+        // vertices. That none of them ends as 4 is EMPIRICAL and thinly supported: the clean-up pass can take five vertices off nine (it steps over the
+        // one behind every removal). A seeded search (tests/quad_ref.py search_early_reject; DESIGN.md) drew 12711 shapes, of which only 57 borders had
+        // more than 8 vertices here (9 or 10, never more), and none of those ended as a quad; borders of 7 and 8 vertices do end as quads.
+        // tests/test_gpu_quad_edges.py pins quads kept at 7 and 8 against shapes refused at 8, 9 and more.
+        if (act && outn + top > 8) reject = true, act = false;
+        if constexpr (G == WAVE) {
+            if (!act) break;
+        } else if (!__any(act)) break;
         int sl_start = 0, sl_end = 0, len = 0;
-        short2 ep = make_short2(0, 0), sp = make_short2(0, 0);
+        short2 sp = make_short2(0, 0);
         uint32_t bd = 0, bq = 0xFFFFFFFFu;
-        int dx = 0, dy = 0;
+        double bound = 0.0;   // of the squared cross product: eps * |ep - sp|^2, ready before the reductions so that they cover its fp64 latency
         if (act) {
             --top;
             sl_start = s_stack[h][top][0], sl_end = s_stack[h][top][1];
-            ep = P[sl_end], sp = P[sl_start];
+            const short2 ep = P[sl_end];
+            sp = P[sl_start];
             len = sl_end - sl_start;
             if (len <= 0) len += count;
             if (len > 1) {
-                dx = ep.x - sp.x, dy = ep.y - sp.y;
+                const int dx = ep.x - sp.x, dy = ep.y - sp.y;
+                bound = eps * ((double)dx * (double)dx + (double)dy * (double)dy);
+                // |(pt.y - sp.y) * dx - (pt.x - sp.x) * dy| = |(pt - sp) . (-dy, dx)|
                 const uint32_t w = ((uint32_t)(-dy) & 0xFFFFu) | ((uint32_t)dx << 16);
-                scan_cyclic<true, 32>(PW, count, sl_start + 1 == count ? 0 : sl_start + 1, len - 1, hl, PW[sl_start], w, bd, bq);
+                scan_cyclic<true, G>(PW, count, sl_start + 1 == count ? 0 : sl_start + 1, len - 1, hl, PW[sl_start], w, bd, bq);
             }
         }
         __syncthreads();
         uint32_t maxd_u, qmax;
-        half_argmax_first(bd, bq, upper, &maxd_u, &qmax);   // every lane takes part: the DPP steps never run under a half's mask
+        group_argmax_first<G>(bd, bq, upper, &maxd_u, &qmax);   // every lane takes part: the DPP steps never run under a group's mask
         if (act) {
             bool small = true;
             int split = 0;
@@ -1356,7 +1227,7 @@ __device__ __forceinline__ void border_pair_to_quads(const QuadArgs& a, const Co
                 const int q = qmax == 0xFFFFFFFFu ? 0 : (int)qmax;
                 split = sl_start + 1 + q;
                 if (split >= count) split -= count;
-                small = maxd * maxd <= eps * ((double)dx * (double)dx + (double)dy * (double)dy);
+                small = maxd * maxd <= bound;
             }
             if (small) {
                 if (hl == 0) s_out[h][outn] = sp;
@@ -1378,7 +1249,7 @@ __device__ __forceinline__ void border_pair_to_quads(const QuadArgs& a, const Co
 // whose L2 then serves the plane's tiles, descriptors and checkpoints to all of them (same unpacking as walker_kernel).
 // pass 0: all borders of TC_CDESC; pass 1: those that existed when the late walker generations were forked; pass 2: the rest; pass 3: the planes' late
 // lists (keep_border<true>: TC_LATE descriptors from the top of the plane's array downwards).
-__device__ __forceinline__ void quad_blocks(const QuadArgs& a, const int bid, short2* Plds, uint32_t* rows, int (*s_stack)[16][2], short2 (*s_out)[12], int& s_outn) {
+__device__ __forceinline__ void quad_blocks(const QuadArgs& a, const int bid, short2* Plds, uint32_t* rows, int (*s_stack)[16][2], short2 (*s_out)[12]) {
     const int xcd = bid & 7, rest = bid >> 3;
     const int chunk = rest % a.qblocks, plane = (rest / a.qblocks) * 8 + xcd;
     if (plane >= a.nplanes) return;
@@ -1400,31 +1271,30 @@ __device__ __forceinline__ void quad_blocks(const QuadArgs& a, const int bid, sh
                 continue;
             }
             __syncthreads();
-            border_pair_to_quads(a, upper ? cd : pend, upper ? ci : pend_ci, true, Plds, s_stack, s_out, rows);
+            border_to_quad<WAVE / 2, true>(a, upper ? cd : pend, upper ? ci : pend_ci, Plds, s_stack, s_out, rows);
             has_pend = false;
             continue;
         }
         __syncthreads();
         if (cd.n <= QP_LDS)
-            border_to_quad<true>(a, cd, ci, Plds, s_stack[0], s_out[0], s_outn, rows);
+            border_to_quad<WAVE, true>(a, cd, ci, Plds, s_stack, s_out, rows);
         else
-            border_to_quad<false>(a, cd, ci, a.pool + cd.pool_off, s_stack[0], s_out[0], s_outn, rows);
+            border_to_quad<WAVE, false>(a, cd, ci, Plds, s_stack, s_out, rows);
     }
     if (has_pend) {   // no partner came: all 64 lanes on the one border
         __syncthreads();
-        border_to_quad<true>(a, pend, pend_ci, Plds, s_stack[0], s_out[0], s_outn, rows);
+        border_to_quad<WAVE, true>(a, pend, pend_ci, Plds, s_stack, s_out, rows);
     }
 }
 
 __global__ __launch_bounds__(64) void contour_quad_kernel(QuadArgs a) {
     throughput_bound_priority();
     __shared__ __align__(16) short2 Plds[QP_LDS];   // contour points (two borders of up to DUAL_MAX points, or one of up to QP_LDS)
-    __shared__ uint32_t rows[TB_ROWS * EMIT_LANES];  // one 32x32-pixel block per emitting lane
+    __shared__ uint32_t rows[TB_ROWS * WAVE];  // one 32x32-pixel block per emitting lane
     __shared__ int s_stack[2][16][2];
     __shared__ short2 s_out[2][12];
-    __shared__ int s_outn;
-    static_assert(QP_LDS >= 2 * DUAL_MAX && EMIT_LANES == 64, "the two-borders-per-wave path uses the whole point buffer and a block per lane");
-    quad_blocks(a, blockIdx.x, Plds, rows, s_stack, s_out, s_outn);
+    static_assert(QP_LDS >= 2 * DUAL_MAX, "the two-borders-per-wave path uses the whole point buffer");
+    quad_blocks(a, blockIdx.x, Plds, rows, s_stack, s_out);
 }
 
 // A pipeline lane's late walks and contour_quad's pass over the borders known when the launch starts, in ONE launch (launch_late_quads): one stream
@@ -1438,11 +1308,9 @@ struct LateQuadArgs {
 };
 __global__ __launch_bounds__(64) void late_quad_kernel(LateQuadArgs a) {
     __shared__ __align__(16) short2 Plds[QP_LDS];
-    __shared__ uint32_t rows[TB_ROWS * EMIT_LANES];   // walker role: one 32x32-pixel block per walking lane
+    __shared__ uint32_t rows[TB_ROWS * WAVE];   // walker role: one 32x32-pixel block per walking lane
     __shared__ int s_stack[2][16][2];
     __shared__ short2 s_out[2][12];
-    __shared__ int s_outn;
-    static_assert(EMIT_LANES == 64, "the late walks use the quad role's blocks: one per lane");
     const int nwalk = 2 * a.w.gen_blocks;
     if ((int)blockIdx.x < nwalk) {
         latency_bound_priority();   // the priority is a wave's own: each role sets its kernel's
@@ -1453,7 +1321,7 @@ __global__ __launch_bounds__(64) void late_quad_kernel(LateQuadArgs a) {
         return;
     }
     throughput_bound_priority();
-    quad_blocks(a.q, (int)blockIdx.x - nwalk, Plds, rows, s_stack, s_out, s_outn);
+    quad_blocks(a.q, (int)blockIdx.x - nwalk, Plds, rows, s_stack, s_out);
 }
 
 // workgroups per plane of contour_quad's passes 0 and 1
