@@ -66,6 +66,19 @@ class Recover(C.Structure):
 
 
 DRAW_OUTLINE, DRAW_IDS, DRAW_AXIS, DRAW_CUBE, DRAW_Y_PERPENDICULAR = 1, 2, 4, 8, 16
+class Charuco(C.Structure):
+    """arucohip_charuco_t: the layout of a chessboard-corner board"""
+    _fields_ = [("squares_x", C.c_int32), ("squares_y", C.c_int32), ("square_px", C.c_int32), ("marker_px", C.c_int32)]
+
+
+class CharucoOpt(C.Structure):
+    _fields_ = [("min_markers", C.c_int32), ("max_win", C.c_int32)]
+
+
+CHARUCO_CORNER_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("start_x", "<f4"), ("start_y", "<f4"), ("found", "<i4"), ("win", "<i4"),
+                                 ("markers", "<i4"), ("pad_", "<i4")])
+assert CHARUCO_CORNER_DTYPE.itemsize == 32
+
 BOARD_DTYPE = np.dtype([("n_markers", "<i4"), ("has_pose", "<i4"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,))])
 assert C.sizeof(Overlay) == 12 and BOARD_DTYPE.itemsize == 56
 
@@ -120,6 +133,8 @@ SYMBOLS = [
     "arucohip_draw_markers_batch", "arucohip_draw_boards_batch",
     "arucohip_set_pyr_down", "arucohip_get_pyr_down", "arucohip_pyr_down",
     "arucohip_default_recover", "arucohip_board_recover_batch",
+    "arucohip_default_charuco", "arucohip_charuco_board_size", "arucohip_charuco_board_image", "arucohip_charuco_corners_batch",
+    "arucohip_charuco_calibrate_batch", "arucohip_charuco_pose_batch",
 ]
 
 _lib = None
@@ -263,6 +278,13 @@ def load():
     L.arucohip_detect_batch_retry_overflowed.argtypes = [vp, vp, i, i, i, sz, sz, i, vp, vp, i, f, i, vp, i, vp, i, vp]
     L.arucohip_refine_candidate_lines.argtypes = [vp, vp, i, vp, vp, vp, i]
     L.arucohip_debug_refine_pixels.argtypes = [vp, vp, i, i, C.c_size_t, vp, i, i, i, i]
+    L.arucohip_default_charuco.argtypes = [vp]
+    L.arucohip_default_charuco.restype = None
+    L.arucohip_charuco_board_size.argtypes = [vp, vp, vp, vp, vp]
+    L.arucohip_charuco_board_image.argtypes = [vp, vp, i, vp, i, vp, sz, i, vp, vp]
+    L.arucohip_charuco_corners_batch.argtypes = [vp, vp, vp, i, vp, i, i, i, sz, sz, i, vp, vp, vp, i]
+    L.arucohip_charuco_calibrate_batch.argtypes = [vp, f, i, i, i, i, vp, vp, vp, vp, vp, vp]
+    L.arucohip_charuco_pose_batch.argtypes = [vp, i, vp, vp, i, f, i, i, vp]
     L.arucohip_default_params.argtypes = [vp]
     L.arucohip_default_limits.argtypes = [vp, i, i, i]
     _lib = L
@@ -297,6 +319,25 @@ def default_recover():
     o = Recover()
     load().arucohip_default_recover(C.byref(o))
     return o
+
+
+def default_charuco():
+    o = CharucoOpt()
+    load().arucohip_default_charuco(C.byref(o))
+    return o
+
+
+def charuco_layout(squares, square_px, marker_px):
+    return Charuco(int(squares[0]), int(squares[1]), int(square_px), int(marker_px))
+
+
+def charuco_board_size(layout):
+    """(width, height, markers, inner corners) of a chessboard-corner layout (host arithmetic, no handle)."""
+    w, hh, nm, nc = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    rc = load().arucohip_charuco_board_size(C.byref(layout), C.byref(w), C.byref(hh), C.byref(nm), C.byref(nc))
+    if rc != OK:
+        raise ArucoHipError(rc, "arucohip_charuco_board_size")
+    return w.value, hh.value, nm.value, nc.value
 
 
 def _ptr(a):
@@ -942,6 +983,72 @@ class Handle:
                                                         _ptr(da), _ptr(used), _ptr(rv), _ptr(tv), C.byref(rms)))
         nv = int(used.sum())
         return {"rms": rms.value, "K": Ka.reshape(3, 3), "dist": da, "rvecs": rv[:nv], "tvecs": tv[:nv], "used": used.astype(bool)}
+
+    # ---- chessboard-corner (ChArUco) boards
+    def charuco_board_image(self, layout, ids, centered=False):
+        """The board image of a layout with the caller's marker ids: (image uint8 [H][W], objPoints of the markers float32 [markers][4][3],
+        object points of the inner corners float32 [corners][3]), in pixels."""
+        a = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        try:
+            w, hh, nm, nc = charuco_board_size(layout)
+        except ArucoHipError:
+            w, hh, nm, nc = 1, 1, 1, 1   # the call below reports the error with its message
+        img = np.zeros((hh, w), np.uint8)
+        obj, cobj = np.zeros((nm, 4, 3), np.float32), np.zeros((nc, 3), np.float32)
+        self._chk(self.L.arucohip_charuco_board_image(self.h, C.byref(layout), int(bool(centered)), _ptr(a), a.size, _ptr(img), w, 0, _ptr(obj),
+                                                      _ptr(cobj)))
+        return img, obj, cobj
+
+    def charuco_corners_batch(self, layout, ids, frames, opt=None, width=None):
+        """The chessboard's inner corners in the frames of the last batch, from its device-resident markers. frames: the gray planes that
+        batch saw, uint8 [N][H][W] (numpy, or a torch tensor on the handle's device), or [N][H][row_stride] with `width` given. Returns
+        (records CHARUCO_CORNER_DTYPE [N][corners], found corners per frame int32 [N]); the records also stay on the device for
+        charuco_calibrate_batch and charuco_pose_batch."""
+        a = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        ptr, n, wid, hgt, _, rs, fs, dev = self._frames(frames, width, 1)
+        try:
+            nc = charuco_board_size(layout)[3]
+        except ArucoHipError:
+            nc = 1
+        out = np.zeros((n, nc), CHARUCO_CORNER_DTYPE)
+        nf = np.zeros(n, np.int32)
+        self._chk(self.L.arucohip_charuco_corners_batch(self.h, C.byref(layout), _ptr(a), a.size, ptr, n, wid, hgt, rs, fs, dev,
+                                                        None if opt is None else C.cast(C.pointer(opt), C.c_void_p), _ptr(out), _ptr(nf), 0))
+        self._charuco_frames = n
+        return out, nf
+
+    def charuco_corners_batch_device(self, layout, ids, frames_ptr, nframes, width, height, out_ptr, opt=None, row_stride=None, frame_stride=None):
+        """charuco_corners_batch on device frames into a device array of nframes * corners records, both given as pointers; returns the found
+        corners per frame."""
+        a = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        rs = int(width) if row_stride is None else int(row_stride)
+        fs = rs * int(height) if frame_stride is None else int(frame_stride)
+        nf = np.zeros(nframes, np.int32)
+        self._chk(self.L.arucohip_charuco_corners_batch(self.h, C.byref(layout), _ptr(a), a.size, C.c_void_p(frames_ptr), int(nframes), int(width),
+                                                        int(height), rs, fs, 1, None if opt is None else C.cast(C.pointer(opt), C.c_void_p),
+                                                        C.c_void_p(out_ptr), _ptr(nf), 1))
+        self._charuco_frames = int(nframes)
+        return nf
+
+    def charuco_calibrate_batch(self, image_size, square_size=-1.0, min_corners=4, flags=0, K=None, dist=None):
+        """calibrate_camera on the corners the last charuco_corners_batch left on the device: frames with at least min_corners found corners are
+        the views. rvecs / tvecs have one row per used frame; used[f] marks them."""
+        Ka, da = self._calib_start(K, dist)
+        nframes = max(getattr(self, "_charuco_frames", 0), 1)   # without resident corners the library reports the error
+        used = np.zeros(nframes, np.int32)
+        rv, tv, rms = np.zeros((nframes, 3)), np.zeros((nframes, 3)), C.c_double()
+        self._chk(self.L.arucohip_charuco_calibrate_batch(self.h, float(square_size), int(min_corners), int(image_size[0]), int(image_size[1]),
+                                                          int(flags), _ptr(Ka), _ptr(da), _ptr(used), _ptr(rv), _ptr(tv), C.byref(rms)))
+        nv = int(used.sum())
+        return {"rms": rms.value, "K": Ka.reshape(3, 3), "dist": da, "rvecs": rv[:nv], "tvecs": tv[:nv], "used": used.astype(bool)}
+
+    def charuco_pose_batch(self, nframes, K, dist=None, square_size=-1.0, min_corners=4, y_perp=False):
+        """The board pose of every frame from the resident corners: a BOARD_DTYPE array, n_markers = the corners used."""
+        Ka, da = _f32(K), _f32(dist)
+        out = np.zeros(max(int(nframes), 1), BOARD_DTYPE)
+        self._chk(self.L.arucohip_charuco_pose_batch(self.h, int(nframes), _ptr(Ka), _ptr(da), 0 if da is None else da.size, float(square_size),
+                                                     int(min_corners), int(bool(y_perp)), _ptr(out)))
+        return out[:max(int(nframes), 0)]
 
     def chromatic(self, mc, nc, thresh_prob, K, dist, width, height, corners):
         """ChromaticMask::setParams(mc, nc, threshProb, CP, BC, corners) on this handle's device and stream: see Chromatic."""

@@ -142,6 +142,16 @@ struct arucohip_handle {
     Mem<uint8_t> d_overlay;           // arucohip_draw_*_batch: primitive lists of one chunk of frames, staged host markers / boards
     Mem<uint8_t> d_overlay_frames;    // arucohip_draw_*_batch: staged host frames
     Mem<uint8_t> d_recover;           // arucohip_board_recover_batch: the board, adoption records and work lists of one call (recover_carve)
+    // arucohip_charuco_corners_batch (capi_charuco.hip), on the handle the caller holds: the corner records of the last call and their counts stay in
+    // d_charuco for the calibration and the pose; the host keeps the layout and the counts
+    Mem<uint8_t> d_charuco;           // records [frames][corners], then n_found [frames], then the layout's ids
+    Mem<uint8_t> d_charuco_frames;    // staged host frames of one call
+    Mem<uint8_t> d_charuco_work;      // the consumers' scratch: calibration views and points, poses
+    struct Charuco {
+        arucohip_charuco_t layout = {};
+        int frames = 0;               // 0: no resident corners
+        std::vector<int32_t> n_found;
+    } charuco;
     Batch last;                       // the last batch (kept on the handle the caller holds)
     bool timing = false;
     hipEvent_t ev[TSETS][K_COUNT + 1] = {};
@@ -174,7 +184,7 @@ struct arucohip_handle {
     //   capture and replay; batches that decode from cell medians neither touch nor move buf.patches, and buf.cells is create-time memory;
     // - neither: the other Buffers arrays, zero_block and h_markers are create-time memory (`held`); d_erode, d_canny and the user decoder's
     //   staging and d_pyr belong to configurations that are not graphed; wt_out is set only inside chunk_enqueue, which does not run this path.
-    //   Memory no captured launch reads (d_bgr, undistortion, calibration, board and GL batches, planar poses, marker recovery, overlays, EM, HRM, fiducial generation and ChromaticMask scratch) may
+    //   Memory no captured launch reads (d_bgr, undistortion, calibration, board and GL batches, planar poses, marker recovery, overlays, EM, HRM, fiducial generation, ChArUco corners and ChromaticMask scratch) may
     //   be replaced at any time.
     struct FrameGraph {
         hipGraphExec_t exec = nullptr;

@@ -433,9 +433,12 @@ void launch_hrm_board(hipStream_t s, const uint64_t* codes, int n, int gw, int g
 // One image of fid_paint_kernel: a gw x gh grid of markers of M pixels (cells of sw = M / 7) at `pitch` on white, GW x GH pixels large,
 // at (off, off) of a W x H image. off = 0: the grid is the image (boards, plain markers). off > 0: the "locked" marker, white around the
 // grid with a black off x off square in every corner.
+// sq > 0: a chessboard of gw x gh squares of sq pixels (arucohip_charuco_board_image): square (sx, sy) is black when sx + sy is even, a white one
+// holds the marker of its slot at (moff, moff) inside it; GW, GH, off and pitch are not read.
 struct FidLayout {
     int W, H, GW, GH, off;
     int gw, gh, M, pitch, sw;
+    int sq, moff;
 };
 // n images of layout L; slots: [n][gh * gw] marker ids, -1 = the cell stays white. Any row_stride >= W, any alignment.
 void launch_fid_paint(hipStream_t s, const FidLayout& L, const int32_t* slots, int nimages, uint8_t* out, size_t row_stride, size_t image_stride);
@@ -443,5 +446,22 @@ void launch_fid_paint(hipStream_t s, const FidLayout& L, const int32_t* slots, i
 void launch_fid_distances(hipStream_t s, int32_t* dist);
 // the greedy selection of n_markers markers; sel [n_markers] ascending, res [4]: selected, complete, smallest pairwise distance, largest entropy
 void launch_fid_select(hipStream_t s, int n_markers, int min_entropy, int32_t* sel, int32_t* res);
+
+// Chessboard-corner boards (k_charuco.hip; capi_charuco.hip).
+struct CharucoArgs {
+    arucohip_charuco_t L;
+    const int32_t* ids;        // device: the layout's marker ids
+    const uint8_t* gray;       // the frames of this worker's span
+    size_t row_stride, frame_stride;
+    int width, height;
+    int min_markers, max_win;
+};
+// one wave per (corner, frame) of the first nframes frames the worker's lists hold; out / n_found: the worker's first frame
+void launch_charuco_corners(hipStream_t s, int nframes, const Buffers& b, const CharucoArgs& a, arucohip_charuco_corner_t* out, int32_t* n_found);
+// views[v] = {frame, first point}: the found corners of the frame, in corner order, to obj / img from the view's first point; npt[v] = their number
+void launch_charuco_gather(hipStream_t s, const arucohip_charuco_t& L, double scale, const arucohip_charuco_corner_t* rec, const int2* views, int nviews,
+                           float* obj, float* img, int32_t* npt);
+void launch_charuco_pose(hipStream_t s, const arucohip_charuco_t& L, double scale, const arucohip_charuco_corner_t* rec, int nframes, int min_corners,
+                         const CamModel& cam, arucohip_board_t* out);
 
 }  // namespace ah

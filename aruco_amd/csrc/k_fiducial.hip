@@ -48,6 +48,29 @@ __global__ __launch_bounds__(256) void fid_paint_kernel(FidLayout L, const int32
     const int lo = max(x0, 0), hi = min(x0 + 16, L.W);
     if (lo >= hi) return;
     const int32_t* slot = slots + (size_t)img * L.gw * L.gh;
+    if (L.sq > 0) {   // a chessboard with the markers inside its white squares: painted once per board, a division per pixel is affordable
+        const int sy = y / L.sq, oy = y - sy * L.sq - L.moff;
+        uint32_t w[4] = {0, 0, 0, 0};
+        for (int x = lo; x < hi; x++) {
+            const int sx = x / L.sq, ox = x - sx * L.sq - L.moff;
+            uint32_t v = 0u;
+            if ((sx + sy) & 1) {
+                v = 255u;
+                if (ox >= 0 && ox < L.M && oy >= 0 && oy < L.M) v = ((fid_row_mask(slot[sy * L.gw + sx], oy / L.sw) >> (ox / L.sw)) & 1u) ? 255u : 0u;
+            }
+            const int q = x - x0;
+            w[q >> 2] |= v << (8 * (q & 3));
+        }
+        if (hi - lo == 16) {
+            *reinterpret_cast<uint4*>(row + x0) = make_uint4(w[0], w[1], w[2], w[3]);
+        } else {
+            for (int x = lo; x < hi; x++) {
+                const int q = x - x0;
+                row[x] = (uint8_t)(w[q >> 2] >> (8 * (q & 3)));
+            }
+        }
+        return;
+    }
     // the row: background only, or cell row cy of grid row gy
     const int ty = y - L.off, pitch = L.pitch;
     bool marker_row = ty >= 0 && ty < L.GH;

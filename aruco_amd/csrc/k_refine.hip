@@ -13,14 +13,10 @@
 #include "internal.h"
 #include "decode_device.h"
 #include "pnp_device.h"
+#include "subpix_device.h"
 
 namespace ah {
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ float wave_minf(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
@@ -275,11 +271,9 @@ struct PixArgs {
     int cap_cands, method, win;
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
 __global__ __launch_bounds__(64) void refine_pixels_kernel(PixArgs a) {
     latency_bound_priority();
-    __shared__ float buf[33 * 33];
+    __shared__ float buf[SUBPIX_PATCH * SUBPIX_PATCH];
     __shared__ uint8_t loc[17 * 17];
     const int frame = blockIdx.z, ci = blockIdx.y, corner = blockIdx.x, lane = threadIdx.x;
     if (ci >= a.ncands[frame]) return;
@@ -291,53 +285,7 @@ __global__ __launch_bounds__(64) void refine_pixels_kernel(PixArgs a) {
     const float cTx = cand->c[2 * corner], cTy = cand->c[2 * corner + 1];
     float rx = cTx, ry = cTy;
     if (a.method == ARUCOHIP_CORNER_SUBPIX) {
-        const int win = a.win, ww = 2 * win + 1, pw = ww + 2;
-        float cIx = cTx, cIy = cTy;
-        int iter = 0;
-        double err = 0;
-        const double eps = 0.005 * 0.005;
-        do {
-            // getRectSubPix 8u -> 32f, (ww+2)^2 patch around cI
-            float ox = cIx - (pw - 1) * 0.5f, oy = cIy - (pw - 1) * 0.5f;
-            int ix = (int)floorf(ox), iy = (int)floorf(oy);
-            float fa = ox - ix, fb = oy - iy;
-            float a11 = (1.f - fa) * (1.f - fb), a12 = fa * (1.f - fb), a21 = (1.f - fa) * fb, a22 = fa * fb;
-            __syncthreads();
-            for (int i = lane; i < pw * pw; i += WAVE) {
-                int r = i / pw, c = i - r * pw;
-                int y0 = clampi(iy + r, 0, H - 1), y1 = clampi(iy + r + 1, 0, H - 1);
-                int x0 = clampi(ix + c, 0, W - 1), x1 = clampi(ix + c + 1, 0, W - 1);
-                float s0 = src[y0 * st + x0] * a11 + src[y0 * st + x1] * a12 + src[y1 * st + x0] * a21 + src[y1 * st + x1] * a22;
-                buf[i] = s0;
-            }
-            __syncthreads();
-            double A = 0, B = 0, C = 0, bb1 = 0, bb2 = 0;
-            for (int k = lane; k < ww * ww; k += WAVE) {
-                int i = k / ww, j = k - i * ww;
-                float y = (float)(i - win) / win, x = (float)(j - win) / win;
-                float vy = expf(-y * y);
-                double m = (double)(float)(vy * expf(-x * x));
-                const float* sp = buf + (i + 1) * pw + (j + 1);
-                double tgx = (double)sp[1] - (double)sp[-1];
-                double tgy = (double)sp[pw] - (double)sp[-pw];
-                double gxx = tgx * tgx * m, gxy = tgx * tgy * m, gyy = tgy * tgy * m;
-                double px = j - win, py = i - win;
-                A += gxx, B += gxy, C += gyy;
-                bb1 += gxx * px + gxy * py;
-                bb2 += gxy * px + gyy * py;
-            }
-            A = wave_sum(A), B = wave_sum(B), C = wave_sum(C), bb1 = wave_sum(bb1), bb2 = wave_sum(bb2);
-            double det = A * C - B * B;
-            if (fabs(det) <= DBL_EPSILON * DBL_EPSILON) break;
-            double scale = 1.0 / det;
-            float nx = (float)(cIx + C * scale * bb1 - B * scale * bb2);
-            float ny = (float)(cIy - B * scale * bb1 + A * scale * bb2);
-            err = (nx - cIx) * (nx - cIx) + (ny - cIy) * (ny - cIy);
-            cIx = nx, cIy = ny;
-            if (cIx < 0 || cIx >= W || cIy < 0 || cIy >= H) break;
-        } while (++iter < 8 && err > eps);
-        if (fabsf(cIx - cTx) > win || fabsf(cIy - cTy) > win) cIx = cTx, cIy = cTy;
-        rx = cIx, ry = cIy;
+        subpix_refine_wave(src, st, W, H, cTx, cTy, a.win, buf, lane, &rx, &ry);   // subpix_device.h
     } else {  // HARRIS (SubPixelCorner)
         const int win = 15, ps = 17;
         bool skip = cTx < 0 || cTy < 0 || cTy > H || cTy > W;

@@ -1479,6 +1479,126 @@ private:
     float repj_err_thres;
 };
 
+// A chessboard whose white squares carry the markers (OpenCV's aruco module: CharucoBoard, interpolateCornersCharuco,
+// estimatePoseCharucoBoard, calibrateCameraCharuco; no counterpart in the reference). The calibration points are the chessboard's inner
+// corners: the markers of the detector's last frame say which corner is which, and each corner is refined in the frame
+// (arucohip_charuco_corners_batch, include/arucohip.h). Corners are numbered row by row; one that was not found is left out.
+class CharucoBoard {
+public:
+    arucohip_charuco_t layout;
+    std::vector<int> ids;                       // marker k (row-major order of the white squares) shows ids[k]
+    std::vector<int> cornerIds;                 // of the last detectCorners: the number of every found corner ...
+    std::vector<cv::Point2f> corners;           // ... and where it is in the frame
+    std::vector<arucohip_charuco_corner_t> records;   // every corner's record of the last detectCorners
+    cv::Mat_<double> Rvec, Tvec;                // of the last estimatePose that gave a pose
+
+    CharucoBoard() { layout.squares_x = layout.squares_y = layout.square_px = layout.marker_px = 0; }
+    static CharucoBoard create(int squaresX, int squaresY, int squarePx, int markerPx, const std::vector<int>& markerIds) {
+        CharucoBoard b;
+        b.layout.squares_x = squaresX, b.layout.squares_y = squaresY, b.layout.square_px = squarePx, b.layout.marker_px = markerPx;
+        int nm = 0;
+        arucohip_throw_(arucohip_charuco_board_size(&b.layout, nullptr, nullptr, &nm, nullptr), "CharucoBoard::create: layout outside the limits", nullptr);
+        if ((int)markerIds.size() != nm) arucohip_throw_(ARUCOHIP_E_INVALID, "CharucoBoard::create: one id per white square", nullptr);
+        b.ids = markerIds;
+        return b;
+    }
+    cv::Size size() const {
+        int w = 0, h = 0;
+        arucohip_throw_(arucohip_charuco_board_size(&layout, &w, &h, nullptr, nullptr), "CharucoBoard::size", nullptr);
+        return cv::Size(w, h);
+    }
+    int cornerCount() const {
+        int n = 0;
+        arucohip_throw_(arucohip_charuco_board_size(&layout, nullptr, nullptr, nullptr, &n), "CharucoBoard::cornerCount", nullptr);
+        return n;
+    }
+    // the board image, painted on the device; with `conf` the markers as a BoardConfiguration (PIX) for BoardDetector
+    cv::Mat image(BoardConfiguration* conf = nullptr, bool centered = true) const {
+        const cv::Size sz = size();
+        cv::Mat img(sz.height, sz.width, CV_8UC1);
+        std::vector<int32_t> id32(ids.begin(), ids.end());
+        std::vector<float> obj(id32.size() * 12);
+        SharedHandle_& sh = SharedHandle_::get();
+        std::lock_guard<std::mutex> lock(sh.mu);
+        arucohip_handle* h = sh.ensure();
+        arucohip_throw_(arucohip_charuco_board_image(h, &layout, centered ? 1 : 0, id32.data(), (int)id32.size(), img.data, img.step, 0, obj.data(), nullptr),
+                        "CharucoBoard::image", h);
+        if (conf) {
+            conf->mInfoType = BoardConfiguration::PIX;
+            conf->ids.assign(ids.begin(), ids.end());
+            conf->objPoints.clear();
+            for (size_t k = 0; k < id32.size(); k++) {
+                std::vector<cv::Point3f> q(4);
+                for (int c = 0; c < 4; c++) q[c].x = obj[12 * k + 3 * c], q[c].y = obj[12 * k + 3 * c + 1], q[c].z = obj[12 * k + 3 * c + 2];
+                conf->objPoints.push_back(q);
+            }
+        }
+        return img;
+    }
+    // the inner corners of `frame`, the gray frame the detector's last detect() saw; returns how many were found
+    int detectCorners(MarkerDetector& detector, const cv::Mat& frame, int minMarkers = 2, int maxWin = 5) {
+        if (frame.type() != CV_8UC1) arucohip_throw_(ARUCOHIP_E_INVALID, "CharucoBoard::detectCorners: the 8-bit gray frame of the last detect()", nullptr);
+        arucohip_charuco_opt_t o;
+        o.min_markers = minMarkers, o.max_win = maxWin;
+        std::vector<int32_t> id32(ids.begin(), ids.end());
+        records.assign((size_t)cornerCount(), arucohip_charuco_corner_t());
+        int32_t n = 0;
+        arucohip_handle* h = detector.handle();
+        detector_ = &detector;
+        arucohip_throw_(arucohip_charuco_corners_batch(h, &layout, id32.data(), (int)id32.size(), frame.data, 1, frame.cols, frame.rows, frame.step,
+                                                       (size_t)frame.rows * frame.step, 0, &o, records.data(), &n, 0),
+                        "CharucoBoard::detectCorners", h);
+        cornerIds.clear(), corners.clear();
+        for (size_t c = 0; c < records.size(); c++)
+            if (records[c].found) {
+                cv::Point2f p;
+                p.x = records[c].x, p.y = records[c].y;
+                cornerIds.push_back((int)c), corners.push_back(p);
+            }
+        return n;
+    }
+    // the board's pose from the corners of the last detectCorners; squareSize: the side of a square in the caller's unit (<= 0: board pixels)
+    bool estimatePose(const CameraParameters& cp, float squareSize, bool setYPerpendicular = false, int minCorners = 4) {
+        if (!detector_) arucohip_throw_(ARUCOHIP_E_INVALID, "CharucoBoard::estimatePose: no detectCorners before", nullptr);
+        float K[9], d[8];
+        const bool hasK = mat_to_K_(cp.CameraMatrix, K);
+        const int nd = mat_to_dist_(cp.Distorsion, d);
+        arucohip_handle* h = detector_->handle();
+        arucohip_throw_(arucohip_charuco_pose_batch(h, 1, hasK ? K : nullptr, nd ? d : nullptr, nd, squareSize, minCorners, setYPerpendicular ? 1 : 0, &pose),
+                        "CharucoBoard::estimatePose", h);
+        if (pose.has_pose) {
+            Rvec = cv::Mat_<double>(3, 1), Tvec = cv::Mat_<double>(3, 1);
+            for (int k = 0; k < 3; k++) Rvec(k) = pose.rvec[k], Tvec(k) = pose.tvec[k];
+        }
+        return pose.has_pose != 0;
+    }
+    arucohip_board_t pose = arucohip_board_t();   // the last estimatePose, as the library returned it
+    // cv::calibrateCamera over views of this board: allIds[v] / allCorners[v] as detectCorners left cornerIds / corners for view v
+    double calibrate(const std::vector<std::vector<int> >& allIds, const std::vector<std::vector<cv::Point2f> >& allCorners, cv::Size imageSize,
+                     float squareSize, cv::Mat& cameraMatrix, cv::Mat& distCoeffs, std::vector<cv::Mat>* rvecs = nullptr, std::vector<cv::Mat>* tvecs = nullptr,
+                     int flags = 0) const {
+        if (allIds.size() != allCorners.size()) arucohip_throw_(ARUCOHIP_E_INVALID, "CharucoBoard::calibrate: id and corner lists differ", nullptr);
+        const int ncx = layout.squares_x - 1, nc = cornerCount();
+        const double scale = squareSize > 0 ? (double)squareSize / (double)layout.square_px : 1.0;
+        std::vector<std::vector<cv::Point3f> > obj(allIds.size());
+        for (size_t v = 0; v < allIds.size(); v++) {
+            if (allIds[v].size() != allCorners[v].size()) arucohip_throw_(ARUCOHIP_E_INVALID, "CharucoBoard::calibrate: a view's counts differ", nullptr);
+            for (size_t i = 0; i < allIds[v].size(); i++) {
+                const int c = allIds[v][i];
+                if (c < 0 || c >= nc) arucohip_throw_(ARUCOHIP_E_INVALID, "CharucoBoard::calibrate: a corner number outside the board", nullptr);
+                cv::Point3f p;
+                p.x = (float)((float)((c % ncx + 1) * layout.square_px) * scale), p.y = (float)((float)((c / ncx + 1) * layout.square_px) * scale), p.z = 0.f;
+                obj[v].push_back(p);
+            }
+        }
+        std::vector<cv::Mat> rv, tv;
+        return calibrateCamera(obj, allCorners, imageSize, cameraMatrix, distCoeffs, rvecs ? *rvecs : rv, tvecs ? *tvecs : tv, flags);
+    }
+
+private:
+    MarkerDetector* detector_ = nullptr;
+};
+
 }  // namespace aruco
 
 #if !ARUCOHIP_HAVE_OPENCV

@@ -560,6 +560,75 @@ int arucohip_planar_poses(arucohip_handle* h, const arucohip_marker_t* markers, 
 int arucohip_planar_poses_batch(arucohip_handle* h, int nframes, const float* K, const float* dist, int ndist, float marker_size,
                                 int refine, int y_perpendicular, arucohip_planar_poses_t* out, int cap, int out_on_device);
 
+/* ---- Chessboard-corner (ChArUco) boards (DESIGN.md "ChArUco"): a chessboard whose white squares carry the markers. The calibration
+ * points are the chessboard's inner corners (saddle points); the markers only say which corner is which. No counterpart in the
+ * reference (OpenCV's aruco module has CharucoBoard / interpolateCornersCharuco); the algorithm is this library's, stated here.
+ *
+ * The board is squares_x * square_px by squares_y * square_px pixels. Square (sx, sy) is black when sx + sy is even. Every white square
+ * holds one marker of side marker_px whose top-left is at (sx * square_px + m, sy * square_px + m), m = (square_px - marker_px) / 2.
+ * Markers are numbered in row-major order of the white squares; marker k shows ids[k]. Inner corner c = iy * (squares_x - 1) + ix lies
+ * at board pixel ((ix + 1) * square_px, (iy + 1) * square_px); its two neighbour markers are those of the two white squares among the
+ * four around it. Limits (ARUCOHIP_E_INVALID otherwise): squares 2..64 each, marker_px >= 7, square_px - marker_px >= 2, at most
+ * ARUCOHIP_CALIB_MAX_VIEW_POINTS inner corners, at most 1024 markers, image at most 16383 a side. */
+typedef struct arucohip_charuco {
+    int32_t squares_x, squares_y, square_px, marker_px;
+} arucohip_charuco_t;
+/* One inner corner of one frame. 32 bytes. */
+typedef struct arucohip_charuco_corner {
+    float x, y;              /* the refined corner (found != 0) */
+    float start_x, start_y;  /* where the neighbour markers' homographies put it */
+    int32_t found;
+    int32_t win;             /* the refinement's half window */
+    int32_t markers;         /* neighbour markers used: 0..2 */
+    int32_t pad_;
+} arucohip_charuco_corner_t;
+typedef struct arucohip_charuco_opt {
+    int32_t min_markers;     /* 1 or 2 neighbour markers a corner needs. Default 2 (OpenCV's; taken over, not measured here) */
+    int32_t max_win;         /* 2..15: the largest half window of the refinement. Default 5 */
+} arucohip_charuco_opt_t;
+void arucohip_default_charuco(arucohip_charuco_opt_t* o);
+/* The image's size, the markers and the inner corners of a layout. Any output may be NULL. Host arithmetic. */
+int arucohip_charuco_board_size(const arucohip_charuco_t* layout, int* width, int* height, int* markers, int* corners);
+/* The board image, painted by one launch on scratch of its own: white, the black squares, createMarkerImage(ids[k], marker_px) in every
+ * white square. image: height rows of row_stride bytes (>= width, no alignment needed), host or device. obj (may be NULL): markers * 4 * 3
+ * floats in pixels (PIX), y down, corner order as arucohip_fiducial_board_image: with ids it is a board for every board call.
+ * corner_obj (may be NULL): corners * 3 floats. Both are shifted by (width / 2, height / 2) (integer halves) when `centered`. nids must be
+ * the layout's marker count, ids 0..1023. */
+int arucohip_charuco_board_image(arucohip_handle* h, const arucohip_charuco_t* layout, int centered, const int32_t* ids, int nids,
+                                 uint8_t* image, size_t row_stride, int image_on_device, float* obj, float* corner_obj);
+/* The inner corners of the first nframes frames of the LAST batch (a synchronous call, a waited ticket or a one-frame arucohip_detect;
+ * every chunk worker), from the batch's device-resident markers. frames: the gray planes that batch saw (host or device; the handle does
+ * not keep them). out[f * corners + c] (host, or device with out_on_device) and n_found[f] (host, may be NULL): the found corners of
+ * frame f. A frame the batch gave up (n = -1) or without markers has found = 0 everywhere. Per corner, one wavefront:
+ *  1. its two neighbour markers are looked up by id in the frame's marker list (the first entry of that id). For each one present, the
+ *     homography that maps its four board-pixel corners to its four image corners is solved exactly (8 x 8, double, from the float
+ *     corners as stored). A singular system or a non-positive w at the corner makes the neighbour absent. `markers` counts the
+ *     neighbours used; fewer than min_markers: not found;
+ *  2. the start is the mean, in double, of the neighbours' projections of the corner, rounded once to float: start_x, start_y;
+ *  3. d = the smallest distance (double) from the unrounded start to an image corner of a used neighbour;
+ *     win = min(max_win, (int)floor(d * 0.70710678118654752) - 1), which keeps the window off the markers' own borders. win < 2: not found;
+ *  4. not found when start - (win + 1) < 0 or start + (win + 1) > size - 1 in x or y (the refinement's patch would leave the frame);
+ *  5. x, y = the SUBPIX refinement (cv::cornerSubPix as the detector's SUBPIX corner method runs it: 8 iterations, step 0.005) of the
+ *     float start with half window win. A refinement that leaves the window returns the start and stays found.
+ * Only final marker corners and ids are read: every corner method, threshold range, pyrDown level and decoder is supported. The result
+ * and the layout also stay on the device, in memory no captured launch reads, until the next call: arucohip_charuco_calibrate_batch and
+ * arucohip_charuco_pose_batch work on them. ARUCOHIP_E_INVALID: a layout outside the limits, nids other than the layout's marker count,
+ * nframes beyond the last batch, width / height other than that batch's frames, strides too small, min_markers outside 1..2, max_win
+ * outside 2..15. opt may be NULL (defaults). */
+int arucohip_charuco_corners_batch(arucohip_handle* h, const arucohip_charuco_t* layout, const int32_t* ids, int nids, const uint8_t* frames,
+                                   int nframes, int width, int height, size_t row_stride, size_t frame_stride, int frames_on_device,
+                                   const arucohip_charuco_opt_t* opt, arucohip_charuco_corner_t* out, int32_t* n_found, int out_on_device);
+/* arucohip_calibrate_camera on the resident corners: a frame is a view when it has >= min_corners (>= 4) found corners; a corner's object
+ * point is its corner_obj (not centred), times square_size / square_px when square_size > 0. The views are laid out on the device, found
+ * corners in corner order, and the device solver runs unchanged. Outputs and errors as arucohip_calibrate_board_batch. */
+int arucohip_charuco_calibrate_batch(arucohip_handle* h, float square_size, int min_corners, int width, int height, int flags, double K[9],
+                                     double dist[5], int32_t* used, double* rvecs, double* tvecs, double* rms);
+/* The board pose of the first nframes frames of the resident corners (one wavefront per frame, planar solvePnP over the found corners,
+ * object points as above): out[f] (host) with n_markers = the corners used; has_pose = 0 below min_corners (>= 4), without K or when the
+ * solve fails. y_perpendicular applies rotateXAxis. */
+int arucohip_charuco_pose_batch(arucohip_handle* h, int nframes, const float* K, const float* dist, int ndist, float square_size,
+                                int min_corners, int y_perpendicular, arucohip_board_t* out);
+
 /* ---- Overlays: Marker::draw (marker.cpp:54-81), Board::draw and CvDrawingUtils::draw3dAxis / draw3dCube (cvdrawingutils.cpp:41-255) painted
  * into 8-bit frames where they lie (DESIGN.md "Overlay"). Primitives, order, colours (B G R) and geometry are the reference's; the pixel
  * coverage is this library's: lines are not antialiased, text uses a 5 x 7 bitmap font. Within a frame the result is that
