@@ -129,7 +129,7 @@ SYMBOLS = [
     "arucohip_debug_hrm_counters",
     "arucohip_fiducial_marker_images", "arucohip_fiducial_marker_side", "arucohip_fiducial_marker_mat", "arucohip_fiducial_shuffle_ids",
     "arucohip_fiducial_board_size", "arucohip_fiducial_board_image", "arucohip_board_pix_to_meters", "arucohip_fiducial_distances",
-    "arucohip_fiducial_select",
+    "arucohip_fiducial_select", "arucohip_board_place",
     "arucohip_draw_markers_batch", "arucohip_draw_boards_batch",
     "arucohip_set_pyr_down", "arucohip_get_pyr_down", "arucohip_pyr_down",
     "arucohip_default_recover", "arucohip_board_recover_batch",
@@ -232,6 +232,7 @@ def load():
     L.arucohip_fiducial_board_size.argtypes = [i, i, i, i, i, vp, vp, vp, vp]
     L.arucohip_fiducial_board_image.argtypes = [vp, i, i, i, i, i, i, vp, i, vp, sz, i, vp]
     L.arucohip_board_pix_to_meters.argtypes = [vp, i, f, vp]
+    L.arucohip_board_place.argtypes = [vp, i, vp, vp, vp]
     L.arucohip_fiducial_distances.argtypes = [vp, vp, i]
     L.arucohip_fiducial_select.argtypes = [vp, i, i, vp, vp, vp]
     L.arucohip_chromatic_debug_geometry.argtypes = [vp, i, vp, vp, vp]
@@ -389,6 +390,18 @@ def board_pix_to_meters(obj, marker_size_m):
     rc = load().arucohip_board_pix_to_meters(_ptr(o), o.shape[0], float(marker_size_m), _ptr(out))
     if rc != OK:
         raise ArucoHipError(rc, "arucohip_board_pix_to_meters")
+    return out
+
+
+def board_place(obj, rvec, tvec):
+    """A board's corners [n][4][3] moved by a rigid transform: R(rvec) p + tvec in double, rounded once to float32 (host, no handle). A cube
+    or a folded board is np.concatenate of placed panels."""
+    o = np.ascontiguousarray(obj, dtype=np.float32).reshape(-1, 4, 3)
+    r, t = np.ascontiguousarray(rvec, dtype=np.float64).reshape(3), np.ascontiguousarray(tvec, dtype=np.float64).reshape(3)
+    out = np.zeros_like(o)
+    rc = load().arucohip_board_place(_ptr(o), o.shape[0], _ptr(r), _ptr(t), _ptr(out))
+    if rc != OK:
+        raise ArucoHipError(rc, "arucohip_board_place")
     return out
 
 

@@ -1,16 +1,19 @@
 // BoardDetector::detect's pose of one frame on one 64-lane wavefront (boarddetector.cpp:157-198), shared by board_pose_kernel
 // (k_finalize.hip) and the marker recovery (k_recover.hip): lane 0 filters the frame's markers by board id and lays out the 3-D / 2-D
-// correspondences in LDS, then the 64 lanes share the points of the planar solvePnP; optional reprojection filter and second solve.
+// correspondences in LDS, then the 64 lanes share the points of solvePnP (any rigid point set: pnp3d_device.h); optional reprojection
+// filter and second solve.
 #pragma once
 #include "internal.h"
-#include "pnp_device.h"
+#include "pnp3d_device.h"
 
 namespace ah {
 
 constexpr int MAX_BOARD_POINTS = 512;
 
-// LDS of one frame's board solve
+// LDS of one frame's board solve. Each solve of a board out of z = 0 borrows the object points of the other one for its plane-frame points:
+// obj2 is not filled before the first solve is over, obj is not read after the filter.
 struct BoardLds {
+    Pnp3dLds w3d;
     float obj[MAX_BOARD_POINTS * 3], img[MAX_BOARD_POINTS * 2], obj2[MAX_BOARD_POINTS * 3], img2[MAX_BOARD_POINTS * 2];
     int npts, nmark, n2;
 };
@@ -65,7 +68,7 @@ __device__ __forceinline__ int board_solve_wave(const arucohip_marker_t* M, int 
     for (int k = 0; k < 3; k++) r[k] = t[k] = 0;
     const bool enough = (bd.marker_size > 0 && bd.info_type == ARUCOHIP_BOARD_PIX) || bd.info_type == ARUCOHIP_BOARD_METERS;
     if (!(nk > 0 && cam.has_K && enough)) return BOARD_NOT_TRIED;
-    bool ok = solve_pnp_planar_wave<64>(s.obj, s.img, np, cam, r, t, lane);
+    bool ok = solve_pnp_wave3d(s.obj, s.img, np, cam, r, t, lane, s.obj2, s.w3d);
     if (bd.repj_thres > 0 && ok) {
         double R[9];
         rodrigues_vec2mat(r, R, nullptr);
@@ -91,7 +94,7 @@ __device__ __forceinline__ int board_solve_wave(const arucohip_marker_t* M, int 
             __syncthreads();
         }
         // fewer than 4 surviving points: the reference's second solvePnP would throw; keep the first pose, flag no pose
-        ok = s.n2 >= 4 && solve_pnp_planar_wave<64>(s.obj2, s.img2, s.n2, cam, r, t, lane);
+        ok = s.n2 >= 4 && solve_pnp_wave3d(s.obj2, s.img2, s.n2, cam, r, t, lane, s.obj, s.w3d);
     }
     return ok ? BOARD_POSE : BOARD_NO_POSE;
 }

@@ -192,6 +192,24 @@ int arucohip_board_pix_to_meters(const float* obj, int nmarkers, float marker_si
     return ARUCOHIP_OK;
 }
 
+int arucohip_board_place(const float* obj, int nmarkers, const double rvec[3], const double tvec[3], float* obj_out) {
+    if (!obj || !obj_out || !rvec || !tvec || nmarkers < 0) return ARUCOHIP_E_INVALID;
+    // Rodrigues in double: R = cos I + (1 - cos) u u^T + sin [u]x
+    const double th = std::sqrt(rvec[0] * rvec[0] + rvec[1] * rvec[1] + rvec[2] * rvec[2]);
+    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    if (th > 0) {
+        const double u[3] = {rvec[0] / th, rvec[1] / th, rvec[2] / th}, c = std::cos(th), s = std::sin(th);
+        const double ux[9] = {0, -u[2], u[1], u[2], 0, -u[0], -u[1], u[0], 0};
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) R[i * 3 + j] = c * (i == j) + (1.0 - c) * u[i] * u[j] + s * ux[i * 3 + j];
+    }
+    for (size_t i = 0; i < (size_t)nmarkers * 4; i++) {   // one rounding to float per coordinate; obj_out may be obj
+        const double p[3] = {obj[3 * i], obj[3 * i + 1], obj[3 * i + 2]};
+        for (int c = 0; c < 3; c++) obj_out[3 * i + c] = (float)(R[c * 3] * p[0] + R[c * 3 + 1] * p[1] + R[c * 3 + 2] * p[2] + tvec[c]);
+    }
+    return ARUCOHIP_OK;
+}
+
 int arucohip_fiducial_distances(arucohip_handle* h, int32_t* dist, int on_device) {
     if (!h) return ARUCOHIP_E_INVALID;
     if (!dist) return fail(h, ARUCOHIP_E_INVALID, "fiducial_distances: NULL dist");

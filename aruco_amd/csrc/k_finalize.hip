@@ -201,13 +201,17 @@ void launch_marker_pose(hipStream_t s, arucohip_marker_t* markers, int n, const 
     hipLaunchKernelGGL(pose_kernel, dim3((n + 15) / 16), dim3(64), 0, s, markers, (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0u, 0, n, cam);
 }
 
-// generic planar PnP over npts correspondences (board pose of one arucohip_board_detect call): one wavefront, the lanes share the
+// generic PnP over npts correspondences (board pose of one arucohip_board_detect call): one wavefront, the lanes share the
 // points (wave sums for the homography and J^T J) like board_pose_kernel. A single lane took 1.7 ms for the 96 points of the
-// reference's board still (ArucoPerf.Board), more than the rest of the call.
+// reference's board still (ArucoPerf.Board), more than the rest of the call. Points out of z = 0: pnp3d_device.h; the plane-frame
+// points of up to PNP_POINTS_MAX correspondences (what arucohip_board_detect's staging buffer holds) are kept in LDS.
+constexpr int PNP_POINTS_MAX = 1170;
 __global__ __launch_bounds__(64) void pnp_points_kernel(const float* obj, const float* img, int npts, CamModel cam, double* rt, int* ok_out) {
+    __shared__ Pnp3dLds w3d;
+    __shared__ float flat[PNP_POINTS_MAX * 3];
     if (blockIdx.x != 0) return;
     double r[3] = {0, 0, 0}, t[3] = {0, 0, 0};
-    const bool ok = solve_pnp_planar_wave<64>(obj, img, npts, cam, r, t, (int)threadIdx.x);
+    const bool ok = npts <= PNP_POINTS_MAX && solve_pnp_wave3d(obj, img, npts, cam, r, t, (int)threadIdx.x, flat, w3d);
     if (threadIdx.x == 0) {
         for (int k = 0; k < 3; k++) rt[k] = r[k], rt[3 + k] = t[k];
         *ok_out = ok ? 1 : 0;

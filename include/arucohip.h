@@ -232,6 +232,11 @@ int arucohip_fiducial_board_image(arucohip_handle* h, int type, int grid_w, int 
 /* utils/aruco_board_pix2meters.cpp:54-63: obj_out = obj * (marker_size_m / float(int(norm of the first marker's first side))), float
  * products. obj_out may be obj. A first side shorter than one pixel is ARUCOHIP_E_INVALID (the reference divides by zero). Host. */
 int arucohip_board_pix_to_meters(const float* obj, int nmarkers, float marker_size_m, float* obj_out);
+/* A board's corners moved by a rigid transform: obj_out = R(rvec) * p + tvec for each of the nmarkers * 4 corners (Rodrigues vector,
+ * computed in double, rounded once to float; obj_out may be obj). No reference counterpart: a marker cube or a folded board is the
+ * concatenation of placed arucohip_fiducial_board_image panels, and arucohip_board_detect poses any such rigid point set. Host
+ * arithmetic, no handle. ARUCOHIP_E_INVALID on a null pointer or a negative count. */
+int arucohip_board_place(const float* obj, int nmarkers, const double rvec[3], const double tvec[3], float* obj_out);
 /* utils/aruco_selectoptimalmarkers.cpp:53-74, :128-131: dist[1024 * i + j] = the minimum over the four rotations of marker i of its
  * 25-cell Hamming distance to marker j (symmetric, zero diagonal). dist: 1024 * 1024 int32, host or device. */
 int arucohip_fiducial_distances(arucohip_handle* h, int32_t* dist, int on_device);
@@ -399,7 +404,18 @@ int arucohip_debug_hrm_counters(arucohip_handle* h, int32_t out[4]);
 /* BoardDetector::detect (boarddetector.h:103-108). markers: output of arucohip_detect; ids/obj: BoardConfiguration
  * (board.h:56-69) as nboard ids and nboard*4*3 floats; returns likelihood in *prob (found / total).
  * out_markers (cap n) receives the board's member markers (Board : vector<Marker>). Up to 1168 correspondences (292 member
- * markers) are solved; more give ARUCOHIP_E_CAPACITY. */
+ * markers) are solved; more give ARUCOHIP_E_CAPACITY.
+ * The object points may be any rigid set (a marker cube, markers on two walls, a planar board written in world coordinates): the pose
+ * starts as cv::solvePnP(ITERATIVE) starts it. With n points M (scaled to metres) and Mc their mean:
+ *   - every z == 0: the planar start (homography), as before;
+ *   - else the eigenvalues w0 >= w1 >= w2 of sum (M - Mc)(M - Mc)^T decide. w2 / w1 < 1e-3: planar in the frame of the eigenvectors;
+ *     the homography is taken there and its pose composed with that frame. Otherwise the direct linear transform of the undistorted
+ *     points (n >= 6; fewer give has_pose = 0): the eigenvector of the smallest eigenvalue of the 12 x 12 normal matrix as [RR | tt],
+ *     R the nearest rotation to RR, t = tt sqrt(3) / |RR|_F;
+ *   - Levenberg-Marquardt on the original points from that start. A start that is not finite gives has_pose = 0, without an error.
+ * The same holds for arucohip_board_detect_batch, arucohip_board_recover_batch and the shim's BoardDetector::detect. No reasoning about
+ * self-occlusion: a face turned away from the camera is simply not detected. Still planar-only: the per-marker pose, arucohip_planar_poses,
+ * calibration (views out of a plane give ARUCOHIP_E_UNSUPPORTED), the ChromaticMask board rectangle and ChArUco boards. */
 int arucohip_board_detect(arucohip_handle* h, const arucohip_marker_t* markers, int n, const int32_t* ids, const float* obj,
                           int nboard, int info_type, const float* K, const float* dist, int ndist, float marker_size,
                           float repj_err_thres, int y_perpendicular, arucohip_marker_t* out_markers, arucohip_board_t* out,
