@@ -21,6 +21,8 @@ BOARD_NONE, BOARD_PIX, BOARD_METERS = -1, 0, 1
 CALIB_USE_INTRINSIC_GUESS, CALIB_FIX_ASPECT_RATIO, CALIB_FIX_PRINCIPAL_POINT, CALIB_ZERO_TANGENT_DIST = 1, 2, 4, 8
 CALIB_FIX_FOCAL_LENGTH, CALIB_FIX_K1, CALIB_FIX_K2, CALIB_FIX_K3 = 16, 32, 64, 128
 CALIB_MAX_VIEW_POINTS = 512
+# arucohip_board_map*: listed markers, listed markers used per frame
+MAP_MAX_MARKERS, MAP_MAX_FRAME_MARKERS = 64, 16
 
 _ERR_NAMES = {1: "ARUCOHIP_E_INVALID", 2: "ARUCOHIP_E_CAPACITY", 3: "ARUCOHIP_E_UNSUPPORTED", 4: "ARUCOHIP_E_HIP",
               5: "ARUCOHIP_E_OVERFLOW", 6: "ARUCOHIP_E_BOARD_CONFIG"}
@@ -118,7 +120,7 @@ SYMBOLS = [
     "arucohip_mgpu_set_depth", "arucohip_mgpu_submit_batch", "arucohip_mgpu_submit_streams", "arucohip_mgpu_wait",
     "arucohip_compact_bytes", "arucohip_compact_markers", "arucohip_wait_event", "arucohip_detect_batch_retry_overflowed",
     "arucohip_refine_candidate_lines", "arucohip_debug_refine_pixels", "arucohip_mgpu_gather_mode", "arucohip_build_info",
-    "arucohip_calibrate_camera", "arucohip_calibrate_board_batch",
+    "arucohip_calibrate_camera", "arucohip_calibrate_board_batch", "arucohip_board_map", "arucohip_board_map_batch",
     "arucohip_planar_poses", "arucohip_planar_poses_batch",
     "arucohip_chromatic_board_corners", "arucohip_chromatic_create", "arucohip_chromatic_destroy", "arucohip_chromatic_train",
     "arucohip_chromatic_classify", "arucohip_chromatic_update", "arucohip_chromatic_get_mask", "arucohip_chromatic_get_cell_map",
@@ -201,6 +203,8 @@ def load():
     L.arucohip_board_recover_batch.argtypes = [vp, i, vp, vp, i, i, vp, vp, i, f, f, i, vp, vp, i, vp, i, vp, vp, vp]
     L.arucohip_calibrate_camera.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp]
     L.arucohip_calibrate_board_batch.argtypes = [vp, i, vp, vp, i, i, f, i, i, i, i, vp, vp, vp, vp, vp, vp]
+    L.arucohip_board_map.argtypes = [vp, vp, vp, vp, i, i, i, vp, i, vp, vp, i, f] + [vp] * 10
+    L.arucohip_board_map_batch.argtypes = [vp, i, vp, i, vp, vp, i, f, i] + [vp] * 10
     L.arucohip_planar_poses.argtypes = [vp, vp, i, i, vp, vp, i, f, i, i, vp]
     L.arucohip_planar_poses_batch.argtypes = [vp, i, vp, vp, i, f, i, i, vp, i, i]
     L.arucohip_draw_markers_batch.argtypes = [vp, vp, i, i, i, i, sz, sz, i, vp, i, vp, i, vp, vp, i, vp]
@@ -996,6 +1000,43 @@ class Handle:
                                                         _ptr(da), _ptr(used), _ptr(rv), _ptr(tv), C.byref(rms)))
         nv = int(used.sum())
         return {"rms": rms.value, "K": Ka.reshape(3, 3), "dist": da, "rvecs": rv[:nv], "tvecs": tv[:nv], "used": used.astype(bool)}
+
+    # ---- marker mapping: the 3-D layout of a rigid marker set
+    def _map_call(self, fn, head, nframes, board_ids, K, dist, marker_size, tail=()):
+        ida = np.ascontiguousarray(board_ids, dtype=np.int32).reshape(-1)
+        nb = len(ida)
+        Ka, da = _f32(K), _f32(dist)
+        obj, rv, tv = np.zeros((max(nb, 1), 4, 3), np.float32), np.zeros((max(nb, 1), 3)), np.zeros((max(nb, 1), 3))
+        mapped, used = np.zeros(max(nb, 1), np.int32), np.zeros(max(nframes, 1), np.int32)
+        frv, ftv, mrms = np.zeros((max(nframes, 1), 3)), np.zeros((max(nframes, 1), 3)), np.zeros(max(nb, 1))
+        rms, it = C.c_double(), C.c_int32()
+        self._chk(fn(self.h, *head, int(nframes), _ptr(ida), nb, _ptr(Ka), _ptr(da), 0 if da is None else da.size, float(marker_size), *tail,
+                     _ptr(obj), _ptr(rv), _ptr(tv), _ptr(mapped), _ptr(used), _ptr(frv), _ptr(ftv), _ptr(mrms), C.byref(rms), C.byref(it)))
+        return {"obj": obj[:nb], "marker_rvecs": rv[:nb], "marker_tvecs": tv[:nb], "mapped": mapped[:nb].astype(bool),
+                "used": used[:nframes].astype(bool), "frame_rvecs": frv[:nframes], "frame_tvecs": ftv[:nframes], "marker_rms": mrms[:nb],
+                "rms": rms.value, "iterations": it.value}
+
+    def board_map(self, frames, ids, corners, nframes, board_ids, K, dist, marker_size):
+        """arucohip_board_map: the placement of every marker of board_ids in the frame of the first one, from observations given as
+        parallel arrays (frame index, id, 4 corners). Returns obj float32 [n][4][3] in metres (board_detect's obj with BOARD_METERS),
+        marker_rvecs / marker_tvecs [n][3], mapped [n], used [nframes], frame_rvecs / frame_tvecs [nframes][3] (zeros where not used),
+        marker_rms [n], rms, iterations."""
+        fa = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+        ia = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        ca = np.ascontiguousarray(corners, dtype=np.float32).reshape(-1, 8)
+        if not len(fa) == len(ia) == len(ca):
+            raise ValueError("frames, ids and corners differ in length")
+        head = (_ptr(fa) if len(fa) else None, _ptr(ia) if len(fa) else None, _ptr(ca) if len(fa) else None, len(fa), 0)
+        return self._map_call(self.L.arucohip_board_map, head, nframes, board_ids, K, dist, marker_size)
+
+    def board_map_device(self, frames_ptr, ids_ptr, corners_ptr, nobs, nframes, board_ids, K, dist, marker_size):
+        """board_map on device arrays (int32 [nobs], int32 [nobs], float32 [nobs][8], given as pointers)."""
+        head = (C.c_void_p(frames_ptr), C.c_void_p(ids_ptr), C.c_void_p(corners_ptr), int(nobs), 1)
+        return self._map_call(self.L.arucohip_board_map, head, nframes, board_ids, K, dist, marker_size)
+
+    def board_map_batch(self, nframes, board_ids, K, dist, marker_size, min_markers=2):
+        """board_map on the device-resident markers of the first nframes frames of the last detect_batch call."""
+        return self._map_call(self.L.arucohip_board_map_batch, (), nframes, board_ids, K, dist, marker_size, tail=(int(min_markers),))
 
     # ---- chessboard-corner (ChArUco) boards
     def charuco_board_image(self, layout, ids, centered=False):

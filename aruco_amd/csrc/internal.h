@@ -351,6 +351,57 @@ void launch_calib_iteration(hipStream_t s, const CalibDev& d);
 void launch_calib_gather(hipStream_t s, int nframes, const Buffers& b, const int32_t* ids, const float* bobj, int nboard, double mpp,
                          int first, float* obj, float* img, int32_t* npt, int32_t* nmark);
 
+// Marker mapping (k_map.hip): the rigid placement of nboard markers in the frame of the first, from frames that show several of them.
+constexpr int MAP_MAX_MARKERS = 64;     // listed markers (ARUCOHIP_MAP_MAX_MARKERS)
+constexpr int MAP_SLOTS = 16;           // listed markers used per frame (ARUCOHIP_MAP_MAX_FRAME_MARKERS): 4 lanes each, one wave per frame
+constexpr int MAP_REC = 116;            // doubles per frame and slot: V_m (36), W_m (36), Y_m (36), g_m - W_m u (6), pad
+enum { MAP_ERR_NO_REFERENCE = 1, MAP_ERR_TOO_FEW = 2, MAP_ERR_DEGENERATE = 4 };
+
+struct MapState {
+    double intr[9];    // fx fy cx cy k1 k2 p1 p2 k3 (fixed)
+    double cost;       // sum of squared residuals at mpose[cur] / fpose[cur]
+    double mdn, mpn;   // |marker step|^2 and |marker parameters|^2 of the last solve
+    int32_t lg, cur, done, iters, max_iter, attempts, err, solve_failed, nmapped, nused, nobs, pad_;
+};
+
+struct MapDev {
+    int nframes, nboard, min_markers;
+    float half;                 // half the marker side, in the float rounding of Marker::getObjectPoints
+    // observations: obs_frame != nullptr: nobs entries in any order; else frame f owns obs_cnt[f] entries from f * obs_stride
+    const int32_t* obs_frame;
+    const int32_t* obs_id;
+    const float* obs_corners;   // 8 per observation
+    const int32_t* obs_cnt;
+    int nobs, obs_stride;
+    const int32_t* ids;         // [nboard]
+    int8_t* slot;               // [F][MAP_MAX_MARKERS] slot of board marker m in frame f, -1: absent
+    int8_t* fm;                 // [F][MAP_SLOTS] board marker of a slot
+    int32_t* fn;                // [F] slots taken
+    int32_t* used;              // [F]
+    float* fc;                  // [F][MAP_SLOTS][8] corners
+    double* fT;                 // [F][MAP_SLOTS][12] the marker's planar pose in the frame: R (9), t (3)
+    double* fq;                 // [F][MAP_SLOTS] its confidence rms[1] / rms[0]
+    int32_t* edge_f;            // [MAP_MAX_MARKERS][MAP_MAX_MARKERS] the frame an edge takes its transform from, -1: no edge
+    double* edge_q;             // its score
+    int32_t* mapped;            // [nboard]
+    double* mpose;              // [2][nboard][6] rvec, tvec of every marker in the frame of marker 0 (current / candidate)
+    double* fpose;              // [2][F][6] board pose of every frame
+    double* rec;                // [F][MAP_SLOTS][MAP_REC]
+    double* fu;                 // [F][6] u = U~^-1 g_p
+    double* S;                  // [N][N] the reduced system (lower triangle; its Cholesky factor after the solve), N = 6 (nboard - 1)
+    double* delta;              // [N] reduced right-hand side, then the marker step
+    double* vcost;              // [2][F]
+    double* vchg;               // [F][2]
+    double* scost;              // [F][MAP_SLOTS] squared residuals of a slot's four corners
+    float* obj;                 // [nboard][12]
+    MapState* st;
+};
+
+void launch_map_gather(hipStream_t s, int nframes, const Buffers& b, int first, int stride, int32_t* obs_id, float* obs_corners, int32_t* obs_cnt);
+void launch_map_init(hipStream_t s, const MapDev& d, const CamModel& cam);
+void launch_map_iteration(hipStream_t s, const MapDev& d);
+void launch_map_finish(hipStream_t s, const MapDev& d);
+
 // Board occlusion mask (k_chromatic.hip): ChromaticMask of the reference, src/chromaticmask.cpp.
 constexpr int CHROMA_CELL = 20;       // ChromaticMask::_cellSize
 constexpr int CHROMA_MIN_FIT = 10;    // EMClassifier::train fits only when the discretised histogram holds >= 10 samples

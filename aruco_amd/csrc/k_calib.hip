@@ -21,50 +21,6 @@ namespace ah {
 constexpr int CJ = 16;
 constexpr int CG = CJ * (CJ + 1) / 2;   // 136 entries of the upper triangle of the Gram matrix
 
-// forward model with a double K (fx fy cx cy) and k1 k2 p1 p2 k3; optional rows d/d(intrinsics) (2 x 9) and d/d(rvec, tvec) (2 x 6)
-__device__ inline void project_point_d(double X, double Y, double Z, const double* R, const double* dRdr, const double* t, const double* in,
-                                       double* mx, double* my, double* di, double* dp) {
-    const double fx = in[0], fy = in[1], cx = in[2], cy = in[3], k1 = in[4], k2 = in[5], p1 = in[6], p2 = in[7], k3 = in[8];
-    double x = R[0] * X + R[1] * Y + R[2] * Z + t[0];
-    double y = R[3] * X + R[4] * Y + R[5] * Z + t[1];
-    double z = R[6] * X + R[7] * Y + R[8] * Z + t[2];
-    z = z ? 1. / z : 1;
-    x *= z, y *= z;
-    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
-    const double a1 = 2 * x * y, a2 = r2 + 2 * x * x, a3 = r2 + 2 * y * y;
-    const double cdist = 1 + k1 * r2 + k2 * r4 + k3 * r6;
-    const double xd = x * cdist + p1 * a1 + p2 * a2;
-    const double yd = y * cdist + p1 * a3 + p2 * a1;
-    *mx = xd * fx + cx;
-    *my = yd * fy + cy;
-    if (!di) return;
-    // intrinsics: rows x (0..8) and y (9..17)
-    const double dx[9] = {xd, 0, 1, 0, fx * x * r2, fx * x * r4, fx * a1, fx * a2, fx * x * r6};
-    const double dy[9] = {0, yd, 0, 1, fy * y * r2, fy * y * r4, fy * a3, fy * a1, fy * y * r6};
-#pragma unroll
-    for (int j = 0; j < 9; j++) di[j] = dx[j], di[9 + j] = dy[j];
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        double dxn, dyn;
-        if (j < 3) {
-            const double* d = dRdr + j * 9;
-            const double dx0 = X * d[0] + Y * d[1] + Z * d[2];
-            const double dy0 = X * d[3] + Y * d[4] + Z * d[5];
-            const double dz0 = X * d[6] + Y * d[7] + Z * d[8];
-            dxn = z * (dx0 - x * dz0), dyn = z * (dy0 - y * dz0);
-        } else {
-            const int q = j - 3;
-            dxn = q == 0 ? z : (q == 1 ? 0 : -x * z);
-            dyn = q == 0 ? 0 : (q == 1 ? z : -y * z);
-        }
-        const double dr2 = 2 * x * dxn + 2 * y * dyn;
-        const double dcdist = k1 * dr2 + 2 * k2 * r2 * dr2 + 3 * k3 * r4 * dr2;
-        const double da1 = 2 * (x * dyn + y * dxn);
-        dp[j] = fx * (dxn * cdist + x * dcdist + p1 * da1 + p2 * (dr2 + 4 * x * dxn));
-        dp[6 + j] = fy * (dyn * cdist + y * dcdist + p1 * (dr2 + 4 * y * dyn) + p2 * da1);
-    }
-}
-
 // pivoted Gaussian elimination for a small run-time n (one thread, n <= 9)
 __device__ inline bool solve_small(double* A, double* b, int n) {
     for (int c = 0; c < n; c++) {

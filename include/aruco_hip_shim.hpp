@@ -1460,6 +1460,29 @@ public:
         detect(_vmarkers, BConf, _boardDetected, cp.CameraMatrix, cp.Distorsion, markerSizeMeters);
         return recovered;
     }
+    // No counterpart in this snapshot of the reference (its later versions ship a marker mapper). The 3-D layout of a rigid marker set
+    // (a cube, markers around a room) from frames that show several of its markers each, solved on the device (arucohip_board_map):
+    // a BoardConfiguration in metres in the frame of the first id, for detect() above. frames[f]: the markers detected in frame f. mapped
+    // (may be NULL) gets one flag per id; an id that no frame connects to the first one has mapped = false and zero corners. rms (may be
+    // NULL): the reprojection error in pixels.
+    BoardConfiguration mapBoard(const std::vector<std::vector<Marker> >& frames, const std::vector<int>& ids, const CameraParameters& cp,
+                                float markerSizeMeters, std::vector<bool>* mapped = nullptr, double* rms = nullptr) {
+        std::vector<int32_t> of, oi;
+        std::vector<float> oc;
+        for (size_t f = 0; f < frames.size(); f++)
+            for (size_t i = 0; i < frames[f].size(); i++) {
+                if (frames[f][i].size() != 4) continue;
+                of.push_back((int32_t)f), oi.push_back(frames[f][i].id);
+                for (int k = 0; k < 4; k++) oc.push_back(frames[f][i][k].x), oc.push_back(frames[f][i][k].y);
+            }
+        return map_(false, (int)frames.size(), &of, &oi, &oc, ids, cp, markerSizeMeters, 2, mapped, rms);
+    }
+    // The same on the device-resident markers of the first nframes frames of the last batch the detector's handle ran
+    // (getMarkerDetector().handle(): arucohip_detect_batch, or the one frame of detect(im)).
+    BoardConfiguration mapBoardLastBatch(int nframes, const std::vector<int>& ids, const CameraParameters& cp, float markerSizeMeters, int minMarkers = 2,
+                                         std::vector<bool>* mapped = nullptr, double* rms = nullptr) {
+        return map_(true, nframes, nullptr, nullptr, nullptr, ids, cp, markerSizeMeters, minMarkers, mapped, rms);
+    }
     Board& getDetectedBoard() { return _boardDetected; }
     MarkerDetector& getMarkerDetector() { return _mdetector; }
     std::vector<Marker>& getDetectedMarkers() { return _vmarkers; }
@@ -1469,6 +1492,36 @@ public:
     float get_repj_err_thres() const { return repj_err_thres; }
 
 private:
+    BoardConfiguration map_(bool batch, int nframes, const std::vector<int32_t>* of, const std::vector<int32_t>* oi, const std::vector<float>* oc,
+                            const std::vector<int>& ids, const CameraParameters& cp, float markerSizeMeters, int minMarkers, std::vector<bool>* mapped,
+                            double* rms) {
+        float K[9], d[8];
+        const bool hasK = mat_to_K_(cp.CameraMatrix, K);
+        const int nd = mat_to_dist_(cp.Distorsion, d);
+        const size_t nb = ids.size();
+        std::vector<int32_t> bid(ids.begin(), ids.end()), flag(std::max<size_t>(nb, 1));
+        std::vector<float> obj(std::max<size_t>(nb, 1) * 12);
+        std::vector<double> rv(std::max<size_t>(nb, 1) * 3), tv(std::max<size_t>(nb, 1) * 3);
+        arucohip_handle* h = _mdetector.handle();
+        const int rc = batch ? arucohip_board_map_batch(h, nframes, bid.data(), (int)nb, hasK ? K : nullptr, nd ? d : nullptr, nd, markerSizeMeters,
+                                                        minMarkers, obj.data(), rv.data(), tv.data(), flag.data(), nullptr, nullptr, nullptr, nullptr,
+                                                        rms, nullptr)
+                             : arucohip_board_map(h, of->data(), oi->data(), oc->data(), (int)of->size(), 0, nframes, bid.data(), (int)nb,
+                                                  hasK ? K : nullptr, nd ? d : nullptr, nd, markerSizeMeters, obj.data(), rv.data(), tv.data(),
+                                                  flag.data(), nullptr, nullptr, nullptr, nullptr, rms, nullptr);
+        arucohip_throw_(rc, "BoardDetector::mapBoard", h);
+        BoardConfiguration bc;
+        bc.mInfoType = BoardConfiguration::METERS;
+        bc.ids = ids;
+        if (mapped) mapped->assign(nb, false);
+        for (size_t i = 0; i < nb; i++) {
+            std::vector<cv::Point3f> c(4);
+            for (int k = 0; k < 4; k++) c[k] = cv::Point3f(obj[12 * i + 3 * k], obj[12 * i + 3 * k + 1], obj[12 * i + 3 * k + 2]);
+            bc.objPoints.push_back(c);
+            if (mapped) (*mapped)[i] = flag[i] != 0;
+        }
+        return bc;
+    }
     bool _setYPerpendicular, _areParamsSet;
     BoardConfiguration _bconf;
     Board _boardDetected;

@@ -499,6 +499,47 @@ int arucohip_calibrate_board_batch(arucohip_handle* h, int nframes, const int32_
                                    float marker_size, int min_markers, int width, int height, int flags, double K[9], double dist[5],
                                    int32_t* used, double* rvecs, double* tvecs, double* rms);
 
+/* Marker mapping: the 3-D layout of a rigid marker set from frames that show several of its markers. This is what produces the
+ * object points of a board that is not planar (a marker cube, markers taped around a room) for arucohip_board_detect* above, whose
+ * comment lists what stays planar-only. No counterpart in this snapshot of the reference (its later versions ship a marker mapper).
+ * Given a camera (K, dist), the marker side in metres and nboard ids, the call finds the rigid placement of every listed marker in
+ * the frame of the FIRST listed one (the reference marker: identity, not a variable) and the board pose of every used frame, minimising
+ * the squared pixel residuals of all four corners of all observations through the full camera model: corner k of marker m in frame
+ * f projects R_f (R_m c_k + t_m) + t_f, c_k = Marker::getObjectPoints of marker_size. Intrinsics are fixed; FP64 on the device.
+ * Start values: both planar solutions of every observation without refinement (arucohip_planar_poses), solution 0 with confidence
+ * q = rms[1] / rms[0]; per marker pair the relative transform from the frame with the largest min(q_a, q_b) (ties: the lower frame); a
+ * spanning tree from the reference marker that always adds the marker whose best edge into the mapped set scores highest (ties: the
+ * lower board index); every frame's pose from its highest-q mapped marker. Then Levenberg-Marquardt with the frames' poses
+ * eliminated per frame (Schur complement), CvLevMarq's rule as arucohip_calibrate_camera: at most 30 accepted steps or a relative
+ * step below DBL_EPSILON. Frames are reduced in frame order: the result is bit-reproducible.
+ * Which observations count: an id that is not listed is ignored; a repeated id within a frame keeps the first; a frame that shows
+ * more than ARUCOHIP_MAP_MAX_FRAME_MARKERS listed markers keeps those with the largest quad perimeter, in detection order; an
+ * observation without planar solutions (a degenerate quad) is dropped; a frame with fewer than max(min_markers, 2) listed markers is
+ * not used. A listed marker that is not connected to the reference marker through used frames gets mapped = 0 and zeros in its
+ * outputs (not an error), and a frame that shows only such markers is not used.
+ * Outputs: obj (nboard * 4 * 3 floats, metres: the `obj` of arucohip_board_detect* with ARUCOHIP_BOARD_METERS), marker_rvec /
+ * marker_tvec (3 doubles per marker), mapped (nboard); optional (may be NULL): used (nframes), frame_rvec / frame_tvec (3 doubles per
+ * frame, zeros for a frame that is not used), marker_rms (nboard, pixels, root mean square over a marker's corners), rms
+ * (sqrt(sum |r|^2 / corners)), iterations (accepted steps).
+ * ARUCOHIP_E_INVALID: no K, ndist not 0, 4 or 5, marker_size <= 0, nboard < 2, nframes < 1 (or beyond the last batch), a NULL
+ * required output, the reference marker in no used frame, fewer than two markers mapped. ARUCOHIP_E_CAPACITY: nboard >
+ * ARUCOHIP_MAP_MAX_MARKERS. The call returns when the results are complete; it leaves the single-frame graph and the last batch's
+ * results as they are. */
+#define ARUCOHIP_MAP_MAX_MARKERS 64         /* listed markers: the reduced system is at most 378 x 378 */
+#define ARUCOHIP_MAP_MAX_FRAME_MARKERS 16   /* listed markers used per frame */
+/* Observations as three parallel arrays of nobs entries (frame index in [0, nframes), id, 8 floats x0 y0 .. x3 y3), in any order of
+ * frames; the order within a frame is the detection order. on_device: the three arrays are device pointers. min_markers is 2. */
+int arucohip_board_map(arucohip_handle* h, const int32_t* obs_frame, const int32_t* obs_id, const float* obs_corners, int nobs,
+                       int on_device, int nframes, const int32_t* ids, int nboard, const float* K, const float* dist, int ndist,
+                       float marker_size, float* obj, double* marker_rvec, double* marker_tvec, int32_t* mapped, int32_t* used,
+                       double* frame_rvec, double* frame_tvec, double* marker_rms, double* rms, int32_t* iterations);
+/* The same on the markers of the first nframes frames of the LAST arucohip_detect_batch call, where they are (device-resident, every
+ * chunk and worker); no frame or marker leaves the device before the solve. */
+int arucohip_board_map_batch(arucohip_handle* h, int nframes, const int32_t* ids, int nboard, const float* K, const float* dist,
+                             int ndist, float marker_size, int min_markers, float* obj, double* marker_rvec, double* marker_tvec,
+                             int32_t* mapped, int32_t* used, double* frame_rvec, double* frame_tvec, double* marker_rms, double* rms,
+                             int32_t* iterations);
+
 /* Board occlusion mask: ChromaticMask / EMClassifier of the reference (src/chromaticmask.cpp). Each of the mc x nc cells of the board
  * holds a 2-component Gaussian mixture over the 256 grey levels of one 8-bit plane; a pixel on the board is 1 when its level is
  * "board colour" under the model, 0 where something in front of the board hides it. The reference's quirks are kept;
