@@ -23,6 +23,8 @@ CALIB_FIX_FOCAL_LENGTH, CALIB_FIX_K1, CALIB_FIX_K2, CALIB_FIX_K3 = 16, 32, 64, 1
 CALIB_MAX_VIEW_POINTS = 512
 # arucohip_board_map*: listed markers, listed markers used per frame
 MAP_MAX_MARKERS, MAP_MAX_FRAME_MARKERS = 64, 16
+# arucohip_rig_*: cameras of a rig, markers of its board
+RIG_MAX_CAMERAS, RIG_MAX_BOARD = 16, 128
 
 _ERR_NAMES = {1: "ARUCOHIP_E_INVALID", 2: "ARUCOHIP_E_CAPACITY", 3: "ARUCOHIP_E_UNSUPPORTED", 4: "ARUCOHIP_E_HIP",
               5: "ARUCOHIP_E_OVERFLOW", 6: "ARUCOHIP_E_BOARD_CONFIG"}
@@ -48,6 +50,12 @@ class Marker(C.Structure):
 
 class BoardOut(C.Structure):
     _fields_ = [("n_markers", C.c_int32), ("has_pose", C.c_int32), ("rvec", C.c_double * 3), ("tvec", C.c_double * 3)]
+
+
+class RigCamera(C.Structure):
+    """arucohip_rig_camera_t: fixed intrinsics (in), calibrated and the transform rig -> camera (out of rig_calibrate, in of rig_pose)."""
+    _fields_ = [("K", C.c_float * 9), ("dist", C.c_float * 5), ("ndist", C.c_int32), ("calibrated", C.c_int32), ("rvec", C.c_double * 3),
+                ("tvec", C.c_double * 3)]
 
 
 class PlanarPoses(C.Structure):
@@ -121,6 +129,7 @@ SYMBOLS = [
     "arucohip_compact_bytes", "arucohip_compact_markers", "arucohip_wait_event", "arucohip_detect_batch_retry_overflowed",
     "arucohip_refine_candidate_lines", "arucohip_debug_refine_pixels", "arucohip_mgpu_gather_mode", "arucohip_build_info",
     "arucohip_calibrate_camera", "arucohip_calibrate_board_batch", "arucohip_board_map", "arucohip_board_map_batch",
+    "arucohip_rig_calibrate", "arucohip_rig_calibrate_batch", "arucohip_rig_pose", "arucohip_rig_pose_batch",
     "arucohip_planar_poses", "arucohip_planar_poses_batch",
     "arucohip_chromatic_board_corners", "arucohip_chromatic_create", "arucohip_chromatic_destroy", "arucohip_chromatic_train",
     "arucohip_chromatic_classify", "arucohip_chromatic_update", "arucohip_chromatic_get_mask", "arucohip_chromatic_get_cell_map",
@@ -205,6 +214,10 @@ def load():
     L.arucohip_calibrate_board_batch.argtypes = [vp, i, vp, vp, i, i, f, i, i, i, i, vp, vp, vp, vp, vp, vp]
     L.arucohip_board_map.argtypes = [vp, vp, vp, vp, i, i, i, vp, i, vp, vp, i, f] + [vp] * 10
     L.arucohip_board_map_batch.argtypes = [vp, i, vp, i, vp, vp, i, f, i] + [vp] * 10
+    L.arucohip_rig_calibrate.argtypes = [vp, vp, vp, vp, i, i, i, vp, i, vp, vp, i, i, f, i] + [vp] * 6
+    L.arucohip_rig_calibrate_batch.argtypes = [vp, i, vp, i, vp, vp, i, i, f, i] + [vp] * 6
+    L.arucohip_rig_pose.argtypes = [vp, vp, vp, vp, i, i, i, vp, i, vp, vp, i, i, f, i, vp, vp]
+    L.arucohip_rig_pose_batch.argtypes = [vp, i, vp, i, vp, vp, i, i, f, i, vp, vp]
     L.arucohip_planar_poses.argtypes = [vp, vp, i, i, vp, vp, i, f, i, i, vp]
     L.arucohip_planar_poses_batch.argtypes = [vp, i, vp, vp, i, f, i, i, vp, i, i]
     L.arucohip_draw_markers_batch.argtypes = [vp, vp, i, i, i, i, sz, sz, i, vp, i, vp, i, vp, vp, i, vp]
@@ -1037,6 +1050,99 @@ class Handle:
     def board_map_batch(self, nframes, board_ids, K, dist, marker_size, min_markers=2):
         """board_map on the device-resident markers of the first nframes frames of the last detect_batch call."""
         return self._map_call(self.L.arucohip_board_map_batch, (), nframes, board_ids, K, dist, marker_size, tail=(int(min_markers),))
+
+    # ---- camera rigs: extrinsics between cameras, one board pose from all of them
+    @staticmethod
+    def rig_cameras(cams):
+        """A RigCamera array from a list of dicts: K, dist (None, 4 or 5 coefficients) and, for rig_pose, calibrated / rvec / tvec (as
+        rig_calibrate returns them). A RigCamera array passes through."""
+        if isinstance(cams, C.Array):
+            return cams
+        arr = (RigCamera * max(len(cams), 1))()
+        for rc, cam in zip(arr, cams):
+            rc.K[:] = [float(v) for v in np.asarray(cam["K"], np.float32).reshape(9)]
+            dist = cam.get("dist")
+            da = np.zeros(0, np.float32) if dist is None else np.asarray(dist, np.float32).reshape(-1)
+            rc.ndist = int(cam.get("ndist", da.size))
+            for k in range(min(da.size, 5)):
+                rc.dist[k] = float(da[k])
+            rc.calibrated = int(bool(cam.get("calibrated", False)))
+            rc.rvec[:] = [float(v) for v in np.asarray(cam.get("rvec", np.zeros(3)), np.float64).reshape(3)]
+            rc.tvec[:] = [float(v) for v in np.asarray(cam.get("tvec", np.zeros(3)), np.float64).reshape(3)]
+        return arr
+
+    @staticmethod
+    def _rig_obs(views, ids, corners):
+        va = np.ascontiguousarray(views, dtype=np.int32).reshape(-1)
+        ia = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        ca = np.ascontiguousarray(corners, dtype=np.float32).reshape(-1, 8)
+        if not len(va) == len(ia) == len(ca):
+            raise ValueError("views, ids and corners differ in length")
+        n = len(va)
+        return (va, ia, ca), (_ptr(va) if n else None, _ptr(ia) if n else None, _ptr(ca) if n else None, n, 0)
+
+    def _rig_calibrate_call(self, fn, head, ninstants, cams, ncams, board_ids, obj, info_type, marker_size, min_markers):
+        arr = self.rig_cameras(cams)
+        ncams = len(cams) if ncams is None else int(ncams)
+        ida = np.ascontiguousarray(board_ids, dtype=np.int32).reshape(-1)
+        oa = _f32(obj)
+        T = max(int(ninstants), 1)
+        used, brv, btv, crms = np.zeros(T, np.int32), np.zeros((T, 3)), np.zeros((T, 3)), np.zeros(max(ncams, 1))
+        rms, it = C.c_double(), C.c_int32()
+        self._chk(fn(self.h, *head, C.cast(arr, C.c_void_p), ncams, _ptr(ida), _ptr(oa), len(ida), int(info_type), float(marker_size), int(min_markers),
+                     _ptr(used), _ptr(brv), _ptr(btv), _ptr(crms), C.byref(rms), C.byref(it)))
+        n = min(ncams, len(arr))
+        return {"cams": arr, "calibrated": np.array([bool(arr[c].calibrated) for c in range(n)]),
+                "rvecs": np.array([list(arr[c].rvec) for c in range(n)]), "tvecs": np.array([list(arr[c].tvec) for c in range(n)]),
+                "used": used[:ninstants].astype(bool), "board_rvecs": brv[:ninstants], "board_tvecs": btv[:ninstants], "camera_rms": crms[:ncams],
+                "rms": rms.value, "iterations": it.value}
+
+    def rig_calibrate(self, views, ids, corners, ninstants, cams, board_ids, obj, info_type, marker_size=-1.0, min_markers=1, ncams=None):
+        """arucohip_rig_calibrate: the transforms rig -> camera of cams (a list of dicts K / dist, or a RigCamera array; camera 0 is the rig
+        frame) from observations given as parallel arrays (view index = instant * ncams + camera, id, 4 corners). Returns cams (the RigCamera
+        array, as rig_pose takes it), calibrated [ncams], rvecs / tvecs [ncams][3], used [ninstants], board_rvecs / board_tvecs
+        [ninstants][3] (zeros where not used), camera_rms [ncams], rms, iterations."""
+        keep, head = self._rig_obs(views, ids, corners)
+        return self._rig_calibrate_call(self.L.arucohip_rig_calibrate, head + (int(ninstants),), ninstants, cams, ncams, board_ids, obj, info_type,
+                                        marker_size, min_markers)
+
+    def rig_calibrate_device(self, views_ptr, ids_ptr, corners_ptr, nobs, ninstants, cams, board_ids, obj, info_type, marker_size=-1.0, min_markers=1):
+        """rig_calibrate on device arrays (int32 [nobs], int32 [nobs], float32 [nobs][8], given as pointers)."""
+        head = (C.c_void_p(views_ptr), C.c_void_p(ids_ptr), C.c_void_p(corners_ptr), int(nobs), 1, int(ninstants))
+        return self._rig_calibrate_call(self.L.arucohip_rig_calibrate, head, ninstants, cams, None, board_ids, obj, info_type, marker_size, min_markers)
+
+    def rig_calibrate_batch(self, nframes, cams, board_ids, obj, info_type, marker_size=-1.0, min_markers=1):
+        """rig_calibrate on the device-resident markers of the first nframes frames of the last detect_batch call: frame f is view f."""
+        ninstants = int(nframes) // max(len(cams), 1)
+        return self._rig_calibrate_call(self.L.arucohip_rig_calibrate_batch, (int(nframes),), ninstants, cams, None, board_ids, obj, info_type,
+                                        marker_size, min_markers)
+
+    def _rig_pose_call(self, fn, head, ninstants, cams, ncams, board_ids, obj, info_type, marker_size, min_markers):
+        arr = self.rig_cameras(cams)
+        ncams = len(cams) if ncams is None else int(ncams)
+        ida = np.ascontiguousarray(board_ids, dtype=np.int32).reshape(-1)
+        oa = _f32(obj)
+        T = max(int(ninstants), 1)
+        out = (BoardOut * T)()
+        vu = np.zeros(T, np.int32)
+        self._chk(fn(self.h, *head, C.cast(arr, C.c_void_p), ncams, _ptr(ida), _ptr(oa), len(ida), int(info_type), float(marker_size), int(min_markers),
+                     C.cast(out, C.c_void_p), _ptr(vu)))
+        return [{"n_markers": out[t].n_markers, "has_pose": out[t].has_pose, "rvec": np.array(out[t].rvec), "tvec": np.array(out[t].tvec),
+                 "views_used": int(vu[t])} for t in range(ninstants)]
+
+    def rig_pose(self, views, ids, corners, ninstants, cams, board_ids, obj, info_type, marker_size=-1.0, min_markers=1, ncams=None):
+        """arucohip_rig_pose: the board's pose in the rig frame at every instant, from every calibrated camera whose view counts. cams: the
+        `cams` of rig_calibrate, or dicts with K, dist, calibrated, rvec, tvec. Returns a list of dicts n_markers, has_pose, rvec, tvec,
+        views_used."""
+        keep, head = self._rig_obs(views, ids, corners)
+        return self._rig_pose_call(self.L.arucohip_rig_pose, head + (int(ninstants),), ninstants, cams, ncams, board_ids, obj, info_type, marker_size,
+                                   min_markers)
+
+    def rig_pose_batch(self, nframes, cams, board_ids, obj, info_type, marker_size=-1.0, min_markers=1):
+        """rig_pose on the device-resident markers of the first nframes frames of the last detect_batch call: frame f is view f."""
+        ninstants = int(nframes) // max(len(cams), 1)
+        return self._rig_pose_call(self.L.arucohip_rig_pose_batch, (int(nframes),), ninstants, cams, None, board_ids, obj, info_type, marker_size,
+                                   min_markers)
 
     # ---- chessboard-corner (ChArUco) boards
     def charuco_board_image(self, layout, ids, centered=False):

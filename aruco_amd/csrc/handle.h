@@ -140,6 +140,8 @@ struct arucohip_handle {
     Mem<CalibState> hc_calib{true};   // pinned copy of the solver state, read once per iteration
     Mem<uint8_t> d_map;               // marker mapping: observations, slot tables, start values, per-frame systems, the reduced system (map_carve)
     Mem<MapState> hc_map{true};       // pinned copy of its solver state, read once per iteration
+    Mem<uint8_t> d_rig;               // camera rigs: observations, view slots, start values, per-view systems, the reduced system, poses (rig_carve)
+    Mem<RigState> hc_rig{true};       // pinned copy of its solver state, read once per iteration
     Mem<uint8_t> d_planar;            // arucohip_planar_poses: results and staged markers of one call
     Mem<uint8_t> d_overlay;           // arucohip_draw_*_batch: primitive lists of one chunk of frames, staged host markers / boards
     Mem<uint8_t> d_overlay_frames;    // arucohip_draw_*_batch: staged host frames
@@ -186,7 +188,7 @@ struct arucohip_handle {
     //   capture and replay; batches that decode from cell medians neither touch nor move buf.patches, and buf.cells is create-time memory;
     // - neither: the other Buffers arrays, zero_block and h_markers are create-time memory (`held`); d_erode, d_canny and the user decoder's
     //   staging and d_pyr belong to configurations that are not graphed; wt_out is set only inside chunk_enqueue, which does not run this path.
-    //   Memory no captured launch reads (d_bgr, undistortion, calibration, marker mapping, board and GL batches, planar poses, marker recovery, overlays, EM, HRM, fiducial generation, ChArUco corners and ChromaticMask scratch) may
+    //   Memory no captured launch reads (d_bgr, undistortion, calibration, marker mapping, camera rigs, board and GL batches, planar poses, marker recovery, overlays, EM, HRM, fiducial generation, ChArUco corners and ChromaticMask scratch) may
     //   be replaced at any time.
     struct FrameGraph {
         hipGraphExec_t exec = nullptr;

@@ -402,6 +402,71 @@ void launch_map_init(hipStream_t s, const MapDev& d, const CamModel& cam);
 void launch_map_iteration(hipStream_t s, const MapDev& d);
 void launch_map_finish(hipStream_t s, const MapDev& d);
 
+// Camera rigs (k_rig.hip): the rigid transforms rig -> camera of ncams cameras with fixed intrinsics, and the pose of a board in the rig
+// frame from every camera that sees it. View v = instant * ncams + camera.
+constexpr int RIG_MAX_CAMERAS = 16;     // ARUCOHIP_RIG_MAX_CAMERAS
+constexpr int RIG_MAX_BOARD = 128;      // board markers: a view holds at most RIG_VIEW_POINTS correspondences
+constexpr int RIG_VIEW_POINTS = 512;    // = MAX_BOARD_POINTS
+constexpr int RIG_MAX_N = 6 * (RIG_MAX_CAMERAS - 1);
+constexpr int RIG_J = 13;               // a Jacobian row: 6 camera columns, 6 board-pose columns, the residual
+constexpr int RIG_G = RIG_J * (RIG_J + 1) / 2;   // 91 entries of the upper triangle of a view's Gram matrix
+constexpr int RIG_REC = 42;             // doubles per view of an eliminated instant: Y_c (36), g_c - W_c u (6)
+enum { RIG_ERR_NO_REFERENCE = 1, RIG_ERR_TOO_FEW = 2, RIG_ERR_DEGENERATE = 4 };
+
+struct RigCam {
+    CamModel cam;      // for the single-camera start pose
+    double in[9];      // fx fy cx cy k1 k2 p1 p2 k3
+};
+
+struct RigState {
+    double cost;       // sum of squared residuals at cpose[cur] / ipose[cur]
+    double cdn, cpn;   // |camera step|^2 and |camera parameters|^2 of the last solve
+    int32_t lg, cur, done, iters, max_iter, attempts, err, solve_failed, ncal, nused, npts, pad_;
+};
+
+struct RigDev {
+    int ncams, ninstants, nboard, min_markers, info_type;
+    float marker_size;
+    // observations: obs_view != nullptr: nobs entries in any order; else view v owns obs_cnt[v] entries from v * obs_stride
+    const int32_t* obs_view;
+    const int32_t* obs_id;
+    const float* obs_corners;   // 8 per observation
+    const int32_t* obs_cnt;
+    int nobs, obs_stride;
+    const int32_t* ids;         // [nboard]
+    const float* bobj;          // [nboard][12]
+    const RigCam* cams;         // [ncams]
+    int32_t* vn;                // [V] member markers of a view
+    int32_t* vok;               // [V] the view counts: >= min_markers member markers and a start pose
+    int32_t* vact;              // [V] the view takes part in the solve
+    double* vT;                 // [V][12] the view's single-camera board pose: R (9), t (3)
+    float* pobj;                // [V][RIG_VIEW_POINTS][3] the view's object points, metres
+    float* pimg;                // [V][RIG_VIEW_POINTS][2]
+    int32_t* edge_t;            // [RIG_MAX_CAMERAS][RIG_MAX_CAMERAS] the instant an edge takes its transform from, -1: no edge
+    int32_t* edge_q;            // its score
+    int32_t* calibrated;        // [ncams]
+    double* cpose;              // [2][ncams][6] rvec, tvec rig -> camera (current / candidate)
+    int32_t* used;              // [T]
+    int32_t* lead;              // [T] the first camera of the instant that takes part
+    double* ipose;              // [2][T][6] board pose of every instant in the rig frame
+    double* gram;               // [V][RIG_G]
+    double* rec;                // [V][RIG_REC]
+    double* fu;                 // [T][6] u = U~^-1 g_p
+    double* S;                  // [N][N] the reduced system (lower triangle; its Cholesky factor after the solve), N = 6 (ncams - 1)
+    double* delta;              // [N] reduced right-hand side, then the camera step
+    double* vcost;              // [2][V]
+    double* vchg;               // [T][2]
+    arucohip_board_t* boards;   // [T] rig pose: results
+    int32_t* views_used;        // [T]
+    RigState* st;
+};
+
+void launch_rig_views(hipStream_t s, const RigDev& d);
+void launch_rig_calib_init(hipStream_t s, const RigDev& d);
+void launch_rig_calib_iteration(hipStream_t s, const RigDev& d);
+void launch_rig_calib_finish(hipStream_t s, const RigDev& d);
+void launch_rig_pose(hipStream_t s, const RigDev& d);
+
 // Board occlusion mask (k_chromatic.hip): ChromaticMask of the reference, src/chromaticmask.cpp.
 constexpr int CHROMA_CELL = 20;       // ChromaticMask::_cellSize
 constexpr int CHROMA_MIN_FIT = 10;    // EMClassifier::train fits only when the discretised histogram holds >= 10 samples

@@ -16,6 +16,7 @@
 //           map_update_kernel   (one thread: accept / reject, lambda, stopping rule)
 #include <float.h>
 
+#include "chol_device.h"
 #include "internal.h"
 #include "planar_device.h"
 
@@ -421,7 +422,7 @@ __global__ __launch_bounds__(256) void map_assemble_kernel(MapDev d) {
     d.S[(size_t)i * N + j] = i == j ? sum + lambda * diag : sum;
 }
 
-// One workgroup. Cholesky S = L L^T in place (right-looking; the matrix stays in HBM, the current column in LDS), L y = g, L^T x = y.
+// One workgroup. Cholesky S = L L^T in place, L y = g, L^T x = y (chol_device.h).
 // A pivot that is not positive or a step that is not finite gives a zero step and st->solve_failed: a rejected step, as does a frame
 // whose damped U~ map_normal_kernel could not solve. Then the
 // candidate marker poses mpose[other] = mpose[cur] - step and the norms of step and parameters.
@@ -429,53 +430,8 @@ __global__ __launch_bounds__(MAP_SOLVE_THREADS) void map_solve_kernel(MapDev d) 
     __shared__ double s_col[MAP_MAX_N], s_b[MAP_MAX_N], s_piv;
     __shared__ int s_fail;
     const int N = 6 * (d.nboard - 1), tid = threadIdx.x, T = MAP_SOLVE_THREADS;
-    double* S = d.S;
-    if (tid == 0) s_fail = 0;
     for (int i = tid; i < N; i += T) s_b[i] = d.delta[i];
-    __syncthreads();
-    for (int k = 0; k < N; k++) {
-        if (tid == 0) {
-            const double v = S[(size_t)k * N + k];
-            if (!(v > 0) || !isfinite(v)) s_fail = 1;
-            s_piv = sqrt(v);
-            S[(size_t)k * N + k] = s_piv;
-        }
-        __syncthreads();
-        if (s_fail) break;
-        const double piv = s_piv;
-        for (int i = k + 1 + tid; i < N; i += T) {
-            const double l = S[(size_t)i * N + k] / piv;
-            S[(size_t)i * N + k] = l, s_col[i] = l;
-        }
-        __syncthreads();
-        const int n = N - k - 1;
-        for (int e = tid; e < n * n; e += T) {
-            const int i = k + 1 + e / n, j = k + 1 + e % n;
-            if (j <= i) S[(size_t)i * N + j] -= s_col[i] * s_col[j];
-        }
-        __syncthreads();
-    }
-    if (!s_fail) {
-        for (int k = 0; k < N; k++) {
-            if (tid == 0) s_b[k] /= S[(size_t)k * N + k];
-            __syncthreads();
-            const double y = s_b[k];
-            for (int i = k + 1 + tid; i < N; i += T) s_b[i] -= S[(size_t)i * N + k] * y;
-            __syncthreads();
-        }
-        for (int k = N - 1; k >= 0; k--) {
-            if (tid == 0) s_b[k] /= S[(size_t)k * N + k];
-            __syncthreads();
-            const double x = s_b[k];
-            for (int i = tid; i < k; i += T) s_b[i] -= S[(size_t)k * N + i] * x;
-            __syncthreads();
-        }
-        int bad = 0;
-        for (int i = tid; i < N; i += T) bad |= !isfinite(s_b[i]);
-        if (__syncthreads_or(bad) && tid == 0) s_fail = 1;
-    }
-    __syncthreads();
-    const int fail = s_fail;
+    const int fail = chol_solve_block<MAP_SOLVE_THREADS>(d.S, N, s_col, s_b, &s_piv, &s_fail, tid);
     MapState* st = d.st;
     const int cur = st->cur, nb = d.nboard;
     for (int i = tid; i < N; i += T) {

@@ -1532,6 +1532,119 @@ private:
     float repj_err_thres;
 };
 
+// Several cameras on one frame, exposed together (no counterpart in this snapshot of the reference; cv::stereoCalibrate answers the
+// first question for two cameras). cameras[c] holds camera c's fixed intrinsics; Rvec[c] / Tvec[c] (3x1 double) its transform rig ->
+// camera and calibrated[c] whether calibrate() reached it; camera 0 is the rig frame. View v = instant * cameras.size() + camera: an
+// interleaved stream is a batch as it stands. Solved on the device (arucohip_rig_calibrate* / arucohip_rig_pose*, include/arucohip.h).
+class CameraRig {
+public:
+    std::vector<CameraParameters> cameras;
+    std::vector<cv::Mat_<double> > Rvec, Tvec;
+    std::vector<bool> calibrated;
+    std::vector<double> cameraRms;   // of the last calibrate, pixels
+    double rms;
+    int minMarkers;                  // member markers a view must hold to count
+
+    CameraRig() : rms(0), minMarkers(1) {}
+    explicit CameraRig(const std::vector<CameraParameters>& cams) : cameras(cams), rms(0), minMarkers(1) {}
+
+    // The cameras' transforms from the markers of every view (views[v]: the markers detected in view v), and the board's pose in the rig
+    // frame at every instant (a Board without Rvec / Tvec for an instant that was not used).
+    std::vector<Board> calibrate(MarkerDetector& detector, const std::vector<std::vector<Marker> >& views, const BoardConfiguration& bc, float markerSizeMeters = -1) {
+        return run_(detector.handle(), true, &views, 0, bc, markerSizeMeters);
+    }
+    // The same on the device-resident markers of the first nframes frames of a handle's last batch: frame f is view f, ncams must equal
+    // cameras.size(). A MarkerDetector's own handle holds one frame, which is no whole instant; a stream of several cameras goes through
+    // arucohip_detect_batch on a handle of the caller's, created with room for the batch, and that handle is passed here.
+    std::vector<Board> calibrate(arucohip_handle* h, const BoardConfiguration& bc, float markerSizeMeters, int ncams, int nframes) {
+        if (ncams != (int)cameras.size()) arucohip_throw_(ARUCOHIP_E_INVALID, "CameraRig::calibrate: ncams differs from the cameras given", nullptr);
+        return run_(h, true, nullptr, nframes, bc, markerSizeMeters);
+    }
+    std::vector<Board> calibrate(MarkerDetector& detector, const BoardConfiguration& bc, float markerSizeMeters, int ncams, int nframes) {
+        return calibrate(detector.handle(), bc, markerSizeMeters, ncams, nframes);
+    }
+    // The board's pose in the rig frame at every instant, from every calibrated camera that sees part of it.
+    std::vector<Board> detect(MarkerDetector& detector, const std::vector<std::vector<Marker> >& views, const BoardConfiguration& bc, float markerSizeMeters = -1) {
+        return run_(detector.handle(), false, &views, 0, bc, markerSizeMeters);
+    }
+    std::vector<Board> detect(arucohip_handle* h, const BoardConfiguration& bc, float markerSizeMeters, int nframes) {
+        return run_(h, false, nullptr, nframes, bc, markerSizeMeters);
+    }
+    std::vector<Board> detect(MarkerDetector& detector, const BoardConfiguration& bc, float markerSizeMeters, int nframes) {
+        return detect(detector.handle(), bc, markerSizeMeters, nframes);
+    }
+
+private:
+    std::vector<Board> run_(arucohip_handle* h, bool calib, const std::vector<std::vector<Marker> >* views, int nframes, const BoardConfiguration& bc,
+                            float markerSizeMeters) {
+        const int nc = (int)cameras.size();
+        std::vector<arucohip_rig_camera_t> cams(std::max(nc, 1));
+        for (int c = 0; c < nc; c++) {
+            arucohip_rig_camera_t& rc = cams[c];
+            std::memset(&rc, 0, sizeof(rc));
+            float d[8];
+            if (!mat_to_K_(cameras[c].CameraMatrix, rc.K)) arucohip_throw_(ARUCOHIP_E_INVALID, "CameraRig: a camera matrix is empty", nullptr);
+            rc.ndist = mat_to_dist_(cameras[c].Distorsion, d);
+            for (int k = 0; k < 5 && k < rc.ndist; k++) rc.dist[k] = d[k];
+            if (!calib && c < (int)calibrated.size() && calibrated[c] && c < (int)Rvec.size() && c < (int)Tvec.size() && !Rvec[c].empty() && !Tvec[c].empty()) {
+                rc.calibrated = 1;
+                for (int k = 0; k < 3; k++) rc.rvec[k] = Rvec[c](k), rc.tvec[k] = Tvec[c](k);
+            }
+        }
+        std::vector<int32_t> ov, oi, ids(bc.ids.begin(), bc.ids.end());
+        std::vector<float> oc, obj;
+        for (size_t i = 0; i < bc.objPoints.size(); i++)
+            for (int p = 0; p < 4 && p < (int)bc.objPoints[i].size(); p++)
+                obj.push_back(bc.objPoints[i][p].x), obj.push_back(bc.objPoints[i][p].y), obj.push_back(bc.objPoints[i][p].z);
+        if (views) {
+            nframes = (int)views->size();
+            for (size_t v = 0; v < views->size(); v++)
+                for (size_t i = 0; i < (*views)[v].size(); i++) {
+                    const Marker& m = (*views)[v][i];
+                    if (m.size() != 4) continue;
+                    ov.push_back((int32_t)v), oi.push_back(m.id);
+                    for (int k = 0; k < 4; k++) oc.push_back(m[k].x), oc.push_back(m[k].y);
+                }
+            if (nc > 0 && nframes % nc != 0) arucohip_throw_(ARUCOHIP_E_INVALID, "CameraRig: the views are not whole instants", nullptr);
+        }
+        const int ninstants = nc > 0 ? nframes / nc : 0;
+        std::vector<arucohip_board_t> out(std::max(ninstants, 1));
+        std::vector<int32_t> used(std::max(ninstants, 1));
+        std::vector<double> brv(std::max(ninstants, 1) * 3), btv(std::max(ninstants, 1) * 3), crms(std::max(nc, 1));
+        int rc;
+        if (calib)
+            rc = views ? arucohip_rig_calibrate(h, ov.data(), oi.data(), oc.data(), (int)ov.size(), 0, ninstants, cams.data(), nc, ids.data(), obj.data(),
+                                                (int)ids.size(), bc.mInfoType, markerSizeMeters, minMarkers, used.data(), brv.data(), btv.data(), crms.data(),
+                                                &rms, nullptr)
+                       : arucohip_rig_calibrate_batch(h, nframes, cams.data(), nc, ids.data(), obj.data(), (int)ids.size(), bc.mInfoType, markerSizeMeters,
+                                                      minMarkers, used.data(), brv.data(), btv.data(), crms.data(), &rms, nullptr);
+        else
+            rc = views ? arucohip_rig_pose(h, ov.data(), oi.data(), oc.data(), (int)ov.size(), 0, ninstants, cams.data(), nc, ids.data(), obj.data(),
+                                           (int)ids.size(), bc.mInfoType, markerSizeMeters, minMarkers, out.data(), nullptr)
+                       : arucohip_rig_pose_batch(h, nframes, cams.data(), nc, ids.data(), obj.data(), (int)ids.size(), bc.mInfoType, markerSizeMeters,
+                                                 minMarkers, out.data(), nullptr);
+        arucohip_throw_(rc, calib ? "CameraRig::calibrate" : "CameraRig::detect", h);
+        if (calib) {
+            Rvec.assign(nc, cv::Mat_<double>()), Tvec.assign(nc, cv::Mat_<double>()), calibrated.assign(nc, false);
+            cameraRms.assign(crms.begin(), crms.begin() + nc);
+            for (int c = 0; c < nc; c++) {
+                calibrated[c] = cams[c].calibrated != 0;
+                Rvec[c] = cv::Mat_<double>(3, 1), Tvec[c] = cv::Mat_<double>(3, 1);
+                for (int k = 0; k < 3; k++) Rvec[c](k) = cams[c].rvec[k], Tvec[c](k) = cams[c].tvec[k];
+            }
+        }
+        std::vector<Board> boards(ninstants);
+        for (int t = 0; t < ninstants; t++) {
+            boards[t].conf = bc;
+            if (!(calib ? used[t] != 0 : out[t].has_pose != 0)) continue;
+            boards[t].Rvec = cv::Mat_<double>(3, 1), boards[t].Tvec = cv::Mat_<double>(3, 1);
+            for (int k = 0; k < 3; k++)
+                boards[t].Rvec(k) = calib ? brv[3 * t + k] : out[t].rvec[k], boards[t].Tvec(k) = calib ? btv[3 * t + k] : out[t].tvec[k];
+        }
+        return boards;
+    }
+};
+
 // A chessboard whose white squares carry the markers (OpenCV's aruco module: CharucoBoard, interpolateCornersCharuco,
 // estimatePoseCharucoBoard, calibrateCameraCharuco; no counterpart in the reference). The calibration points are the chessboard's inner
 // corners: the markers of the detector's last frame say which corner is which, and each corner is refined in the frame

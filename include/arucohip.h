@@ -540,6 +540,73 @@ int arucohip_board_map_batch(arucohip_handle* h, int nframes, const int32_t* ids
                              int32_t* mapped, int32_t* used, double* frame_rvec, double* frame_tvec, double* marker_rms, double* rms,
                              int32_t* iterations);
 
+/* Camera rigs: several cameras on one frame, exposed together. Two questions that no single-camera call answers: where the cameras stand
+ * relative to each other (arucohip_rig_calibrate*, what cv::stereoCalibrate answers for two cameras with fixed intrinsics), and where a
+ * board is, using every camera that sees part of it at this instant (arucohip_rig_pose*). No counterpart in this snapshot of the
+ * reference.
+ * A rig is ncams cameras, 2 .. ARUCOHIP_RIG_MAX_CAMERAS. Camera c has fixed intrinsics (K, dist with ndist 0, 4 or 5) and a rigid
+ * transform rig -> camera, X_c = R_c X_rig + t_c. Camera 0 is the rig frame: its transform is the identity and never a variable. An
+ * instant t is one simultaneous exposure of all cameras, a view the pair (t, c) with index v = t * ncams + c: the camera varies
+ * fastest, so an interleaved multi-camera stream is a batch as it stands. The board is ids / obj / nboard / info_type / marker_size
+ * as arucohip_board_detect_batch takes it (planar or not, PIX boards scaled to metres by marker_size), at most 128 markers: a view
+ * holds at most 512 points. The cost, everywhere: over every counted view and every corner k of every member marker m in it, the
+ * squared pixel residual of project(K_c, dist_c, R_c (R_t X_mk + t_t) + t_c) - x, with (R_t, t_t) the board's pose in the rig frame at
+ * instant t. FP64 on the device.
+ * Which observations count:
+ *  - an id that is not on the board is ignored; a repeated id within a view keeps the first, in detection order;
+ *  - a view counts when it holds >= min_markers (>= 1) member markers and its single-camera start pose exists: the pose of
+ *    arucohip_board_detect_batch without the reprojection filter;
+ *  - calibration: an instant is eligible when at least 2 of its views count. The score of a camera pair (a, b) is the largest
+ *    min(n_a, n_b) of member-marker counts over the eligible instants where both views count (ties: the lower instant). A spanning tree
+ *    grows from camera 0 and always adds the camera whose best edge into the reached set scores highest (ties: the lower camera; among a
+ *    camera's equal edges the lower reached camera). A camera b reached through edge (a, b) at instant t starts at T_b = V_tb V_ta^-1 T_a,
+ *    V the view's single-camera pose. A camera the tree does not reach gets calibrated = 0 and zeros (not an error); its views are not
+ *    used. An instant is used when at least 2 of its counted views belong to calibrated cameras; it starts at T_c^-1 V_tc from the
+ *    counted, calibrated view with the most member markers (ties: the lower camera);
+ *  - rig pose: the same view rule; only cameras passed with calibrated != 0 take part (camera 0's transform is the identity whatever
+ *    its rvec / tvec hold); an instant has a pose when at least one such view counts, with the same start;
+ *  - views and instants that do not count or are not used change no output bit.
+ * Calibration is Levenberg-Marquardt over the cameras' transforms with every used instant's pose eliminated per instant (Schur
+ * complement; the reduced system is 6 (ncams - 1) square), CvLevMarq's rule as arucohip_calibrate_camera and arucohip_board_map: at most
+ * 30 accepted steps or a relative step below DBL_EPSILON. All sums run in a fixed order (points within a view, views in camera order,
+ * instants in instant order, no floating-point atomics): two calls, or host and device input, give the same bits. The rig pose runs
+ * the same rule on the 6 pose unknowns of every instant, all instants in one launch.
+ * ARUCOHIP_E_INVALID: ncams < 2, ninstants < 1 (or beyond the last batch), ndist not 0, 4 or 5, a NULL required pointer (cams, ids,
+ * obj; out of the pose calls), a PIX board without marker_size, min_markers < 1, nframes no multiple of ncams; calibrate: no eligible
+ * instant shows camera 0, or no camera besides camera 0 is reached; pose: no camera has calibrated != 0. ARUCOHIP_E_CAPACITY: ncams >
+ * ARUCOHIP_RIG_MAX_CAMERAS, nboard > 128. A call that fails writes none of its outputs. The calls return when their outputs are
+ * complete and leave the single-frame graph and the last batch's results as they are. rotateXAxis is not offered here. */
+#define ARUCOHIP_RIG_MAX_CAMERAS 16
+typedef struct arucohip_rig_camera {
+    float K[9];           /* in: fixed intrinsics, row-major 3x3 */
+    float dist[5];        /* in: k1 k2 p1 p2 k3, the first ndist are read */
+    int32_t ndist;        /* in: 0, 4 or 5 */
+    int32_t calibrated;   /* out of calibrate, in of pose */
+    double rvec[3], tvec[3];   /* rig -> camera, out of calibrate, in of pose; camera 0: zeros */
+} arucohip_rig_camera_t;
+/* Observations as three parallel arrays of nobs entries (view index in [0, ninstants * ncams), id, 8 floats x0 y0 .. x3 y3), in any order
+ * of views; the order within a view is the detection order. on_device: the three arrays are device pointers. cams: ncams entries,
+ * in-out. Optional outputs (may be NULL): used (ninstants), board_rvec / board_tvec (3 doubles per instant: the board in the rig frame,
+ * zeros for an instant that is not used), camera_rms (ncams, pixels, root mean square over the points of a camera's views), rms
+ * (sqrt(sum |r|^2 / points)), iterations (accepted steps). */
+int arucohip_rig_calibrate(arucohip_handle* h, const int32_t* obs_view, const int32_t* obs_id, const float* obs_corners, int nobs,
+                           int on_device, int ninstants, arucohip_rig_camera_t* cams, int ncams, const int32_t* ids, const float* obj,
+                           int nboard, int info_type, float marker_size, int min_markers, int32_t* used, double* board_rvec,
+                           double* board_tvec, double* camera_rms, double* rms, int32_t* iterations);
+/* The same on the markers of the first nframes frames of the LAST arucohip_detect_batch call, where they are (device-resident, every
+ * chunk and worker): frame f is view f, nframes / ncams instants. */
+int arucohip_rig_calibrate_batch(arucohip_handle* h, int nframes, arucohip_rig_camera_t* cams, int ncams, const int32_t* ids,
+                                 const float* obj, int nboard, int info_type, float marker_size, int min_markers, int32_t* used,
+                                 double* board_rvec, double* board_tvec, double* camera_rms, double* rms, int32_t* iterations);
+/* The board's pose in the rig frame at every instant: out[t] (ninstants entries; has_pose = 0 and zeros for an instant no calibrated
+ * camera's view counts in; n_markers = the member markers summed over the views used), views_used[t] (may be NULL). */
+int arucohip_rig_pose(arucohip_handle* h, const int32_t* obs_view, const int32_t* obs_id, const float* obs_corners, int nobs,
+                      int on_device, int ninstants, const arucohip_rig_camera_t* cams, int ncams, const int32_t* ids, const float* obj,
+                      int nboard, int info_type, float marker_size, int min_markers, arucohip_board_t* out, int32_t* views_used);
+int arucohip_rig_pose_batch(arucohip_handle* h, int nframes, const arucohip_rig_camera_t* cams, int ncams, const int32_t* ids,
+                            const float* obj, int nboard, int info_type, float marker_size, int min_markers, arucohip_board_t* out,
+                            int32_t* views_used);
+
 /* Board occlusion mask: ChromaticMask / EMClassifier of the reference (src/chromaticmask.cpp). Each of the mc x nc cells of the board
  * holds a 2-component Gaussian mixture over the 256 grey levels of one 8-bit plane; a pixel on the board is 1 when its level is
  * "board colour" under the model, 0 where something in front of the board hides it. The reference's quirks are kept;
