@@ -21,6 +21,9 @@ BOARD_NONE, BOARD_PIX, BOARD_METERS = -1, 0, 1
 CALIB_USE_INTRINSIC_GUESS, CALIB_FIX_ASPECT_RATIO, CALIB_FIX_PRINCIPAL_POINT, CALIB_ZERO_TANGENT_DIST = 1, 2, 4, 8
 CALIB_FIX_FOCAL_LENGTH, CALIB_FIX_K1, CALIB_FIX_K2, CALIB_FIX_K3 = 16, 32, 64, 128
 CALIB_MAX_VIEW_POINTS = 512
+# arucohip_fisheye_calibrate*
+FISHEYE_USE_INTRINSIC_GUESS, FISHEYE_FIX_ASPECT_RATIO, FISHEYE_FIX_PRINCIPAL_POINT = 1, 2, 4
+FISHEYE_FIX_K1, FISHEYE_FIX_K2, FISHEYE_FIX_K3, FISHEYE_FIX_K4 = 8, 16, 32, 64
 # arucohip_board_map*: listed markers, listed markers used per frame
 MAP_MAX_MARKERS, MAP_MAX_FRAME_MARKERS = 64, 16
 # arucohip_rig_*: cameras of a rig, markers of its board
@@ -85,6 +88,22 @@ class CharucoOpt(C.Structure):
     _fields_ = [("min_markers", C.c_int32), ("max_win", C.c_int32)]
 
 
+class Fisheye(C.Structure):
+    """arucohip_fisheye_t: the equidistant fisheye model, K row-major and D = k1..k4."""
+    _fields_ = [("K", C.c_double * 9), ("D", C.c_double * 4)]
+
+
+def fisheye_models(models):
+    """A ctypes array of Fisheye from one (K, D) pair or a list of them; K is 3x3 or 9 values."""
+    if len(models) == 2 and len(models[1]) == 4:   # one (K, D): D has four entries, a second model two
+        models = [models]
+    arr = (Fisheye * len(models))()
+    for m, (K, D) in zip(arr, models):
+        m.K[:] = [float(v) for v in np.asarray(K, np.float64).reshape(9)]
+        m.D[:] = [float(v) for v in np.asarray(D, np.float64).reshape(4)]
+    return arr
+
+
 CHARUCO_CORNER_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("start_x", "<f4"), ("start_y", "<f4"), ("found", "<i4"), ("win", "<i4"),
                                  ("markers", "<i4"), ("pad_", "<i4")])
 assert CHARUCO_CORNER_DTYPE.itemsize == 32
@@ -146,6 +165,8 @@ SYMBOLS = [
     "arucohip_default_recover", "arucohip_board_recover_batch",
     "arucohip_default_charuco", "arucohip_charuco_board_size", "arucohip_charuco_board_image", "arucohip_charuco_corners_batch",
     "arucohip_charuco_calibrate_batch", "arucohip_charuco_pose_batch",
+    "arucohip_fisheye_undistort_points", "arucohip_fisheye_distort_points", "arucohip_fisheye_undistort",
+    "arucohip_fisheye_undistort_markers_batch", "arucohip_fisheye_calibrate", "arucohip_fisheye_calibrate_board_batch",
 ]
 
 _lib = None
@@ -303,6 +324,12 @@ def load():
     L.arucohip_charuco_corners_batch.argtypes = [vp, vp, vp, i, vp, i, i, i, sz, sz, i, vp, vp, vp, i]
     L.arucohip_charuco_calibrate_batch.argtypes = [vp, f, i, i, i, i, vp, vp, vp, vp, vp, vp]
     L.arucohip_charuco_pose_batch.argtypes = [vp, i, vp, vp, i, f, i, i, vp]
+    L.arucohip_fisheye_undistort_points.argtypes = [vp, vp, vp, f, vp, i, i, vp, vp]
+    L.arucohip_fisheye_distort_points.argtypes = [vp, vp, vp, vp, i, i, vp]
+    L.arucohip_fisheye_undistort.argtypes = [vp, vp, i, i, i, sz, sz, i, i, vp, vp, f, vp, i]
+    L.arucohip_fisheye_undistort_markers_batch.argtypes = [vp, i, vp, i, vp, f, vp, i, vp, i, vp]
+    L.arucohip_fisheye_calibrate.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp]
+    L.arucohip_fisheye_calibrate_board_batch.argtypes = [vp, i, vp, vp, i, i, f, i, i, i, i, vp, vp, vp, vp, vp]
     L.arucohip_default_params.argtypes = [vp]
     L.arucohip_default_limits.argtypes = [vp, i, i, i]
     _lib = L
@@ -543,6 +570,80 @@ class Handle:
         self._chk(self.L.arucohip_undistort(self.h, _ptr(a), n, wid, hgt, wid * cn, wid * hgt * cn, cn, 0, _ptr(Ka), _ptr(da),
                                             0 if da is None else da.size, _ptr(out), 0))
         return out
+
+    # ---- fisheye lenses: model = (K, D) with D = k1..k4; Knew = the ideal pinhole camera (None: K); max_angle <= 0: the default 1.4 rad
+    def fisheye_undistort_points(self, pts, model, Knew=None, max_angle=0.0):
+        """Fisheye pixels [n][2] -> (ideal pixels under Knew as float32 [n][2], valid [n] bool); invalid points are (0, 0)."""
+        p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 2)
+        m, Kn = fisheye_models((model[0], model[1])), _f32(Knew)
+        out = np.zeros_like(p)
+        valid = np.zeros(len(p), np.uint8)
+        self._chk(self.L.arucohip_fisheye_undistort_points(self.h, m, _ptr(Kn), float(max_angle), _ptr(p), len(p), 0, _ptr(out), _ptr(valid)))
+        return out, valid.astype(bool)
+
+    def fisheye_distort_points(self, pts, model, Knew=None):
+        """Ideal pixels under Knew [n][2] -> fisheye pixels float32 [n][2]."""
+        p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 2)
+        m, Kn = fisheye_models((model[0], model[1])), _f32(Knew)
+        out = np.zeros_like(p)
+        self._chk(self.L.arucohip_fisheye_distort_points(self.h, m, _ptr(Kn), _ptr(p), len(p), 0, _ptr(out)))
+        return out
+
+    def fisheye_points_device(self, src_ptr, n, dst_ptr, model, Knew=None, max_angle=0.0, valid_ptr=None):
+        """Either direction on device arrays (plain integers), asynchronous on the handle's stream: with valid_ptr fisheye -> ideal pixels,
+        without it ideal -> fisheye pixels."""
+        m, Kn = fisheye_models((model[0], model[1])), _f32(Knew)
+        if valid_ptr is None:
+            rc = self.L.arucohip_fisheye_distort_points(self.h, m, _ptr(Kn), C.c_void_p(src_ptr), int(n), 1, C.c_void_p(dst_ptr))
+        else:
+            rc = self.L.arucohip_fisheye_undistort_points(self.h, m, _ptr(Kn), float(max_angle), C.c_void_p(src_ptr), int(n), 1, C.c_void_p(dst_ptr),
+                                                          C.c_void_p(valid_ptr))
+        self._chk(rc)
+
+    def fisheye_undistort(self, img, model, Knew=None, max_angle=0.0):
+        """Host frames seen through a fisheye lens -> the frames of the ideal camera Knew: [H][W], [H][W][3], [N][H][W] -> same shape."""
+        a = np.ascontiguousarray(img, dtype=np.uint8)
+        if a.ndim == 2:
+            n, (hgt, wid), cn = 1, a.shape, 1
+        elif a.ndim == 3 and a.shape[2] == 3:
+            n, (hgt, wid), cn = 1, a.shape[:2], 3
+        else:
+            n, hgt, wid = a.shape
+            cn = 1
+        m, Kn = fisheye_models((model[0], model[1])), _f32(Knew)
+        out = np.empty_like(a)
+        self._chk(self.L.arucohip_fisheye_undistort(self.h, _ptr(a), n, wid, hgt, wid * cn, wid * hgt * cn, cn, 0, m, _ptr(Kn), float(max_angle),
+                                                    _ptr(out), 0))
+        return out
+
+    def fisheye_undistort_device(self, src_ptr, nframes, width, height, channels, dst_ptr, model, Knew=None, max_angle=0.0, row_stride=None,
+                                 frame_stride=None):
+        """The same between device arrays (plain integers): asynchronous on the handle's stream, dst tightly packed."""
+        m, Kn = fisheye_models((model[0], model[1])), _f32(Knew)
+        rs = width * channels if row_stride is None else row_stride
+        self._chk(self.L.arucohip_fisheye_undistort(self.h, C.c_void_p(src_ptr), int(nframes), int(width), int(height), rs,
+                                                    rs * height if frame_stride is None else frame_stride, int(channels), 1, m, _ptr(Kn),
+                                                    float(max_angle), C.c_void_p(dst_ptr), 1))
+
+    def fisheye_undistort_markers_batch(self, nframes, models, Knew=None, max_angle=0.0, cap=64, allow=()):
+        """arucohip_fisheye_undistort_markers_batch on the last batch, in place: models = one (K, D) or a list of them (frame f uses
+        models[f % len]), Knew = None, one 3x3 or one per model. Returns (markers per frame, counts, dropped per frame); cap = 0: the
+        lists are not fetched (empty lists, counts None)."""
+        m = fisheye_models(models)
+        Kn = None if Knew is None else np.ascontiguousarray(np.broadcast_to(np.asarray(Knew, np.float32).reshape(-1, 9), (len(m), 9)))
+        out = np.zeros((nframes, cap), MARKER_DTYPE)
+        n = np.zeros(nframes, np.int32)
+        dropped = np.zeros(nframes, np.int32)
+        self._chk(self.L.arucohip_fisheye_undistort_markers_batch(self.h, int(nframes), m, len(m), _ptr(Kn), float(max_angle), _ptr(out) if cap else None,
+                                                                  int(cap), _ptr(n) if cap else None, 0, _ptr(dropped)), allow=allow)
+        return [out[f, :max(min(int(n[f]), cap), 0)].copy() for f in range(nframes)], n if cap else None, dropped
+
+    def fisheye_undistort_markers_batch_device(self, nframes, models, out_ptr, cap, n_out_ptr, Knew=None, max_angle=0.0):
+        """The same with the lists written to device arrays (pointers as plain integers): asynchronous on the handle's stream."""
+        m = fisheye_models(models)
+        Kn = None if Knew is None else np.ascontiguousarray(np.broadcast_to(np.asarray(Knew, np.float32).reshape(-1, 9), (len(m), 9)))
+        self._chk(self.L.arucohip_fisheye_undistort_markers_batch(self.h, int(nframes), m, len(m), _ptr(Kn), float(max_angle), C.c_void_p(out_ptr), int(cap),
+                                                                  C.c_void_p(n_out_ptr), 1, None))
 
     def set_pyr_down(self, level):
         """MarkerDetector::pyrDown(level): threshold, contours and quads on the frame reduced `level` times (0..3), the rest on the frame."""
@@ -1013,6 +1114,58 @@ class Handle:
                                                         _ptr(da), _ptr(used), _ptr(rv), _ptr(tv), C.byref(rms)))
         nv = int(used.sum())
         return {"rms": rms.value, "K": Ka.reshape(3, 3), "dist": da, "rvecs": rv[:nv], "tvecs": tv[:nv], "used": used.astype(bool)}
+
+    # ---- fisheye calibration: model = (K, D) is the start with FISHEYE_USE_INTRINSIC_GUESS, K's fx / fy ratio with FISHEYE_FIX_ASPECT_RATIO
+    @staticmethod
+    def _fisheye_start(model):
+        m = Fisheye()
+        if model is not None:
+            m = fisheye_models((model[0], model[1]))[0]
+        return m
+
+    @staticmethod
+    def _fisheye_result(m, rms, **more):
+        return dict({"rms": rms.value, "K": np.array(list(m.K)).reshape(3, 3), "D": np.array(list(m.D))}, **more)
+
+    def fisheye_calibrate(self, obj_list, img_list, image_size, flags=0, model=None):
+        """arucohip_fisheye_calibrate on planar views: obj_list[v] (n, 3), img_list[v] (n, 2); image_size = (width, height)."""
+        if len(obj_list) != len(img_list):
+            raise ValueError("obj_list and img_list differ in length")
+        objs = [np.asarray(o, np.float32).reshape(-1, 3) for o in obj_list]
+        imgs = [np.asarray(p, np.float32).reshape(-1, 2) for p in img_list]
+        if any(len(o) != len(p) for o, p in zip(objs, imgs)):
+            raise ValueError("a view has different numbers of object and image points")
+        npts = np.array([len(o) for o in objs], np.int32)
+        oa = np.ascontiguousarray(np.concatenate(objs) if objs else np.zeros((0, 3), np.float32))
+        ia = np.ascontiguousarray(np.concatenate(imgs) if imgs else np.zeros((0, 2), np.float32))
+        m = self._fisheye_start(model)
+        V = len(objs)
+        rv, tv, pv, rms = np.zeros((V, 3)), np.zeros((V, 3)), np.zeros(V), C.c_double()
+        self._chk(self.L.arucohip_fisheye_calibrate(self.h, _ptr(oa), _ptr(ia), _ptr(npts), V, 0, int(image_size[0]), int(image_size[1]), int(flags),
+                                                    C.byref(m), _ptr(rv), _ptr(tv), _ptr(pv), C.byref(rms)))
+        return self._fisheye_result(m, rms, rvecs=rv, tvecs=tv, per_view_rms=pv)
+
+    def fisheye_calibrate_device(self, obj_ptr, img_ptr, npoints_ptr, nviews, image_size, flags=0, model=None):
+        """fisheye_calibrate on device arrays (obj float32 [N,3], img float32 [N,2], npoints int32 [nviews], given as pointers)."""
+        m = self._fisheye_start(model)
+        rv, tv, pv, rms = np.zeros((nviews, 3)), np.zeros((nviews, 3)), np.zeros(nviews), C.c_double()
+        self._chk(self.L.arucohip_fisheye_calibrate(self.h, obj_ptr, img_ptr, npoints_ptr, nviews, 1, int(image_size[0]), int(image_size[1]), int(flags),
+                                                    C.byref(m), _ptr(rv), _ptr(tv), _ptr(pv), C.byref(rms)))
+        return self._fisheye_result(m, rms, rvecs=rv, tvecs=tv, per_view_rms=pv)
+
+    def fisheye_calibrate_board_batch(self, nframes, ids, obj, info_type, image_size, marker_size=-1.0, min_markers=4, flags=0, model=None):
+        """fisheye_calibrate on the board detections of the last detect_batch call, left on the device: frames with at least min_markers
+        board markers are the views. rvecs / tvecs have one row per used frame; used[f] marks them."""
+        ida = np.ascontiguousarray(ids, dtype=np.int32)
+        oa = _f32(obj)
+        m = self._fisheye_start(model)
+        used = np.zeros(nframes, np.int32)
+        rv, tv, rms = np.zeros((nframes, 3)), np.zeros((nframes, 3)), C.c_double()
+        self._chk(self.L.arucohip_fisheye_calibrate_board_batch(self.h, nframes, _ptr(ida), _ptr(oa), len(ida), info_type, float(marker_size),
+                                                                int(min_markers), int(image_size[0]), int(image_size[1]), int(flags), C.byref(m),
+                                                                _ptr(used), _ptr(rv), _ptr(tv), C.byref(rms)))
+        nv = int(used.sum())
+        return self._fisheye_result(m, rms, rvecs=rv[:nv], tvecs=tv[:nv], used=used.astype(bool))
 
     # ---- marker mapping: the 3-D layout of a rigid marker set
     def _map_call(self, fn, head, nframes, board_ids, K, dist, marker_size, tail=()):

@@ -1,4 +1,4 @@
-// Host side of camera calibration (k_calib.hip).
+// Host side of camera calibration (k_calib.hip): the pinhole entry points, and the pieces the fisheye ones (capi_fisheye.hip) share.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -8,13 +8,7 @@
 
 #include "handle.h"
 
-extern "C" {
-
-// Byte offsets into h->d_calib for V views, npts points, nframes gather slots and a board of nboard markers.
-struct CalibCarve {
-    size_t st, off, npt, init, red, bs, pose, vcost, vchg, obj, img, nmark, bids, bobj, total;
-};
-static CalibCarve calib_carve(int V, size_t npts, int nframes, int nboard) {
+CalibCarve calib_carve(int V, size_t npts, int nframes, int nboard) {
     CalibCarve c;
     size_t at = 0;
     auto take = [&](size_t bytes) {
@@ -34,47 +28,28 @@ static CalibCarve calib_carve(int V, size_t npts, int nframes, int nboard) {
     return c;
 }
 
-// Levenberg-Marquardt on views whose points are already on the device (d.obj / d.img, offsets off[], counts npt[]): start values, then
-// one host synchronisation per iteration for the stop flag.
-static int calib_solve(arucohip_handle* h, CalibDev d, const CalibCarve& c, const std::vector<int32_t>& off, const std::vector<int32_t>& npt,
-                       int W, int H, int flags, double* K, double* dist, double* rvecs, double* tvecs, double* per_view_rms, double* rms) {
+// Levenberg-Marquardt on views whose points are already on the device (v.d.obj / v.d.img, offsets off[], counts npt[]) from the state
+// `st` (start intrinsics, free mask, flags, model): start values, then one host synchronisation per iteration for the stop flag.
+// focal_start: the focal lengths come from the views' homographies (pinhole without a guess).
+int calib_solve(arucohip_handle* h, const CalibViews& v, CalibState st, bool focal_start, double intr[9], double* rvecs, double* tvecs,
+                double* per_view_rms, double* rms) {
+    CalibDev d = v.d;
+    const CalibCarve& c = v.c;
     const int V = d.nviews;
     uint8_t* base = h->d_calib;
     d.off = (const int32_t*)(base + c.off), d.npt = (const int32_t*)(base + c.npt);
     d.init = (double*)(base + c.init), d.red = (double*)(base + c.red), d.bs = (double*)(base + c.bs);
     d.pose = (double*)(base + c.pose), d.vcost = (double*)(base + c.vcost), d.vchg = (double*)(base + c.vchg);
     d.st = (CalibState*)(base + c.st);
-    const bool guess = flags & ARUCOHIP_CALIB_USE_INTRINSIC_GUESS;
-    CalibState st;
-    std::memset(&st, 0, sizeof(st));
-    st.flags = flags, st.max_iter = 30, st.lg = -3;
-    st.aspect = (K[0] > 0 && K[4] > 0) ? K[0] / K[4] : 1.0;
-    if (guess) {
-        const double g[9] = {K[0], K[4], K[2], K[5], dist[0], dist[1], dist[2], dist[3], dist[4]};
-        for (int i = 0; i < 9; i++) st.intr[i] = g[i];
-        if (!(g[0] > 0 && g[1] > 0)) return fail(h, ARUCOHIP_E_INVALID, "USE_INTRINSIC_GUESS needs positive focal lengths");
-        if (flags & ARUCOHIP_CALIB_FIX_ASPECT_RATIO) st.intr[0] = st.aspect * st.intr[1];
-    } else {
-        st.intr[2] = (W - 1) * 0.5, st.intr[3] = (H - 1) * 0.5;
-    }
-    if (flags & ARUCOHIP_CALIB_ZERO_TANGENT_DIST) st.intr[6] = st.intr[7] = 0;
-    int mask = 0x1FF;
-    if (flags & ARUCOHIP_CALIB_FIX_ASPECT_RATIO) mask &= ~1;
-    if (flags & ARUCOHIP_CALIB_FIX_FOCAL_LENGTH) mask &= ~3;
-    if (flags & ARUCOHIP_CALIB_FIX_PRINCIPAL_POINT) mask &= ~(4 | 8);
-    if (flags & ARUCOHIP_CALIB_ZERO_TANGENT_DIST) mask &= ~(64 | 128);
-    if (flags & ARUCOHIP_CALIB_FIX_K1) mask &= ~16;
-    if (flags & ARUCOHIP_CALIB_FIX_K2) mask &= ~32;
-    if (flags & ARUCOHIP_CALIB_FIX_K3) mask &= ~256;
-    st.free_mask = mask;
+    st.max_iter = 30, st.lg = -3;
     hipStream_t s = h->stream;
     HIPCHK(h, h->hc_calib.reserve(sizeof(CalibState)));
     CalibState* hs = h->hc_calib;
     *hs = st;
     HIPCHK(h, hipMemcpyAsync(d.st, hs, sizeof(st), hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync((void*)d.off, off.data(), (size_t)V * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync((void*)d.npt, npt.data(), (size_t)V * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    launch_calib_init(s, d, guess);
+    HIPCHK(h, hipMemcpyAsync((void*)d.off, v.off.data(), (size_t)V * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync((void*)d.npt, v.npt.data(), (size_t)V * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    launch_calib_init(s, d, !focal_start);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(hs, d.st, sizeof(st), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
@@ -92,67 +67,61 @@ static int calib_solve(arucohip_handle* h, CalibDev d, const CalibCarve& c, cons
     HIPCHK(h, hipMemcpyAsync(pose.data(), d.pose + (size_t)st.cur * V * 6, pose.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipMemcpyAsync(vcost.data(), d.vcost + (size_t)st.cur * V, vcost.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
-    const double* in = st.intr;
-    const double Ko[9] = {in[0], 0, in[2], 0, in[1], in[3], 0, 0, 1};
-    for (int i = 0; i < 9; i++) K[i] = Ko[i];
-    for (int i = 0; i < 5; i++) dist[i] = in[4 + i];
+    for (int i = 0; i < 9; i++) intr[i] = st.intr[i];
     double e2 = 0, np = 0;
-    for (int v = 0; v < V; v++) {
-        e2 += vcost[v], np += npt[v];
-        if (per_view_rms) per_view_rms[v] = std::sqrt(vcost[v] / npt[v]);
+    for (int i = 0; i < V; i++) {
+        e2 += vcost[i], np += v.npt[i];
+        if (per_view_rms) per_view_rms[i] = std::sqrt(vcost[i] / v.npt[i]);
         for (int k = 0; k < 3; k++) {
-            if (rvecs) rvecs[3 * v + k] = pose[6 * v + k];
-            if (tvecs) tvecs[3 * v + k] = pose[6 * v + 3 + k];
+            if (rvecs) rvecs[3 * i + k] = pose[6 * i + k];
+            if (tvecs) tvecs[3 * i + k] = pose[6 * i + 3 + k];
         }
     }
     if (rms) *rms = std::sqrt(e2 / np);
     return ARUCOHIP_OK;
 }
 
-int arucohip_calibrate_camera(arucohip_handle* h, const float* obj, const float* img, const int32_t* npoints, int nviews, int on_device, int W,
-                              int H, int flags, double* K, double* dist, double* rvecs, double* tvecs, double* per_view_rms, double* rms) {
-    if (!h) return ARUCOHIP_E_INVALID;
-    if (!obj || !img || !npoints || !K || !dist || nviews < 1 || W <= 0 || H <= 0)
-        return fail(h, ARUCOHIP_E_INVALID, "calibrate_camera: NULL argument, no views or an empty image size");
+// the caller's views (host or device arrays) as the solver takes them, in h->d_calib
+int calib_views_of_points(arucohip_handle* h, const float* obj, const float* img, const int32_t* npoints, int nviews, int on_device, CalibViews* v) {
     HIPCHK(h, hipSetDevice(h->device));
-    std::vector<int32_t> npt((size_t)nviews), off((size_t)nviews);
+    v->npt.resize((size_t)nviews), v->off.resize((size_t)nviews);
     if (on_device)
-        HIPCHK(h, hipMemcpy(npt.data(), npoints, (size_t)nviews * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(v->npt.data(), npoints, (size_t)nviews * sizeof(int32_t), hipMemcpyDeviceToHost));
     else
-        std::memcpy(npt.data(), npoints, (size_t)nviews * sizeof(int32_t));
+        std::memcpy(v->npt.data(), npoints, (size_t)nviews * sizeof(int32_t));
     size_t total = 0;
-    for (int v = 0; v < nviews; v++) {
-        if (npt[v] < 4) return fail(h, ARUCOHIP_E_INVALID, "a calibration view has fewer than 4 points");
-        if (npt[v] > CALIB_MAX_POINTS) return fail(h, ARUCOHIP_E_CAPACITY, "a calibration view has more than ARUCOHIP_CALIB_MAX_VIEW_POINTS points");
-        off[v] = (int32_t)total, total += (size_t)npt[v];
+    for (int i = 0; i < nviews; i++) {
+        if (v->npt[i] < 4) return fail(h, ARUCOHIP_E_INVALID, "a calibration view has fewer than 4 points");
+        if (v->npt[i] > CALIB_MAX_POINTS) return fail(h, ARUCOHIP_E_CAPACITY, "a calibration view has more than ARUCOHIP_CALIB_MAX_VIEW_POINTS points");
+        v->off[i] = (int32_t)total, total += (size_t)v->npt[i];
     }
     if (total > (size_t)INT32_MAX) return fail(h, ARUCOHIP_E_CAPACITY, "too many calibration points");
-    const CalibCarve c = calib_carve(nviews, on_device ? 0 : total, 0, 0);
-    HIPCHK(h, h->d_calib.reserve(c.total));
-    CalibDev d{};
-    d.nviews = nviews;
+    v->c = calib_carve(nviews, on_device ? 0 : total, 0, 0);
+    HIPCHK(h, h->d_calib.reserve(v->c.total));
+    v->d = CalibDev{};
+    v->d.nviews = nviews;
     if (on_device) {
-        d.obj = obj, d.img = img;
+        v->d.obj = obj, v->d.img = img;
     } else {
-        float* dobj = (float*)((uint8_t*)h->d_calib + c.obj);
-        float* dimg = (float*)((uint8_t*)h->d_calib + c.img);
+        float* dobj = (float*)((uint8_t*)h->d_calib + v->c.obj);
+        float* dimg = (float*)((uint8_t*)h->d_calib + v->c.img);
         HIPCHK(h, hipMemcpyAsync(dobj, obj, total * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(dimg, img, total * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        d.obj = dobj, d.img = dimg;
+        v->d.obj = dobj, v->d.img = dimg;
     }
-    return calib_solve(h, d, c, off, npt, W, H, flags, K, dist, rvecs, tvecs, per_view_rms, rms);
+    return ARUCOHIP_OK;
 }
 
-int arucohip_calibrate_board_batch(arucohip_handle* h, int nframes, const int32_t* ids, const float* obj, int nboard, int info_type,
-                                   float marker_size, int min_markers, int W, int H, int flags, double* K, double* dist, int32_t* used,
-                                   double* rvecs, double* tvecs, double* rms) {
-    if (!h) return ARUCOHIP_E_INVALID;
-    if (!K || !dist || W <= 0 || H <= 0) return fail(h, ARUCOHIP_E_INVALID, "calibrate_board_batch: NULL K / dist or an empty image size");
+// the board detections of the last batch's first nframes frames as views, where they are: *owner is the worker of the batch's first chunk,
+// in whose scratch and on whose stream the calibration then runs
+int calib_views_of_batch(arucohip_handle* h, int nframes, const int32_t* ids, const float* obj, int nboard, int info_type, float marker_size,
+                         int min_markers, int32_t* used, arucohip_handle** owner, CalibViews* v) {
     if (nboard <= 0 || !ids || !obj) return fail(h, ARUCOHIP_E_BOARD_CONFIG, "invalid BoardConfig that is empty");
     if (nframes < 1 || nframes > h->last.frames) return fail(h, ARUCOHIP_E_INVALID, "nframes exceeds the last batch");
     HIPCHK(h, hipSetDevice(h->device));
     const Batch b = h->last.cut(nframes);
-    arucohip_handle* o = b.span[0].w;   // the worker of the batch's first chunk: the calibration runs on its stream, in its scratch
+    arucohip_handle* o = b.span[0].w;
+    *owner = o;
     // the metres-per-unit factor of board_pose_kernel for PIX boards (marker side from the first edge of marker 0)
     const float dx = obj[0] - obj[3], dy = obj[1] - obj[4], dz = obj[2] - obj[5];
     const double side = std::sqrt((double)dx * dx + (double)dy * dy + (double)dz * dz);
@@ -180,18 +149,78 @@ int arucohip_calibrate_board_batch(arucohip_handle* h, int nframes, const int32_
     HIPCHK(h, hipMemcpyAsync(fnpt.data(), dnpt, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, o->stream));
     HIPCHK(h, hipMemcpyAsync(fnmark.data(), dnmark, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, o->stream));
     HIPCHK(h, hipStreamSynchronize(o->stream));
-    std::vector<int32_t> off, npt;
+    v->off.clear(), v->npt.clear();
     for (int f = 0; f < nframes; f++) {
         const bool take = fnmark[f] >= std::max(min_markers, 1) && fnpt[f] != 0;
         if (take && fnpt[f] < 0) return fail(h, ARUCOHIP_E_CAPACITY, "a frame has more board points than ARUCOHIP_CALIB_MAX_VIEW_POINTS");
         if (used) used[f] = take ? 1 : 0;
-        if (take) off.push_back(f * CALIB_MAX_POINTS), npt.push_back(fnpt[f]);
+        if (take) v->off.push_back(f * CALIB_MAX_POINTS), v->npt.push_back(fnpt[f]);
     }
-    if (off.empty()) return fail(h, ARUCOHIP_E_INVALID, "no frame holds min_markers board markers");
-    CalibDev d{};
-    d.nviews = (int)off.size(), d.obj = dobj, d.img = dimg;
+    if (v->off.empty()) return fail(h, ARUCOHIP_E_INVALID, "no frame holds min_markers board markers");
     // the per-view arrays are carved for nframes >= views; the off / npt arrays are rewritten with the views
-    rc = calib_solve(o, d, c, off, npt, W, H, flags, K, dist, rvecs, tvecs, nullptr, rms);
+    v->c = c, v->d = CalibDev{};
+    v->d.nviews = (int)v->off.size(), v->d.obj = dobj, v->d.img = dimg;
+    return ARUCOHIP_OK;
+}
+
+// the pinhole run: start state from (K, dist, flags), results back into K and dist
+static int calib_pinhole(arucohip_handle* h, const CalibViews& v, int W, int H, int flags, double* K, double* dist, double* rvecs, double* tvecs,
+                         double* per_view_rms, double* rms) {
+    const bool guess = flags & ARUCOHIP_CALIB_USE_INTRINSIC_GUESS;
+    CalibState st;
+    std::memset(&st, 0, sizeof(st));
+    st.flags = flags, st.model = CALIB_MODEL_PINHOLE;
+    st.aspect = (K[0] > 0 && K[4] > 0) ? K[0] / K[4] : 1.0;
+    if (guess) {
+        const double g[9] = {K[0], K[4], K[2], K[5], dist[0], dist[1], dist[2], dist[3], dist[4]};
+        for (int i = 0; i < 9; i++) st.intr[i] = g[i];
+        if (!(g[0] > 0 && g[1] > 0)) return fail(h, ARUCOHIP_E_INVALID, "USE_INTRINSIC_GUESS needs positive focal lengths");
+        if (flags & ARUCOHIP_CALIB_FIX_ASPECT_RATIO) st.intr[0] = st.aspect * st.intr[1];
+    } else {
+        st.intr[2] = (W - 1) * 0.5, st.intr[3] = (H - 1) * 0.5;
+    }
+    if (flags & ARUCOHIP_CALIB_ZERO_TANGENT_DIST) st.intr[6] = st.intr[7] = 0;
+    int mask = 0x1FF;
+    if (flags & ARUCOHIP_CALIB_FIX_ASPECT_RATIO) mask &= ~1;
+    if (flags & ARUCOHIP_CALIB_FIX_FOCAL_LENGTH) mask &= ~3;
+    if (flags & ARUCOHIP_CALIB_FIX_PRINCIPAL_POINT) mask &= ~(4 | 8);
+    if (flags & ARUCOHIP_CALIB_ZERO_TANGENT_DIST) mask &= ~(64 | 128);
+    if (flags & ARUCOHIP_CALIB_FIX_K1) mask &= ~16;
+    if (flags & ARUCOHIP_CALIB_FIX_K2) mask &= ~32;
+    if (flags & ARUCOHIP_CALIB_FIX_K3) mask &= ~256;
+    st.free_mask = mask;
+    double in[9];
+    const int rc = calib_solve(h, v, st, !guess, in, rvecs, tvecs, per_view_rms, rms);
+    if (rc) return rc;
+    const double Ko[9] = {in[0], 0, in[2], 0, in[1], in[3], 0, 0, 1};
+    for (int i = 0; i < 9; i++) K[i] = Ko[i];
+    for (int i = 0; i < 5; i++) dist[i] = in[4 + i];
+    return ARUCOHIP_OK;
+}
+
+extern "C" {
+
+int arucohip_calibrate_camera(arucohip_handle* h, const float* obj, const float* img, const int32_t* npoints, int nviews, int on_device, int W,
+                              int H, int flags, double* K, double* dist, double* rvecs, double* tvecs, double* per_view_rms, double* rms) {
+    if (!h) return ARUCOHIP_E_INVALID;
+    if (!obj || !img || !npoints || !K || !dist || nviews < 1 || W <= 0 || H <= 0)
+        return fail(h, ARUCOHIP_E_INVALID, "calibrate_camera: NULL argument, no views or an empty image size");
+    CalibViews v;
+    const int rc = calib_views_of_points(h, obj, img, npoints, nviews, on_device, &v);
+    if (rc) return rc;
+    return calib_pinhole(h, v, W, H, flags, K, dist, rvecs, tvecs, per_view_rms, rms);
+}
+
+int arucohip_calibrate_board_batch(arucohip_handle* h, int nframes, const int32_t* ids, const float* obj, int nboard, int info_type,
+                                   float marker_size, int min_markers, int W, int H, int flags, double* K, double* dist, int32_t* used,
+                                   double* rvecs, double* tvecs, double* rms) {
+    if (!h) return ARUCOHIP_E_INVALID;
+    if (!K || !dist || W <= 0 || H <= 0) return fail(h, ARUCOHIP_E_INVALID, "calibrate_board_batch: NULL K / dist or an empty image size");
+    CalibViews v;
+    arucohip_handle* o = nullptr;
+    int rc = calib_views_of_batch(h, nframes, ids, obj, nboard, info_type, marker_size, min_markers, used, &o, &v);
+    if (rc) return rc;
+    rc = calib_pinhole(o, v, W, H, flags, K, dist, rvecs, tvecs, nullptr, rms);
     if (rc && o != h) h->err = o->err;
     return rc;
 }

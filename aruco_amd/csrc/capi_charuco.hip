@@ -130,6 +130,8 @@ int arucohip_charuco_corners_batch(arucohip_handle* h, const arucohip_charuco_t*
     if (o.max_win < 2 || o.max_win > 15) return fail(h, ARUCOHIP_E_INVALID, "charuco_corners_batch: max_win is 2..15");
     if (nframes < 1 || nframes > h->last.frames) return fail(h, ARUCOHIP_E_INVALID, "nframes exceeds the last batch");
     if (W != h->last.frame_w || H != h->last.frame_h) return fail(h, ARUCOHIP_E_INVALID, "charuco_corners_batch: width / height are not the last batch's");
+    if (h->last.ideal)
+        return fail(h, ARUCOHIP_E_UNSUPPORTED, "charuco_corners_batch: the markers hold ideal corners (arucohip_fisheye_undistort_markers_batch); undistort the frames instead");
     if (row_stride < (size_t)W || (nframes > 1 && frame_stride < row_stride * (size_t)(H - 1) + W))
         return fail(h, ARUCOHIP_E_INVALID, "charuco_corners_batch: strides too small");
     HIPCHK(h, hipSetDevice(h->device));

@@ -43,6 +43,8 @@ int arucohip_board_recover_batch(arucohip_handle* h, int nframes, const int32_t*
     if (nboard <= 0 || !ids || !obj) return fail(h, ARUCOHIP_E_BOARD_CONFIG, "invalid BoardConfig that is empty");
     if (nboard * 12 > 8192) return fail(h, ARUCOHIP_E_CAPACITY, "board with too many markers");
     if (nframes < 1 || nframes > h->last.frames) return fail(h, ARUCOHIP_E_INVALID, "nframes exceeds the last batch");
+    if (h->last.ideal)
+        return fail(h, ARUCOHIP_E_UNSUPPORTED, "board_recover_batch: the markers hold ideal corners (arucohip_fisheye_undistort_markers_batch); undistort the frames instead");
     if ((out == nullptr) != (n_out == nullptr) || (out && cap < 1)) return fail(h, ARUCOHIP_E_INVALID, "board_recover_batch: out and n_out go together, with cap >= 1");
     if (!K) return fail(h, ARUCOHIP_E_INVALID, "board_recover_batch: K is required");
     if (info_type != ARUCOHIP_BOARD_PIX && info_type != ARUCOHIP_BOARD_METERS) return fail(h, ARUCOHIP_E_INVALID, "board_recover_batch: info_type is neither PIX nor METERS");

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "fisheye_device.h"
 #include "internal.h"
 
 using namespace ah;
@@ -63,6 +64,8 @@ struct Batch {
     int W = 0, H = 0, nthr = 1;   // W x H: the thresholded image (the frame reduced by the pyrDown level)
     int frame_w = 0, frame_h = 0;   // the frames themselves
     int board_frames = 0;   // frames whose board poses arucohip_board_detect_batch left in the workers' d_board
+    bool ideal = false;     // arucohip_fisheye_undistort_markers_batch replaced the corners by those of an ideal pinhole camera: they no
+                            // longer match the frames' pixels. Every detection sets the record whole and so clears it
     const Span* begin() const { return span; }
     const Span* end() const { return span + nspan; }
     // the worker that holds frame `frame` and the frame's index there; nullptr: the batch has no such frame
@@ -113,6 +116,14 @@ struct arucohip_handle {
     int umap_w = 0, umap_h = 0, umap_nd = -1;
     float umap_K[9] = {}, umap_d[8] = {};
     Mem<uint8_t> d_undist;            // undistorted frames when the caller wants them on the host
+    // fisheye lenses (capi_fisheye.hip): a map slot of its own, so that a fisheye camera never evicts the pinhole map above
+    Mem<short2> d_fmap_xy;
+    Mem<uint16_t> d_fmap_f;
+    int fmap_w = 0, fmap_h = 0;       // fmap_w = 0: none
+    double fmap_key[18] = {};         // K (4), D (4), Knew (9), max_angle
+    Mem<uint8_t> d_fisheye;           // scratch of one call: staged points and results, or the models and the dropped counts of a marker call
+    Mem<uint8_t> d_fisheye_frames;    // staged host frames and the remapped frames a host caller gets
+    std::vector<FisheyeCam> fisheye_cams;   // the models of the last marker call as they were copied to the workers
     Dictionary hrm;
     Mem<uint64_t> d_hrm;              // hrm.codes on the device
     // caller's own decoder (arucohip_set_decoder_callback)
@@ -188,7 +199,7 @@ struct arucohip_handle {
     //   capture and replay; batches that decode from cell medians neither touch nor move buf.patches, and buf.cells is create-time memory;
     // - neither: the other Buffers arrays, zero_block and h_markers are create-time memory (`held`); d_erode, d_canny and the user decoder's
     //   staging and d_pyr belong to configurations that are not graphed; wt_out is set only inside chunk_enqueue, which does not run this path.
-    //   Memory no captured launch reads (d_bgr, undistortion, calibration, marker mapping, camera rigs, board and GL batches, planar poses, marker recovery, overlays, EM, HRM, fiducial generation, ChArUco corners and ChromaticMask scratch) may
+    //   Memory no captured launch reads (d_bgr, undistortion, fisheye maps and scratch, calibration, marker mapping, camera rigs, board and GL batches, planar poses, marker recovery, overlays, EM, HRM, fiducial generation, ChArUco corners and ChromaticMask scratch) may
     //   be replaced at any time.
     struct FrameGraph {
         hipGraphExec_t exec = nullptr;
@@ -237,6 +248,24 @@ inline void border_rect(float border_dist, int W, int H, int r[4]) {
     const int x2 = (int)lrintf((float)W * (1.0f - border_dist)), y2 = (int)lrintf((float)H * (1.0f - border_dist));
     r[0] = std::min(x1, x2), r[1] = std::min(y1, y2), r[2] = std::max(x1, x2), r[3] = std::max(y1, y2);
 }
+
+// Camera calibration (capi_calib.hip), shared by the pinhole and the fisheye entry points.
+// Byte offsets into a handle's d_calib for V views, npts points, nframes gather slots and a board of nboard markers.
+struct CalibCarve {
+    size_t st, off, npt, init, red, bs, pose, vcost, vchg, obj, img, nmark, bids, bobj, total;
+};
+CalibCarve calib_carve(int V, size_t npts, int nframes, int nboard);
+// the views of one run: points on the device (d.obj / d.img, d.nviews), each view's offset and count, the scratch layout
+struct CalibViews {
+    CalibDev d{};
+    CalibCarve c{};
+    std::vector<int32_t> off, npt;
+};
+int calib_views_of_points(arucohip_handle* h, const float* obj, const float* img, const int32_t* npoints, int nviews, int on_device, CalibViews* v);
+int calib_views_of_batch(arucohip_handle* h, int nframes, const int32_t* ids, const float* obj, int nboard, int info_type, float marker_size,
+                         int min_markers, int32_t* used, arucohip_handle** owner, CalibViews* v);
+int calib_solve(arucohip_handle* h, const CalibViews& v, CalibState st, bool focal_start, double intr[9], double* rvecs, double* tvecs,
+                double* per_view_rms, double* rms);
 
 // fork: the other workers' streams wait for what the first worker's stream (the batch's own) has queued so far; errors are reported on h
 int fork_workers(arucohip_handle* h, const Batch& b);

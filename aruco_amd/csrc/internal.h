@@ -218,6 +218,11 @@ void launch_expand_thres(hipStream_t s, const FrameGeom& g, int plane, const Buf
 void launch_undist_map(hipStream_t s, int W, int H, const float* K, const float* dist, int ndist, short2* xy, uint16_t* fxy);
 void launch_remap(hipStream_t s, const uint8_t* src, size_t row_stride, size_t frame_stride, int W, int H, int cn, int nframes, const short2* xy,
                   const uint16_t* fxy, uint8_t* dst);
+// fisheye lenses (k_fisheye.hip; the model is fisheye_device.h's)
+struct FisheyeCam;
+void launch_fisheye_points(hipStream_t s, const FisheyeCam& cam, const float* src, int n, int undistort, float* dst, uint8_t* valid);
+void launch_fisheye_markers(hipStream_t s, const FisheyeCam* cams, int nmodels, int first, int nframes, const Buffers& b, int32_t* dropped);
+void launch_fisheye_map(hipStream_t s, const FisheyeCam& cam, int W, int H, short2* xy, uint16_t* fxy);
 int launch_canny(hipStream_t s, const uint8_t* gray, const FrameGeom& g, int nframes, int nthr, const Buffers& b, uint64_t* surv, uint64_t* edge, uint32_t* changed);
 void launch_erode(hipStream_t s, const FrameGeom& g, int nplanes, const Buffers& b, uint8_t* tmp);
 size_t erode_tiles_tmp_bytes(const FrameGeom& g, int nplanes);
@@ -322,13 +327,14 @@ constexpr int CALIB_MAX_POINTS = 512;   // points of one view (= the board kerne
 constexpr int CALIB_RED = 100;          // doubles per view of the reduced system: S_i (81), diag A_i (9), rhs_i (9), pad
 constexpr int CALIB_BS = 60;            // doubles per view for the back-substitution: u (6), M (6 x 9)
 enum { CALIB_ERR_DEGENERATE = 1, CALIB_ERR_NONPLANAR = 2 };
+enum { CALIB_MODEL_PINHOLE = 0, CALIB_MODEL_FISHEYE = 1 };   // fisheye: intr = fx fy cx cy k1 k2 k3 k4 and a ninth entry that stays 0
 
 struct CalibState {
     double intr[9];    // fx fy cx cy k1 k2 p1 p2 k3
     double cand[9], delta[9];
     double aspect;     // fx / fy under ARUCOHIP_CALIB_FIX_ASPECT_RATIO
     double cost;       // sum of squared residuals at intr / pose[cur]
-    int32_t flags, free_mask, lg, cur, done, iters, max_iter, attempts, err, pad_;
+    int32_t flags, free_mask, lg, cur, done, iters, max_iter, attempts, err, model;   // model: CALIB_MODEL_*
 };
 
 struct CalibDev {

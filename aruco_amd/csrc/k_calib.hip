@@ -1,4 +1,5 @@
-// Camera calibration from planar views (cv::calibrateCamera, pinhole + k1 k2 p1 p2 k3), FP64 throughout.
+// Camera calibration from planar views (cv::calibrateCamera, pinhole + k1 k2 p1 p2 k3), FP64 throughout. The same solver calibrates a
+// fisheye lens (CalibState::model, arucohip_fisheye_calibrate*): another projection and another start, everything else as below.
 //
 // Views are given as points (obj xyz float, img xy float) at d.off[v], d.npt[v] points each. One wave per view does everything
 // that touches the view's points; the few kernels that combine views run on one workgroup and add the views in view order, so
@@ -12,10 +13,21 @@
 //           calib_update_kernel     (one thread: accept / reject, lambda, stopping rule)
 #include <float.h>
 
+#include "fisheye_device.h"
 #include "internal.h"
 #include "pnp_device.h"
 
 namespace ah {
+
+// The camera model of a run (CalibState::model): the pinhole model of this file's header, or the fisheye model of fisheye_device.h, whose
+// eight intrinsics fx fy cx cy k1..k4 take the first eight of the nine columns (the ninth is zero and never free).
+__device__ inline void calib_project(int model, double X, double Y, double Z, const double* R, const double* dRdr, const double* t, const double* in,
+                                     double* mx, double* my, double* di, double* dp) {
+    if (model == CALIB_MODEL_FISHEYE)
+        fisheye_project_point_d(X, Y, Z, R, dRdr, t, in, mx, my, di, dp);
+    else
+        project_point_d(X, Y, Z, R, dRdr, t, in, mx, my, di, dp);
+}
 
 // Jacobian rows of one point are 16 doubles: 9 intrinsic columns, 6 pose columns, the residual
 constexpr int CJ = 16;
@@ -158,12 +170,23 @@ __global__ __launch_bounds__(64) void calib_pose_kernel(CalibDev d) {
     const float* obj = d.obj + (size_t)3 * d.off[v];
     const float* img = d.img + (size_t)2 * d.off[v];
     const float z0 = obj[2];
+    const double* in = d.st->intr;
+    const bool fisheye = d.st->model == CALIB_MODEL_FISHEYE;
     if (lane == 0) s_bad = 0;
     __syncthreads();
     for (int i = lane; i < n; i += 64) {
         if (obj[3 * i + 2] != z0) s_bad = 1;
         s_obj[3 * i] = obj[3 * i], s_obj[3 * i + 1] = obj[3 * i + 1], s_obj[3 * i + 2] = 0.f;
-        s_img[2 * i] = img[2 * i], s_img[2 * i + 1] = img[2 * i + 1];
+        if (fisheye) {
+            // the point undistorted with the start model, its angle clamped to 1.5 rad for this start only: normalised coordinates
+            const double x = ((double)img[2 * i] - in[2]) / in[0], y = ((double)img[2 * i + 1] - in[3]) / in[1], thd = hypot(x, y);
+            bool rising;
+            const double th = fmin(fmax(fisheye_solve_theta(in + 4, thd, &rising), 0.0), 1.5);
+            const double sc = thd > 0 ? tan(th) / thd : 1.0;
+            s_img[2 * i] = (float)(x * sc), s_img[2 * i + 1] = (float)(y * sc);
+        } else {
+            s_img[2 * i] = img[2 * i], s_img[2 * i + 1] = img[2 * i + 1];
+        }
     }
     __syncthreads();
     if (s_bad) {
@@ -172,11 +195,14 @@ __global__ __launch_bounds__(64) void calib_pose_kernel(CalibDev d) {
     }
     CamModel cam;
     cam.has_K = 1, cam.has_dist = 1, cam.marker_size = 0, cam.y_perp = 0;
-    const double* in = d.st->intr;
     for (int i = 0; i < 9; i++) cam.K[i] = 0;
     cam.K[0] = (float)in[0], cam.K[4] = (float)in[1], cam.K[2] = (float)in[2], cam.K[5] = (float)in[3], cam.K[8] = 1.f;
     for (int i = 0; i < 8; i++) cam.k[i] = 0;
     for (int i = 0; i < 5; i++) cam.k[i] = in[4 + i];
+    if (fisheye) {   // the points are normalised already: the identity camera
+        cam.K[0] = cam.K[4] = 1.f, cam.K[2] = cam.K[5] = 0.f;
+        for (int i = 0; i < 5; i++) cam.k[i] = 0;
+    }
     double r[3] = {0, 0, 0}, t[3] = {0, 0, 0};
     const bool ok = solve_pnp_planar_wave<64>(s_obj, s_img, n, cam, r, t, lane);
     if (lane != 0) return;
@@ -223,7 +249,7 @@ __global__ __launch_bounds__(64) void calib_normal_kernel(CalibDev d) {
         for (int c = 0; c < CJ; c++) rowv[c] = 0;
         if (i < n) {
             double mx, my, di[18], dp[12];
-            project_point_d(obj[3 * i], obj[3 * i + 1], obj[3 * i + 2], R, dRdr, p + 3, in, &mx, &my, di, dp);
+            calib_project(st->model, obj[3 * i], obj[3 * i + 1], obj[3 * i + 2], R, dRdr, p + 3, in, &mx, &my, di, dp);
             for (int c = 0; c < 9; c++) rowv[c] = di[row * 9 + c];
             if (fixar) rowv[1] += aspect * rowv[0], rowv[0] = 0;   // fx = aspect * fy: fy's column carries both
             for (int c = 0; c < 6; c++) rowv[9 + c] = dp[row * 6 + c];
@@ -331,7 +357,7 @@ __global__ __launch_bounds__(64) void calib_eval_kernel(CalibDev d, int step) {
     double e2 = 0;
     for (int i = lane; i < n; i += 64) {
         double mx, my;
-        project_point_d(obj[3 * i], obj[3 * i + 1], obj[3 * i + 2], R, nullptr, p + 3, in, &mx, &my, nullptr, nullptr);
+        calib_project(st->model, obj[3 * i], obj[3 * i + 1], obj[3 * i + 2], R, nullptr, p + 3, in, &mx, &my, nullptr, nullptr);
         const double ex = mx - (double)img[2 * i], ey = my - (double)img[2 * i + 1];
         e2 += ex * ex + ey * ey;
     }

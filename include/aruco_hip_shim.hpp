@@ -1645,6 +1645,121 @@ private:
     }
 };
 
+// A camera with a fisheye lens (cv::fisheye's equidistant model; no counterpart in the reference): K (3x3), D (k1..k4) and the image
+// size. The detector's corners, or the frames, are mapped once to an ideal pinhole camera (idealCamera(): Knew, no distortion), with
+// which every other class of this header then works unchanged. Knew is K unless newCameraMatrix holds a 3x3 matrix; maxAngle <= 0 is
+// 1.4 rad (arucohip_fisheye_*, include/arucohip.h).
+class FisheyeCamera {
+public:
+    cv::Mat_<double> K, D;
+    cv::Size size;
+    cv::Mat_<double> newCameraMatrix;
+    float maxAngle;
+    double rms;   // of the last calibrate, pixels
+
+    FisheyeCamera() : maxAngle(0), rms(0) {}
+    FisheyeCamera(const double k[9], const double d[4], cv::Size sz) : K(3, 3), D(1, 4), size(sz), maxAngle(0), rms(0) {
+        for (int i = 0; i < 9; i++) K(i / 3, i % 3) = k[i];
+        for (int i = 0; i < 4; i++) D(0, i) = d[i];
+    }
+    // the pinhole camera the undistorted markers and frames belong to
+    CameraParameters idealCamera() const {
+        float kn[9];
+        knew_(kn);
+        const float none[4] = {0.f, 0.f, 0.f, 0.f};
+        return CameraParameters(kn, none, 4, size);
+    }
+    // The markers of the detector's last frame where they lie on the device, mapped in place to the ideal camera and returned (without
+    // poses: BoardDetector::detect or MarkerDetector::calculateExtrinsics with idealCamera() give them). A marker with a corner beyond
+    // maxAngle is left out. The next detect() starts afresh.
+    std::vector<Marker> undistortMarkers(MarkerDetector& detector) {
+        std::vector<std::vector<Marker> > out = undistortMarkers(detector.handle(), 1);
+        return out[0];
+    }
+    // The same on the first nframes frames of the last batch of a handle of the caller's (arucohip_detect_batch): one list per frame.
+    std::vector<std::vector<Marker> > undistortMarkers(arucohip_handle* h, int nframes, int cap = 128) {
+        const arucohip_fisheye_t m = model_();
+        float kn[9];
+        knew_(kn);
+        std::vector<arucohip_marker_t> buf((size_t)std::max(nframes, 1) * cap);
+        std::vector<int32_t> n(std::max(nframes, 1));
+        arucohip_throw_(arucohip_fisheye_undistort_markers_batch(h, nframes, &m, 1, kn, maxAngle, buf.data(), cap, n.data(), 0, nullptr),
+                        "FisheyeCamera::undistortMarkers", h);
+        std::vector<std::vector<Marker> > out(nframes);
+        for (int f = 0; f < nframes; f++)
+            for (int i = 0; i < n[f] && i < cap; i++) out[f].push_back(Marker::from_abi(buf[(size_t)f * cap + i]));
+        return out;
+    }
+    // A frame (CV_8UC1 or CV_8UC3) as the ideal camera sees it, for the paths that read pixels around the markers (CharucoBoard, marker
+    // recovery, drawing): detect on the result with idealCamera().
+    void undistortImage(const cv::Mat& src, cv::Mat& dst) const {
+        if (src.type() != CV_8UC1 && src.type() != CV_8UC3) arucohip_throw_(ARUCOHIP_E_INVALID, "FisheyeCamera::undistortImage: CV_8UC1 or CV_8UC3 frames", nullptr);
+        const arucohip_fisheye_t m = model_();
+        float kn[9];
+        knew_(kn);
+        const int cn = src.type() == CV_8UC3 ? 3 : 1;
+        cv::Mat out(src.rows, src.cols, src.type());
+        SharedHandle_& sh = SharedHandle_::get();
+        std::lock_guard<std::mutex> lock(sh.mu);
+        arucohip_handle* h = sh.ensure(src.cols, src.rows);
+        arucohip_throw_(arucohip_fisheye_undistort(h, src.data, 1, src.cols, src.rows, src.step, (size_t)src.rows * src.step, cn, 0, &m, kn, maxAngle, out.data, 0),
+                        "FisheyeCamera::undistortImage", h);
+        dst = out;
+    }
+    // K and D from planar views (one list of object and image points per view), as cv::fisheye::calibrate is called: flags are
+    // ARUCOHIP_FISHEYE_*; with USE_INTRINSIC_GUESS the current K and D are the start. Returns the RMS reprojection error; rvecs / tvecs
+    // (3x1 double per view) may be NULL.
+    double calibrate(const std::vector<std::vector<cv::Point3f> >& objPointsV, const std::vector<std::vector<cv::Point2f> >& imgPointsV, cv::Size imageSize,
+                     int flags = 0, std::vector<cv::Mat>* rvecs = nullptr, std::vector<cv::Mat>* tvecs = nullptr) {
+        if (objPointsV.size() != imgPointsV.size()) arucohip_throw_(ARUCOHIP_E_INVALID, "FisheyeCamera::calibrate: object and image point lists differ", nullptr);
+        const int nv = (int)objPointsV.size();
+        std::vector<float> obj, img;
+        std::vector<int32_t> np;
+        for (int v = 0; v < nv; v++) {
+            if (objPointsV[v].size() != imgPointsV[v].size()) arucohip_throw_(ARUCOHIP_E_INVALID, "FisheyeCamera::calibrate: a view's point counts differ", nullptr);
+            np.push_back((int32_t)objPointsV[v].size());
+            for (const cv::Point3f& p : objPointsV[v]) obj.push_back(p.x), obj.push_back(p.y), obj.push_back(p.z);
+            for (const cv::Point2f& p : imgPointsV[v]) img.push_back(p.x), img.push_back(p.y);
+        }
+        arucohip_fisheye_t m;
+        std::memset(&m, 0, sizeof(m));
+        if (!K.empty() && !D.empty()) m = model_();
+        std::vector<double> rv((size_t)std::max(nv, 1) * 3), tv((size_t)std::max(nv, 1) * 3);
+        {
+            SharedHandle_& sh = SharedHandle_::get();
+            std::lock_guard<std::mutex> lock(sh.mu);
+            arucohip_handle* h = sh.ensure();
+            arucohip_throw_(arucohip_fisheye_calibrate(h, obj.data(), img.data(), np.data(), nv, 0, imageSize.width, imageSize.height, flags, &m, rv.data(),
+                                                       tv.data(), nullptr, &rms),
+                            "FisheyeCamera::calibrate", h);
+        }
+        K = cv::Mat_<double>(3, 3), D = cv::Mat_<double>(1, 4), size = imageSize;
+        for (int i = 0; i < 9; i++) K(i / 3, i % 3) = m.K[i];
+        for (int i = 0; i < 4; i++) D(0, i) = m.D[i];
+        for (int v = 0; v < nv && rvecs && tvecs; v++) {
+            if (v == 0) rvecs->clear(), tvecs->clear();
+            cv::Mat r(3, 1, CV_64FC1), t(3, 1, CV_64FC1);
+            for (int k = 0; k < 3; k++) r.at<double>(k, 0) = rv[3 * v + k], t.at<double>(k, 0) = tv[3 * v + k];
+            rvecs->push_back(r), tvecs->push_back(t);
+        }
+        return rms;
+    }
+
+private:
+    arucohip_fisheye_t model_() const {
+        if (K.empty() || D.empty() || K.total() != 9 || D.total() != 4) arucohip_throw_(ARUCOHIP_E_INVALID, "FisheyeCamera: K (3x3) and D (4) are not set", nullptr);
+        arucohip_fisheye_t m;
+        for (int i = 0; i < 9; i++) m.K[i] = K(i / 3, i % 3);
+        for (int i = 0; i < 4; i++) m.D[i] = D(i);
+        return m;
+    }
+    void knew_(float kn[9]) const {
+        const cv::Mat_<double>& src = (!newCameraMatrix.empty() && newCameraMatrix.total() == 9) ? newCameraMatrix : K;
+        if (src.empty() || src.total() != 9) arucohip_throw_(ARUCOHIP_E_INVALID, "FisheyeCamera: K (3x3) is not set", nullptr);
+        for (int i = 0; i < 9; i++) kn[i] = (float)src(i / 3, i % 3);
+    }
+};
+
 // A chessboard whose white squares carry the markers (OpenCV's aruco module: CharucoBoard, interpolateCornersCharuco,
 // estimatePoseCharucoBoard, calibrateCameraCharuco; no counterpart in the reference). The calibration points are the chessboard's inner
 // corners: the markers of the detector's last frame say which corner is which, and each corner is refined in the frame

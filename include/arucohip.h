@@ -607,6 +607,81 @@ int arucohip_rig_pose_batch(arucohip_handle* h, int nframes, const arucohip_rig_
                             const float* obj, int nboard, int info_type, float marker_size, int min_markers, arucohip_board_t* out,
                             int32_t* views_used);
 
+/* Fisheye lenses: the equidistant model as cv::fisheye writes it, FP64 on the device. No counterpart in the reference. For a
+ * camera-frame point (X, Y, Z): r = hypot(X, Y), theta = atan2(r, Z), theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 +
+ * k4 theta^8), pixel = (fx X theta_d / r + cx, fy Y theta_d / r + cy), the principal point when r = 0. Skew (K[1]) must be 0.
+ * Pixel to ray: x = (u - cx) / fx, y = (v - cy) / fy, theta_d = hypot(x, y); 10 Newton steps on theta P(theta) - theta_d from
+ * theta = theta_d; the ideal normalised point is (x, y) tan(theta) / theta_d, and (x, y) itself when theta_d = 0. A pixel is VALID
+ * when the residual after the last step is at most 1e-12 max(theta_d, 1), the derivative stayed positive during the iteration and
+ * theta <= max_angle. max_angle is in radians, 0 < max_angle < pi / 2 (ARUCOHIP_E_INVALID at or above pi / 2); a value <= 0 selects
+ * 1.4. The residual bound is loose on purpose: it only catches coefficients for which theta_d(theta) is not monotone up to the pixel.
+ * The pinhole entry points know nothing of this model. Instead the detected corners, or the frames, are mapped once to the pixels of
+ * an ideal pinhole camera Knew (row-major 3 x 3 floats, NULL: the model's K), and every solver of this header (marker and planar
+ * poses, board poses planar or 3-D, mapping, rig calibration and rig pose) then runs unchanged with K = Knew and ndist = 0.
+ * Not provided: skew, a fisheye model inside arucohip_rig_camera_t. */
+typedef struct arucohip_fisheye {
+    double K[9]; /* row-major */
+    double D[4]; /* k1..k4 */
+} arucohip_fisheye_t;
+/* n pixel pairs (src, dst: 2 floats per point; host memory, or device memory with on_device: then the call is asynchronous on the
+ * handle's stream) between fisheye pixels and ideal pixels under Knew. One lane per point; the result is rounded once from double to
+ * float. undistort: valid[i] = 1 or 0 (n bytes, where src and dst are), and an invalid point is written as (0, 0). distort: the
+ * forward model on the ray Knew^-1 (u, v, 1), every point. */
+int arucohip_fisheye_undistort_points(arucohip_handle* h, const arucohip_fisheye_t* model, const float* Knew, float max_angle,
+                                      const float* src, int n, int on_device, float* dst, uint8_t* valid);
+int arucohip_fisheye_distort_points(arucohip_handle* h, const arucohip_fisheye_t* model, const float* Knew, const float* src, int n,
+                                    int on_device, float* dst);
+/* Frames, for the paths that read pixels around the markers (arucohip_charuco_corners_batch, arucohip_board_recover_batch, overlays):
+ * detect on the result with K = Knew and no distortion. Arguments as arucohip_undistort (1 or 3 channels, dst tightly packed in host
+ * or device memory, asynchronous with a device dst). Destination pixel (x, y) reads the source at the forward model of the ray
+ * Knew^-1 (x, y, 1), bilinear with 5 fractional bits (round half to even) and constant 0 outside the frame and where theta >
+ * max_angle. The map is kept per (size, model, Knew, max_angle) in a slot of its own: it never evicts arucohip_undistort's map. */
+int arucohip_fisheye_undistort(arucohip_handle* h, const uint8_t* src, int nframes, int width, int height, size_t row_stride,
+                               size_t frame_stride, int channels, int src_on_device, const arucohip_fisheye_t* model, const float* Knew,
+                               float max_angle, uint8_t* dst, int dst_on_device);
+/* The device-resident markers of the first nframes frames of the LAST batch (a synchronous call, a waited ticket or a one-frame
+ * arucohip_detect; every chunk worker), in place: frame f uses models[f % nmodels] (an interleaved rig stream with one lens per camera
+ * is one call) and Knew + 9 (f % nmodels) (Knew: NULL or nmodels x 9 floats). Each marker's four corners become their ideal pixels;
+ * has_pose is set to 0 and ssize to -1, since a pose the batch computed came from the wrong model. A marker with an invalid corner
+ * leaves the list, which closes up in order; dropped[f] (host, nframes, may be NULL) counts them. Frames with n = -1 stay -1.
+ * out / n_out: both NULL or both given, with the layout, capacity rule and asynchrony rule of arucohip_board_recover_batch (the call
+ * is asynchronous when out is on the device or NULL and dropped is NULL).
+ * Every later reader of the last batch sees the ideal corners (arucohip_board_detect_batch, arucohip_planar_poses_batch,
+ * arucohip_board_map_batch, arucohip_rig_*_batch, ...: pass K = Knew, ndist = 0). Until the next detection a second call returns
+ * ARUCOHIP_E_INVALID, and arucohip_board_recover_batch and arucohip_charuco_corners_batch return ARUCOHIP_E_UNSUPPORTED: they match
+ * corners against the pixels of the distorted frame. For those, undistort the frames with arucohip_fisheye_undistort and detect on
+ * the result. */
+int arucohip_fisheye_undistort_markers_batch(arucohip_handle* h, int nframes, const arucohip_fisheye_t* models, int nmodels,
+                                             const float* Knew, float max_angle, arucohip_marker_t* out, int cap, int32_t* n_out,
+                                             int out_on_device, int32_t* dropped);
+/* Fisheye calibration from planar views, so that K and D need no other library. Arguments as arucohip_calibrate_camera and
+ * arucohip_calibrate_board_batch, with the model in/out instead of K / dist; rvecs, tvecs, per_view_rms, rms and used may be NULL.
+ * Views are planar (ARUCOHIP_E_UNSUPPORTED otherwise), at most ARUCOHIP_CALIB_MAX_VIEW_POINTS points each. The algorithm is this
+ * library's own:
+ *  - start values: cx = (width - 1) / 2, cy = (height - 1) / 2, fx = fy = max(width, height) / pi, D = 0; with
+ *    ARUCOHIP_FISHEYE_USE_INTRINSIC_GUESS the given model;
+ *  - every view's start pose: its points undistorted with the start model (each angle clamped to 1.5 rad, for this start only), then
+ *    the planar homography start of arucohip_calibrate_camera on the normalised points;
+ *  - Levenberg-Marquardt over the 8 intrinsics and every view's pose, the poses eliminated per view (Schur complement; per point 8
+ *    intrinsic, 6 pose and 1 residual column from the analytic Jacobian), the views' Gram matrices added in view order. It is
+ *    arucohip_calibrate_camera's solver with this projection: CvLevMarq's rule, at most 30 accepted steps or a relative step below
+ *    DBL_EPSILON. No floating-point atomics: two calls, or host and device input, give the same bits.
+ * The batch form reads the distorted corners of the last batch: after arucohip_fisheye_undistort_markers_batch it returns
+ * ARUCOHIP_E_INVALID. */
+#define ARUCOHIP_FISHEYE_USE_INTRINSIC_GUESS 1 /* start from the given model (else its K only gives the FIX_ASPECT_RATIO ratio) */
+#define ARUCOHIP_FISHEYE_FIX_ASPECT_RATIO 2    /* fx / fy stays at the ratio of the given K (1 when K holds no focal lengths) */
+#define ARUCOHIP_FISHEYE_FIX_PRINCIPAL_POINT 4
+#define ARUCOHIP_FISHEYE_FIX_K1 8
+#define ARUCOHIP_FISHEYE_FIX_K2 16
+#define ARUCOHIP_FISHEYE_FIX_K3 32
+#define ARUCOHIP_FISHEYE_FIX_K4 64
+int arucohip_fisheye_calibrate(arucohip_handle* h, const float* obj, const float* img, const int32_t* npoints, int nviews, int on_device,
+                               int width, int height, int flags, arucohip_fisheye_t* model, double* rvecs, double* tvecs,
+                               double* per_view_rms, double* rms);
+int arucohip_fisheye_calibrate_board_batch(arucohip_handle* h, int nframes, const int32_t* ids, const float* obj, int nboard,
+                                           int info_type, float marker_size, int min_markers, int width, int height, int flags,
+                                           arucohip_fisheye_t* model, int32_t* used, double* rvecs, double* tvecs, double* rms);
+
 /* Board occlusion mask: ChromaticMask / EMClassifier of the reference (src/chromaticmask.cpp). Each of the mc x nc cells of the board
  * holds a 2-component Gaussian mixture over the 256 grey levels of one 8-bit plane; a pixel on the board is 1 when its level is
  * "board colour" under the model, 0 where something in front of the board hides it. The reference's quirks are kept;
