@@ -8,64 +8,44 @@
 
 #include "handle.h"
 
-CalibCarve calib_carve(int V, size_t npts, int nframes, int nboard) {
-    CalibCarve c;
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t here = at;
-        at += (bytes + 255) & ~(size_t)255;
-        return here;
-    };
-    c.st = take(sizeof(CalibState));
-    c.off = take((size_t)V * sizeof(int32_t)), c.npt = take((size_t)std::max(V, nframes) * sizeof(int32_t));
-    c.init = take((size_t)V * 6 * sizeof(double)), c.red = take((size_t)V * CALIB_RED * sizeof(double));
-    c.bs = take((size_t)V * CALIB_BS * sizeof(double)), c.pose = take((size_t)V * 12 * sizeof(double));
-    c.vcost = take((size_t)V * 2 * sizeof(double)), c.vchg = take((size_t)V * 2 * sizeof(double));
-    c.obj = take(npts * 3 * sizeof(float)), c.img = take(npts * 2 * sizeof(float));
-    c.nmark = take((size_t)nframes * sizeof(int32_t));
-    c.bids = take((size_t)nboard * sizeof(int32_t)), c.bobj = take((size_t)nboard * 12 * sizeof(float));
-    c.total = at;
-    return c;
+// v's arrays in `base` for V views, npts staged points, nframes gather slots and a board of nboard markers; returns the bytes.
+// One quirk: npt is laid out for max(V, nframes) counts. A batch's gather counts every frame into it; the solve then overwrites
+// off / npt with the (fewer) views that are used, and the per-view arrays, laid out for nframes, hold them with room to spare.
+static size_t calib_layout(CalibViews& v, uint8_t* base, int V, size_t npts, int nframes, int nboard) {
+    Carver c{base};
+    CalibDev& d = v.d;
+    d.st = c.take<CalibState>(1);
+    d.off = v.off_dev = c.take<int32_t>((size_t)V), d.npt = v.npt_dev = c.take<int32_t>((size_t)std::max(V, nframes));
+    d.init = c.take<double>((size_t)V * 6), d.red = c.take<double>((size_t)V * CALIB_RED);
+    d.bs = c.take<double>((size_t)V * CALIB_BS), d.pose = c.take<double>((size_t)V * 12);
+    d.vcost = c.take<double>((size_t)V * 2), d.vchg = c.take<double>((size_t)V * 2);
+    d.obj = v.obj = c.take<float>(npts * 3), d.img = v.img = c.take<float>(npts * 2);
+    v.nmark = c.take<int32_t>((size_t)nframes);
+    v.bids = c.take<int32_t>((size_t)nboard), v.bobj = c.take<float>((size_t)nboard * 12);
+    return c.at;
 }
 
-// Levenberg-Marquardt on views whose points are already on the device (v.d.obj / v.d.img, offsets off[], counts npt[]) from the state
-// `st` (start intrinsics, free mask, flags, model): start values, then one host synchronisation per iteration for the stop flag.
+// Levenberg-Marquardt (lm_drive) on views whose points are already on the device (v.d.obj / v.d.img, offsets off[], counts npt[]),
+// in h's d_calib where v is bound, from the state `st` (start intrinsics, free mask, flags, model).
 // focal_start: the focal lengths come from the views' homographies (pinhole without a guess).
 int calib_solve(arucohip_handle* h, const CalibViews& v, CalibState st, bool focal_start, double intr[9], double* rvecs, double* tvecs,
                 double* per_view_rms, double* rms) {
-    CalibDev d = v.d;
-    const CalibCarve& c = v.c;
+    const CalibDev& d = v.d;
     const int V = d.nviews;
-    uint8_t* base = h->d_calib;
-    d.off = (const int32_t*)(base + c.off), d.npt = (const int32_t*)(base + c.npt);
-    d.init = (double*)(base + c.init), d.red = (double*)(base + c.red), d.bs = (double*)(base + c.bs);
-    d.pose = (double*)(base + c.pose), d.vcost = (double*)(base + c.vcost), d.vchg = (double*)(base + c.vchg);
-    d.st = (CalibState*)(base + c.st);
-    st.max_iter = 30, st.lg = -3;
     hipStream_t s = h->stream;
-    HIPCHK(h, h->hc_calib.reserve(sizeof(CalibState)));
-    CalibState* hs = h->hc_calib;
-    *hs = st;
-    HIPCHK(h, hipMemcpyAsync(d.st, hs, sizeof(st), hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync((void*)d.off, v.off.data(), (size_t)V * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync((void*)d.npt, v.npt.data(), (size_t)V * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    launch_calib_init(s, d, !focal_start);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(hs, d.st, sizeof(st), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    if (hs->err & CALIB_ERR_NONPLANAR) return fail(h, ARUCOHIP_E_UNSUPPORTED, "calibration views must be planar (constant z per view)");
-    if (hs->err) return fail(h, ARUCOHIP_E_INVALID, "degenerate calibration views: no start values");
-    // at most 30 accepted steps; every rejected step raises lambda tenfold, and lambda above 1e16 stops
-    for (int it = 0; it < 256 && !hs->done; it++) {
-        launch_calib_iteration(s, d);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(hs, d.st, sizeof(st), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-    }
-    st = *hs;
+    HIPCHK(h, hipMemcpyAsync(v.off_dev, v.off.data(), (size_t)V * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(v.npt_dev, v.npt.data(), (size_t)V * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    const int rc = lm_drive(
+        h, d.st, &st, [&] { launch_calib_init(s, d, !focal_start); },
+        [&](const CalibState& at) {
+            if (at.lm.err & CALIB_ERR_NONPLANAR) return fail(h, ARUCOHIP_E_UNSUPPORTED, "calibration views must be planar (constant z per view)");
+            return at.lm.err ? fail(h, ARUCOHIP_E_INVALID, "degenerate calibration views: no start values") : 0;
+        },
+        [&] { launch_calib_iteration(s, d); });
+    if (rc) return rc;
     std::vector<double> pose((size_t)V * 6), vcost((size_t)V);
-    HIPCHK(h, hipMemcpyAsync(pose.data(), d.pose + (size_t)st.cur * V * 6, pose.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(vcost.data(), d.vcost + (size_t)st.cur * V, vcost.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(pose.data(), d.pose + (size_t)st.lm.cur * V * 6, pose.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(vcost.data(), d.vcost + (size_t)st.lm.cur * V, vcost.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
     for (int i = 0; i < 9; i++) intr[i] = st.intr[i];
     double e2 = 0, np = 0;
@@ -96,18 +76,15 @@ int calib_views_of_points(arucohip_handle* h, const float* obj, const float* img
         v->off[i] = (int32_t)total, total += (size_t)v->npt[i];
     }
     if (total > (size_t)INT32_MAX) return fail(h, ARUCOHIP_E_CAPACITY, "too many calibration points");
-    v->c = calib_carve(nviews, on_device ? 0 : total, 0, 0);
-    HIPCHK(h, h->d_calib.reserve(v->c.total));
-    v->d = CalibDev{};
+    const size_t staged = on_device ? 0 : total;
+    HIPCHK(h, h->d_calib.reserve(calib_layout(*v, nullptr, nviews, staged, 0, 0)));
+    calib_layout(*v, h->d_calib, nviews, staged, 0, 0);
     v->d.nviews = nviews;
     if (on_device) {
         v->d.obj = obj, v->d.img = img;
     } else {
-        float* dobj = (float*)((uint8_t*)h->d_calib + v->c.obj);
-        float* dimg = (float*)((uint8_t*)h->d_calib + v->c.img);
-        HIPCHK(h, hipMemcpyAsync(dobj, obj, total * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(dimg, img, total * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        v->d.obj = dobj, v->d.img = dimg;
+        HIPCHK(h, hipMemcpyAsync(v->obj, obj, total * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(v->img, img, total * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
     }
     return ARUCOHIP_OK;
 }
@@ -126,28 +103,20 @@ int calib_views_of_batch(arucohip_handle* h, int nframes, const int32_t* ids, co
     const float dx = obj[0] - obj[3], dy = obj[1] - obj[4], dz = obj[2] - obj[5];
     const double side = std::sqrt((double)dx * dx + (double)dy * dy + (double)dz * dz);
     const double mpp = (info_type == ARUCOHIP_BOARD_PIX && marker_size > 0) ? (double)marker_size / side : 1.0;
-    const CalibCarve c = calib_carve(nframes, (size_t)nframes * CALIB_MAX_POINTS, nframes, nboard);
-    HIPCHK(h, o->d_calib.reserve(c.total));
-    uint8_t* base = o->d_calib;
-    float* dobj = (float*)(base + c.obj);
-    float* dimg = (float*)(base + c.img);
-    int32_t* dnpt = (int32_t*)(base + c.npt);
-    int32_t* dnmark = (int32_t*)(base + c.nmark);
-    int32_t* dids = (int32_t*)(base + c.bids);
-    float* dbobj = (float*)(base + c.bobj);
-    HIPCHK(h, hipMemcpyAsync(dids, ids, (size_t)nboard * sizeof(int32_t), hipMemcpyHostToDevice, o->stream));
-    HIPCHK(h, hipMemcpyAsync(dbobj, obj, (size_t)nboard * 12 * sizeof(float), hipMemcpyHostToDevice, o->stream));
+    const size_t npts = (size_t)nframes * CALIB_MAX_POINTS;
+    HIPCHK(h, o->d_calib.reserve(calib_layout(*v, nullptr, nframes, npts, nframes, nboard)));
+    calib_layout(*v, o->d_calib, nframes, npts, nframes, nboard);
+    HIPCHK(h, hipMemcpyAsync(v->bids, ids, (size_t)nboard * sizeof(int32_t), hipMemcpyHostToDevice, o->stream));
+    HIPCHK(h, hipMemcpyAsync(v->bobj, obj, (size_t)nboard * 12 * sizeof(float), hipMemcpyHostToDevice, o->stream));
     // every worker lays out the correspondences of the frames it detected, on its own stream
-    int rc;
-    if ((rc = fork_workers(h, b))) return rc;
-    for (const Span& s : b) {
-        launch_calib_gather(s.w->stream, s.count, s.w->buf, dids, dbobj, nboard, mpp, s.first, dobj, dimg, dnpt, dnmark);
-        HIPCHK(h, hipGetLastError());
-    }
-    if ((rc = join_workers(h, b))) return rc;
+    const int rc = on_workers(h, b, [&](const Span& s) {
+        launch_calib_gather(s.w->stream, s.count, s.w->buf, v->bids, v->bobj, nboard, mpp, s.first, v->obj, v->img, v->npt_dev, v->nmark);
+        return 0;
+    });
+    if (rc) return rc;
     std::vector<int32_t> fnpt((size_t)nframes), fnmark((size_t)nframes);
-    HIPCHK(h, hipMemcpyAsync(fnpt.data(), dnpt, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, o->stream));
-    HIPCHK(h, hipMemcpyAsync(fnmark.data(), dnmark, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, o->stream));
+    HIPCHK(h, hipMemcpyAsync(fnpt.data(), v->npt_dev, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, o->stream));
+    HIPCHK(h, hipMemcpyAsync(fnmark.data(), v->nmark, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, o->stream));
     HIPCHK(h, hipStreamSynchronize(o->stream));
     v->off.clear(), v->npt.clear();
     for (int f = 0; f < nframes; f++) {
@@ -157,9 +126,7 @@ int calib_views_of_batch(arucohip_handle* h, int nframes, const int32_t* ids, co
         if (take) v->off.push_back(f * CALIB_MAX_POINTS), v->npt.push_back(fnpt[f]);
     }
     if (v->off.empty()) return fail(h, ARUCOHIP_E_INVALID, "no frame holds min_markers board markers");
-    // the per-view arrays are carved for nframes >= views; the off / npt arrays are rewritten with the views
-    v->c = c, v->d = CalibDev{};
-    v->d.nviews = (int)v->off.size(), v->d.obj = dobj, v->d.img = dimg;
+    v->d.nviews = (int)v->off.size();   // <= nframes, for which the per-view arrays are laid out (calib_layout)
     return ARUCOHIP_OK;
 }
 
@@ -172,9 +139,8 @@ static int calib_pinhole(arucohip_handle* h, const CalibViews& v, int W, int H, 
     st.flags = flags, st.model = CALIB_MODEL_PINHOLE;
     st.aspect = (K[0] > 0 && K[4] > 0) ? K[0] / K[4] : 1.0;
     if (guess) {
-        const double g[9] = {K[0], K[4], K[2], K[5], dist[0], dist[1], dist[2], dist[3], dist[4]};
-        for (int i = 0; i < 9; i++) st.intr[i] = g[i];
-        if (!(g[0] > 0 && g[1] > 0)) return fail(h, ARUCOHIP_E_INVALID, "USE_INTRINSIC_GUESS needs positive focal lengths");
+        intr9(K, dist, st.intr);
+        if (!(st.intr[0] > 0 && st.intr[1] > 0)) return fail(h, ARUCOHIP_E_INVALID, "USE_INTRINSIC_GUESS needs positive focal lengths");
         if (flags & ARUCOHIP_CALIB_FIX_ASPECT_RATIO) st.intr[0] = st.aspect * st.intr[1];
     } else {
         st.intr[2] = (W - 1) * 0.5, st.intr[3] = (H - 1) * 0.5;

@@ -27,15 +27,12 @@ bool charuco_plan(const arucohip_charuco_t* L, CharucoPlan* p) {
     return p->corners <= ARUCOHIP_CALIB_MAX_VIEW_POINTS && p->markers <= CH_MAX_MARKERS;
 }
 
-// byte offsets into d_charuco
-struct CharucoCarve {
-    size_t rec = 0, nfound, ids, total;
-    CharucoCarve(int nframes, int corners, int nids) {
-        nfound = align256((size_t)nframes * corners * sizeof(arucohip_charuco_corner_t));
-        ids = nfound + align256((size_t)nframes * sizeof(int32_t));
-        total = ids + align256((size_t)nids * sizeof(int32_t));
-    }
-};
+// d_charuco: the corner records [frames][corners] at its start (where the consumers read them), then n_found [frames], then the layout's ids
+size_t charuco_layout(uint8_t* base, int nframes, int corners, int nids, arucohip_charuco_corner_t** rec, int32_t** nfound, int32_t** ids) {
+    Carver c{base};
+    *rec = c.take<arucohip_charuco_corner_t>((size_t)nframes * corners), *nfound = c.take<int32_t>((size_t)nframes), *ids = c.take<int32_t>((size_t)nids);
+    return c.at;
+}
 
 // what one unit of the board's pixels is in the caller's unit
 double charuco_scale(const arucohip_charuco_t& L, float square_size) { return square_size > 0 ? (double)square_size / (double)L.square_px : 1.0; }
@@ -139,12 +136,10 @@ int arucohip_charuco_corners_batch(arucohip_handle* h, const arucohip_charuco_t*
     arucohip_handle* w0 = b.span[0].w;   // the worker of the batch's first chunk: copies run on its stream
     hipStream_t s0 = w0->stream;
     h->charuco.frames = 0;               // nothing resident until this call completes
-    const CharucoCarve cv(nframes, p.corners, nids);
-    HIPCHK(h, h->d_charuco.reserve(cv.total));
-    uint8_t* base = h->d_charuco;
-    arucohip_charuco_corner_t* d_rec = (arucohip_charuco_corner_t*)(base + cv.rec);
-    int32_t* d_nf = (int32_t*)(base + cv.nfound);
-    int32_t* d_ids = (int32_t*)(base + cv.ids);
+    arucohip_charuco_corner_t* d_rec;
+    int32_t *d_nf, *d_ids;
+    HIPCHK(h, h->d_charuco.reserve(charuco_layout(nullptr, nframes, p.corners, nids, &d_rec, &d_nf, &d_ids)));
+    charuco_layout(h->d_charuco, nframes, p.corners, nids, &d_rec, &d_nf, &d_ids);
     HIPCHK(h, hipMemcpyAsync(d_ids, ids, (size_t)nids * sizeof(int32_t), hipMemcpyHostToDevice, s0));
     HIPCHK(h, hipMemsetAsync(d_nf, 0, (size_t)nframes * sizeof(int32_t), s0));
     CharucoArgs a{};
@@ -201,10 +196,9 @@ int arucohip_charuco_calibrate_batch(arucohip_handle* h, float square_size, int 
     const size_t o_img = o_obj + align256((size_t)total * 3 * sizeof(float)), bytes = o_img + align256((size_t)total * 2 * sizeof(float));
     HIPCHK(h, h->d_charuco_work.reserve(bytes));
     uint8_t* wk = h->d_charuco_work;
-    const CharucoCarve cv(nframes, nc, 0);
     hipStream_t s = h->stream;
     HIPCHK(h, hipMemcpyAsync(wk, views.data(), (size_t)V * sizeof(int2), hipMemcpyHostToDevice, s));
-    launch_charuco_gather(s, L, charuco_scale(L, square_size), (const arucohip_charuco_corner_t*)((uint8_t*)h->d_charuco + cv.rec), (const int2*)wk, V,
+    launch_charuco_gather(s, L, charuco_scale(L, square_size), (const arucohip_charuco_corner_t*)(uint8_t*)h->d_charuco, (const int2*)wk, V,
                           (float*)(wk + o_obj), (float*)(wk + o_img), (int32_t*)(wk + o_npt));
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(s));
@@ -230,11 +224,10 @@ int arucohip_charuco_pose_batch(arucohip_handle* h, int nframes, const float* K,
     cam.marker_size = square_size, cam.y_perp = y_perp;
     HIPCHK(h, hipSetDevice(h->device));
     const arucohip_charuco_t L = h->charuco.layout;
-    const CharucoCarve cv(h->charuco.frames, (L.squares_x - 1) * (L.squares_y - 1), 0);
     HIPCHK(h, h->d_charuco_work.reserve((size_t)nframes * sizeof(arucohip_board_t)));
     arucohip_board_t* d_out = (arucohip_board_t*)(uint8_t*)h->d_charuco_work;
     hipStream_t s = h->stream;
-    launch_charuco_pose(s, L, charuco_scale(L, square_size), (const arucohip_charuco_corner_t*)((uint8_t*)h->d_charuco + cv.rec), nframes, min_corners, cam, d_out);
+    launch_charuco_pose(s, L, charuco_scale(L, square_size), (const arucohip_charuco_corner_t*)(uint8_t*)h->d_charuco, nframes, min_corners, cam, d_out);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(out, d_out, (size_t)nframes * sizeof(arucohip_board_t), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));

@@ -10,33 +10,28 @@
 
 extern "C" {
 
-// Byte offsets into h->d_map for F frames, nboard markers and room for nobs staged observations.
-struct MapCarve {
-    size_t st, ids, slot, fm, fn, used, fc, fT, fq, edge_f, edge_q, mapped, mpose, fpose, rec, fu, S, delta, vcost, vchg, scost, obj, obs_frame, obs_id,
-        obs_corners, obs_cnt, total;
+// The writable ends of what a call uploads or gathers into d_map: the listed ids, and the observation arrays (staging of host
+// arrays, or a batch's gather). d.obs_* are set by the caller, who knows where the observations are.
+struct MapStage {
+    int32_t *ids, *obs_frame, *obs_id, *obs_cnt;
+    float* obs_corners;
 };
-static MapCarve map_carve(int F, int nboard, size_t nobs) {
-    MapCarve c;
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t here = at;
-        at += (bytes + 255) & ~(size_t)255;
-        return here;
-    };
-    const size_t N = (size_t)6 * (nboard - 1), f = (size_t)F;
-    c.st = take(sizeof(MapState)), c.ids = take((size_t)nboard * sizeof(int32_t));
-    c.slot = take(f * MAP_MAX_MARKERS), c.fm = take(f * MAP_SLOTS), c.fn = take(f * sizeof(int32_t)), c.used = take(f * sizeof(int32_t));
-    c.fc = take(f * MAP_SLOTS * 8 * sizeof(float)), c.fT = take(f * MAP_SLOTS * 12 * sizeof(double)), c.fq = take(f * MAP_SLOTS * sizeof(double));
-    c.edge_f = take((size_t)MAP_MAX_MARKERS * MAP_MAX_MARKERS * sizeof(int32_t)), c.edge_q = take((size_t)MAP_MAX_MARKERS * MAP_MAX_MARKERS * sizeof(double));
-    c.mapped = take((size_t)nboard * sizeof(int32_t)), c.mpose = take((size_t)nboard * 12 * sizeof(double)), c.fpose = take(f * 12 * sizeof(double));
-    c.rec = take(f * MAP_SLOTS * MAP_REC * sizeof(double)), c.fu = take(f * 6 * sizeof(double));
-    c.S = take(N * N * sizeof(double)), c.delta = take(N * sizeof(double));
-    c.vcost = take(f * 2 * sizeof(double)), c.vchg = take(f * 2 * sizeof(double)), c.scost = take(f * MAP_SLOTS * sizeof(double));
-    c.obj = take((size_t)nboard * 12 * sizeof(float));
-    c.obs_frame = take(nobs * sizeof(int32_t)), c.obs_id = take(nobs * sizeof(int32_t)), c.obs_corners = take(nobs * 8 * sizeof(float));
-    c.obs_cnt = take(f * sizeof(int32_t));
-    c.total = at;
-    return c;
+// d's arrays in `base` for F frames, nboard markers and room for nobs staged observations; returns the bytes.
+static size_t map_layout(MapDev& d, MapStage& w, uint8_t* base, int F, int nboard, size_t nobs) {
+    Carver c{base};
+    const size_t N = (size_t)6 * (nboard - 1), f = (size_t)F, nb = (size_t)nboard;
+    d.st = c.take<MapState>(1), d.ids = w.ids = c.take<int32_t>(nb);
+    d.slot = c.take<int8_t>(f * MAP_MAX_MARKERS), d.fm = c.take<int8_t>(f * MAP_SLOTS), d.fn = c.take<int32_t>(f), d.used = c.take<int32_t>(f);
+    d.fc = c.take<float>(f * MAP_SLOTS * 8), d.fT = c.take<double>(f * MAP_SLOTS * 12), d.fq = c.take<double>(f * MAP_SLOTS);
+    d.edge_f = c.take<int32_t>((size_t)MAP_MAX_MARKERS * MAP_MAX_MARKERS), d.edge_q = c.take<double>((size_t)MAP_MAX_MARKERS * MAP_MAX_MARKERS);
+    d.mapped = c.take<int32_t>(nb), d.mpose = c.take<double>(nb * 12), d.fpose = c.take<double>(f * 12);
+    d.rec = c.take<double>(f * MAP_SLOTS * MAP_REC), d.fu = c.take<double>(f * 6);
+    d.S = c.take<double>(N * N), d.delta = c.take<double>(N);
+    d.vcost = c.take<double>(f * 2), d.vchg = c.take<double>(f * 2), d.scost = c.take<double>(f * MAP_SLOTS);
+    d.obj = c.take<float>(nb * 12);
+    w.obs_frame = c.take<int32_t>(nobs), w.obs_id = c.take<int32_t>(nobs), w.obs_corners = c.take<float>(nobs * 8);
+    w.obs_cnt = c.take<int32_t>(f);
+    return c.at;
 }
 
 struct MapOut {
@@ -67,52 +62,32 @@ static int map_args(arucohip_handle* h, int nframes, const int32_t* ids, int nbo
     return ARUCOHIP_OK;
 }
 
-// Start values and Levenberg-Marquardt on observations that are already on the device (d.obs_*), on o's stream and in o's d_map; one
-// host synchronisation per iteration for the stop flag.
-static int map_solve(arucohip_handle* o, MapDev d, const MapCarve& c, const int32_t* ids, const CamModel& cam, const MapOut& out) {
+// Start values and Levenberg-Marquardt (lm_drive) on observations that are already on the device (d.obs_*), on o's stream and in
+// o's d_map, where d is bound.
+static int map_solve(arucohip_handle* o, MapDev d, int32_t* dids, const int32_t* ids, const CamModel& cam, const MapOut& out) {
     const int F = d.nframes, nb = d.nboard;
-    uint8_t* base = o->d_map;
     hipStream_t s = o->stream;
-    int32_t* dids = (int32_t*)(base + c.ids);
-    d.ids = dids;
     d.half = (float)((double)cam.marker_size / 2.);
-    d.slot = (int8_t*)(base + c.slot), d.fm = (int8_t*)(base + c.fm), d.fn = (int32_t*)(base + c.fn), d.used = (int32_t*)(base + c.used);
-    d.fc = (float*)(base + c.fc), d.fT = (double*)(base + c.fT), d.fq = (double*)(base + c.fq);
-    d.edge_f = (int32_t*)(base + c.edge_f), d.edge_q = (double*)(base + c.edge_q);
-    d.mapped = (int32_t*)(base + c.mapped), d.mpose = (double*)(base + c.mpose), d.fpose = (double*)(base + c.fpose);
-    d.rec = (double*)(base + c.rec), d.fu = (double*)(base + c.fu), d.S = (double*)(base + c.S), d.delta = (double*)(base + c.delta);
-    d.vcost = (double*)(base + c.vcost), d.vchg = (double*)(base + c.vchg), d.scost = (double*)(base + c.scost);
-    d.obj = (float*)(base + c.obj), d.st = (MapState*)(base + c.st);
-    HIPCHK(o, o->hc_map.reserve(sizeof(MapState)));
-    MapState* hs = o->hc_map;
-    std::memset(hs, 0, sizeof(*hs));
-    hs->max_iter = 30, hs->lg = -3;
-    const double in[9] = {cam.K[0], cam.K[4], cam.K[2], cam.K[5], cam.k[0], cam.k[1], cam.k[2], cam.k[3], cam.k[4]};
-    for (int i = 0; i < 9; i++) hs->intr[i] = in[i];
-    HIPCHK(o, hipMemcpyAsync(d.st, hs, sizeof(*hs), hipMemcpyHostToDevice, s));
+    MapState st;
+    std::memset(&st, 0, sizeof(st));
+    intr9(cam.K, cam.k, st.intr);
     HIPCHK(o, hipMemcpyAsync(dids, ids, (size_t)nb * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    launch_map_init(s, d, cam);
-    HIPCHK(o, hipGetLastError());
-    HIPCHK(o, hipMemcpyAsync(hs, d.st, sizeof(*hs), hipMemcpyDeviceToHost, s));
-    HIPCHK(o, hipStreamSynchronize(s));
-    if (hs->err & MAP_ERR_NO_REFERENCE) return fail(o, ARUCOHIP_E_INVALID, "board_map: the reference marker (the first id) is in no used frame");
-    if (hs->err & MAP_ERR_TOO_FEW) return fail(o, ARUCOHIP_E_INVALID, "board_map: no marker is seen together with the reference marker");
-    if (hs->err) return fail(o, ARUCOHIP_E_INVALID, "board_map: degenerate observations, no start values");
-    // at most 30 accepted steps; every rejected step raises lambda tenfold, and lambda above 1e16 stops
-    for (int it = 0; it < 256 && !hs->done; it++) {
-        launch_map_iteration(s, d);
-        HIPCHK(o, hipGetLastError());
-        HIPCHK(o, hipMemcpyAsync(hs, d.st, sizeof(*hs), hipMemcpyDeviceToHost, s));
-        HIPCHK(o, hipStreamSynchronize(s));
-    }
-    const MapState st = *hs;
+    const int rc = lm_drive(
+        o, d.st, &st, [&] { launch_map_init(s, d, cam); },
+        [&](const MapState& at) {
+            if (at.lm.err & MAP_ERR_NO_REFERENCE) return fail(o, ARUCOHIP_E_INVALID, "board_map: the reference marker (the first id) is in no used frame");
+            if (at.lm.err & MAP_ERR_TOO_FEW) return fail(o, ARUCOHIP_E_INVALID, "board_map: no marker is seen together with the reference marker");
+            return at.lm.err ? fail(o, ARUCOHIP_E_INVALID, "board_map: degenerate observations, no start values") : 0;
+        },
+        [&] { launch_map_iteration(s, d); });
+    if (rc) return rc;
     launch_map_finish(s, d);
     HIPCHK(o, hipGetLastError());
     std::vector<double> mpose((size_t)nb * 6), fpose((size_t)F * 6), scost((size_t)F * MAP_SLOTS);
     std::vector<int32_t> mapped((size_t)nb), used((size_t)F), fn((size_t)F);
     std::vector<int8_t> fm((size_t)F * MAP_SLOTS);
-    HIPCHK(o, hipMemcpyAsync(mpose.data(), d.mpose + (size_t)st.cur * nb * 6, mpose.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(o, hipMemcpyAsync(fpose.data(), d.fpose + (size_t)st.cur * F * 6, fpose.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(o, hipMemcpyAsync(mpose.data(), d.mpose + (size_t)st.lm.cur * nb * 6, mpose.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(o, hipMemcpyAsync(fpose.data(), d.fpose + (size_t)st.lm.cur * F * 6, fpose.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(o, hipMemcpyAsync(scost.data(), d.scost, scost.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(o, hipMemcpyAsync(mapped.data(), d.mapped, mapped.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(o, hipMemcpyAsync(used.data(), d.used, used.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -139,8 +114,8 @@ static int map_solve(arucohip_handle* o, MapDev d, const MapCarve& c, const int3
         for (int k = 0; k < 3; k++) out.marker_rvec[3 * m + k] = mpose[6 * m + k], out.marker_tvec[3 * m + k] = mpose[6 * m + 3 + k];
         if (out.marker_rms) out.marker_rms[m] = (mapped[m] && mcnt[m] > 0) ? std::sqrt(me2[m] / mcnt[m]) : 0.;
     }
-    if (out.rms) *out.rms = std::sqrt(st.cost / (4. * st.nobs));
-    if (out.iterations) *out.iterations = st.iters;
+    if (out.rms) *out.rms = std::sqrt(st.lm.cost / (4. * st.nobs));
+    if (out.iterations) *out.iterations = st.lm.iters;
     return ARUCOHIP_OK;
 }
 
@@ -155,24 +130,16 @@ int arucohip_board_map(arucohip_handle* h, const int32_t* obs_frame, const int32
     if (rc) return rc;
     if (nobs < 0 || (nobs > 0 && (!obs_frame || !obs_id || !obs_corners))) return fail(h, ARUCOHIP_E_INVALID, "board_map: NULL observations or a negative count");
     HIPCHK(h, hipSetDevice(h->device));
-    const MapCarve c = map_carve(nframes, nboard, on_device ? 0 : (size_t)nobs);
-    HIPCHK(h, h->d_map.reserve(c.total));
     MapDev d{};
+    MapStage w;
+    const size_t staged = on_device ? 0 : (size_t)nobs;
+    HIPCHK(h, h->d_map.reserve(map_layout(d, w, nullptr, nframes, nboard, staged)));
+    map_layout(d, w, h->d_map, nframes, nboard, staged);
     d.nframes = nframes, d.nboard = nboard, d.min_markers = 2, d.nobs = nobs;
-    if (on_device) {
-        d.obs_frame = obs_frame, d.obs_id = obs_id, d.obs_corners = obs_corners;
-    } else {
-        uint8_t* base = h->d_map;
-        if (nobs > 0) {
-            HIPCHK(h, hipMemcpyAsync(base + c.obs_frame, obs_frame, (size_t)nobs * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(base + c.obs_id, obs_id, (size_t)nobs * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(base + c.obs_corners, obs_corners, (size_t)nobs * 8 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        }
-        d.obs_frame = (const int32_t*)(base + c.obs_frame), d.obs_id = (const int32_t*)(base + c.obs_id);
-        d.obs_corners = (const float*)(base + c.obs_corners);
-    }
-    if (!d.obs_frame) d.obs_frame = (const int32_t*)((uint8_t*)h->d_map + c.obs_frame);   // nobs == 0: nothing is read
-    return map_solve(h, d, c, ids, cam, out);
+    ObsArrays obs;
+    if ((rc = stage_obs(h, ObsArrays{obs_frame, obs_id, obs_corners}, nobs, on_device, w.obs_frame, w.obs_id, w.obs_corners, &obs))) return rc;
+    d.obs_frame = obs.owner, d.obs_id = obs.id, d.obs_corners = obs.corners;
+    return map_solve(h, d, w.ids, ids, cam, out);
 }
 
 int arucohip_board_map_batch(arucohip_handle* h, int nframes, const int32_t* ids, int nboard, const float* K, const float* dist, int ndist,
@@ -189,26 +156,19 @@ int arucohip_board_map_batch(arucohip_handle* h, int nframes, const int32_t* ids
     arucohip_handle* o = b.span[0].w;   // the worker of the batch's first chunk: the solve runs on its stream, in its scratch
     int stride = 1;
     for (const Span& s : b) stride = std::max(stride, s.w->buf.cap_markers);
-    const MapCarve c = map_carve(nframes, nboard, (size_t)nframes * stride);
-    HIPCHK(h, o->d_map.reserve(c.total));
-    uint8_t* base = o->d_map;
-    int32_t* obs_id = (int32_t*)(base + c.obs_id);
-    float* obs_corners = (float*)(base + c.obs_corners);
-    int32_t* obs_cnt = (int32_t*)(base + c.obs_cnt);
-    // every worker lays out the markers of the frames it detected, on its own stream
-    if ((rc = fork_workers(h, b))) return rc;
-    hipError_t launched = hipSuccess;
-    for (const Span& s : b) {
-        launch_map_gather(s.w->stream, s.count, s.w->buf, s.first, stride, obs_id, obs_corners, obs_cnt);
-        if (launched == hipSuccess) launched = hipGetLastError();
-    }
-    // the workers rejoin the first worker's stream whether or not every launch was taken
-    if ((rc = join_workers(h, b))) return rc;
-    HIPCHK(h, launched);
     MapDev d{};
+    MapStage w;
+    HIPCHK(h, o->d_map.reserve(map_layout(d, w, nullptr, nframes, nboard, (size_t)nframes * stride)));
+    map_layout(d, w, o->d_map, nframes, nboard, (size_t)nframes * stride);
+    // every worker lays out the markers of the frames it detected, on its own stream
+    rc = on_workers(h, b, [&](const Span& s) {
+        launch_map_gather(s.w->stream, s.count, s.w->buf, s.first, stride, w.obs_id, w.obs_corners, w.obs_cnt);
+        return 0;
+    });
+    if (rc) return rc;
     d.nframes = nframes, d.nboard = nboard, d.min_markers = min_markers, d.nobs = nframes * stride;
-    d.obs_id = obs_id, d.obs_corners = obs_corners, d.obs_cnt = obs_cnt, d.obs_stride = stride;
-    rc = map_solve(o, d, c, ids, cam, out);
+    d.obs_id = w.obs_id, d.obs_corners = w.obs_corners, d.obs_cnt = w.obs_cnt, d.obs_stride = stride;
+    rc = map_solve(o, d, w.ids, ids, cam, out);
     if (rc && o != h) h->err = o->err;
     return rc;
 }

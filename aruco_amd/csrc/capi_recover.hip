@@ -14,25 +14,15 @@ void arucohip_default_recover(arucohip_recover_t* o) {
     o->max_corner_dist = 10.f, o->max_cell_errors = 3, o->min_markers = 2, o->pose_markers = 0;
 }
 
-// Byte offsets into a worker's d_recover for F frames of cap_markers markers and a board of nboard markers
-struct RecoverCarve {
-    size_t base, nrec, recovered, status, rec, rlist, plist, ids, obj, total;
-};
-static RecoverCarve recover_carve(int F, int cap_markers, int nboard) {
-    RecoverCarve c;
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t here = at;
-        at += (bytes + 255) & ~(size_t)255;
-        return here;
-    };
+// r's arrays and the board (ids, obj) in a worker's d_recover for F frames of cap_markers markers and a board of nboard markers; returns the bytes
+static size_t recover_layout(RecoverBufs& r, int32_t** ids, float** obj, uint8_t* base, int F, int cap_markers, int nboard) {
+    Carver c{base};
     const size_t slots = (size_t)F * cap_markers;
-    c.base = take((size_t)F * sizeof(int32_t)), c.nrec = take((size_t)F * sizeof(int32_t)), c.recovered = take((size_t)F * sizeof(int32_t));
-    c.status = take(sizeof(uint32_t));
-    c.rec = take(slots * sizeof(RecoverRec)), c.rlist = take(slots * sizeof(uint32_t)), c.plist = take(slots * sizeof(uint32_t));
-    c.ids = take((size_t)nboard * sizeof(int32_t)), c.obj = take((size_t)nboard * 12 * sizeof(float));
-    c.total = at;
-    return c;
+    r.base = c.take<int32_t>((size_t)F), r.nrec = c.take<int32_t>((size_t)F), r.recovered = c.take<int32_t>((size_t)F);
+    r.status = c.take<uint32_t>(1);
+    r.rec = c.take<RecoverRec>(slots), r.rlist = c.take<uint32_t>(slots), r.plist = c.take<uint32_t>(slots);
+    *ids = c.take<int32_t>((size_t)nboard), *obj = c.take<float>((size_t)nboard * 12);
+    return c.at;
 }
 
 int arucohip_board_recover_batch(arucohip_handle* h, int nframes, const int32_t* ids, const float* obj, int nboard, int info_type, const float* K,
@@ -91,14 +81,12 @@ int arucohip_board_recover_batch(arucohip_handle* h, int nframes, const int32_t*
         arucohip_handle* w = s.w;
         const Buffers& wb = w->buf;
         const int capM = wb.cap_markers;
-        const RecoverCarve cv = recover_carve(w->cap_frames, capM, nboard);
-        HIPCHK(h, w->d_recover.reserve(cv.total));
-        uint8_t* base = w->d_recover;
         RecoverBufs r;
-        r.base = (int32_t*)(base + cv.base), r.nrec = (int32_t*)(base + cv.nrec), r.recovered = (int32_t*)(base + cv.recovered);
-        r.status = (uint32_t*)(base + cv.status), r.rec = (RecoverRec*)(base + cv.rec), r.rlist = (uint32_t*)(base + cv.rlist);
-        r.plist = (uint32_t*)(base + cv.plist);
-        a.ids = (const int32_t*)(base + cv.ids), a.obj = (const float*)(base + cv.obj);
+        int32_t* dids;
+        float* dobj;
+        HIPCHK(h, w->d_recover.reserve(recover_layout(r, &dids, &dobj, nullptr, w->cap_frames, capM, nboard)));
+        recover_layout(r, &dids, &dobj, w->d_recover, w->cap_frames, capM, nboard);
+        a.ids = dids, a.obj = dobj;
         a.cells_valid = w->cells_valid ? 1 : 0;
         HIPCHK(h, w->d_board.reserve((size_t)w->cap_frames * (sizeof(arucohip_board_t) + sizeof(float)) + 8192 * sizeof(int32_t)));
         arucohip_board_t* d_boards = w->d_board;
@@ -106,8 +94,8 @@ int arucohip_board_recover_batch(arucohip_handle* h, int nframes, const int32_t*
         hipStream_t st = w->stream;
         HIPCHK(h, hipMemsetAsync(r.base, 0xFF, (size_t)w->cap_frames * sizeof(int32_t), st));
         HIPCHK(h, hipMemsetAsync(r.status, 0, sizeof(uint32_t), st));
-        HIPCHK(h, hipMemcpyAsync(base + cv.ids, ids, (size_t)nboard * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipMemcpyAsync(base + cv.obj, obj, (size_t)nboard * 12 * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(dids, ids, (size_t)nboard * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(dobj, obj, (size_t)nboard * 12 * sizeof(float), hipMemcpyHostToDevice, st));
         launch_recover_match(st, h->last.span[c].count, s.count, wb, a, bcam, r);
         launch_refine_recovered(st, s.count, p.corner_method, cam, wb, r.rlist, r.nrec, capM);
         launch_recover_insert(st, s.count, wb, a, bcam, r, d_boards, d_prob);

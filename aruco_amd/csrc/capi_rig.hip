@@ -10,35 +10,39 @@
 
 extern "C" {
 
-// Byte offsets into h->d_rig for T instants of C cameras, nboard markers and room for nobs staged observations.
-struct RigCarve {
-    size_t st, ids, bobj, cams, vn, vok, vact, vT, pobj, pimg, edge_t, edge_q, calibrated, cpose, used, lead, ipose, gram, rec, fu, S, delta, vcost, vchg,
-        boards, views_used, obs_view, obs_id, obs_corners, obs_cnt, total;
+// The writable ends of what a call uploads or gathers into d_rig: the board, the cameras, and the observation arrays (staging of
+// host arrays, or a batch's gather). d.obs_* are set by rig_begin from where the observations are (RigObs).
+struct RigStage {
+    int32_t* ids;
+    float* bobj;
+    RigCam* cams;
+    int32_t *obs_view, *obs_id, *obs_cnt;
+    float* obs_corners;
 };
-static RigCarve rig_carve(int T, int C, int nboard, size_t nobs) {
-    RigCarve c;
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t here = at;
-        at += (bytes + 255) & ~(size_t)255;
-        return here;
-    };
-    const size_t t = (size_t)T, V = t * C, N = (size_t)6 * (C - 1);
-    c.st = take(sizeof(RigState)), c.ids = take((size_t)nboard * sizeof(int32_t)), c.bobj = take((size_t)nboard * 12 * sizeof(float));
-    c.cams = take((size_t)C * sizeof(RigCam));
-    c.vn = take(V * sizeof(int32_t)), c.vok = take(V * sizeof(int32_t)), c.vact = take(V * sizeof(int32_t)), c.vT = take(V * 12 * sizeof(double));
-    c.pobj = take(V * RIG_VIEW_POINTS * 3 * sizeof(float)), c.pimg = take(V * RIG_VIEW_POINTS * 2 * sizeof(float));
-    c.edge_t = take((size_t)RIG_MAX_CAMERAS * RIG_MAX_CAMERAS * sizeof(int32_t)), c.edge_q = take((size_t)RIG_MAX_CAMERAS * RIG_MAX_CAMERAS * sizeof(int32_t));
-    c.calibrated = take((size_t)C * sizeof(int32_t)), c.cpose = take((size_t)C * 12 * sizeof(double));
-    c.used = take(t * sizeof(int32_t)), c.lead = take(t * sizeof(int32_t)), c.ipose = take(t * 12 * sizeof(double));
-    c.gram = take(V * RIG_G * sizeof(double)), c.rec = take(V * RIG_REC * sizeof(double)), c.fu = take(t * 6 * sizeof(double));
-    c.S = take(N * N * sizeof(double)), c.delta = take(N * sizeof(double));
-    c.vcost = take(V * 2 * sizeof(double)), c.vchg = take(t * 2 * sizeof(double));
-    c.boards = take(t * sizeof(arucohip_board_t)), c.views_used = take(t * sizeof(int32_t));
-    c.obs_view = take(nobs * sizeof(int32_t)), c.obs_id = take(nobs * sizeof(int32_t)), c.obs_corners = take(nobs * 8 * sizeof(float));
-    c.obs_cnt = take(V * sizeof(int32_t));
-    c.total = at;
-    return c;
+// d's arrays in `base` for T instants of C cameras, nboard markers and room for nobs staged observations; returns the bytes.
+static size_t rig_layout(RigDev& d, RigStage& w, uint8_t* base, int T, int C, int nboard, size_t nobs) {
+    Carver c{base};
+    const size_t t = (size_t)T, nc = (size_t)C, V = t * nc, N = (size_t)6 * (C - 1), nb = (size_t)nboard;
+    d.st = c.take<RigState>(1), d.ids = w.ids = c.take<int32_t>(nb), d.bobj = w.bobj = c.take<float>(nb * 12);
+    d.cams = w.cams = c.take<RigCam>(nc);
+    d.vn = c.take<int32_t>(V), d.vok = c.take<int32_t>(V), d.vact = c.take<int32_t>(V), d.vT = c.take<double>(V * 12);
+    d.pobj = c.take<float>(V * RIG_VIEW_POINTS * 3), d.pimg = c.take<float>(V * RIG_VIEW_POINTS * 2);
+    d.edge_t = c.take<int32_t>((size_t)RIG_MAX_CAMERAS * RIG_MAX_CAMERAS), d.edge_q = c.take<int32_t>((size_t)RIG_MAX_CAMERAS * RIG_MAX_CAMERAS);
+    d.calibrated = c.take<int32_t>(nc), d.cpose = c.take<double>(nc * 12);
+    d.used = c.take<int32_t>(t), d.lead = c.take<int32_t>(t), d.ipose = c.take<double>(t * 12);
+    d.gram = c.take<double>(V * RIG_G), d.rec = c.take<double>(V * RIG_REC), d.fu = c.take<double>(t * 6);
+    d.S = c.take<double>(N * N), d.delta = c.take<double>(N);
+    d.vcost = c.take<double>(V * 2), d.vchg = c.take<double>(t * 2);
+    d.boards = c.take<arucohip_board_t>(t), d.views_used = c.take<int32_t>(t);
+    w.obs_view = c.take<int32_t>(nobs), w.obs_id = c.take<int32_t>(nobs), w.obs_corners = c.take<float>(nobs * 8);
+    w.obs_cnt = c.take<int32_t>(V);
+    return c.at;
+}
+// sized, reserved on o (the handle that owns the scratch), then bound there
+static int rig_reserve(arucohip_handle* h, arucohip_handle* o, RigDev& d, RigStage& w, int T, int C, int nboard, size_t nobs) {
+    HIPCHK(h, o->d_rig.reserve(rig_layout(d, w, nullptr, T, C, nboard, nobs)));
+    rig_layout(d, w, o->d_rig, T, C, nboard, nobs);
+    return ARUCOHIP_OK;
 }
 
 // the board and the cameras of a call, checked before anything runs
@@ -73,8 +77,7 @@ static int rig_args(arucohip_handle* h, const char* who, int ninstants, const ar
         for (int i = 0; i < 9; i++) r.cam.K[i] = cams[c].K[i];
         for (int i = 0; i < cams[c].ndist; i++) r.cam.k[i] = (double)cams[c].dist[i];
         r.cam.marker_size = b.marker_size;
-        const double in[9] = {r.cam.K[0], r.cam.K[4], r.cam.K[2], r.cam.K[5], r.cam.k[0], r.cam.k[1], r.cam.k[2], r.cam.k[3], r.cam.k[4]};
-        for (int i = 0; i < 9; i++) r.in[i] = in[i];
+        intr9(r.cam.K, r.cam.k, r.in);
     }
     return ARUCOHIP_OK;
 }
@@ -88,34 +91,17 @@ struct RigObs {
     int nobs, stride;
 };
 
-// d over o's d_rig, the board, the cameras and a cleared solver state uploaded, the view kernel launched on o's stream. A rig pose
-// passes the caller's camera transforms (pose_cams), which go up with the rest, so that nothing waits between the view kernel and
-// the pose kernel; a calibration passes null and computes them.
-static int rig_begin(arucohip_handle* o, const RigCarve& c, int ninstants, int ncams, const RigBoard& b, const std::vector<RigCam>& rc, const RigObs& obs,
-                     const arucohip_rig_camera_t* pose_cams, RigDev* out) {
-    uint8_t* base = o->d_rig;
+// d, bound in o's d_rig, gets the call's numbers and observations, and the board and the cameras go up on o's stream; the solve then
+// starts with the view kernel. A rig pose passes the caller's camera transforms (pose_cams), which go up with the rest, so that nothing
+// waits between the view kernel and the pose kernel; a calibration passes null and computes them.
+static int rig_begin(arucohip_handle* o, RigDev& d, const RigStage& w, int ninstants, int ncams, const RigBoard& b, const std::vector<RigCam>& rc,
+                     const RigObs& obs, const arucohip_rig_camera_t* pose_cams) {
     hipStream_t s = o->stream;
-    RigDev d{};
     d.ncams = ncams, d.ninstants = ninstants, d.nboard = b.nboard, d.min_markers = b.min_markers, d.info_type = b.info_type, d.marker_size = b.marker_size;
     d.obs_view = obs.view, d.obs_id = obs.id, d.obs_corners = obs.corners, d.obs_cnt = obs.cnt, d.nobs = obs.nobs, d.obs_stride = obs.stride;
-    d.ids = (const int32_t*)(base + c.ids), d.bobj = (const float*)(base + c.bobj), d.cams = (const RigCam*)(base + c.cams);
-    d.vn = (int32_t*)(base + c.vn), d.vok = (int32_t*)(base + c.vok), d.vact = (int32_t*)(base + c.vact), d.vT = (double*)(base + c.vT);
-    d.pobj = (float*)(base + c.pobj), d.pimg = (float*)(base + c.pimg);
-    d.edge_t = (int32_t*)(base + c.edge_t), d.edge_q = (int32_t*)(base + c.edge_q);
-    d.calibrated = (int32_t*)(base + c.calibrated), d.cpose = (double*)(base + c.cpose);
-    d.used = (int32_t*)(base + c.used), d.lead = (int32_t*)(base + c.lead), d.ipose = (double*)(base + c.ipose);
-    d.gram = (double*)(base + c.gram), d.rec = (double*)(base + c.rec), d.fu = (double*)(base + c.fu);
-    d.S = (double*)(base + c.S), d.delta = (double*)(base + c.delta), d.vcost = (double*)(base + c.vcost), d.vchg = (double*)(base + c.vchg);
-    d.boards = (arucohip_board_t*)(base + c.boards), d.views_used = (int32_t*)(base + c.views_used);
-    d.st = (RigState*)(base + c.st);
-    HIPCHK(o, o->hc_rig.reserve(sizeof(RigState)));
-    RigState* hs = o->hc_rig;
-    std::memset(hs, 0, sizeof(*hs));
-    hs->max_iter = 30, hs->lg = -3;
-    HIPCHK(o, hipMemcpyAsync(d.st, hs, sizeof(*hs), hipMemcpyHostToDevice, s));
-    HIPCHK(o, hipMemcpyAsync(base + c.ids, b.ids, (size_t)b.nboard * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(o, hipMemcpyAsync(base + c.bobj, b.obj, (size_t)b.nboard * 12 * sizeof(float), hipMemcpyHostToDevice, s));
-    HIPCHK(o, hipMemcpyAsync(base + c.cams, rc.data(), rc.size() * sizeof(RigCam), hipMemcpyHostToDevice, s));
+    HIPCHK(o, hipMemcpyAsync(w.ids, b.ids, (size_t)b.nboard * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(o, hipMemcpyAsync(w.bobj, b.obj, (size_t)b.nboard * 12 * sizeof(float), hipMemcpyHostToDevice, s));
+    HIPCHK(o, hipMemcpyAsync(w.cams, rc.data(), rc.size() * sizeof(RigCam), hipMemcpyHostToDevice, s));
     std::vector<double> cpose;
     std::vector<int32_t> calibrated;
     if (pose_cams) {
@@ -128,47 +114,25 @@ static int rig_begin(arucohip_handle* o, const RigCarve& c, int ninstants, int n
         HIPCHK(o, hipMemcpyAsync(d.calibrated, calibrated.data(), calibrated.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     }
     HIPCHK(o, hipStreamSynchronize(s));   // the vectors and the caller's arrays are pageable: the copies above have left them
-    launch_rig_views(s, d);
-    HIPCHK(o, hipGetLastError());
-    *out = d;
     return ARUCOHIP_OK;
 }
 
 // observations given as arrays: staged in h's d_rig unless they are on the device already
-static int rig_stage(arucohip_handle* h, const RigCarve& c, const int32_t* obs_view, const int32_t* obs_id, const float* obs_corners, int nobs,
+static int rig_stage(arucohip_handle* h, const RigStage& w, const int32_t* obs_view, const int32_t* obs_id, const float* obs_corners, int nobs,
                      int on_device, RigObs* obs) {
-    uint8_t* base = h->d_rig;
-    *obs = RigObs{obs_view, obs_id, obs_corners, nullptr, nobs, 0};
-    if (!on_device) {
-        if (nobs > 0) {
-            HIPCHK(h, hipMemcpyAsync(base + c.obs_view, obs_view, (size_t)nobs * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(base + c.obs_id, obs_id, (size_t)nobs * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(base + c.obs_corners, obs_corners, (size_t)nobs * 8 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        }
-        obs->view = (const int32_t*)(base + c.obs_view), obs->id = (const int32_t*)(base + c.obs_id), obs->corners = (const float*)(base + c.obs_corners);
-    }
-    if (!obs->view) obs->view = (const int32_t*)(base + c.obs_view);   // nobs == 0: nothing is read
-    return ARUCOHIP_OK;
+    ObsArrays at;
+    const int rc = stage_obs(h, ObsArrays{obs_view, obs_id, obs_corners}, nobs, on_device, w.obs_view, w.obs_id, w.obs_corners, &at);
+    *obs = RigObs{at.owner, at.id, at.corners, nullptr, nobs, 0};
+    return rc;
 }
 
-// the markers of the first nframes frames of the last batch, laid out per view by the workers that hold them (in o's d_rig)
-static int rig_gather(arucohip_handle* h, const Batch& b, arucohip_handle* o, const RigCarve& c, int nframes, int stride, RigObs* obs) {
-    uint8_t* base = o->d_rig;
-    int32_t* obs_id = (int32_t*)(base + c.obs_id);
-    float* obs_corners = (float*)(base + c.obs_corners);
-    int32_t* obs_cnt = (int32_t*)(base + c.obs_cnt);
-    int rc;
-    if ((rc = fork_workers(h, b))) return rc;
-    hipError_t launched = hipSuccess;
-    for (const Span& s : b) {
-        launch_map_gather(s.w->stream, s.count, s.w->buf, s.first, stride, obs_id, obs_corners, obs_cnt);
-        if (launched == hipSuccess) launched = hipGetLastError();
-    }
-    // the workers rejoin the first worker's stream whether or not every launch was taken
-    if ((rc = join_workers(h, b))) return rc;
-    HIPCHK(h, launched);
-    *obs = RigObs{nullptr, obs_id, obs_corners, obs_cnt, nframes * stride, stride};
-    return ARUCOHIP_OK;
+// the markers of the first nframes frames of the last batch, laid out per view by the workers that hold them (in the owner's d_rig)
+static int rig_gather(arucohip_handle* h, const Batch& b, const RigStage& w, int nframes, int stride, RigObs* obs) {
+    *obs = RigObs{nullptr, w.obs_id, w.obs_corners, w.obs_cnt, nframes * stride, stride};
+    return on_workers(h, b, [&](const Span& s) {
+        launch_map_gather(s.w->stream, s.count, s.w->buf, s.first, stride, w.obs_id, w.obs_corners, w.obs_cnt);
+        return 0;
+    });
 }
 
 struct RigCalibOut {
@@ -177,34 +141,30 @@ struct RigCalibOut {
     int32_t* iterations;
 };
 
-// Start values and Levenberg-Marquardt behind the view kernel, on o's stream; one host synchronisation per iteration for the stop flag.
+// The view kernel, start values and Levenberg-Marquardt (lm_drive) on o's stream; the state goes up ahead of the view kernel, which
+// does not read it, so that no copy stands between the kernels.
 // Nothing of the caller's is written before the solve is over.
 static int rig_calibrate_solve(arucohip_handle* o, const RigDev& d, arucohip_rig_camera_t* cams, const RigCalibOut& out) {
     const int T = d.ninstants, C = d.ncams, V = T * C;
     hipStream_t s = o->stream;
-    RigState* hs = o->hc_rig;
-    launch_rig_calib_init(s, d);
-    HIPCHK(o, hipGetLastError());
-    HIPCHK(o, hipMemcpyAsync(hs, d.st, sizeof(*hs), hipMemcpyDeviceToHost, s));
-    HIPCHK(o, hipStreamSynchronize(s));
-    if (hs->err & RIG_ERR_NO_REFERENCE) return fail(o, ARUCOHIP_E_INVALID, "rig_calibrate: no eligible instant shows camera 0");
-    if (hs->err & RIG_ERR_TOO_FEW) return fail(o, ARUCOHIP_E_INVALID, "rig_calibrate: no camera shares an instant with camera 0");
-    if (hs->err) return fail(o, ARUCOHIP_E_INVALID, "rig_calibrate: degenerate observations, no start values");
-    // at most 30 accepted steps; every rejected step raises lambda tenfold, and lambda above 1e16 stops
-    for (int it = 0; it < 256 && !hs->done; it++) {
-        launch_rig_calib_iteration(s, d);
-        HIPCHK(o, hipGetLastError());
-        HIPCHK(o, hipMemcpyAsync(hs, d.st, sizeof(*hs), hipMemcpyDeviceToHost, s));
-        HIPCHK(o, hipStreamSynchronize(s));
-    }
-    const RigState st = *hs;
+    RigState st;
+    std::memset(&st, 0, sizeof(st));
+    const int rc = lm_drive(
+        o, d.st, &st, [&] { launch_rig_views(s, d), launch_rig_calib_init(s, d); },
+        [&](const RigState& at) {
+            if (at.lm.err & RIG_ERR_NO_REFERENCE) return fail(o, ARUCOHIP_E_INVALID, "rig_calibrate: no eligible instant shows camera 0");
+            if (at.lm.err & RIG_ERR_TOO_FEW) return fail(o, ARUCOHIP_E_INVALID, "rig_calibrate: no camera shares an instant with camera 0");
+            return at.lm.err ? fail(o, ARUCOHIP_E_INVALID, "rig_calibrate: degenerate observations, no start values") : 0;
+        },
+        [&] { launch_rig_calib_iteration(s, d); });
+    if (rc) return rc;
     launch_rig_calib_finish(s, d);
     HIPCHK(o, hipGetLastError());
     std::vector<double> cpose((size_t)C * 6), ipose((size_t)T * 6), vcost((size_t)V);
     std::vector<int32_t> calibrated((size_t)C), used((size_t)T), vact((size_t)V), vn((size_t)V);
-    HIPCHK(o, hipMemcpyAsync(cpose.data(), d.cpose + (size_t)st.cur * C * 6, cpose.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(o, hipMemcpyAsync(ipose.data(), d.ipose + (size_t)st.cur * T * 6, ipose.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(o, hipMemcpyAsync(vcost.data(), d.vcost + (size_t)st.cur * V, vcost.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(o, hipMemcpyAsync(cpose.data(), d.cpose + (size_t)st.lm.cur * C * 6, cpose.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(o, hipMemcpyAsync(ipose.data(), d.ipose + (size_t)st.lm.cur * T * 6, ipose.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(o, hipMemcpyAsync(vcost.data(), d.vcost + (size_t)st.lm.cur * V, vcost.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(o, hipMemcpyAsync(calibrated.data(), d.calibrated, calibrated.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(o, hipMemcpyAsync(used.data(), d.used, used.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(o, hipMemcpyAsync(vact.data(), d.vact, vact.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -227,15 +187,16 @@ static int rig_calibrate_solve(arucohip_handle* o, const RigDev& d, arucohip_rig
         for (int k = 0; k < 3; k++) cams[c].rvec[k] = (cal && c) ? cpose[6 * c + k] : 0., cams[c].tvec[k] = (cal && c) ? cpose[6 * c + 3 + k] : 0.;
         if (out.camera_rms) out.camera_rms[c] = (cal && cnt[c] > 0) ? std::sqrt(ce2[c] / cnt[c]) : 0.;
     }
-    if (out.rms) *out.rms = std::sqrt(st.cost / st.npts);
-    if (out.iterations) *out.iterations = st.iters;
+    if (out.rms) *out.rms = std::sqrt(st.lm.cost / st.npts);
+    if (out.iterations) *out.iterations = st.lm.iters;
     return ARUCOHIP_OK;
 }
 
-// the pose kernel behind the view kernel (the caller's camera transforms went up in rig_begin), the results back
+// the view kernel and the pose kernel behind it (the caller's camera transforms went up in rig_begin), the results back
 static int rig_pose_solve(arucohip_handle* o, const RigDev& d, arucohip_board_t* out, int32_t* views_used) {
     const int T = d.ninstants;
     hipStream_t s = o->stream;
+    launch_rig_views(s, d);
     launch_rig_pose(s, d);
     HIPCHK(o, hipGetLastError());
     std::vector<int32_t> vu((size_t)T);
@@ -270,12 +231,12 @@ int arucohip_rig_calibrate(arucohip_handle* h, const int32_t* obs_view, const in
     if (r) return r;
     if (!rig_obs_ok(obs_view, obs_id, obs_corners, nobs)) return fail(h, ARUCOHIP_E_INVALID, "rig_calibrate: NULL observations or a negative count");
     HIPCHK(h, hipSetDevice(h->device));
-    const RigCarve c = rig_carve(ninstants, ncams, nboard, on_device ? 0 : (size_t)nobs);
-    HIPCHK(h, h->d_rig.reserve(c.total));
+    RigDev d{};
+    RigStage w;
+    if ((r = rig_reserve(h, h, d, w, ninstants, ncams, nboard, on_device ? 0 : (size_t)nobs))) return r;
     RigObs obs;
-    if ((r = rig_stage(h, c, obs_view, obs_id, obs_corners, nobs, on_device, &obs))) return r;
-    RigDev d;
-    if ((r = rig_begin(h, c, ninstants, ncams, b, rc, obs, nullptr, &d))) return r;
+    if ((r = rig_stage(h, w, obs_view, obs_id, obs_corners, nobs, on_device, &obs))) return r;
+    if ((r = rig_begin(h, d, w, ninstants, ncams, b, rc, obs, nullptr))) return r;
     return rig_calibrate_solve(h, d, cams, RigCalibOut{used, board_rvec, board_tvec, camera_rms, rms, iterations});
 }
 
@@ -290,12 +251,12 @@ int arucohip_rig_pose(arucohip_handle* h, const int32_t* obs_view, const int32_t
     if ((r = rig_pose_args(h, "rig_pose", cams, ncams, out))) return r;
     if (!rig_obs_ok(obs_view, obs_id, obs_corners, nobs)) return fail(h, ARUCOHIP_E_INVALID, "rig_pose: NULL observations or a negative count");
     HIPCHK(h, hipSetDevice(h->device));
-    const RigCarve c = rig_carve(ninstants, ncams, nboard, on_device ? 0 : (size_t)nobs);
-    HIPCHK(h, h->d_rig.reserve(c.total));
+    RigDev d{};
+    RigStage w;
+    if ((r = rig_reserve(h, h, d, w, ninstants, ncams, nboard, on_device ? 0 : (size_t)nobs))) return r;
     RigObs obs;
-    if ((r = rig_stage(h, c, obs_view, obs_id, obs_corners, nobs, on_device, &obs))) return r;
-    RigDev d;
-    if ((r = rig_begin(h, c, ninstants, ncams, b, rc, obs, cams, &d))) return r;
+    if ((r = rig_stage(h, w, obs_view, obs_id, obs_corners, nobs, on_device, &obs))) return r;
+    if ((r = rig_begin(h, d, w, ninstants, ncams, b, rc, obs, cams))) return r;
     return rig_pose_solve(h, d, out, views_used);
 }
 
@@ -314,12 +275,12 @@ static int rig_batch(arucohip_handle* h, const char* who, int nframes, arucohip_
     int stride = 1;
     for (const Span& s : batch) stride = std::max(stride, s.w->buf.cap_markers);
     const int ninstants = nframes / ncams;
-    const RigCarve c = rig_carve(ninstants, ncams, b.nboard, (size_t)nframes * stride);
-    HIPCHK(h, o->d_rig.reserve(c.total));
+    RigDev d{};
+    RigStage w;
+    if ((r = rig_reserve(h, o, d, w, ninstants, ncams, b.nboard, (size_t)nframes * stride))) return r;
     RigObs obs;
-    if ((r = rig_gather(h, batch, o, c, nframes, stride, &obs))) return r;
-    RigDev d;
-    r = rig_begin(o, c, ninstants, ncams, b, rc, obs, calib ? nullptr : cams, &d);
+    if ((r = rig_gather(h, batch, w, nframes, stride, &obs))) return r;
+    r = rig_begin(o, d, w, ninstants, ncams, b, rc, obs, calib ? nullptr : cams);
     if (!r) r = calib ? rig_calibrate_solve(o, d, cams, *calib) : rig_pose_solve(o, d, out, views_used);
     if (r && o != h) h->err = o->err;
     return r;

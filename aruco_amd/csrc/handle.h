@@ -147,16 +147,14 @@ struct arucohip_handle {
     uint32_t* zero_block = nullptr;   // counters, gen_cnt, trig_cnt, raw_cnt, ring_cnt: zeroed together at the start of a batch
     size_t zero_words = 0;
     Mem<double> d_gl;                 // batched GL modelview matrices
-    Mem<uint8_t> d_calib;             // camera calibration: solver state, per-view systems and poses, correspondences (calib_carve)
-    Mem<CalibState> hc_calib{true};   // pinned copy of the solver state, read once per iteration
-    Mem<uint8_t> d_map;               // marker mapping: observations, slot tables, start values, per-frame systems, the reduced system (map_carve)
-    Mem<MapState> hc_map{true};       // pinned copy of its solver state, read once per iteration
-    Mem<uint8_t> d_rig;               // camera rigs: observations, view slots, start values, per-view systems, the reduced system, poses (rig_carve)
-    Mem<RigState> hc_rig{true};       // pinned copy of its solver state, read once per iteration
+    Mem<uint8_t> d_calib;             // camera calibration: solver state, per-view systems and poses, correspondences (calib_layout)
+    Mem<uint8_t> d_map;               // marker mapping: observations, slot tables, start values, per-frame systems, the reduced system (map_layout)
+    Mem<uint8_t> d_rig;               // camera rigs: observations, view slots, start values, per-view systems, the reduced system, poses (rig_layout)
+    Mem<uint8_t> hc_solver{true};     // pinned copy of the state of whichever solver runs (lm_drive), read once per iteration: the calls are synchronous, so one serves all
     Mem<uint8_t> d_planar;            // arucohip_planar_poses: results and staged markers of one call
     Mem<uint8_t> d_overlay;           // arucohip_draw_*_batch: primitive lists of one chunk of frames, staged host markers / boards
     Mem<uint8_t> d_overlay_frames;    // arucohip_draw_*_batch: staged host frames
-    Mem<uint8_t> d_recover;           // arucohip_board_recover_batch: the board, adoption records and work lists of one call (recover_carve)
+    Mem<uint8_t> d_recover;           // arucohip_board_recover_batch: the board, adoption records and work lists of one call (recover_layout)
     // arucohip_charuco_corners_batch (capi_charuco.hip), on the handle the caller holds: the corner records of the last call and their counts stay in
     // d_charuco for the calibration and the pose; the host keeps the layout and the counts
     Mem<uint8_t> d_charuco;           // records [frames][corners], then n_found [frames], then the layout's ids
@@ -199,7 +197,7 @@ struct arucohip_handle {
     //   capture and replay; batches that decode from cell medians neither touch nor move buf.patches, and buf.cells is create-time memory;
     // - neither: the other Buffers arrays, zero_block and h_markers are create-time memory (`held`); d_erode, d_canny and the user decoder's
     //   staging and d_pyr belong to configurations that are not graphed; wt_out is set only inside chunk_enqueue, which does not run this path.
-    //   Memory no captured launch reads (d_bgr, undistortion, fisheye maps and scratch, calibration, marker mapping, camera rigs, board and GL batches, planar poses, marker recovery, overlays, EM, HRM, fiducial generation, ChArUco corners and ChromaticMask scratch) may
+    //   Memory no captured launch reads (d_bgr, undistortion, fisheye maps and scratch, calibration, marker mapping, camera rigs and the pinned solver state, board and GL batches, planar poses, marker recovery, overlays, EM, HRM, fiducial generation, ChArUco corners and ChromaticMask scratch) may
     //   be replaced at any time.
     struct FrameGraph {
         hipGraphExec_t exec = nullptr;
@@ -249,16 +247,107 @@ inline void border_rect(float border_dist, int W, int H, int r[4]) {
     r[0] = std::min(x1, x2), r[1] = std::min(y1, y2), r[2] = std::max(x1, x2), r[3] = std::max(y1, y2);
 }
 
-// Camera calibration (capi_calib.hip), shared by the pinhole and the fisheye entry points.
-// Byte offsets into a handle's d_calib for V views, npts points, nframes gather slots and a board of nboard markers.
-struct CalibCarve {
-    size_t st, off, npt, init, red, bs, pose, vcost, vchg, obj, img, nmark, bids, bobj, total;
+// A call's scratch, laid out once: take() hands out consecutive 256-byte aligned arrays of `base`. A layout function names every
+// buffer in one take() and returns `at`, the bytes it needs; it runs twice, with a null base to size the memory (every take() is then
+// null) and, after reserve(), with the memory of the handle that owns the scratch to bind the pointers.
+struct Carver {
+    uint8_t* base;
+    size_t at = 0;
+    template <class T>
+    T* take(size_t count) {
+        const size_t here = at;
+        at += (count * sizeof(T) + 255) & ~(size_t)255;
+        return base ? (T*)(base + here) : nullptr;
+    }
 };
-CalibCarve calib_carve(int V, size_t npts, int nframes, int nboard);
-// the views of one run: points on the device (d.obj / d.img, d.nviews), each view's offset and count, the scratch layout
+
+// fork: the other workers' streams wait for what the first worker's stream (the batch's own) has queued so far; errors are reported on h
+int fork_workers(arucohip_handle* h, const Batch& b);
+// join: the first worker's stream waits for the others
+int join_workers(arucohip_handle* h, const Batch& b);
+
+// per_span(span) for every span of the batch between fork and join, each on its worker's stream. The workers rejoin the first worker's
+// stream whether or not every span was taken; then the first failure is returned: a span's own, a refused launch, the join's.
+template <class F>
+int on_workers(arucohip_handle* h, const Batch& b, F per_span) {
+    int rc = fork_workers(h, b);
+    if (rc) return rc;
+    hipError_t launched = hipSuccess;
+    for (const Span& s : b) {
+        const int r = per_span(s);
+        if (!rc) rc = r;
+        if (launched == hipSuccess) launched = hipGetLastError();
+    }
+    const int joined = join_workers(h, b);
+    if (rc) return rc;
+    HIPCHK(h, launched);
+    return joined;
+}
+
+// The host side of a Levenberg-Marquardt run on o's stream (lm_device.h): *st goes up to dev through the pinned hc_solver, init()
+// launches the start values, and started(state) turns the solver's err bits into its own message and code. Then iter() launches
+// one attempt at a time, with one copy of the state and one synchronisation each for the stop flag: at most 30 accepted steps; every
+// rejected step raises lambda tenfold, and lambda above 1e16 stops. *st returns the final state.
+template <class State, class Init, class Started, class Iter>
+int lm_drive(arucohip_handle* o, State* dev, State* st, Init init, Started started, Iter iter) {
+    hipStream_t s = o->stream;
+    HIPCHK(o, o->hc_solver.reserve(sizeof(State)));
+    State* hs = (State*)(uint8_t*)o->hc_solver;
+    *hs = *st;
+    hs->lm.max_iter = 30, hs->lm.lg = -3;
+    HIPCHK(o, hipMemcpyAsync(dev, hs, sizeof(State), hipMemcpyHostToDevice, s));
+    init();
+    HIPCHK(o, hipGetLastError());
+    HIPCHK(o, hipMemcpyAsync(hs, dev, sizeof(State), hipMemcpyDeviceToHost, s));
+    HIPCHK(o, hipStreamSynchronize(s));
+    if (const int rc = started(*hs)) return rc;
+    for (int it = 0; it < 256 && !hs->lm.done; it++) {
+        iter();
+        HIPCHK(o, hipGetLastError());
+        HIPCHK(o, hipMemcpyAsync(hs, dev, sizeof(State), hipMemcpyDeviceToHost, s));
+        HIPCHK(o, hipStreamSynchronize(s));
+    }
+    *st = *hs;
+    return ARUCOHIP_OK;
+}
+
+// fx fy cx cy k1 k2 p1 p2 k3, as the solvers take a camera, from a 3 x 3 K and five distortion coefficients
+template <class TK, class Tk>
+inline void intr9(const TK* K, const Tk* k, double in[9]) {
+    const double v[9] = {(double)K[0], (double)K[4], (double)K[2], (double)K[5], (double)k[0], (double)k[1], (double)k[2], (double)k[3], (double)k[4]};
+    for (int i = 0; i < 9; i++) in[i] = v[i];
+}
+
+// Observations given as arrays (owner = the frame or view of each, id, 8 corner coordinates): where they are when they are on the device
+// already, else copied into the staging arrays on h's stream.
+struct ObsArrays {
+    const int32_t *owner, *id;
+    const float* corners;
+};
+inline int stage_obs(arucohip_handle* h, ObsArrays in, int nobs, int on_device, int32_t* d_owner, int32_t* d_id, float* d_corners, ObsArrays* out) {
+    *out = in;
+    if (!on_device) {
+        if (nobs > 0) {
+            HIPCHK(h, hipMemcpyAsync(d_owner, in.owner, (size_t)nobs * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(d_id, in.id, (size_t)nobs * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(d_corners, in.corners, (size_t)nobs * 8 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        }
+        *out = ObsArrays{d_owner, d_id, d_corners};
+    }
+    if (!out->owner) out->owner = d_owner;   // nobs == 0: nothing is read, but a null owner array means the strided layout of a batch
+    return ARUCOHIP_OK;
+}
+
+// Camera calibration (capi_calib.hip), shared by the pinhole and the fisheye entry points.
+// The views of one run, bound in the d_calib of the handle the run is on: the solver's arrays (d; d.obj / d.img may be the caller's
+// own device arrays), the staging of points and of a batch's gather, each view's offset and count.
 struct CalibViews {
     CalibDev d{};
-    CalibCarve c{};
+    float *obj = nullptr, *img = nullptr;             // [npts][3], [npts][2]
+    int32_t *off_dev = nullptr, *npt_dev = nullptr;   // d.off and d.npt, writable: the solve uploads off / npt, a gather counts into npt_dev
+    int32_t* nmark = nullptr;                         // [nframes] board markers of a frame
+    int32_t* bids = nullptr;                          // [nboard]
+    float* bobj = nullptr;                            // [nboard][12]
     std::vector<int32_t> off, npt;
 };
 int calib_views_of_points(arucohip_handle* h, const float* obj, const float* img, const int32_t* npoints, int nviews, int on_device, CalibViews* v);
@@ -266,8 +355,3 @@ int calib_views_of_batch(arucohip_handle* h, int nframes, const int32_t* ids, co
                          int min_markers, int32_t* used, arucohip_handle** owner, CalibViews* v);
 int calib_solve(arucohip_handle* h, const CalibViews& v, CalibState st, bool focal_start, double intr[9], double* rvecs, double* tvecs,
                 double* per_view_rms, double* rms);
-
-// fork: the other workers' streams wait for what the first worker's stream (the batch's own) has queued so far; errors are reported on h
-int fork_workers(arucohip_handle* h, const Batch& b);
-// join: the first worker's stream waits for the others
-int join_workers(arucohip_handle* h, const Batch& b);

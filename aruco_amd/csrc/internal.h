@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "../../include/arucohip.h"
+#include "lm_device.h"
 
 namespace ah {
 
@@ -330,11 +331,11 @@ enum { CALIB_ERR_DEGENERATE = 1, CALIB_ERR_NONPLANAR = 2 };
 enum { CALIB_MODEL_PINHOLE = 0, CALIB_MODEL_FISHEYE = 1 };   // fisheye: intr = fx fy cx cy k1 k2 k3 k4 and a ninth entry that stays 0
 
 struct CalibState {
+    LmCtl lm;          // cost at intr / pose[cur]; sdn, spn and solve_failed stay 0: the intrinsic step is in cand / delta
     double intr[9];    // fx fy cx cy k1 k2 p1 p2 k3
     double cand[9], delta[9];
     double aspect;     // fx / fy under ARUCOHIP_CALIB_FIX_ASPECT_RATIO
-    double cost;       // sum of squared residuals at intr / pose[cur]
-    int32_t flags, free_mask, lg, cur, done, iters, max_iter, attempts, err, model;   // model: CALIB_MODEL_*
+    int32_t flags, free_mask, model, pad_;   // model: CALIB_MODEL_*
 };
 
 struct CalibDev {
@@ -364,10 +365,9 @@ constexpr int MAP_REC = 116;            // doubles per frame and slot: V_m (36),
 enum { MAP_ERR_NO_REFERENCE = 1, MAP_ERR_TOO_FEW = 2, MAP_ERR_DEGENERATE = 4 };
 
 struct MapState {
+    LmCtl lm;          // cost at mpose[cur] / fpose[cur]; the shared block is the markers
     double intr[9];    // fx fy cx cy k1 k2 p1 p2 k3 (fixed)
-    double cost;       // sum of squared residuals at mpose[cur] / fpose[cur]
-    double mdn, mpn;   // |marker step|^2 and |marker parameters|^2 of the last solve
-    int32_t lg, cur, done, iters, max_iter, attempts, err, solve_failed, nmapped, nused, nobs, pad_;
+    int32_t nmapped, nused, nobs, pad_;
 };
 
 struct MapDev {
@@ -425,9 +425,8 @@ struct RigCam {
 };
 
 struct RigState {
-    double cost;       // sum of squared residuals at cpose[cur] / ipose[cur]
-    double cdn, cpn;   // |camera step|^2 and |camera parameters|^2 of the last solve
-    int32_t lg, cur, done, iters, max_iter, attempts, err, solve_failed, ncal, nused, npts, pad_;
+    LmCtl lm;          // cost at cpose[cur] / ipose[cur]; the shared block is the cameras
+    int32_t ncal, nused, npts, pad_;
 };
 
 struct RigDev {

@@ -10,7 +10,7 @@
 //   LM:     calib_normal_kernel     (per view: Gram matrix of [J_intr | J_pose | r], elimination of the view's pose -> S_i, reduced rhs)
 //           calib_solve_kernel      (sum of S_i in view order + damping, NI x NI solve on the free intrinsics)
 //           calib_eval_kernel       (per view: pose back-substitution, candidate cost)
-//           calib_update_kernel     (one thread: accept / reject, lambda, stopping rule)
+//           calib_update_kernel     (one thread: accept / reject, lambda, stopping rule: lm_decide of lm_device.h)
 #include <float.h>
 
 #include "fisheye_device.h"
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(64) void calib_homography_kernel(CalibDev d) {
     }
     double* out = d.init + (size_t)v * 6;
     if (!ok) {
-        atomicOr(&d.st->err, CALIB_ERR_DEGENERATE);
+        atomicOr(&d.st->lm.err, CALIB_ERR_DEGENERATE);
         for (int k = 0; k < 6; k++) out[k] = 0;
         return;
     }
@@ -155,7 +155,7 @@ __global__ void calib_focal_kernel(CalibDev d) {
         fx = st->aspect * tf, fy = tf;
     }
     if (!(det != 0 && isfinite(fx) && isfinite(fy) && fx > 0 && fy > 0)) {
-        atomicOr(&st->err, CALIB_ERR_DEGENERATE);
+        atomicOr(&st->lm.err, CALIB_ERR_DEGENERATE);
         return;
     }
     st->intr[0] = fx, st->intr[1] = fy;
@@ -190,7 +190,7 @@ __global__ __launch_bounds__(64) void calib_pose_kernel(CalibDev d) {
     }
     __syncthreads();
     if (s_bad) {
-        if (lane == 0) atomicOr(&d.st->err, CALIB_ERR_NONPLANAR);
+        if (lane == 0) atomicOr(&d.st->lm.err, CALIB_ERR_NONPLANAR);
         return;
     }
     CamModel cam;
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(64) void calib_pose_kernel(CalibDev d) {
     double r[3] = {0, 0, 0}, t[3] = {0, 0, 0};
     const bool ok = solve_pnp_planar_wave<64>(s_obj, s_img, n, cam, r, t, lane);
     if (lane != 0) return;
-    if (!ok) atomicOr(&d.st->err, CALIB_ERR_DEGENERATE);
+    if (!ok) atomicOr(&d.st->lm.err, CALIB_ERR_DEGENERATE);
     double R[9];
     rodrigues_vec2mat(r, R, nullptr);
     double* p = d.pose + (size_t)v * 6;   // buffer 0
@@ -230,8 +230,8 @@ __global__ __launch_bounds__(64) void calib_normal_kernel(CalibDev d) {
     double in[9];
     for (int k = 0; k < 9; k++) in[k] = st->intr[k];
     const bool fixar = st->flags & ARUCOHIP_CALIB_FIX_ASPECT_RATIO;
-    const double aspect = st->aspect, lambda = lm_lambda(st->lg);
-    const double* p = view_pose(d, st->cur, v);
+    const double aspect = st->aspect, lambda = lm_lambda(st->lm.lg);
+    const double* p = view_pose(d, st->lm.cur, v);
     double R[9], dRdr[27];
     rodrigues_vec2mat(p, R, dRdr);
     int ea[3], eb[3];   // (row, column) of the Gram entries this lane sums
@@ -313,7 +313,7 @@ __global__ __launch_bounds__(128) void calib_solve_kernel(CalibDev d) {
     __syncthreads();
     if (e != 0) return;
     CalibState* st = d.st;
-    const double lambda = lm_lambda(st->lg);
+    const double lambda = lm_lambda(st->lm.lg);
     int fr[9], nf = 0;
     for (int i = 0; i < 9; i++)
         if (st->free_mask & (1 << i)) fr[nf++] = i;
@@ -338,7 +338,7 @@ __global__ __launch_bounds__(64) void calib_eval_kernel(CalibDev d, int step) {
     const float* obj = d.obj + (size_t)3 * d.off[v];
     const float* img = d.img + (size_t)2 * d.off[v];
     const CalibState* st = d.st;
-    const int cur = st->cur, dst = step ? 1 - cur : cur;
+    const int cur = st->lm.cur, dst = step ? 1 - cur : cur;
     const double* p0 = view_pose(d, cur, v);
     double in[9], p[6], dn = 0, pn = 0;
     for (int k = 0; k < 9; k++) in[k] = step ? st->cand[k] : st->intr[k];
@@ -371,35 +371,29 @@ __global__ __launch_bounds__(64) void calib_eval_kernel(CalibDev d, int step) {
     }
 }
 
-// CvLevMarq's rule: a candidate whose error is not larger is taken and lambda falls tenfold, else lambda rises tenfold (stop above
-// 1e16). Stop after max_iter accepted steps or when |step| / |params| < DBL_EPSILON.
+// One thread: the cost over the views in view order; step 0 records the start, a step decides by lm_decide, and an accepted
+// candidate's intrinsics become the current ones. The step norms add the views, then the intrinsics.
 __global__ void calib_update_kernel(CalibDev d, int step) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     CalibState* st = d.st;
-    const int other = step ? 1 - st->cur : st->cur;
+    const int other = step ? 1 - st->lm.cur : st->lm.cur;
     double c = 0;
     for (int v = 0; v < d.nviews; v++) c += d.vcost[(size_t)other * d.nviews + v];
     if (!step) {
-        st->cost = c;
-        if (!isfinite(c)) st->err |= CALIB_ERR_DEGENERATE;
+        st->lm.cost = c;
+        if (!isfinite(c)) st->lm.err |= CALIB_ERR_DEGENERATE;
         return;
     }
-    st->attempts++;
-    if (isfinite(c) && c <= st->cost) {
-        double dn = 0, pn = 0;
+    double dn = 0, pn = 0;
+    if (lm_takes(st->lm, c)) {
         for (int v = 0; v < d.nviews; v++) dn += d.vchg[2 * v], pn += d.vchg[2 * v + 1];
         for (int i = 0; i < 9; i++) {
             const double dd = st->cand[i] - st->intr[i];
             dn += dd * dd, pn += st->intr[i] * st->intr[i];
-            st->intr[i] = st->cand[i];
         }
-        st->cur = other, st->cost = c;
-        st->lg = max(st->lg - 1, -16);
-        st->iters++;
-        if (st->iters >= st->max_iter || sqrt(dn) < DBL_EPSILON * sqrt(pn)) st->done = 1;
-    } else if (++st->lg > 16) {
-        st->done = 1;
     }
+    if (lm_decide(st->lm, c, dn, pn))
+        for (int i = 0; i < 9; i++) st->intr[i] = st->cand[i];
 }
 
 void launch_calib_init(hipStream_t s, const CalibDev& d, bool guess) {

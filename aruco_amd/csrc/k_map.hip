@@ -1,6 +1,6 @@
 // Marker mapping: the rigid placement of every listed marker in the frame of the first one, and the board pose of every frame,
-// from frames that show several of the markers. Bundle adjustment with fixed intrinsics, FP64 throughout, the third user of the
-// Schur-complement Levenberg-Marquardt of k_calib.hip: there the shared unknowns are 9 intrinsics, here 6 numbers per marker.
+// from frames that show several of the markers. Bundle adjustment with fixed intrinsics, FP64 throughout, with the
+// Schur-complement Levenberg-Marquardt of k_calib.hip (lm_device.h): there the shared unknowns are 9 intrinsics, here 6 numbers per marker.
 //
 // A corner k of marker m in frame f projects R_f (R_m c_k + t_m) + t_f through project_point_d. Marker 0 is the gauge (identity, no
 // variable). One wave per frame does everything that touches the frame's corners (4 lanes per marker slot, 16 slots); whatever
@@ -72,30 +72,7 @@ __global__ __launch_bounds__(64) void map_build_kernel(MapDev d, CamModel cam) {
     const int f = blockIdx.x, lane = threadIdx.x;
     int lo = 0, hi = d.nobs;
     if (!d.obs_frame) lo = f * d.obs_stride, hi = lo + max(min(d.obs_cnt[f], d.obs_stride), 0);
-    int n = 0;
-    unsigned long long seen = 0;
-    for (int base = lo; base < hi; base += 64) {
-        const int i = base + lane;
-        int bi = -1;
-        if (i < hi && (!d.obs_frame || d.obs_frame[i] == f)) {
-            const int id = d.obs_id[i];
-            for (int j = 0; j < d.nboard; j++)
-                if (d.ids[j] == id) {
-                    bi = j;
-                    break;
-                }
-        }
-        unsigned long long mask = __ballot(bi >= 0);
-        while (mask) {
-            const int j = __ffsll((long long)mask) - 1;
-            mask &= mask - 1;
-            const int b = __shfl(bi, j, 64);
-            if ((seen >> b) & 1) continue;
-            seen |= 1ull << b;
-            if (lane == 0) s_m[n] = b, s_o[n] = base + j;
-            n++;   // n <= nboard <= 64: every listed marker enters once
-        }
-    }
+    const int n = listed_scan(d.obs_frame, f, d.obs_id, lo, hi, d.ids, d.nboard, lane, s_m, s_o);   // n <= nboard <= 64
     d.slot[(size_t)f * MAP_MAX_MARKERS + lane] = -1;
     __syncthreads();
     if (lane < n) {
@@ -233,9 +210,9 @@ __global__ __launch_bounds__(64) void map_tree_kernel(MapDev d) {
         for (int k = 0; k < nb; k++) nm += s_mapped[k];
         d.st->nmapped = seen ? nm : 0;
         if (!seen)
-            d.st->err |= MAP_ERR_NO_REFERENCE;
+            d.st->lm.err |= MAP_ERR_NO_REFERENCE;
         else if (nm < 2)
-            d.st->err |= MAP_ERR_TOO_FEW;
+            d.st->lm.err |= MAP_ERR_TOO_FEW;
     }
 }
 
@@ -273,7 +250,7 @@ __global__ __launch_bounds__(64) void map_frame_kernel(MapDev d) {
 // slot spread over the lanes, each summed over the rows in order). With U = sum_s J_p^T J_p and g_p = sum_s J_p^T r in slot order,
 // U~ = U with its diagonal times (1 + lambda):
 //   u = U~^-1 g_p, and per slot V = J_m^T J_m, W = J_m^T J_p, Y = W U~^-1, rec = {V, W, Y, g_m - W u}
-// (one 6 x 6 solve per row of W and one for g_p, a lane each; a singular U~ sets st->solve_failed). Marker 0's columns are zero.
+// (one 6 x 6 solve per row of W and one for g_p, a lane each: solve_damped6). Marker 0's columns are zero.
 __global__ __launch_bounds__(64) void map_normal_kernel(MapDev d) {
     __shared__ double s_j[8 * MAP_SLOTS][MJ];
     __shared__ double s_g[MAP_SLOTS][MG];
@@ -281,8 +258,8 @@ __global__ __launch_bounds__(64) void map_normal_kernel(MapDev d) {
     const int f = blockIdx.x, lane = threadIdx.x;
     if (!d.used[f]) return;
     const MapState* st = d.st;
-    const int cur = st->cur, ns = d.fn[f], s = lane >> 2, k = lane & 3;
-    const double lambda = lm_lambda(st->lg);
+    const int cur = st->lm.cur, ns = d.fn[f], s = lane >> 2, k = lane & 3;
+    const double lambda = lm_lambda(st->lm.lg);
     double in[9];
     for (int i = 0; i < 9; i++) in[i] = st->intr[i];
     const double* p = d.fpose + ((size_t)cur * d.nframes + f) * 6;
@@ -343,16 +320,10 @@ __global__ __launch_bounds__(64) void map_normal_kernel(MapDev d) {
     }
     for (int c = lane; c < ns * 6 + 1; c += 64) {
         const int sl = c / 6, j = c % 6;
-        double Uc[36], bc[6];
-#pragma unroll
-        for (int a = 0; a < 36; a++) Uc[a] = U[a];
+        double bc[6];
 #pragma unroll
         for (int a = 0; a < 6; a++) bc[a] = sl < ns ? s_g[sl][mg_index(j, 6 + a)] : gp[a];
-        if (!solve_static<6>(Uc, bc)) {   // the frame's pose cannot be eliminated: the step is rejected (map_update_kernel)
-            atomicOr(&d.st->solve_failed, 1);
-#pragma unroll
-            for (int a = 0; a < 6; a++) bc[a] = 0;
-        }
+        solve_damped6(U, bc, &d.st->lm.solve_failed);   // a failure: the frame's pose cannot be eliminated
         if (sl < ns) {
             double* Yrow = d.rec + ((size_t)f * MAP_SLOTS + sl) * MAP_REC + 72 + j * 6;
 #pragma unroll
@@ -406,7 +377,7 @@ __global__ __launch_bounds__(256) void map_assemble_kernel(MapDev d) {
         d.S[(size_t)i * N + j] = i == j ? 1. : 0.;
         return;
     }
-    const double lambda = lm_lambda(d.st->lg);
+    const double lambda = lm_lambda(d.st->lm.lg);
     double sum = 0, diag = 0;
     for (int f = 0; f < d.nframes; f++) {
         if (!d.used[f]) continue;
@@ -422,32 +393,11 @@ __global__ __launch_bounds__(256) void map_assemble_kernel(MapDev d) {
     d.S[(size_t)i * N + j] = i == j ? sum + lambda * diag : sum;
 }
 
-// One workgroup. Cholesky S = L L^T in place, L y = g, L^T x = y (chol_device.h).
-// A pivot that is not positive or a step that is not finite gives a zero step and st->solve_failed: a rejected step, as does a frame
-// whose damped U~ map_normal_kernel could not solve. Then the
-// candidate marker poses mpose[other] = mpose[cur] - step and the norms of step and parameters.
+// One workgroup: the marker step from the reduced system and the candidate marker poses mpose[other] (reduced_step_block).
 __global__ __launch_bounds__(MAP_SOLVE_THREADS) void map_solve_kernel(MapDev d) {
     __shared__ double s_col[MAP_MAX_N], s_b[MAP_MAX_N], s_piv;
     __shared__ int s_fail;
-    const int N = 6 * (d.nboard - 1), tid = threadIdx.x, T = MAP_SOLVE_THREADS;
-    for (int i = tid; i < N; i += T) s_b[i] = d.delta[i];
-    const int fail = chol_solve_block<MAP_SOLVE_THREADS>(d.S, N, s_col, s_b, &s_piv, &s_fail, tid);
-    MapState* st = d.st;
-    const int cur = st->cur, nb = d.nboard;
-    for (int i = tid; i < N; i += T) {
-        const double dl = fail ? 0. : s_b[i];
-        s_b[i] = dl, d.delta[i] = dl;
-        d.mpose[((size_t)(1 - cur) * nb + 1) * 6 + i] = d.mpose[((size_t)cur * nb + 1) * 6 + i] - dl;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double dn = 0, pn = 0;
-        for (int i = 0; i < N; i++) {
-            const double v = d.mpose[((size_t)cur * nb + 1) * 6 + i];
-            dn += s_b[i] * s_b[i], pn += v * v;
-        }
-        st->mdn = dn, st->mpn = pn, st->solve_failed |= fail;   // map_normal_kernel may have set it already
-    }
+    reduced_step_block<MAP_SOLVE_THREADS>(d.S, d.delta, d.mpose, d.nboard - 1, &d.st->lm, s_col, s_b, &s_piv, &s_fail);
 }
 
 // Per used frame: step = 0 evaluates the cost at the current parameters into vcost[cur]; step = 1 back-substitutes the pose step
@@ -457,7 +407,7 @@ __global__ __launch_bounds__(64) void map_eval_kernel(MapDev d, int step) {
     const int f = blockIdx.x, lane = threadIdx.x;
     if (!d.used[f]) return;
     const MapState* st = d.st;
-    const int cur = st->cur, dst = step ? 1 - cur : cur, ns = d.fn[f], s = lane >> 2, k = lane & 3;
+    const int cur = st->lm.cur, dst = step ? 1 - cur : cur, ns = d.fn[f], s = lane >> 2, k = lane & 3;
     const double* p0 = d.fpose + ((size_t)cur * d.nframes + f) * 6;
     double in[9], p[6], dn = 0, pn = 0;
     for (int i = 0; i < 9; i++) in[i] = st->intr[i];
@@ -500,35 +450,25 @@ __global__ __launch_bounds__(64) void map_eval_kernel(MapDev d, int step) {
     }
 }
 
-// CvLevMarq's rule as in calib_update_kernel: a candidate whose error is not larger is taken and lambda falls tenfold, else (or when
-// the reduced system could not be factorised) lambda rises tenfold (stop above 1e16). Stop after max_iter accepted steps or when
-// |step| / |params| < DBL_EPSILON.
+// One thread: the cost over the used frames in frame order; step 0 records the start, a step decides by lm_decide.
 __global__ void map_update_kernel(MapDev d, int step) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     MapState* st = d.st;
-    const int other = step ? 1 - st->cur : st->cur;
+    const int other = step ? 1 - st->lm.cur : st->lm.cur;
     double c = 0;
     int nu = 0, no = 0;
     for (int f = 0; f < d.nframes; f++)
         if (d.used[f]) c += d.vcost[(size_t)other * d.nframes + f], nu++, no += d.fn[f];
     if (!step) {
-        st->cost = c, st->nused = nu, st->nobs = no;
-        if (!isfinite(c)) st->err |= MAP_ERR_DEGENERATE;
+        st->lm.cost = c, st->nused = nu, st->nobs = no;
+        if (!isfinite(c)) st->lm.err |= MAP_ERR_DEGENERATE;
         return;
     }
-    st->attempts++;
-    if (!st->solve_failed && isfinite(c) && c <= st->cost) {
-        double dn = st->mdn, pn = st->mpn;
+    double dn = st->lm.sdn, pn = st->lm.spn;
+    if (lm_takes(st->lm, c))
         for (int f = 0; f < d.nframes; f++)
             if (d.used[f]) dn += d.vchg[2 * f], pn += d.vchg[2 * f + 1];
-        st->cur = other, st->cost = c;
-        st->lg = max(st->lg - 1, -16);
-        st->iters++;
-        if (st->iters >= st->max_iter || sqrt(dn) < DBL_EPSILON * sqrt(pn)) st->done = 1;
-    } else if (++st->lg > 16) {
-        st->done = 1;
-    }
-    st->solve_failed = 0;
+    lm_decide(st->lm, c, dn, pn);
 }
 
 // The corners of every marker in the frame of marker 0, rounded once to float; zeros for a marker that is not mapped.
@@ -541,7 +481,7 @@ __global__ __launch_bounds__(64) void map_obj_kernel(MapDev d) {
         o[0] = o[1] = o[2] = 0.f;
         return;
     }
-    const double* mp = d.mpose + ((size_t)d.st->cur * d.nboard + m) * 6;
+    const double* mp = d.mpose + ((size_t)d.st->lm.cur * d.nboard + m) * 6;
     double Rm[9], cx, cy;
     rodrigues_vec2mat(mp, Rm, nullptr);
     map_corner(d.half, k, &cx, &cy);

@@ -1,6 +1,6 @@
 // Camera rigs: where ncams cameras with fixed intrinsics stand relative to each other (camera 0 is the rig frame: identity, no
-// variable), and the pose of a board in the rig frame from every camera that sees part of it at one instant. FP64 throughout, the
-// fourth user of the Schur-complement Levenberg-Marquardt of k_calib.hip; the composition is the one of k_map.hip with the roles
+// variable), and the pose of a board in the rig frame from every camera that sees part of it at one instant. FP64 throughout, with
+// the Schur-complement Levenberg-Marquardt of k_calib.hip (lm_device.h); the composition is the one of k_map.hip with the roles
 // swapped: the shared block is the outer transform (the camera), the eliminated block the inner one (the board at an instant).
 //
 // Corner k of board marker m seen by camera c at instant t projects R_c (R_t X_mk + t_t) + t_c through project_point_d with camera c's
@@ -88,31 +88,7 @@ __global__ __launch_bounds__(64) void rig_view_kernel(RigDev d) {
     const int v = blockIdx.x, lane = threadIdx.x, c = v % d.ncams;
     int lo = 0, hi = d.nobs;
     if (!d.obs_view) lo = v * d.obs_stride, hi = lo + max(min(d.obs_cnt[v], d.obs_stride), 0);
-    int n = 0;
-    unsigned long long seen0 = 0, seen1 = 0;
-    for (int base = lo; base < hi; base += 64) {
-        const int i = base + lane;
-        int bi = -1;
-        if (i < hi && (!d.obs_view || d.obs_view[i] == v)) {
-            const int id = d.obs_id[i];
-            for (int j = 0; j < d.nboard; j++)
-                if (d.ids[j] == id) {
-                    bi = j;
-                    break;
-                }
-        }
-        unsigned long long mask = __ballot(bi >= 0);
-        while (mask) {
-            const int j = __ffsll((long long)mask) - 1;
-            mask &= mask - 1;
-            const int b = __shfl(bi, j, 64);
-            unsigned long long& seen = b < 64 ? seen0 : seen1;
-            if ((seen >> (b & 63)) & 1) continue;
-            seen |= 1ull << (b & 63);
-            if (lane == 0) s_m[n] = b, s_o[n] = base + j;
-            n++;   // n <= nboard <= RIG_MAX_BOARD: every board marker enters once
-        }
-    }
+    const int n = listed_scan(d.obs_view, v, d.obs_id, lo, hi, d.ids, d.nboard, lane, s_m, s_o);   // n <= nboard <= RIG_MAX_BOARD
     __syncthreads();
     BoardDef bd;
     bd.ids = d.ids, bd.obj = d.bobj, bd.nboard = d.nboard, bd.info_type = d.info_type, bd.marker_size = d.marker_size, bd.repj_thres = -1.f;
@@ -238,9 +214,9 @@ __global__ __launch_bounds__(64) void rig_tree_kernel(RigDev d) {
         for (int k = 0; k < nc; k++) nr += s_reached[k];
         d.st->ncal = seen ? nr : 0;
         if (!seen)
-            d.st->err |= RIG_ERR_NO_REFERENCE;
+            d.st->lm.err |= RIG_ERR_NO_REFERENCE;
         else if (nr < 2)
-            d.st->err |= RIG_ERR_TOO_FEW;
+            d.st->lm.err |= RIG_ERR_TOO_FEW;
     }
 }
 
@@ -293,7 +269,7 @@ __global__ __launch_bounds__(64) void rig_instant_kernel(RigDev d) {
 __global__ __launch_bounds__(64) void rig_gram_kernel(RigDev d) {
     const int v = blockIdx.x, lane = threadIdx.x;
     if (!d.vact[v]) return;
-    const int nc = d.ncams, t = v / nc, c = v % nc, cur = d.st->cur, np = d.vn[v] * 4;
+    const int nc = d.ncams, t = v / nc, c = v % nc, cur = d.st->lm.cur, np = d.vn[v] * 4;
     const double* cp = d.cpose + ((size_t)cur * nc + c) * 6;
     const double* ip = d.ipose + ((size_t)cur * d.ninstants + t) * 6;
     double in[9], Rc[9], dRc[27], Rt[9], dRt[27];
@@ -329,12 +305,12 @@ __global__ __launch_bounds__(64) void rig_gram_kernel(RigDev d) {
 
 // Per used instant. U = sum_c J_p^T J_p and g_p = sum_c J_p^T r over its views in camera order, U~ = U with its diagonal times
 // (1 + lambda); u = U~^-1 g_p, and per view of a camera c > 0: Y_c = W_c U~^-1 with W_c = J_c^T J_p, rec = {Y_c, g_c - W_c u} (one 6 x 6
-// solve per row of W_c and one for g_p, a lane each; a singular U~ sets st->solve_failed).
+// solve per row of W_c and one for g_p, a lane each: solve_damped6).
 __global__ __launch_bounds__(64) void rig_instant_solve_kernel(RigDev d) {
     __shared__ double s_u[6];
     const int t = blockIdx.x, lane = threadIdx.x, nc = d.ncams;
     if (!d.used[t]) return;
-    const double lambda = lm_lambda(d.st->lg);
+    const double lambda = lm_lambda(d.st->lm.lg);
     double U[36], gp[6];
 #pragma unroll
     for (int a = 0; a < 36; a++) U[a] = 0;
@@ -356,16 +332,10 @@ __global__ __launch_bounds__(64) void rig_instant_solve_kernel(RigDev d) {
         const int c = e / 6, j = e % 6;
         if (c < nc && (c == 0 || !d.vact[(size_t)t * nc + c])) continue;
         const double* g = d.gram + ((size_t)t * nc + min(c, nc - 1)) * RIG_G;
-        double Uc[36], bc[6];
-#pragma unroll
-        for (int a = 0; a < 36; a++) Uc[a] = U[a];
+        double bc[6];
 #pragma unroll
         for (int a = 0; a < 6; a++) bc[a] = c < nc ? g[rg_index(j, 6 + a)] : gp[a];
-        if (!solve_static<6>(Uc, bc)) {   // the instant's pose cannot be eliminated: the step is rejected (rig_update_kernel)
-            atomicOr(&d.st->solve_failed, 1);
-#pragma unroll
-            for (int a = 0; a < 6; a++) bc[a] = 0;
-        }
+        solve_damped6(U, bc, &d.st->lm.solve_failed);   // a failure: the instant's pose cannot be eliminated
         if (c < nc) {
             double* Y = d.rec + ((size_t)t * nc + c) * RIG_REC + j * 6;
 #pragma unroll
@@ -410,7 +380,7 @@ __global__ __launch_bounds__(256) void rig_assemble_kernel(RigDev d) {
         d.S[(size_t)i * N + j] = i == j ? 1. : 0.;
         return;
     }
-    const double lambda = lm_lambda(d.st->lg);
+    const double lambda = lm_lambda(d.st->lm.lg);
     double sum = 0, diag = 0;
     for (int t = 0; t < d.ninstants; t++) {
         const size_t va = (size_t)t * nc + a, vb = (size_t)t * nc + b;
@@ -426,30 +396,11 @@ __global__ __launch_bounds__(256) void rig_assemble_kernel(RigDev d) {
     d.S[(size_t)i * N + j] = i == j ? sum + lambda * diag : sum;
 }
 
-// One workgroup: the reduced system by Cholesky (chol_device.h). A failed solve gives a zero step and st->solve_failed: a rejected step.
-// Then the candidate camera transforms cpose[other] = cpose[cur] - step and the norms of step and parameters.
+// One workgroup: the camera step from the reduced system and the candidate camera transforms cpose[other] (reduced_step_block).
 __global__ __launch_bounds__(RIG_SOLVE_THREADS) void rig_solve_kernel(RigDev d) {
     __shared__ double s_col[RIG_MAX_N], s_b[RIG_MAX_N], s_piv;
     __shared__ int s_fail;
-    const int nc = d.ncams, N = 6 * (nc - 1), tid = threadIdx.x, T = RIG_SOLVE_THREADS;
-    for (int i = tid; i < N; i += T) s_b[i] = d.delta[i];
-    const int fail = chol_solve_block<RIG_SOLVE_THREADS>(d.S, N, s_col, s_b, &s_piv, &s_fail, tid);
-    RigState* st = d.st;
-    const int cur = st->cur;
-    for (int i = tid; i < N; i += T) {
-        const double dl = fail ? 0. : s_b[i];
-        s_b[i] = dl, d.delta[i] = dl;
-        d.cpose[((size_t)(1 - cur) * nc + 1) * 6 + i] = d.cpose[((size_t)cur * nc + 1) * 6 + i] - dl;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double dn = 0, pn = 0;
-        for (int i = 0; i < N; i++) {
-            const double val = d.cpose[((size_t)cur * nc + 1) * 6 + i];
-            dn += s_b[i] * s_b[i], pn += val * val;
-        }
-        st->cdn = dn, st->cpn = pn, st->solve_failed |= fail;   // rig_instant_solve_kernel may have set it already
-    }
+    reduced_step_block<RIG_SOLVE_THREADS>(d.S, d.delta, d.cpose, d.ncams - 1, &d.st->lm, s_col, s_b, &s_piv, &s_fail);
 }
 
 // Per view that takes part: step = 0 evaluates the cost at the current parameters into vcost[cur]; step = 1 back-substitutes the
@@ -458,7 +409,7 @@ __global__ __launch_bounds__(RIG_SOLVE_THREADS) void rig_solve_kernel(RigDev d) 
 __global__ __launch_bounds__(64) void rig_eval_kernel(RigDev d, int step) {
     const int v = blockIdx.x, lane = threadIdx.x;
     if (!d.vact[v]) return;
-    const int nc = d.ncams, t = v / nc, c = v % nc, cur = d.st->cur, dst = step ? 1 - cur : cur, np = d.vn[v] * 4;
+    const int nc = d.ncams, t = v / nc, c = v % nc, cur = d.st->lm.cur, dst = step ? 1 - cur : cur, np = d.vn[v] * 4;
     const double* p0 = d.ipose + ((size_t)cur * d.ninstants + t) * 6;
     const double* cp = d.cpose + ((size_t)dst * nc + c) * 6;
     double in[9], p[6], dn = 0, pn = 0;
@@ -492,36 +443,27 @@ __global__ __launch_bounds__(64) void rig_eval_kernel(RigDev d, int step) {
     }
 }
 
-// CvLevMarq's rule as in calib_update_kernel and map_update_kernel: a candidate whose error is not larger is taken and lambda falls
-// tenfold, else (or when a system could not be solved) lambda rises tenfold (stop above 1e16). Stop after max_iter accepted steps or
-// when |step| / |params| < DBL_EPSILON. Views are added in view order: instants in order, cameras in order.
+// One thread: the cost over the views that take part, in view order (instants in order, cameras in order); step 0 records the
+// start, a step decides by lm_decide.
 __global__ void rig_update_kernel(RigDev d, int step) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     RigState* st = d.st;
-    const int other = step ? 1 - st->cur : st->cur, V = d.ninstants * d.ncams;
+    const int other = step ? 1 - st->lm.cur : st->lm.cur, V = d.ninstants * d.ncams;
     double c = 0;
     int np = 0, nu = 0;
     for (int v = 0; v < V; v++)
         if (d.vact[v]) c += d.vcost[(size_t)other * V + v], np += d.vn[v] * 4;
     for (int t = 0; t < d.ninstants; t++) nu += d.used[t];
     if (!step) {
-        st->cost = c, st->nused = nu, st->npts = np;
-        if (!isfinite(c) || nu < 1) st->err |= RIG_ERR_DEGENERATE;
+        st->lm.cost = c, st->nused = nu, st->npts = np;
+        if (!isfinite(c) || nu < 1) st->lm.err |= RIG_ERR_DEGENERATE;
         return;
     }
-    st->attempts++;
-    if (!st->solve_failed && isfinite(c) && c <= st->cost) {
-        double dn = st->cdn, pn = st->cpn;
+    double dn = st->lm.sdn, pn = st->lm.spn;
+    if (lm_takes(st->lm, c))
         for (int t = 0; t < d.ninstants; t++)
             if (d.used[t]) dn += d.vchg[2 * t], pn += d.vchg[2 * t + 1];
-        st->cur = other, st->cost = c;
-        st->lg = max(st->lg - 1, -16);
-        st->iters++;
-        if (st->iters >= st->max_iter || sqrt(dn) < DBL_EPSILON * sqrt(pn)) st->done = 1;
-    } else if (++st->lg > 16) {
-        st->done = 1;
-    }
-    st->solve_failed = 0;
+    lm_decide(st->lm, c, dn, pn);
 }
 
 // ---- rig pose --------------------------------------------------------------------------------------------------------------------------
