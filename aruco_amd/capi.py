@@ -147,7 +147,7 @@ SYMBOLS = [
     "arucohip_mgpu_set_depth", "arucohip_mgpu_submit_batch", "arucohip_mgpu_submit_streams", "arucohip_mgpu_wait",
     "arucohip_compact_bytes", "arucohip_compact_markers", "arucohip_wait_event", "arucohip_detect_batch_retry_overflowed",
     "arucohip_refine_candidate_lines", "arucohip_debug_refine_pixels", "arucohip_mgpu_gather_mode", "arucohip_build_info",
-    "arucohip_calibrate_camera", "arucohip_calibrate_board_batch", "arucohip_board_map", "arucohip_board_map_batch",
+    "arucohip_calibrate_camera", "arucohip_calibrate_board_batch", "arucohip_debug_calib_start", "arucohip_board_map", "arucohip_board_map_batch",
     "arucohip_rig_calibrate", "arucohip_rig_calibrate_batch", "arucohip_rig_pose", "arucohip_rig_pose_batch",
     "arucohip_planar_poses", "arucohip_planar_poses_batch",
     "arucohip_chromatic_board_corners", "arucohip_chromatic_create", "arucohip_chromatic_destroy", "arucohip_chromatic_train",
@@ -232,6 +232,7 @@ def load():
     L.arucohip_default_recover.restype = None
     L.arucohip_board_recover_batch.argtypes = [vp, i, vp, vp, i, i, vp, vp, i, f, f, i, vp, vp, i, vp, i, vp, vp, vp]
     L.arucohip_calibrate_camera.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp]
+    L.arucohip_debug_calib_start.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, vp, vp, vp, vp, vp, vp]
     L.arucohip_calibrate_board_batch.argtypes = [vp, i, vp, vp, i, i, f, i, i, i, i, vp, vp, vp, vp, vp, vp]
     L.arucohip_board_map.argtypes = [vp, vp, vp, vp, i, i, i, vp, i, vp, vp, i, f] + [vp] * 10
     L.arucohip_board_map_batch.argtypes = [vp, i, vp, i, vp, vp, i, f, i] + [vp] * 10
@@ -1100,6 +1101,26 @@ class Handle:
         self._chk(self.L.arucohip_calibrate_camera(self.h, obj_ptr, img_ptr, npoints_ptr, nviews, 1, int(image_size[0]), int(image_size[1]),
                                                    int(flags), _ptr(Ka), _ptr(da), _ptr(rv), _ptr(tv), _ptr(pv), C.byref(rms)))
         return {"rms": rms.value, "K": Ka.reshape(3, 3), "dist": da, "rvecs": rv, "tvecs": tv, "per_view_rms": pv}
+
+    def debug_calib_start(self, obj_list, img_list, image_size, flags=0, K=None, dist=None, fisheye=False):
+        """arucohip_debug_calib_start: the start values of calibrate_camera (or, with fisheye, of fisheye_calibrate: K and dist = D are its
+        model, flags its FISHEYE_*) on the same views: intr [9], poses [V, 6] (rvec, tvec), cost and the start kernels' err bits."""
+        objs = [np.asarray(o, np.float32).reshape(-1, 3) for o in obj_list]
+        imgs = [np.asarray(m, np.float32).reshape(-1, 2) for m in img_list]
+        if len(objs) != len(imgs) or any(len(o) != len(m) for o, m in zip(objs, imgs)):
+            raise ValueError("the views' object and image points differ in number")
+        npts = np.array([len(o) for o in objs], np.int32)
+        oa, ia = np.ascontiguousarray(np.concatenate(objs)), np.ascontiguousarray(np.concatenate(imgs))
+        Ka = np.zeros(9) if K is None else np.array(K, dtype=np.float64).reshape(9)
+        da = np.zeros(5)
+        if dist is not None:
+            dd = np.asarray(dist, np.float64).reshape(-1)
+            da[:dd.size] = dd
+        V = len(objs)
+        intr, poses, cost, err = np.zeros(9), np.zeros((V, 6)), C.c_double(), C.c_int32()
+        self._chk(self.L.arucohip_debug_calib_start(self.h, _ptr(oa), _ptr(ia), _ptr(npts), V, 0, int(image_size[0]), int(image_size[1]), int(flags),
+                                                    int(bool(fisheye)), _ptr(Ka), _ptr(da), _ptr(intr), _ptr(poses), C.byref(cost), C.byref(err)))
+        return {"intr": intr, "poses": poses, "cost": cost.value, "err": err.value}
 
     def calibrate_board_batch(self, nframes, ids, obj, info_type, image_size, marker_size=-1.0, min_markers=4, flags=0, K=None, dist=None):
         """calibrate_camera on the board detections of the last detect_batch call, left on the device: frames with at least

@@ -25,6 +25,14 @@ static size_t calib_layout(CalibViews& v, uint8_t* base, int V, size_t npts, int
     return c.at;
 }
 
+// the used views' offsets and counts, on h's stream
+static int calib_counts_up(arucohip_handle* h, const CalibViews& v) {
+    const size_t bytes = (size_t)v.d.nviews * sizeof(int32_t);
+    HIPCHK(h, hipMemcpyAsync(v.off_dev, v.off.data(), bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(v.npt_dev, v.npt.data(), bytes, hipMemcpyHostToDevice, h->stream));
+    return ARUCOHIP_OK;
+}
+
 // Levenberg-Marquardt (lm_drive) on views whose points are already on the device (v.d.obj / v.d.img, offsets off[], counts npt[]),
 // in h's d_calib where v is bound, from the state `st` (start intrinsics, free mask, flags, model).
 // focal_start: the focal lengths come from the views' homographies (pinhole without a guess).
@@ -33,8 +41,7 @@ int calib_solve(arucohip_handle* h, const CalibViews& v, CalibState st, bool foc
     const CalibDev& d = v.d;
     const int V = d.nviews;
     hipStream_t s = h->stream;
-    HIPCHK(h, hipMemcpyAsync(v.off_dev, v.off.data(), (size_t)V * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(v.npt_dev, v.npt.data(), (size_t)V * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (const int up = calib_counts_up(h, v)) return up;
     const int rc = lm_drive(
         h, d.st, &st, [&] { launch_calib_init(s, d, !focal_start); },
         [&](const CalibState& at) {
@@ -130,11 +137,10 @@ int calib_views_of_batch(arucohip_handle* h, int nframes, const int32_t* ids, co
     return ARUCOHIP_OK;
 }
 
-// the pinhole run: start state from (K, dist, flags), results back into K and dist
-static int calib_pinhole(arucohip_handle* h, const CalibViews& v, int W, int H, int flags, double* K, double* dist, double* rvecs, double* tvecs,
-                         double* per_view_rms, double* rms) {
+// the start state of a pinhole run from (K, dist, flags)
+static int calib_pinhole_state(arucohip_handle* h, int W, int H, int flags, const double* K, const double* dist, CalibState* stp) {
     const bool guess = flags & ARUCOHIP_CALIB_USE_INTRINSIC_GUESS;
-    CalibState st;
+    CalibState& st = *stp;
     std::memset(&st, 0, sizeof(st));
     st.flags = flags, st.model = CALIB_MODEL_PINHOLE;
     st.aspect = (K[0] > 0 && K[4] > 0) ? K[0] / K[4] : 1.0;
@@ -155,8 +161,17 @@ static int calib_pinhole(arucohip_handle* h, const CalibViews& v, int W, int H, 
     if (flags & ARUCOHIP_CALIB_FIX_K2) mask &= ~32;
     if (flags & ARUCOHIP_CALIB_FIX_K3) mask &= ~256;
     st.free_mask = mask;
+    return ARUCOHIP_OK;
+}
+
+// the pinhole run: start state from (K, dist, flags), results back into K and dist
+static int calib_pinhole(arucohip_handle* h, const CalibViews& v, int W, int H, int flags, double* K, double* dist, double* rvecs, double* tvecs,
+                         double* per_view_rms, double* rms) {
+    CalibState st;
+    int rc = calib_pinhole_state(h, W, H, flags, K, dist, &st);
+    if (rc) return rc;
     double in[9];
-    const int rc = calib_solve(h, v, st, !guess, in, rvecs, tvecs, per_view_rms, rms);
+    rc = calib_solve(h, v, st, !(flags & ARUCOHIP_CALIB_USE_INTRINSIC_GUESS), in, rvecs, tvecs, per_view_rms, rms);
     if (rc) return rc;
     const double Ko[9] = {in[0], 0, in[2], 0, in[1], in[3], 0, 0, 1};
     for (int i = 0; i < 9; i++) K[i] = Ko[i];
@@ -175,6 +190,39 @@ int arucohip_calibrate_camera(arucohip_handle* h, const float* obj, const float*
     const int rc = calib_views_of_points(h, obj, img, npoints, nviews, on_device, &v);
     if (rc) return rc;
     return calib_pinhole(h, v, W, H, flags, K, dist, rvecs, tvecs, per_view_rms, rms);
+}
+
+int arucohip_debug_calib_start(arucohip_handle* h, const float* obj, const float* img, const int32_t* npoints, int nviews, int on_device, int W,
+                               int H, int flags, int model, const double* K, const double* dist, double* intr, double* poses, double* cost,
+                               int32_t* err) {
+    if (!h) return ARUCOHIP_E_INVALID;
+    if (!obj || !img || !npoints || !K || !dist || !intr || !poses || !cost || !err || nviews < 1 || W <= 0 || H <= 0)
+        return fail(h, ARUCOHIP_E_INVALID, "debug_calib_start: NULL argument, no views or an empty image size");
+    if (model != CALIB_MODEL_PINHOLE && model != CALIB_MODEL_FISHEYE) return fail(h, ARUCOHIP_E_INVALID, "debug_calib_start: model is 0 (pinhole) or 1 (fisheye)");
+    CalibViews v;
+    int rc = calib_views_of_points(h, obj, img, npoints, nviews, on_device, &v);
+    if (rc) return rc;
+    CalibState st;
+    bool focal_start = false;
+    if (model == CALIB_MODEL_FISHEYE) {
+        arucohip_fisheye_t m;
+        for (int i = 0; i < 9; i++) m.K[i] = K[i];
+        for (int i = 0; i < 4; i++) m.D[i] = dist[i];
+        rc = calib_fisheye_state(h, W, H, flags, &m, &st);
+    } else {
+        rc = calib_pinhole_state(h, W, H, flags, K, dist, &st);
+        focal_start = !(flags & ARUCOHIP_CALIB_USE_INTRINSIC_GUESS);
+    }
+    if (rc) return rc;
+    if ((rc = calib_counts_up(h, v))) return rc;
+    hipStream_t s = h->stream;
+    CalibState* at = nullptr;
+    if ((rc = lm_start(h, v.d.st, &st, [&] { launch_calib_init(s, v.d, !focal_start); }, &at))) return rc;
+    HIPCHK(h, hipMemcpyAsync(poses, v.d.pose, (size_t)nviews * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    for (int i = 0; i < 9; i++) intr[i] = at->intr[i];
+    *cost = at->lm.cost, *err = at->lm.err;
+    return ARUCOHIP_OK;
 }
 
 int arucohip_calibrate_board_batch(arucohip_handle* h, int nframes, const int32_t* ids, const float* obj, int nboard, int info_type,

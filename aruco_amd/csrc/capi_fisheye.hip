@@ -62,10 +62,9 @@ static int fisheye_points(arucohip_handle* h, const arucohip_fisheye_t* model, c
     return ARUCOHIP_OK;
 }
 
-// the fisheye run of the calibration solver (k_calib.hip with CALIB_MODEL_FISHEYE): start state from (model, flags), results back
-static int calib_fisheye(arucohip_handle* h, const CalibViews& v, int W, int H, int flags, arucohip_fisheye_t* model, double* rvecs, double* tvecs,
-                         double* per_view_rms, double* rms) {
-    CalibState st;
+// the start state of a fisheye run from (model, flags)
+int calib_fisheye_state(arucohip_handle* h, int W, int H, int flags, const arucohip_fisheye_t* model, CalibState* stp) {
+    CalibState& st = *stp;
     std::memset(&st, 0, sizeof(st));
     st.model = CALIB_MODEL_FISHEYE;
     st.flags = (flags & ARUCOHIP_FISHEYE_FIX_ASPECT_RATIO) ? ARUCOHIP_CALIB_FIX_ASPECT_RATIO : 0;   // the one flag the kernels read
@@ -91,8 +90,17 @@ static int calib_fisheye(arucohip_handle* h, const CalibViews& v, int W, int H, 
     if (flags & ARUCOHIP_FISHEYE_FIX_K3) mask &= ~64;
     if (flags & ARUCOHIP_FISHEYE_FIX_K4) mask &= ~128;
     st.free_mask = mask;
+    return ARUCOHIP_OK;
+}
+
+// the fisheye run of the calibration solver (k_calib.hip with CALIB_MODEL_FISHEYE): start state from (model, flags), results back
+static int calib_fisheye(arucohip_handle* h, const CalibViews& v, int W, int H, int flags, arucohip_fisheye_t* model, double* rvecs, double* tvecs,
+                         double* per_view_rms, double* rms) {
+    CalibState st;
+    int rc = calib_fisheye_state(h, W, H, flags, model, &st);
+    if (rc) return rc;
     double in[9];
-    const int rc = calib_solve(h, v, st, false, in, rvecs, tvecs, per_view_rms, rms);
+    rc = calib_solve(h, v, st, false, in, rvecs, tvecs, per_view_rms, rms);
     if (rc) return rc;
     const double Ko[9] = {in[0], 0, in[2], 0, in[1], in[3], 0, 0, 1};
     for (int i = 0; i < 9; i++) model->K[i] = Ko[i];

@@ -288,8 +288,10 @@ int on_workers(arucohip_handle* h, const Batch& b, F per_span) {
 // launches the start values, and started(state) turns the solver's err bits into its own message and code. Then iter() launches
 // one attempt at a time, with one copy of the state and one synchronisation each for the stop flag: at most 30 accepted steps; every
 // rejected step raises lambda tenfold, and lambda above 1e16 stops. *st returns the final state.
-template <class State, class Init, class Started, class Iter>
-int lm_drive(arucohip_handle* o, State* dev, State* st, Init init, Started started, Iter iter) {
+// lm_start is its first phase alone (the start-value hook stops after it): the state up, init(), the state back in the pinned copy,
+// which it returns in *hs.
+template <class State, class Init>
+int lm_start(arucohip_handle* o, State* dev, const State* st, Init init, State** hs_out) {
     hipStream_t s = o->stream;
     HIPCHK(o, o->hc_solver.reserve(sizeof(State)));
     State* hs = (State*)(uint8_t*)o->hc_solver;
@@ -300,6 +302,14 @@ int lm_drive(arucohip_handle* o, State* dev, State* st, Init init, Started start
     HIPCHK(o, hipGetLastError());
     HIPCHK(o, hipMemcpyAsync(hs, dev, sizeof(State), hipMemcpyDeviceToHost, s));
     HIPCHK(o, hipStreamSynchronize(s));
+    *hs_out = hs;
+    return ARUCOHIP_OK;
+}
+template <class State, class Init, class Started, class Iter>
+int lm_drive(arucohip_handle* o, State* dev, State* st, Init init, Started started, Iter iter) {
+    hipStream_t s = o->stream;
+    State* hs = nullptr;
+    if (const int rc = lm_start(o, dev, st, init, &hs)) return rc;
     if (const int rc = started(*hs)) return rc;
     for (int it = 0; it < 256 && !hs->lm.done; it++) {
         iter();
@@ -355,3 +365,5 @@ int calib_views_of_batch(arucohip_handle* h, int nframes, const int32_t* ids, co
                          int min_markers, int32_t* used, arucohip_handle** owner, CalibViews* v);
 int calib_solve(arucohip_handle* h, const CalibViews& v, CalibState st, bool focal_start, double intr[9], double* rvecs, double* tvecs,
                 double* per_view_rms, double* rms);
+// the fisheye run's start state from (model, flags) (capi_fisheye.hip)
+int calib_fisheye_state(arucohip_handle* h, int W, int H, int flags, const arucohip_fisheye_t* model, CalibState* st);

@@ -498,6 +498,15 @@ int arucohip_calibrate_camera(arucohip_handle* h, const float* obj, const float*
 int arucohip_calibrate_board_batch(arucohip_handle* h, int nframes, const int32_t* ids, const float* obj, int nboard, int info_type,
                                    float marker_size, int min_markers, int width, int height, int flags, double K[9], double dist[5],
                                    int32_t* used, double* rvecs, double* tvecs, double* rms);
+/* Test hook: the start values of a calibration and nothing after them. Views, size and flags as arucohip_calibrate_camera (model 0) or as
+ * arucohip_fisheye_calibrate (model 1: K and the four coefficients dist[0..3] are its model, flags its ARUCOHIP_FISHEYE_*); K and dist are
+ * read only. The views are staged and the start kernels run as in those calls, then: intr[9] the start intrinsics (fx fy cx cy and the
+ * model's coefficients, a fisheye's ninth entry 0), poses[6 per view] the start rvec, tvec, *cost the sum of squared residuals at that
+ * start, *err the start kernels' condition bits (0: fine, 1: degenerate views, 2: a view is not planar). The condition is reported, not
+ * turned into an error: the call answers ARUCOHIP_OK, and with *err != 0 the other outputs are not meaningful. */
+int arucohip_debug_calib_start(arucohip_handle* h, const float* obj, const float* img, const int32_t* npoints, int nviews, int on_device,
+                               int width, int height, int flags, int model, const double K[9], const double* dist, double intr[9],
+                               double* poses, double* cost, int32_t* err);
 
 /* Marker mapping: the 3-D layout of a rigid marker set from frames that show several of its markers. This is what produces the
  * object points of a board that is not planar (a marker cube, markers taped around a room) for arucohip_board_detect* above, whose

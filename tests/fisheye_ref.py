@@ -283,6 +283,30 @@ def make_views(nviews=12, noise=0.0, seed=5, intr=INTR_TRUE, size=(W, H)):
     return objs, imgs
 
 
+def start_points(intr, img):
+    """a view's pixels undistorted with the start model, each angle clamped to 1.5 rad: the normalised points (n, 2) float64 from which
+    the start pose is made"""
+    m = np.asarray(img, np.float64)
+    x, y = (m[:, 0] - intr[2]) / intr[0], (m[:, 1] - intr[3]) / intr[1]
+    thd = np.hypot(x, y)
+    th = thd.copy()
+    for _ in range(NEWTON_STEPS):
+        th = th - (theta_d(intr[4:8], th) - thd) / dtheta_d(intr[4:8], th)
+    sc = np.where(thd > 0, np.tan(np.clip(th, 0, 1.5)) / np.where(thd > 0, thd, 1), 1.0)
+    return np.stack([x * sc, y * sc], axis=1)
+
+
+MIXED_COUNTS = (20, 31, 63, 64, 65, 96, 24, 40, 96, 70, 33, 50)   # below 32, either side of 64, and the whole board
+
+
+def mixed_views():
+    """make_views(12, noise=0.3) with view v cut down to a seeded subset of MIXED_COUNTS[v] of its 96 corners, in corner order"""
+    objs, imgs = make_views(12, noise=0.3)
+    rng = np.random.RandomState(77)
+    keep = [np.sort(rng.choice(96, n, replace=False)) for n in MIXED_COUNTS]
+    return [o[k] for o, k in zip(objs, keep)], [m[k] for m, k in zip(imgs, keep)]
+
+
 def calib_start(objs, imgs, size, flags=0, model=None):
     """The start of arucohip_fisheye_calibrate: cx, cy at the image centre, fx = fy = max(w, h) / pi, D = 0 (or the given model); every
     view's pose from the homography of its points undistorted with that model, each angle clamped to 1.5 rad."""
@@ -299,14 +323,7 @@ def calib_start(objs, imgs, size, flags=0, model=None):
         intr[0] = aspect * intr[1]
     poses = []
     for o, m in zip(objs, imgs):
-        m = np.asarray(m, np.float64)
-        x, y = (m[:, 0] - intr[2]) / intr[0], (m[:, 1] - intr[3]) / intr[1]
-        thd = np.hypot(x, y)
-        th = thd.copy()
-        for _ in range(NEWTON_STEPS):
-            th = th - (theta_d(intr[4:8], th) - thd) / dtheta_d(intr[4:8], th)
-        sc = np.where(thd > 0, np.tan(np.clip(th, 0, 1.5)) / np.where(thd > 0, thd, 1), 1.0)
-        Hm = homography(np.asarray(o, np.float64), np.stack([x * sc, y * sc], axis=1))
+        Hm = homography(np.asarray(o, np.float64), start_points(intr, m))
         s = 2 / (np.linalg.norm(Hm[:, 0]) + np.linalg.norm(Hm[:, 1]))
         r1, r2 = Hm[:, 0] / np.linalg.norm(Hm[:, 0]), Hm[:, 1] / np.linalg.norm(Hm[:, 1])
         U, _, Vt = np.linalg.svd(np.stack([r1, r2, np.cross(r1, r2)], axis=1))
@@ -318,85 +335,24 @@ def calib_start(objs, imgs, size, flags=0, model=None):
     return intr, aspect, np.array(poses)
 
 
-class _Problem:
-    """The cost both solvers minimise: residuals over the free intrinsics (masked as the device masks them) and every view's pose."""
+def _Problem(objs, imgs, size, flags, model):
+    """The cost both solvers minimise (calib_ref.Problem with this model's projection): residuals over the free intrinsics (masked as the
+    device masks them) and every view's pose, from calib_start."""
+    from tests.calib_ref import Problem
 
-    def __init__(self, objs, imgs, size, flags, model):
-        self.intr0, self.aspect, self.poses0 = calib_start(objs, imgs, size, flags, model)
-        self.flags = flags
-        self.free = np.ones(8, bool)
-        for bit, idx in ((2, [0]), (4, [2, 3]), (8, [4]), (16, [5]), (32, [6]), (64, [7])):
-            if flags & bit:
-                self.free[idx] = False
-        self.nf, self.V = int(self.free.sum()), len(objs)
-        self.o64 = [np.asarray(o, np.float64) for o in objs]
-        self.m64 = [np.asarray(m, np.float64) for m in imgs]
-        self.rows = np.cumsum([0] + [2 * len(o) for o in objs])
-        self.npoints = sum(len(o) for o in objs)
-        self.x0 = np.concatenate([self.intr0[self.free], self.poses0.ravel()])
-
-    def unpack(self, x):
-        intr = self.intr0.astype(x.dtype)
-        intr[self.free] = x[:self.nf]
-        if self.flags & 2:
-            intr[0] = self.aspect * intr[1]
-        return intr, x[self.nf:].reshape(self.V, 6)
-
-    def resid(self, x):
-        intr, poses = self.unpack(x)
-        return np.concatenate([(project_view(intr, p[:3], p[3:], o) - m).ravel() for o, m, p in zip(self.o64, self.m64, poses)])
-
-    def jac(self, x):
-        """complex-step derivatives, exact to rounding"""
-        step = 1e-30
-        J = np.zeros((self.rows[-1], x.size))
-        for j in range(self.nf):
-            xc = x.astype(complex)
-            xc[j] += 1j * step
-            J[:, j] = self.resid(xc).imag / step
-        for k in range(6):
-            xc = x.astype(complex)
-            xc[self.nf + k::6] += 1j * step
-            col = self.resid(xc).imag / step
-            for v in range(self.V):
-                J[self.rows[v]:self.rows[v + 1], self.nf + 6 * v + k] = col[self.rows[v]:self.rows[v + 1]]
-        return J
-
-    def result(self, x, **more):
-        intr, poses = self.unpack(x)
-        res = self.resid(x)
-        return dict({"intr": intr, "rms": float(np.sqrt(np.sum(res ** 2) / self.npoints)), "rvecs": poses[:, :3], "tvecs": poses[:, 3:],
-                     "start": self.intr0}, **more)
+    intr0, aspect, poses0 = calib_start(objs, imgs, size, flags, model)
+    free = np.ones(8, bool)
+    for bit, idx in ((2, [0]), (4, [2, 3]), (8, [4]), (16, [5]), (32, [6]), (64, [7])):
+        if flags & bit:
+            free[idx] = False
+    return Problem(project_view, objs, imgs, intr0, poses0, free, aspect if flags & 2 else None)
 
 
 def lm_calibrate(objs, imgs, size, flags=0, model=None, max_iter=30):
-    """The device's Levenberg-Marquardt, dense: (J^T J + lambda diag(J^T J)) step = J^T r is what the per-view Schur elimination
-    solves. CvLevMarq's rule: lambda = 10^lg from lg = -3; a candidate whose cost is not larger is taken and lg falls by one, else lg
-    rises by one (stop above 16); stop after max_iter accepted steps or when |step| < DBL_EPSILON |parameters|."""
-    p = _Problem(objs, imgs, size, flags, model)
-    x, lg, iters = p.x0.copy(), -3, 0
-    r = p.resid(x)
-    cost = float(r @ r)
-    J = p.jac(x)
-    while True:
-        A, g = J.T @ J, J.T @ r
-        A[np.diag_indices_from(A)] *= 1 + 10.0 ** lg
-        step = np.linalg.solve(A, g)
-        xc = x - step
-        rc = p.resid(xc)
-        cc = float(rc @ rc)
-        if np.isfinite(cc) and cc <= cost:
-            full_old = np.concatenate([p.unpack(x)[0], x[p.nf:]])
-            full_new = np.concatenate([p.unpack(xc)[0], xc[p.nf:]])
-            x, r, cost, lg, iters = xc, rc, cc, max(lg - 1, -16), iters + 1
-            if iters >= max_iter or np.linalg.norm(full_new - full_old) < np.finfo(float).eps * np.linalg.norm(full_old):
-                break
-            J = p.jac(x)
-        else:
-            lg += 1
-            if lg > 16:
-                break
-    return p.result(x, iterations=iters)
+    """The device's Levenberg-Marquardt, dense (calib_ref.lm_solve: CvLevMarq's rule, at most max_iter accepted steps), on this model."""
+    from tests.calib_ref import lm_solve
+
+    return lm_solve(_Problem(objs, imgs, size, flags, model), max_iter)
 
 
 def scipy_calibrate(objs, imgs, size, flags=0, model=None):

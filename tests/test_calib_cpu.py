@@ -8,7 +8,7 @@ import numpy as np
 from tests import calib_ref as cr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("arucohip_calibrate_camera", "arucohip_calibrate_board_batch")
+NEW = ("arucohip_calibrate_camera", "arucohip_calibrate_board_batch", "arucohip_debug_calib_start")
 
 
 def test_library_exports_the_calibration_entry_points():
