@@ -146,7 +146,7 @@ SYMBOLS = [
     "arucohip_mgpu_set_params", "arucohip_mgpu_last_error_string", "arucohip_mgpu_detect_batch", "arucohip_mgpu_detect_streams",
     "arucohip_mgpu_set_depth", "arucohip_mgpu_submit_batch", "arucohip_mgpu_submit_streams", "arucohip_mgpu_wait",
     "arucohip_compact_bytes", "arucohip_compact_markers", "arucohip_wait_event", "arucohip_detect_batch_retry_overflowed",
-    "arucohip_refine_candidate_lines", "arucohip_debug_refine_pixels", "arucohip_mgpu_gather_mode", "arucohip_build_info",
+    "arucohip_refine_candidate_lines", "arucohip_debug_refine_pixels", "arucohip_debug_decode_quads", "arucohip_mgpu_gather_mode", "arucohip_build_info",
     "arucohip_calibrate_camera", "arucohip_calibrate_board_batch", "arucohip_debug_calib_start", "arucohip_board_map", "arucohip_board_map_batch",
     "arucohip_rig_calibrate", "arucohip_rig_calibrate_batch", "arucohip_rig_pose", "arucohip_rig_pose_batch",
     "arucohip_planar_poses", "arucohip_planar_poses_batch",
@@ -318,6 +318,7 @@ def load():
     L.arucohip_detect_batch_retry_overflowed.argtypes = [vp, vp, i, i, i, sz, sz, i, vp, vp, i, f, i, vp, i, vp, i, vp]
     L.arucohip_refine_candidate_lines.argtypes = [vp, vp, i, vp, vp, vp, i]
     L.arucohip_debug_refine_pixels.argtypes = [vp, vp, i, i, C.c_size_t, vp, i, i, i, i]
+    L.arucohip_debug_decode_quads.argtypes = [vp, vp, i, i, i, C.c_size_t, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp]
     L.arucohip_default_charuco.argtypes = [vp]
     L.arucohip_default_charuco.restype = None
     L.arucohip_charuco_board_size.argtypes = [vp, vp, vp, vp, vp]
@@ -692,6 +693,33 @@ class Handle:
         self._chk(self.L.arucohip_debug_refine_pixels(self.h, _ptr(g), stride if width is None else int(width), hgt, stride, _ptr(c), len(c), int(method),
                                                       int(win), int(locked_wsize)))
         return c
+
+    def debug_decode_quads(self, frames, quads, frame_of=None, width=None):
+        """The decode stage on integer quads (n x 4 x 2, what an int16 holds) of gray frames [nframes][H][stride] (one frame: [H][stride]); `width` <
+        stride gives padded frames whose row stride is kept on the device; frame_of: the frame of each quad (default 0). The handle's warp size,
+        decoder and dictionary and the frame count choose the kernels as they do for a batch. Returns a dict: iM (n x 9 float64), hist (n x 256
+        uint16), thr, ids, nrot (n, int32) and, as the path that ran left them, cells (n x 49 cell medians) or patches (n x ws x ws), else None."""
+        g = np.ascontiguousarray(frames, dtype=np.uint8)
+        if g.ndim == 2:
+            g = g[None]
+        nf, hgt, stride = g.shape
+        q = np.ascontiguousarray(quads, dtype=np.int16).reshape(-1, 8)
+        n = len(q)
+        fo = np.zeros(n, np.int32) if frame_of is None else np.ascontiguousarray(frame_of, dtype=np.int32).reshape(-1)
+        assert len(fo) == n
+        ws = self.get_params().warp_size
+        out = {"iM": np.zeros((n, 9), np.float64), "hist": np.zeros((n, 256), np.uint16), "thr": np.zeros(n, np.int32),
+               "cells": np.zeros((n, 49), np.uint8), "patches": np.zeros((n, ws, ws), np.uint8), "ids": np.zeros(n, np.int32),
+               "nrot": np.zeros(n, np.int32)}
+        paths = C.c_int32(0)
+        self._chk(self.L.arucohip_debug_decode_quads(self.h, _ptr(g), nf, stride if width is None else int(width), hgt, stride, _ptr(q), _ptr(fo), n,
+                                                     _ptr(out["iM"]), _ptr(out["hist"]), _ptr(out["thr"]), _ptr(out["cells"]), _ptr(out["patches"]),
+                                                     _ptr(out["ids"]), _ptr(out["nrot"]), C.byref(paths)))
+        if not paths.value & 1:
+            out["cells"] = None
+        if not paths.value & 2:
+            out["patches"] = None
+        return out
 
     def bgr_to_gray(self, bgr):
         b = np.ascontiguousarray(bgr, dtype=np.uint8)

@@ -1649,6 +1649,90 @@ int arucohip_debug_refine_pixels(arucohip_handle* h, const uint8_t* gray, int W,
     return ARUCOHIP_OK;
 }
 
+// Test hook: the decode stage on caller-supplied integer quads. The quads become candidates of the frames they name (in the order given, which is
+// also their order in the flat list), stage_quads_kernel solves their inverse homographies with the pipeline's homography_lane, and launch_decode
+// runs with the handle's current parameters and the frame count of the call, so the kernels a batch of that shape would take are the ones that
+// run (fused_cells = false: cells_decode_kernel stands in for the head of refine_lines_kernel, the same cells_decode_wave). Like
+// arucohip_debug_refine_pixels the frames keep their row stride on the device.
+int arucohip_debug_decode_quads(arucohip_handle* h, const uint8_t* gray, int nframes, int W, int H, size_t row_stride, const int16_t* quads_xy,
+                                const int32_t* frame_of, int n, double* iM, uint16_t* hist, int32_t* thr, uint8_t* cells49, uint8_t* patches, int32_t* ids,
+                                int32_t* nrot, int32_t* paths) {
+    if (!h || !gray || !quads_xy || !frame_of) return ARUCOHIP_E_INVALID;
+    int rc = check_geometry(h, nframes, W, H, row_stride);
+    if (rc) return rc;
+    if (nframes > h->cap_frames) return fail(h, ARUCOHIP_E_INVALID, "decode_quads: more frames than one worker of the handle holds");
+    if (row_stride > 4 * (size_t)h->lim.max_width) return fail(h, ARUCOHIP_E_INVALID, "row_stride beyond four times the handle's width");
+    if (h->params.decoder_kind == ARUCOHIP_DECODER_USER) return fail(h, ARUCOHIP_E_UNSUPPORTED, "decode_quads: the caller's decoder runs on the host");
+    const Buffers& b = h->buf;
+    if (n < 1) return fail(h, ARUCOHIP_E_INVALID, "decode_quads: n < 1");
+    if ((uint32_t)n > b.cap_flat) return fail(h, ARUCOHIP_E_CAPACITY, "decode_quads: more quads than the handle's flat candidate list holds");
+    std::vector<int32_t> per_frame((size_t)nframes, 0);
+    std::vector<uint32_t> list((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const int32_t f = frame_of[i];
+        if (f < 0 || f >= nframes) return fail(h, ARUCOHIP_E_INVALID, "decode_quads: frame index outside the call's frames");
+        if (per_frame[f] >= b.cap_cands) return fail(h, ARUCOHIP_E_CAPACITY, "decode_quads: more quads in a frame than candidates_per_frame");
+        list[i] = ((uint32_t)f << 16) | (uint32_t)per_frame[f]++;
+    }
+    DetectParams dp;
+    if ((rc = make_detect_params(h, W, H, &dp))) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::vector<Cand> v((size_t)nframes * b.cap_cands);
+    for (int i = 0; i < n; i++) {
+        Cand c{};
+        for (int k = 0; k < 4; k++) {
+            c.qx[k] = quads_xy[8 * i + 2 * k], c.qy[k] = quads_xy[8 * i + 2 * k + 1];
+            c.c[2 * k] = (float)c.qx[k], c.c[2 * k + 1] = (float)c.qy[k];
+        }
+        c.cdesc = 0, c.swapped = 0, c.id = -1, c.nrot = 0;
+        v[(size_t)(list[i] >> 16) * b.cap_cands + (list[i] & 0xFFFFu)] = c;
+    }
+    FrameGeom g{};
+    g.width = W, g.height = H, g.row_stride = row_stride, g.frame_stride = (size_t)H * row_stride;
+    const bool cells = decode_from_cells(g, nframes, dp);
+    const size_t npx = (size_t)dp.warp_size * dp.warp_size;
+    if (!cells) {
+        HIPCHK(h, h->patches.reserve((size_t)b.cap_flat * npx));
+        h->buf.patches = h->patches;
+    }
+    hipStream_t s = h->stream;
+    const size_t bytes = ((size_t)nframes * H - 1) * row_stride + (size_t)W;   // the last row need not be padded
+    HIPCHK(h, h->d_gray.reserve(bytes));
+    HIPCHK(h, hipMemcpyAsync(h->d_gray, gray, bytes, hipMemcpyHostToDevice, s));
+    const uint32_t n32 = (uint32_t)n;
+    HIPCHK(h, hipMemsetAsync(h->zero_block, 0, h->zero_words * sizeof(uint32_t), s));
+    HIPCHK(h, hipMemcpyAsync(b.cands, v.data(), v.size() * sizeof(Cand), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(b.ncands, per_frame.data(), per_frame.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(b.cand_list, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(b.counters + CNT_NCAND, &n32, sizeof(n32), hipMemcpyHostToDevice, s));
+    launch_stage_quads(s, b, n32, dp.warp_size);
+    launch_decode(s, h->d_gray, g, nframes, dp, b, false);
+    HIPCHK(h, hipGetLastError());
+    std::vector<uint8_t> cells64;
+    if (iM) HIPCHK(h, hipMemcpyAsync(iM, b.iM, (size_t)n * 9 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (hist) HIPCHK(h, hipMemcpyAsync(hist, b.hist, (size_t)n * 256 * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
+    if (thr) HIPCHK(h, hipMemcpyAsync(thr, b.othr, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (cells49 && cells) {
+        cells64.resize((size_t)n * 64);
+        HIPCHK(h, hipMemcpyAsync(cells64.data(), b.cells, cells64.size(), hipMemcpyDeviceToHost, s));
+    }
+    if (patches && !cells) HIPCHK(h, hipMemcpyAsync(patches, b.patches, (size_t)n * npx, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(v.data(), b.cands, v.size() * sizeof(Cand), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    h->last = Batch{};   // the lists no longer hold a batch
+    h->cells_valid = false;
+    for (size_t i = 0; i < cells64.size() / 64; i++)
+        for (int cy = 0; cy < 7; cy++)
+            for (int cx = 0; cx < 7; cx++) cells49[i * 49 + cy * 7 + cx] = cells64[i * 64 + cy * 8 + cx];
+    for (int i = 0; i < n; i++) {
+        const Cand& c = v[(size_t)(list[i] >> 16) * b.cap_cands + (list[i] & 0xFFFFu)];
+        if (ids) ids[i] = c.id;
+        if (nrot) nrot[i] = c.nrot;
+    }
+    if (paths) *paths = cells ? 1 : 2;
+    return ARUCOHIP_OK;
+}
+
 int arucohip_board_detect_batch(arucohip_handle* h, int nframes, const int32_t* ids, const float* obj, int nboard, int info_type, const float* K,
                                 const float* dist, int ndist, float marker_size, float repj_err_thres, int y_perp, arucohip_board_t* out, float* prob) {
     if (!h || !out || !prob) return ARUCOHIP_E_INVALID;

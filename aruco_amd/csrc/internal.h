@@ -257,6 +257,8 @@ void launch_lift(hipStream_t s, int nframes, const DetectParams& p, const Buffer
 // a kernel of its own; never together with decode_from_cells
 bool decode_from_cells(const FrameGeom& g, int nframes, const DetectParams& p);
 void launch_decode(hipStream_t s, const uint8_t* gray, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b, bool fused_cells = false);
+// test hook: the inverse homographies (b.iM) of the first n entries of the flat candidate list, from the candidates' integer corners
+void launch_stage_quads(hipStream_t s, const Buffers& b, uint32_t n, int ws);
 void launch_set_decoded(hipStream_t s, const Buffers& b, uint32_t n, const int2* id_nrot_dev);
 void launch_refine_lines(hipStream_t s, const FrameGeom& g, int nframes, const DetectParams& p, const CamModel& cam, const Buffers& b, bool fused_cells = false);
 void launch_locked_corners(hipStream_t s, const uint8_t* gray, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b);

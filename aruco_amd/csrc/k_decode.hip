@@ -525,6 +525,28 @@ void launch_decode(hipStream_t s, const uint8_t* gray, const FrameGeom& g, int n
     }   // else: refine_lines_kernel decodes the cells of a candidate before it refines it (launch_refine_lines)
 }
 
+// Test hook (arucohip_debug_decode_quads): the inverse homographies of n caller-made candidates of the flat list, one candidate per lane and
+// HOMOGRAPHY_GROUP lanes at a time, as the tail of frame_candidates_kernel solves them - the same homography_lane on the same LaneMat. It is the
+// batch layout whatever the frame count: for one or two frames the pipeline solves all 64 lanes at once (frame_candidates_kernel<64>, LaneMatT<64>),
+// which places the systems differently in LDS and performs the same operations in the same order, so the bits are those of this kernel.
+__global__ __launch_bounds__(64) void stage_quads_kernel(const Cand* cands, int cap_cands, const uint32_t* cand_list, uint32_t n, int ws, double* iM) {
+    __shared__ double s_big[HOMOGRAPHY_LDS_DOUBLES];
+    const int lane = threadIdx.x;
+    const uint32_t k = blockIdx.x * WAVE + lane;
+    int16_t qx[4] = {0, 0, 0, 0}, qy[4] = {0, 0, 0, 0};
+    if (k < n) {
+        const uint32_t e = cand_list[k];
+        const Cand* c = cands + (size_t)(e >> 16) * cap_cands + (e & 0xFFFFu);
+        for (int i = 0; i < 4; i++) qx[i] = c->qx[i], qy[i] = c->qy[i];
+    }
+    const LaneMat A{s_big, lane}, b{s_big + 64 * HOMOGRAPHY_GROUP, lane};
+    for (int g = 0; g < WAVE / HOMOGRAPHY_GROUP; g++)   // one group of lanes at a time: they share the LDS the systems sit in
+        if (lane / HOMOGRAPHY_GROUP == g && k < n) homography_lane(qx, qy, ws, A, b, iM + (size_t)k * 9);
+}
+void launch_stage_quads(hipStream_t s, const Buffers& b, uint32_t n, int ws) {
+    if (n) hipLaunchKernelGGL(stage_quads_kernel, dim3((n + WAVE - 1) / WAVE), dim3(64), 0, s, b.cands, b.cap_cands, b.cand_list, n, ws, b.iM);
+}
+
 // ids / rotations a host decoder returned for the first n entries of the flat candidate list
 __global__ void set_decoded_kernel(Cand* cands, int cap_cands, const uint32_t* cand_list, uint32_t n, const int2* dec) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -395,6 +395,21 @@ int arucohip_debug_counters(arucohip_handle* h, uint32_t* out8);
 int arucohip_debug_refine_pixels(arucohip_handle* h, const uint8_t* gray, int width, int height, size_t row_stride, float* corners_xy,
                                  int ncorners, int method, int win, int locked_wsize);
 
+/* Test hook: the decode stage (inverse homography, warp + histogram, Otsu threshold, cell votes, id and rotation) on quads of the caller's.
+ * gray: nframes host frames [nframes][height][row_stride] (the stride is kept on the device, at most four times the handle's width; nframes at most
+ * the handle's max_batch); quads_xy: n quads of four integer corners x0,y0 .. x3,y3, as detectRectangles leaves them (any values an int16 holds,
+ * outside the frame included); frame_of: the frame each quad is warped from. The handle's current parameters (warp_size, decoder_kind, dictionary)
+ * and nframes choose the kernels exactly as a batch of nframes frames would: one or two frames store the patch, three or more with the built-in 5x5
+ * decoder and warp_size 56 keep the cell medians instead. Outputs, each optional, in the order of the quads: iM [n][9] inverse homographies,
+ * hist [n][256], thr [n] Otsu thresholds, cells49 [n][49] (written when *paths & 1: the cell medians were kept), patches [n][warp_size^2] (written
+ * when *paths & 2: the patches were stored), ids / nrot [n] (id -1: not a marker). n is 1..the flat candidate list (max_batch * min(candidates_per_frame,
+ * 96)) and at most candidates_per_frame quads per frame: ARUCOHIP_E_CAPACITY beyond; a frame index outside the call: ARUCOHIP_E_INVALID; the
+ * caller's decoder (ARUCOHIP_DECODER_USER): ARUCOHIP_E_UNSUPPORTED. Everything is checked before anything runs. Uses the handle's candidate
+ * lists: results of the last batch are gone afterwards. */
+int arucohip_debug_decode_quads(arucohip_handle* h, const uint8_t* gray, int nframes, int width, int height, size_t row_stride,
+                                const int16_t* quads_xy, const int32_t* frame_of, int n, double* iM, uint16_t* hist, int32_t* thr, uint8_t* cells49,
+                                uint8_t* patches, int32_t* ids, int32_t* nrot, int32_t* paths);
+
 /* glibc's rand() outputs [offset, offset + count) after srand(seed), as the device makes them for arucohip_hrm_create_dictionary
  * (jump-ahead of the stream's state). count <= 2^24, offset + count < 2^48. */
 int arucohip_debug_hrm_stream(arucohip_handle* h, uint32_t seed, uint64_t offset, int count, uint32_t* out);

@@ -223,6 +223,16 @@ def hrm_codes(markers):
     return [sum(1 << i for i, ch in enumerate(m) if ch == "1") for m in markers]
 
 
+def hrm_detect(patch, n, codes, tau0, rate=1.0):
+    """HighlyReliableMarkers::detect on one canonical patch: (position in the dictionary or -1, nRotations). codes: as hrm_codes() gives them."""
+    p, pp = _u8(patch)
+    codes = [int(c) for c in codes]
+    arr = (C.c_uint64 * len(codes))(*codes)
+    nrot = C.c_int(0)
+    mid = lib().orc_hrm_detect(pp, p.shape[0], n, len(codes), arr, int(tau0), C.c_float(rate), C.byref(nrot))
+    return mid, nrot.value
+
+
 def bgr2gray(bgr):
     """cv::cvtColor(BGR2GRAY) for 8-bit data (orc_imgproc.cpp; call site src/markerdetector.cpp:307-310)."""
     b = np.ascontiguousarray(bgr, dtype=np.uint8)

@@ -164,6 +164,14 @@ int orc_fiducial_detect(const uint8_t* patch, int size, int* nrot) {
     std::vector<uint8_t> p(patch, patch + size * size);
     return fiducial_detect(p.data(), size, nrot);
 }
+// HighlyReliableMarkers::detect on one canonical patch with a dictionary of the caller's (what Detector::detect runs per candidate)
+int orc_hrm_detect(const uint8_t* patch, int size, int n, int count, const uint64_t* codes, int tau0, float rate, int* nrot) {
+    HrmDict d;
+    d.n = n, d.tau0 = tau0, d.rate = rate;
+    d.codes.assign(codes, codes + (count > 0 ? count : 0));
+    std::vector<uint8_t> p(patch, patch + size * size);
+    return hrm_detect(p.data(), size, d, nrot);
+}
 int orc_solve_pnp(const float* obj_xyz, const float* img_xy, int n, const float* K, const float* dist, int ndist,
                   double* rvec, double* tvec) {
     std::vector<Pt3f> o(n);
