@@ -18,20 +18,6 @@ struct BoardLds {
     int npts, nmark, n2;
 };
 
-struct BoardDef {
-    const int32_t* ids;
-    const float* obj;      // nboard * 4 * 3
-    int nboard, info_type;
-    float marker_size, repj_thres;
-};
-
-// metres per unit of the board's object points: PIX boards are scaled by the marker side taken from the first edge of marker 0
-__device__ __forceinline__ double board_mpp(const BoardDef& bd) {
-    const float dx = bd.obj[0] - bd.obj[3], dy = bd.obj[1] - bd.obj[4], dz = bd.obj[2] - bd.obj[5];
-    const double side = sqrt((double)dx * dx + (double)dy * dy + (double)dz * dz);
-    return bd.info_type == ARUCOHIP_BOARD_PIX ? (double)bd.marker_size / side : 1.0;
-}
-
 // All 64 lanes call it. M[0 .. nm): the frame's markers. Returns BOARD_NOT_TRIED without K, without a member marker or on a PIX board
 // without a marker size, else whether the solve gave a pose; r / t hold what the solver left, BEFORE rotateXAxis (on every lane),
 // *nk_out the member markers found.

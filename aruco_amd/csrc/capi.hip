@@ -539,16 +539,8 @@ static int make_detect_params(arucohip_handle* h, int W, int H, DetectParams* dp
 }
 
 static int make_cam(arucohip_handle* h, const float* K, const float* dist, int ndist, float marker_size, int y_perp, CamModel* cam) {
-    std::memset(cam, 0, sizeof(*cam));
     if (ndist < 0 || ndist > 8) return fail(h, ARUCOHIP_E_INVALID, "ndist must be 0..8");
-    cam->has_K = K != nullptr;
-    if (K)
-        for (int i = 0; i < 9; i++) cam->K[i] = K[i];
-    cam->has_dist = dist != nullptr && ndist > 0;
-    if (cam->has_dist)
-        for (int i = 0; i < ndist; i++) cam->k[i] = (double)dist[i];
-    cam->marker_size = marker_size;
-    cam->y_perp = y_perp;
+    fill_cam(cam, K, dist, ndist, marker_size, y_perp);
     return ARUCOHIP_OK;
 }
 
@@ -878,21 +870,12 @@ static int chunk_enqueue(arucohip_handle* w, const uint8_t* frames, int nframes,
     return ARUCOHIP_OK;
 }
 
-// after the worker's stream has drained: copy the chunk's markers from the pinned staging to the caller's arrays
-static int chunk_collect_host(arucohip_handle* h, arucohip_handle* w, int nframes, arucohip_marker_t* out, int cap, int32_t* n_out) {
-    int ret = check_status(h, w->h_counters[CNT_STATUS] & ~(uint32_t)ST_MARKER_OVERFLOW);
-    const Buffers& b = w->buf;
-    for (int f = 0; f < nframes; f++) {
-        int n = w->h_n[f];
-        n_out[f] = n;
-        if (n > cap) {
-            if (ret == ARUCOHIP_OK) ret = fail(h, ARUCOHIP_E_CAPACITY, "marker output array too small");
-            n = cap;
-        }
-        n = std::min(n, b.cap_markers);
-        if (n > 0) std::memcpy(out + (size_t)f * cap, w->h_markers + (size_t)f * b.cap_markers, (size_t)n * sizeof(arucohip_marker_t));
-    }
-    return ret;
+// after the worker's stream has drained: copy the chunk's markers from the pinned staging to the caller's arrays; a device list that
+// overflowed is reported ahead of an output array that is too small
+static int chunk_collect_host(arucohip_handle* h, const Span& s, arucohip_marker_t* out, int cap, int32_t* n_out) {
+    const int fits = collect_markers(h, s, cap, out, n_out, s.w->h_markers, s.w->h_n);
+    const int st = check_status(h, s.w->h_counters[CNT_STATUS] & ~(uint32_t)ST_MARKER_OVERFLOW);
+    return st ? st : fits;
 }
 
 int fork_workers(arucohip_handle* h, const Batch& b) {
@@ -916,7 +899,7 @@ static int collect_batch_host(arucohip_handle* h, arucohip_marker_t* out, int ca
     HIPCHK(h, hipStreamSynchronize(h->stream));
     int ret = ARUCOHIP_OK;
     for (const Span& s : h->last) {
-        int r = chunk_collect_host(h, s.w, s.count, out + (size_t)s.first * cap, cap, n_out + s.first);
+        int r = chunk_collect_host(h, s, out, cap, n_out);
         if (ret == ARUCOHIP_OK) ret = r;
     }
     return ret;
@@ -1745,23 +1728,22 @@ int arucohip_board_detect_batch(arucohip_handle* h, int nframes, const int32_t* 
     CamModel cam;
     int rc = make_cam(h, K, dist, ndist, marker_size, y_perp, &cam);
     if (rc) return rc;
+    const BoardDef board{ids, obj, nboard, info_type, marker_size, repj_err_thres};
     // every worker solves the boards of the frames it detected, on its own stream
     const Batch b = h->last.cut(nframes);
-    if ((rc = fork_workers(h, b))) return rc;
-    for (const Span& s : b) {
+    rc = on_workers(h, b, [&](const Span& s) -> int {
         arucohip_handle* w = s.w;
         HIPCHK(h, w->d_board.reserve((size_t)w->cap_frames * (sizeof(arucohip_board_t) + sizeof(float)) + 8192 * sizeof(int32_t)));
         arucohip_board_t* d_out = w->d_board;
         float* d_prob = (float*)(d_out + w->cap_frames);
-        int32_t* d_ids = (int32_t*)(d_prob + w->cap_frames);
-        HIPCHK(h, hipMemcpyAsync(d_ids, ids, (size_t)nboard * sizeof(int32_t), hipMemcpyHostToDevice, w->stream));
-        HIPCHK(h, hipMemcpyAsync(w->d_small_f, obj, (size_t)nboard * 12 * sizeof(float), hipMemcpyHostToDevice, w->stream));
-        launch_board_pose(w->stream, s.count, w->buf, d_ids, w->d_small_f, nboard, info_type, marker_size, repj_err_thres, cam, d_out, d_prob);
-        HIPCHK(h, hipGetLastError());
+        BoardDef bd;
+        if (const int r = upload_board(h, board, w->stream, (int32_t*)(d_prob + w->cap_frames), w->d_small_f, &bd)) return r;
+        launch_board_pose(w->stream, s.count, w->buf, bd, cam, d_out, d_prob);
         HIPCHK(h, hipMemcpyAsync(out + s.first, d_out, (size_t)s.count * sizeof(arucohip_board_t), hipMemcpyDeviceToHost, w->stream));
         HIPCHK(h, hipMemcpyAsync(prob + s.first, d_prob, (size_t)s.count * sizeof(float), hipMemcpyDeviceToHost, w->stream));
-    }
-    if ((rc = join_workers(h, b))) return rc;
+        return ARUCOHIP_OK;
+    });
+    if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(b.span[0].w->stream));
     // a frame with more member markers than the kernel's correspondence array holds is reported, not truncated silently
     for (const Span& s : h->last) {
@@ -1819,16 +1801,11 @@ int arucohip_board_detect(arucohip_handle* h, const arucohip_marker_t* markers, 
     if (nboard <= 0 || !ids || !obj) return fail(h, ARUCOHIP_E_BOARD_CONFIG, "invalid BoardConfig that is empty");
     std::memset(out, 0, sizeof(*out));
     *prob = 0;
-    auto onorm = [&](int a, int b) {
-        // Point3f difference in float, cv::norm in double
-        float dx = obj[3 * a] - obj[3 * b], dy = obj[3 * a + 1] - obj[3 * b + 1], dz = obj[3 * a + 2] - obj[3 * b + 2];
-        return std::sqrt((double)dx * dx + (double)dy * dy + (double)dz * dz);
-    };
     float ssize = -1;
     if (info_type == ARUCOHIP_BOARD_PIX && marker_size > 0)
         ssize = marker_size;
     else if (info_type == ARUCOHIP_BOARD_METERS)
-        ssize = (float)onorm(0, 1);
+        ssize = (float)board_side(obj);
     std::vector<int> slot;
     int nb = 0;
     for (int i = 0; i < n; i++) {
@@ -1843,7 +1820,7 @@ int arucohip_board_detect(arucohip_handle* h, const arucohip_marker_t* markers, 
     if (nb == 0 || !K) return ARUCOHIP_OK;
     bool enough = (marker_size > 0 && info_type == ARUCOHIP_BOARD_PIX) || info_type == ARUCOHIP_BOARD_METERS;
     if (!enough) return ARUCOHIP_OK;
-    double mpp = info_type == ARUCOHIP_BOARD_PIX ? marker_size / onorm(0, 1) : 1;
+    const double mpp = board_mpp(BoardDef{ids, obj, nboard, info_type, marker_size, repj_err_thres});
     std::vector<float> o3, i2;
     for (int i = 0; i < nb; i++)
         for (int p = 0; p < 4; p++) {

@@ -98,26 +98,24 @@ int calib_views_of_points(arucohip_handle* h, const float* obj, const float* img
 
 // the board detections of the last batch's first nframes frames as views, where they are: *owner is the worker of the batch's first chunk,
 // in whose scratch and on whose stream the calibration then runs
-int calib_views_of_batch(arucohip_handle* h, int nframes, const int32_t* ids, const float* obj, int nboard, int info_type, float marker_size,
-                         int min_markers, int32_t* used, arucohip_handle** owner, CalibViews* v) {
-    if (nboard <= 0 || !ids || !obj) return fail(h, ARUCOHIP_E_BOARD_CONFIG, "invalid BoardConfig that is empty");
+int calib_views_of_batch(arucohip_handle* h, int nframes, const BoardDef& board, int min_markers, int32_t* used, arucohip_handle** owner,
+                         CalibViews* v) {
+    const int nboard = board.nboard;
+    if (nboard <= 0 || !board.ids || !board.obj) return fail(h, ARUCOHIP_E_BOARD_CONFIG, "invalid BoardConfig that is empty");
     if (nframes < 1 || nframes > h->last.frames) return fail(h, ARUCOHIP_E_INVALID, "nframes exceeds the last batch");
     HIPCHK(h, hipSetDevice(h->device));
     const Batch b = h->last.cut(nframes);
     arucohip_handle* o = b.span[0].w;
     *owner = o;
-    // the metres-per-unit factor of board_pose_kernel for PIX boards (marker side from the first edge of marker 0)
-    const float dx = obj[0] - obj[3], dy = obj[1] - obj[4], dz = obj[2] - obj[5];
-    const double side = std::sqrt((double)dx * dx + (double)dy * dy + (double)dz * dz);
-    const double mpp = (info_type == ARUCOHIP_BOARD_PIX && marker_size > 0) ? (double)marker_size / side : 1.0;
+    const double mpp = board_mpp(board);   // board_pose_kernel's scale
     const size_t npts = (size_t)nframes * CALIB_MAX_POINTS;
     HIPCHK(h, o->d_calib.reserve(calib_layout(*v, nullptr, nframes, npts, nframes, nboard)));
     calib_layout(*v, o->d_calib, nframes, npts, nframes, nboard);
-    HIPCHK(h, hipMemcpyAsync(v->bids, ids, (size_t)nboard * sizeof(int32_t), hipMemcpyHostToDevice, o->stream));
-    HIPCHK(h, hipMemcpyAsync(v->bobj, obj, (size_t)nboard * 12 * sizeof(float), hipMemcpyHostToDevice, o->stream));
+    BoardDef bd;
+    if (const int e = upload_board(h, board, o->stream, v->bids, v->bobj, &bd)) return e;
     // every worker lays out the correspondences of the frames it detected, on its own stream
     const int rc = on_workers(h, b, [&](const Span& s) {
-        launch_calib_gather(s.w->stream, s.count, s.w->buf, v->bids, v->bobj, nboard, mpp, s.first, v->obj, v->img, v->npt_dev, v->nmark);
+        launch_calib_gather(s.w->stream, s.count, s.w->buf, bd, mpp, s.first, v->obj, v->img, v->npt_dev, v->nmark);
         return 0;
     });
     if (rc) return rc;
@@ -232,7 +230,7 @@ int arucohip_calibrate_board_batch(arucohip_handle* h, int nframes, const int32_
     if (!K || !dist || W <= 0 || H <= 0) return fail(h, ARUCOHIP_E_INVALID, "calibrate_board_batch: NULL K / dist or an empty image size");
     CalibViews v;
     arucohip_handle* o = nullptr;
-    int rc = calib_views_of_batch(h, nframes, ids, obj, nboard, info_type, marker_size, min_markers, used, &o, &v);
+    int rc = calib_views_of_batch(h, nframes, BoardDef{ids, obj, nboard, info_type, marker_size, -1.f}, min_markers, used, &o, &v);
     if (rc) return rc;
     rc = calib_pinhole(o, v, W, H, flags, K, dist, rvecs, tvecs, nullptr, rms);
     if (rc && o != h) h->err = o->err;

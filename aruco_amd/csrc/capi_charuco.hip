@@ -154,14 +154,12 @@ int arucohip_charuco_corners_batch(arucohip_handle* h, const arucohip_charuco_t*
         gray = h->d_charuco_frames, a.row_stride = W, a.frame_stride = px;
     }
     // every worker interpolates the corners of the frames it detected, on its own stream
-    int rc;
-    if ((rc = fork_workers(h, b))) return rc;
-    for (const Span& s : b) {
+    const int rc = on_workers(h, b, [&](const Span& s) {
         a.gray = gray + (size_t)s.first * a.frame_stride;
         launch_charuco_corners(s.w->stream, s.count, s.w->buf, a, d_rec + (size_t)s.first * p.corners, d_nf + s.first);
-        HIPCHK(h, hipGetLastError());
-    }
-    if ((rc = join_workers(h, b))) return rc;
+        return 0;
+    });
+    if (rc) return rc;
     h->charuco.n_found.assign((size_t)nframes, 0);
     HIPCHK(h, hipMemcpyAsync(h->charuco.n_found.data(), d_nf, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, s0));
     HIPCHK(h, hipMemcpyAsync(out, d_rec, (size_t)nframes * p.corners * sizeof(arucohip_charuco_corner_t),
@@ -216,12 +214,7 @@ int arucohip_charuco_pose_batch(arucohip_handle* h, int nframes, const float* K,
     if (ndist > 0 && !dist) return fail(h, ARUCOHIP_E_INVALID, "charuco_pose_batch: dist is NULL with ndist > 0");
     if (nframes < 1 || nframes > h->charuco.frames) return fail(h, ARUCOHIP_E_INVALID, "charuco_pose_batch: nframes exceeds the last arucohip_charuco_corners_batch");
     CamModel cam;
-    std::memset(&cam, 0, sizeof(cam));
-    cam.has_K = K ? 1 : 0;
-    for (int i = 0; K && i < 9; i++) cam.K[i] = K[i];
-    cam.has_dist = K && ndist > 0;
-    for (int i = 0; cam.has_dist && i < ndist; i++) cam.k[i] = (double)dist[i];
-    cam.marker_size = square_size, cam.y_perp = y_perp;
+    fill_cam(&cam, K, dist, ndist, square_size, y_perp);
     HIPCHK(h, hipSetDevice(h->device));
     const arucohip_charuco_t L = h->charuco.layout;
     HIPCHK(h, h->d_charuco_work.reserve((size_t)nframes * sizeof(arucohip_board_t)));

@@ -129,7 +129,7 @@ int arucohip_fisheye_calibrate_board_batch(arucohip_handle* h, int nframes, cons
     if (h->last.ideal) return fail(h, ARUCOHIP_E_INVALID, "fisheye_calibrate_board_batch: the last batch holds ideal corners, not the lens's pixels");
     CalibViews v;
     arucohip_handle* o = nullptr;
-    int rc = calib_views_of_batch(h, nframes, ids, obj, nboard, info_type, marker_size, min_markers, used, &o, &v);
+    int rc = calib_views_of_batch(h, nframes, BoardDef{ids, obj, nboard, info_type, marker_size, -1.f}, min_markers, used, &o, &v);
     if (rc) return rc;
     rc = calib_fisheye(o, v, W, H, flags, model, rvecs, tvecs, nullptr, rms);
     if (rc && o != h) h->err = o->err;
@@ -215,53 +215,31 @@ int arucohip_fisheye_undistort_markers_batch(arucohip_handle* h, int nframes, co
 
     const Batch b = h->last.cut(nframes);
     std::vector<std::vector<arucohip_marker_t>> stage((size_t)b.nspan);
-    std::vector<int32_t> n_host;
-    if (out && !out_on_device) n_host.resize((size_t)nframes);
-    if ((rc = fork_workers(h, b))) return rc;
-    h->last.ideal = true;       // from here on a worker's lists may have changed, whatever happens to the rest of the call
-    h->last.board_frames = 0;   // board poses left on the device came from the distorted corners
-    for (int c = 0; c < b.nspan; c++) {
-        const Span& s = b.span[c];
+    std::vector<int32_t> n_host((size_t)nframes);
+    rc = on_workers(h, b, [&](const Span& s) -> int {
+        h->last.ideal = true;       // from the first span on a worker's lists may have changed, whatever happens to the rest of the call
+        h->last.board_frames = 0;   // board poses left on the device came from the distorted corners
         arucohip_handle* w = s.w;
-        const Buffers& wb = w->buf;
-        const int capM = wb.cap_markers;
         const size_t drop_bytes = ((size_t)w->cap_frames * sizeof(int32_t) + 255) & ~(size_t)255;
         HIPCHK(h, w->d_fisheye.reserve(drop_bytes + cam_bytes));
         int32_t* d_dropped = (int32_t*)w->d_fisheye.p;
         FisheyeCam* d_cams = (FisheyeCam*)(w->d_fisheye.p + drop_bytes);
         hipStream_t st = w->stream;
         HIPCHK(h, hipMemcpyAsync(d_cams, h->fisheye_cams.data(), cam_bytes, hipMemcpyHostToDevice, st));
-        launch_fisheye_markers(st, d_cams, nmodels, s.first, s.count, wb, d_dropped);
-        HIPCHK(h, hipGetLastError());
-        if (out && out_on_device) {
-            HIPCHK(h, hipMemcpy2DAsync(out + (size_t)s.first * cap, (size_t)cap * sizeof(arucohip_marker_t), wb.markers, (size_t)capM * sizeof(arucohip_marker_t),
-                                       (size_t)std::min(cap, capM) * sizeof(arucohip_marker_t), (size_t)s.count, hipMemcpyDeviceToDevice, st));
-            HIPCHK(h, hipMemcpyAsync(n_out + s.first, wb.nmarkers, (size_t)s.count * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        } else if (out) {
-            stage[c].resize((size_t)s.count * capM);
-            HIPCHK(h, hipMemcpyAsync(stage[c].data(), wb.markers, stage[c].size() * sizeof(arucohip_marker_t), hipMemcpyDeviceToHost, st));
-            HIPCHK(h, hipMemcpyAsync(n_host.data() + s.first, wb.nmarkers, (size_t)s.count * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        }
+        launch_fisheye_markers(st, d_cams, nmodels, s.first, s.count, w->buf, d_dropped);
+        if (out)
+            if (const int e = enqueue_markers(h, s, out, cap, n_out, out_on_device, &stage[b.index(s)], n_host.data() + s.first)) return e;
         if (dropped) HIPCHK(h, hipMemcpyAsync(dropped + s.first, d_dropped, (size_t)s.count * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    }
-    if ((rc = join_workers(h, b))) return rc;
+        return ARUCOHIP_OK;
+    });
+    if (rc) return rc;
     if (!wait) return ARUCOHIP_OK;
     HIPCHK(h, hipStreamSynchronize(b.span[0].w->stream));
     int ret = ARUCOHIP_OK;
     if (out && !out_on_device)
-        for (int c = 0; c < b.nspan; c++) {
-            const Span& s = b.span[c];
-            const int capM = s.w->buf.cap_markers;
-            for (int f = 0; f < s.count; f++) {
-                int n = n_host[s.first + f];
-                n_out[s.first + f] = n;
-                if (n > cap) {
-                    if (ret == ARUCOHIP_OK) ret = fail(h, ARUCOHIP_E_CAPACITY, "marker output array too small");
-                    n = cap;
-                }
-                n = std::min(n, capM);
-                if (n > 0) std::memcpy(out + (size_t)(s.first + f) * cap, stage[c].data() + (size_t)f * capM, (size_t)n * sizeof(arucohip_marker_t));
-            }
+        for (const Span& s : b) {
+            const int r = collect_markers(h, s, cap, out, n_out, stage[b.index(s)].data(), n_host.data() + s.first);
+            if (ret == ARUCOHIP_OK) ret = r;
         }
     return ret;
 }

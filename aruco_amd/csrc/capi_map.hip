@@ -53,12 +53,7 @@ static int map_args(arucohip_handle* h, int nframes, const int32_t* ids, int nbo
     if (nframes < 1) return fail(h, ARUCOHIP_E_INVALID, "board_map: no frames");
     if (!o.obj || !o.marker_rvec || !o.marker_tvec || !o.mapped) return fail(h, ARUCOHIP_E_INVALID, "board_map: NULL obj / marker_rvec / marker_tvec / mapped");
     if (nboard > MAP_MAX_MARKERS) return fail(h, ARUCOHIP_E_CAPACITY, "board_map: more than ARUCOHIP_MAP_MAX_MARKERS markers");
-    std::memset(cam, 0, sizeof(*cam));
-    cam->has_K = 1;
-    for (int i = 0; i < 9; i++) cam->K[i] = K[i];
-    cam->has_dist = ndist > 0;
-    for (int i = 0; i < ndist; i++) cam->k[i] = (double)dist[i];
-    cam->marker_size = marker_size;
+    fill_cam(cam, K, dist, ndist, marker_size, 0);
     return ARUCOHIP_OK;
 }
 

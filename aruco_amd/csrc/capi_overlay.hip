@@ -29,12 +29,7 @@ int check_camera(arucohip_handle* h, bool need_K, const float* K, const float* d
     if (need_K && !K) return fail(h, ARUCOHIP_E_INVALID, "draw: K is required for ARUCOHIP_DRAW_AXIS / ARUCOHIP_DRAW_CUBE");
     if (!(ndist == 0 || ndist == 4 || ndist == 5 || ndist == 8)) return fail(h, ARUCOHIP_E_INVALID, "ndist must be 0, 4, 5 or 8");
     if (ndist > 0 && !dist) return fail(h, ARUCOHIP_E_INVALID, "draw: dist is NULL with ndist > 0");
-    std::memset(cam, 0, sizeof(*cam));
-    if (!K) return ARUCOHIP_OK;
-    cam->has_K = 1;
-    for (int i = 0; i < 9; i++) cam->K[i] = K[i];
-    cam->has_dist = ndist > 0;
-    for (int i = 0; i < ndist; i++) cam->k[i] = (double)dist[i];
+    fill_cam(cam, K, dist, ndist, 0.f, 0);
     return ARUCOHIP_OK;
 }
 

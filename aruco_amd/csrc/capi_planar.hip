@@ -12,13 +12,7 @@ static int planar_cam(arucohip_handle* h, const float* K, const float* dist, int
     if (!(ndist == 0 || ndist == 4 || ndist == 5 || ndist == 8)) return fail(h, ARUCOHIP_E_INVALID, "ndist must be 0, 4, 5 or 8");
     if (ndist > 0 && !dist) return fail(h, ARUCOHIP_E_INVALID, "planar_poses: dist is NULL with ndist > 0");
     if (!(marker_size > 0)) return fail(h, ARUCOHIP_E_INVALID, "marker size must be positive");
-    std::memset(cam, 0, sizeof(*cam));
-    cam->has_K = 1;
-    for (int i = 0; i < 9; i++) cam->K[i] = K[i];
-    cam->has_dist = ndist > 0;
-    for (int i = 0; i < ndist; i++) cam->k[i] = (double)dist[i];
-    cam->marker_size = marker_size;
-    cam->y_perp = y_perp;
+    fill_cam(cam, K, dist, ndist, marker_size, y_perp);
     return ARUCOHIP_OK;
 }
 
@@ -75,23 +69,20 @@ int arucohip_planar_poses_batch(arucohip_handle* h, int nframes, const float* K,
     // every worker solves the markers of the frames it detected, on its own stream; host results go through the worker's d_planar
     std::vector<arucohip_planar_poses_t> stage;
     if (!out_on_device) stage.resize((size_t)nframes * cap);
-    if ((rc = fork_workers(h, b))) return rc;
-    for (int c = 0; c < b.nspan; c++) {
-        const Span& s = b.span[c];
+    rc = on_workers(h, b, [&](const Span& s) -> int {
         arucohip_handle* w = s.w;
-        const int list_frames = h->last.span[c].count;   // the worker's list holds the markers of every frame it detected
+        const int list_frames = h->last.span[b.index(s)].count;   // the worker's list holds the markers of every frame it detected
         if (out_on_device) {
             launch_planar_poses_list(w->stream, list_frames, s.count, s.first, w->buf, cam, refine, out, cap);
-            HIPCHK(h, hipGetLastError());
         } else {
             const size_t bytes = (size_t)s.count * cap * sizeof(arucohip_planar_poses_t);
             HIPCHK(h, w->d_planar.reserve(bytes));
             launch_planar_poses_list(w->stream, list_frames, s.count, 0, w->buf, cam, refine, (arucohip_planar_poses_t*)(uint8_t*)w->d_planar, cap);
-            HIPCHK(h, hipGetLastError());
             HIPCHK(h, hipMemcpyAsync(stage.data() + (size_t)s.first * cap, (uint8_t*)w->d_planar, bytes, hipMemcpyDeviceToHost, w->stream));
         }
-    }
-    if ((rc = join_workers(h, b))) return rc;
+        return ARUCOHIP_OK;
+    });
+    if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(b.span[0].w->stream));
     if (!out_on_device)
         for (int f = 0; f < nframes; f++)

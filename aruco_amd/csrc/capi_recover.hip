@@ -55,13 +55,10 @@ int arucohip_board_recover_batch(arucohip_handle* h, int nframes, const int32_t*
     HIPCHK(h, hipSetDevice(h->device));
     // cam: the refinement's and the markers' own poses; bcam: the board solves, which always carry a distortion vector (board_detect_batch)
     CamModel cam, bcam;
-    std::memset(&cam, 0, sizeof(cam));
-    cam.has_K = 1, cam.has_dist = dist != nullptr && ndist > 0, cam.marker_size = marker_size, cam.y_perp = y_perp;
-    for (int i = 0; i < 9; i++) cam.K[i] = K[i];
-    for (int i = 0; i < (cam.has_dist ? ndist : 0); i++) cam.k[i] = (double)dist[i];
+    fill_cam(&cam, K, dist, ndist, marker_size, y_perp);
     bcam = cam, bcam.has_dist = 1;
+    const BoardDef board{ids, obj, nboard, info_type, marker_size, repj_err_thres};
     RecoverArgs a;
-    a.nboard = nboard, a.info_type = info_type, a.marker_size = marker_size, a.repj_thres = repj_err_thres;
     a.max_corner_dist = o.max_corner_dist, a.max_cell_errors = o.max_cell_errors, a.min_markers = o.min_markers;
     a.ws = p.warp_size;
     int rect[4];
@@ -70,14 +67,11 @@ int arucohip_board_recover_batch(arucohip_handle* h, int nframes, const int32_t*
     const bool wait = !out_on_device || recovered || boards || prob;
 
     const Batch b = h->last.cut(nframes);
-    int rc;
     std::vector<std::vector<arucohip_marker_t>> stage((size_t)b.nspan);
     std::vector<uint32_t> status((size_t)b.nspan, 0u);
-    std::vector<int32_t> n_host;
-    if (out && !out_on_device) n_host.resize((size_t)nframes);
-    if ((rc = fork_workers(h, b))) return rc;
-    for (int c = 0; c < b.nspan; c++) {
-        const Span& s = b.span[c];
+    std::vector<int32_t> n_host((size_t)nframes);
+    const int rc = on_workers(h, b, [&](const Span& s) -> int {
+        const int c = b.index(s);
         arucohip_handle* w = s.w;
         const Buffers& wb = w->buf;
         const int capM = wb.cap_markers;
@@ -86,7 +80,6 @@ int arucohip_board_recover_batch(arucohip_handle* h, int nframes, const int32_t*
         float* dobj;
         HIPCHK(h, w->d_recover.reserve(recover_layout(r, &dids, &dobj, nullptr, w->cap_frames, capM, nboard)));
         recover_layout(r, &dids, &dobj, w->d_recover, w->cap_frames, capM, nboard);
-        a.ids = dids, a.obj = dobj;
         a.cells_valid = w->cells_valid ? 1 : 0;
         HIPCHK(h, w->d_board.reserve((size_t)w->cap_frames * (sizeof(arucohip_board_t) + sizeof(float)) + 8192 * sizeof(int32_t)));
         arucohip_board_t* d_boards = w->d_board;
@@ -94,50 +87,35 @@ int arucohip_board_recover_batch(arucohip_handle* h, int nframes, const int32_t*
         hipStream_t st = w->stream;
         HIPCHK(h, hipMemsetAsync(r.base, 0xFF, (size_t)w->cap_frames * sizeof(int32_t), st));
         HIPCHK(h, hipMemsetAsync(r.status, 0, sizeof(uint32_t), st));
-        HIPCHK(h, hipMemcpyAsync(dids, ids, (size_t)nboard * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipMemcpyAsync(dobj, obj, (size_t)nboard * 12 * sizeof(float), hipMemcpyHostToDevice, st));
+        if (const int e = upload_board(h, board, st, dids, dobj, &a.bd)) return e;
         launch_recover_match(st, h->last.span[c].count, s.count, wb, a, bcam, r);
         launch_refine_recovered(st, s.count, p.corner_method, cam, wb, r.rlist, r.nrec, capM);
         launch_recover_insert(st, s.count, wb, a, bcam, r, d_boards, d_prob);
         if (o.pose_markers) launch_pose_sparse(st, wb, r.plist, (uint32_t)s.count * (uint32_t)capM, cam);
-        HIPCHK(h, hipGetLastError());
-        if (out && out_on_device) {
-            HIPCHK(h, hipMemcpy2DAsync(out + (size_t)s.first * cap, (size_t)cap * sizeof(arucohip_marker_t), wb.markers, (size_t)capM * sizeof(arucohip_marker_t),
-                                       (size_t)std::min(cap, capM) * sizeof(arucohip_marker_t), (size_t)s.count, hipMemcpyDeviceToDevice, st));
-            HIPCHK(h, hipMemcpyAsync(n_out + s.first, wb.nmarkers, (size_t)s.count * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        } else if (out) {
-            stage[c].resize((size_t)s.count * capM);
-            HIPCHK(h, hipMemcpyAsync(stage[c].data(), wb.markers, stage[c].size() * sizeof(arucohip_marker_t), hipMemcpyDeviceToHost, st));
-            HIPCHK(h, hipMemcpyAsync(n_host.data() + s.first, wb.nmarkers, (size_t)s.count * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        }
+        if (out)
+            if (const int e = enqueue_markers(h, s, out, cap, n_out, out_on_device, &stage[c], n_host.data() + s.first)) return e;
         if (recovered) HIPCHK(h, hipMemcpyAsync(recovered + s.first, r.recovered, (size_t)s.count * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         if (boards) HIPCHK(h, hipMemcpyAsync(boards + s.first, d_boards, (size_t)s.count * sizeof(arucohip_board_t), hipMemcpyDeviceToHost, st));
         if (prob) HIPCHK(h, hipMemcpyAsync(prob + s.first, d_prob, (size_t)s.count * sizeof(float), hipMemcpyDeviceToHost, st));
         if (wait) HIPCHK(h, hipMemcpyAsync(&status[c], r.status, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    }
-    if ((rc = join_workers(h, b))) return rc;
+        return ARUCOHIP_OK;
+    });
+    if (rc) return rc;
     h->last.board_frames = nframes;
     if (!wait) return ARUCOHIP_OK;
     HIPCHK(h, hipStreamSynchronize(b.span[0].w->stream));
+    // the lists first: a board or a marker list that overflowed is reported ahead of an output array that is too small
     int ret = ARUCOHIP_OK;
+    if (out && !out_on_device)
+        for (int c = 0; c < b.nspan; c++) {
+            const int r = collect_markers(h, b.span[c], cap, out, n_out, stage[c].data(), n_host.data() + b.span[c].first);
+            if (ret == ARUCOHIP_OK) ret = r;
+        }
     for (int c = 0; c < b.nspan; c++) {
-        const Span& s = b.span[c];
-        arucohip_handle* w = s.w;
+        arucohip_handle* w = b.span[c].w;
         HIPCHK(h, hipMemcpy(w->h_counters, w->buf.counters, CNT_FIXED * sizeof(uint32_t), hipMemcpyDeviceToHost));
         if (w->h_counters[CNT_STATUS] & ST_MARKER_OVERFLOW) ret = fail(h, ARUCOHIP_E_CAPACITY, "a frame has more than 128 board markers");
         if (status[c] & 1u) ret = fail(h, ARUCOHIP_E_CAPACITY, "board_recover_batch: a frame's marker list is full (markers_per_frame)");
-        if (!out || out_on_device) continue;
-        const int capM = w->buf.cap_markers;
-        for (int f = 0; f < s.count; f++) {
-            int n = n_host[s.first + f];
-            n_out[s.first + f] = n;
-            if (n > cap) {
-                if (ret == ARUCOHIP_OK) ret = fail(h, ARUCOHIP_E_CAPACITY, "marker output array too small");
-                n = cap;
-            }
-            n = std::min(n, capM);
-            if (n > 0) std::memcpy(out + (size_t)(s.first + f) * cap, stage[c].data() + (size_t)f * capM, (size_t)n * sizeof(arucohip_marker_t));
-        }
     }
     return ret;
 }

@@ -23,7 +23,7 @@ struct RigStage {
 static size_t rig_layout(RigDev& d, RigStage& w, uint8_t* base, int T, int C, int nboard, size_t nobs) {
     Carver c{base};
     const size_t t = (size_t)T, nc = (size_t)C, V = t * nc, N = (size_t)6 * (C - 1), nb = (size_t)nboard;
-    d.st = c.take<RigState>(1), d.ids = w.ids = c.take<int32_t>(nb), d.bobj = w.bobj = c.take<float>(nb * 12);
+    d.st = c.take<RigState>(1), w.ids = c.take<int32_t>(nb), w.bobj = c.take<float>(nb * 12);
     d.cams = w.cams = c.take<RigCam>(nc);
     d.vn = c.take<int32_t>(V), d.vok = c.take<int32_t>(V), d.vact = c.take<int32_t>(V), d.vT = c.take<double>(V * 12);
     d.pobj = c.take<float>(V * RIG_VIEW_POINTS * 3), d.pimg = c.take<float>(V * RIG_VIEW_POINTS * 2);
@@ -46,15 +46,8 @@ static int rig_reserve(arucohip_handle* h, arucohip_handle* o, RigDev& d, RigSta
 }
 
 // the board and the cameras of a call, checked before anything runs
-struct RigBoard {
-    const int32_t* ids;
-    const float* obj;
-    int nboard, info_type;
-    float marker_size;
-    int min_markers;
-};
-
-static int rig_args(arucohip_handle* h, const char* who, int ninstants, const arucohip_rig_camera_t* cams, int ncams, const RigBoard& b, std::vector<RigCam>* rc) {
+static int rig_args(arucohip_handle* h, const char* who, int ninstants, const arucohip_rig_camera_t* cams, int ncams, const BoardDef& b, int min_markers,
+                    std::vector<RigCam>* rc) {
     char msg[160];
     auto bad = [&](int code, const char* what) {
         std::snprintf(msg, sizeof(msg), "%s: %s", who, what);
@@ -65,7 +58,7 @@ static int rig_args(arucohip_handle* h, const char* who, int ninstants, const ar
     if (!b.ids || !b.obj || b.nboard < 1) return bad(ARUCOHIP_E_INVALID, "NULL or empty board");
     if (b.info_type != ARUCOHIP_BOARD_PIX && b.info_type != ARUCOHIP_BOARD_METERS) return bad(ARUCOHIP_E_INVALID, "the board is neither PIX nor METERS");
     if (b.info_type == ARUCOHIP_BOARD_PIX && !(b.marker_size > 0)) return bad(ARUCOHIP_E_INVALID, "a PIX board needs a marker size");
-    if (b.min_markers < 1) return bad(ARUCOHIP_E_INVALID, "min_markers must be at least 1");
+    if (min_markers < 1) return bad(ARUCOHIP_E_INVALID, "min_markers must be at least 1");
     if (ncams > RIG_MAX_CAMERAS) return bad(ARUCOHIP_E_CAPACITY, "more than ARUCOHIP_RIG_MAX_CAMERAS cameras");
     if (b.nboard > RIG_MAX_BOARD) return bad(ARUCOHIP_E_CAPACITY, "more than 128 board markers");
     for (int c = 0; c < ncams; c++)
@@ -73,10 +66,7 @@ static int rig_args(arucohip_handle* h, const char* who, int ninstants, const ar
     rc->assign((size_t)ncams, RigCam{});
     for (int c = 0; c < ncams; c++) {
         RigCam& r = (*rc)[c];
-        r.cam.has_K = 1, r.cam.has_dist = cams[c].ndist > 0;
-        for (int i = 0; i < 9; i++) r.cam.K[i] = cams[c].K[i];
-        for (int i = 0; i < cams[c].ndist; i++) r.cam.k[i] = (double)cams[c].dist[i];
-        r.cam.marker_size = b.marker_size;
+        fill_cam(&r.cam, cams[c].K, cams[c].dist, cams[c].ndist, b.marker_size, 0);
         intr9(r.cam.K, r.cam.k, r.in);
     }
     return ARUCOHIP_OK;
@@ -94,13 +84,12 @@ struct RigObs {
 // d, bound in o's d_rig, gets the call's numbers and observations, and the board and the cameras go up on o's stream; the solve then
 // starts with the view kernel. A rig pose passes the caller's camera transforms (pose_cams), which go up with the rest, so that nothing
 // waits between the view kernel and the pose kernel; a calibration passes null and computes them.
-static int rig_begin(arucohip_handle* o, RigDev& d, const RigStage& w, int ninstants, int ncams, const RigBoard& b, const std::vector<RigCam>& rc,
-                     const RigObs& obs, const arucohip_rig_camera_t* pose_cams) {
+static int rig_begin(arucohip_handle* o, RigDev& d, const RigStage& w, int ninstants, int ncams, const BoardDef& b, int min_markers,
+                     const std::vector<RigCam>& rc, const RigObs& obs, const arucohip_rig_camera_t* pose_cams) {
     hipStream_t s = o->stream;
-    d.ncams = ncams, d.ninstants = ninstants, d.nboard = b.nboard, d.min_markers = b.min_markers, d.info_type = b.info_type, d.marker_size = b.marker_size;
+    d.ncams = ncams, d.ninstants = ninstants, d.min_markers = min_markers;
     d.obs_view = obs.view, d.obs_id = obs.id, d.obs_corners = obs.corners, d.obs_cnt = obs.cnt, d.nobs = obs.nobs, d.obs_stride = obs.stride;
-    HIPCHK(o, hipMemcpyAsync(w.ids, b.ids, (size_t)b.nboard * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(o, hipMemcpyAsync(w.bobj, b.obj, (size_t)b.nboard * 12 * sizeof(float), hipMemcpyHostToDevice, s));
+    if (const int e = upload_board(o, b, s, w.ids, w.bobj, &d.bd)) return e;
     HIPCHK(o, hipMemcpyAsync(w.cams, rc.data(), rc.size() * sizeof(RigCam), hipMemcpyHostToDevice, s));
     std::vector<double> cpose;
     std::vector<int32_t> calibrated;
@@ -225,9 +214,9 @@ int arucohip_rig_calibrate(arucohip_handle* h, const int32_t* obs_view, const in
                            float marker_size, int min_markers, int32_t* used, double* board_rvec, double* board_tvec, double* camera_rms, double* rms,
                            int32_t* iterations) {
     if (!h) return ARUCOHIP_E_INVALID;
-    const RigBoard b{ids, obj, nboard, info_type, marker_size, min_markers};
+    const BoardDef b{ids, obj, nboard, info_type, marker_size, -1.f};
     std::vector<RigCam> rc;
-    int r = rig_args(h, "rig_calibrate", ninstants, cams, ncams, b, &rc);
+    int r = rig_args(h, "rig_calibrate", ninstants, cams, ncams, b, min_markers, &rc);
     if (r) return r;
     if (!rig_obs_ok(obs_view, obs_id, obs_corners, nobs)) return fail(h, ARUCOHIP_E_INVALID, "rig_calibrate: NULL observations or a negative count");
     HIPCHK(h, hipSetDevice(h->device));
@@ -236,7 +225,7 @@ int arucohip_rig_calibrate(arucohip_handle* h, const int32_t* obs_view, const in
     if ((r = rig_reserve(h, h, d, w, ninstants, ncams, nboard, on_device ? 0 : (size_t)nobs))) return r;
     RigObs obs;
     if ((r = rig_stage(h, w, obs_view, obs_id, obs_corners, nobs, on_device, &obs))) return r;
-    if ((r = rig_begin(h, d, w, ninstants, ncams, b, rc, obs, nullptr))) return r;
+    if ((r = rig_begin(h, d, w, ninstants, ncams, b, min_markers, rc, obs, nullptr))) return r;
     return rig_calibrate_solve(h, d, cams, RigCalibOut{used, board_rvec, board_tvec, camera_rms, rms, iterations});
 }
 
@@ -244,9 +233,9 @@ int arucohip_rig_pose(arucohip_handle* h, const int32_t* obs_view, const int32_t
                       const arucohip_rig_camera_t* cams, int ncams, const int32_t* ids, const float* obj, int nboard, int info_type, float marker_size,
                       int min_markers, arucohip_board_t* out, int32_t* views_used) {
     if (!h) return ARUCOHIP_E_INVALID;
-    const RigBoard b{ids, obj, nboard, info_type, marker_size, min_markers};
+    const BoardDef b{ids, obj, nboard, info_type, marker_size, -1.f};
     std::vector<RigCam> rc;
-    int r = rig_args(h, "rig_pose", ninstants, cams, ncams, b, &rc);
+    int r = rig_args(h, "rig_pose", ninstants, cams, ncams, b, min_markers, &rc);
     if (r) return r;
     if ((r = rig_pose_args(h, "rig_pose", cams, ncams, out))) return r;
     if (!rig_obs_ok(obs_view, obs_id, obs_corners, nobs)) return fail(h, ARUCOHIP_E_INVALID, "rig_pose: NULL observations or a negative count");
@@ -256,15 +245,15 @@ int arucohip_rig_pose(arucohip_handle* h, const int32_t* obs_view, const int32_t
     if ((r = rig_reserve(h, h, d, w, ninstants, ncams, nboard, on_device ? 0 : (size_t)nobs))) return r;
     RigObs obs;
     if ((r = rig_stage(h, w, obs_view, obs_id, obs_corners, nobs, on_device, &obs))) return r;
-    if ((r = rig_begin(h, d, w, ninstants, ncams, b, rc, obs, cams))) return r;
+    if ((r = rig_begin(h, d, w, ninstants, ncams, b, min_markers, rc, obs, cams))) return r;
     return rig_pose_solve(h, d, out, views_used);
 }
 
 // the batch forms: frame f of the last batch is view f
-static int rig_batch(arucohip_handle* h, const char* who, int nframes, arucohip_rig_camera_t* cams, int ncams, const RigBoard& b, const RigCalibOut* calib,
-                     arucohip_board_t* out, int32_t* views_used) {
+static int rig_batch(arucohip_handle* h, const char* who, int nframes, arucohip_rig_camera_t* cams, int ncams, const BoardDef& b, int min_markers,
+                     const RigCalibOut* calib, arucohip_board_t* out, int32_t* views_used) {
     std::vector<RigCam> rc;
-    int r = rig_args(h, who, nframes, cams, ncams, b, &rc);
+    int r = rig_args(h, who, nframes, cams, ncams, b, min_markers, &rc);
     if (r) return r;
     if (!calib && (r = rig_pose_args(h, who, cams, ncams, out))) return r;
     if (nframes % ncams != 0) return fail(h, ARUCOHIP_E_INVALID, "the frames are not whole instants: nframes is no multiple of ncams");
@@ -280,7 +269,7 @@ static int rig_batch(arucohip_handle* h, const char* who, int nframes, arucohip_
     if ((r = rig_reserve(h, o, d, w, ninstants, ncams, b.nboard, (size_t)nframes * stride))) return r;
     RigObs obs;
     if ((r = rig_gather(h, batch, w, nframes, stride, &obs))) return r;
-    r = rig_begin(o, d, w, ninstants, ncams, b, rc, obs, calib ? nullptr : cams);
+    r = rig_begin(o, d, w, ninstants, ncams, b, min_markers, rc, obs, calib ? nullptr : cams);
     if (!r) r = calib ? rig_calibrate_solve(o, d, cams, *calib) : rig_pose_solve(o, d, out, views_used);
     if (r && o != h) h->err = o->err;
     return r;
@@ -291,14 +280,14 @@ int arucohip_rig_calibrate_batch(arucohip_handle* h, int nframes, arucohip_rig_c
                                  double* camera_rms, double* rms, int32_t* iterations) {
     if (!h) return ARUCOHIP_E_INVALID;
     const RigCalibOut out{used, board_rvec, board_tvec, camera_rms, rms, iterations};
-    return rig_batch(h, "rig_calibrate_batch", nframes, cams, ncams, RigBoard{ids, obj, nboard, info_type, marker_size, min_markers}, &out, nullptr, nullptr);
+    return rig_batch(h, "rig_calibrate_batch", nframes, cams, ncams, BoardDef{ids, obj, nboard, info_type, marker_size, -1.f}, min_markers, &out, nullptr, nullptr);
 }
 
 int arucohip_rig_pose_batch(arucohip_handle* h, int nframes, const arucohip_rig_camera_t* cams, int ncams, const int32_t* ids, const float* obj, int nboard,
                             int info_type, float marker_size, int min_markers, arucohip_board_t* out, int32_t* views_used) {
     if (!h) return ARUCOHIP_E_INVALID;
-    return rig_batch(h, "rig_pose_batch", nframes, const_cast<arucohip_rig_camera_t*>(cams), ncams, RigBoard{ids, obj, nboard, info_type, marker_size, min_markers},
-                     nullptr, out, views_used);
+    return rig_batch(h, "rig_pose_batch", nframes, const_cast<arucohip_rig_camera_t*>(cams), ncams, BoardDef{ids, obj, nboard, info_type, marker_size, -1.f},
+                     min_markers, nullptr, out, views_used);
 }
 
 }  // extern "C"

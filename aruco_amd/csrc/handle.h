@@ -7,6 +7,7 @@
 #include <array>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -68,6 +69,7 @@ struct Batch {
                             // longer match the frames' pixels. Every detection sets the record whole and so clears it
     const Span* begin() const { return span; }
     const Span* end() const { return span + nspan; }
+    int index(const Span& s) const { return (int)(&s - span); }   // s is one of this batch's own spans, as on_workers hands them out
     // the worker that holds frame `frame` and the frame's index there; nullptr: the batch has no such frame
     arucohip_handle* holder(int frame, int* local) const {
         for (const Span& s : *this)
@@ -348,6 +350,62 @@ inline int stage_obs(arucohip_handle* h, ObsArrays in, int nobs, int on_device, 
     return ARUCOHIP_OK;
 }
 
+// A board given as a host BoardDef: ids and obj go up to d_ids / d_obj on stream s; *dev is the record with the device arrays.
+inline int upload_board(arucohip_handle* h, const BoardDef& bd, hipStream_t s, int32_t* d_ids, float* d_obj, BoardDef* dev) {
+    HIPCHK(h, hipMemcpyAsync(d_ids, bd.ids, (size_t)bd.nboard * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(d_obj, bd.obj, (size_t)bd.nboard * 12 * sizeof(float), hipMemcpyHostToDevice, s));
+    *dev = bd, dev->ids = d_ids, dev->obj = d_obj;
+    return ARUCOHIP_OK;
+}
+
+// The caller's camera as the kernels take it. Every entry point keeps its own argument checks (which ndist, whether K is required)
+// and fills the record here: zeroed whole first, padding included, because the one-frame graph's key digests its bytes.
+inline void fill_cam(CamModel* cam, const float* K, const float* dist, int ndist, float marker_size, int y_perp) {
+    std::memset(cam, 0, sizeof(*cam));
+    cam->has_K = K != nullptr, cam->has_dist = K && dist && ndist > 0;
+    for (int i = 0; K && i < 9; i++) cam->K[i] = K[i];
+    for (int i = 0; cam->has_dist && i < ndist; i++) cam->k[i] = (double)dist[i];
+    cam->marker_size = marker_size, cam->y_perp = y_perp;
+}
+
+// A span's marker lists to the caller's out [frames][cap] / n_out [frames], queued on the worker's stream. Device arrays take the
+// lists as they are (rows cut to the smaller of cap and the worker's cap_markers). Host arrays take them in two steps: the worker's
+// whole lists and counts go to *staged and n_host [s.count] here, and collect_markers finishes once the stream has drained.
+inline int enqueue_markers(arucohip_handle* h, const Span& s, arucohip_marker_t* out, int cap, int32_t* n_out, int out_on_device,
+                           std::vector<arucohip_marker_t>* staged, int32_t* n_host) {
+    const Buffers& wb = s.w->buf;
+    const size_t row = (size_t)wb.cap_markers * sizeof(arucohip_marker_t), counts = (size_t)s.count * sizeof(int32_t);
+    hipStream_t st = s.w->stream;
+    if (out_on_device) {
+        HIPCHK(h, hipMemcpy2DAsync(out + (size_t)s.first * cap, (size_t)cap * sizeof(arucohip_marker_t), wb.markers, row,
+                                   (size_t)std::min(cap, wb.cap_markers) * sizeof(arucohip_marker_t), (size_t)s.count, hipMemcpyDeviceToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(n_out + s.first, wb.nmarkers, counts, hipMemcpyDeviceToDevice, st));
+        return ARUCOHIP_OK;
+    }
+    staged->resize((size_t)s.count * wb.cap_markers);
+    HIPCHK(h, hipMemcpyAsync(staged->data(), wb.markers, (size_t)s.count * row, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(n_host, wb.nmarkers, counts, hipMemcpyDeviceToHost, st));
+    return ARUCOHIP_OK;
+}
+// The second step, on the host: staged [s.count][cap_markers] and n_host [s.count], the span's own, to its rows of out / n_out. n_out
+// gets the true counts; a list longer than cap is cut and reported.
+inline int collect_markers(arucohip_handle* h, const Span& s, int cap, arucohip_marker_t* out, int32_t* n_out, const arucohip_marker_t* staged,
+                           const int32_t* n_host) {
+    const int capM = s.w->buf.cap_markers;
+    int ret = ARUCOHIP_OK;
+    for (int f = 0; f < s.count; f++) {
+        int n = n_host[f];
+        n_out[s.first + f] = n;
+        if (n > cap) {
+            if (ret == ARUCOHIP_OK) ret = fail(h, ARUCOHIP_E_CAPACITY, "marker output array too small");
+            n = cap;
+        }
+        n = std::min(n, capM);
+        if (n > 0) std::memcpy(out + (size_t)(s.first + f) * cap, staged + (size_t)f * capM, (size_t)n * sizeof(arucohip_marker_t));
+    }
+    return ret;
+}
+
 // Camera calibration (capi_calib.hip), shared by the pinhole and the fisheye entry points.
 // The views of one run, bound in the d_calib of the handle the run is on: the solver's arrays (d; d.obj / d.img may be the caller's
 // own device arrays), the staging of points and of a batch's gather, each view's offset and count.
@@ -361,8 +419,8 @@ struct CalibViews {
     std::vector<int32_t> off, npt;
 };
 int calib_views_of_points(arucohip_handle* h, const float* obj, const float* img, const int32_t* npoints, int nviews, int on_device, CalibViews* v);
-int calib_views_of_batch(arucohip_handle* h, int nframes, const int32_t* ids, const float* obj, int nboard, int info_type, float marker_size,
-                         int min_markers, int32_t* used, arucohip_handle** owner, CalibViews* v);
+int calib_views_of_batch(arucohip_handle* h, int nframes, const BoardDef& board, int min_markers, int32_t* used, arucohip_handle** owner,
+                         CalibViews* v);
 int calib_solve(arucohip_handle* h, const CalibViews& v, CalibState st, bool focal_start, double intr[9], double* rvecs, double* tvecs,
                 double* per_view_rms, double* rms);
 // the fisheye run's start state from (model, flags) (capi_fisheye.hip)

@@ -271,8 +271,24 @@ void launch_pnp_points(hipStream_t s, const float* obj, const float* img, int np
 void launch_project_points(hipStream_t s, const float* obj, int npts, const double* rt, const CamModel& cam, float* img_out);
 void launch_gl_modelview(hipStream_t s, int nframes, int cap, const Buffers& b, double* out_dev);
 void launch_marker_pose(hipStream_t s, arucohip_marker_t* markers, int n, const CamModel& cam);
-void launch_board_pose(hipStream_t s, int nframes, const Buffers& b, const int32_t* ids, const float* obj, int nboard, int info_type,
-                       float marker_size, float repj_thres, const CamModel& cam, arucohip_board_t* out, float* prob);
+
+// A board, the one record of it: the caller's arrays on the host, the uploaded ones (upload_board, handle.h) where a kernel reads it.
+struct BoardDef {
+    const int32_t* ids;
+    const float* obj;      // nboard * 4 * 3
+    int nboard, info_type;
+    float marker_size, repj_thres;
+};
+// metres per unit of the board's object points: a PIX board is scaled by the marker side taken from the first edge of marker 0
+// (board_side; a METERS board's marker side is that edge itself). A PIX board without a marker size has no scale: nothing solves it.
+__host__ __device__ inline double board_side(const float* obj) {
+    const float dx = obj[0] - obj[3], dy = obj[1] - obj[4], dz = obj[2] - obj[5];   // Point3f difference in float, cv::norm in double
+    return sqrt((double)dx * dx + (double)dy * dy + (double)dz * dz);
+}
+__host__ __device__ inline double board_mpp(const BoardDef& bd) {
+    return (bd.info_type == ARUCOHIP_BOARD_PIX && bd.marker_size > 0) ? (double)bd.marker_size / board_side(bd.obj) : 1.0;
+}
+void launch_board_pose(hipStream_t s, int nframes, const Buffers& b, const BoardDef& bd, const CamModel& cam, arucohip_board_t* out, float* prob);
 
 // Board marker recovery (k_recover.hip; arucohip_board_recover_batch). A worker's scratch: per frame the first entry of its block in the flat
 // candidate list, the adoptions of the matching pass, and the lists the refinement and the per-marker solver walk.
@@ -289,10 +305,7 @@ struct RecoverBufs {
     uint32_t* status;     // bit 0: a frame's marker list was full
 };
 struct RecoverArgs {
-    const int32_t* ids;   // device: the board
-    const float* obj;
-    int nboard, info_type;
-    float marker_size, repj_thres;
+    BoardDef bd;          // device arrays
     float max_corner_dist;
     int max_cell_errors, min_markers;
     int cells_valid, ws;             // votes from Buffers::cells, else from the stored patches of side ws
@@ -357,8 +370,9 @@ struct CalibDev {
 
 void launch_calib_init(hipStream_t s, const CalibDev& d, bool guess);
 void launch_calib_iteration(hipStream_t s, const CalibDev& d);
-void launch_calib_gather(hipStream_t s, int nframes, const Buffers& b, const int32_t* ids, const float* bobj, int nboard, double mpp,
-                         int first, float* obj, float* img, int32_t* npt, int32_t* nmark);
+// bd: device arrays; mpp: board_mpp of the board
+void launch_calib_gather(hipStream_t s, int nframes, const Buffers& b, const BoardDef& bd, double mpp, int first, float* obj, float* img,
+                         int32_t* npt, int32_t* nmark);
 
 // Marker mapping (k_map.hip): the rigid placement of nboard markers in the frame of the first, from frames that show several of them.
 constexpr int MAP_MAX_MARKERS = 64;     // listed markers (ARUCOHIP_MAP_MAX_MARKERS)
@@ -432,16 +446,14 @@ struct RigState {
 };
 
 struct RigDev {
-    int ncams, ninstants, nboard, min_markers, info_type;
-    float marker_size;
+    int ncams, ninstants, min_markers;
+    BoardDef bd;                // device arrays; repj_thres is not read
     // observations: obs_view != nullptr: nobs entries in any order; else view v owns obs_cnt[v] entries from v * obs_stride
     const int32_t* obs_view;
     const int32_t* obs_id;
     const float* obs_corners;   // 8 per observation
     const int32_t* obs_cnt;
     int nobs, obs_stride;
-    const int32_t* ids;         // [nboard]
-    const float* bobj;          // [nboard][12]
     const RigCam* cams;         // [ncams]
     int32_t* vn;                // [V] member markers of a view
     int32_t* vok;               // [V] the view counts: >= min_markers member markers and a start pose

@@ -452,9 +452,9 @@ __global__ __launch_bounds__(64) void calib_gather_kernel(const arucohip_marker_
     nmark[slot0] = nk;
 }
 
-void launch_calib_gather(hipStream_t s, int nframes, const Buffers& b, const int32_t* ids, const float* bobj, int nboard, double mpp,
-                         int first, float* obj, float* img, int32_t* npt, int32_t* nmark) {
-    hipLaunchKernelGGL(calib_gather_kernel, dim3(nframes), dim3(64), 0, s, b.markers, b.nmarkers, b.cap_markers, ids, bobj, nboard, mpp,
+void launch_calib_gather(hipStream_t s, int nframes, const Buffers& b, const BoardDef& bd, double mpp, int first, float* obj, float* img,
+                         int32_t* npt, int32_t* nmark) {
+    hipLaunchKernelGGL(calib_gather_kernel, dim3(nframes), dim3(64), 0, s, b.markers, b.nmarkers, b.cap_markers, bd.ids, bd.obj, bd.nboard, mpp,
                        first, obj, img, npt, nmark);
 }
 

@@ -274,12 +274,10 @@ __global__ __launch_bounds__(64) void board_pose_kernel(BoardArgs a) {
     if (lane == 0) a.out[frame] = res, a.prob[frame] = prob;
 }
 
-void launch_board_pose(hipStream_t s, int nframes, const Buffers& b, const int32_t* ids, const float* obj, int nboard, int info_type,
-                       float marker_size, float repj_thres, const CamModel& cam, arucohip_board_t* out, float* prob) {
+void launch_board_pose(hipStream_t s, int nframes, const Buffers& b, const BoardDef& bd, const CamModel& cam, arucohip_board_t* out, float* prob) {
     BoardArgs a;
     a.markers = b.markers, a.nmarkers = b.nmarkers, a.cap_markers = b.cap_markers;
-    a.bd.ids = ids, a.bd.obj = obj, a.bd.nboard = nboard, a.bd.info_type = info_type, a.bd.marker_size = marker_size, a.bd.repj_thres = repj_thres;
-    a.cam = cam, a.out = out, a.prob = prob, a.counters = b.counters;
+    a.bd = bd, a.cam = cam, a.out = out, a.prob = prob, a.counters = b.counters;
     hipLaunchKernelGGL(board_pose_kernel, dim3(nframes), dim3(64), 0, s, a);
 }
 

@@ -79,11 +79,9 @@ __global__ __launch_bounds__(64) void recover_match_kernel(RecoverK k) {
     const int nm_raw = k.nmarkers[frame];
     const int nm = min(nm_raw, k.cap_markers);
     const int nc = min(min(k.ncands[frame], k.cap_cands), RECOVER_MAX_CANDS);
-    BoardDef bd;
-    bd.ids = a.ids, bd.obj = a.obj, bd.nboard = a.nboard, bd.info_type = a.info_type, bd.marker_size = a.marker_size, bd.repj_thres = a.repj_thres;
     double r[3], t[3];
     int nk = 0;
-    const int st = nm_raw >= 0 ? board_solve_wave(k.markers + (size_t)frame * k.cap_markers, nm, bd, k.cam, k.counters, s, lane, r, t, &nk) : BOARD_NOT_TRIED;
+    const int st = nm_raw >= 0 ? board_solve_wave(k.markers + (size_t)frame * k.cap_markers, nm, a.bd, k.cam, k.counters, s, lane, r, t, &nk) : BOARD_NOT_TRIED;
     if (st == BOARD_POSE && nk >= a.min_markers && nc > 0) {
         const arucohip_marker_t* M = k.markers + (size_t)frame * k.cap_markers;
         Cand* C = k.cands + (size_t)frame * k.cap_cands;
@@ -93,10 +91,10 @@ __global__ __launch_bounds__(64) void recover_match_kernel(RecoverK k) {
         for (int i = lane; i < nc; i += WAVE) s_taken[i] = 0;
         double R[9];
         rodrigues_vec2mat(r, R, nullptr);
-        const double mpp = board_mpp(bd);
+        const double mpp = board_mpp(a.bd);
         __syncthreads();
-        for (int j = 0; j < a.nboard; j++) {
-            const int want = a.ids[j];
+        for (int j = 0; j < a.bd.nboard; j++) {
+            const int want = a.bd.ids[j];
             bool have = false;
             for (int i = lane; i < nm; i += WAVE) have = have || M[i].id == want;
             if (__ballot(have)) continue;
@@ -106,7 +104,7 @@ __global__ __launch_bounds__(64) void recover_match_kernel(RecoverK k) {
             }
             __syncthreads();   // the previous entry's readers of s_proj are done
             if (lane < 4) {
-                const float* q = a.obj + ((size_t)j * 4 + lane) * 3;
+                const float* q = a.bd.obj + ((size_t)j * 4 + lane) * 3;
                 double mx, my;
                 project_point((float)(q[0] * mpp), (float)(q[1] * mpp), (float)(q[2] * mpp), R, nullptr, t, k.cam.K, k.cam.k, &mx, &my, nullptr, nullptr);
                 s_proj[2 * lane] = (float)mx, s_proj[2 * lane + 1] = (float)my;
@@ -241,11 +239,9 @@ __global__ __launch_bounds__(64) void recover_insert_kernel(RecoverK k) {
     __threadfence_block();
     __syncthreads();
     // the board over all members, as board_pose_kernel gives it
-    BoardDef bd;
-    bd.ids = a.ids, bd.obj = a.obj, bd.nboard = a.nboard, bd.info_type = a.info_type, bd.marker_size = a.marker_size, bd.repj_thres = a.repj_thres;
     double r[3], t[3];
     int nk;
-    const int st = board_solve_wave(M, max(s_nm, 0), bd, k.cam, k.counters, s, lane, r, t, &nk);
+    const int st = board_solve_wave(M, max(s_nm, 0), a.bd, k.cam, k.counters, s, lane, r, t, &nk);
     arucohip_board_t res;
     res.n_markers = nk, res.has_pose = 0;
     for (int c = 0; c < 3; c++) res.rvec[c] = res.tvec[c] = 0;
@@ -254,7 +250,7 @@ __global__ __launch_bounds__(64) void recover_insert_kernel(RecoverK k) {
         if (st == BOARD_POSE && k.cam.y_perp) rotate_x_axis(r);
         res.has_pose = st == BOARD_POSE ? 1 : 0;
         for (int c = 0; c < 3; c++) res.rvec[c] = r[c], res.tvec[c] = t[c];
-        prob = (float)nk / (float)a.nboard;
+        prob = (float)nk / (float)a.bd.nboard;
     }
     if (lane == 0) k.boards[frame] = res, k.prob[frame] = prob;
 }

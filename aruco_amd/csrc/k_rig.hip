@@ -88,17 +88,15 @@ __global__ __launch_bounds__(64) void rig_view_kernel(RigDev d) {
     const int v = blockIdx.x, lane = threadIdx.x, c = v % d.ncams;
     int lo = 0, hi = d.nobs;
     if (!d.obs_view) lo = v * d.obs_stride, hi = lo + max(min(d.obs_cnt[v], d.obs_stride), 0);
-    const int n = listed_scan(d.obs_view, v, d.obs_id, lo, hi, d.ids, d.nboard, lane, s_m, s_o);   // n <= nboard <= RIG_MAX_BOARD
+    const int n = listed_scan(d.obs_view, v, d.obs_id, lo, hi, d.bd.ids, d.bd.nboard, lane, s_m, s_o);   // n <= nboard <= RIG_MAX_BOARD
     __syncthreads();
-    BoardDef bd;
-    bd.ids = d.ids, bd.obj = d.bobj, bd.nboard = d.nboard, bd.info_type = d.info_type, bd.marker_size = d.marker_size, bd.repj_thres = -1.f;
-    const double mpp = board_mpp(bd);
+    const double mpp = board_mpp(d.bd);
     float* pobj = d.pobj + (size_t)v * RIG_VIEW_POINTS * 3;
     float* pimg = d.pimg + (size_t)v * RIG_VIEW_POINTS * 2;
     for (int e = lane; e < n * 4; e += 64) {
         const int i = e >> 2, p = e & 3;
         const float* cn = d.obs_corners + (size_t)s_o[i] * 8;
-        const float* q = d.bobj + ((size_t)s_m[i] * 4 + p) * 3;
+        const float* q = d.bd.obj + ((size_t)s_m[i] * 4 + p) * 3;
         s_img[2 * e] = cn[2 * p], s_img[2 * e + 1] = cn[2 * p + 1];
         pimg[2 * e] = cn[2 * p], pimg[2 * e + 1] = cn[2 * p + 1];
         for (int k = 0; k < 3; k++) {

@@ -290,6 +290,42 @@ def test_two_lenses_interleaved(env):
         h.close()
 
 
+def test_two_spans_equal_one_span(env, monkeypatch):
+    """Four frames on two chunk workers give the bytes of one worker: the host lists, counts and dropped counts, and the device copy.
+    max_angle = 0.6 drops markers, so that the dropped counts and the compacted lists carry something."""
+    capi, torch = env["capi"], env["torch"]
+    frames = np.concatenate([env["frames"], env["frames"]])
+    cap = 32
+
+    def run(h, chunks):
+        h.detect_batch_host(frames)
+        assert h.batch_chunks() == chunks
+        out, n, dropped = h.fisheye_undistort_markers_batch(4, MODEL, KNEW32, max_angle=0.6, cap=cap)
+        h.detect_batch_host(frames)
+        d_out = torch.zeros((4, cap, 96), dtype=torch.uint8, device="cuda")
+        d_n = torch.zeros(4, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        h.fisheye_undistort_markers_batch_device(4, MODEL, d_out.data_ptr(), cap, d_n.data_ptr(), KNEW32, max_angle=0.6)
+        h.synchronize()
+        dev = np.frombuffer(d_out.cpu().numpy().tobytes(), capi.MARKER_DTYPE).reshape(4, cap)
+        dn = d_n.cpu().tolist()
+        return [o.tobytes() for o in out], list(n), list(dropped), [dev[f, :dn[f]].tobytes() for f in range(4)], dn
+
+    monkeypatch.setenv("ARUCOHIP_STREAMS", "2")
+    h2 = make_handle(env, 4)
+    monkeypatch.delenv("ARUCOHIP_STREAMS")
+    h1 = make_handle(env, 4)
+    try:
+        two, one = run(h2, (2, 2)), run(h1, (1, 4))
+        assert two == one
+        lists, n, dropped, dev, dn = two
+        assert dev == lists and dn == n   # the device copy holds what the host lists hold
+        assert dropped == [4, 8, 4, 8] and n == [20, 16, 20, 16]   # test_small_max_angle_drops_what_the_restatement_drops
+    finally:
+        h1.close()
+        h2.close()
+
+
 def test_one_frame_detect_keeps_its_graph(env):
     capi = env["capi"]
     h = make_handle(env)

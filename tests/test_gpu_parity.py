@@ -184,6 +184,21 @@ def test_golden_boards(env, handle, name):
     assert rel_err(b2["rvec"], o2["rvec"]) < POSE_REL_TOL and rel_err(b2["tvec"], o2["tvec"]) < POSE_REL_TOL
 
 
+def test_pix_board_without_a_marker_size_is_counted_not_solved(env, handle):
+    """A PIX board with marker_size = -1 has no metres per unit: board_detect_batch counts the member markers of every frame and leaves
+    pose and probability at zero, as BoardDetector::detect does."""
+    capi = env["capi"]
+    g, doc = load_case("board")
+    intr, bc = doc["intrinsics"], doc["board_conf"]
+    markers = handle.detect_batch_host(np.stack([g, np.ascontiguousarray(g[::-1, ::-1])]))
+    members = [sum(int(m["id"]) in bc["ids"] for m in ms) for ms in markers]
+    assert members[0] == len(doc["markers"]) > 0
+    boards = handle.board_detect_batch(2, bc["ids"], bc["obj"], capi.BOARD_PIX, intr["K"], intr["dist"], -1.0)
+    for b, n in zip(boards, members):
+        assert b["n_markers"] == n and b["has_pose"] == 0 and b["prob"] == 0.0
+        assert not b["rvec"].any() and not b["tvec"].any()
+
+
 @pytest.mark.parametrize("method", ["NONE", "HARRIS", "SUBPIX", "LINES"])
 def test_corner_methods_vs_oracle(env, handle, method):
     capi, orc = env["capi"], env["orc"]

@@ -179,10 +179,8 @@ def test_argument_checks(handle, poses):
         assert e.value.code == capi.E_INVALID
 
 
-@pytest.fixture(scope="module")
-def batch():
-    """Four 640 x 480 frames, one of them empty, detected without a pose on a handle of four frames."""
-    from aruco_amd import capi
+def _batch_frames():
+    """Four 640 x 480 frames, one of them empty."""
     from aruco_amd import synth
 
     # make_stream scales its markers with the frame: at 640 x 480 they fall below the detector's smallest size, so the sides are set here
@@ -192,8 +190,16 @@ def batch():
         lay = synth.frame_layout(rng, 640, 480, n_markers=6, side_range=(60, 110), margin=20)
         frames[f] = synth.render_frame(lay, 640, 480, rng).numpy()
     frames[2] = 128
+    return frames
+
+
+@pytest.fixture(scope="module")
+def batch():
+    """The four frames detected without a pose on a handle of four frames."""
+    from aruco_amd import capi
+
     h = capi.Handle(640, 480, max_batch=4, device=0)
-    markers = h.detect_batch_host(frames)
+    markers = h.detect_batch_host(_batch_frames())
     yield h, markers
     h.close()
 
@@ -222,6 +228,34 @@ def test_batch_equals_the_single_call_on_the_returned_markers(batch, refine):
             assert np.all(got[:counts[f]]["n_solutions"] == 2)
             for e in got[counts[f]:]:
                 assert e.tobytes() == sentinel
+
+
+def test_two_spans_equal_one_span(batch, monkeypatch):
+    """The four frames on two chunk workers give the bytes of the one-worker handle, in host and in device memory."""
+    import torch
+    from aruco_amd import capi
+
+    h1, markers = batch
+    _, Kc, dist = _golden_camera()
+    cap = 16
+    monkeypatch.setenv("ARUCOHIP_STREAMS", "2")
+    h2 = capi.Handle(640, 480, max_batch=4, device=0)
+    monkeypatch.delenv("ARUCOHIP_STREAMS")
+    try:
+        assert [m.tobytes() for m in h2.detect_batch_host(_batch_frames())] == [m.tobytes() for m in markers]
+        assert h2.batch_chunks() == (2, 2) and h1.batch_chunks() == (1, 4)
+        got = []
+        for h in (h2, h1):
+            host = bytes(h.planar_poses_batch(4, Kc, dist, 0.05, cap=cap, fill=0xA5))
+            dev = torch.full((4 * cap * 120,), 0xA5, dtype=torch.uint8, device="cuda:0")
+            torch.cuda.synchronize()
+            h.planar_poses_batch_device(4, C.c_void_p(dev.data_ptr()), cap, Kc, dist, 0.05)
+            torch.cuda.synchronize()
+            got.append((host, dev.cpu().numpy().tobytes()))
+        assert got[0] == got[1]
+        assert got[0][0] == got[0][1]   # entries beyond a frame's markers keep the fill byte in both forms
+    finally:
+        h2.close()
 
 
 def test_batch_capacity_and_missing_batch(batch):
