@@ -112,6 +112,15 @@ BOARD_DTYPE = np.dtype([("n_markers", "<i4"), ("has_pose", "<i4"), ("rvec", "<f8
 assert C.sizeof(Overlay) == 12 and BOARD_DTYPE.itemsize == 56
 
 
+class Rectify(C.Structure):
+    """arucohip_rectify_t: a window of the board plane. Output pixel (u, v) shows the plane point (x0 + u ux + v vx, y0 + u uy + v vy)."""
+    _fields_ = [("out_width", C.c_int32), ("out_height", C.c_int32), ("x0", C.c_float), ("y0", C.c_float), ("ux", C.c_float),
+                ("uy", C.c_float), ("vx", C.c_float), ("vy", C.c_float)]
+
+
+assert C.sizeof(Rectify) == 32
+
+
 class Limits(C.Structure):
     _fields_ = [("max_width", C.c_int32), ("max_height", C.c_int32), ("max_batch", C.c_int32),
                 ("max_thres_planes", C.c_int32), ("triggers_per_frame", C.c_int32), ("contours_per_frame", C.c_int32),
@@ -167,6 +176,7 @@ SYMBOLS = [
     "arucohip_charuco_calibrate_batch", "arucohip_charuco_pose_batch",
     "arucohip_fisheye_undistort_points", "arucohip_fisheye_distort_points", "arucohip_fisheye_undistort",
     "arucohip_fisheye_undistort_markers_batch", "arucohip_fisheye_calibrate", "arucohip_fisheye_calibrate_board_batch",
+    "arucohip_warp_plane_batch", "arucohip_rectify_board_window", "arucohip_board_rectify_batch",
 ]
 
 _lib = None
@@ -332,6 +342,9 @@ def load():
     L.arucohip_fisheye_undistort_markers_batch.argtypes = [vp, i, vp, i, vp, f, vp, i, vp, i, vp]
     L.arucohip_fisheye_calibrate.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp]
     L.arucohip_fisheye_calibrate_board_batch.argtypes = [vp, i, vp, vp, i, i, f, i, i, i, i, vp, vp, vp, vp, vp]
+    L.arucohip_warp_plane_batch.argtypes = [vp, vp, i, i, i, i, sz, sz, i, vp, vp, i, vp, vp, i, vp, i, i, sz, sz, i]
+    L.arucohip_rectify_board_window.argtypes = [vp, i, i, f, f, f, i, vp]
+    L.arucohip_board_rectify_batch.argtypes = [vp, vp, i, i, i, i, sz, sz, i, vp, i, vp, vp, i, vp, vp, sz, sz, i, vp, vp]
     L.arucohip_default_params.argtypes = [vp]
     L.arucohip_default_limits.argtypes = [vp, i, i, i]
     _lib = L
@@ -437,6 +450,18 @@ def board_pix_to_meters(obj, marker_size_m):
     if rc != OK:
         raise ArucoHipError(rc, "arucohip_board_pix_to_meters")
     return out
+
+
+def rectify_board_window(obj, info_type, marker_size, px_per_unit, margin=0.0, flip_y=False):
+    """arucohip_rectify_board_window: the Rectify window that shows the bounding box of obj[N][4][3] plus `margin` (plane units: metres
+    for a PIX board with a marker size) at px_per_unit output pixels per unit; flip_y for boards whose y points up."""
+    oa = _f32(obj)
+    win = Rectify()
+    rc = load().arucohip_rectify_board_window(_ptr(oa), oa.size // 12, int(info_type), float(marker_size), float(px_per_unit), float(margin),
+                                              int(bool(flip_y)), C.byref(win))
+    if rc != OK:
+        raise ArucoHipError(rc, "arucohip_rectify_board_window")
+    return win
 
 
 def board_place(obj, rvec, tvec):
@@ -999,6 +1024,69 @@ class Handle:
         self._chk(self.L.arucohip_draw_boards_batch(self.h, ptr, n, wid, hgt, ch, rs, fs, dev, bptr, bdev, float(marker_size), _ptr(Ka), _ptr(da),
                                                     0 if da is None else da.size, int(flags)))
         return frames
+
+    # ---- plane rectification: the fronto-parallel view of a board's plane, one map per frame
+    def warp_plane_device(self, src_ptr, nframes, width, height, channels, maps_ptr, dst_ptr, out_width, out_height, K=None, dist=None,
+                          valid_ptr=None, row_stride=None, frame_stride=None, dst_row_stride=None, dst_frame_stride=None, src_on_device=1,
+                          maps_on_device=1, dst_on_device=1):
+        """arucohip_warp_plane_batch on plain addresses: dst pixel (u, v) of frame f = src frame f sampled at cam(maps[f] (u, v, 1)). Strides
+        default to tightly packed. With everything on the device the call is asynchronous on the handle's stream."""
+        rs = width * channels if row_stride is None else row_stride
+        drs = out_width * channels if dst_row_stride is None else dst_row_stride
+        Ka, da = _f32(K), _f32(dist)
+        self._chk(self.L.arucohip_warp_plane_batch(self.h, src_ptr, int(nframes), int(width), int(height), int(channels), rs,
+                                                   rs * height if frame_stride is None else frame_stride, int(src_on_device), maps_ptr, valid_ptr,
+                                                   int(maps_on_device), _ptr(Ka), _ptr(da), 0 if da is None else da.size, dst_ptr, int(out_width),
+                                                   int(out_height), drs, drs * out_height if dst_frame_stride is None else dst_frame_stride,
+                                                   int(dst_on_device)))
+
+    def warp_plane(self, frames, maps, out_size, K=None, dist=None, valid=None, width=None, channels=1):
+        """Host frames uint8 [N][H][W] or [N][H][W][3] (see _frames for padded rows), maps float64 [N][3][3] or [N][9], out_size =
+        (out_width, out_height), valid: N flags or None. Returns uint8 [N][out_height][out_width] (x 3)."""
+        assert isinstance(frames, np.ndarray)
+        ptr, n, wid, hgt, ch, rs, fs, _ = self._frames(frames, width, channels)
+        m = np.ascontiguousarray(maps, dtype=np.float64).reshape(n, 9)
+        va = None if valid is None else np.ascontiguousarray(valid, dtype=np.int32).reshape(n)
+        ow, oh = int(out_size[0]), int(out_size[1])
+        out = np.zeros((n, oh, ow) if ch == 1 else (n, oh, ow, ch), np.uint8)
+        self.warp_plane_device(ptr, n, wid, hgt, ch, _ptr(m), _ptr(out), ow, oh, K, dist, _ptr(va), rs, fs, src_on_device=0, maps_on_device=0,
+                               dst_on_device=0)
+        return out
+
+    def board_rectify_device(self, frames_ptr, nframes, width, height, channels, boards, K, win, dst_ptr, dist=None, row_stride=None,
+                             frame_stride=None, dst_row_stride=None, dst_frame_stride=None, frames_on_device=1, dst_on_device=1, report=False):
+        """arucohip_board_rectify_batch on plain addresses. boards: N BOARD_DTYPE entries (numpy) or a device tensor of N * 56 bytes. With
+        report: returns (status int32 [N], maps float64 [N][9]) and is synchronous; without it device frames, boards and dst make the
+        call asynchronous on the handle's stream."""
+        if isinstance(boards, np.ndarray):
+            assert boards.dtype == BOARD_DTYPE and boards.size == nframes
+        bptr, bdev = self._buf(boards)
+        rs = width * channels if row_stride is None else row_stride
+        drs = win.out_width * channels if dst_row_stride is None else dst_row_stride
+        Ka, da = _f32(K), _f32(dist)
+        status = np.zeros(nframes, np.int32) if report else None
+        maps = np.zeros((nframes, 9), np.float64) if report else None
+        self._chk(self.L.arucohip_board_rectify_batch(self.h, frames_ptr, int(nframes), int(width), int(height), int(channels), rs,
+                                                      rs * height if frame_stride is None else frame_stride, int(frames_on_device), bptr, bdev,
+                                                      _ptr(Ka), _ptr(da), 0 if da is None else da.size, C.byref(win), dst_ptr, drs,
+                                                      drs * win.out_height if dst_frame_stride is None else dst_frame_stride, int(dst_on_device),
+                                                      _ptr(status), _ptr(maps)))
+        return (status, maps) if report else None
+
+    def board_rectify(self, frames, boards, K, win, dist=None, width=None, channels=1):
+        """Host frames (as warp_plane) resampled on the plane of boards[f]: N BOARD_DTYPE entries, or the list of dicts board_detect_batch
+        returns. Returns (images uint8 [N][win.out_height][win.out_width] (x 3), status int32 [N], maps float64 [N][9])."""
+        assert isinstance(frames, np.ndarray)
+        ptr, n, wid, hgt, ch, rs, fs, _ = self._frames(frames, width, channels)
+        if not isinstance(boards, np.ndarray):
+            b = np.zeros(len(boards), BOARD_DTYPE)
+            for k, d in enumerate(boards):
+                b[k] = (d.get("n_markers", 0), d["has_pose"], d["rvec"], d["tvec"])
+            boards = b
+        out = np.zeros((n, win.out_height, win.out_width) if ch == 1 else (n, win.out_height, win.out_width, ch), np.uint8)
+        status, maps = self.board_rectify_device(ptr, n, wid, hgt, ch, boards, K, win, _ptr(out), dist, rs, fs, frames_on_device=0, dst_on_device=0,
+                                                 report=True)
+        return out, status, maps
 
     def board_detect(self, markers, ids, obj, info_type, K=None, dist=None, marker_size=-1.0, repj_err_thres=-1.0, y_perp=False):
         m = np.ascontiguousarray(markers, dtype=MARKER_DTYPE)

@@ -156,6 +156,8 @@ struct arucohip_handle {
     Mem<uint8_t> d_planar;            // arucohip_planar_poses: results and staged markers of one call
     Mem<uint8_t> d_overlay;           // arucohip_draw_*_batch: primitive lists of one chunk of frames, staged host markers / boards
     Mem<uint8_t> d_overlay_frames;    // arucohip_draw_*_batch: staged host frames
+    Mem<uint8_t> d_rectify;           // arucohip_warp_plane_batch / arucohip_board_rectify_batch: maps, valid words and staged boards of one call
+    Mem<uint8_t> d_rectify_frames;    // ... and its staged host frames and the images a host caller gets
     Mem<uint8_t> d_recover;           // arucohip_board_recover_batch: the board, adoption records and work lists of one call (recover_layout)
     // arucohip_charuco_corners_batch (capi_charuco.hip), on the handle the caller holds: the corner records of the last call and their counts stay in
     // d_charuco for the calibration and the pose; the host keeps the layout and the counts
@@ -199,7 +201,7 @@ struct arucohip_handle {
     //   capture and replay; batches that decode from cell medians neither touch nor move buf.patches, and buf.cells is create-time memory;
     // - neither: the other Buffers arrays, zero_block and h_markers are create-time memory (`held`); d_erode, d_canny and the user decoder's
     //   staging and d_pyr belong to configurations that are not graphed; wt_out is set only inside chunk_enqueue, which does not run this path.
-    //   Memory no captured launch reads (d_bgr, undistortion, fisheye maps and scratch, calibration, marker mapping, camera rigs and the pinned solver state, board and GL batches, planar poses, marker recovery, overlays, EM, HRM, fiducial generation, ChArUco corners and ChromaticMask scratch) may
+    //   Memory no captured launch reads (d_bgr, undistortion, fisheye maps and scratch, calibration, marker mapping, camera rigs and the pinned solver state, board and GL batches, planar poses, marker recovery, overlays, plane rectification, EM, HRM, fiducial generation, ChArUco corners and ChromaticMask scratch) may
     //   be replaced at any time.
     struct FrameGraph {
         hipGraphExec_t exec = nullptr;

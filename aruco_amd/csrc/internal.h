@@ -219,6 +219,23 @@ void launch_expand_thres(hipStream_t s, const FrameGeom& g, int plane, const Buf
 void launch_undist_map(hipStream_t s, int W, int H, const float* K, const float* dist, int ndist, short2* xy, uint16_t* fxy);
 void launch_remap(hipStream_t s, const uint8_t* src, size_t row_stride, size_t frame_stride, int W, int H, int cn, int nframes, const short2* xy,
                   const uint16_t* fxy, uint8_t* dst);
+// Plane rectification (k_rectify.hip): dst pixel (u, v) of frame f = src frame f sampled at cam(maps[f] * (u, v, 1)), the rule arucohip.h
+// states at arucohip_warp_plane_batch. The camera: px = fx * x' + cx with the Brown polynomial k (dist: all of it, else skipped);
+// no camera is fx = fy = 1, cx = cy = 0. valid may be null (every frame valid).
+struct PlaneWarp {
+    const uint8_t* src;
+    size_t row_stride, frame_stride;
+    int width, height;
+    const double* maps;     // [nframes][9], row-major
+    const int32_t* valid;   // [nframes]
+    double fx, fy, cx, cy, k[8];
+    uint8_t* dst;
+    size_t dst_row_stride, dst_frame_stride;
+    int out_width, out_height;
+};
+void launch_plane_warp(hipStream_t s, const PlaneWarp& a, int cn, bool dist, int nframes);
+// maps[f] / valid[f] of the window `win` on the plane of boards[f]
+void launch_plane_maps(hipStream_t s, const arucohip_board_t* boards, int nframes, const arucohip_rectify_t& win, double* maps, int32_t* valid);
 // fisheye lenses (k_fisheye.hip; the model is fisheye_device.h's)
 struct FisheyeCam;
 void launch_fisheye_points(hipStream_t s, const FisheyeCam& cam, const float* src, int n, int undistort, float* dst, uint8_t* valid);

@@ -9,6 +9,7 @@
 // position of column j is the running sum of j additions in the reference — and cached in the handle; per frame the
 // remap kernel is a streaming gather (4 source bytes per channel and pixel, coalesced stores).
 #include "internal.h"
+#include "remap_device.h"
 
 namespace ah {
 
@@ -77,23 +78,10 @@ __global__ __launch_bounds__(256) void remap_linear_kernel(RemapArgs a) {
     const size_t pix = (size_t)y * a.width + x;
     const short2 s = a.xy[pix];
     const int fq = a.fxy[pix], fx = fq & 31, fy = fq >> 5;
-    const int sx = s.x, sy = s.y, W = a.width, H = a.height, cn = a.cn;
-    const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
+    const int W = a.width, H = a.height, cn = a.cn;
     const uint8_t* src = a.src + (size_t)f * a.frame_stride;
     uint8_t* d = a.dst + ((size_t)f * W * H + pix) * cn;
-    const bool outside = sx >= W || sx + 1 < 0 || sy >= H || sy + 1 < 0;
-    const bool x0in = sx >= 0 && sx < W, x1in = sx + 1 >= 0 && sx + 1 < W, y0in = sy >= 0 && sy < H, y1in = sy + 1 >= 0 && sy + 1 < H;
-    for (int c = 0; c < cn; c++) {
-        int v = 0;
-        if (!outside) {
-            const int p00 = (x0in && y0in) ? src[(size_t)sy * a.row_stride + (size_t)sx * cn + c] : 0;
-            const int p01 = (x1in && y0in) ? src[(size_t)sy * a.row_stride + (size_t)(sx + 1) * cn + c] : 0;
-            const int p10 = (x0in && y1in) ? src[(size_t)(sy + 1) * a.row_stride + (size_t)sx * cn + c] : 0;
-            const int p11 = (x1in && y1in) ? src[(size_t)(sy + 1) * a.row_stride + (size_t)(sx + 1) * cn + c] : 0;
-            v = (p00 * w00 + p01 * w01 + p10 * w10 + p11 * w11 + (1 << 14)) >> 15;
-        }
-        d[c] = (uint8_t)min(max(v, 0), 255);
-    }
+    for (int c = 0; c < cn; c++) d[c] = (uint8_t)remap_bilinear(src, a.row_stride, W, H, cn, s.x, s.y, fx, fy, c);
 }
 
 void launch_undist_map(hipStream_t s, int W, int H, const float* K, const float* dist, int ndist, short2* xy, uint16_t* fxy) {

@@ -678,6 +678,83 @@ private:
 inline void Board::draw(cv::Mat& im, unsigned char b, unsigned char g, unsigned char r, int lineWidth, bool writeId) const {
     DeviceDrawing::draw(im, *this, ARUCOHIP_DRAW_OUTLINE | (writeId ? ARUCOHIP_DRAW_IDS : 0), lineWidth, b, g, r);
 }
+
+// The fronto-parallel view of the plane a board lies in (arucohip_board_rectify_batch on the process-wide handle): the frame goes up, is
+// resampled through the board's pose and the camera, and the view comes back. No reference counterpart. 8-bit frames with 1 or 3 channels.
+// A caller that keeps its frames on the device calls the C ABI directly, a whole batch at a time, and copies nothing.
+class BoardRectifier {
+public:
+    BoardRectifier() { std::memset(&win_, 0, sizeof(win_)); }
+    // The window: the board's bounding box plus `margin` at pxPerUnit output pixels per plane unit. The units are those of the pose:
+    // metres for a PIX board with markerSize (as BoardDetector scales it), the board's own for a METERS board. flipY: boards whose y points up.
+    void setWindow(const BoardConfiguration& bc, float markerSize, float pxPerUnit, float margin = 0.f, bool flipY = false) {
+        std::vector<float> obj;
+        for (const std::vector<cv::Point3f>& m : bc.objPoints) {
+            if (m.size() != 4) arucohip_throw_(ARUCOHIP_E_INVALID, "BoardRectifier::setWindow: a marker needs 4 corners", nullptr);
+            for (const cv::Point3f& p : m) obj.push_back(p.x), obj.push_back(p.y), obj.push_back(p.z);
+        }
+        arucohip_throw_(arucohip_rectify_board_window(obj.data(), (int)bc.objPoints.size(), bc.mInfoType, markerSize, pxPerUnit, margin, flipY ? 1 : 0, &win_),
+                        "BoardRectifier::setWindow: no board, or a window below 1 or above 16383 pixels", nullptr);
+    }
+    void setWindow(const arucohip_rectify_t& window) { win_ = window; }
+    const arucohip_rectify_t& getWindow() const { return win_; }
+    // the view of B's plane in `frame`; all zero when B carries no pose
+    cv::Mat rectify(const cv::Mat& frame, const Board& B, const CameraParameters& CP) const {
+        const int cn = channels_(frame);
+        float K[9], d[8];
+        const bool hasK = mat_to_K_(CP.CameraMatrix, K);
+        const int nd = mat_to_dist_(CP.Distorsion, d);
+        arucohip_board_t b;
+        std::memset(&b, 0, sizeof(b));
+        b.n_markers = (int32_t)B.size();
+        if (!B.Rvec.empty() && !B.Tvec.empty()) {
+            b.has_pose = 1;
+            for (int k = 0; k < 3; k++) b.rvec[k] = B.Rvec(k), b.tvec[k] = B.Tvec(k);
+        }
+        if (win_.out_width < 1 || win_.out_height < 1) arucohip_throw_(ARUCOHIP_E_INVALID, "BoardRectifier::rectify: no window set", nullptr);
+        cv::Mat out(win_.out_height, win_.out_width, frame.type());
+        SharedHandle_& sh = SharedHandle_::get();
+        std::lock_guard<std::mutex> lock(sh.mu);
+        arucohip_handle* h = sh.ensure();
+        arucohip_throw_(arucohip_board_rectify_batch(h, frame.data, 1, frame.cols, frame.rows, cn, (size_t)frame.step, (size_t)frame.step * frame.rows, 0, &b, 0,
+                                                     hasK ? K : nullptr, nd ? d : nullptr, nd, &win_, out.data, (size_t)out.step,
+                                                     (size_t)out.step * out.rows, 0, nullptr, nullptr),
+                        "BoardRectifier::rectify", h);
+        return out;
+    }
+    // frames[i] on the plane of boards[i]
+    std::vector<cv::Mat> rectify(const std::vector<cv::Mat>& frames, const std::vector<Board>& boards, const CameraParameters& CP) const {
+        if (frames.size() != boards.size()) arucohip_throw_(ARUCOHIP_E_INVALID, "BoardRectifier::rectify: one board per frame", nullptr);
+        std::vector<cv::Mat> out;
+        for (size_t i = 0; i < frames.size(); i++) out.push_back(rectify(frames[i], boards[i], CP));
+        return out;
+    }
+    // cv::warpPerspective(src, dst, M, size, INTER_LINEAR | WARP_INVERSE_MAP, BORDER_CONSTANT 0) with every pixel projected in double
+    // (arucohip_warp_plane_batch without a camera): dst (u, v) = src at M (u, v, 1). M: 3 x 3, CV_64F or CV_32F.
+    static cv::Mat warpPerspectiveInverse(const cv::Mat& src, const cv::Mat& M, cv::Size size) {
+        const int cn = channels_(src);
+        if (M.rows != 3 || M.cols != 3 || (M.type() != CV_64FC1 && M.type() != CV_32FC1))
+            arucohip_throw_(ARUCOHIP_E_INVALID, "warpPerspectiveInverse: M must be 3x3, CV_64F or CV_32F", nullptr);
+        double m[9];
+        for (int i = 0; i < 9; i++) m[i] = M.type() == CV_64FC1 ? M.at<double>(i / 3, i % 3) : (double)M.at<float>(i / 3, i % 3);
+        if (size.width < 1 || size.height < 1) arucohip_throw_(ARUCOHIP_E_INVALID, "warpPerspectiveInverse: empty size", nullptr);
+        cv::Mat out(size.height, size.width, src.type());
+        SharedHandle_& sh = SharedHandle_::get();
+        std::lock_guard<std::mutex> lock(sh.mu);
+        arucohip_handle* h = sh.ensure();
+        arucohip_throw_(arucohip_warp_plane_batch(h, src.data, 1, src.cols, src.rows, cn, (size_t)src.step, (size_t)src.step * src.rows, 0, m, nullptr, 0, nullptr,
+                                                  nullptr, 0, out.data, size.width, size.height, (size_t)out.step, (size_t)out.step * out.rows, 0),
+                        "warpPerspectiveInverse", h);
+        return out;
+    }
+
+private:
+    arucohip_rectify_t win_;
+    static int channels_(const cv::Mat& image) {
+        if (image.type() != CV_8UC1 && image.type() != CV_8UC3) arucohip_throw_(ARUCOHIP_E_INVALID, "rectification: CV_8UC1 or CV_8UC3 frames", nullptr);
+        return image.type() == CV_8UC3 ? 3 : 1;
+    }
+};
 #if ARUCOHIP_HAVE_OPENCV && defined(ARUCOHIP_SHIM_DEFINE_DRAWING)
 // The reference's drawing names, defined through the device overlay. Off by default: an integration that keeps the reference's own
 // src/marker.cpp / src/cvdrawingutils.{h,cpp} (or any other definition of these names) must not define the macro.

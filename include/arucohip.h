@@ -890,6 +890,66 @@ int arucohip_draw_boards_batch(arucohip_handle* h, uint8_t* frames, int nframes,
                                size_t frame_stride, int frames_on_device, const arucohip_board_t* boards, int boards_on_device, float marker_size,
                                const float* K, const float* dist, int ndist, int flags);
 
+/* ---- Plane rectification: the fronto-parallel ("bird's-eye") view of the plane a board lies in, resampled from every frame with a
+ * map of its own (k_rectify.hip). No reference counterpart. With K = NULL it is what cv::warpPerspective(src, dst, M, size,
+ * INTER_LINEAR | WARP_INVERSE_MAP, BORDER_CONSTANT 0) computes, up to OpenCV's own blocking (OpenCV interpolates the source position
+ * inside blocks; here every pixel is projected).
+ * The rule for a pixel. Frame f has the 3 x 3 row-major double map M = maps + 9 f. Output pixel (u, v), integer indices = pixel
+ * centres, is computed in double, in this order, no operation fused:
+ *   1. X = (M0 u + M1 v) + M2, Y = (M3 u + M4 v) + M5, W = (M6 u + M7 v) + M8. Unless W > 0 (NaN included) the pixel is 0.
+ *   2. x = X / W, y = Y / W (true divisions).
+ *   3. K = NULL: px = x, py = y. Otherwise the Brown model as arucohip_undistort's map applies it, k = dist[0..7] with absent
+ *      coefficients 0 (k1 k2 p1 p2 k3 k4 k5 k6), fx = K[0], fy = K[4], cx = K[2], cy = K[5] (nothing else of K is used):
+ *        r2 = x x + y y, kr = (1 + ((k3 r2 + k2) r2 + k1) r2) / (1 + ((k6 r2 + k5) r2 + k4) r2)
+ *        px = fx (x kr + p1 2xy + p2 (r2 + 2 x x)) + cx, py = fy (y kr + p1 (r2 + 2 y y) + p2 2xy) + cy
+ *   4. If px or py is not finite the pixel is 0.
+ *   5. iu = the nearest integer, ties to even, of px * 32 clamped to [-2^31, 2^31 - 1]; sx = iu >> 5, ax = iu & 31; iv, sy, ay from py.
+ *   6. Per channel the bilinear sample of arucohip_undistort's remap at (sx + ax / 32, sy + ay / 32): weights (32 - ax)(32 - ay) * 32
+ *      and so on, sum + (1 << 14) >> 15, taps outside the source count 0.
+ * src: nframes frames of `channels` (1 or 3) interleaved 8-bit channels; dst: nframes images of out_width x out_height (1..16383 each)
+ * with the same channels. Bytes between out_width * channels and dst_row_stride are never written. valid (nframes, may be NULL: all
+ * valid): a frame with valid[f] == 0 becomes all zero and its source is not read. maps_on_device covers maps and valid. K (may be
+ * NULL) and dist (ndist = 0, 4, 5 or 8 floats; needs K) are host arrays. When src, maps and dst are all on the device the call is
+ * asynchronous on the handle's stream, behind whatever is queued there; otherwise it returns when dst is complete. Uses scratch of its
+ * own: the single-frame graph and the last batch stay valid. ARUCOHIP_E_INVALID, with a message that names it and before anything runs:
+ * a null pointer, channels not 1 or 3, ndist not 0, 4, 5 or 8 (or dist without K), a stride smaller than a row or a frame, a size
+ * below 1 or an output above 16383, nframes < 1, dst overlapping src. */
+int arucohip_warp_plane_batch(arucohip_handle* h, const uint8_t* src, int nframes, int width, int height, int channels, size_t row_stride,
+                              size_t frame_stride, int src_on_device, const double* maps, const int32_t* valid, int maps_on_device,
+                              const float* K, const float* dist, int ndist, uint8_t* dst, int out_width, int out_height,
+                              size_t dst_row_stride, size_t dst_frame_stride, int dst_on_device);
+
+typedef struct arucohip_rectify {   /* a window of the board plane, in the units the pose was solved in */
+    int32_t out_width, out_height;
+    float x0, y0;                   /* plane point of output pixel (0, 0) */
+    float ux, uy, vx, vy;           /* plane step per output column / per output row */
+} arucohip_rectify_t;
+
+/* Host arithmetic: the window that shows a board's bounding box plus `margin` (plane units) at px_per_unit, u along +x, v along +y
+ * (flip_y: v along -y, for y-up boards such as arucohip_hrm_board_image's). Object points are scaled as arucohip_board_detect
+ * scales them (PIX: marker_size / first side; METERS: 1). With the box [xmin, xmax] x [ymin, ymax] of the scaled points and
+ * step = 1 / px_per_unit: out_width = ceil((xmax - xmin + 2 margin) * px_per_unit), where an extent within 1e-6 (relative) above a whole
+ * number of pixels counts as that number; x0 = xmin - margin + step / 2 (output pixel 0 covers the first step of the box, its centre is
+ * half a step in), ux = step, uy = vx = 0; rows likewise with vy = step, or y0 = ymax + margin - step / 2 and vy = -step with flip_y.
+ * For a PIX board painted by arucohip_fiducial_board_image, px_per_unit = first side / marker_size and margin 0 give one output pixel per
+ * board pixel. ARUCOHIP_E_INVALID: a null pointer, nboard < 1, px_per_unit not positive and finite, margin not finite, a window of
+ * less than one pixel or more than 16383. */
+int arucohip_rectify_board_window(const float* obj, int nboard, int info_type, float marker_size, float px_per_unit, float margin,
+                                  int flip_y, arucohip_rectify_t* win);
+
+/* Frame f is resampled on the plane of boards[f] (rvec / tvec as the board calls return them; y_perpendicular poses are the
+ * caller's to undo): maps[f] has the columns R (ux, uy, 0), R (vx, vy, 0) and R (x0, y0, 0) + t with R = Rodrigues(rvec), and the
+ * rest is arucohip_warp_plane_batch with win's size. K is required. status[f] (host, may be NULL) = 1, or 0 when the frame had no
+ * pose (has_pose == 0, or a map entry that is not finite) and its image is all zero. maps_out (host, may be NULL): the nframes x 9 maps
+ * that were used (zeros for a frame without pose). With frames, boards and dst on the device and neither status nor maps_out the call
+ * is asynchronous on the handle's stream; otherwise it returns when dst, status and maps_out are complete. ARUCOHIP_E_INVALID as above,
+ * and for a window whose u and v steps are parallel, zero or not finite. */
+int arucohip_board_rectify_batch(arucohip_handle* h, const uint8_t* frames, int nframes, int width, int height, int channels,
+                                 size_t row_stride, size_t frame_stride, int frames_on_device, const arucohip_board_t* boards,
+                                 int boards_on_device, const float* K, const float* dist, int ndist, const arucohip_rectify_t* win,
+                                 uint8_t* dst, size_t dst_row_stride, size_t dst_frame_stride, int dst_on_device, int32_t* status,
+                                 double* maps_out);
+
 /* Execution time of the dominant streaming kernel (the 16-pixel-per-lane adaptive threshold kernel) from the device's constant-rate
  * clock: every wave leaves its first and last reading, *total_ms = sum over the launches since arucohip_enable_timing(h, 1) of
  * (last wave's end - first wave's start), *launches = their number (0 when another threshold kernel ran: use the event times).
