@@ -121,6 +121,27 @@ class Rectify(C.Structure):
 assert C.sizeof(Rectify) == 32
 
 
+class Texture(C.Structure):
+    """arucohip_texture_t: what arucohip_composite_plane_batch / arucohip_board_composite_batch lay on the plane. texture() fills one."""
+    _fields_ = [("data", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32), ("on_device", C.c_int32),
+                ("row_stride", C.c_size_t), ("frame_stride", C.c_size_t), ("opacity", C.c_int32), ("pad_", C.c_int32)]
+
+
+assert C.sizeof(Texture) == 48
+
+
+def texture(tex, opacity=255, per_frame=False):
+    """The Texture of a contiguous uint8 numpy array or torch tensor: [H][W] or [H][W][C], or with per_frame [N][H][W] / [N][H][W][C] (frame
+    f takes tex[f]). C is the frames' channels, or one more with straight alpha last. The record keeps a reference to the array."""
+    shape = tuple(int(v) for v in (tex.shape[1:] if per_frame else tex.shape))
+    assert len(shape) in (2, 3) and str(tex.dtype).endswith("uint8")
+    ch = shape[2] if len(shape) == 3 else 1
+    ptr, dev = Handle._buf(tex)
+    t = Texture(ptr.value, shape[1], shape[0], ch, dev, shape[1] * ch, shape[0] * shape[1] * ch if per_frame else 0, int(opacity), 0)
+    t.keep = tex
+    return t
+
+
 class Limits(C.Structure):
     _fields_ = [("max_width", C.c_int32), ("max_height", C.c_int32), ("max_batch", C.c_int32),
                 ("max_thres_planes", C.c_int32), ("triggers_per_frame", C.c_int32), ("contours_per_frame", C.c_int32),
@@ -177,6 +198,7 @@ SYMBOLS = [
     "arucohip_fisheye_undistort_points", "arucohip_fisheye_distort_points", "arucohip_fisheye_undistort",
     "arucohip_fisheye_undistort_markers_batch", "arucohip_fisheye_calibrate", "arucohip_fisheye_calibrate_board_batch",
     "arucohip_warp_plane_batch", "arucohip_rectify_board_window", "arucohip_board_rectify_batch",
+    "arucohip_composite_plane_batch", "arucohip_board_composite_batch",
 ]
 
 _lib = None
@@ -345,6 +367,8 @@ def load():
     L.arucohip_warp_plane_batch.argtypes = [vp, vp, i, i, i, i, sz, sz, i, vp, vp, i, vp, vp, i, vp, i, i, sz, sz, i]
     L.arucohip_rectify_board_window.argtypes = [vp, i, i, f, f, f, i, vp]
     L.arucohip_board_rectify_batch.argtypes = [vp, vp, i, i, i, i, sz, sz, i, vp, i, vp, vp, i, vp, vp, sz, sz, i, vp, vp]
+    L.arucohip_composite_plane_batch.argtypes = [vp, vp, i, i, i, i, sz, sz, i, vp, vp, vp, i, vp, vp, i, vp, i]
+    L.arucohip_board_composite_batch.argtypes = [vp, vp, i, i, i, i, sz, sz, i, vp, i, vp, vp, i, vp, vp, vp, i, vp, vp]
     L.arucohip_default_params.argtypes = [vp]
     L.arucohip_default_limits.argtypes = [vp, i, i, i]
     _lib = L
@@ -1025,6 +1049,16 @@ class Handle:
                                                     0 if da is None else da.size, int(flags)))
         return frames
 
+    @staticmethod
+    def _board_records(boards):
+        """N BOARD_DTYPE entries of the list of dicts board_detect_batch returns; an array passes through."""
+        if isinstance(boards, np.ndarray):
+            return boards
+        b = np.zeros(len(boards), BOARD_DTYPE)
+        for k, d in enumerate(boards):
+            b[k] = (d.get("n_markers", 0), d["has_pose"], d["rvec"], d["tvec"])
+        return b
+
     # ---- plane rectification: the fronto-parallel view of a board's plane, one map per frame
     def warp_plane_device(self, src_ptr, nframes, width, height, channels, maps_ptr, dst_ptr, out_width, out_height, K=None, dist=None,
                           valid_ptr=None, row_stride=None, frame_stride=None, dst_row_stride=None, dst_frame_stride=None, src_on_device=1,
@@ -1078,14 +1112,68 @@ class Handle:
         returns. Returns (images uint8 [N][win.out_height][win.out_width] (x 3), status int32 [N], maps float64 [N][9])."""
         assert isinstance(frames, np.ndarray)
         ptr, n, wid, hgt, ch, rs, fs, _ = self._frames(frames, width, channels)
-        if not isinstance(boards, np.ndarray):
-            b = np.zeros(len(boards), BOARD_DTYPE)
-            for k, d in enumerate(boards):
-                b[k] = (d.get("n_markers", 0), d["has_pose"], d["rvec"], d["tvec"])
-            boards = b
+        boards = self._board_records(boards)
         out = np.zeros((n, win.out_height, win.out_width) if ch == 1 else (n, win.out_height, win.out_width, ch), np.uint8)
         status, maps = self.board_rectify_device(ptr, n, wid, hgt, ch, boards, K, win, _ptr(out), dist, rs, fs, frames_on_device=0, dst_on_device=0,
                                                  report=True)
+        return out, status, maps
+
+    # ---- plane compositing: a texture blended onto the plane of every frame, in place
+    def composite_plane_device(self, frames_ptr, nframes, width, height, channels, tex, maps_ptr, K=None, dist=None, valid_ptr=None, masks_ptr=None,
+                               row_stride=None, frame_stride=None, frames_on_device=1, maps_on_device=1, masks_on_device=1):
+        """arucohip_composite_plane_batch on plain addresses: frame pixel (u, v) of frame f is blended with the Texture `tex` sampled at
+        maps[f] ray(u, v). Strides default to tightly packed. With everything on the device the call is asynchronous on the handle's stream."""
+        rs = width * channels if row_stride is None else row_stride
+        Ka, da = _f32(K), _f32(dist)
+        self._chk(self.L.arucohip_composite_plane_batch(self.h, frames_ptr, int(nframes), int(width), int(height), int(channels), rs,
+                                                        rs * height if frame_stride is None else frame_stride, int(frames_on_device), C.byref(tex),
+                                                        maps_ptr, valid_ptr, int(maps_on_device), _ptr(Ka), _ptr(da), 0 if da is None else da.size,
+                                                        masks_ptr, int(masks_on_device)))
+
+    def composite_plane(self, frames, tex, maps, K=None, dist=None, valid=None, opacity=255, masks=None, per_frame=False, width=None, channels=1):
+        """Host frames uint8 [N][H][W] or [N][H][W][3] (see _frames for padded rows), tex: a uint8 array as texture() takes it (with
+        per_frame one texture per frame) or a Texture, maps float64 [N][3][3] or [N][9], valid: N flags or None, masks: uint8 [N][H][W] or
+        None. Returns the painted frames (a copy)."""
+        assert isinstance(frames, np.ndarray)
+        out = np.ascontiguousarray(frames).copy()
+        ptr, n, wid, hgt, ch, rs, fs, _ = self._frames(out, width, channels)
+        t = tex if isinstance(tex, Texture) else texture(np.ascontiguousarray(tex), opacity, per_frame)
+        m = np.ascontiguousarray(maps, dtype=np.float64).reshape(n, 9)
+        va = None if valid is None else np.ascontiguousarray(valid, dtype=np.int32).reshape(n)
+        ma = None if masks is None else np.ascontiguousarray(masks, dtype=np.uint8).reshape(n, hgt, wid)
+        self.composite_plane_device(ptr, n, wid, hgt, ch, t, _ptr(m), K, dist, _ptr(va), _ptr(ma), rs, fs, frames_on_device=0, maps_on_device=0,
+                                    masks_on_device=0)
+        return out
+
+    def board_composite_device(self, frames_ptr, nframes, width, height, channels, boards, K, win, tex, dist=None, masks_ptr=None, row_stride=None,
+                               frame_stride=None, frames_on_device=1, masks_on_device=1, report=False):
+        """arucohip_board_composite_batch on plain addresses. boards: N BOARD_DTYPE entries (numpy) or a device tensor of N * 56 bytes; tex: a
+        Texture of win's size. With report: returns (status int32 [N], maps float64 [N][9]) and is synchronous; without it device frames,
+        boards, texture and masks make the call asynchronous on the handle's stream."""
+        if isinstance(boards, np.ndarray):
+            assert boards.dtype == BOARD_DTYPE and boards.size == nframes
+        bptr, bdev = self._buf(boards)
+        rs = width * channels if row_stride is None else row_stride
+        Ka, da = _f32(K), _f32(dist)
+        status = np.zeros(nframes, np.int32) if report else None
+        maps = np.zeros((nframes, 9), np.float64) if report else None
+        self._chk(self.L.arucohip_board_composite_batch(self.h, frames_ptr, int(nframes), int(width), int(height), int(channels), rs,
+                                                        rs * height if frame_stride is None else frame_stride, int(frames_on_device), bptr, bdev,
+                                                        _ptr(Ka), _ptr(da), 0 if da is None else da.size, C.byref(win), C.byref(tex), masks_ptr,
+                                                        int(masks_on_device), _ptr(status), _ptr(maps)))
+        return (status, maps) if report else None
+
+    def board_composite(self, frames, boards, K, win, tex, dist=None, opacity=255, masks=None, per_frame=False, width=None, channels=1):
+        """Host frames (as composite_plane) painted with tex on the plane of boards[f]: N BOARD_DTYPE entries, or the list of dicts
+        board_detect_batch returns. Returns (the painted frames, status int32 [N], maps float64 [N][9])."""
+        assert isinstance(frames, np.ndarray)
+        out = np.ascontiguousarray(frames).copy()
+        ptr, n, wid, hgt, ch, rs, fs, _ = self._frames(out, width, channels)
+        boards = self._board_records(boards)
+        t = tex if isinstance(tex, Texture) else texture(np.ascontiguousarray(tex), opacity, per_frame)
+        ma = None if masks is None else np.ascontiguousarray(masks, dtype=np.uint8).reshape(n, hgt, wid)
+        status, maps = self.board_composite_device(ptr, n, wid, hgt, ch, boards, K, win, t, dist, _ptr(ma), rs, fs, frames_on_device=0,
+                                                   masks_on_device=0, report=True)
         return out, status, maps
 
     def board_detect(self, markers, ids, obj, info_type, K=None, dist=None, marker_size=-1.0, repj_err_thres=-1.0, y_perp=False):

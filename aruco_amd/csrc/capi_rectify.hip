@@ -67,21 +67,6 @@ int reserve_scratch(arucohip_handle* h, int n, Scratch* s) {
     return ARUCOHIP_OK;
 }
 
-// rows of `bytes` bytes between a host array with strides (row, frame) and the tightly packed device array `dev`, on h's stream
-int copy_rows(arucohip_handle* h, uint8_t* host, size_t row, size_t frame, size_t bytes, int rows, int n, uint8_t* dev, bool up) {
-    const bool flat = frame == row * (size_t)rows;
-    const int calls = flat ? 1 : n;
-    const size_t per = flat ? (size_t)n * rows : (size_t)rows;
-    for (int i = 0; i < calls; i++) {
-        uint8_t *hp = host + (size_t)i * frame, *dp = dev + (size_t)i * rows * bytes;
-        if (up)
-            HIPCHK(h, hipMemcpy2DAsync(dp, bytes, hp, row, bytes, per, hipMemcpyHostToDevice, h->stream));
-        else
-            HIPCHK(h, hipMemcpy2DAsync(hp, row, dp, bytes, bytes, per, hipMemcpyDeviceToHost, h->stream));
-    }
-    return ARUCOHIP_OK;
-}
-
 // The resampling of a checked call with device maps: host frames go up, host images come back. Queues only; the caller synchronises.
 int warp(arucohip_handle* h, const Call& c, const double* maps, const int32_t* valid) {
     const size_t src_bytes = c.src_on_device ? 0 : ((size_t)c.n * c.h * c.src_row_bytes() + 255) & ~(size_t)255;
@@ -171,8 +156,7 @@ int arucohip_board_rectify_batch(arucohip_handle* h, const uint8_t* frames, int 
     const Call c = {frames, nframes, width, height, channels, row_stride, frame_stride, frames_on_device, K, dist, ndist,
                     dst, win->out_width, win->out_height, dst_row_stride, dst_frame_stride, dst_on_device};
     if (const int rc = check_call(h, c, true)) return rc;
-    const double cross = (double)win->ux * win->vy - (double)win->uy * win->vx;
-    if (!(std::fabs(cross) > 0) || !std::isfinite(cross) || !std::isfinite(win->x0) || !std::isfinite(win->y0))
+    if (!window_spans_plane(*win))
         return fail(h, ARUCOHIP_E_INVALID, "rectify: the window's u and v steps are parallel, zero or not finite");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;

@@ -158,6 +158,8 @@ struct arucohip_handle {
     Mem<uint8_t> d_overlay_frames;    // arucohip_draw_*_batch: staged host frames
     Mem<uint8_t> d_rectify;           // arucohip_warp_plane_batch / arucohip_board_rectify_batch: maps, valid words and staged boards of one call
     Mem<uint8_t> d_rectify_frames;    // ... and its staged host frames and the images a host caller gets
+    Mem<uint8_t> d_composite;         // arucohip_composite_plane_batch / arucohip_board_composite_batch: maps, valid words and staged boards of one call
+    Mem<uint8_t> d_composite_frames;  // ... and its staged host frames, textures and masks
     Mem<uint8_t> d_recover;           // arucohip_board_recover_batch: the board, adoption records and work lists of one call (recover_layout)
     // arucohip_charuco_corners_batch (capi_charuco.hip), on the handle the caller holds: the corner records of the last call and their counts stay in
     // d_charuco for the calibration and the pose; the host keeps the layout and the counts
@@ -201,7 +203,7 @@ struct arucohip_handle {
     //   capture and replay; batches that decode from cell medians neither touch nor move buf.patches, and buf.cells is create-time memory;
     // - neither: the other Buffers arrays, zero_block and h_markers are create-time memory (`held`); d_erode, d_canny and the user decoder's
     //   staging and d_pyr belong to configurations that are not graphed; wt_out is set only inside chunk_enqueue, which does not run this path.
-    //   Memory no captured launch reads (d_bgr, undistortion, fisheye maps and scratch, calibration, marker mapping, camera rigs and the pinned solver state, board and GL batches, planar poses, marker recovery, overlays, plane rectification, EM, HRM, fiducial generation, ChArUco corners and ChromaticMask scratch) may
+    //   Memory no captured launch reads (d_bgr, undistortion, fisheye maps and scratch, calibration, marker mapping, camera rigs and the pinned solver state, board and GL batches, planar poses, marker recovery, overlays, plane rectification and compositing, EM, HRM, fiducial generation, ChArUco corners and ChromaticMask scratch) may
     //   be replaced at any time.
     struct FrameGraph {
         hipGraphExec_t exec = nullptr;
@@ -264,6 +266,27 @@ struct Carver {
         return base ? (T*)(base + here) : nullptr;
     }
 };
+
+// rows of `bytes` bytes between a host array with strides (row, frame) and the tightly packed device array `dev`, on h's stream
+inline int copy_rows(arucohip_handle* h, uint8_t* host, size_t row, size_t frame, size_t bytes, int rows, int n, uint8_t* dev, bool up) {
+    const bool flat = frame == row * (size_t)rows;
+    const int calls = flat ? 1 : n;
+    const size_t per = flat ? (size_t)n * rows : (size_t)rows;
+    for (int i = 0; i < calls; i++) {
+        uint8_t *hp = host + (size_t)i * frame, *dp = dev + (size_t)i * rows * bytes;
+        if (up)
+            HIPCHK(h, hipMemcpy2DAsync(dp, bytes, hp, row, bytes, per, hipMemcpyHostToDevice, h->stream));
+        else
+            HIPCHK(h, hipMemcpy2DAsync(hp, row, dp, bytes, bytes, per, hipMemcpyDeviceToHost, h->stream));
+    }
+    return ARUCOHIP_OK;
+}
+
+// whether a window of a board plane (arucohip_rectify_t) spans it: finite, with u and v steps that are neither zero nor parallel
+inline bool window_spans_plane(const arucohip_rectify_t& win) {
+    const double cross = (double)win.ux * win.vy - (double)win.uy * win.vx;
+    return std::fabs(cross) > 0 && std::isfinite(cross) && std::isfinite(win.x0) && std::isfinite(win.y0);
+}
 
 // fork: the other workers' streams wait for what the first worker's stream (the batch's own) has queued so far; errors are reported on h
 int fork_workers(arucohip_handle* h, const Batch& b);

@@ -236,6 +236,26 @@ struct PlaneWarp {
 void launch_plane_warp(hipStream_t s, const PlaneWarp& a, int cn, bool dist, int nframes);
 // maps[f] / valid[f] of the window `win` on the plane of boards[f]
 void launch_plane_maps(hipStream_t s, const arucohip_board_t* boards, int nframes, const arucohip_rectify_t& win, double* maps, int32_t* valid);
+// Plane compositing (k_composite.hip): frame pixel (u, v) of frame f is blended, in place, with the texture sampled at
+// maps[f] * ray(u, v), the rule arucohip.h states at arucohip_composite_plane_batch. K: the caller's, or the identity without a camera
+// (the ray is then (u, v) bit for bit); k: the Brown coefficients (dist: five iterations of undistort_point, else none). valid and masks
+// may be null. Everything is a device address.
+struct PlaneComposite {
+    uint8_t* frames;
+    size_t row_stride, frame_stride;
+    int width, height;
+    const uint8_t* tex;
+    size_t tex_row_stride, tex_frame_stride;   // tex_frame_stride 0: one texture for every frame
+    int tex_width, tex_height, opacity;
+    const double* maps;     // [nframes][9], row-major
+    const int32_t* valid;   // [nframes]
+    const uint8_t* masks;   // [nframes][height][width]
+    float K[9];
+    double k[8];
+};
+void launch_plane_composite(hipStream_t s, const PlaneComposite& a, int cn, bool alpha, bool dist, int nframes);
+// maps[f] / valid[f]: the signed adjugate of the map of `win` on the plane of boards[f]
+void launch_plane_inverse_maps(hipStream_t s, const arucohip_board_t* boards, int nframes, const arucohip_rectify_t& win, double* maps, int32_t* valid);
 // fisheye lenses (k_fisheye.hip; the model is fisheye_device.h's)
 struct FisheyeCam;
 void launch_fisheye_points(hipStream_t s, const FisheyeCam& cam, const float* src, int n, int undistort, float* dst, uint8_t* valid);

@@ -9,6 +9,7 @@
 //   iu = rint_half_even(clamp(px * 32, -2^31, 2^31 - 1)), sx = iu >> 5, ax = iu & 31 (iv, sy, ay likewise); remap_bilinear at (sx, sy, ax, ay)
 // tests/rectify_ref.py restates it in numpy.
 #include "internal.h"
+#include "plane_device.h"
 #include "pnp_device.h"
 #include "remap_device.h"
 
@@ -82,22 +83,14 @@ __global__ __launch_bounds__(256) void plane_warp_kernel(PlaneWarp a) {
     }
 }
 
-// One lane per frame: the columns of M are R (ux, uy, 0), R (vx, vy, 0) and R (x0, y0, 0) + t, so that M (u, v, 1) is the camera-frame
-// point of output pixel (u, v). A frame without a pose, or with an entry that is not finite, gets valid = 0 and a zero map.
+// One lane per frame: M of plane_device.h, so that M (u, v, 1) is the camera-frame point of output pixel (u, v). A frame without a pose,
+// or with an entry that is not finite, gets valid = 0 and a zero map.
 __global__ __launch_bounds__(64) void plane_maps_kernel(const arucohip_board_t* boards, int nframes, arucohip_rectify_t win, double* maps, int32_t* valid) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= nframes) return;
     const arucohip_board_t b = boards[f];
-    double R[9], M[9];
-    rodrigues_vec2mat(b.rvec, R, nullptr);
-    const double ux = win.ux, uy = win.uy, vx = win.vx, vy = win.vy, x0 = win.x0, y0 = win.y0;
-    bool ok = b.has_pose != 0;
-    for (int i = 0; i < 3; i++) {
-        M[3 * i] = R[3 * i] * ux + R[3 * i + 1] * uy;
-        M[3 * i + 1] = R[3 * i] * vx + R[3 * i + 1] * vy;
-        M[3 * i + 2] = (R[3 * i] * x0 + R[3 * i + 1] * y0) + b.tvec[i];
-    }
-    for (int k = 0; k < 9; k++) ok = ok && isfinite(M[k]);
+    double M[9];
+    const bool ok = plane_map_of_board(b, win, M);
     for (int k = 0; k < 9; k++) maps[(size_t)f * 9 + k] = ok ? M[k] : 0.0;
     valid[f] = ok ? 1 : 0;
 }

@@ -615,6 +615,18 @@ public:
 #endif
 };
 
+// a Board as the batched calls take it: the pose when it carries one (Rvec and Tvec), has_pose = 0 otherwise
+inline arucohip_board_t board_record_(const Board& B) {
+    arucohip_board_t b;
+    std::memset(&b, 0, sizeof(b));
+    b.n_markers = (int32_t)B.size();
+    if (!B.Rvec.empty() && !B.Tvec.empty()) {
+        b.has_pose = 1;
+        for (int k = 0; k < 3; k++) b.rvec[k] = B.Rvec(k), b.tvec[k] = B.Tvec(k);
+    }
+    return b;
+}
+
 // Marker::draw, Board::draw and CvDrawingUtils::draw3dAxis / draw3dCube through the device overlay pass (arucohip_draw_markers_batch /
 // arucohip_draw_boards_batch on the process-wide handle): the frame goes up, is painted and comes back. The reference's primitives, order,
 // colours and geometry; lines are not antialiased and the text uses the library's bitmap font (INTEGRATION.md "drawing"). 8-bit frames
@@ -657,13 +669,7 @@ private:
     }
     static void board_(cv::Mat& image, const Board& B, const CameraParameters& CP, int flags) {
         if (B.empty()) arucohip_throw_(ARUCOHIP_E_INVALID, "drawing: the board holds no marker (B[0].ssize is its scale)", nullptr);
-        arucohip_board_t b;
-        std::memset(&b, 0, sizeof(b));
-        b.n_markers = (int32_t)B.size();
-        if (!B.Rvec.empty() && !B.Tvec.empty()) {
-            b.has_pose = 1;
-            for (int k = 0; k < 3; k++) b.rvec[k] = B.Rvec(k), b.tvec[k] = B.Tvec(k);
-        }
+        const arucohip_board_t b = board_record_(B);
         float K[9], d[8];
         const bool hasK = mat_to_K_(CP.CameraMatrix, K);
         const int nd = mat_to_dist_(CP.Distorsion, d);
@@ -704,13 +710,7 @@ public:
         float K[9], d[8];
         const bool hasK = mat_to_K_(CP.CameraMatrix, K);
         const int nd = mat_to_dist_(CP.Distorsion, d);
-        arucohip_board_t b;
-        std::memset(&b, 0, sizeof(b));
-        b.n_markers = (int32_t)B.size();
-        if (!B.Rvec.empty() && !B.Tvec.empty()) {
-            b.has_pose = 1;
-            for (int k = 0; k < 3; k++) b.rvec[k] = B.Rvec(k), b.tvec[k] = B.Tvec(k);
-        }
+        const arucohip_board_t b = board_record_(B);
         if (win_.out_width < 1 || win_.out_height < 1) arucohip_throw_(ARUCOHIP_E_INVALID, "BoardRectifier::rectify: no window set", nullptr);
         cv::Mat out(win_.out_height, win_.out_width, frame.type());
         SharedHandle_& sh = SharedHandle_::get();
@@ -753,6 +753,61 @@ private:
     static int channels_(const cv::Mat& image) {
         if (image.type() != CV_8UC1 && image.type() != CV_8UC3) arucohip_throw_(ARUCOHIP_E_INVALID, "rectification: CV_8UC1 or CV_8UC3 frames", nullptr);
         return image.type() == CV_8UC3 ? 3 : 1;
+    }
+};
+
+// A picture on the plane a board lies in (arucohip_board_composite_batch on the process-wide handle): the frame goes up, the texture is
+// blended onto the board as the camera sees it and the frame comes back. No reference counterpart. 8-bit frames with 1 or 3 channels; the
+// texture has the frame's channels, or one more (CV_8UC2 / CV_8UC4: the last is straight alpha), and the window's size. A caller that keeps
+// its frames on the device calls the C ABI directly, a whole batch at a time, and copies nothing.
+class BoardCompositor {
+public:
+    // The window the texture covers, as BoardRectifier::setWindow defines it: texel (s, t) lies where output pixel (s, t) of the rectified view lies.
+    void setWindow(const BoardConfiguration& bc, float markerSize, float pxPerUnit, float margin = 0.f, bool flipY = false) {
+        rect_.setWindow(bc, markerSize, pxPerUnit, margin, flipY);
+    }
+    void setWindow(const arucohip_rectify_t& window) { rect_.setWindow(window); }
+    const arucohip_rectify_t& getWindow() const { return rect_.getWindow(); }
+    // texture onto B's plane in `frame`, in place; nothing where mask (CV_8UC1, the frame's size; empty: none) is 0, nothing at all when B
+    // carries no pose
+    void paint(cv::Mat& frame, const Board& B, const CameraParameters& CP, const cv::Mat& texture, int opacity = 255, const cv::Mat& mask = cv::Mat()) const {
+        const int cn = frame.type() == CV_8UC3 ? 3 : 1, tcn = texture_channels_(texture);
+        if (frame.type() != CV_8UC1 && frame.type() != CV_8UC3) arucohip_throw_(ARUCOHIP_E_INVALID, "compositing: CV_8UC1 or CV_8UC3 frames", nullptr);
+        if (!mask.empty() && (mask.type() != CV_8UC1 || mask.rows != frame.rows || mask.cols != frame.cols))
+            arucohip_throw_(ARUCOHIP_E_INVALID, "compositing: the mask is CV_8UC1 of the frame's size", nullptr);
+        float K[9], d[8];
+        const bool hasK = mat_to_K_(CP.CameraMatrix, K);
+        const int nd = mat_to_dist_(CP.Distorsion, d);
+        const arucohip_board_t b = board_record_(B);
+        const arucohip_texture_t tex = {texture.data, texture.cols, texture.rows, tcn, 0, (size_t)texture.step, 0, opacity, 0};
+        std::vector<unsigned char> packed;   // the C call takes masks tightly packed
+        for (int y = 0; y < mask.rows; y++) packed.insert(packed.end(), mask.data + (size_t)y * (size_t)mask.step, mask.data + (size_t)y * (size_t)mask.step + mask.cols);
+        SharedHandle_& sh = SharedHandle_::get();
+        std::lock_guard<std::mutex> lock(sh.mu);
+        arucohip_handle* h = sh.ensure();
+        arucohip_throw_(arucohip_board_composite_batch(h, frame.data, 1, frame.cols, frame.rows, cn, (size_t)frame.step, (size_t)frame.step * frame.rows, 0, &b, 0,
+                                                       hasK ? K : nullptr, nd ? d : nullptr, nd, &rect_.getWindow(), &tex, mask.empty() ? nullptr : packed.data(), 0,
+                                                       nullptr, nullptr),
+                        "BoardCompositor::paint", h);
+    }
+    // texture onto the plane of boards[i] in frames[i]; masks: empty, or one per frame
+    void paint(std::vector<cv::Mat>& frames, const std::vector<Board>& boards, const CameraParameters& CP, const cv::Mat& texture, int opacity = 255,
+               const std::vector<cv::Mat>& masks = std::vector<cv::Mat>()) const {
+        if (frames.size() != boards.size()) arucohip_throw_(ARUCOHIP_E_INVALID, "BoardCompositor::paint: one board per frame", nullptr);
+        if (!masks.empty() && masks.size() != frames.size()) arucohip_throw_(ARUCOHIP_E_INVALID, "BoardCompositor::paint: no masks, or one per frame", nullptr);
+        for (size_t i = 0; i < frames.size(); i++) paint(frames[i], boards[i], CP, texture, opacity, masks.empty() ? cv::Mat() : masks[i]);
+    }
+
+private:
+    BoardRectifier rect_;
+    static int texture_channels_(const cv::Mat& t) {
+#if ARUCOHIP_HAVE_OPENCV
+        if (!t.empty() && t.depth() == CV_8U) return t.channels();
+#else   // the stand-in Mat has no 2- or 4-channel type: no alpha without OpenCV
+        if (!t.empty() && (t.type() == CV_8UC1 || t.type() == CV_8UC3)) return (int)t.elemSize();
+#endif
+        arucohip_throw_(ARUCOHIP_E_INVALID, "compositing: an 8-bit texture", nullptr);
+        return 0;
     }
 };
 #if ARUCOHIP_HAVE_OPENCV && defined(ARUCOHIP_SHIM_DEFINE_DRAWING)

@@ -950,6 +950,75 @@ int arucohip_board_rectify_batch(arucohip_handle* h, const uint8_t* frames, int 
                                  uint8_t* dst, size_t dst_row_stride, size_t dst_frame_stride, int dst_on_device, int32_t* status,
                                  double* maps_out);
 
+/* ---- Plane compositing: a texture (a label, a replacement print, a video) blended onto the plane of every frame, in place, seen through
+ * the camera and its lens and hidden where a mask says so (k_composite.hip). The inverse direction of plane rectification: it runs over
+ * frame pixels and leaves everything outside the texture's footprint untouched. No reference counterpart. */
+typedef struct arucohip_texture {
+    const uint8_t* data;
+    int32_t width, height;      /* 1..16383 each */
+    int32_t channels;           /* the frames' channels, or one more: the last channel is then straight (not premultiplied) alpha */
+    int32_t on_device;
+    size_t row_stride;          /* >= width * channels */
+    size_t frame_stride;        /* 0: one texture for every frame; otherwise frame f takes data + f * frame_stride (a video on the board) */
+    int32_t opacity;            /* 0..255 */
+    int32_t pad_;
+} arucohip_texture_t;
+
+/* The rule for a pixel. Frame f has the 3 x 3 row-major double map N = maps + 9 f, which takes a normalised camera ray to homogeneous
+ * texel coordinates. Frame pixel (u, v), integer indices = pixel centres, is computed in double, in this order, no operation fused:
+ *   1. valid (nframes, may be NULL: all valid) with valid[f] == 0: the frame is untouched; neither its map nor its texture is read.
+ *   2. masks (may be NULL) with masks[(f * height + v) * width + u] == 0: the pixel is untouched. Masks are nframes x height x width
+ *      bytes, tightly packed: the layout arucohip_chromatic_classify_batch writes, where 1 means the board is visible.
+ *   3. The ray. K = NULL: x = u, y = v. Otherwise fx = K[0], fy = K[4], cx = K[2], cy = K[5] as doubles (nothing else of K is used),
+ *      ifx = 1 / fx, ify = 1 / fy, x0 = (u - cx) * ifx, y0 = (v - cy) * ify. ndist == 0: x = x0, y = y0. ndist > 0: the inverse
+ *      Brown model as the pose solvers apply it (cvUndistortPoints), k = dist[0..7] with absent coefficients 0 (k1 k2 p1 p2 k3 k4 k5 k6);
+ *      from x = x0, y = y0, exactly five times:
+ *        r2 = x x + y y, ic = (1 + ((k[7] r2 + k[6]) r2 + k[5]) r2) / (1 + ((k[4] r2 + k[1]) r2 + k[0]) r2)
+ *        dx = 2 k[2] x y + k[3] (r2 + 2 x x), dy = k[2] (r2 + 2 y y) + 2 k[3] x y, x = (x0 - dx) ic, y = (y0 - dy) ic
+ *      The poses were solved through the same function, so the picture lands where the solver thinks the board is.
+ *   4. S = (N0 x + N1 y) + N2, T = (N3 x + N4 y) + N5, Q = (N6 x + N7 y) + N8. Unless Q > 0 (NaN included) the pixel is untouched.
+ *      s = S / Q, t = T / Q (true divisions); if either is not finite the pixel is untouched.
+ *   5. is = the nearest integer, ties to even, of s * 32 clamped to [-2^31, 2^31 - 1]; it from t. The pixel is painted iff
+ *      0 <= is <= 32 (tex.width - 1) and 0 <= it <= 32 (tex.height - 1): the sampling position lies inside the box of texel centres, so
+ *      every tap with a non-zero weight is inside the texture and nothing darkens at the rim. Integer texel coordinates are texel
+ *      centres: the outermost half texel of the texture is therefore not shown.
+ *   6. Per frame channel c, C_c = the bilinear sample of arucohip_undistort's remap (as step 6 of arucohip_warp_plane_batch) of the
+ *      texture at (is >> 5, it >> 5, is & 31, it & 31). A = 255 without an alpha channel, else the same sample of the texture's last
+ *      channel. w = (A * opacity + 127) / 255 by integer division. w == 0: the pixel is untouched. Otherwise
+ *      out_c = (C_c * w + frame_c * (255 - w) + 127) / 255; with w == 255 that is C_c exactly.
+ * A pixel that is not painted keeps its value; bytes between width * channels and row_stride are never written. Minification aliases:
+ * every frame pixel takes one bilinear sample, so the caller brings a texture of a resolution that suits the board's size in the frame.
+ * frames: nframes frames of `channels` (1 or 3) interleaved 8-bit channels, width and height 1..16383. maps_on_device covers maps and
+ * valid. K (may be NULL) and dist (ndist = 0, 4, 5 or 8 floats; needs K) are host arrays. With frames, texture, maps and masks all on the
+ * device the call is asynchronous on the handle's stream, behind whatever is queued there (detect -> board pose -> classify -> composite
+ * needs no host round trip); otherwise it returns when the frames are done: host frames go up, are painted and come back row by row, so
+ * the caller's padding stays as it was. Uses scratch of its own: the single-frame graph and the last batch stay valid.
+ * ARUCOHIP_E_INVALID, with a message that names it and before anything runs: a null h, frames, tex, tex->data or maps; channels not 1
+ * or 3; tex->channels not channels or channels + 1; opacity outside 0..255; a size below 1 or above 16383 (frames and texture); a stride
+ * smaller than a row or a frame (tex->frame_stride may be 0); ndist not 0, 4, 5 or 8, dist without K, ndist > 0 with dist NULL;
+ * nframes < 1; the texture or the masks overlapping the frames. */
+int arucohip_composite_plane_batch(arucohip_handle* h, uint8_t* frames, int nframes, int width, int height, int channels,
+                                   size_t row_stride, size_t frame_stride, int frames_on_device, const arucohip_texture_t* tex,
+                                   const double* maps, const int32_t* valid, int maps_on_device, const float* K, const float* dist,
+                                   int ndist, const uint8_t* masks, int masks_on_device);
+
+/* The texture is laid on the plane of boards[f] in frame f. The window has the meaning it has for arucohip_board_rectify_batch: texel
+ * (s, t) lies at plane point (x0 + s ux + t vx, y0 + s uy + t vy); win->out_width / out_height must equal the texture's size. K is
+ * required. With M the map of arucohip_board_rectify_batch (texel -> camera-frame point), the map is its signed adjugate, products unfused:
+ *   N0 = M4 M8 - M5 M7, N1 = M2 M7 - M1 M8, N2 = M1 M5 - M2 M4, N3 = M5 M6 - M3 M8, N4 = M0 M8 - M2 M6, N5 = M2 M3 - M0 M5,
+ *   N6 = M3 M7 - M4 M6, N7 = M1 M6 - M0 M7, N8 = M0 M4 - M1 M3, det = (M0 N0 + M1 N3) + M2 N6
+ * det > 0 keeps N, det < 0 negates all nine entries: Q > 0 then holds exactly for rays that meet the plane in front of the camera,
+ * whichever way the window is handed. With det zero or not finite, or without a pose, the frame is invalid: a zero map, status[f] = 0,
+ * the frame untouched. The rest is arucohip_composite_plane_batch. status (host, may be NULL) and maps_out (host, may be NULL: the
+ * nframes x 9 maps N actually used) make the call wait; without them, and with frames, boards, texture and masks on the device, it is
+ * asynchronous on the handle's stream. ARUCOHIP_E_INVALID as above, and for null boards or win, a missing K, a window whose size differs
+ * from the texture's or whose u and v steps are parallel, zero or not finite. */
+int arucohip_board_composite_batch(arucohip_handle* h, uint8_t* frames, int nframes, int width, int height, int channels,
+                                   size_t row_stride, size_t frame_stride, int frames_on_device, const arucohip_board_t* boards,
+                                   int boards_on_device, const float* K, const float* dist, int ndist, const arucohip_rectify_t* win,
+                                   const arucohip_texture_t* tex, const uint8_t* masks, int masks_on_device, int32_t* status,
+                                   double* maps_out);
+
 /* Execution time of the dominant streaming kernel (the 16-pixel-per-lane adaptive threshold kernel) from the device's constant-rate
  * clock: every wave leaves its first and last reading, *total_ms = sum over the launches since arucohip_enable_timing(h, 1) of
  * (last wave's end - first wave's start), *launches = their number (0 when another threshold kernel ran: use the event times).
