@@ -142,6 +142,44 @@ def texture(tex, opacity=255, per_frame=False):
     return t
 
 
+class FrameFormat(C.Structure):
+    """arucohip_frame_format_t: how a caller's frames are stored (camera-native input). bits belongs to GRAY16, chroma_offset to NV12."""
+    _fields_ = [("format", C.c_int32), ("bits", C.c_int32), ("chroma_offset", C.c_uint64)]
+
+    def min_row_stride(self, width):
+        """Bytes of a row that are read (0: invalid format, bits or width)."""
+        return int(load().arucohip_frame_min_row_stride(C.byref(self), int(width)))
+
+    def min_stride(self, width, height, row_stride=None):
+        """Bytes of one frame from its first to its last byte read (0: invalid)."""
+        rs = self.min_row_stride(width) if row_stride is None else row_stride
+        return int(load().arucohip_frame_min_stride(C.byref(self), int(width), int(height), rs))
+
+
+# arucohip_pixel_format
+(PIX_GRAY8, PIX_BGR8, PIX_RGB8, PIX_BGRA8, PIX_RGBA8, PIX_GRAY16, PIX_YUYV, PIX_UYVY, PIX_NV12, PIX_BAYER_RGGB, PIX_BAYER_BGGR, PIX_BAYER_GRBG,
+ PIX_BAYER_GBRG) = range(13)
+PIX_NAMES = ("GRAY8", "BGR8", "RGB8", "BGRA8", "RGBA8", "GRAY16", "YUYV", "UYVY", "NV12", "BAYER_RGGB", "BAYER_BGGR", "BAYER_GRBG", "BAYER_GBRG")
+
+
+def frame_format(fmt, bits=0, chroma_offset=0):
+    """A FrameFormat from a PIX_* value or its name ("NV12", "BAYER_RGGB", ...)."""
+    return FrameFormat(PIX_NAMES.index(fmt.upper()) if isinstance(fmt, str) else int(fmt), int(bits), int(chroma_offset))
+
+
+def gray16(bits=16):
+    return FrameFormat(PIX_GRAY16, int(bits), 0)
+
+
+def nv12(chroma_offset=0):
+    return FrameFormat(PIX_NV12, 0, int(chroma_offset))
+
+
+def bayer(pattern):
+    """pattern: the top-left 2 x 2 block row by row, "RGGB", "BGGR", "GRBG" or "GBRG"."""
+    return frame_format("BAYER_" + pattern)
+
+
 class Limits(C.Structure):
     _fields_ = [("max_width", C.c_int32), ("max_height", C.c_int32), ("max_batch", C.c_int32),
                 ("max_thres_planes", C.c_int32), ("triggers_per_frame", C.c_int32), ("contours_per_frame", C.c_int32),
@@ -199,6 +237,7 @@ SYMBOLS = [
     "arucohip_fisheye_undistort_markers_batch", "arucohip_fisheye_calibrate", "arucohip_fisheye_calibrate_board_batch",
     "arucohip_warp_plane_batch", "arucohip_rectify_board_window", "arucohip_board_rectify_batch",
     "arucohip_composite_plane_batch", "arucohip_board_composite_batch",
+    "arucohip_frame_min_row_stride", "arucohip_frame_min_stride", "arucohip_convert_batch",
 ]
 
 _lib = None
@@ -369,6 +408,11 @@ def load():
     L.arucohip_board_rectify_batch.argtypes = [vp, vp, i, i, i, i, sz, sz, i, vp, i, vp, vp, i, vp, vp, sz, sz, i, vp, vp]
     L.arucohip_composite_plane_batch.argtypes = [vp, vp, i, i, i, i, sz, sz, i, vp, vp, vp, i, vp, vp, i, vp, i]
     L.arucohip_board_composite_batch.argtypes = [vp, vp, i, i, i, i, sz, sz, i, vp, i, vp, vp, i, vp, vp, vp, i, vp, vp]
+    L.arucohip_frame_min_row_stride.argtypes = [vp, i]
+    L.arucohip_frame_min_row_stride.restype = sz
+    L.arucohip_frame_min_stride.argtypes = [vp, i, i, sz]
+    L.arucohip_frame_min_stride.restype = sz
+    L.arucohip_convert_batch.argtypes = [vp, vp, vp, i, i, i, sz, sz, i, i, vp, sz, sz, i]
     L.arucohip_default_params.argtypes = [vp]
     L.arucohip_default_limits.argtypes = [vp, i, i, i]
     _lib = L
@@ -605,6 +649,35 @@ class Handle:
         self._chk(self.L.arucohip_detect_batch_bgr(self.h, _ptr(fr), nf, w, h, 3 * w, 3 * w * h, 0, _ptr(Ka), _ptr(da),
                                                    0 if da is None else da.size, float(marker_size), int(bool(y_perp)), _ptr(out), cap, _ptr(n), 0))
         return [out[f, :n[f]].copy() for f in range(nf)]
+
+    # ---- camera-native input: fmt is a FrameFormat; host arrays are uint8 [n][rows][row bytes] exactly as the producer stores them
+    # (NV12: rows = height * 3 / 2 with the U,V plane behind the Y plane; GRAY16: a uint16 array [n][H][W] is taken as its bytes)
+    @staticmethod
+    def _raw_frames(frames, fmt, width, height):
+        a = np.ascontiguousarray(frames)
+        if a.dtype == np.uint16:
+            a = a.view(np.uint8)
+        assert a.dtype == np.uint8 and a.ndim == 3
+        n, rows, row_bytes = a.shape
+        w = width if width is not None else row_bytes // max(fmt.min_row_stride(2) // 2, 1)   # tight rows: bytes per pixel from a 2-pixel row
+        h = height if height is not None else (rows * 2 // 3 if fmt.format == PIX_NV12 else rows)
+        return a, n, w, h, row_bytes, rows * row_bytes
+
+    def convert(self, frames, fmt, channels, width=None, height=None):
+        """arucohip_convert_batch of host frames: -> uint8 [n][H][W] (channels = 1) or [n][H][W][3] (B,G,R)."""
+        a, n, w, h, rs, fs = self._raw_frames(frames, fmt, width, height)
+        out = np.empty((n, h, w) if channels == 1 else (n, h, w, channels), np.uint8)
+        self._chk(self.L.arucohip_convert_batch(self.h, _ptr(a), C.byref(fmt), n, w, h, rs, fs, 0, int(channels), _ptr(out), w * channels,
+                                                w * h * channels, 0))
+        return out
+
+    def convert_device(self, src_ptr, fmt, nframes, width, height, row_stride, frame_stride, channels, dst_ptr, dst_row_stride=None,
+                       dst_frame_stride=None, src_on_device=True, dst_on_device=True):
+        """arucohip_convert_batch on pointers (plain integers); with dst_on_device asynchronous on the handle's stream."""
+        drs = width * channels if dst_row_stride is None else dst_row_stride
+        dfs = drs * height if dst_frame_stride is None else dst_frame_stride
+        self._chk(self.L.arucohip_convert_batch(self.h, C.c_void_p(src_ptr), C.byref(fmt), nframes, width, height, row_stride, frame_stride,
+                                                int(bool(src_on_device)), int(channels), C.c_void_p(dst_ptr), drs, dfs, int(bool(dst_on_device))))
 
     def undistort(self, img, K, dist):
         """cv::undistort of host frames: [H][W], [H][W][3], [N][H][W] (gray batch) -> same shape."""

@@ -228,6 +228,9 @@ struct arucohip_handle {
         int32_t* n_out = nullptr;
     } pend;
     std::string err;
+    // arucohip_convert_batch (capi_ingest.hip): the raw host frames of one call, and the converted frames a host caller gets
+    Mem<uint8_t> d_ingest_src;
+    Mem<uint8_t> d_ingest;
 };
 
 #define HIPCHK(h, expr)                                                                         \

@@ -211,6 +211,15 @@ __device__ __forceinline__ void throughput_bound_priority() { if (LBP_PRIO_HEAVY
 
 // ---- kernel launchers (host side, defined in the .hip files)
 void launch_bgr2gray(hipStream_t s, const uint8_t* bgr, size_t row_stride, size_t frame_stride, int width, int height, int nframes, uint8_t* gray);
+// How a caller's frames are stored (arucohip_frame_format_t as the host code carries it): format is an arucohip_pixel_format, bits belongs to
+// GRAY16, chroma_offset to NV12 (0: the U,V plane follows the Y plane's last row)
+struct FrameFmt {
+    int format, bits;
+    size_t chroma_offset;
+};
+// camera-native frames (k_ingest.hip) -> dst_channels = 1 (grey) or 3 (B,G,R) at dst_row_stride / dst_frame_stride; fmt and the geometry are valid
+void launch_ingest(hipStream_t s, const FrameFmt& fmt, const uint8_t* src, size_t row_stride, size_t frame_stride, int width, int height, int nframes,
+                   int dst_channels, uint8_t* dst, size_t dst_row_stride, size_t dst_frame_stride);
 // cv::pyrDown of nframes 8-bit frames (k_pyrdown.hip): W x H at src_row / src_frame -> (W + 1) / 2 x (H + 1) / 2 at dst_row / dst_frame
 void launch_pyr_down(hipStream_t s, const uint8_t* src, size_t src_row, size_t src_frame, int W, int H, int nframes, uint8_t* dst, size_t dst_row,
                      size_t dst_frame);

@@ -5,11 +5,10 @@
 //   gray = (B*1868 + G*9617 + R*4899 + 8192) >> 14
 // (coefficients 0.114, 0.587, 0.299 in 14 bits), restated in oracle/orc_imgproc.cpp and used by tests/golden/make_fixtures.py.
 // Streaming kernel: a lane turns 4 pixels (three dwords in, one dword out), so a wave reads 768 and writes 256 contiguous bytes.
+#include "convert_device.h"   // gray_of
 #include "internal.h"
 
 namespace ah {
-
-__device__ __forceinline__ uint32_t gray_of(uint32_t b, uint32_t g, uint32_t r) { return (b * 1868u + g * 9617u + r * 4899u + 8192u) >> 14; }
 
 __global__ __launch_bounds__(256) void bgr2gray_kernel(const uint8_t* __restrict__ bgr, size_t row_stride, size_t frame_stride, int width, int height,
                                                        uint8_t* __restrict__ gray, int fast) {

@@ -356,6 +356,42 @@ inline void undistort(const cv::Mat& src, cv::Mat& dst, const cv::Mat& cameraMat
     dst = out;
 }
 
+// Camera-native input (include/arucohip.h, "Camera-native input"): a frame as a camera or a video decoder delivers it, in host memory.
+// No counterpart in the reference, which takes what cv::VideoCapture hands it.
+enum class PixelFormat {
+    GRAY8 = ARUCOHIP_PIX_GRAY8, BGR8 = ARUCOHIP_PIX_BGR8, RGB8 = ARUCOHIP_PIX_RGB8, BGRA8 = ARUCOHIP_PIX_BGRA8, RGBA8 = ARUCOHIP_PIX_RGBA8,
+    GRAY16 = ARUCOHIP_PIX_GRAY16, YUYV = ARUCOHIP_PIX_YUYV, UYVY = ARUCOHIP_PIX_UYVY, NV12 = ARUCOHIP_PIX_NV12,
+    BAYER_RGGB = ARUCOHIP_PIX_BAYER_RGGB, BAYER_BGGR = ARUCOHIP_PIX_BAYER_BGGR, BAYER_GRBG = ARUCOHIP_PIX_BAYER_GRBG,
+    BAYER_GBRG = ARUCOHIP_PIX_BAYER_GBRG
+};
+struct RawFrame {
+    const void* data;      // host memory
+    int width, height;     // pixels
+    size_t step;           // bytes between rows (of both planes of NV12)
+    PixelFormat format;
+    int bits;              // GRAY16 only: 8..16
+    size_t chromaOffset;   // NV12 only: bytes from data to the U,V plane; 0: step * height
+};
+// one host frame through arucohip_convert_batch on handle h into a new CV_8UC1 (channels = 1) or CV_8UC3 (B,G,R) image
+inline void convert_frame_(arucohip_handle* h, const RawFrame& in, cv::Mat& dst, int channels) {
+    if (channels != 1 && channels != 3) arucohip_throw_(ARUCOHIP_E_INVALID, "convertFrame: channels is 1 or 3", nullptr);
+    if (!in.data || in.width < 1 || in.height < 1) arucohip_throw_(ARUCOHIP_E_INVALID, "convertFrame: empty frame", nullptr);
+    arucohip_frame_format_t fmt;
+    fmt.format = (int32_t)in.format, fmt.bits = in.bits, fmt.chroma_offset = in.chromaOffset;
+    cv::Mat out(in.height, in.width, channels == 3 ? CV_8UC3 : CV_8UC1);
+    const size_t fs = arucohip_frame_min_stride(&fmt, in.width, in.height, in.step);   // one frame: never used as a stride
+    arucohip_throw_(arucohip_convert_batch(h, in.data, &fmt, 1, in.width, in.height, in.step, fs, 0, channels, out.data, out.step,
+                                           (size_t)in.height * out.step, 0),
+                    "convertFrame", h);
+    dst = out;
+}
+// The conversion alone, on the process-wide handle: dst becomes CV_8UC1 (channels = 1) or CV_8UC3 in B,G,R order (channels = 3).
+inline void convertFrame(const RawFrame& src, cv::Mat& dst, int channels) {
+    SharedHandle_& sh = SharedHandle_::get();
+    std::lock_guard<std::mutex> lock(sh.mu);
+    convert_frame_(sh.ensure(src.width, src.height), src, dst, channels);
+}
+
 // cv::calibrateCamera(objectPoints, imagePoints, imageSize, cameraMatrix, distCoeffs, rvecs, tvecs, flags) for planar views
 // (utils/aruco_calibration.cpp's call) on the process-wide handle. flags: cv::CALIB_* values (ARUCOHIP_CALIB_*). Returns the RMS
 // reprojection error; cameraMatrix (3x3), distCoeffs (1x5), rvecs / tvecs (3x1 each) come back as CV_64F.
@@ -1226,6 +1262,23 @@ public:
     void detect(const cv::Mat& input, std::vector<Marker>& detectedMarkers, const CameraParameters& camParams, float markerSizeMeters = -1,
                 bool setYPerpendicular = false) {
         detect(input, detectedMarkers, camParams.CameraMatrix, camParams.Distorsion, markerSizeMeters, setYPerpendicular);
+    }
+    // A camera-native host frame: GRAY8 and the Y plane of NV12 are grey frames as they lie; every other format is converted to grey on the
+    // device (arucohip_convert_batch), and the grey image then takes the path of detect(cv::Mat).
+    void detect(const RawFrame& input, std::vector<Marker>& detectedMarkers, const CameraParameters& camParams = CameraParameters(),
+                float markerSizeMeters = -1, bool setYPerpendicular = false) {
+        arucohip_frame_format_t fmt;
+        fmt.format = (int32_t)input.format, fmt.bits = input.bits, fmt.chroma_offset = input.chromaOffset;
+        if (!input.data || !arucohip_frame_min_stride(&fmt, input.width, input.height, input.step))
+            arucohip_throw_(ARUCOHIP_E_INVALID, "detect: RawFrame with an invalid format, size, step or chromaOffset", nullptr);
+        cv::Mat grey;
+        if (input.format == PixelFormat::GRAY8 || input.format == PixelFormat::NV12) {
+            grey = cv::Mat(input.height, input.width, CV_8UC1, const_cast<void*>(input.data), input.step);
+        } else {
+            ensure_(input.width, input.height);
+            convert_frame_(h_, input, grey, 1);
+        }
+        detect(grey, detectedMarkers, camParams.CameraMatrix, camParams.Distorsion, markerSizeMeters, setYPerpendicular);
     }
 
 #if ARUCOHIP_HAVE_OPENCV

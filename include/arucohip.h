@@ -274,6 +274,74 @@ int arucohip_detect_batch_bgr(arucohip_handle* h, const uint8_t* frames, int nfr
                               int out_on_device);
 /* The conversion alone: one host BGR frame -> host gray frame (width*height bytes). */
 int arucohip_bgr_to_gray(arucohip_handle* h, const uint8_t* bgr, int width, int height, size_t row_stride, uint8_t* gray);
+
+/* Camera-native input (k_ingest.hip, capi_ingest.hip) - frames as cameras and decoders deliver them, converted on the device
+ * (arucohip_convert_batch) to the 8-bit grey image the pipeline reads or to interleaved B,G,R for the colour consumers (arucohip_chromatic_*, arucohip_draw_*_batch,
+ * arucohip_board_composite_batch, arucohip_warp_plane_batch, arucohip_undistort). All arithmetic is integer; >> of a negative value is
+ * the floor shift; sat clamps to 0..255; gray_of(b, g, r) = (b*1868 + g*9617 + r*4899 + 8192) >> 14 as for arucohip_detect_bgr.
+ * The YUV and Bayer definitions are this library's own and have no reference counterpart (the reference takes what cv::VideoCapture
+ * hands it); nothing here claims bit-identity with OpenCV beyond what arucohip_detect_bgr claims.
+ *   GRAY8                  1 byte per pixel. Grey: the byte; BGR: the byte three times.
+ *   BGR8                   3 interleaved bytes, row_stride >= 3 * width. Grey: gray_of(b, g, r), the bytes of arucohip_bgr_to_gray.
+ *   RGB8, BGRA8, RGBA8     3 / 4 interleaved bytes, row_stride >= 3 / 4 * width. Grey: gray_of(b, g, r). BGR: reordered, alpha ignored.
+ *   GRAY16, bits = 8..16   little-endian uint16, row_stride >= 2 * width; neither rows nor the base need 2-byte alignment.
+ *                          Grey: min(v >> (bits - 8), 255); BGR: that value three times. An MSB-aligned decoder plane (P010 / P016
+ *                          luma) is bits = 16.
+ *   YUYV (Y0 U Y1 V), UYVY (U Y0 V Y1)   2 bytes per pixel, width even, row_stride >= 2 * width. Grey: the Y byte. BGR: the formula
+ *                          below, U and V shared by the pixel pair.
+ *   NV12                   Y plane of `height` rows, then an interleaved U,V plane of height / 2 rows with the same row_stride that
+ *                          starts chroma_offset bytes after the frame's start (0: row_stride * height). width and height even,
+ *                          row_stride >= width, chroma_offset >= row_stride * height when given, frame_stride covers both planes.
+ *                          Grey: the Y plane. BGR: the formula below with U, V of chroma sample (x / 2, y / 2).
+ *   BAYER_RGGB, _BGGR, _GRBG, _GBRG      1 byte per pixel; the name is the top-left 2 x 2 block row by row. width, height >= 2, odd sizes
+ *                          allowed. BGR: the bilinear demosaic below. Grey: gray_of of the demosaiced pixel.
+ * YUV -> BGR, BT.601 video range in 20-bit fixed point (round of 1.164, 1.596, 0.813, 0.391, 2.018 times 2^20):
+ *     y = max(0, Y - 16) * 1220542
+ *     R = sat((y + 1673527 * (V - 128) + 524288) >> 20)
+ *     G = sat((y - 852492 * (V - 128) - 409993 * (U - 128) + 524288) >> 20)
+ *     B = sat((y + 2116026 * (U - 128) + 524288) >> 20)
+ * Bayer -> BGR: neighbours outside the image by reflect-101 (-1 -> 1, N -> N - 2; it keeps the mosaic's colour parity). At a site of
+ * colour C the channel C is the sample. At a red or blue site green = (N + S + E + W + 2) >> 2 and the opposite colour =
+ * (NW + NE + SW + SE + 2) >> 2. At a green site the colour of its row's other sites = (W + E + 1) >> 1 and the colour of its column's
+ * other sites = (N + S + 1) >> 1.
+ * Out of scope: full-range (JPEG) YUV and BT.709, planar I420 / YV12, packed 10 / 12-bit (MIPI) rows, 16-bit Bayer, big-endian 16-bit
+ * data, and the multi-GPU entry points (arucohip_mgpu_*: convert first, then shard the grey frames). */
+typedef enum {
+    ARUCOHIP_PIX_GRAY8 = 0, ARUCOHIP_PIX_BGR8, ARUCOHIP_PIX_RGB8, ARUCOHIP_PIX_BGRA8, ARUCOHIP_PIX_RGBA8,
+    ARUCOHIP_PIX_GRAY16, ARUCOHIP_PIX_YUYV, ARUCOHIP_PIX_UYVY, ARUCOHIP_PIX_NV12,
+    ARUCOHIP_PIX_BAYER_RGGB, ARUCOHIP_PIX_BAYER_BGGR, ARUCOHIP_PIX_BAYER_GRBG, ARUCOHIP_PIX_BAYER_GBRG
+} arucohip_pixel_format;
+typedef struct {
+    int32_t format;          /* arucohip_pixel_format */
+    int32_t bits;            /* GRAY16 only, else 0 */
+    uint64_t chroma_offset;  /* NV12 only */
+} arucohip_frame_format_t;
+/* Host arithmetic. The bytes of a row the library reads (0: the format, its bits or the width are invalid), and the bytes of one frame
+ * from its first to its last byte read, which frame_stride must cover when a call has more than one frame (0: invalid format, size,
+ * row_stride or chroma_offset): row_stride * (height - 1) + the row's bytes; NV12: chroma_offset + row_stride * (height / 2 - 1) + width. */
+size_t arucohip_frame_min_row_stride(const arucohip_frame_format_t* fmt, int width);
+size_t arucohip_frame_min_stride(const arucohip_frame_format_t* fmt, int width, int height, size_t row_stride);
+/* The conversion as a stage of its own, like arucohip_undistort / arucohip_pyr_down: dst_channels = 1 (grey) or 3 (B,G,R); dst rows are
+ * dst_row_stride apart (>= width * dst_channels), frames dst_frame_stride apart (they cover dst_row_stride * (height - 1) + width * dst_channels bytes);
+ * the bytes between are never written. src and dst in host or device memory; nframes and the size within the handle's limits. With
+ * dst_on_device the call is asynchronous on the handle's stream, so arucohip_detect_batch(frames_on_device = 1) on the grey result, or a
+ * colour consumer on the B,G,R result, can follow without a round trip; host src frames (pinned memory in particular, whose copies are
+ * only queued when the call returns) must then stay untouched until the stream has passed the call (arucohip_synchronize, or whatever
+ * completes the work queued behind it). Host frames are copied raw (arucohip_frame_min_row_stride bytes
+ * per row; of NV12 with dst_channels = 1 the Y plane only) and converted on the device: a Bayer or NV12 frame crosses the link with a
+ * third of the bytes of its BGR form. Everything is checked before anything runs: ARUCOHIP_E_INVALID for an unknown format, bits
+ * outside 8..16, an odd width (YUYV / UYVY / NV12) or height (NV12), a Bayer frame below 2 x 2, strides below the minimum,
+ * dst_channels other than 1 or 3 and a dst that overlaps src; the last batch's results stay as they were.
+ * The detection calls carry no format: convert to grey (dst_channels = 1, dst_on_device = 1) and hand the result to
+ * arucohip_detect_batch / arucohip_detect_batch_submit / arucohip_detect_batch_retry_overflowed with frames_on_device = 1. The Y plane
+ * of an NV12 device frame needs no conversion: it is a grey frame with the same row_stride and frame_stride.
+ * A host Bayer batch therefore takes a device buffer the caller owns and two calls:
+ *     arucohip_frame_format_t f = {ARUCOHIP_PIX_BAYER_RGGB, 0, 0};              // d_grey: n * w * h bytes of device memory
+ *     arucohip_convert_batch(h, bayer, &f, n, w, h, w, (size_t)w * h, 0, 1, d_grey, w, (size_t)w * h, 1);
+ *     arucohip_detect_batch(h, d_grey, n, w, h, w, (size_t)w * h, 1, K, dist, ndist, size, 0, out, cap, n_out, 0);   // waits, fills out */
+int arucohip_convert_batch(arucohip_handle* h, const void* src, const arucohip_frame_format_t* fmt, int nframes, int width, int height,
+                           size_t row_stride, size_t frame_stride, int src_on_device, int dst_channels, uint8_t* dst,
+                           size_t dst_row_stride, size_t dst_frame_stride, int dst_on_device);
 /* SURVEY §8 row f3 — lens undistortion of the frames on the device: cv::undistort(src, dst, CameraMatrix, Distorsion), which
  * the reference's GL apps run on every frame before detect() (utils/aruco_test_gl.cpp:237-240, utils/aruco_test_board_gl.cpp:
  * 265-268; detect is then called with an empty distortion vector). 8-bit frames with `channels` = 1 or 3 interleaved channels;
