@@ -202,6 +202,7 @@ SYMBOLS = [
     "arucohip_get_thresholded", "arucohip_get_candidates", "arucohip_threshold", "arucohip_detect_rectangles",
     "arucohip_warp", "arucohip_debug_num_contours", "arucohip_debug_contour", "arucohip_debug_candidates", "arucohip_debug_otsu",
     "arucohip_debug_cells", "arucohip_debug_start_candidates",
+    "arucohip_debug_threshold_batch", "arucohip_debug_threshold_plan", "arucohip_debug_threshold_plane",
     "arucohip_board_detect", "arucohip_calculate_extrinsics", "arucohip_stage_times", "arucohip_stage_name",
     "arucohip_enable_timing", "arucohip_kernel_times", "arucohip_threshold_exec_ms", "arucohip_kernel_name",
     "arucohip_debug_counters", "arucohip_board_detect_batch",
@@ -298,6 +299,9 @@ def load():
     L.arucohip_kernel_name.argtypes = [i]
     L.arucohip_debug_counters.argtypes = [vp, vp]
     L.arucohip_debug_start_candidates.argtypes = [vp, i, i, vp, i, vp]
+    L.arucohip_debug_threshold_batch.argtypes = [vp, vp, i, i, i, C.c_size_t, C.c_size_t, i, i]
+    L.arucohip_debug_threshold_plan.argtypes = [vp, vp, i, vp]
+    L.arucohip_debug_threshold_plane.argtypes = [vp, i, i, vp, vp, vp]
     L.arucohip_board_detect_batch.argtypes = [vp, i, vp, vp, i, i, vp, vp, i, f, f, i, vp, vp]
     L.arucohip_default_recover.argtypes = [vp]
     L.arucohip_default_recover.restype = None
@@ -949,6 +953,42 @@ class Handle:
         out = np.empty(shape, np.uint8)
         self._chk(self.L.arucohip_get_thresholded(self.h, frame, _ptr(out)))
         return out
+
+    def debug_threshold_batch(self, frames, nframes=None, width=None, height=None, row_stride=None, frame_stride=None, want_bytes=False):
+        """arucohip_debug_threshold_batch: the threshold stage alone, with the handle's parameters. frames: a device address (an int; nframes,
+        width and height are then required) or a host array [nframes][height][width]."""
+        if isinstance(frames, int):
+            ptr, on_dev = C.c_void_p(frames), 1
+        else:
+            fr = np.ascontiguousarray(frames, np.uint8)
+            nframes, height, width = fr.shape
+            ptr, on_dev = _ptr(fr), 0
+        rs = width if row_stride is None else row_stride
+        fs = rs * height if frame_stride is None else frame_stride
+        self._chk(self.L.arucohip_debug_threshold_batch(self.h, ptr, int(nframes), int(width), int(height), rs, fs, on_dev, int(bool(want_bytes))))
+
+    THR_FAMILIES = ("strip", "wide", "eo")
+
+    def debug_threshold_plan(self):
+        """arucohip_debug_threshold_plan: {"planes": [{"family", "R", "p16", "fast", "seg"}, ...], "strips", "no_bytes", "bitmap_pass"} of the last
+        threshold launch."""
+        out = np.zeros(5 * 16 + 3, np.int32)
+        n = C.c_int(0)
+        self._chk(self.L.arucohip_debug_threshold_plan(self.h, _ptr(out), out.size, C.byref(n)))
+        k = n.value
+        planes = [{"family": self.THR_FAMILIES[out[5 * t]], "R": int(out[5 * t + 1]), "p16": bool(out[5 * t + 2]), "fast": bool(out[5 * t + 3]),
+                   "seg": int(out[5 * t + 4])} for t in range(k)]
+        return {"planes": planes, "strips": int(out[5 * k]), "no_bytes": bool(out[5 * k + 1]), "bitmap_pass": bool(out[5 * k + 2])}
+
+    def debug_threshold_plane(self, frame, t, width, height):
+        """arucohip_debug_threshold_plane: (bytes [height][width], tiles [tiles_y][tiles_x], tile_bits [tiles_y][2 * strips]) of plane t of a frame
+        of the last batch."""
+        tnx, tny, ns = max(4, (width + 7) // 8 + 1), max(4, (height + 7) // 8 + 1), (width + 1023) // 1024
+        b = np.empty((height, width), np.uint8)
+        tl = np.empty((tny, tnx), np.uint64)
+        tb = np.empty((tny, 2 * ns), np.uint64)
+        self._chk(self.L.arucohip_debug_threshold_plane(self.h, int(frame), int(t), _ptr(b), _ptr(tl), _ptr(tb)))
+        return b, tl, tb
 
     def candidates(self, frame=0, cap=512):
         q = np.zeros((cap, 4, 2), np.float32)

@@ -277,7 +277,11 @@ static int create_handle(const arucohip_params_t* params, int device, const aruc
     const size_t bits_bytes = P * (size_t)tiles_x(lim->max_width) * tiles_y(lim->max_height) * sizeof(uint64_t) + 64;
     ALLOC(b.tiles, bits_bytes);
     if ((e = hipMemset(b.tiles, 0, bits_bytes)) != hipSuccess) return bail(e);   // pad tiles must read as zero
-    ALLOC(b.tile_bits, P * (size_t)tiles_y(lim->max_height) * 2 * tile_strips(lim->max_width) * sizeof(uint64_t));
+    h->tile_bits_bytes = P * (size_t)tiles_y(lim->max_height) * 2 * tile_strips(lim->max_width) * sizeof(uint64_t);
+    ALLOC(b.tile_bits, h->tile_bits_bytes);
+    // the 16-pixel-per-lane threshold kernels write the bitmap rows of real tile rows only; a frame lower than 17 pixels has a tile row
+    // beyond them (tiles_y() is at least 4) whose words candidates_sparse_kernel reads: they must read as zero like the tiles there
+    if ((e = hipMemset(b.tile_bits, 0, h->tile_bits_bytes)) != hipSuccess) return bail(e);
     h->bits_bytes = bits_bytes;
     ALLOC(b.trig, P * (size_t)b.cap_trig * sizeof(uint2));
     {
@@ -556,10 +560,12 @@ static int check_status(arucohip_handle* h, uint32_t st) {
     return ARUCOHIP_E_OVERFLOW;
 }
 
-// the pad word of every bit-image row must be zero; its position depends on the frame width
+// the pad word of every bit-image row must be zero; its position depends on the frame width. The same holds for the bitmap words of tile
+// rows no threshold kernel writes (see create_handle)
 static int ensure_bits_geometry(arucohip_handle* h, int W, int H) {
     if (h->bits_w == W && h->bits_h == H) return ARUCOHIP_OK;
     HIPCHK(h, hipMemsetAsync(h->buf.tiles, 0, h->bits_bytes, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->buf.tile_bits, 0, h->tile_bits_bytes, h->stream));
     h->bits_w = W, h->bits_h = H;
     return ARUCOHIP_OK;
 }
@@ -712,9 +718,10 @@ static int run_rectangles(arucohip_handle* h, hipStream_t s, const FrameGeom& g,
 static int run_threshold(arucohip_handle* h, hipStream_t s, const uint8_t* gray_dev, const FrameGeom& g, int nframes, const DetectParams& dp, bool want_bytes) {
     const Buffers& b = h->buf;
     h->thres_bytes = true;
+    h->thr_plan_planes = 0;
     if (dp.thres_method != ARUCOHIP_THRES_CANNY) {
-        const bool lazy = launch_threshold(s, gray_dev, g, nframes, dp, b, b.env.thres_lazy && !want_bytes);
-        h->thres_bytes = !lazy;
+        const bool lazy = launch_threshold(s, gray_dev, g, nframes, dp, b, b.env.thres_lazy && !want_bytes, &h->thr_plan_done);
+        h->thres_bytes = !lazy, h->thr_plan_planes = dp.nthr;
         return ARUCOHIP_OK;
     }
     const size_t ntiles = (size_t)nframes * dp.nthr * ((g.width + 7) / 8) * ((g.height + 7) / 8);
@@ -970,10 +977,12 @@ static int detect_one_graphed(arucohip_handle* h, const uint8_t* frame, int W, i
         }
         (void)hipGraphDestroy(graph);
         h->fgraph.key = key, h->fgraph.addrs = addrs, h->fgraph.thres_bytes = h->thres_bytes;
+        h->fgraph.thr_plan = h->thr_plan_done, h->fgraph.thr_plan_planes = h->thr_plan_planes;
     }
     *handled = true;
     HIPCHK(h, hipGraphLaunch(h->fgraph.exec, h->stream));
     h->thres_bytes = h->fgraph.thres_bytes;
+    h->thr_plan_done = h->fgraph.thr_plan, h->thr_plan_planes = h->fgraph.thr_plan_planes;
     h->cells_valid = false;   // one frame per call stores the patch
     h->last = plan_batch(h, 1, W, H, dp.nthr);
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1191,21 +1200,80 @@ int arucohip_detect(arucohip_handle* h, const uint8_t* gray, int W, int H, size_
     return rc;
 }
 
-int arucohip_get_thresholded(arucohip_handle* h0, int frame, uint8_t* dst) {
-    if (!h0 || !dst) return ARUCOHIP_E_INVALID;
+int arucohip_debug_threshold_plane(arucohip_handle* h0, int frame, int t, uint8_t* bytes, uint64_t* tiles, uint64_t* tile_bits) {
+    if (!h0) return ARUCOHIP_E_INVALID;
     const Batch& r = h0->last;
     arucohip_handle* h = r.holder(frame, &frame);
-    if (!h) return ARUCOHIP_E_INVALID;
+    if (!h || t < 0 || t >= r.nthr) return ARUCOHIP_E_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
-    size_t px = (size_t)r.W * r.H;
-    int plane = frame * r.nthr + r.nthr / 2;   // thres = thres_images[n_param1 / 2]
-    if (!h->thres_bytes) {   // the batch kept the image as tiles + border lines: rebuild this plane's bytes
-        FrameGeom g;
-        g.width = r.W, g.height = r.H, g.row_stride = (size_t)r.W, g.frame_stride = px;
-        launch_expand_thres(h->stream, g, plane, h->buf);
-        HIPCHK(h, hipGetLastError());
+    const size_t px = (size_t)r.W * r.H;
+    const size_t plane = (size_t)frame * r.nthr + t;
+    if (bytes) {
+        if (!h->thres_bytes) {   // the batch kept the image as tiles + border lines: rebuild this plane's bytes
+            FrameGeom g;
+            g.width = r.W, g.height = r.H, g.row_stride = (size_t)r.W, g.frame_stride = px;
+            launch_expand_thres(h->stream, g, (int)plane, h->buf);
+            HIPCHK(h, hipGetLastError());
+        }
+        HIPCHK(h, hipMemcpyAsync(bytes, h->buf.thres + plane * px, px, hipMemcpyDeviceToHost, h->stream));
     }
-    HIPCHK(h, hipMemcpyAsync(dst, h->buf.thres + plane * px, px, hipMemcpyDeviceToHost, h->stream));
+    const size_t ntiles = (size_t)tiles_x(r.W) * tiles_y(r.H), nwords = (size_t)tiles_y(r.H) * 2 * tile_strips(r.W);
+    if (tiles) HIPCHK(h, hipMemcpyAsync(tiles, h->buf.tiles + plane * ntiles, ntiles * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    if (tile_bits) HIPCHK(h, hipMemcpyAsync(tile_bits, h->buf.tile_bits + plane * nwords, nwords * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return ARUCOHIP_OK;
+}
+
+int arucohip_get_thresholded(arucohip_handle* h, int frame, uint8_t* dst) {
+    if (!h || !dst) return ARUCOHIP_E_INVALID;
+    return arucohip_debug_threshold_plane(h, frame, h->last.nthr / 2, dst, nullptr, nullptr);   // thres = thres_images[n_param1 / 2]
+}
+
+int arucohip_debug_threshold_plan(arucohip_handle* h, int32_t* out, int cap, int* nplanes) {
+    if (!h || !nplanes || (cap > 0 && !out) || cap < 0) return ARUCOHIP_E_INVALID;
+    const arucohip_handle* w = h->last.nspan > 0 ? h->last.span[0].w : h;
+    const int n = w->thr_plan_planes;
+    *nplanes = n;
+    if (n <= 0) return fail(h, ARUCOHIP_E_INVALID, "no threshold launch to report");
+    if (cap < 5 * n + 3) return fail(h, ARUCOHIP_E_CAPACITY, "threshold plan: 5 words per plane and 3 behind them");
+    const ThrPlan& pl = w->thr_plan_done;
+    for (int t = 0; t < n; t++) {
+        const ThrPlanePlan& q = pl.plane[t];
+        int32_t* o = out + 5 * t;
+        o[0] = (int32_t)q.family, o[1] = q.R, o[2] = q.p16, o[3] = q.fast, o[4] = q.seg;
+    }
+    out[5 * n] = pl.strips, out[5 * n + 1] = pl.no_bytes, out[5 * n + 2] = pl.bitmap_pass;
+    return ARUCOHIP_OK;
+}
+
+int arucohip_debug_threshold_batch(arucohip_handle* h, const uint8_t* gray, int nframes, int W, int H, size_t row_stride, size_t frame_stride,
+                                   int frames_on_device, int want_bytes) {
+    if (!h || !gray) return ARUCOHIP_E_INVALID;
+    int rc = check_geometry(h, nframes, W, H, row_stride);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    DetectParams dp;
+    if ((rc = make_detect_params(h, W, H, &dp))) return rc;
+    h->last = plan_batch(h, nframes, W, H, dp.nthr);
+    const Batch& plan = h->last;
+    if ((rc = fork_workers(h, plan))) return rc;
+    for (const Span& s : plan) {
+        const uint8_t* gray_dev;
+        FrameGeom g;
+        rc = stage_frames(s.w, gray + (size_t)s.first * frame_stride, s.count, W, H, row_stride, frame_stride, frames_on_device, 1, &gray_dev, &g);
+        s.w->cells_valid = false;   // the cell medians belong to the batch this one replaces
+        if (!rc) rc = ensure_bits_geometry(s.w, W, H);
+        if (!rc) rc = run_threshold(s.w, s.w->stream, gray_dev, g, s.count, dp, want_bytes != 0);
+        if (!rc && hipGetLastError() != hipSuccess) rc = fail(s.w, ARUCOHIP_E_HIP, "threshold launch failed");
+        if (rc) {
+            const std::string keep = s.w->err;
+            (void)join_workers(h, plan);
+            h->err = keep;
+            h->last = Batch{};   // the planes hold part of a batch
+            return rc;
+        }
+    }
+    if ((rc = join_workers(h, plan))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return ARUCOHIP_OK;
 }

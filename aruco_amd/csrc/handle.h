@@ -13,6 +13,7 @@
 
 #include "fisheye_device.h"
 #include "internal.h"
+#include "thr_plan.h"
 
 using namespace ah;
 
@@ -134,7 +135,7 @@ struct arucohip_handle {
     Mem<int2> d_user_dec;             // [cap_flat] {id, nRotations} returned by the callback
     Mem<uint32_t> hu_list{true};      // pinned staging of the callback path: candidate list, decoder results, call order
     Mem<uint8_t> hu_patches{true};    // pinned staging: the canonical patches handed to the callback (+ one scratch patch)
-    size_t bits_bytes = 0;
+    size_t bits_bytes = 0, tile_bits_bytes = 0;
     int bits_w = 0, bits_h = 0;       // geometry the bit image was last written with (pad words depend on it)
     // pinned host staging
     arucohip_marker_t* h_markers = nullptr;
@@ -188,6 +189,8 @@ struct arucohip_handle {
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_wfork = nullptr, ev_wjoin = nullptr;
     bool thres_bytes = true;             // buf.thres holds the last batch's byte image (else: tiles + buf.thres_edge, expanded on demand)
+    ThrPlan thr_plan_done{};             // the plan the last launch_threshold of this worker executed (arucohip_debug_threshold_plan)
+    int thr_plan_planes = 0;             // its planes; 0: none yet, or the last threshold was CANNY
     Mem<uint8_t> d_em;                   // arucohip_em_fit scratch
     Mem<uint8_t> d_hrm_gen;              // HRM dictionary / board generation scratch (k_hrm.hip)
     int32_t hrm_stats[4] = {};           // the last arucohip_hrm_create_dictionary: windows, host synchronisations, acceptances, tau decrements
@@ -211,6 +214,8 @@ struct arucohip_handle {
         uint64_t seen = 0;         // key of the previous eager call: the second call with the same key captures (buffers are sized by then)
         std::array<const void*, 3> addrs{};   // gray_dev, buf.walk_scratch and buf.patches at the capture
         bool thres_bytes = false;  // what the captured threshold left in buf.thres (a replay sets thres_bytes to it)
+        ThrPlan thr_plan{};        // ... and the plan it executed (a replay sets thr_plan_done / thr_plan_planes to it)
+        int thr_plan_planes = 0;
         int disabled = 0;          // ARUCOHIP_GRAPH=0, or a capture failed once
     } fgraph;
     // Batches in flight (arucohip_set_pipeline_depth / _submit / _wait): every pipeline lane is a complete worker (own

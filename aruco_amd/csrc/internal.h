@@ -223,7 +223,10 @@ void launch_ingest(hipStream_t s, const FrameFmt& fmt, const uint8_t* src, size_
 // cv::pyrDown of nframes 8-bit frames (k_pyrdown.hip): W x H at src_row / src_frame -> (W + 1) / 2 x (H + 1) / 2 at dst_row / dst_frame
 void launch_pyr_down(hipStream_t s, const uint8_t* src, size_t src_row, size_t src_frame, int W, int H, int nframes, uint8_t* dst, size_t dst_row,
                      size_t dst_frame);
-bool launch_threshold(hipStream_t s, const uint8_t* gray, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b, bool lazy);
+struct ThrPlan;   // thr_plan.h
+// executed (optional): the plan the launch executed, for the handle to keep (arucohip_debug_threshold_plan)
+bool launch_threshold(hipStream_t s, const uint8_t* gray, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b, bool lazy,
+                      ThrPlan* executed = nullptr);
 void launch_expand_thres(hipStream_t s, const FrameGeom& g, int plane, const Buffers& b);
 void launch_undist_map(hipStream_t s, int W, int H, const float* K, const float* dist, int ndist, short2* xy, uint16_t* fxy);
 void launch_remap(hipStream_t s, const uint8_t* src, size_t row_stride, size_t frame_stride, int W, int H, int cn, int nframes, const short2* xy,

@@ -854,7 +854,7 @@ static void fill_args(ThrArgs& a, const uint8_t* gray, const FrameGeom& g, const
 
 // lazy: the caller does not need the byte image now. Returns true if it was left out (every plane ran a 16-pixel-per-lane kernel,
 // which keeps the border lines instead: launch_expand_thres rebuilds a plane on demand). Executes thr_plan() and decides nothing itself.
-bool launch_threshold(hipStream_t s, const uint8_t* gray, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b, bool lazy) {
+bool launch_threshold(hipStream_t s, const uint8_t* gray, const FrameGeom& g, int nframes, const DetectParams& p, const Buffers& b, bool lazy, ThrPlan* executed) {
     const ThrPlan pl = thr_plan({g.width, g.height, g.row_stride, g.frame_stride, (uintptr_t)gray, (uintptr_t)b.thres, p.thres_method, p.nthr, p.block,
                                  p.idelta, nframes, b.thres_edge != nullptr, lazy});
     for (int t = 0; t < p.nthr; t++) {
@@ -876,6 +876,7 @@ bool launch_threshold(hipStream_t s, const uint8_t* gray, const FrameGeom& g, in
         });
     }
     if (pl.bitmap_pass) launch_tile_bitmap(s, g, nframes * p.nthr, b);
+    if (executed) *executed = pl;
     return pl.no_bytes;
 }
 

@@ -449,6 +449,28 @@ int arucohip_debug_otsu(arucohip_handle* h, int frame, int32_t* thr, int cap, in
  * i's 56x56 patch. The last batch must have decoded from them (built-in 5x5 decoder, warp size 56, three frames or more); ARUCOHIP_E_INVALID otherwise. */
 int arucohip_debug_cells(arucohip_handle* h, int frame, uint8_t* cells49, int cap, int* n);
 
+/* Test hooks of the threshold stage.
+ * arucohip_debug_threshold_batch runs the threshold stage of a batch and nothing behind it: the geometry and argument checks of
+ * arucohip_detect_batch, the handle's current parameters (method, block sizes, C, range), the same kernel choice as a batch of nframes
+ * frames with this geometry and base address. want_bytes != 0 asks for the byte image at once, as the stage entry points and
+ * ARUCOHIP_THRES_BYTES=1 do; 0 leaves the choice to the handle. The frames are thresholded as given, whatever pyramid level the handle has
+ * (arucohip_set_pyr_down). The batch becomes the last one for the getters below and for arucohip_get_thresholded; the contour, candidate and
+ * marker lists and the cell medians of an earlier batch no longer belong to it (arucohip_debug_cells answers ARUCOHIP_E_INVALID).
+ * arucohip_debug_threshold_plan reports which kernels the last threshold launch ran (of a batch in chunks: the first chunk's), as
+ * its launcher executed them: per plane five words - family (0 strip, 1 wide, 2 eo kernel), block radius R (0 with the FIXED method),
+ * the strip kernel's P16 and FAST, the wide / eo kernel's rows per wave (16, 32, 128; 0 for a strip plane) - then the strips per row,
+ * whether the byte image was left out, and whether the separate bitmap pass ran. cap counts int32 words: 5 * planes + 3 are needed
+ * (ARUCOHIP_E_CAPACITY below that; *nplanes is set either way). ARUCOHIP_E_INVALID before any threshold launch and after CANNY.
+ * arucohip_debug_threshold_plane reads plane t (0 .. 2 * thres_param1_range) of frame `frame` of the last batch; every output may be
+ * null. bytes: width * height, as arucohip_get_thresholded returns the middle plane (expanded from tiles and border lines when the
+ * batch left the byte image out). tiles: the contour image as the device keeps it, [tiles_y][tiles_x] words of 8 x 8 pixels, bit
+ * (y & 7) * 8 + (x & 7), tiles_x = max(4, ceil(width / 8) + 1) and likewise tiles_y. tile_bits: the non-empty-tile bitmap,
+ * [tiles_y][2 * ceil(width / 1024)] words: per 128-tile strip the even tiles' word, then the odd tiles'. */
+int arucohip_debug_threshold_batch(arucohip_handle* h, const uint8_t* gray, int nframes, int width, int height, size_t row_stride,
+                                   size_t frame_stride, int frames_on_device, int want_bytes);
+int arucohip_debug_threshold_plan(arucohip_handle* h, int32_t* out, int cap, int* nplanes);
+int arucohip_debug_threshold_plane(arucohip_handle* h, int frame, int t, uint8_t* bytes, uint64_t* tiles, uint64_t* tile_bits);
+
 /* Device list fill levels of the last batch: [0] border-start candidates, [1] borders kept, [2] contour points,
  * [3] overflow bits, [4] long walks (waypoint records in segment mode). For sizing arucohip_limits_t. For tests: [6] the long walks that
  * reached the late generations (borders of more than 960 points), [7] how many of the workers that hold the batch own a side stream for

@@ -2,6 +2,7 @@
 // threshold kernels rely on. The first one is the reason this file exists: the strip kernel stores through ThrArgs::thres without a
 // test, so a plan that leaves the byte image out while a plane runs the strip kernel is a store through a null-based pointer on the
 // device. The conditions are restated here from the kernels' requirements, in arithmetic of their own (no tolerance: they are rules).
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -15,6 +16,53 @@ static long failures = 0;
                     #cond, in.W, in.H, in.row_stride, (int)(in.gray & 15), (int)(in.thres & 15), in.method, blocks[0], in.idelta, in.nframes,  \
                     in.nthr, (int)in.lazy, (int)in.has_edge, t);                                                                     \
     } while (0)
+
+// One plane on a 272 x 140 frame with everything 16-byte aligned, lazy: only the block size, C and the launch's size choose the kernel.
+static ah::ThrPlan plan_of(int block, double C, int W = 272, int H = 140, int frames = 3) {
+    static int blocks[1];
+    blocks[0] = block;
+    ah::ThrPlanIn in;
+    in.W = W, in.H = H, in.row_stride = (size_t)W, in.frame_stride = (size_t)W * H;
+    in.gray = 0x10000u, in.thres = 0x800000u;
+    in.method = ARUCOHIP_THRES_ADPT, in.nthr = 1, in.block = blocks, in.idelta = (int)floor(C), in.nframes = frames, in.has_edge = true, in.lazy = true;
+    return ah::thr_plan(in);
+}
+
+// The exact boundaries of the plan, as literals: the last C at which the packed 16-bit compare holds for a block size
+// ((256 + |C|) b^2 + b^2 / 2 < 32768), the last C the eo kernel's folded constants take, and the launch sizes at which the segment height changes.
+static long boundaries() {
+    long bad = 0;
+#define EXPECT(cond)                                      \
+    do {                                                  \
+        if (!(cond)) bad++, fprintf(stderr, "FAIL boundary: %s\n", #cond); \
+    } while (0)
+    for (int sgn = -1; sgn <= 1; sgn += 2) {
+        // 9x9: 404 * 81 + 40 = 32764, 405 * 81 + 40 = 32845
+        EXPECT(plan_of(9, sgn * 148).plane[0].family == ah::THR_WIDE && plan_of(9, sgn * 148).no_bytes);
+        EXPECT(plan_of(9, sgn * 149).plane[0].family == ah::THR_STRIP && !plan_of(9, sgn * 149).plane[0].p16 && !plan_of(9, sgn * 149).no_bytes);
+        // 11x11 never runs the 16-pixel kernels; its strip kernel packs up to 270 * 121 + 60 = 32730 (271 * 121 + 60 = 32851)
+        EXPECT(plan_of(11, sgn * 14).plane[0].family == ah::THR_STRIP && plan_of(11, sgn * 14).plane[0].p16);
+        EXPECT(plan_of(11, sgn * 15).plane[0].family == ah::THR_STRIP && !plan_of(11, sgn * 15).plane[0].p16);
+        // 7x7: eo up to |C| = 200, wide up to 412 (668 * 49 + 24 = 32756, 669 * 49 + 24 = 32805), then the strip kernel in 32 bits
+        EXPECT(plan_of(7, sgn * 200).plane[0].family == ah::THR_EO);
+        EXPECT(plan_of(7, sgn * 201).plane[0].family == ah::THR_WIDE);
+        EXPECT(plan_of(7, sgn * 412).plane[0].family == ah::THR_WIDE);
+        EXPECT(plan_of(7, sgn * 413).plane[0].family == ah::THR_STRIP && !plan_of(7, sgn * 413).plane[0].p16 && plan_of(7, sgn * 413).plane[0].fast);
+    }
+    EXPECT(plan_of(7, -200.5).plane[0].family == ah::THR_WIDE);   // floor(-200.5) = -201
+    EXPECT(plan_of(7, 200.5).plane[0].family == ah::THR_EO);      // floor(200.5) = 200
+    // rows per wave: waves128 = strips * ceil(H / 128) * frames; 48 x 129 has 2 per frame, 48 x 128 one
+    EXPECT(plan_of(7, 7, 48, 128, 127).plane[0].seg == 16);
+    EXPECT(plan_of(7, 7, 48, 128, 128).plane[0].seg == 32);
+    EXPECT(plan_of(7, 7, 48, 128, 511).plane[0].seg == 32);
+    EXPECT(plan_of(7, 7, 48, 128, 512).plane[0].seg == 128);
+    EXPECT(plan_of(7, 7, 48, 129, 63).plane[0].seg == 16 && plan_of(7, 7, 48, 129, 64).plane[0].seg == 32);
+    EXPECT(plan_of(7, 7, 48, 129, 255).plane[0].seg == 32 && plan_of(7, 7, 48, 129, 256).plane[0].seg == 128);
+    EXPECT(plan_of(5, 7, 2064, 136, 86).plane[0].seg == 128 && plan_of(5, 7, 2064, 136, 86).strips == 3);   // 3 * 2 * 86 = 516
+    EXPECT(plan_of(5, 7, 2064, 136, 85).plane[0].seg == 32);                                                 // 510
+#undef EXPECT
+    return bad;
+}
 
 int main() {
     const int widths[] = {1, 4, 15, 16, 20, 640, 1024, 1920, 4112}, heights[] = {1, 8, 480, 1080}, pads[] = {0, 4, 16}, offs[] = {0, 4, 1};
@@ -66,5 +114,6 @@ int main() {
            count[2], failures);
     // the grid reaches every family and both answers about the byte image, or the checks above were vacuous
     if (!lazy_points || lazy_points == points || !count[0] || !count[1] || !count[2]) return 2;
+    if (boundaries()) return 1;
     return failures ? 1 : 0;
 }
