@@ -159,6 +159,7 @@ class FrameFormat(C.Structure):
 # arucohip_pixel_format
 (PIX_GRAY8, PIX_BGR8, PIX_RGB8, PIX_BGRA8, PIX_RGBA8, PIX_GRAY16, PIX_YUYV, PIX_UYVY, PIX_NV12, PIX_BAYER_RGGB, PIX_BAYER_BGGR, PIX_BAYER_GRBG,
  PIX_BAYER_GBRG) = range(13)
+EXPORT_GREY_IS_LUMA = 1   # arucohip_export_batch: a grey source is the Y of a YUV destination as it lies
 PIX_NAMES = ("GRAY8", "BGR8", "RGB8", "BGRA8", "RGBA8", "GRAY16", "YUYV", "UYVY", "NV12", "BAYER_RGGB", "BAYER_BGGR", "BAYER_GRBG", "BAYER_GBRG")
 
 
@@ -238,7 +239,7 @@ SYMBOLS = [
     "arucohip_fisheye_undistort_markers_batch", "arucohip_fisheye_calibrate", "arucohip_fisheye_calibrate_board_batch",
     "arucohip_warp_plane_batch", "arucohip_rectify_board_window", "arucohip_board_rectify_batch",
     "arucohip_composite_plane_batch", "arucohip_board_composite_batch",
-    "arucohip_frame_min_row_stride", "arucohip_frame_min_stride", "arucohip_convert_batch",
+    "arucohip_frame_min_row_stride", "arucohip_frame_min_stride", "arucohip_convert_batch", "arucohip_export_batch",
 ]
 
 _lib = None
@@ -417,6 +418,7 @@ def load():
     L.arucohip_frame_min_stride.argtypes = [vp, i, i, sz]
     L.arucohip_frame_min_stride.restype = sz
     L.arucohip_convert_batch.argtypes = [vp, vp, vp, i, i, i, sz, sz, i, i, vp, sz, sz, i]
+    L.arucohip_export_batch.argtypes = [vp, vp, i, i, i, i, sz, sz, i, vp, i, vp, sz, sz, i]
     L.arucohip_default_params.argtypes = [vp]
     L.arucohip_default_limits.argtypes = [vp, i, i, i]
     _lib = L
@@ -682,6 +684,31 @@ class Handle:
         dfs = drs * height if dst_frame_stride is None else dst_frame_stride
         self._chk(self.L.arucohip_convert_batch(self.h, C.c_void_p(src_ptr), C.byref(fmt), nframes, width, height, row_stride, frame_stride,
                                                 int(bool(src_on_device)), int(channels), C.c_void_p(dst_ptr), drs, dfs, int(bool(dst_on_device))))
+
+    # ---- frames out: the library's grey [n][H][W] or B,G,R [n][H][W][3] frames in the layout fmt describes
+    def export_frames(self, frames, fmt, row_stride=None, chroma_offset=0, flags=0):
+        """arucohip_export_batch of host frames: -> uint8 [n][frame bytes], every frame as fmt.min_stride(W, H, row_stride) bytes (NV12: the
+        U,V plane at chroma_offset, 0: behind the Y plane). fmt: a FrameFormat, a PIX_* value or a name. Bytes the call does not write are 0."""
+        a = np.ascontiguousarray(frames, dtype=np.uint8)
+        assert a.ndim in (3, 4)
+        n, h, w = a.shape[:3]
+        c = 1 if a.ndim == 3 else a.shape[3]
+        fmt = frame_format(fmt.format if isinstance(fmt, FrameFormat) else fmt, chroma_offset=chroma_offset)
+        rs = fmt.min_row_stride(w) if row_stride is None else int(row_stride)
+        fs = fmt.min_stride(w, h, rs)
+        out = np.zeros((n, max(fs, 1)), np.uint8)
+        self._chk(self.L.arucohip_export_batch(self.h, _ptr(a), c, n, w, h, w * c, w * h * c, 0, C.byref(fmt), int(flags), _ptr(out), rs, fs, 0))
+        return out
+
+    def export_batch_ptr(self, src_ptr, channels, nframes, width, height, fmt, dst_ptr, dst_row_stride=None, dst_frame_stride=None,
+                         src_row_stride=None, src_frame_stride=None, flags=0, src_on_device=True, dst_on_device=True):
+        """arucohip_export_batch on pointers (plain integers); with dst_on_device asynchronous on the handle's stream."""
+        srs = width * channels if src_row_stride is None else src_row_stride
+        sfs = srs * height if src_frame_stride is None else src_frame_stride
+        drs = fmt.min_row_stride(width) if dst_row_stride is None else dst_row_stride
+        dfs = fmt.min_stride(width, height, drs) if dst_frame_stride is None else dst_frame_stride
+        self._chk(self.L.arucohip_export_batch(self.h, C.c_void_p(src_ptr), int(channels), nframes, width, height, srs, sfs, int(bool(src_on_device)),
+                                               C.byref(fmt), int(flags), C.c_void_p(dst_ptr), drs, dfs, int(bool(dst_on_device))))
 
     def undistort(self, img, K, dist):
         """cv::undistort of host frames: [H][W], [H][W][3], [N][H][W] (gray batch) -> same shape."""

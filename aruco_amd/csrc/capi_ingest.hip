@@ -9,15 +9,6 @@ namespace {
 bool is_bayer(int f) { return f >= ARUCOHIP_PIX_BAYER_RGGB && f <= ARUCOHIP_PIX_BAYER_GBRG; }
 bool is_yuv(int f) { return f == ARUCOHIP_PIX_YUYV || f == ARUCOHIP_PIX_UYVY || f == ARUCOHIP_PIX_NV12; }
 
-// the caller's record as the host code carries it; bits and chroma_offset only where the format has them
-int take_format(arucohip_handle* h, const arucohip_frame_format_t* fmt, FrameFmt* f) {
-    if (!fmt) return fail(h, ARUCOHIP_E_INVALID, "frame format: fmt is NULL");
-    f->format = fmt->format;
-    f->bits = fmt->format == ARUCOHIP_PIX_GRAY16 ? fmt->bits : 0;
-    f->chroma_offset = fmt->format == ARUCOHIP_PIX_NV12 ? (size_t)fmt->chroma_offset : 0;
-    return ARUCOHIP_OK;
-}
-
 // the bytes of a row that are read (0: invalid format, bits or width)
 size_t frame_min_row_stride(const FrameFmt& fmt, int W) {
     if (W < 1) return 0;
@@ -47,6 +38,17 @@ size_t frame_min_stride(const FrameFmt& fmt, int W, int H, size_t row_stride) {
     return (fmt.chroma_offset ? fmt.chroma_offset : luma) + row_stride * (size_t)(H / 2 - 1) + row;
 }
 
+}  // namespace
+
+// the caller's record as the host code carries it; bits and chroma_offset only where the format has them
+int take_format(arucohip_handle* h, const arucohip_frame_format_t* fmt, FrameFmt* f) {
+    if (!fmt) return fail(h, ARUCOHIP_E_INVALID, "frame format: fmt is NULL");
+    f->format = fmt->format;
+    f->bits = fmt->format == ARUCOHIP_PIX_GRAY16 ? fmt->bits : 0;
+    f->chroma_offset = fmt->format == ARUCOHIP_PIX_NV12 ? (size_t)fmt->chroma_offset : 0;
+    return ARUCOHIP_OK;
+}
+
 // a format against a geometry, with the limits of the detection calls (check_geometry of capi.hip): one message per refusal
 int check_frame_format(arucohip_handle* h, const FrameFmt& fmt, int nframes, int W, int H, size_t row_stride, size_t frame_stride) {
     if (fmt.format < ARUCOHIP_PIX_GRAY8 || fmt.format > ARUCOHIP_PIX_BAYER_GBRG) return fail(h, ARUCOHIP_E_INVALID, "frame format: unknown pixel format");
@@ -64,8 +66,6 @@ int check_frame_format(arucohip_handle* h, const FrameFmt& fmt, int nframes, int
     if (nframes > 1 && frame_stride < need) return fail(h, ARUCOHIP_E_INVALID, "frame format: frame_stride does not cover a frame");
     return ARUCOHIP_OK;
 }
-
-}  // namespace
 
 extern "C" {
 

@@ -236,6 +236,9 @@ struct arucohip_handle {
     // arucohip_convert_batch (capi_ingest.hip): the raw host frames of one call, and the converted frames a host caller gets
     Mem<uint8_t> d_ingest_src;
     Mem<uint8_t> d_ingest;
+    // arucohip_export_batch (capi_egress.hip): the host frames of one call, and the exported frames a host caller gets
+    Mem<uint8_t> d_egress_src;
+    Mem<uint8_t> d_egress;
 };
 
 #define HIPCHK(h, expr)                                                                         \
@@ -253,6 +256,12 @@ inline int fail(arucohip_handle* h, int code, const char* msg) {
     if (h) h->err = msg;
     return code;
 }
+
+// Frame formats (capi_ingest.hip), shared by arucohip_convert_batch and arucohip_export_batch.
+// the caller's record as the host code carries it; bits and chroma_offset only where the format has them
+int take_format(arucohip_handle* h, const arucohip_frame_format_t* fmt, FrameFmt* f);
+// a format against a geometry, with the limits of the detection calls (check_geometry of capi.hip): one message per refusal
+int check_frame_format(arucohip_handle* h, const FrameFmt& fmt, int nframes, int W, int H, size_t row_stride, size_t frame_stride);
 
 // the border filter's rectangle [r[0], r[2]) x [r[1], r[3]) of a W x H frame: markerdetector.cpp:433-434, Rect(Point(size) * t, Point(size) * (1 - t)) with cvRound
 inline void border_rect(float border_dist, int W, int H, int r[4]) {

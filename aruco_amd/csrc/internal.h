@@ -220,6 +220,10 @@ struct FrameFmt {
 // camera-native frames (k_ingest.hip) -> dst_channels = 1 (grey) or 3 (B,G,R) at dst_row_stride / dst_frame_stride; fmt and the geometry are valid
 void launch_ingest(hipStream_t s, const FrameFmt& fmt, const uint8_t* src, size_t row_stride, size_t frame_stride, int width, int height, int nframes,
                    int dst_channels, uint8_t* dst, size_t dst_row_stride, size_t dst_frame_stride);
+// frames out (k_egress.hip): 8-bit frames of src_channels = 1 (grey) or 3 (B,G,R) -> the format fmt at dst_row_stride / dst_frame_stride;
+// fmt is one of the accepted destinations and the geometry is valid. grey_is_luma: a grey source is the Y of a YUV destination as it lies
+void launch_egress(hipStream_t s, const uint8_t* src, int src_channels, size_t src_row_stride, size_t src_frame_stride, int width, int height, int nframes,
+                   const FrameFmt& fmt, bool grey_is_luma, uint8_t* dst, size_t dst_row_stride, size_t dst_frame_stride);
 // cv::pyrDown of nframes 8-bit frames (k_pyrdown.hip): W x H at src_row / src_frame -> (W + 1) / 2 x (H + 1) / 2 at dst_row / dst_frame
 void launch_pyr_down(hipStream_t s, const uint8_t* src, size_t src_row, size_t src_frame, int W, int H, int nframes, uint8_t* dst, size_t dst_row,
                      size_t dst_frame);

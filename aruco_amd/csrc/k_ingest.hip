@@ -10,7 +10,7 @@
 // Two instances restate work that exists elsewhere, on purpose, so that every format has the same strided destination: PACKED3 to grey
 // with B first is bgr2gray_kernel's arithmetic (k_convert.hip; both call gray_of of convert_device.h), and GRAY8 / NV12 to grey is a 2-D
 // copy. A change to one of a pair belongs in the other as well.
-#include "convert_device.h"   // gray_of
+#include "convert_device.h"   // gray_of, ld32, byte_of, sat8
 #include "internal.h"
 
 namespace ah {
@@ -26,18 +26,6 @@ struct IngestArgs {
 };
 
 enum IngestKind { IK_PACKED3 = 0, IK_PACKED4, IK_GRAY8, IK_GRAY16, IK_YUV422, IK_NV12, IK_BAYER };
-
-// bytes [0, nbytes) of p as a little-endian word (the others 0); whole: p is dword aligned and all four bytes are the row's
-__device__ __forceinline__ uint32_t ld32(const uint8_t* p, int nbytes, bool whole) {
-    if (whole) return *(const uint32_t*)p;
-    uint32_t v = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-        if (j < nbytes) v |= (uint32_t)p[j] << (8 * j);
-    return v;
-}
-__device__ __forceinline__ uint32_t byte_of(const uint32_t* w, int k) { return (w[k >> 2] >> (8 * (k & 3))) & 0xFFu; }
-__device__ __forceinline__ uint32_t sat8(int v) { return (uint32_t)min(max(v, 0), 255); }
 
 // BT.601 video range in 20-bit fixed point: round(1.164, 1.596, 0.813, 0.391, 2.018 * 2^20); >> of a negative sum is the floor shift
 __device__ __forceinline__ void yuv_to_bgr(int Y, int U, int V, uint32_t* b, uint32_t* g, uint32_t* r) {

@@ -391,6 +391,26 @@ inline void convertFrame(const RawFrame& src, cv::Mat& dst, int channels) {
     std::lock_guard<std::mutex> lock(sh.mu);
     convert_frame_(sh.ensure(src.width, src.height), src, dst, channels);
 }
+// Frames out (include/arucohip.h, "Frames out"): one CV_8UC1 (grey) or CV_8UC3 (B,G,R) image through arucohip_export_batch on the
+// process-wide handle. bytes receives the tightly packed frame in `format` (NV12: the U,V plane behind the Y plane) and view describes
+// it, so that convertFrame(view, ...) and MarkerDetector::detect(view, ...) accept it; view points into bytes. flags: ARUCOHIP_EXPORT_*.
+inline void exportFrame(const cv::Mat& src, PixelFormat format, std::vector<uint8_t>& bytes, RawFrame& view, int flags = 0) {
+    if (src.empty() || (src.type() != CV_8UC1 && src.type() != CV_8UC3)) arucohip_throw_(ARUCOHIP_E_INVALID, "exportFrame: CV_8UC1 or CV_8UC3 frames", nullptr);
+    arucohip_frame_format_t fmt;
+    fmt.format = (int32_t)format, fmt.bits = 0, fmt.chroma_offset = 0;
+    const size_t step = arucohip_frame_min_row_stride(&fmt, src.cols);
+    const size_t size = arucohip_frame_min_stride(&fmt, src.cols, src.rows, step);   // 0: the call below refuses the format or the size
+    std::vector<uint8_t> out(size ? size : 1);
+    SharedHandle_& sh = SharedHandle_::get();
+    std::lock_guard<std::mutex> lock(sh.mu);
+    arucohip_handle* h = sh.ensure(src.cols, src.rows);
+    arucohip_throw_(arucohip_export_batch(h, src.data, src.type() == CV_8UC3 ? 3 : 1, 1, src.cols, src.rows, src.step, (size_t)src.rows * src.step, 0, &fmt,
+                                          flags, out.data(), step, size, 0),
+                    "exportFrame", h);
+    bytes.swap(out);
+    view.data = bytes.data(), view.width = src.cols, view.height = src.rows, view.step = step;
+    view.format = format, view.bits = 0, view.chromaOffset = 0;
+}
 
 // cv::calibrateCamera(objectPoints, imagePoints, imageSize, cameraMatrix, distCoeffs, rvecs, tvecs, flags) for planar views
 // (utils/aruco_calibration.cpp's call) on the process-wide handle. flags: cv::CALIB_* values (ARUCOHIP_CALIB_*). Returns the RMS

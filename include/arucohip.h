@@ -342,6 +342,53 @@ size_t arucohip_frame_min_stride(const arucohip_frame_format_t* fmt, int width, 
 int arucohip_convert_batch(arucohip_handle* h, const void* src, const arucohip_frame_format_t* fmt, int nframes, int width, int height,
                            size_t row_stride, size_t frame_stride, int src_on_device, int dst_channels, uint8_t* dst,
                            size_t dst_row_stride, size_t dst_frame_stride, int dst_on_device);
+
+/* Frames out (k_egress.hip, capi_egress.hip) - the mirror of camera-native input: the 8-bit grey or interleaved B,G,R frames the library
+ * paints, rectifies and composites, converted on the device to what the next stage takes: NV12 for a hardware video encoder, YUYV / UYVY
+ * for a capture or loop-back sink, BGRA / RGBA for a display or a texture. src is src_channels = 1 (grey) or 3 (B,G,R) with rows
+ * src_row_stride apart (>= width * src_channels) and frames src_frame_stride apart (they cover src_row_stride * (height - 1) +
+ * width * src_channels bytes). fmt describes the destination with the record of the input side; its rows are dst_row_stride apart
+ * (>= arucohip_frame_min_row_stride) and its frames dst_frame_stride apart (>= arucohip_frame_min_stride); NV12 puts its U,V plane
+ * chroma_offset bytes after the frame's start (0: dst_row_stride * height). Destinations: GRAY8, BGR8, RGB8, BGRA8, RGBA8, YUYV, UYVY,
+ * NV12. GRAY16 and the Bayer mosaics are input formats only and are refused.
+ * All arithmetic is integer; >> is the floor shift; every sum below is non-negative and fits int32; gray_of is the one above. These
+ * definitions are this library's own and have no reference counterpart. The colour transform is BT.601 video range in 20-bit fixed
+ * point, the constants round(c * 2^20 / 255) of the standard matrix (65.481, 128.553, 24.966 / -37.797, -74.203, 112 /
+ * 112, -93.786, -18.214); both chroma rows sum to exactly 0, the luma row to 900542:
+ *     Y = (269262 R + 528618 G + 102662 B + (16 << 20) + (1 << 19)) >> 20
+ *     U = (-155424 Sr - 305127 Sg + 460551 Sb + (128 << (20 + k)) + (1 << (19 + k))) >> (20 + k)
+ *     V = ( 460551 Sr - 385654 Sg -  74897 Sb + (128 << (20 + k)) + (1 << (19 + k))) >> (20 + k)
+ * Sr, Sg, Sb are the channel sums over the pixels that share the chroma sample: the two pixels of a YUYV / UYVY pair (k = 1), the
+ * 2 x 2 block of NV12 (k = 2). This box filter matches the way the input side replicates chroma at (x / 2, y / 2). No clamp is
+ * needed: Y stays in 16..235, U and V in 16..240.
+ *   grey  -> Y of YUYV / UYVY / NV12     (900542 g + (16 << 20) + (1 << 19)) >> 20, the Y of (g, g, g); U = V = 128.
+ *            with ARUCOHIP_EXPORT_GREY_IS_LUMA: Y = g, untouched, for a grey frame that was the Y plane of an NV12 or YUYV frame
+ *            which the input side hands over as it lies; U = V = 128.
+ *   grey  -> GRAY8                       a strided copy
+ *   grey  -> BGR8, RGB8, BGRA8, RGBA8    the byte three times, alpha 255
+ *   B,G,R -> GRAY8                       gray_of(b, g, r)
+ *   B,G,R -> RGB8, BGRA8, RGBA8          reordered, alpha 255
+ *   B,G,R -> BGR8                        a strided copy
+ *   B,G,R -> YUYV / UYVY / NV12          the formulas above
+ * The flag is ignored for a B,G,R source and for destinations other than the three YUV formats.
+ * src and dst are each in host or device memory. With dst_on_device the call is asynchronous on the handle's stream, so it can follow
+ * arucohip_draw_*_batch or arucohip_board_composite_batch on device frames with no synchronisation between:
+ *     arucohip_board_composite_batch(h, d_bgr, ...);                              // frames in device memory, painted in place
+ *     arucohip_frame_format_t f = {ARUCOHIP_PIX_NV12, 0, 0};                      // d_nv12: n * w * h * 3 / 2 bytes of device memory
+ *     arucohip_export_batch(h, d_bgr, 3, n, w, h, 3 * w, (size_t)3 * w * h, 1, &f, 0, d_nv12, w, (size_t)w * h * 3 / 2, 1);
+ *     arucohip_synchronize(h);                                                    // or an event: d_nv12 goes to the encoder
+ * Host sources go up raw (width * src_channels bytes per row) and host destinations come down by rows; of NV12 only the bytes of both
+ * planes move, not the gap before chroma_offset. The bytes between rows, between the planes and between frames are never written.
+ * Everything is checked before anything runs: ARUCOHIP_E_INVALID for NULL pointers, an unknown or refused format, src_channels other
+ * than 1 or 3, an odd width (YUYV / UYVY / NV12) or height (NV12), strides below the minimum, a frame_stride that does not cover a
+ * frame, chroma_offset inside the Y plane, nframes or the size beyond the handle's limits, a dst that overlaps src and flag bits other
+ * than the one defined; the last batch's results stay as they were.
+ * Out of scope: planar I420 / YV12 and P010, full-range and BT.709 matrices, any resize, and the multi-GPU entry points. */
+#define ARUCOHIP_EXPORT_GREY_IS_LUMA 1
+int arucohip_export_batch(arucohip_handle* h, const uint8_t* src, int src_channels, int nframes, int width, int height,
+                          size_t src_row_stride, size_t src_frame_stride, int src_on_device,
+                          const arucohip_frame_format_t* fmt, int flags,
+                          void* dst, size_t dst_row_stride, size_t dst_frame_stride, int dst_on_device);
 /* SURVEY §8 row f3 — lens undistortion of the frames on the device: cv::undistort(src, dst, CameraMatrix, Distorsion), which
  * the reference's GL apps run on every frame before detect() (utils/aruco_test_gl.cpp:237-240, utils/aruco_test_board_gl.cpp:
  * 265-268; detect is then called with an empty distortion vector). 8-bit frames with `channels` = 1 or 3 interleaved channels;

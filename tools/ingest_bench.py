@@ -11,6 +11,11 @@ alternates settings on one box.
 --mode kernel: arucohip_convert_batch alone, device to device, grey and B,G,R, with the achieved bytes per second (bytes in + bytes out,
   counted from shapes). The leg also runs arucohip_detect_batch_bgr --runs times, so that under
   `rocprofv3 --kernel-trace --stats -- python tools/ingest_bench.py --mode kernel` bgr2gray_kernel's own time stands beside ingest_kernel's.
+--mode export: the way out, arucohip_export_batch alone, device to device: grey and B,G,R frames to every destination format, with the
+  achieved bytes per second (bytes in + bytes out, counted from shapes). Beside them bgr2gray_kernel's from the same run: the batch time of
+  arucohip_detect_batch_bgr minus that of arucohip_detect_batch on the grey frames it computes (the B,G,R frames carry the grey value in
+  all three channels, so the detection work is the same), over its 4 bytes per pixel; a `rocprofv3 --kernel-trace --stats` run of this
+  mode shows the kernel's own time beside egress_kernel's. With few frames the difference is within the noise of the two detection legs.
 The BGR legs run the library this process loaded: ARUCOHIP_LIB=<a build of the parent commit> gives the parent's numbers for them.
 Prints one JSON line with arucohip_build_info()."""
 import argparse
@@ -55,7 +60,7 @@ def fmt_of(name):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["device", "host", "kernel"], default="device")
+    ap.add_argument("--mode", choices=["device", "host", "kernel", "export"], default="device")
     ap.add_argument("--frames", type=int, default=256)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
@@ -127,6 +132,31 @@ def main():
         res["legs"] = {k: {"ms_per_batch": round(ms, 3), "frames_per_s": round(N / ms * 1e3, 1), "ratio_to_bgr": round(med["bgr_path"] / ms, 3),
                            "byte_ratio": 1.0 if k == "bgr_path" else round(3 / IN_BYTES[k], 3), "runs_ms": [round(t, 3) for t in runs[k]]}
                        for k, ms in med.items()}
+    elif a.mode == "export":
+        dests = ("GRAY8", "BGR8", "RGB8", "BGRA8", "RGBA8", "YUYV", "UYVY", "NV12")
+        src = {1: grey, 3: encode("BGR8", grey)}
+        d_out = torch.zeros(N * H * W * 4, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+
+        def export(name, c):
+            h.export_batch_ptr(src[c].data_ptr(), c, N, W, H, fmt_of(name), d_out.data_ptr())
+
+        legs = {"bgr_path_detect": lambda: detect_bgr(src[3].data_ptr()), "grey_path_detect": lambda: detect_grey(grey.data_ptr())}
+        for n in dests:
+            for c in (1, 3):
+                legs["%d_to_%s" % (c, n)] = (lambda n=n, c=c: export(n, c))
+        med, runs = run_legs(legs)
+        res["legs"] = {}
+        for k, ms in med.items():
+            if k.endswith("_detect"):
+                continue
+            c, n = k.split("_to_", 1)
+            nbytes = int(N * W * H * (int(c) + IN_BYTES[n]))
+            res["legs"][k] = {"ms": round(ms, 4), "bytes_in_plus_out": nbytes, "tb_per_s": round(nbytes / ms / 1e9, 3),
+                              "runs_ms": [round(t, 4) for t in runs[k]]}
+        ms = med["bgr_path_detect"] - med["grey_path_detect"]
+        res["bgr2gray_kernel_by_difference"] = {"ms": round(ms, 4), "bytes_in_plus_out": N * W * H * 4,
+                                                "tb_per_s": round(N * W * H * 4 / ms / 1e9, 3) if ms > 0 else None}
     else:
         raw = {n: encode(n, grey) for n in names}
         torch.cuda.synchronize()
