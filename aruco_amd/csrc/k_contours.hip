@@ -12,7 +12,12 @@
 //   outer border: a visited pixel precedes the start in raster order
 //   hole border : a 4-neighbour background pixel examined during the walk precedes the trigger pixel
 // or as soon as the border is longer than the size filter admits. Survivors are exactly the borders
-// detectRectangles keeps, with the same start and direction.
+// detectRectangles keeps, with the same start and direction. tests/border_ref.py restates the scan and this formulation in plain
+// Python and holds them against each other at the edge topologies (closure at a start passed twice, each comparison of the hole rule,
+// the reverse probe's 10 steps, every generation hand-over, the size filter's bounds, thin and touching shapes, the image frame, the
+// waypoint grid): tests/test_border_edges_cpu.py without a GPU, tests/test_gpu_border_edges.py against these kernels and k_segments.hip
+// on every route. Of the hole rule's four comparisons S never decides (a clear pixel that precedes the trigger is examined from the
+// border pixel beside it before the walk gets above it), and leaving any one out costs time, never a wrong survivor.
 #include <algorithm>
 
 #include "bits_tiles.h"

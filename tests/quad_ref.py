@@ -10,7 +10,8 @@ which `<=` held with equality and what every clause of the clean-up pass said ab
 `mut` names deliberate misreadings (MUTATIONS); tests/test_quad_edges_cpu.py shows that the cases tell every one of them from the right reading.
 
 The generator draws binary tiles with numpy (convex polygons by half-plane tests, unions, notches), each with its own quiet zone, and packs them into
-sheets of 640 x 480. Borders come from the oracle's find_contours: border following is pinned elsewhere.
+sheets of 640 x 480. Borders come from the oracle's find_contours: border following is pinned by tests/border_ref.py
+(tests/test_border_edges_cpu.py, tests/test_gpu_border_edges.py).
 """
 import math
 import struct
