@@ -1090,27 +1090,18 @@ int arucohip_undistort(arucohip_handle* h, const uint8_t* src, int nframes, int 
         std::memcpy(h->umap_K, K, sizeof(h->umap_K));
         if (ndist) std::memcpy(h->umap_d, dist, ndist * sizeof(float));
     }
-    const size_t fbytes = (size_t)W * H * channels;
-    const uint8_t* sdev = src;
-    size_t rs = row_stride, fs = frame_stride;
-    if (!src_on_device) {
-        HIPCHK(h, h->d_bgr.reserve((size_t)nframes * fbytes));
-        for (int f = 0; f < nframes; f++)
-            HIPCHK(h, hipMemcpy2DAsync(h->d_bgr + (size_t)f * fbytes, (size_t)W * channels, src + (size_t)f * frame_stride, row_stride, (size_t)W * channels, H,
-                                       hipMemcpyHostToDevice, s));
-        sdev = h->d_bgr, rs = (size_t)W * channels, fs = fbytes;
-    }
-    uint8_t* ddev = dst;
-    if (!dst_on_device) {
-        HIPCHK(h, h->d_undist.reserve((size_t)nframes * fbytes));
-        ddev = h->d_undist;
-    }
-    launch_remap(s, sdev, rs, fs, W, H, channels, nframes, h->d_umap_xy, h->d_umap_f, ddev);
+    // host frames borrow d_bgr; the packed result a host caller gets is staged in d_undist
+    const size_t row = (size_t)W * channels;
+    const Images in = images(src, nframes, H, row, row_stride, frame_stride, src_on_device), out = images(dst, nframes, H, row, row, row * H, dst_on_device);
+    if (!src_on_device) HIPCHK(h, h->d_bgr.reserve(in.packed_bytes()));
+    if (!dst_on_device) HIPCHK(h, h->d_undist.reserve(out.packed_bytes()));
+    DevImages sdev, ddev;
+    if ((rc = stage_input(h, s, in, h->d_bgr, 0, &sdev))) return rc;
+    if ((rc = stage_output(h, out, h->d_undist, 0, &ddev))) return rc;
+    launch_remap(s, sdev.p, sdev.row, sdev.frame, W, H, channels, nframes, h->d_umap_xy, h->d_umap_f, ddev.p);
     HIPCHK(h, hipGetLastError());
-    if (!dst_on_device) {
-        HIPCHK(h, hipMemcpyAsync(dst, ddev, (size_t)nframes * fbytes, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-    }
+    if ((rc = unstage(h, s, out, ddev))) return rc;
+    if (!dst_on_device) HIPCHK(h, hipStreamSynchronize(s));
     return ARUCOHIP_OK;
 }
 

@@ -144,18 +144,14 @@ int arucohip_charuco_corners_batch(arucohip_handle* h, const arucohip_charuco_t*
     HIPCHK(h, hipMemsetAsync(d_nf, 0, (size_t)nframes * sizeof(int32_t), s0));
     CharucoArgs a{};
     a.L = *layout, a.ids = d_ids, a.width = W, a.height = H, a.min_markers = o.min_markers, a.max_win = o.max_win;
-    const uint8_t* gray = frames;
-    a.row_stride = row_stride, a.frame_stride = frame_stride;
-    if (!frames_on_device) {
-        const size_t px = (size_t)W * H;
-        HIPCHK(h, h->d_charuco_frames.reserve((size_t)nframes * px));
-        for (int f = 0; f < nframes; f++)
-            HIPCHK(h, hipMemcpy2DAsync(h->d_charuco_frames + (size_t)f * px, W, frames + (size_t)f * frame_stride, row_stride, W, H, hipMemcpyHostToDevice, s0));
-        gray = h->d_charuco_frames, a.row_stride = W, a.frame_stride = px;
-    }
+    const Images in = images(frames, nframes, H, (size_t)W, row_stride, frame_stride, frames_on_device);
+    if (!frames_on_device) HIPCHK(h, h->d_charuco_frames.reserve(in.packed_bytes()));
+    DevImages gray;
+    if (const int rc = stage_input(h, s0, in, h->d_charuco_frames, 0, &gray)) return rc;
+    a.row_stride = gray.row, a.frame_stride = gray.frame;
     // every worker interpolates the corners of the frames it detected, on its own stream
     const int rc = on_workers(h, b, [&](const Span& s) {
-        a.gray = gray + (size_t)s.first * a.frame_stride;
+        a.gray = gray.p + (size_t)s.first * gray.frame;
         launch_charuco_corners(s.w->stream, s.count, s.w->buf, a, d_rec + (size_t)s.first * p.corners, d_nf + s.first);
         return 0;
     });

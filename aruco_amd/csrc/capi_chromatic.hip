@@ -108,12 +108,9 @@ static int chroma_plane(arucohip_chromatic* m, const uint8_t* plane, int on_devi
     arucohip_handle* h = m->h;
     if (!plane || row_stride < (size_t)m->cam.W) return fail(h, ARUCOHIP_E_INVALID, "chromatic: NULL plane or row stride below the width");
     HIPCHK(h, hipSetDevice(h->device));
-    if (on_device) {
-        *dev = plane, *dev_stride = row_stride;
-        return ARUCOHIP_OK;
-    }
-    HIPCHK(h, hipMemcpy2DAsync(m->d_frame, m->cam.W, plane, row_stride, m->cam.W, m->cam.H, hipMemcpyHostToDevice, h->stream));
-    *dev = m->d_frame, *dev_stride = m->cam.W;
+    DevImages v;
+    if (const int rc = stage_input(h, h->stream, images(plane, 1, m->cam.H, (size_t)m->cam.W, row_stride, 0, on_device), m->d_frame, 0, &v)) return rc;
+    *dev = v.p, *dev_stride = v.row;
     return ARUCOHIP_OK;
 }
 
@@ -318,15 +315,12 @@ int arucohip_chromatic_classify_batch(arucohip_chromatic* m, arucohip_handle* h,
     if (!masks_on_device) HIPCHK(mh, m->d_bmasks.reserve(std::min(nframes, piece) * px));
     for (int first = 0; first < nframes; first += piece) {
         const int cnt = std::min(piece, nframes - first);
-        const uint8_t* src = frames + (size_t)first * frame_stride;
-        size_t rs = row_stride, fs = frame_stride;
-        if (!frames_on_device) {
-            for (int f = 0; f < cnt; f++)
-                HIPCHK(mh, hipMemcpy2DAsync(m->d_bframes + (size_t)f * px, W, src + (size_t)f * frame_stride, row_stride, W, H, hipMemcpyHostToDevice, s));
-            src = m->d_bframes, rs = W, fs = px;
-        }
+        DevImages src;
+        if (const int rc = stage_input(mh, s, images(frames + (size_t)first * frame_stride, cnt, H, (size_t)W, row_stride, frame_stride, frames_on_device),
+                                       m->d_bframes, 0, &src))
+            return rc;
         uint8_t* dst = masks_on_device ? masks + (size_t)first * px : (uint8_t*)m->d_bmasks;
-        launch_chroma_classify(s, m->cam, method, m->thresh, cnt, src, rs, fs, m->d_bgeom + first, m->d_prob, m->d_inside, dst,
+        launch_chroma_classify(s, m->cam, method, m->thresh, cnt, src.p, src.row, src.frame, m->d_bgeom + first, m->d_prob, m->d_inside, dst,
                                npix ? (int32_t*)m->d_npix + first : nullptr);
         HIPCHK(mh, hipGetLastError());
         if (!masks_on_device) HIPCHK(mh, hipMemcpyAsync(masks + (size_t)first * px, dst, (size_t)cnt * px, hipMemcpyDeviceToHost, s));

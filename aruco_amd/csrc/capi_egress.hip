@@ -20,48 +20,36 @@ int arucohip_export_batch(arucohip_handle* h, const uint8_t* src, int C, int nfr
     if (C != 1 && C != 3) return fail(h, ARUCOHIP_E_INVALID, "export: src_channels must be 1 or 3");
     if (flags & ~ARUCOHIP_EXPORT_GREY_IS_LUMA) return fail(h, ARUCOHIP_E_INVALID, "export: unknown flag bits");
     if ((rc = check_frame_format(h, f, nframes, W, H, drs, dfs))) return rc;
-    const size_t srow = (size_t)W * C, sframe = srs * (size_t)(H - 1) + srow;
-    if (srs < srow) return fail(h, ARUCOHIP_E_INVALID, "export: src_row_stride below width * src_channels");
-    if (nframes > 1 && sfs < sframe) return fail(h, ARUCOHIP_E_INVALID, "export: src_frame_stride does not cover a frame");
-    const size_t drow = arucohip_frame_min_row_stride(fmt, W), dframe = arucohip_frame_min_stride(fmt, W, H, drs);
-    const size_t src_extent = (size_t)(nframes - 1) * sfs + sframe;
-    const size_t dst_extent = (size_t)(nframes - 1) * dfs + dframe;
-    if ((uintptr_t)src < (uintptr_t)dst + dst_extent && (uintptr_t)dst < (uintptr_t)src + src_extent) return fail(h, ARUCOHIP_E_INVALID, "export: dst overlaps src");
+    const Images in = images(src, nframes, H, (size_t)W * C, srs, sfs, src_on_device);
+    if ((rc = check_strides(h, "export", "src_", in))) return rc;
+    // the destination as planes of rows: the one plane of a format, or NV12's Y plane and its U,V plane behind it
+    const size_t drow = arucohip_frame_min_row_stride(fmt, W);
+    const bool nv12 = f.format == ARUCOHIP_PIX_NV12;
+    const Images luma = images(dst, nframes, H, drow, drs, dfs, dst_on_device);
+    Images chroma = luma;
+    chroma.p += f.chroma_offset ? f.chroma_offset : drs * (size_t)H, chroma.rows = H / 2;
+    // what an exported frame spans from its first to its last byte written, as one row: of NV12 both planes and what lies between them
+    const Images span = images(dst, nframes, 1, arucohip_frame_min_stride(fmt, W, H, drs), 0, dfs, dst_on_device);
+    if ((rc = check_disjoint(h, "export", "dst", span, "src", in))) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    const uint8_t* sdev = src;
-    size_t rs = srs, fs = sfs;
-    if (!src_on_device) {   // the rows' own bytes go up
-        HIPCHK(h, h->d_egress_src.reserve((size_t)nframes * srow * H));
-        if ((rc = copy_rows(h, const_cast<uint8_t*>(src), srs, nframes > 1 ? sfs : srs * (size_t)H, srow, H, nframes, h->d_egress_src, true))) return rc;
-        sdev = h->d_egress_src, rs = srow, fs = srow * H;
-    }
-    // the rows of one frame: NV12 has H / 2 rows of chroma, which in the staging buffer follow the Y plane
-    const bool nv12 = f.format == ARUCOHIP_PIX_NV12;
-    const size_t rows = nv12 ? (size_t)H + H / 2 : (size_t)H;
-    uint8_t* ddev = dst;
-    size_t ors = drs, ofs = dfs;
+    const size_t staged_frame = luma.packed_frame() + (nv12 ? chroma.packed_frame() : 0);
+    if (!src_on_device) HIPCHK(h, h->d_egress_src.reserve(in.packed_bytes()));
+    if (!dst_on_device) HIPCHK(h, h->d_egress.reserve((size_t)nframes * staged_frame));
+    DevImages sdev, ddev, cdev;
     FrameFmt df = f;
+    if ((rc = stage_input(h, s, in, h->d_egress_src, 0, &sdev))) return rc;
+    if ((rc = stage_output(h, luma, h->d_egress, 0, &ddev, staged_frame))) return rc;
     if (!dst_on_device) {
-        HIPCHK(h, h->d_egress.reserve((size_t)nframes * drow * rows));
-        ddev = h->d_egress, ors = drow, ofs = drow * rows, df.chroma_offset = 0;
+        df.chroma_offset = 0;   // the staged chroma plane follows the Y plane
+        if (nv12 && (rc = stage_output(h, chroma, h->d_egress, luma.packed_frame(), &cdev, staged_frame))) return rc;
     }
-    launch_egress(s, sdev, C, rs, fs, W, H, nframes, df, (flags & ARUCOHIP_EXPORT_GREY_IS_LUMA) != 0, ddev, ors, ofs);
+    launch_egress(s, sdev.p, C, sdev.row, sdev.frame, W, H, nframes, df, (flags & ARUCOHIP_EXPORT_GREY_IS_LUMA) != 0, ddev.p, ddev.row, ddev.frame);
     HIPCHK(h, hipGetLastError());
-    if (!dst_on_device) {   // down by rows: the bytes between rows, between the planes and between frames stay the caller's
-        if (!nv12) {
-            if ((rc = copy_rows(h, dst, drs, nframes > 1 ? dfs : drs * (size_t)H, drow, H, nframes, ddev, false))) return rc;
-        } else {
-            const size_t coff = f.chroma_offset ? f.chroma_offset : drs * (size_t)H;
-            for (int i = 0; i < nframes; i++) {
-                uint8_t* fr = dst + (size_t)i * dfs;
-                const uint8_t* st = ddev + (size_t)i * ofs;
-                HIPCHK(h, hipMemcpy2DAsync(fr, drs, st, drow, drow, H, hipMemcpyDeviceToHost, s));
-                HIPCHK(h, hipMemcpy2DAsync(fr + coff, drs, st + drow * H, drow, drow, H / 2, hipMemcpyDeviceToHost, s));
-            }
-        }
-        HIPCHK(h, hipStreamSynchronize(s));
-    }
+    // down by rows: the bytes between rows, between the planes and between frames stay the caller's
+    if ((rc = unstage(h, s, luma, ddev))) return rc;
+    if (nv12 && !dst_on_device && (rc = unstage(h, s, chroma, cdev))) return rc;
+    if (!dst_on_device) HIPCHK(h, hipStreamSynchronize(s));
     return ARUCOHIP_OK;
 }
 

@@ -175,24 +175,18 @@ int arucohip_fisheye_undistort(arucohip_handle* h, const uint8_t* src, int nfram
         h->fmap_w = W, h->fmap_h = H;
         std::memcpy(h->fmap_key, key, sizeof(key));
     }
-    const size_t fbytes = (size_t)W * H * channels, staged = src_on_device ? 0 : (size_t)nframes * fbytes;
-    if (!src_on_device || !dst_on_device) HIPCHK(h, h->d_fisheye_frames.reserve(staged + (dst_on_device ? 0 : (size_t)nframes * fbytes)));
-    const uint8_t* sdev = src;
-    size_t rs = row_stride, fs = frame_stride;
-    if (!src_on_device) {
-        uint8_t* stage = h->d_fisheye_frames;
-        for (int f = 0; f < nframes; f++)
-            HIPCHK(h, hipMemcpy2DAsync(stage + (size_t)f * fbytes, (size_t)W * channels, src + (size_t)f * frame_stride, row_stride, (size_t)W * channels, H,
-                                       hipMemcpyHostToDevice, s));
-        sdev = stage, rs = (size_t)W * channels, fs = fbytes;
-    }
-    uint8_t* ddev = dst_on_device ? dst : h->d_fisheye_frames + staged;
-    launch_remap(s, sdev, rs, fs, W, H, channels, nframes, h->d_fmap_xy, h->d_fmap_f, ddev);
+    // one staging buffer: the host frames, then the packed result a host caller gets
+    const size_t row = (size_t)W * channels;
+    const Images in = images(src, nframes, H, row, row_stride, frame_stride, src_on_device), out = images(dst, nframes, H, row, row, row * H, dst_on_device);
+    const size_t staged = src_on_device ? 0 : in.packed_bytes();
+    if (!src_on_device || !dst_on_device) HIPCHK(h, h->d_fisheye_frames.reserve(staged + (dst_on_device ? 0 : out.packed_bytes())));
+    DevImages sdev, ddev;
+    if ((rc = stage_input(h, s, in, h->d_fisheye_frames, 0, &sdev))) return rc;
+    if ((rc = stage_output(h, out, h->d_fisheye_frames, staged, &ddev))) return rc;
+    launch_remap(s, sdev.p, sdev.row, sdev.frame, W, H, channels, nframes, h->d_fmap_xy, h->d_fmap_f, ddev.p);
     HIPCHK(h, hipGetLastError());
-    if (!dst_on_device) {
-        HIPCHK(h, hipMemcpyAsync(dst, ddev, (size_t)nframes * fbytes, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-    }
+    if ((rc = unstage(h, s, out, ddev))) return rc;
+    if (!dst_on_device) HIPCHK(h, hipStreamSynchronize(s));
     return ARUCOHIP_OK;
 }
 

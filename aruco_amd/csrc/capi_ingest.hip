@@ -91,42 +91,35 @@ int arucohip_convert_batch(arucohip_handle* h, const void* src_, const arucohip_
     if (rc) return rc;
     if ((rc = check_frame_format(h, f, nframes, W, H, row_stride, frame_stride))) return rc;
     if (C != 1 && C != 3) return fail(h, ARUCOHIP_E_INVALID, "convert: dst_channels must be 1 or 3");
-    const size_t drow = (size_t)W * C, dframe = drs * (size_t)(H - 1) + drow;
-    if (drs < drow) return fail(h, ARUCOHIP_E_INVALID, "convert: dst_row_stride below width * dst_channels");
-    if (nframes > 1 && dfs < dframe) return fail(h, ARUCOHIP_E_INVALID, "convert: dst_frame_stride does not cover a frame");
-    const size_t src_extent = (size_t)(nframes - 1) * frame_stride + frame_min_stride(f, W, H, row_stride);
-    const size_t dst_extent = (size_t)(nframes - 1) * dfs + dframe;
-    if ((uintptr_t)src < (uintptr_t)dst + dst_extent && (uintptr_t)dst < (uintptr_t)src + src_extent) return fail(h, ARUCOHIP_E_INVALID, "convert: dst overlaps src");
+    const Images out = images(dst, nframes, H, (size_t)W * C, drs, dfs, dst_on_device);
+    if ((rc = check_strides(h, "convert", "dst_", out))) return rc;
+    // the raw source as planes of rows: the one plane of a format, or NV12's Y plane and, where colour is wanted, its U,V plane behind it
+    const size_t row = frame_min_row_stride(f, W);
+    const bool nv12 = f.format == ARUCOHIP_PIX_NV12;
+    const Images luma = images(src, nframes, H, row, row_stride, frame_stride, src_on_device);
+    Images chroma = luma;
+    chroma.p += f.chroma_offset ? f.chroma_offset : row_stride * (size_t)H, chroma.rows = H / 2;
+    // what a raw frame spans from its first to its last byte read, as one row: of NV12 both planes and what lies between them
+    const Images span = images(src, nframes, 1, frame_min_stride(f, W, H, row_stride), 0, frame_stride, src_on_device);
+    if ((rc = check_disjoint(h, "convert", "dst", out, "src", span))) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    const uint8_t* sdev = src;
-    size_t rs = row_stride, fs = frame_stride;
+    const bool with_chroma = nv12 && C == 3;
+    const size_t staged_frame = luma.packed_frame() + (with_chroma ? chroma.packed_frame() : 0);
+    if (!src_on_device) HIPCHK(h, h->d_ingest_src.reserve((size_t)nframes * staged_frame));
+    if (!dst_on_device) HIPCHK(h, h->d_ingest.reserve(out.packed_bytes()));
+    DevImages sdev, cdev, ddev;
     FrameFmt sf = f;
-    if (!src_on_device) {   // the raw bytes go up: the rows' own bytes, and of NV12 the chroma plane only when colour is wanted
-        const size_t row = frame_min_row_stride(f, W);
-        const bool chroma = f.format == ARUCOHIP_PIX_NV12 && C == 3;
-        const size_t luma = row * H, fbytes = luma + (chroma ? luma / 2 : 0);
-        const size_t coff = f.chroma_offset ? f.chroma_offset : row_stride * (size_t)H;
-        HIPCHK(h, h->d_ingest_src.reserve((size_t)nframes * fbytes));
-        for (int i = 0; i < nframes; i++) {
-            const uint8_t* fr = src + (size_t)i * frame_stride;
-            HIPCHK(h, hipMemcpy2DAsync(h->d_ingest_src + (size_t)i * fbytes, row, fr, row_stride, row, H, hipMemcpyHostToDevice, s));
-            if (chroma) HIPCHK(h, hipMemcpy2DAsync(h->d_ingest_src + (size_t)i * fbytes + luma, row, fr + coff, row_stride, row, H / 2, hipMemcpyHostToDevice, s));
-        }
-        sdev = h->d_ingest_src, rs = row, fs = fbytes, sf.chroma_offset = 0;   // the staged chroma plane follows the Y plane
+    if ((rc = stage_input(h, s, luma, h->d_ingest_src, 0, &sdev, staged_frame))) return rc;
+    if (!src_on_device) {
+        sf.chroma_offset = 0;   // the staged chroma plane follows the Y plane
+        if (with_chroma && (rc = stage_input(h, s, chroma, h->d_ingest_src, luma.packed_frame(), &cdev, staged_frame))) return rc;
     }
-    uint8_t* ddev = dst;
-    size_t ors = drs, ofs = dfs;
-    if (!dst_on_device) {
-        HIPCHK(h, h->d_ingest.reserve((size_t)nframes * drow * H));
-        ddev = h->d_ingest, ors = drow, ofs = drow * H;
-    }
-    launch_ingest(s, sf, sdev, rs, fs, W, H, nframes, C, ddev, ors, ofs);
+    if ((rc = stage_output(h, out, h->d_ingest, 0, &ddev))) return rc;
+    launch_ingest(s, sf, sdev.p, sdev.row, sdev.frame, W, H, nframes, C, ddev.p, ddev.row, ddev.frame);
     HIPCHK(h, hipGetLastError());
-    if (!dst_on_device) {
-        if ((rc = copy_rows(h, dst, drs, nframes > 1 ? dfs : drs * (size_t)H, drow, H, nframes, ddev, false))) return rc;
-        HIPCHK(h, hipStreamSynchronize(s));
-    }
+    if ((rc = unstage(h, s, out, ddev))) return rc;
+    if (!dst_on_device) HIPCHK(h, hipStreamSynchronize(s));
     return ARUCOHIP_OK;
 }
 

@@ -7,21 +7,20 @@
 
 namespace {
 
+// the frames of a call, drawn into in place
 struct Frames {
-    uint8_t* p;
-    int n, w, h, ch;
-    size_t row, frame;
-    int on_device;
-    size_t row_bytes() const { return (size_t)w * ch; }
-    size_t extent() const { return (size_t)(n - 1) * frame + (size_t)(h - 1) * row + row_bytes(); }
+    Images im;
+    int w, ch;
 };
+Frames make_frames(uint8_t* p, int n, int w, int h, int ch, size_t row, size_t frame, int on_device) {
+    return {images(p, n, h, (size_t)w * ch, row, frame, on_device), w, ch};
+}
 
 int check_frames(arucohip_handle* h, const Frames& f) {
-    if (!f.p || f.n < 1 || f.w < 1 || f.h < 1) return fail(h, ARUCOHIP_E_INVALID, "draw: NULL frames, or nframes / width / height below 1");
+    if (!f.im.p || f.im.n < 1 || f.w < 1 || f.im.rows < 1) return fail(h, ARUCOHIP_E_INVALID, "draw: NULL frames, or nframes / width / height below 1");
     if (f.ch != 1 && f.ch != 3) return fail(h, ARUCOHIP_E_INVALID, "draw: channels must be 1 or 3");
-    if (f.row < f.row_bytes()) return fail(h, ARUCOHIP_E_INVALID, "draw: row_stride is smaller than width * channels");
-    if (f.n > 1 && f.frame < (size_t)(f.h - 1) * f.row + f.row_bytes()) return fail(h, ARUCOHIP_E_INVALID, "draw: frame_stride lets the frames overlap");
-    if (f.w > h->lim.max_width || f.h > h->lim.max_height) return fail(h, ARUCOHIP_E_UNSUPPORTED, "draw: width / height exceed the handle's limits");
+    if (const int rc = check_strides(h, "draw", "", f.im)) return rc;
+    if (f.w > h->lim.max_width || f.im.rows > h->lim.max_height) return fail(h, ARUCOHIP_E_UNSUPPORTED, "draw: width / height exceed the handle's limits");
     return ARUCOHIP_OK;
 }
 
@@ -33,32 +32,17 @@ int check_camera(arucohip_handle* h, bool need_K, const float* K, const float* d
     return ARUCOHIP_OK;
 }
 
-// host frames -> d_overlay_frames with the caller's strides (only the width * channels bytes of every row travel, either way)
-int frames_copy(arucohip_handle* h, const Frames& f, uint8_t* dev, bool up) {
-    const bool flat = f.frame == f.row * (size_t)f.h;
-    const int calls = flat ? 1 : f.n;
-    const size_t rows = flat ? (size_t)f.n * f.h : (size_t)f.h;
-    for (int i = 0; i < calls; i++) {
-        uint8_t *d = dev + (size_t)i * f.frame, *s = f.p + (size_t)i * f.frame;
-        if (up)
-            HIPCHK(h, hipMemcpy2DAsync(d, f.row, s, f.row, f.row_bytes(), rows, hipMemcpyHostToDevice, h->stream));
-        else
-            HIPCHK(h, hipMemcpy2DAsync(s, f.row, d, f.row, f.row_bytes(), rows, hipMemcpyDeviceToHost, h->stream));
-    }
-    return ARUCOHIP_OK;
-}
-
 // The common part: `slots` marker slots per frame (1 for boards). src / counts: device pointers, or host arrays of `elem` bytes per slot
 // that are staged behind the scratch. build(frames0, nframes, src, counts, recs, prims) enqueues the build kernel of one chunk.
 template <typename Build>
-int draw(arucohip_handle* h, Frames f, const void* src, size_t elem, int slots, const int32_t* counts, int src_on_device, Build build) {
+int draw(arucohip_handle* h, const Frames& f, const void* src, size_t elem, int slots, const int32_t* counts, int src_on_device, Build build) {
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     // the scratch holds the primitive lists of a chunk of frames: at most 64 MiB (and 65535 frames, the grid's z limit), at least one frame
     const size_t per_frame = (size_t)slots * (OV_REC_BYTES + OV_PRIM_BYTES);
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)f.n, 65535, ((size_t)64 << 20) / per_frame}));
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)f.im.n, 65535, ((size_t)64 << 20) / per_frame}));
     const size_t scratch = (size_t)chunk * per_frame;
-    const size_t src_bytes = src_on_device ? 0 : (size_t)f.n * slots * elem, cnt_bytes = (src_on_device || !counts) ? 0 : (size_t)f.n * sizeof(int32_t);
+    const size_t src_bytes = src_on_device ? 0 : (size_t)f.im.n * slots * elem, cnt_bytes = (src_on_device || !counts) ? 0 : (size_t)f.im.n * sizeof(int32_t);
     HIPCHK(h, h->d_overlay.reserve(scratch + src_bytes + cnt_bytes));
     uint8_t* base = h->d_overlay;
     if (!src_on_device) {
@@ -69,26 +53,19 @@ int draw(arucohip_handle* h, Frames f, const void* src, size_t elem, int slots, 
             counts = (const int32_t*)(base + scratch + src_bytes);
         }
     }
-    uint8_t* dev = f.p;
-    if (!f.on_device) {
-        HIPCHK(h, h->d_overlay_frames.reserve(f.extent()));
-        dev = h->d_overlay_frames;
-        int rc = frames_copy(h, f, dev, true);
-        if (rc) return rc;
-    }
+    if (!f.im.on_device) HIPCHK(h, h->d_overlay_frames.reserve(f.im.packed_bytes()));
+    DevImages dev;
+    if (const int rc = stage_input(h, s, f.im, h->d_overlay_frames, 0, &dev)) return rc;
     void *recs = base, *prims = base + (size_t)chunk * slots * OV_REC_BYTES;
-    for (int f0 = 0; f0 < f.n; f0 += chunk) {
-        const int nf = std::min(chunk, f.n - f0);
+    for (int f0 = 0; f0 < f.im.n; f0 += chunk) {
+        const int nf = std::min(chunk, f.im.n - f0);
         build(s, nf, (const uint8_t*)src + (size_t)f0 * slots * elem, counts ? counts + f0 : nullptr, recs, prims);
         HIPCHK(h, hipGetLastError());
-        launch_overlay_raster(s, dev + (size_t)f0 * f.frame, nf, f.w, f.h, f.ch, f.row, f.frame, recs, prims, slots);
+        launch_overlay_raster(s, dev.p + (size_t)f0 * dev.frame, nf, f.w, f.im.rows, f.ch, dev.row, dev.frame, recs, prims, slots);
         HIPCHK(h, hipGetLastError());
     }
-    if (!f.on_device) {
-        int rc = frames_copy(h, f, dev, false);
-        if (rc) return rc;
-    }
-    if (!f.on_device || !src_on_device) HIPCHK(h, hipStreamSynchronize(s));
+    if (const int rc = unstage(h, s, f.im, dev)) return rc;
+    if (!f.im.on_device || !src_on_device) HIPCHK(h, hipStreamSynchronize(s));
     return ARUCOHIP_OK;
 }
 
@@ -100,7 +77,7 @@ int arucohip_draw_markers_batch(arucohip_handle* h, uint8_t* frames, int nframes
                                 size_t frame_stride, int frames_on_device, const arucohip_marker_t* markers, int cap, const int32_t* counts,
                                 int markers_on_device, const float* K, const float* dist, int ndist, const arucohip_overlay_t* style) {
     if (!h) return ARUCOHIP_E_INVALID;
-    const Frames f = {frames, nframes, width, height, channels, row_stride, frame_stride, frames_on_device};
+    const Frames f = make_frames(frames, nframes, width, height, channels, row_stride, frame_stride, frames_on_device);
     int rc = check_frames(h, f);
     if (rc) return rc;
     if (!markers || !counts || cap < 1) return fail(h, ARUCOHIP_E_INVALID, "draw_markers: NULL markers / counts, or cap below 1");
@@ -121,7 +98,7 @@ int arucohip_draw_boards_batch(arucohip_handle* h, uint8_t* frames, int nframes,
                                size_t frame_stride, int frames_on_device, const arucohip_board_t* boards, int boards_on_device, float marker_size,
                                const float* K, const float* dist, int ndist, int flags) {
     if (!h) return ARUCOHIP_E_INVALID;
-    const Frames f = {frames, nframes, width, height, channels, row_stride, frame_stride, frames_on_device};
+    const Frames f = make_frames(frames, nframes, width, height, channels, row_stride, frame_stride, frames_on_device);
     int rc = check_frames(h, f);
     if (rc) return rc;
     if (!boards) return fail(h, ARUCOHIP_E_INVALID, "draw_boards: NULL boards");

@@ -9,86 +9,51 @@ namespace {
 
 // the arguments both entry points share, as the caller gave them
 struct Call {
-    const uint8_t* src;
-    int n, w, h, ch;
-    size_t row, frame;
-    int src_on_device;
+    Images src;
+    int w, ch;
     const float *K, *dist;
     int ndist;
-    uint8_t* dst;
-    int ow, oh;
-    size_t drow, dframe;
-    int dst_on_device;
-    size_t src_row_bytes() const { return (size_t)w * ch; }
-    size_t dst_row_bytes() const { return (size_t)ow * ch; }
-    size_t src_extent() const { return (size_t)(n - 1) * frame + (size_t)(h - 1) * row + src_row_bytes(); }
-    size_t dst_extent() const { return (size_t)(n - 1) * dframe + (size_t)(oh - 1) * drow + dst_row_bytes(); }
+    Images dst;
+    int ow;
 };
+Call make_call(const uint8_t* src, int n, int w, int h, int ch, size_t row, size_t frame, int src_on_device, const float* K, const float* dist, int ndist,
+               uint8_t* dst, int ow, int oh, size_t drow, size_t dframe, int dst_on_device) {
+    return {images(src, n, h, (size_t)w * ch, row, frame, src_on_device), w, ch, K, dist, ndist,
+            images(dst, n, oh, (size_t)ow * ch, drow, dframe, dst_on_device), ow};
+}
 
 int check_call(arucohip_handle* h, const Call& c, bool need_K) {
-    if (!c.src) return fail(h, ARUCOHIP_E_INVALID, "rectify: src (the frames) is NULL");
-    if (!c.dst) return fail(h, ARUCOHIP_E_INVALID, "rectify: dst is NULL");
-    if (c.n < 1) return fail(h, ARUCOHIP_E_INVALID, "rectify: nframes is below 1");
-    if (c.w < 1 || c.h < 1) return fail(h, ARUCOHIP_E_INVALID, "rectify: width / height is below 1");
+    if (!c.src.p) return fail(h, ARUCOHIP_E_INVALID, "rectify: src (the frames) is NULL");
+    if (!c.dst.p) return fail(h, ARUCOHIP_E_INVALID, "rectify: dst is NULL");
+    if (c.src.n < 1) return fail(h, ARUCOHIP_E_INVALID, "rectify: nframes is below 1");
+    if (c.w < 1 || c.src.rows < 1) return fail(h, ARUCOHIP_E_INVALID, "rectify: width / height is below 1");
     if (c.ch != 1 && c.ch != 3) return fail(h, ARUCOHIP_E_INVALID, "rectify: channels must be 1 or 3");
-    if (need_K && !c.K) return fail(h, ARUCOHIP_E_INVALID, "rectify: K is NULL (the board call needs the camera)");
-    if (!(c.ndist == 0 || c.ndist == 4 || c.ndist == 5 || c.ndist == 8)) return fail(h, ARUCOHIP_E_INVALID, "rectify: ndist must be 0, 4, 5 or 8");
-    if (c.ndist > 0 && !c.dist) return fail(h, ARUCOHIP_E_INVALID, "rectify: dist is NULL with ndist > 0");
-    if (c.ndist > 0 && !c.K) return fail(h, ARUCOHIP_E_INVALID, "rectify: dist without K");
-    if (c.ow < 1 || c.oh < 1) return fail(h, ARUCOHIP_E_INVALID, "rectify: out_width / out_height is below 1");
-    if (c.ow > 16383 || c.oh > 16383) return fail(h, ARUCOHIP_E_INVALID, "rectify: out_width / out_height is above 16383");
-    if (c.row < c.src_row_bytes()) return fail(h, ARUCOHIP_E_INVALID, "rectify: row_stride is smaller than width * channels");
-    if (c.n > 1 && c.frame < (size_t)(c.h - 1) * c.row + c.src_row_bytes()) return fail(h, ARUCOHIP_E_INVALID, "rectify: frame_stride is smaller than a frame");
-    if (c.drow < c.dst_row_bytes()) return fail(h, ARUCOHIP_E_INVALID, "rectify: dst_row_stride is smaller than out_width * channels");
-    if (c.n > 1 && c.dframe < (size_t)(c.oh - 1) * c.drow + c.dst_row_bytes())
-        return fail(h, ARUCOHIP_E_INVALID, "rectify: dst_frame_stride is smaller than an image");
-    // host and device addresses share one space, so one comparison serves every combination
-    const uintptr_t s0 = (uintptr_t)c.src, d0 = (uintptr_t)c.dst;
-    if (s0 < d0 + c.dst_extent() && d0 < s0 + c.src_extent()) return fail(h, ARUCOHIP_E_INVALID, "rectify: dst overlaps src");
-    return ARUCOHIP_OK;
-}
-
-// one call's scratch in d_rectify
-struct Scratch {
-    double* maps;
-    int32_t* valid;
-    arucohip_board_t* boards;
-};
-size_t scratch_layout(uint8_t* base, int n, Scratch* s) {
-    Carver cv{base};
-    s->maps = cv.take<double>((size_t)n * 9);
-    s->valid = cv.take<int32_t>((size_t)n);
-    s->boards = cv.take<arucohip_board_t>((size_t)n);
-    return cv.at;
-}
-int reserve_scratch(arucohip_handle* h, int n, Scratch* s) {
-    HIPCHK(h, h->d_rectify.reserve(scratch_layout(nullptr, n, s)));
-    scratch_layout(h->d_rectify, n, s);
-    return ARUCOHIP_OK;
+    if (const int rc = check_plane_camera(h, "rectify", need_K, c.K, c.dist, c.ndist)) return rc;
+    if (c.ow < 1 || c.dst.rows < 1) return fail(h, ARUCOHIP_E_INVALID, "rectify: out_width / out_height is below 1");
+    if (c.ow > 16383 || c.dst.rows > 16383) return fail(h, ARUCOHIP_E_INVALID, "rectify: out_width / out_height is above 16383");
+    if (const int rc = check_strides(h, "rectify", "", c.src)) return rc;
+    if (const int rc = check_strides(h, "rectify", "dst_", c.dst)) return rc;
+    return check_disjoint(h, "rectify", "dst", c.dst, "src", c.src);
 }
 
 // The resampling of a checked call with device maps: host frames go up, host images come back. Queues only; the caller synchronises.
 int warp(arucohip_handle* h, const Call& c, const double* maps, const int32_t* valid) {
-    const size_t src_bytes = c.src_on_device ? 0 : ((size_t)c.n * c.h * c.src_row_bytes() + 255) & ~(size_t)255;
-    const size_t dst_bytes = c.dst_on_device ? 0 : (size_t)c.n * c.oh * c.dst_row_bytes();
-    HIPCHK(h, h->d_rectify_frames.reserve(src_bytes + dst_bytes));
+    const size_t src_bytes = c.src.on_device ? 0 : (c.src.packed_bytes() + 255) & ~(size_t)255;
+    HIPCHK(h, h->d_rectify_frames.reserve(src_bytes + (c.dst.on_device ? 0 : c.dst.packed_bytes())));
+    DevImages src, dst;
+    if (const int rc = stage_input(h, h->stream, c.src, h->d_rectify_frames, 0, &src)) return rc;
+    if (const int rc = stage_output(h, c.dst, h->d_rectify_frames, src_bytes, &dst)) return rc;
     PlaneWarp a;
     std::memset(&a, 0, sizeof(a));
-    a.src = c.src, a.row_stride = c.row, a.frame_stride = c.frame;
-    if (!c.src_on_device) {
-        if (const int rc = copy_rows(h, const_cast<uint8_t*>(c.src), c.row, c.frame, c.src_row_bytes(), c.h, c.n, h->d_rectify_frames, true)) return rc;
-        a.src = h->d_rectify_frames, a.row_stride = c.src_row_bytes(), a.frame_stride = (size_t)c.h * c.src_row_bytes();
-    }
-    a.dst = c.dst, a.dst_row_stride = c.drow, a.dst_frame_stride = c.dframe;
-    if (!c.dst_on_device) a.dst = h->d_rectify_frames + src_bytes, a.dst_row_stride = c.dst_row_bytes(), a.dst_frame_stride = (size_t)c.oh * c.dst_row_bytes();
-    a.width = c.w, a.height = c.h, a.out_width = c.ow, a.out_height = c.oh;
+    a.src = src.p, a.row_stride = src.row, a.frame_stride = src.frame;
+    a.dst = dst.p, a.dst_row_stride = dst.row, a.dst_frame_stride = dst.frame;
+    a.width = c.w, a.height = c.src.rows, a.out_width = c.ow, a.out_height = c.dst.rows;
     a.maps = maps, a.valid = valid;
     a.fx = c.K ? (double)c.K[0] : 1.0, a.fy = c.K ? (double)c.K[4] : 1.0, a.cx = c.K ? (double)c.K[2] : 0.0, a.cy = c.K ? (double)c.K[5] : 0.0;
     for (int i = 0; i < c.ndist; i++) a.k[i] = (double)c.dist[i];
-    launch_plane_warp(h->stream, a, c.ch, c.ndist > 0, c.n);
+    launch_plane_warp(h->stream, a, c.ch, c.ndist > 0, c.src.n);
     HIPCHK(h, hipGetLastError());
-    if (!c.dst_on_device) return copy_rows(h, c.dst, c.drow, c.dframe, c.dst_row_bytes(), c.oh, c.n, a.dst, false);
-    return ARUCOHIP_OK;
+    return unstage(h, h->stream, c.dst, dst);
 }
 
 }  // namespace
@@ -100,21 +65,12 @@ int arucohip_warp_plane_batch(arucohip_handle* h, const uint8_t* src, int nframe
                               const float* K, const float* dist, int ndist, uint8_t* dst, int out_width, int out_height,
                               size_t dst_row_stride, size_t dst_frame_stride, int dst_on_device) {
     if (!h) return ARUCOHIP_E_INVALID;
-    const Call c = {src, nframes, width, height, channels, row_stride, frame_stride, src_on_device, K, dist, ndist,
-                    dst, out_width, out_height, dst_row_stride, dst_frame_stride, dst_on_device};
+    const Call c = make_call(src, nframes, width, height, channels, row_stride, frame_stride, src_on_device, K, dist, ndist, dst, out_width, out_height,
+                             dst_row_stride, dst_frame_stride, dst_on_device);
     if (!maps) return fail(h, ARUCOHIP_E_INVALID, "rectify: maps is NULL");
     if (const int rc = check_call(h, c, false)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    if (!maps_on_device) {
-        Scratch sc;
-        if (const int rc = reserve_scratch(h, nframes, &sc)) return rc;
-        HIPCHK(h, hipMemcpyAsync(sc.maps, maps, (size_t)nframes * 9 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        maps = sc.maps;
-        if (valid) {
-            HIPCHK(h, hipMemcpyAsync(sc.valid, valid, (size_t)nframes * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-            valid = sc.valid;
-        }
-    }
+    if (const int rc = stage_plane_maps(h, h->d_rectify, nframes, maps_on_device, &maps, &valid)) return rc;
     if (const int rc = warp(h, c, maps, valid)) return rc;
     if (!src_on_device || !maps_on_device || !dst_on_device) HIPCHK(h, hipStreamSynchronize(h->stream));
     return ARUCOHIP_OK;
@@ -153,25 +109,17 @@ int arucohip_board_rectify_batch(arucohip_handle* h, const uint8_t* frames, int 
     if (!h) return ARUCOHIP_E_INVALID;
     if (!boards) return fail(h, ARUCOHIP_E_INVALID, "rectify: boards is NULL");
     if (!win) return fail(h, ARUCOHIP_E_INVALID, "rectify: win (the window) is NULL");
-    const Call c = {frames, nframes, width, height, channels, row_stride, frame_stride, frames_on_device, K, dist, ndist,
-                    dst, win->out_width, win->out_height, dst_row_stride, dst_frame_stride, dst_on_device};
+    const Call c = make_call(frames, nframes, width, height, channels, row_stride, frame_stride, frames_on_device, K, dist, ndist, dst, win->out_width,
+                             win->out_height, dst_row_stride, dst_frame_stride, dst_on_device);
     if (const int rc = check_call(h, c, true)) return rc;
     if (!window_spans_plane(*win))
         return fail(h, ARUCOHIP_E_INVALID, "rectify: the window's u and v steps are parallel, zero or not finite");
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    Scratch sc;
-    if (const int rc = reserve_scratch(h, nframes, &sc)) return rc;
-    if (!boards_on_device) {
-        HIPCHK(h, hipMemcpyAsync(sc.boards, boards, (size_t)nframes * sizeof(arucohip_board_t), hipMemcpyHostToDevice, s));
-        boards = sc.boards;
-    }
-    launch_plane_maps(s, boards, nframes, *win, sc.maps, sc.valid);
-    HIPCHK(h, hipGetLastError());
-    if (const int rc = warp(h, c, sc.maps, sc.valid)) return rc;
-    if (status) HIPCHK(h, hipMemcpyAsync(status, sc.valid, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (maps_out) HIPCHK(h, hipMemcpyAsync(maps_out, sc.maps, (size_t)nframes * 9 * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (!frames_on_device || !boards_on_device || !dst_on_device || status || maps_out) HIPCHK(h, hipStreamSynchronize(s));
+    PlaneMaps m;
+    if (const int rc = plane_maps_of_boards(h, h->d_rectify, launch_plane_maps, boards, boards_on_device, nframes, *win, &m)) return rc;
+    if (const int rc = warp(h, c, m.maps, m.valid)) return rc;
+    if (const int rc = read_plane_maps(h, m, nframes, status, maps_out)) return rc;
+    if (!frames_on_device || !boards_on_device || !dst_on_device || status || maps_out) HIPCHK(h, hipStreamSynchronize(h->stream));
     return ARUCOHIP_OK;
 }
 

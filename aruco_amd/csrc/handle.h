@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "fisheye_device.h"
+#include "frames_host.h"
 #include "internal.h"
 #include "thr_plan.h"
 
@@ -284,18 +285,119 @@ struct Carver {
     }
 };
 
-// rows of `bytes` bytes between a host array with strides (row, frame) and the tightly packed device array `dev`, on h's stream
-inline int copy_rows(arucohip_handle* h, uint8_t* host, size_t row, size_t frame, size_t bytes, int rows, int n, uint8_t* dev, bool up) {
-    const bool flat = frame == row * (size_t)rows;
-    const int calls = flat ? 1 : n;
-    const size_t per = flat ? (size_t)n * rows : (size_t)rows;
-    for (int i = 0; i < calls; i++) {
-        uint8_t *hp = host + (size_t)i * frame, *dp = dev + (size_t)i * rows * bytes;
-        if (up)
-            HIPCHK(h, hipMemcpy2DAsync(dp, bytes, hp, row, bytes, per, hipMemcpyHostToDevice, h->stream));
-        else
-            HIPCHK(h, hipMemcpy2DAsync(hp, row, dp, bytes, bytes, per, hipMemcpyDeviceToHost, h->stream));
+// Image batches of the caller (frames_host.h) as the kernels take them. A batch on the device is used where it lies, at the caller's
+// strides. A host batch is staged packed at mem + at, image i at i * staged_frame (0: the images back to back), in the Mem of the
+// entry point it belongs to, which the caller has reserved: stage_input queues the upload on s, stage_output queues nothing, unstage
+// queues the way back of an output or of a batch changed in place (nothing for a device batch). None of them synchronises. These and
+// the checks below are static, so the library's exported symbols stay the C ABI's and the older inline helpers'.
+struct DevImages {
+    uint8_t* p;
+    size_t row, frame;
+};
+static inline int stage_output(arucohip_handle* h, const Images& im, const Mem<uint8_t>& mem, size_t at, DevImages* v, size_t staged_frame = 0) {
+    *v = {im.p, im.row, im.frame};
+    if (im.on_device) return ARUCOHIP_OK;
+    const size_t frame = staged_frame ? staged_frame : im.packed_frame();
+    if (!mem.p || at + (size_t)(im.n - 1) * frame + im.packed_frame() > mem.bytes)
+        return fail(h, ARUCOHIP_E_HIP, "staging memory is smaller than the images it is to hold");
+    *v = {mem.p + at, im.packed_row(), frame};
+    return ARUCOHIP_OK;
+}
+static inline int stage_input(arucohip_handle* h, hipStream_t s, const Images& im, const Mem<uint8_t>& mem, size_t at, DevImages* v, size_t staged_frame = 0) {
+    if (const int rc = stage_output(h, im, mem, at, v, staged_frame)) return rc;
+    if (im.on_device) return ARUCOHIP_OK;
+    return im.for_each_copy(
+        [&](size_t from, size_t pitch, size_t to, size_t packed_pitch, size_t bytes, size_t rows) -> int {
+            HIPCHK(h, hipMemcpy2DAsync(v->p + to, packed_pitch, im.p + from, pitch, bytes, rows, hipMemcpyHostToDevice, s));
+            return ARUCOHIP_OK;
+        },
+        v->frame);
+}
+static inline int unstage(arucohip_handle* h, hipStream_t s, const Images& im, const DevImages& v) {
+    if (im.on_device) return ARUCOHIP_OK;
+    return im.for_each_copy(
+        [&](size_t to, size_t pitch, size_t from, size_t packed_pitch, size_t bytes, size_t rows) -> int {
+            HIPCHK(h, hipMemcpy2DAsync(im.p + to, pitch, v.p + from, packed_pitch, bytes, rows, hipMemcpyDeviceToHost, s));
+            return ARUCOHIP_OK;
+        },
+        v.frame);
+}
+
+// The refusals every image entry point words the same way: `call` is its prefix ("rectify", "draw", ...), `arg` what precedes
+// row_stride / frame_stride in the argument's name ("", "dst_", "tex->").
+static inline int check_strides(arucohip_handle* h, const char* call, const char* arg, const Images& im) {
+    const Images::Strides bad = im.check_strides();
+    if (bad == Images::STRIDES_OK) return ARUCOHIP_OK;
+    const std::string msg = std::string(call) + ": " + arg +
+                            (bad == Images::ROW_BELOW_ROW_BYTES ? "row_stride is smaller than a row of the image" : "frame_stride is smaller than an image");
+    return fail(h, ARUCOHIP_E_INVALID, msg.c_str());
+}
+static inline int check_disjoint(arucohip_handle* h, const char* call, const char* a_name, const Images& a, const char* b_name, const Images& b) {
+    if (!a.overlaps(b)) return ARUCOHIP_OK;
+    const std::string msg = std::string(call) + ": " + a_name + " overlaps " + b_name;
+    return fail(h, ARUCOHIP_E_INVALID, msg.c_str());
+}
+
+// The camera arguments of the plane calls (rectify, composite): K only where the call needs it, dist only with K.
+static inline int check_plane_camera(arucohip_handle* h, const char* call, bool need_K, const float* K, const float* dist, int ndist) {
+    const char* bad = need_K && !K                                                ? "K is NULL (the board call needs the camera)"
+                      : !(ndist == 0 || ndist == 4 || ndist == 5 || ndist == 8) ? "ndist must be 0, 4, 5 or 8"
+                      : ndist > 0 && !dist                                        ? "dist is NULL with ndist > 0"
+                      : ndist > 0 && !K                                           ? "dist without K"
+                                                                                  : nullptr;
+    if (!bad) return ARUCOHIP_OK;
+    const std::string msg = std::string(call) + ": " + bad;
+    return fail(h, ARUCOHIP_E_INVALID, msg.c_str());
+}
+
+// The plane maps of one rectify or composite call, in the scratch of the entry point (d_rectify / d_composite): one 3 x 3 map and
+// one valid word per frame, and the staged boards of a board call.
+struct PlaneMaps {
+    double* maps;
+    int32_t* valid;
+    arucohip_board_t* boards;
+};
+static inline int reserve_plane_maps(arucohip_handle* h, Mem<uint8_t>& mem, int n, PlaneMaps* m) {
+    auto layout = [&](uint8_t* base) {
+        Carver cv{base};
+        m->maps = cv.take<double>((size_t)n * 9);
+        m->valid = cv.take<int32_t>((size_t)n);
+        m->boards = cv.take<arucohip_board_t>((size_t)n);
+        return cv.at;
+    };
+    HIPCHK(h, mem.reserve(layout(nullptr)));
+    layout(mem);
+    return ARUCOHIP_OK;
+}
+// the caller's own maps and valid words: where they are on the device, else uploaded on h's stream and *maps / *valid repointed
+static inline int stage_plane_maps(arucohip_handle* h, Mem<uint8_t>& mem, int n, int on_device, const double** maps, const int32_t** valid) {
+    if (on_device) return ARUCOHIP_OK;
+    PlaneMaps m;
+    if (const int rc = reserve_plane_maps(h, mem, n, &m)) return rc;
+    HIPCHK(h, hipMemcpyAsync(m.maps, *maps, (size_t)n * 9 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    *maps = m.maps;
+    if (*valid) {
+        HIPCHK(h, hipMemcpyAsync(m.valid, *valid, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        *valid = m.valid;
     }
+    return ARUCOHIP_OK;
+}
+// the maps of a board call: host boards go up, `launch` (launch_plane_maps / launch_plane_inverse_maps) writes maps and valid words
+static inline int plane_maps_of_boards(arucohip_handle* h, Mem<uint8_t>& mem, decltype(launch_plane_maps)* launch, const arucohip_board_t* boards,
+                                int boards_on_device, int n, const arucohip_rectify_t& win, PlaneMaps* m) {
+    if (const int rc = reserve_plane_maps(h, mem, n, m)) return rc;
+    if (!boards_on_device) {
+        HIPCHK(h, hipMemcpyAsync(m->boards, boards, (size_t)n * sizeof(arucohip_board_t), hipMemcpyHostToDevice, h->stream));
+        boards = m->boards;
+    }
+    launch(h->stream, boards, n, win, m->maps, m->valid);
+    HIPCHK(h, hipGetLastError());
+    return ARUCOHIP_OK;
+}
+// ... and what a board call hands back of them, queued behind the call's own work
+static inline int read_plane_maps(arucohip_handle* h, const PlaneMaps& m, int n, int32_t* status, double* maps_out) {
+    if (status) HIPCHK(h, hipMemcpyAsync(status, m.valid, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (maps_out) HIPCHK(h, hipMemcpyAsync(maps_out, m.maps, (size_t)n * 9 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     return ARUCOHIP_OK;
 }
 
