@@ -1100,15 +1100,24 @@ __device__ __forceinline__ void polygon_to_quad(const QuadArgs& a, const Contour
 // the fixed cost of every approxPolyDP iteration - stack traffic, two reductions on the DPP network, the fp64 test, the barriers; about 150
 // instructions against 10 per 64 points scanned - per border; with two, the halves run the same instruction stream on their own border. Every
 // quantity below is uniform per group of G lanes: for G = 64 wave-uniform, so that instantiation's control flow is scalar.
+//
+// ONE LDS array, `rows`, is the emitting lanes' 32x32 blocks and then the border's points (LDSP: P = its start, half h at + h * DUAL_MAX). The two lives never
+// meet: a border of at most QP_LDS (DUAL_MAX) points is ONE emission round of the wave (half), so every lane keeps the CK points of its stretch in
+// registers while the blocks are read, a barrier ends the last step of every lane, and only then are the points stored over the blocks; a second barrier
+// stands before the first scan. The blocks are dead from the first barrier on: nothing after emission reads one. The other paths keep the array as blocks
+// only (LDSP = false: several rounds, points straight to the border's pool range) or as points only (from_pool: no blocks), and late_quad_kernel's walker
+// workgroups never come here. Four kilobytes less per workgroup is what lets a fourth wave per SIMD stay resident (QUAD_WAVES_N below).
 template <int G, bool LDSP>
-__device__ __forceinline__ void border_to_quad(const QuadArgs& a, const ContourDesc& cd, const uint32_t ci, short2* Plds, int (*s_stack)[16][2], short2 (*s_out)[12],
-                                               uint32_t* rows) {
+__device__ __forceinline__ void border_to_quad(const QuadArgs& a, const ContourDesc& cd, const uint32_t ci, int (*s_stack)[16][2], short2 (*s_out)[12], uint32_t* rows) {
     static_assert(G == WAVE || (G == WAVE / 2 && LDSP), "a half wave's border is one of at most DUAL_MAX points in LDS");
+    static_assert(WAVE * CK >= QP_LDS && (WAVE / 2) * CK >= DUAL_MAX, "a border whose points go to LDS is one emission round: every stretch has its own lane");
+    static_assert(QP_LDS * sizeof(short2) <= TB_ROWS * WAVE * sizeof(uint32_t) && QP_LDS >= 2 * DUAL_MAX, "the points overlay the emission blocks");
+    static_assert(QP_LDS % CK == 0 && DUAL_MAX % CK == 0, "a lane stores its whole stretch: the last one's padding stays inside the border's own range");
     // h = lane / G, with the 0 of G = 64 written out: the compiler does not conclude lane < 64 from the launch bounds, and an h it takes to differ
     // between lanes turns that instantiation's stack and vertex accesses, and every branch behind them, divergent
     const int lane = threadIdx.x, h = G == WAVE ? 0 : lane / G, hl = lane - h * G;
     const bool upper = h != 0;
-    short2* P = LDSP ? Plds + h * DUAL_MAX : a.pool + cd.pool_off;
+    short2* P = LDSP ? (short2*)rows + h * DUAL_MAX : a.pool + cd.pool_off;
     const int count = cd.n;
     // ---- points: already emitted (segment pipeline) or every lane resumes the walk at one checkpoint and records CK points
     if (a.from_pool) {
@@ -1124,11 +1133,11 @@ __device__ __forceinline__ void border_to_quad(const QuadArgs& a, const ContourD
         // of L steps from A to B cannot leave their bounding box by more than (L - |dx|) / 2 columns or (L - |dy|) / 2 rows (a pixel further
         // out would need more than L steps to be reached from A and left towards B), so with the ring of neighbours the stretch spans at most
         // 19 pixels each way and a tile-aligned block of 32 that holds it always exists.
-        // The trip count is wave-uniform: a border's own number of rounds for G = 64, the one round that DUAL_MAX points need for G = 32.
+        // The trip count is wave-uniform: ONE round for a border whose points go to LDS, the border's own number of rounds for a longer one.
         uint32_t* P32 = (uint32_t*)P;
         const uint32_t* rb = rows + lane - WAVE;
-        const int kend = G == WAVE ? ncp : (DUAL_MAX + CK - 1) / CK;
-        for (int k0 = 0; k0 < kend; k0 += G) {
+        uint32_t pts[CK];   // LDSP: the stretch's points, in registers until every lane has taken its last step (the j loop is unrolled: no indexing at run time)
+        for (int k0 = 0; k0 < (LDSP ? 1 : ncp); k0 += G) {
             const int k = k0 + hl;
             if (k >= ncp) continue;
             const uint32_t c = ckp[k];
@@ -1150,10 +1159,19 @@ __device__ __forceinline__ void border_to_quad(const QuadArgs& a, const ContourD
             uint32_t lp = pos - base1, s1c = tb_s1c((int)(c >> 28));
 #pragma unroll
             for (int j = 0; j < CK; j++) {
+                if constexpr (LDSP) pts[j] = lp + base1;   // behind the end of the last stretch: the end repeated, into words of the border's own range that nothing reads
                 if (n0 + j < n1) {
-                    P32[n0 + j] = lp + base1;
+                    if constexpr (!LDSP) P32[n0 + j] = lp + base1;
                     tb_step<WAVE>(rb, lp, s1c);
                 }
+            }
+        }
+        if constexpr (LDSP) {
+            __syncthreads();   // every lane has read its block for the last time: from here on the array is the border's points
+            if (hl < ncp) {
+                uint4* dst = (uint4*)(P32 + hl * CK);
+#pragma unroll
+                for (int q = 0; q < CK / 4; q++) dst[q] = make_uint4(pts[4 * q], pts[4 * q + 1], pts[4 * q + 2], pts[4 * q + 3]);
             }
         }
     }
@@ -1254,7 +1272,7 @@ __device__ __forceinline__ void border_to_quad(const QuadArgs& a, const ContourD
 // whose L2 then serves the plane's tiles, descriptors and checkpoints to all of them (same unpacking as walker_kernel).
 // pass 0: all borders of TC_CDESC; pass 1: those that existed when the late walker generations were forked; pass 2: the rest; pass 3: the planes' late
 // lists (keep_border<true>: TC_LATE descriptors from the top of the plane's array downwards).
-__device__ __forceinline__ void quad_blocks(const QuadArgs& a, const int bid, short2* Plds, uint32_t* rows, int (*s_stack)[16][2], short2 (*s_out)[12]) {
+__device__ __forceinline__ void quad_blocks(const QuadArgs& a, const int bid, uint32_t* rows, int (*s_stack)[16][2], short2 (*s_out)[12]) {
     const int xcd = bid & 7, rest = bid >> 3;
     const int chunk = rest % a.qblocks, plane = (rest / a.qblocks) * 8 + xcd;
     if (plane >= a.nplanes) return;
@@ -1263,6 +1281,11 @@ __device__ __forceinline__ void quad_blocks(const QuadArgs& a, const int bid, sh
     const uint32_t nlate = a.pass == 3 ? min(a.trig_cnt[plane * TRIG_CNT_STRIDE + TC_LATE], a.cap_cdesc - nall) : 0u;
     const uint32_t lo = a.pass == 2 ? nsnap : 0u, ncd = a.pass == 3 ? nlate : a.pass == 1 ? nsnap : nall;
     const bool upper = threadIdx.x >= 32;
+    // The barrier in front of every border_to_quad call below is what lets the next border's block loads overwrite the last border's points: inside a call every
+    // read of the points (the scans, the recursion's end points, the write-back to the pool) is followed by a barrier before the call returns - the lane that
+    // writes the quad reads vertices only - and a call that uses the array as blocks alone (a border above QP_LDS points) has read them for the last time before
+    // its own barrier behind emission. So short, paired, long and late borders may follow each other in any order; a pending short border is descriptor words
+    // in registers until its call.
     ContourDesc pend;   // a short border waiting for a partner
     uint32_t pend_ci = 0;
     bool has_pend = false;
@@ -1276,30 +1299,33 @@ __device__ __forceinline__ void quad_blocks(const QuadArgs& a, const int bid, sh
                 continue;
             }
             __syncthreads();
-            border_to_quad<WAVE / 2, true>(a, upper ? cd : pend, upper ? ci : pend_ci, Plds, s_stack, s_out, rows);
+            border_to_quad<WAVE / 2, true>(a, upper ? cd : pend, upper ? ci : pend_ci, s_stack, s_out, rows);
             has_pend = false;
             continue;
         }
         __syncthreads();
         if (cd.n <= QP_LDS)
-            border_to_quad<WAVE, true>(a, cd, ci, Plds, s_stack, s_out, rows);
+            border_to_quad<WAVE, true>(a, cd, ci, s_stack, s_out, rows);
         else
-            border_to_quad<WAVE, false>(a, cd, ci, Plds, s_stack, s_out, rows);
+            border_to_quad<WAVE, false>(a, cd, ci, s_stack, s_out, rows);
     }
     if (has_pend) {   // no partner came: all 64 lanes on the one border
         __syncthreads();
-        border_to_quad<WAVE, true>(a, pend, pend_ci, Plds, s_stack, s_out, rows);
+        border_to_quad<WAVE, true>(a, pend, pend_ci, s_stack, s_out, rows);
     }
 }
 
-__global__ __launch_bounds__(64) void contour_quad_kernel(QuadArgs a) {
+#ifndef QUAD_WAVES_N
+#define QUAD_WAVES_N 4   // waves per SIMD the register allocator is held to in contour_quad_kernel and late_quad_kernel. 8 544 B of LDS admit 16 one-wave workgroups per CU;
+                         // the attribute brings the registers from 143 to at most 128 without scratch. 3 is the build for the A/B (profiles/quad_overlay_ab.txt)
+#endif
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QUAD_WAVES_N, QUAD_WAVES_N))) void contour_quad_kernel(QuadArgs a) {
     throughput_bound_priority();
-    __shared__ __align__(16) short2 Plds[QP_LDS];   // contour points (two borders of up to DUAL_MAX points, or one of up to QP_LDS)
-    __shared__ uint32_t rows[TB_ROWS * WAVE];  // one 32x32-pixel block per emitting lane
+    // one 32x32-pixel block per emitting lane, then the border's points: two borders of up to DUAL_MAX points, or one of up to QP_LDS (border_to_quad)
+    __shared__ __align__(16) uint32_t rows[TB_ROWS * WAVE];
     __shared__ int s_stack[2][16][2];
     __shared__ short2 s_out[2][12];
-    static_assert(QP_LDS >= 2 * DUAL_MAX, "the two-borders-per-wave path uses the whole point buffer");
-    quad_blocks(a, blockIdx.x, Plds, rows, s_stack, s_out);
+    quad_blocks(a, blockIdx.x, rows, s_stack, s_out);
 }
 
 // A pipeline lane's late walks and contour_quad's pass over the borders known when the launch starts, in ONE launch (launch_late_quads): one stream
@@ -1311,9 +1337,8 @@ struct LateQuadArgs {
     WalkArgs w;
     QuadArgs q;
 };
-__global__ __launch_bounds__(64) void late_quad_kernel(LateQuadArgs a) {
-    __shared__ __align__(16) short2 Plds[QP_LDS];
-    __shared__ uint32_t rows[TB_ROWS * WAVE];   // walker role: one 32x32-pixel block per walking lane
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QUAD_WAVES_N, QUAD_WAVES_N))) void late_quad_kernel(LateQuadArgs a) {
+    __shared__ __align__(16) uint32_t rows[TB_ROWS * WAVE];   // walker role: one 32x32-pixel block per walking lane; quad role: blocks, then points
     __shared__ int s_stack[2][16][2];
     __shared__ short2 s_out[2][12];
     const int nwalk = 2 * a.w.gen_blocks;
@@ -1326,15 +1351,20 @@ __global__ __launch_bounds__(64) void late_quad_kernel(LateQuadArgs a) {
         return;
     }
     throughput_bound_priority();
-    quad_blocks(a.q, (int)blockIdx.x - nwalk, Plds, rows, s_stack, s_out);
+    quad_blocks(a.q, (int)blockIdx.x - nwalk, rows, s_stack, s_out);
 }
 
 // workgroups per plane of contour_quad's passes 0 and 1
+#ifndef QUAD_BLOCKS_N
+#define QUAD_BLOCKS_N 12
+#endif
 static int quad_blocks_per_plane(int nplanes) {
     // workgroups per plane of a batch. One border per wave (rounds 1-3): 8: 0.93 ms, 16: 0.68, 24: 0.60, 32: 0.72 -> 24. Two borders per wave
     // (round 4): a workgroup needs an even number of short borders to pair them all, so fewer, longer lists: 24 / 16 / 12 = 467.7k / 471.1k /
     // 480.0k frames/s (flat stream), 273.1k / 276.2k / 276.2k (cluttered), same box
-    constexpr int kBlocks = 12;
+    // With 8 544 B of LDS per workgroup 16 are resident per CU, 4 096 on the chip: a batch's 12 288 workgroups are three rounds instead of four. 16 per plane measured
+    // again: 470.5-471.7 k against 471.4-472.0 k at 12 (profiles/quad_overlay_ab.txt): 12 stays
+    constexpr int kBlocks = QUAD_BLOCKS_N;
     // a handful of planes (one detect() per frame): a wave per kept border instead of a few waves that take the borders one after the other
     return nplanes <= 2 ? 128 : nplanes <= 8 ? 48 : kBlocks;
 }
