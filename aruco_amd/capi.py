@@ -142,6 +142,74 @@ def texture(tex, opacity=255, per_frame=False):
     return t
 
 
+class Mesh(C.Structure):
+    """arucohip_mesh_t: what arucohip_render_markers_batch / arucohip_render_boards_batch draw. mesh() fills one."""
+    _fields_ = [("vertices", C.c_void_p), ("triangles", C.c_void_p), ("colors", C.c_void_p), ("nverts", C.c_int32), ("ntris", C.c_int32),
+                ("on_device", C.c_int32), ("pad_", C.c_int32)]
+
+
+class Render(C.Structure):
+    """arucohip_render_t: RENDER_* flags, opacity and ambient 0..255, the scale, the direction towards the light (camera frame) and the
+    colour (B, G, R) of a mesh without colours of its own. render_style() fills one."""
+    _fields_ = [("flags", C.c_int32), ("opacity", C.c_int32), ("ambient", C.c_int32), ("scale", C.c_float), ("light", C.c_float * 3),
+                ("color", C.c_uint8 * 4)]
+
+
+assert C.sizeof(Mesh) == 40 and C.sizeof(Render) == 32
+RENDER_CULL_BACK, RENDER_UNLIT, RENDER_EDGES_INT64 = 1, 2, 4
+
+
+def mesh(vertices, triangles, colors=None):
+    """The Mesh of float32 [nverts][3] vertices, int32 [ntris][3] indices and optional uint8 [ntris][3] B G R colours: numpy arrays
+    (converted where needed) or contiguous torch tensors on the device, all of one kind. The record keeps references to the arrays."""
+    if isinstance(vertices, (np.ndarray, list, tuple)):
+        vertices = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        triangles = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
+        colors = None if colors is None else np.ascontiguousarray(colors, dtype=np.uint8).reshape(-1, 3)
+    assert colors is None or len(colors) == len(triangles)
+    (vp, vd), (tp, td) = Handle._buf(vertices), Handle._buf(triangles)
+    cp, cd = (None, vd) if colors is None else Handle._buf(colors)
+    assert vd == td == cd
+    m = Mesh(vp.value, tp.value, cp.value if cp is not None else None, len(vertices), len(triangles), vd, 0)
+    m._keep = (vertices, triangles, colors)
+    return m
+
+
+def render_style(flags=RENDER_CULL_BACK, opacity=255, ambient=64, scale=1.0, light=(0.0, 0.0, -1.0), color=(0, 200, 0)):
+    return Render(int(flags), int(opacity), int(ambient), float(scale), (C.c_float * 3)(*[float(v) for v in light]),
+                  (C.c_uint8 * 4)(*[int(c) for c in color][:3], 0))
+
+
+def cube_mesh():
+    """The unit cube on the pose's plane: [-0.5, 0.5]^2 x [0, 1], 8 vertices, 12 outward (counter-clockwise) triangles."""
+    v = np.array([[x, y, z] for z in (0.0, 1.0) for y in (-0.5, 0.5) for x in (-0.5, 0.5)], np.float32)
+    quads = [(0, 2, 3, 1), (4, 5, 7, 6), (0, 1, 5, 4), (2, 6, 7, 3), (0, 4, 6, 2), (1, 3, 7, 5)]
+    t = np.array([tri for a, b, c, d in quads for tri in ((a, b, c), (a, c, d))], np.int32)
+    return v, t
+
+
+def uv_sphere_mesh(stacks, slices, radius=0.5, center=(0.0, 0.0, 0.5)):
+    """A latitude / longitude sphere: 2 + (stacks - 1) * slices vertices, 2 * slices * (stacks - 1) outward triangles."""
+    assert stacks >= 2 and slices >= 3
+    v = [(0.0, 0.0, 1.0)]
+    for i in range(1, stacks):
+        th = np.pi * i / stacks
+        for j in range(slices):
+            ph = 2.0 * np.pi * j / slices
+            v.append((np.sin(th) * np.cos(ph), np.sin(th) * np.sin(ph), np.cos(th)))
+    v.append((0.0, 0.0, -1.0))
+    ring = lambda i, j: 1 + (i - 1) * slices + j % slices   # noqa: E731
+    south = len(v) - 1
+    t = []
+    for j in range(slices):
+        t.append((0, ring(1, j), ring(1, j + 1)))
+        for i in range(1, stacks - 1):
+            t.append((ring(i, j), ring(i + 1, j), ring(i + 1, j + 1)))
+            t.append((ring(i, j), ring(i + 1, j + 1), ring(i, j + 1)))
+        t.append((south, ring(stacks - 1, j + 1), ring(stacks - 1, j)))
+    return (np.asarray(v, np.float64) * radius + np.asarray(center, np.float64)).astype(np.float32), np.asarray(t, np.int32)
+
+
 class FrameFormat(C.Structure):
     """arucohip_frame_format_t: how a caller's frames are stored (camera-native input). bits belongs to GRAY16, chroma_offset to NV12."""
     _fields_ = [("format", C.c_int32), ("bits", C.c_int32), ("chroma_offset", C.c_uint64)]
@@ -239,6 +307,7 @@ SYMBOLS = [
     "arucohip_fisheye_undistort_markers_batch", "arucohip_fisheye_calibrate", "arucohip_fisheye_calibrate_board_batch",
     "arucohip_warp_plane_batch", "arucohip_rectify_board_window", "arucohip_board_rectify_batch",
     "arucohip_composite_plane_batch", "arucohip_board_composite_batch",
+    "arucohip_default_render", "arucohip_render_markers_batch", "arucohip_render_boards_batch", "arucohip_render_times",
     "arucohip_frame_min_row_stride", "arucohip_frame_min_stride", "arucohip_convert_batch", "arucohip_export_batch",
 ]
 
@@ -413,6 +482,11 @@ def load():
     L.arucohip_board_rectify_batch.argtypes = [vp, vp, i, i, i, i, sz, sz, i, vp, i, vp, vp, i, vp, vp, sz, sz, i, vp, vp]
     L.arucohip_composite_plane_batch.argtypes = [vp, vp, i, i, i, i, sz, sz, i, vp, vp, vp, i, vp, vp, i, vp, i]
     L.arucohip_board_composite_batch.argtypes = [vp, vp, i, i, i, i, sz, sz, i, vp, i, vp, vp, i, vp, vp, vp, i, vp, vp]
+    L.arucohip_default_render.argtypes = [vp]
+    L.arucohip_default_render.restype = None
+    L.arucohip_render_markers_batch.argtypes = [vp, vp, i, i, i, i, sz, sz, i, vp, i, vp, i, vp, vp, i, vp, vp, vp, i]
+    L.arucohip_render_boards_batch.argtypes = [vp, vp, i, i, i, i, sz, sz, i, vp, i, vp, vp, i, vp, vp, vp, i]
+    L.arucohip_render_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.arucohip_frame_min_row_stride.argtypes = [vp, i]
     L.arucohip_frame_min_row_stride.restype = sz
     L.arucohip_frame_min_stride.argtypes = [vp, i, i, sz]
@@ -1315,6 +1389,64 @@ class Handle:
         status, maps = self.board_composite_device(ptr, n, wid, hgt, ch, boards, K, win, t, dist, _ptr(ma), rs, fs, frames_on_device=0,
                                                    masks_on_device=0, report=True)
         return out, status, maps
+
+    # ---- mesh rendering: shaded triangle meshes at marker and board poses, in place
+    def render_markers_device(self, frames_ptr, nframes, width, height, channels, markers_ptr, cap, counts_ptr, K, msh, style=None, dist=None,
+                              masks_ptr=None, row_stride=None, frame_stride=None, frames_on_device=1, markers_on_device=1, masks_on_device=1):
+        """arucohip_render_markers_batch on plain addresses. msh: a Mesh (mesh()), style: a Render (render_style()) or None for the
+        defaults. Strides default to tightly packed. With everything on the device the call is asynchronous on the handle's stream."""
+        rs = width * channels if row_stride is None else row_stride
+        Ka, da = _f32(K), _f32(dist)
+        self._chk(self.L.arucohip_render_markers_batch(self.h, frames_ptr, int(nframes), int(width), int(height), int(channels), rs,
+                                                       rs * height if frame_stride is None else frame_stride, int(frames_on_device), markers_ptr,
+                                                       int(cap), counts_ptr, int(markers_on_device), _ptr(Ka), _ptr(da),
+                                                       0 if da is None else da.size, C.byref(msh) if msh is not None else None,
+                                                       C.byref(style) if style is not None else None, masks_ptr, int(masks_on_device)))
+
+    def render_markers(self, frames, markers, counts, K, msh, style=None, dist=None, masks=None, width=None, channels=1):
+        """arucohip_render_markers_batch, in place. frames, markers and counts as draw_markers takes them (numpy, or torch tensors on the
+        device); masks: uint8 [N][H][W] of the same kind as the frames, or None."""
+        ptr, n, wid, hgt, ch, rs, fs, dev = self._frames(frames, width, channels)
+        if isinstance(markers, np.ndarray):
+            assert markers.dtype == MARKER_DTYPE and counts.dtype == np.int32
+            total = markers.size
+        else:
+            total = markers.numel() * markers.element_size() // MARKER_DTYPE.itemsize
+        assert total % n == 0 and total >= n and len(counts) == n
+        (mptr, mdev), (cptr, cdev) = self._buf(markers), self._buf(counts)
+        assert mdev == cdev
+        kptr, kdev = (None, 1) if masks is None else self._buf(masks)
+        self.render_markers_device(ptr, n, wid, hgt, ch, mptr, total // n, cptr, K, msh, style, dist, kptr, rs, fs, dev, mdev, kdev)
+        return frames
+
+    def render_boards_device(self, frames_ptr, nframes, width, height, channels, boards, K, msh, style=None, dist=None, masks_ptr=None,
+                             row_stride=None, frame_stride=None, frames_on_device=1, masks_on_device=1):
+        """arucohip_render_boards_batch on plain addresses. boards: N BOARD_DTYPE entries (numpy) or a device tensor of N * 56 bytes."""
+        if isinstance(boards, np.ndarray):
+            assert boards.dtype == BOARD_DTYPE and boards.size == nframes
+        bptr, bdev = self._buf(boards)
+        rs = width * channels if row_stride is None else row_stride
+        Ka, da = _f32(K), _f32(dist)
+        self._chk(self.L.arucohip_render_boards_batch(self.h, frames_ptr, int(nframes), int(width), int(height), int(channels), rs,
+                                                      rs * height if frame_stride is None else frame_stride, int(frames_on_device), bptr, bdev,
+                                                      _ptr(Ka), _ptr(da), 0 if da is None else da.size, C.byref(msh) if msh is not None else None,
+                                                      C.byref(style) if style is not None else None, masks_ptr, int(masks_on_device)))
+
+    def render_boards(self, frames, boards, K, msh, style=None, dist=None, masks=None, width=None, channels=1):
+        """arucohip_render_boards_batch, in place. boards: N BOARD_DTYPE entries, the list of dicts board_detect_batch returns, or a
+        device tensor of N * 56 bytes."""
+        ptr, n, wid, hgt, ch, rs, fs, dev = self._frames(frames, width, channels)
+        if isinstance(boards, (list, tuple)):
+            boards = self._board_records(boards)
+        kptr, kdev = (None, 1) if masks is None else self._buf(masks)
+        self.render_boards_device(ptr, n, wid, hgt, ch, boards, K, msh, style, dist, kptr, rs, fs, dev, kdev)
+        return frames
+
+    def render_times(self):
+        """(calls, build ms, raster ms): the render calls since enable_timing(True) and their kernels' average times per call."""
+        b, r = C.c_float(0), C.c_float(0)
+        n = self.L.arucohip_render_times(self.h, C.byref(b), C.byref(r))
+        return n, b.value, r.value
 
     def board_detect(self, markers, ids, obj, info_type, K=None, dist=None, marker_size=-1.0, repj_err_thres=-1.0, y_perp=False):
         m = np.ascontiguousarray(markers, dtype=MARKER_DTYPE)

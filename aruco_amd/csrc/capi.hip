@@ -429,6 +429,7 @@ int arucohip_enable_timing(arucohip_handle* h, int on) {
     // batches exactly as in an uninstrumented run: bench.py's replica pass)
     for_each_worker(h, [&](arucohip_handle* w) {
         w->timing = on == 1, w->tsets = 0;
+        w->render_ms[0] = w->render_ms[1] = 0, w->render_calls = 0;
         arm_stamps(w, on != 0);
         return ARUCOHIP_OK;
     });

@@ -207,7 +207,7 @@ struct arucohip_handle {
     //   capture and replay; batches that decode from cell medians neither touch nor move buf.patches, and buf.cells is create-time memory;
     // - neither: the other Buffers arrays, zero_block and h_markers are create-time memory (`held`); d_erode, d_canny and the user decoder's
     //   staging and d_pyr belong to configurations that are not graphed; wt_out is set only inside chunk_enqueue, which does not run this path.
-    //   Memory no captured launch reads (d_bgr, undistortion, fisheye maps and scratch, calibration, marker mapping, camera rigs and the pinned solver state, board and GL batches, planar poses, marker recovery, overlays, plane rectification and compositing, EM, HRM, fiducial generation, ChArUco corners and ChromaticMask scratch) may
+    //   Memory no captured launch reads (d_bgr, undistortion, fisheye maps and scratch, calibration, marker mapping, camera rigs and the pinned solver state, board and GL batches, planar poses, marker recovery, overlays, mesh rendering, plane rectification and compositing, EM, HRM, fiducial generation, ChArUco corners and ChromaticMask scratch) may
     //   be replaced at any time.
     struct FrameGraph {
         hipGraphExec_t exec = nullptr;
@@ -240,6 +240,12 @@ struct arucohip_handle {
     // arucohip_export_batch (capi_egress.hip): the host frames of one call, and the exported frames a host caller gets
     Mem<uint8_t> d_egress_src;
     Mem<uint8_t> d_egress;
+    // arucohip_render_*_batch (capi_render.hip): instances, transformed vertices and triangle records of one chunk of frames with the staged
+    // host markers / boards and mesh behind them; the staged host frames and masks of one call
+    Mem<uint8_t> d_render;
+    Mem<uint8_t> d_render_frames;
+    double render_ms[2] = {};            // with timing: build and raster kernel time summed over render_calls calls (arucohip_render_times)
+    int render_calls = 0;
 };
 
 #define HIPCHK(h, expr)                                                                         \

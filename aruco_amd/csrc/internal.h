@@ -391,6 +391,32 @@ void launch_overlay_build_boards(hipStream_t s, const arucohip_board_t* boards, 
 void launch_overlay_raster(hipStream_t s, uint8_t* frames, int nframes, int width, int height, int channels, size_t row_stride, size_t frame_stride,
                            const void* recs, const void* prims, int cap);
 
+// Mesh rendering (k_render.hip): shaded triangle meshes at marker and board poses, the rule arucohip.h states at
+// arucohip_render_markers_batch. Scratch of one chunk of frames, per instance slot (`slots` per frame: cap for markers, 1 for boards):
+// one 80-byte instance record (pose, product of the scales, box), nverts 40-byte transformed vertices, ntris 64-byte triangle records.
+constexpr size_t RD_INST_BYTES = 80, RD_VERT_BYTES = 40, RD_TRI_BYTES = 64;
+struct RdMesh {
+    const float* vertices;
+    const int32_t* triangles;
+    const uint8_t* colors;   // may be null: RdStyle::color
+    int nverts, ntris;
+};
+struct RdStyle {
+    int flags, opacity, ambient;
+    uint32_t color;      // B | G << 8 | R << 16
+    double light[3];     // unit, towards the light, camera frame
+    double scale;
+};
+void launch_render_instances_markers(hipStream_t s, const arucohip_marker_t* markers, const int32_t* counts, int nframes, int cap, double scale,
+                                     void* insts);
+void launch_render_instances_boards(hipStream_t s, const arucohip_board_t* boards, int nframes, double scale, void* insts);
+// insts [ninst] -> verts [ninst][nverts], tris [ninst][ntris] and the instances' boxes
+void launch_render_build(hipStream_t s, void* insts, int ninst, const CamModel& cam, const RdMesh& mesh, const RdStyle& style, void* verts, void* tris);
+// masks: null, or nframes images of `width` bytes a row, mask_row / mask_frame bytes apart
+void launch_render_raster(hipStream_t s, uint8_t* frames, int nframes, int width, int height, int channels, size_t row_stride, size_t frame_stride,
+                          const uint8_t* masks, size_t mask_row, size_t mask_frame, const void* insts, const void* tris, int slots, int ntris,
+                          const RdStyle& style);
+
 // Camera calibration (k_calib.hip). Views: points obj (xyz) / img (xy) at off[v], npt[v] points each.
 constexpr int CALIB_MAX_POINTS = 512;   // points of one view (= the board kernels' MAX_BOARD_POINTS)
 constexpr int CALIB_RED = 100;          // doubles per view of the reduced system: S_i (81), diag A_i (9), rhs_i (9), pad

@@ -866,6 +866,123 @@ private:
         return 0;
     }
 };
+
+// A triangle mesh in the object frame of a pose: what the reference's aruco_test_gl applications hand to OpenGL as glut solids.
+// triangles are vertex indices, counter-clockwise seen from outside (right-handed); colors is empty (one colour for all) or holds
+// B G R per triangle.
+struct Mesh {
+    std::vector<float> vertices;          // 3 per vertex
+    std::vector<int32_t> triangles;       // 3 per triangle
+    std::vector<unsigned char> colors;    // empty, or 3 per triangle
+    size_t nverts() const { return vertices.size() / 3; }
+    size_t ntris() const { return triangles.size() / 3; }
+    // the unit cube standing on the pose's plane: [-0.5, 0.5]^2 x [0, 1], 8 vertices, 12 triangles
+    static Mesh cube() {
+        Mesh m;
+        for (int i = 0; i < 8; i++) {
+            m.vertices.push_back((i & 1) ? 0.5f : -0.5f), m.vertices.push_back((i & 2) ? 0.5f : -0.5f), m.vertices.push_back((i & 4) ? 1.f : 0.f);
+        }
+        static const int q[6][4] = {{0, 2, 3, 1}, {4, 5, 7, 6}, {0, 1, 5, 4}, {2, 6, 7, 3}, {0, 4, 6, 2}, {1, 3, 7, 5}};
+        for (int f = 0; f < 6; f++) m.quad_(q[f][0], q[f][1], q[f][2], q[f][3]);
+        return m;
+    }
+    // a latitude / longitude sphere of the given radius about `center`: 2 + (stacks - 1) * slices vertices, 2 * slices * (stacks - 1) triangles
+    static Mesh uvSphere(int stacks, int slices, float radius = 0.5f, float cx = 0.f, float cy = 0.f, float cz = 0.5f) {
+        if (stacks < 2 || slices < 3) arucohip_throw_(ARUCOHIP_E_INVALID, "Mesh::uvSphere: at least 2 stacks and 3 slices", nullptr);
+        const double pi = 3.14159265358979323846;
+        Mesh m;
+        auto add = [&](double x, double y, double z) {
+            m.vertices.push_back((float)(x * radius + cx)), m.vertices.push_back((float)(y * radius + cy)), m.vertices.push_back((float)(z * radius + cz));
+        };
+        add(0, 0, 1);
+        for (int i = 1; i < stacks; i++)
+            for (int j = 0; j < slices; j++) {
+                const double th = pi * i / stacks, ph = 2 * pi * j / slices;
+                add(std::sin(th) * std::cos(ph), std::sin(th) * std::sin(ph), std::cos(th));
+            }
+        add(0, 0, -1);
+        auto ring = [&](int i, int j) { return 1 + (i - 1) * slices + j % slices; };
+        const int south = (int)m.nverts() - 1;
+        for (int j = 0; j < slices; j++) {
+            m.tri_(0, ring(1, j), ring(1, j + 1));
+            for (int i = 1; i < stacks - 1; i++) m.quad_(ring(i, j), ring(i + 1, j), ring(i + 1, j + 1), ring(i, j + 1));
+            m.tri_(south, ring(stacks - 1, j + 1), ring(stacks - 1, j));
+        }
+        return m;
+    }
+    arucohip_mesh_t abi() const {
+        arucohip_mesh_t a;
+        std::memset(&a, 0, sizeof(a));
+        a.vertices = vertices.data(), a.triangles = triangles.data(), a.colors = colors.empty() ? nullptr : colors.data();
+        a.nverts = (int32_t)nverts(), a.ntris = (int32_t)ntris();
+        return a;
+    }
+
+private:
+    void tri_(int a, int b, int c) { triangles.push_back(a), triangles.push_back(b), triangles.push_back(c); }
+    void quad_(int a, int b, int c, int d) { tri_(a, b, c), tri_(a, c, d); }
+};
+
+// Solid objects at marker and board poses (arucohip_render_markers_batch / arucohip_render_boards_batch on the process-wide handle):
+// the frame goes up, the mesh is drawn flat-shaded with a depth test and the frame comes back. What aruco_test_gl, aruco_test_board_gl
+// and aruco_test_board_gl_mask do through OpenGL; the pixel rule is the library's own (arucohip.h). 8-bit frames with 1 or 3 (B G R)
+// channels. A caller that keeps its frames on the device calls the C ABI directly, a whole batch at a time, and copies nothing.
+class MeshRenderer {
+public:
+    MeshRenderer() { arucohip_default_render(&style_); }
+    arucohip_render_t& style() { return style_; }
+    const arucohip_render_t& style() const { return style_; }
+    // the mesh on every marker that carries a pose, in units of the marker's side; nothing where mask (CV_8UC1, the frame's size; empty: none) is 0
+    void draw(cv::Mat& image, const std::vector<Marker>& markers, const CameraParameters& CP, const Mesh& mesh, const cv::Mat& mask = cv::Mat()) const {
+        if (markers.empty()) return;
+        std::vector<arucohip_marker_t> m(markers.size());
+        for (size_t i = 0; i < markers.size(); i++) markers[i].to_abi(&m[i]);
+        const int32_t n = (int32_t)m.size();
+        Call_ c(image, CP, mesh, mask);
+        SharedHandle_& sh = SharedHandle_::get();
+        std::lock_guard<std::mutex> lock(sh.mu);
+        arucohip_handle* h = sh.ensure(image.cols, image.rows);
+        arucohip_throw_(arucohip_render_markers_batch(h, image.data, 1, image.cols, image.rows, c.cn, (size_t)image.step, (size_t)image.step * image.rows, 0,
+                                                      m.data(), n, &n, 0, c.hasK ? c.K : nullptr, c.nd ? c.d : nullptr, c.nd, &c.mesh, &style_, c.mask(), 0),
+                        "MeshRenderer::draw", h);
+    }
+    // the mesh at the board's pose, in the units the pose was solved in (style().scale sizes it); nothing at all when B carries no pose
+    void draw(cv::Mat& image, const Board& B, const CameraParameters& CP, const Mesh& mesh, const cv::Mat& mask = cv::Mat()) const {
+        const arucohip_board_t b = board_record_(B);
+        Call_ c(image, CP, mesh, mask);
+        SharedHandle_& sh = SharedHandle_::get();
+        std::lock_guard<std::mutex> lock(sh.mu);
+        arucohip_handle* h = sh.ensure(image.cols, image.rows);
+        arucohip_throw_(arucohip_render_boards_batch(h, image.data, 1, image.cols, image.rows, c.cn, (size_t)image.step, (size_t)image.step * image.rows, 0, &b, 0,
+                                                     c.hasK ? c.K : nullptr, c.nd ? c.d : nullptr, c.nd, &c.mesh, &style_, c.mask(), 0),
+                        "MeshRenderer::draw (board)", h);
+    }
+
+private:
+    arucohip_render_t style_;
+    // the arguments both forms share
+    struct Call_ {
+        int cn, nd;
+        bool hasK;
+        float K[9], d[8];
+        arucohip_mesh_t mesh;
+        std::vector<unsigned char> packed;   // the C call takes masks tightly packed
+        bool masked;
+        Call_(const cv::Mat& image, const CameraParameters& CP, const Mesh& m, const cv::Mat& msk) : mesh(m.abi()), masked(!msk.empty()) {
+            if (image.type() != CV_8UC1 && image.type() != CV_8UC3) arucohip_throw_(ARUCOHIP_E_INVALID, "rendering: CV_8UC1 or CV_8UC3 frames", nullptr);
+            if (masked && (msk.type() != CV_8UC1 || msk.rows != image.rows || msk.cols != image.cols))
+                arucohip_throw_(ARUCOHIP_E_INVALID, "rendering: the mask is CV_8UC1 of the frame's size", nullptr);
+            if (m.vertices.size() % 3 || m.triangles.size() % 3 || (!m.colors.empty() && m.colors.size() != m.triangles.size()))
+                arucohip_throw_(ARUCOHIP_E_INVALID, "rendering: a mesh has 3 floats per vertex, 3 indices and no or 3 colour bytes per triangle", nullptr);
+            cn = image.type() == CV_8UC3 ? 3 : 1;
+            hasK = mat_to_K_(CP.CameraMatrix, K);
+            nd = mat_to_dist_(CP.Distorsion, d);
+            for (int y = 0; y < msk.rows; y++)
+                packed.insert(packed.end(), msk.data + (size_t)y * (size_t)msk.step, msk.data + (size_t)y * (size_t)msk.step + msk.cols);
+        }
+        const unsigned char* mask() const { return masked ? packed.data() : nullptr; }
+    };
+};
 #if ARUCOHIP_HAVE_OPENCV && defined(ARUCOHIP_SHIM_DEFINE_DRAWING)
 // The reference's drawing names, defined through the device overlay. Off by default: an integration that keeps the reference's own
 // src/marker.cpp / src/cvdrawingutils.{h,cpp} (or any other definition of these names) must not define the macro.

@@ -1156,6 +1156,97 @@ int arucohip_board_composite_batch(arucohip_handle* h, uint8_t* frames, int nfra
                                    const arucohip_texture_t* tex, const uint8_t* masks, int masks_on_device, int32_t* status,
                                    double* maps_out);
 
+/* ---- Mesh rendering: a solid, flat-shaded triangle mesh at the pose of every marker, or of every frame's board, painted into the frames
+ * in place with a depth test and hidden where a mask says so (k_render.hip, DESIGN.md "Mesh rendering"). What the reference's
+ * aruco_test_gl, aruco_test_board_gl and aruco_test_board_gl_mask hand to OpenGL; a device without a graphics pipeline draws it itself.
+ * The rule below is this library's own definition and does not claim to match any GL implementation. */
+typedef struct arucohip_mesh {
+    const float* vertices;     /* nverts * 3, the pose's object frame */
+    const int32_t* triangles;  /* ntris * 3 vertex indices; counter-clockwise seen from outside (right-handed) */
+    const uint8_t* colors;     /* ntris * 3, B G R per triangle; NULL: style->color for all */
+    int32_t nverts, ntris;     /* 1..65536, 1..16384 */
+    int32_t on_device;         /* covers the three arrays */
+    int32_t pad_;
+} arucohip_mesh_t;
+
+enum {
+    ARUCOHIP_RENDER_CULL_BACK = 1,   /* triangles that face away from the camera are dropped */
+    ARUCOHIP_RENDER_UNLIT = 2,       /* q = 255: the base colours as they are */
+    ARUCOHIP_RENDER_EDGES_INT64 = 4  /* evaluate the edge functions in int64 instead of double: the same bytes, for measurement */
+};
+typedef struct arucohip_render {
+    int32_t flags;       /* ARUCOHIP_RENDER_* */
+    int32_t opacity;     /* 0..255 */
+    int32_t ambient;     /* 0..255 */
+    float scale;         /* > 0, finite */
+    float light[3];      /* direction towards the light, camera frame; default (0, 0, -1): a headlight */
+    uint8_t color[4];    /* B G R when mesh->colors is NULL; [3] is ignored */
+} arucohip_render_t;
+/* CULL_BACK, opacity 255, ambient 64, scale 1, light (0, 0, -1), colour (0, 200, 0) */
+void arucohip_default_render(arucohip_render_t* r);
+
+/* Instances. Markers: every marker i < min(counts[f], cap) of frame f with has_pose is one instance at (rvec, tvec) with the object
+ * point s * v for mesh vertex v, s = (double) style->scale * (double) ssize: the mesh is a shape in units of the marker's side. Boards:
+ * frame f has one instance when boards[f].has_pose, with s = (double) style->scale, in the units the pose was solved in. All instances of
+ * a frame share one depth test.
+ * The rule for a pixel, in double unless it says integer, in this order, no operation fused:
+ *   1. Vertex. R = Rodrigues(rvec) and the projection are those of the pose solvers and the overlay (cv::projectPoints): with
+ *      (X, Y, Z) = (s vx, s vy, s vz) as doubles, x = ((R0 X + R1 Y) + R2 Z) + t0, y and z likewise from rows 1 and 2; the pixel
+ *      (px, py) = K * Brown(x / z, y / z) with k = dist[0..7], absent coefficients 0. A triangle is dropped whole if any of its vertices
+ *      has a depth z that is not > 0 (NaN included: there is no near-plane clipping), or a px or py that is not finite or lies beyond
+ *      +-2^20. Edges between distorted vertices stay straight: under lens distortion that is an approximation, good for meshes whose
+ *      triangles are small against the lens's curvature.
+ *   2. Snap. X = the nearest integer, ties to even, of px * 16; Y from py. Integer pixel indices are pixel centres: pixel (u, v) is the
+ *      point P = (16 u, 16 v). Everything up to step 5 is integer.
+ *   3. Area and facing. E_ij(P) = (Xj - Xi)(Py - Yi) - (Yj - Yi)(Px - Xi) and A = E_ab(c) for the triangle's vertices a, b, c in index
+ *      order. A == 0: dropped. A < 0 is front-facing: sign(A) = sign(det[a b c]) is the sign of the outward normal dotted with the
+ *      view ray. With CULL_BACK triangles with A > 0 are dropped. If A < 0, b and c are swapped and A negated, so that the interior has
+ *      all of E_bc, E_ca, E_ab > 0.
+ *   4. Coverage. The pixel is covered iff each of E_bc(P), E_ca(P), E_ab(P) is > 0, or is == 0 on an edge that owns its points: an edge
+ *      i -> j of the reordered triangle owns its points when Yj - Yi < 0 (a left edge), or Yj - Yi == 0 and Xj - Xi > 0 (a top edge).
+ *      Two triangles that share an edge therefore paint every pixel of their union once. All values stay below 2^53: int64 and double
+ *      evaluate them exactly.
+ *   5. Depth. iz = ((E_bc / A) (1 / z_a) + (E_ca / A) (1 / z_b)) + (E_ab / A) (1 / z_c), true divisions, each E with the depth of its
+ *      opposite vertex as they stand after the swap. Over the frame's instances in slot order, and each instance's triangles in index
+ *      order, the first triangle that covers the pixel takes it and a later one replaces it only if its iz is strictly greater.
+ *   6. Colour, per triangle, with a, b, c the camera-frame vertices (x, y, z) in the mesh's index order: n = (b - a) x (c - a),
+ *      len = sqrt((nx nx + ny ny) + nz nz), d = (nx lx + ny ly) + nz lz with l = light / sqrt((lx lx + ly ly) + lz lz) computed in
+ *      double from the floats; d is negated when A > 0 (the normal is turned towards the camera); lam = d / len, or 0 unless that is
+ *      > 0. q = the nearest integer, ties to even, of ambient + (255 - ambient) * lam, clamped to 0..255; with UNLIT q = 255.
+ *      C_c = (base_c * q + 127) / 255 in integers, base = the triangle's colour. On a one-channel frame
+ *      C = (1868 C_b + 9617 C_g + 4899 C_r + 8192) >> 14, the grey of arucohip_bgr_to_gray.
+ *   7. Blend. masks (may be NULL) with masks[(f * height + v) * width + u] == 0: the pixel is untouched; the layout is that of
+ *      arucohip_composite_plane_batch, which arucohip_chromatic_classify_batch writes. Otherwise
+ *      out_c = (C_c * opacity + frame_c * (255 - opacity) + 127) / 255 in integers: opacity 255 gives C_c exactly, opacity 0 leaves
+ *      the frame untouched.
+ * A pixel that no triangle covers keeps its value; bytes between width * channels and row_stride are never written, and a 64 x 16 tile
+ * that nothing covers is neither read nor written. The result is the same on every run.
+ * frames, markers, cap and counts as arucohip_draw_markers_batch takes them (markers_on_device covers markers and counts); K (9 floats,
+ * required) and dist (ndist = 0, 4, 5 or 8 floats) are host arrays; style NULL: arucohip_default_render's. With frames, markers, mesh and
+ * masks all on the device the call is asynchronous on the handle's stream, behind whatever is queued there (detect -> board pose ->
+ * classify -> render -> export needs no host round trip); otherwise it returns when the frames are done. A device mesh cannot be
+ * checked on the host: a triangle with an index outside 0..nverts-1 is dropped, and nothing outside the vertex array is read. Uses
+ * scratch of its own, 64 MiB for a chunk of frames at a time: the single-frame graph and the last batch stay valid.
+ * ARUCOHIP_E_INVALID, with a message that names it and before anything runs: a null h, frames, markers, counts, mesh, mesh->vertices or
+ * mesh->triangles; K missing; channels not 1 or 3; opacity or ambient outside 0..255; a scale that is not positive and finite; a light
+ * that is zero or not finite; nframes, width, height or cap below 1; nverts outside 1..65536 or ntris outside 1..16384; ndist not 0, 4,
+ * 5 or 8, or dist NULL with ndist > 0; a stride smaller than a row or a frame; mesh arrays or masks overlapping the frames; a host mesh
+ * with an index outside 0..nverts-1. ARUCOHIP_E_UNSUPPORTED: frames wider or taller than the handle, cap above 65535, or
+ * cap * (80 + 40 nverts + 64 ntris) bytes, the scratch of one frame, above 1 GiB. */
+int arucohip_render_markers_batch(arucohip_handle* h, uint8_t* frames, int nframes, int width, int height, int channels, size_t row_stride,
+                                  size_t frame_stride, int frames_on_device, const arucohip_marker_t* markers, int cap,
+                                  const int32_t* counts, int markers_on_device, const float* K, const float* dist, int ndist,
+                                  const arucohip_mesh_t* mesh, const arucohip_render_t* style, const uint8_t* masks, int masks_on_device);
+/* One instance per frame at boards[f] (rvec / tvec as the board calls return them; nothing is drawn without has_pose). The rest is
+ * arucohip_render_markers_batch. */
+int arucohip_render_boards_batch(arucohip_handle* h, uint8_t* frames, int nframes, int width, int height, int channels, size_t row_stride,
+                                 size_t frame_stride, int frames_on_device, const arucohip_board_t* boards, int boards_on_device,
+                                 const float* K, const float* dist, int ndist, const arucohip_mesh_t* mesh, const arucohip_render_t* style,
+                                 const uint8_t* masks, int masks_on_device);
+/* After arucohip_enable_timing(h, 1) every render call brackets its build kernels (instances, vertices, triangles) and its raster
+ * kernel with events and waits for them. *build_ms / *raster_ms (may be NULL): their averages per call since then; returns the calls. */
+int arucohip_render_times(arucohip_handle* h, float* build_ms, float* raster_ms);
+
 /* Execution time of the dominant streaming kernel (the 16-pixel-per-lane adaptive threshold kernel) from the device's constant-rate
  * clock: every wave leaves its first and last reading, *total_ms = sum over the launches since arucohip_enable_timing(h, 1) of
  * (last wave's end - first wave's start), *launches = their number (0 when another threshold kernel ran: use the event times).
