@@ -284,7 +284,7 @@ SYMBOLS = [
     "arucohip_mgpu_set_params", "arucohip_mgpu_last_error_string", "arucohip_mgpu_detect_batch", "arucohip_mgpu_detect_streams",
     "arucohip_mgpu_set_depth", "arucohip_mgpu_submit_batch", "arucohip_mgpu_submit_streams", "arucohip_mgpu_wait",
     "arucohip_compact_bytes", "arucohip_compact_markers", "arucohip_wait_event", "arucohip_detect_batch_retry_overflowed",
-    "arucohip_refine_candidate_lines", "arucohip_debug_refine_pixels", "arucohip_debug_decode_quads", "arucohip_mgpu_gather_mode", "arucohip_build_info",
+    "arucohip_refine_candidate_lines", "arucohip_debug_refine_pixels", "arucohip_debug_decode_quads", "arucohip_debug_marker_tail", "arucohip_mgpu_gather_mode", "arucohip_build_info",
     "arucohip_calibrate_camera", "arucohip_calibrate_board_batch", "arucohip_debug_calib_start", "arucohip_board_map", "arucohip_board_map_batch",
     "arucohip_rig_calibrate", "arucohip_rig_calibrate_batch", "arucohip_rig_pose", "arucohip_rig_pose_batch",
     "arucohip_planar_poses", "arucohip_planar_poses_batch",
@@ -464,6 +464,7 @@ def load():
     L.arucohip_refine_candidate_lines.argtypes = [vp, vp, i, vp, vp, vp, i]
     L.arucohip_debug_refine_pixels.argtypes = [vp, vp, i, i, C.c_size_t, vp, i, i, i, i]
     L.arucohip_debug_decode_quads.argtypes = [vp, vp, i, i, i, C.c_size_t, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.arucohip_debug_marker_tail.argtypes = [vp, i, i, i, vp, vp, vp, i, vp, vp, vp, i, f, i, vp, i, vp, vp, vp, vp, vp, vp, vp]
     L.arucohip_default_charuco.argtypes = [vp]
     L.arucohip_default_charuco.restype = None
     L.arucohip_charuco_board_size.argtypes = [vp, vp, vp, vp, vp]
@@ -637,8 +638,12 @@ class Handle:
         p = params if params is not None else default_params()
         if limits is None:
             rc = self.L.arucohip_create(C.byref(p), device, max_width, max_height, max_batch, C.byref(self.h))
+            lim = Limits()
+            self.L.arucohip_default_limits(C.byref(lim), max_width, max_height, max_batch)
+            self._markers_per_frame = lim.markers_per_frame
         else:
             rc = self.L.arucohip_create_ex(C.byref(p), device, C.byref(limits), C.byref(self.h))
+            self._markers_per_frame = limits.markers_per_frame
         if rc != OK:
             raise ArucoHipError(rc, "arucohip_create")
         self.max_batch = max_batch
@@ -947,6 +952,40 @@ class Handle:
         if not paths.value & 2:
             out["patches"] = None
         return out
+
+    def debug_marker_tail(self, nframes, width, height, ids, corners, frame_of=None, plane_status=None, K=None, dist=None, marker_size=-1.0,
+                          y_perp=False, out_dev=None, out_cap=0, n_out_dev=None):
+        """The marker-list tail (sort by id, same-id dedupe, border filter, capacities and statuses, poses with K and marker_size) on decoded
+        candidates: ids (n, -1 = not a marker), corners (n x 4 x 2 float32), frame_of (n, default 0). plane_status: [nframes][planes] status words
+        of the threshold planes. out_dev / n_out_dev: device pointers (integers) of [nframes][out_cap] markers and [nframes] counts for the
+        write-through path. Returns a dict: rows ([nframes][markers_per_frame] MARKER_DTYPE, 0xA5 bytes where nothing was written), n (true
+        counts, -1 = given up), status, nmark, list (the flat marker list's nmark entries), raw_list (all of it) and hdr (the two words behind
+        the rows). The frames stay the handle's last batch."""
+        ia = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        n = len(ia)
+        ca = np.ascontiguousarray(corners, dtype=np.float32).reshape(n, 8)
+        fo = np.zeros(n, np.int32) if frame_of is None else np.ascontiguousarray(frame_of, dtype=np.int32).reshape(-1)
+        assert len(fo) == n
+        ps = None if plane_status is None else np.ascontiguousarray(plane_status, dtype=np.uint32).reshape(nframes, -1)
+        assert ps is None or ps.shape[1] == 2 * self.get_params().thres_param1_range + 1
+        Ka, da = _f32(K), _f32(dist)
+        capm = self.markers_per_frame()
+        out = {"rows": np.zeros((nframes, capm), MARKER_DTYPE), "n": np.zeros(nframes, np.int32), "raw_list": np.zeros(nframes * capm, np.uint32),
+               "hdr": np.zeros(2, np.int32)}
+        status, nmark = C.c_uint32(0), C.c_uint32(0)
+        self._chk(self.L.arucohip_debug_marker_tail(self.h, int(nframes), int(width), int(height), _ptr(ia) if n else None, _ptr(ca) if n else None,
+                                                    _ptr(fo) if n else None, n, None if ps is None else _ptr(ps), _ptr(Ka), _ptr(da),
+                                                    0 if da is None else da.size, float(marker_size), int(bool(y_perp)),
+                                                    None if out_dev is None else C.c_void_p(out_dev), int(out_cap),
+                                                    None if n_out_dev is None else C.c_void_p(n_out_dev), _ptr(out["rows"]), _ptr(out["n"]),
+                                                    C.byref(status), C.byref(nmark), _ptr(out["raw_list"]), _ptr(out["hdr"])))
+        out["status"], out["nmark"] = status.value, nmark.value
+        out["list"] = out["raw_list"][:nmark.value].copy()
+        return out
+
+    def markers_per_frame(self):
+        """The handle's markers_per_frame limit (rows of a frame in the device marker array)."""
+        return int(self._markers_per_frame)
 
     def bgr_to_gray(self, bgr):
         b = np.ascontiguousarray(bgr, dtype=np.uint8)
@@ -1494,7 +1533,7 @@ class Handle:
         mv = np.zeros((nframes, cap, 16), np.float64)
         n = np.zeros(nframes, np.int32)
         self._chk(self.L.arucohip_gl_modelview_batch(self.h, nframes, cap, _ptr(mv), _ptr(n)))
-        return [mv[f, :n[f]].copy() for f in range(nframes)]
+        return [mv[f, :max(int(n[f]), 0)].copy() for f in range(nframes)]   # n = -1: a frame the batch gave up
 
     def board_detect_batch(self, nframes, ids, obj, info_type, K=None, dist=None, marker_size=-1.0, repj_err_thres=-1.0, y_perp=False):
         """BoardDetector::detect on the device-resident markers of the last detect_batch call, all frames at once."""

@@ -220,7 +220,7 @@ static int create_handle(const arucohip_params_t* params, int device, const aruc
     if (!out || !lim) return ARUCOHIP_E_INVALID;
     *out = nullptr;
     if (lim->max_width < 32 || lim->max_height < 32 || lim->max_width > 16383 || lim->max_height > 16383 || lim->max_batch < 1 ||
-        lim->max_thres_planes < 1 || lim->max_thres_planes > 16 || lim->candidates_per_frame > 512 || lim->markers_per_frame > 256 ||
+        lim->max_thres_planes < 1 || lim->max_thres_planes > 16 || lim->candidates_per_frame > MAX_CANDS_PER_FRAME || lim->markers_per_frame > 256 ||
         (long)lim->max_width * lim->max_height > (1L << 26) /* Quad::key holds a 26-bit raster index */)
         return ARUCOHIP_E_INVALID;
     arucohip_handle* h = new arucohip_handle();
@@ -1773,6 +1773,80 @@ int arucohip_debug_decode_quads(arucohip_handle* h, const uint8_t* gray, int nfr
         if (nrot) nrot[i] = c.nrot;
     }
     if (paths) *paths = cells ? 1 : 2;
+    return ARUCOHIP_OK;
+}
+
+// Test hook: the marker-list tail of a batch (finalize_kernel, then the list-driven pose_kernel under detect_core's condition) on caller-made decoded
+// candidates. They become the candidates of the frames they name, in the order given; make_detect_params builds the parameters, so the border
+// rectangle is the pipeline's; the counters are cleared as a batch clears them, plane_status goes into the planes' TC_STATUS words, and the marker
+// rows with the header slot are filled with 0xA5 first, so that what the kernels leave alone can be told. Unlike the other hooks it leaves h->last
+// describing these frames (one span on this handle): the batch consumers then run on the crafted lists.
+int arucohip_debug_marker_tail(arucohip_handle* h, int nframes, int W, int H, const int32_t* ids, const float* corners, const int32_t* frame_of, int n,
+                               const uint32_t* plane_status, const float* K, const float* dist, int ndist, float marker_size, int y_perp,
+                               arucohip_marker_t* out_dev, int out_cap, int32_t* n_out_dev, arucohip_marker_t* rows, int32_t* nmarkers, uint32_t* status,
+                               uint32_t* nmark, uint32_t* marker_list, int32_t* hdr) {
+    if (!h || n < 0 || (n > 0 && (!ids || !corners || !frame_of))) return ARUCOHIP_E_INVALID;
+    int rc = check_geometry(h, nframes, W, H, (size_t)W);
+    if (rc) return rc;
+    if (nframes > h->cap_frames) return fail(h, ARUCOHIP_E_INVALID, "marker_tail: more frames than one worker of the handle holds");
+    if ((out_dev || n_out_dev) && (!out_dev || !n_out_dev || out_cap < 1))
+        return fail(h, ARUCOHIP_E_INVALID, "marker_tail: the write-through arrays come together, with out_cap >= 1");
+    const Buffers& b = h->buf;
+    std::vector<int32_t> per_frame((size_t)nframes, 0);
+    std::vector<Cand> v((size_t)nframes * b.cap_cands);
+    for (int i = 0; i < n; i++) {
+        const int32_t f = frame_of[i];
+        if (f < 0 || f >= nframes) return fail(h, ARUCOHIP_E_INVALID, "marker_tail: frame index outside the call's frames");
+        if (per_frame[f] >= b.cap_cands) return fail(h, ARUCOHIP_E_CAPACITY, "marker_tail: more candidates in a frame than candidates_per_frame");
+        Cand c{};
+        for (int k = 0; k < 8; k++) {
+            const float x = corners[8 * (size_t)i + k];
+            if (!(std::fabs(x) <= 65534.f)) return fail(h, ARUCOHIP_E_INVALID, "corner not finite or outside +-65534");   // NaN fails the comparison
+            c.c[k] = x;
+        }
+        for (int k = 0; k < 4; k++) c.qx[k] = (int16_t)std::min<long>(std::max<long>(lrintf(c.c[2 * k]), -32768), 32767),
+                                    c.qy[k] = (int16_t)std::min<long>(std::max<long>(lrintf(c.c[2 * k + 1]), -32768), 32767);
+        c.cdesc = 0, c.swapped = 0, c.id = ids[i], c.nrot = 0;
+        v[(size_t)f * b.cap_cands + per_frame[f]++] = c;
+    }
+    DetectParams dp;
+    if ((rc = make_detect_params(h, W, H, &dp))) return rc;
+    CamModel cam;
+    if ((rc = make_cam(h, K, dist, ndist, marker_size, y_perp, &cam))) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const size_t nrows = (size_t)nframes * b.cap_markers;
+    HIPCHK(h, hipMemsetAsync(h->zero_block, 0, h->zero_words * sizeof(uint32_t), s));
+    uint32_t st_all = 0;
+    if (plane_status) {   // one word per plane, each in the plane's own counter line; the batch's status word carries every bit as well (flag_overflow)
+        HIPCHK(h, hipMemcpy2DAsync(b.trig_cnt + TC_STATUS, TRIG_CNT_STRIDE * sizeof(uint32_t), plane_status, sizeof(uint32_t), sizeof(uint32_t),
+                                   (size_t)nframes * dp.nthr, hipMemcpyHostToDevice, s));
+        for (int i = 0; i < nframes * dp.nthr; i++) st_all |= plane_status[i];
+        HIPCHK(h, hipMemcpyAsync(b.counters + CNT_STATUS, &st_all, sizeof(st_all), hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(h, hipMemsetAsync(b.markers, 0xA5, (nrows + 1) * sizeof(arucohip_marker_t), s));
+    HIPCHK(h, hipMemsetAsync(b.marker_list, 0xA5, nrows * sizeof(uint32_t), s));
+    HIPCHK(h, hipMemcpyAsync(b.cands, v.data(), v.size() * sizeof(Cand), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(b.ncands, per_frame.data(), per_frame.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    FrameGeom g{};
+    g.width = W, g.height = H, g.row_stride = (size_t)W, g.frame_stride = (size_t)W * H;
+    launch_finalize(s, g, nframes, dp, cam, b, out_dev, out_cap, n_out_dev);
+    if (cam.has_K && cam.marker_size > 0) launch_pose(s, nframes, cam, b);
+    HIPCHK(h, hipGetLastError());
+    std::vector<uint32_t> cnt(CNT_FIXED);
+    if (rows) HIPCHK(h, hipMemcpyAsync(rows, b.markers, nrows * sizeof(arucohip_marker_t), hipMemcpyDeviceToHost, s));
+    if (nmarkers) HIPCHK(h, hipMemcpyAsync(nmarkers, b.nmarkers, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (marker_list) HIPCHK(h, hipMemcpyAsync(marker_list, b.marker_list, nrows * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (hdr) HIPCHK(h, hipMemcpyAsync(hdr, b.markers + nrows, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(cnt.data(), b.counters, CNT_FIXED * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (status) *status = cnt[CNT_STATUS];
+    if (nmark) *nmark = cnt[CNT_NMARK];
+    Batch last;
+    last.nspan = 1, last.frames = nframes, last.W = W, last.H = H, last.nthr = dp.nthr, last.frame_w = W, last.frame_h = H;
+    last.span[0] = {h, 0, nframes};
+    h->last = last;
+    h->cells_valid = false;
     return ARUCOHIP_OK;
 }
 

@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "border_rect.h"
 #include "fisheye_device.h"
 #include "frames_host.h"
 #include "internal.h"
@@ -269,13 +270,6 @@ inline int fail(arucohip_handle* h, int code, const char* msg) {
 int take_format(arucohip_handle* h, const arucohip_frame_format_t* fmt, FrameFmt* f);
 // a format against a geometry, with the limits of the detection calls (check_geometry of capi.hip): one message per refusal
 int check_frame_format(arucohip_handle* h, const FrameFmt& fmt, int nframes, int W, int H, size_t row_stride, size_t frame_stride);
-
-// the border filter's rectangle [r[0], r[2]) x [r[1], r[3]) of a W x H frame: markerdetector.cpp:433-434, Rect(Point(size) * t, Point(size) * (1 - t)) with cvRound
-inline void border_rect(float border_dist, int W, int H, int r[4]) {
-    const int x1 = (int)lrintf((float)W * border_dist), y1 = (int)lrintf((float)H * border_dist);
-    const int x2 = (int)lrintf((float)W * (1.0f - border_dist)), y2 = (int)lrintf((float)H * (1.0f - border_dist));
-    r[0] = std::min(x1, x2), r[1] = std::min(y1, y2), r[2] = std::max(x1, x2), r[3] = std::max(y1, y2);
-}
 
 // A call's scratch, laid out once: take() hands out consecutive 256-byte aligned arrays of `base`. A layout function names every
 // buffer in one take() and returns `at`, the bytes it needs; it runs twice, with a null base to size the memory (every take() is then

@@ -28,6 +28,7 @@ constexpr int TC_SNAP = 4;            // 4 = descriptors that existed when the l
 constexpr int TC_LATE = 6;            // 6 = descriptors of the plane's late list (from the top of its cdesc array downwards): the borders a pipeline
                                       //     lane's late walks keep while contour_quad's first pass runs (k_contours.hip: late_quad_kernel)
 constexpr int WALK_BLOCKS = 16;       // 64-lane walker workgroups per plane
+constexpr int MAX_CANDS_PER_FRAME = 512;   // the largest candidates_per_frame a handle is created with: per-frame LDS arrays of the tail are this long
 
 
 enum Counter {

@@ -10,7 +10,7 @@
 
 namespace ah {
 
-constexpr int MAXM = 512;   // = the largest candidates_per_frame arucohip_create_ex accepts
+constexpr int MAXM = MAX_CANDS_PER_FRAME;   // = the largest candidates_per_frame arucohip_create_ex accepts
 
 __device__ __forceinline__ float perimeter_f(const float* c) {
     float sum = 0;

@@ -547,6 +547,24 @@ int arucohip_debug_decode_quads(arucohip_handle* h, const uint8_t* gray, int nfr
                                 const int16_t* quads_xy, const int32_t* frame_of, int n, double* iM, uint16_t* hist, int32_t* thr, uint8_t* cells49,
                                 uint8_t* patches, int32_t* ids, int32_t* nrot, int32_t* paths);
 
+/* Test hook: the marker-list tail of a batch (sort by id, same-id dedupe by perimeter, border filter, capacities and statuses, then the per-marker
+ * poses when K is given and marker_size > 0) on decoded candidates of the caller's. nframes frames of width x height (no pixels are read; nframes at
+ * most the handle's max_batch); n >= 0 candidates: ids [n] (-1: not a marker), corners [n][8] (every coordinate finite and within +-65534),
+ * frame_of [n] the frame of each; they become their frames' candidates in the order given, at most candidates_per_frame in a frame
+ * (ARUCOHIP_E_CAPACITY beyond). plane_status (optional): [nframes][planes] status words stored as the threshold planes' own, planes =
+ * 2 * thres_param1_range + 1 of the handle's parameters; a frame with a non-zero word is given up (count -1), and the batch's status bits hold every word's bits, as when a kernel reports an overflow. The handle's border_dist gives the border
+ * rectangle as in a detection. out_dev [nframes][out_cap] / n_out_dev [nframes] (optional, both or neither): DEVICE arrays the list kernel writes
+ * through to, as it does for a batch whose results stay on the device. Outputs, each optional, on the host: rows [nframes][markers_per_frame] the raw
+ * marker rows, filled with the byte 0xA5 before the kernels ran; nmarkers [nframes] the true counts (-1: given up); *status the batch's status
+ * bits (32: a frame kept more than markers_per_frame markers); *nmark the length of the flat marker list and marker_list [nframes * markers_per_frame]
+ * its entries frame << 16 | slot (0xA5 bytes beyond *nmark); hdr [2] the two words behind the rows, which a one-frame call sets to the count and the
+ * status bits. Everything is checked before anything runs. Unlike the other hooks it leaves the frames as the handle's last batch: the batch
+ * consumers (arucohip_gl_modelview_batch, arucohip_board_detect_batch, arucohip_planar_poses_batch, ...) then work on these lists. */
+int arucohip_debug_marker_tail(arucohip_handle* h, int nframes, int width, int height, const int32_t* ids, const float* corners,
+                               const int32_t* frame_of, int n, const uint32_t* plane_status, const float* K, const float* dist, int ndist,
+                               float marker_size, int y_perp, arucohip_marker_t* out_dev, int out_cap, int32_t* n_out_dev, arucohip_marker_t* rows,
+                               int32_t* nmarkers, uint32_t* status, uint32_t* nmark, uint32_t* marker_list, int32_t* hdr);
+
 /* glibc's rand() outputs [offset, offset + count) after srand(seed), as the device makes them for arucohip_hrm_create_dictionary
  * (jump-ahead of the stream's state). count <= 2^24, offset + count < 2^48. */
 int arucohip_debug_hrm_stream(arucohip_handle* h, uint32_t seed, uint64_t offset, int count, uint32_t* out);
