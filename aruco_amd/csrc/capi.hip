@@ -1091,14 +1091,18 @@ int arucohip_undistort(arucohip_handle* h, const uint8_t* src, int nframes, int 
         std::memcpy(h->umap_K, K, sizeof(h->umap_K));
         if (ndist) std::memcpy(h->umap_d, dist, ndist * sizeof(float));
     }
-    // host frames borrow d_bgr; the packed result a host caller gets is staged in d_undist
+    // host frames and the packed result a host caller gets are staged in the arena
     const size_t row = (size_t)W * channels;
     const Images in = images(src, nframes, H, row, row_stride, frame_stride, src_on_device), out = images(dst, nframes, H, row, row, row * H, dst_on_device);
-    if (!src_on_device) HIPCHK(h, h->d_bgr.reserve(in.packed_bytes()));
-    if (!dst_on_device) HIPCHK(h, h->d_undist.reserve(out.packed_bytes()));
+    size_t src_at, dst_at;
+    if ((rc = carve_scratch(h, h, [&](Carver& cv) {
+             src_at = cv.take_at(src_on_device ? 0 : in.packed_bytes());
+             dst_at = cv.take_at(dst_on_device ? 0 : out.packed_bytes());
+         })))
+        return rc;
     DevImages sdev, ddev;
-    if ((rc = stage_input(h, s, in, h->d_bgr, 0, &sdev))) return rc;
-    if ((rc = stage_output(h, out, h->d_undist, 0, &ddev))) return rc;
+    if ((rc = stage_input(h, s, in, h->scratch, src_at, &sdev))) return rc;
+    if ((rc = stage_output(h, out, h->scratch, dst_at, &ddev))) return rc;
     launch_remap(s, sdev.p, sdev.row, sdev.frame, W, H, channels, nframes, h->d_umap_xy, h->d_umap_f, ddev.p);
     HIPCHK(h, hipGetLastError());
     if ((rc = unstage(h, s, out, ddev))) return rc;
@@ -1898,10 +1902,14 @@ int arucohip_gl_modelview_batch(arucohip_handle* h, int nframes, int cap, double
     arucohip_handle* w = r.span[0].w;
     HIPCHK(h, hipSetDevice(h->device));
     const size_t need = (size_t)nframes * cap * 16 * sizeof(double);
-    HIPCHK(h, w->d_gl.reserve(need));
-    launch_gl_modelview(w->stream, nframes, cap, w->buf, w->d_gl);
+    double* d_mv;
+    if (const int rc = carve_scratch(w, h, [&](Carver& cv) {
+            d_mv = cv.take<double>((size_t)nframes * cap * 16);
+        }))
+        return rc;
+    launch_gl_modelview(w->stream, nframes, cap, w->buf, d_mv);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(modelview, w->d_gl, need, hipMemcpyDeviceToHost, w->stream));
+    HIPCHK(h, hipMemcpyAsync(modelview, d_mv, need, hipMemcpyDeviceToHost, w->stream));
     HIPCHK(h, hipMemcpyAsync(n_out, w->buf.nmarkers, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, w->stream));
     HIPCHK(h, hipStreamSynchronize(w->stream));
     for (int f = 0; f < nframes; f++) n_out[f] = std::min(std::min(n_out[f], cap), w->buf.cap_markers);

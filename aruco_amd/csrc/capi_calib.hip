@@ -8,11 +8,10 @@
 
 #include "handle.h"
 
-// v's arrays in `base` for V views, npts staged points, nframes gather slots and a board of nboard markers; returns the bytes.
+// v's arrays from `c` for V views, npts staged points, nframes gather slots and a board of nboard markers.
 // One quirk: npt is laid out for max(V, nframes) counts. A batch's gather counts every frame into it; the solve then overwrites
 // off / npt with the (fewer) views that are used, and the per-view arrays, laid out for nframes, hold them with room to spare.
-static size_t calib_layout(CalibViews& v, uint8_t* base, int V, size_t npts, int nframes, int nboard) {
-    Carver c{base};
+static void calib_layout(CalibViews& v, Carver& c, int V, size_t npts, int nframes, int nboard) {
     CalibDev& d = v.d;
     d.st = c.take<CalibState>(1);
     d.off = v.off_dev = c.take<int32_t>((size_t)V), d.npt = v.npt_dev = c.take<int32_t>((size_t)std::max(V, nframes));
@@ -22,7 +21,6 @@ static size_t calib_layout(CalibViews& v, uint8_t* base, int V, size_t npts, int
     d.obj = v.obj = c.take<float>(npts * 3), d.img = v.img = c.take<float>(npts * 2);
     v.nmark = c.take<int32_t>((size_t)nframes);
     v.bids = c.take<int32_t>((size_t)nboard), v.bobj = c.take<float>((size_t)nboard * 12);
-    return c.at;
 }
 
 // the used views' offsets and counts, on h's stream
@@ -34,7 +32,7 @@ static int calib_counts_up(arucohip_handle* h, const CalibViews& v) {
 }
 
 // Levenberg-Marquardt (lm_drive) on views whose points are already on the device (v.d.obj / v.d.img, offsets off[], counts npt[]),
-// in h's d_calib where v is bound, from the state `st` (start intrinsics, free mask, flags, model).
+// in h's arena where v is bound, from the state `st` (start intrinsics, free mask, flags, model).
 // focal_start: the focal lengths come from the views' homographies (pinhole without a guess).
 int calib_solve(arucohip_handle* h, const CalibViews& v, CalibState st, bool focal_start, double intr[9], double* rvecs, double* tvecs,
                 double* per_view_rms, double* rms) {
@@ -68,7 +66,7 @@ int calib_solve(arucohip_handle* h, const CalibViews& v, CalibState st, bool foc
     return ARUCOHIP_OK;
 }
 
-// the caller's views (host or device arrays) as the solver takes them, in h->d_calib
+// the caller's views (host or device arrays) as the solver takes them, in h's arena
 int calib_views_of_points(arucohip_handle* h, const float* obj, const float* img, const int32_t* npoints, int nviews, int on_device, CalibViews* v) {
     HIPCHK(h, hipSetDevice(h->device));
     v->npt.resize((size_t)nviews), v->off.resize((size_t)nviews);
@@ -84,8 +82,7 @@ int calib_views_of_points(arucohip_handle* h, const float* obj, const float* img
     }
     if (total > (size_t)INT32_MAX) return fail(h, ARUCOHIP_E_CAPACITY, "too many calibration points");
     const size_t staged = on_device ? 0 : total;
-    HIPCHK(h, h->d_calib.reserve(calib_layout(*v, nullptr, nviews, staged, 0, 0)));
-    calib_layout(*v, h->d_calib, nviews, staged, 0, 0);
+    if (const int rc = carve_scratch(h, h, [&](Carver& c) { calib_layout(*v, c, nviews, staged, 0, 0); })) return rc;
     v->d.nviews = nviews;
     if (on_device) {
         v->d.obj = obj, v->d.img = img;
@@ -109,8 +106,7 @@ int calib_views_of_batch(arucohip_handle* h, int nframes, const BoardDef& board,
     *owner = o;
     const double mpp = board_mpp(board);   // board_pose_kernel's scale
     const size_t npts = (size_t)nframes * CALIB_MAX_POINTS;
-    HIPCHK(h, o->d_calib.reserve(calib_layout(*v, nullptr, nframes, npts, nframes, nboard)));
-    calib_layout(*v, o->d_calib, nframes, npts, nframes, nboard);
+    if (const int rc = carve_scratch(o, h, [&](Carver& c) { calib_layout(*v, c, nframes, npts, nframes, nboard); })) return rc;
     BoardDef bd;
     if (const int e = upload_board(h, board, o->stream, v->bids, v->bobj, &bd)) return e;
     // every worker lays out the correspondences of the frames it detected, on its own stream

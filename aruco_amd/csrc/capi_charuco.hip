@@ -9,8 +9,6 @@
 namespace {
 constexpr int CH_MAX_SIDE = 16383, CH_MAX_MARKERS = 1024, CH_IDS = 1024;
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct CharucoPlan {
     int W = 0, H = 0, markers = 0, corners = 0;
 };
@@ -94,19 +92,24 @@ int arucohip_charuco_board_image(arucohip_handle* h, const arucohip_charuco_t* l
             corner_obj[3 * c + 2] = 0.f;
         }
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t rs = ((size_t)p.W + 15) & ~(size_t)15, o_img = align256(slots.size() * sizeof(int32_t));
-    HIPCHK(h, h->d_fiducial.reserve(o_img + (image_on_device ? 0 : rs * p.H)));
-    uint8_t* b = h->d_fiducial;
+    const size_t rs = ((size_t)p.W + 15) & ~(size_t)15;
+    int32_t* d_slots;
+    uint8_t* d_img;
+    if (const int rc = carve_scratch(h, h, [&](Carver& cv) {
+            d_slots = cv.take<int32_t>(slots.size());
+            d_img = cv.take<uint8_t>(image_on_device ? 0 : rs * p.H);
+        }))
+        return rc;
     hipStream_t s = h->stream;
-    HIPCHK(h, hipMemcpyAsync(b, slots.data(), slots.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(d_slots, slots.data(), slots.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     const FidLayout FL{p.W, p.H, p.W, p.H, 0, L.squares_x, L.squares_y, L.marker_px, L.square_px, L.marker_px / 7, L.square_px, m};
     if (image_on_device) {
-        launch_fid_paint(s, FL, (const int32_t*)b, 1, image, row_stride, 0);
+        launch_fid_paint(s, FL, d_slots, 1, image, row_stride, 0);
         HIPCHK(h, hipGetLastError());
     } else {
-        launch_fid_paint(s, FL, (const int32_t*)b, 1, b + o_img, rs, 0);
+        launch_fid_paint(s, FL, d_slots, 1, d_img, rs, 0);
         HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpy2DAsync(image, row_stride, b + o_img, rs, p.W, p.H, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpy2DAsync(image, row_stride, d_img, rs, p.W, p.H, hipMemcpyDeviceToHost, s));
     }
     HIPCHK(h, hipStreamSynchronize(s));
     return ARUCOHIP_OK;
@@ -145,9 +148,13 @@ int arucohip_charuco_corners_batch(arucohip_handle* h, const arucohip_charuco_t*
     CharucoArgs a{};
     a.L = *layout, a.ids = d_ids, a.width = W, a.height = H, a.min_markers = o.min_markers, a.max_win = o.max_win;
     const Images in = images(frames, nframes, H, (size_t)W, row_stride, frame_stride, frames_on_device);
-    if (!frames_on_device) HIPCHK(h, h->d_charuco_frames.reserve(in.packed_bytes()));
+    size_t frames_at;   // host frames are staged in the first worker's arena, on its stream (after a waited ticket w0 is a lane, not h)
+    if (const int rc = carve_scratch(w0, h, [&](Carver& cv) {
+            frames_at = cv.take_at(frames_on_device ? 0 : in.packed_bytes());
+        }))
+        return rc;
     DevImages gray;
-    if (const int rc = stage_input(h, s0, in, h->d_charuco_frames, 0, &gray)) return rc;
+    if (const int rc = stage_input(h, s0, in, w0->scratch, frames_at, &gray)) return rc;
     a.row_stride = gray.row, a.frame_stride = gray.frame;
     // every worker interpolates the corners of the frames it detected, on its own stream
     const int rc = on_workers(h, b, [&](const Span& s) {
@@ -186,19 +193,25 @@ int arucohip_charuco_calibrate_batch(arucohip_handle* h, float square_size, int 
     if (views.empty()) return fail(h, ARUCOHIP_E_INVALID, "no frame holds min_corners chessboard corners");
     HIPCHK(h, hipSetDevice(h->device));
     const int V = (int)views.size();
-    const size_t o_npt = align256((size_t)V * sizeof(int2)), o_obj = o_npt + align256((size_t)V * sizeof(int32_t));
-    const size_t o_img = o_obj + align256((size_t)total * 3 * sizeof(float)), bytes = o_img + align256((size_t)total * 2 * sizeof(float));
-    HIPCHK(h, h->d_charuco_work.reserve(bytes));
-    uint8_t* wk = h->d_charuco_work;
+    // the views live in a Mem of their own, not in the arena: arucohip_calibrate_camera below reads them and carves the arena itself
+    int2* d_views;
+    int32_t* d_npt;
+    float *d_obj, *d_img;
+    auto layout = [&](uint8_t* base) {
+        Carver cv{base};
+        d_views = cv.take<int2>((size_t)V), d_npt = cv.take<int32_t>((size_t)V);
+        d_obj = cv.take<float>((size_t)total * 3), d_img = cv.take<float>((size_t)total * 2);
+        return cv.at;
+    };
+    HIPCHK(h, h->d_charuco_views.reserve(layout(nullptr)));
+    layout(h->d_charuco_views);
     hipStream_t s = h->stream;
-    HIPCHK(h, hipMemcpyAsync(wk, views.data(), (size_t)V * sizeof(int2), hipMemcpyHostToDevice, s));
-    launch_charuco_gather(s, L, charuco_scale(L, square_size), (const arucohip_charuco_corner_t*)(uint8_t*)h->d_charuco, (const int2*)wk, V,
-                          (float*)(wk + o_obj), (float*)(wk + o_img), (int32_t*)(wk + o_npt));
+    HIPCHK(h, hipMemcpyAsync(d_views, views.data(), (size_t)V * sizeof(int2), hipMemcpyHostToDevice, s));
+    launch_charuco_gather(s, L, charuco_scale(L, square_size), (const arucohip_charuco_corner_t*)(uint8_t*)h->d_charuco, d_views, V, d_obj, d_img, d_npt);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(s));
     // the device solver, unchanged, on the device-resident views
-    return arucohip_calibrate_camera(h, (const float*)(wk + o_obj), (const float*)(wk + o_img), (const int32_t*)(wk + o_npt), V, 1, W, H, flags, K, dist,
-                                     rvecs, tvecs, nullptr, rms);
+    return arucohip_calibrate_camera(h, d_obj, d_img, d_npt, V, 1, W, H, flags, K, dist, rvecs, tvecs, nullptr, rms);
 }
 
 int arucohip_charuco_pose_batch(arucohip_handle* h, int nframes, const float* K, const float* dist, int ndist, float square_size, int min_corners,
@@ -213,8 +226,11 @@ int arucohip_charuco_pose_batch(arucohip_handle* h, int nframes, const float* K,
     fill_cam(&cam, K, dist, ndist, square_size, y_perp);
     HIPCHK(h, hipSetDevice(h->device));
     const arucohip_charuco_t L = h->charuco.layout;
-    HIPCHK(h, h->d_charuco_work.reserve((size_t)nframes * sizeof(arucohip_board_t)));
-    arucohip_board_t* d_out = (arucohip_board_t*)(uint8_t*)h->d_charuco_work;
+    arucohip_board_t* d_out;
+    if (const int rc = carve_scratch(h, h, [&](Carver& cv) {
+            d_out = cv.take<arucohip_board_t>((size_t)nframes);
+        }))
+        return rc;
     hipStream_t s = h->stream;
     launch_charuco_pose(s, L, charuco_scale(L, square_size), (const arucohip_charuco_corner_t*)(uint8_t*)h->d_charuco, nframes, min_corners, cam, d_out);
     HIPCHK(h, hipGetLastError());

@@ -234,26 +234,32 @@ int arucohip_chromatic_set_model(arucohip_chromatic* m, const double* prob, cons
     return ARUCOHIP_OK;
 }
 
-// EMClassifier::train of one cell by chroma_em_kernel, in a small scratch of the handle's
+// EMClassifier::train of one cell by chroma_em_kernel, in the handle's arena
 int arucohip_em_fit(arucohip_handle* h, const uint32_t samples_hist[256], double thresh_prob, double prob[256], uint8_t inside[256], int* trained) {
     if (!h) return ARUCOHIP_E_INVALID;
     if (!samples_hist || !prob || !inside || !trained) return fail(h, ARUCOHIP_E_INVALID, "em_fit: NULL argument");
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t o_hc = 1024, o_fit = 2048, o_tr = 2056, o_prob = 2064, o_in = o_prob + 2048, total = o_in + 256;
-    HIPCHK(h, h->d_em.reserve(total));   // kept for the handle's life
-    uint8_t* b = h->d_em;
+    uint32_t *d_hist, *d_hcount;
+    int32_t *d_fit, *d_tr;
+    double* d_prob;
+    uint8_t* d_in;
+    if (const int rc = carve_scratch(h, h, [&](Carver& cv) {
+            d_hist = cv.take<uint32_t>(256), d_hcount = cv.take<uint32_t>(256);
+            d_fit = cv.take<int32_t>(1), d_tr = cv.take<int32_t>(1);
+            d_prob = cv.take<double>(256), d_in = cv.take<uint8_t>(256);
+        }))
+        return rc;
     hipStream_t s = h->stream;
-    HIPCHK(h, hipMemcpyAsync(b, samples_hist, 1024, hipMemcpyHostToDevice, s));
-    launch_chroma_em(s, 1, (const uint32_t*)b, 0, thresh_prob, (uint32_t*)(b + o_hc), (int32_t*)(b + o_fit), (double*)(b + o_prob), b + o_in,
-                     (int32_t*)(b + o_tr));
+    HIPCHK(h, hipMemcpyAsync(d_hist, samples_hist, 1024, hipMemcpyHostToDevice, s));
+    launch_chroma_em(s, 1, d_hist, 0, thresh_prob, d_hcount, d_fit, d_prob, d_in, d_tr);
     HIPCHK(h, hipGetLastError());
     int32_t fitted = 0;
-    HIPCHK(h, hipMemcpyAsync(&fitted, b + o_fit, sizeof(fitted), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(&fitted, d_fit, sizeof(fitted), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
     *trained = fitted == 1;
     if (fitted == 1) {
-        HIPCHK(h, hipMemcpyAsync(prob, b + o_prob, 256 * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(inside, b + o_in, 256, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(prob, d_prob, 256 * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(inside, d_in, 256, hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipStreamSynchronize(s));
     }
     return ARUCOHIP_OK;

@@ -48,25 +48,30 @@ int check_call(arucohip_handle* h, const Call& c, bool need_K) {
     return c.masks.p ? check_disjoint(h, "composite", "masks", c.masks, "the frames", c.frames) : ARUCOHIP_OK;
 }
 
-// The painting of a checked call with device maps: host frames, textures and masks go up, staged tightly packed in d_composite_frames,
-// and host frames come back. Queues only; the caller synchronises.
-int paint(arucohip_handle* h, const Call& c, const double* maps, const int32_t* valid) {
+// The one layout of a call in the handle's arena: the plane maps it uploads or computes (n_maps frames; 0: the caller's are on the
+// device) and the staged host frames, textures and masks, tightly packed.
+struct Scratch {
+    PlaneMaps m;
+    size_t frames_at, tex_at, masks_at;
+};
+int carve(arucohip_handle* h, const Call& c, int n_maps, Scratch* sc) {
+    return carve_scratch(h, h, [&](Carver& cv) {
+        carve_plane_maps(cv, n_maps, &sc->m);
+        sc->frames_at = cv.take_at(c.frames.on_device ? 0 : c.frames.packed_bytes());
+        sc->tex_at = cv.take_at(c.tex->on_device ? 0 : c.tex_images.packed_bytes());
+        sc->masks_at = cv.take_at(c.masks.p && !c.masks.on_device ? c.masks.packed_bytes() : 0);
+    });
+}
+
+// The painting of a checked call with device maps: host frames, textures and masks go up and host frames come back. Queues only; the
+// caller synchronises.
+int paint(arucohip_handle* h, const Call& c, const Scratch& sc, const double* maps, const int32_t* valid) {
     const arucohip_texture_t& t = *c.tex;
-    size_t bytes = 0;
-    auto room = [&](const Images& im, bool staged) {   // where a staged batch goes: 256-byte aligned, one after the other
-        const size_t at = bytes;
-        if (staged) bytes += (im.packed_bytes() + 255) & ~(size_t)255;
-        return at;
-    };
-    const size_t frames_at = room(c.frames, !c.frames.on_device);
-    const size_t tex_at = room(c.tex_images, !t.on_device);
-    const size_t masks_at = room(c.masks, c.masks.p && !c.masks.on_device);
-    HIPCHK(h, h->d_composite_frames.reserve(bytes));
     DevImages frames, tex, masks = {nullptr, 0, 0};
-    if (const int rc = stage_input(h, h->stream, c.frames, h->d_composite_frames, frames_at, &frames)) return rc;
-    if (const int rc = stage_input(h, h->stream, c.tex_images, h->d_composite_frames, tex_at, &tex)) return rc;
+    if (const int rc = stage_input(h, h->stream, c.frames, h->scratch, sc.frames_at, &frames)) return rc;
+    if (const int rc = stage_input(h, h->stream, c.tex_images, h->scratch, sc.tex_at, &tex)) return rc;
     if (c.masks.p)
-        if (const int rc = stage_input(h, h->stream, c.masks, h->d_composite_frames, masks_at, &masks)) return rc;
+        if (const int rc = stage_input(h, h->stream, c.masks, h->scratch, sc.masks_at, &masks)) return rc;
     PlaneComposite a;
     std::memset(&a, 0, sizeof(a));
     a.frames = frames.p, a.row_stride = frames.row, a.frame_stride = frames.frame;
@@ -95,8 +100,10 @@ int arucohip_composite_plane_batch(arucohip_handle* h, uint8_t* frames, int nfra
     if (!maps) return fail(h, ARUCOHIP_E_INVALID, "composite: maps is NULL");
     if (const int rc = check_call(h, c, false)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    if (const int rc = stage_plane_maps(h, h->d_composite, nframes, maps_on_device, &maps, &valid)) return rc;
-    if (const int rc = paint(h, c, maps, valid)) return rc;
+    Scratch sc;
+    if (const int rc = carve(h, c, maps_on_device ? 0 : nframes, &sc)) return rc;
+    if (const int rc = stage_plane_maps(h, sc.m, nframes, maps_on_device, &maps, &valid)) return rc;
+    if (const int rc = paint(h, c, sc, maps, valid)) return rc;
     if (!c.resident() || !maps_on_device) HIPCHK(h, hipStreamSynchronize(h->stream));
     return ARUCOHIP_OK;
 }
@@ -114,10 +121,11 @@ int arucohip_board_composite_batch(arucohip_handle* h, uint8_t* frames, int nfra
         return fail(h, ARUCOHIP_E_INVALID, "composite: the window's out_width / out_height differ from the texture's size");
     if (!window_spans_plane(*win)) return fail(h, ARUCOHIP_E_INVALID, "composite: the window's u and v steps are parallel, zero or not finite");
     HIPCHK(h, hipSetDevice(h->device));
-    PlaneMaps m;
-    if (const int rc = plane_maps_of_boards(h, h->d_composite, launch_plane_inverse_maps, boards, boards_on_device, nframes, *win, &m)) return rc;
-    if (const int rc = paint(h, c, m.maps, m.valid)) return rc;
-    if (const int rc = read_plane_maps(h, m, nframes, status, maps_out)) return rc;
+    Scratch sc;
+    if (const int rc = carve(h, c, nframes, &sc)) return rc;
+    if (const int rc = plane_maps_of_boards(h, sc.m, launch_plane_inverse_maps, boards, boards_on_device, nframes, *win)) return rc;
+    if (const int rc = paint(h, c, sc, sc.m.maps, sc.m.valid)) return rc;
+    if (const int rc = read_plane_maps(h, sc.m, nframes, status, maps_out)) return rc;
     if (!c.resident() || !boards_on_device || status || maps_out) HIPCHK(h, hipStreamSynchronize(h->stream));
     return ARUCOHIP_OK;
 }

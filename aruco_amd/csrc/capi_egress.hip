@@ -34,15 +34,20 @@ int arucohip_export_batch(arucohip_handle* h, const uint8_t* src, int C, int nfr
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const size_t staged_frame = luma.packed_frame() + (nv12 ? chroma.packed_frame() : 0);
-    if (!src_on_device) HIPCHK(h, h->d_egress_src.reserve(in.packed_bytes()));
-    if (!dst_on_device) HIPCHK(h, h->d_egress.reserve((size_t)nframes * staged_frame));
+    // the arena holds the host frames of the call and the exported frames a host caller gets
+    size_t src_at, dst_at;
+    if ((rc = carve_scratch(h, h, [&](Carver& cv) {
+             src_at = cv.take_at(src_on_device ? 0 : in.packed_bytes());
+             dst_at = cv.take_at(dst_on_device ? 0 : (size_t)nframes * staged_frame);
+         })))
+        return rc;
     DevImages sdev, ddev, cdev;
     FrameFmt df = f;
-    if ((rc = stage_input(h, s, in, h->d_egress_src, 0, &sdev))) return rc;
-    if ((rc = stage_output(h, luma, h->d_egress, 0, &ddev, staged_frame))) return rc;
+    if ((rc = stage_input(h, s, in, h->scratch, src_at, &sdev))) return rc;
+    if ((rc = stage_output(h, luma, h->scratch, dst_at, &ddev, staged_frame))) return rc;
     if (!dst_on_device) {
         df.chroma_offset = 0;   // the staged chroma plane follows the Y plane
-        if (nv12 && (rc = stage_output(h, chroma, h->d_egress, luma.packed_frame(), &cdev, staged_frame))) return rc;
+        if (nv12 && (rc = stage_output(h, chroma, h->scratch, dst_at + luma.packed_frame(), &cdev, staged_frame))) return rc;
     }
     launch_egress(s, sdev.p, C, sdev.row, sdev.frame, W, H, nframes, df, (flags & ARUCOHIP_EXPORT_GREY_IS_LUMA) != 0, ddev.p, ddev.row, ddev.frame);
     HIPCHK(h, hipGetLastError());

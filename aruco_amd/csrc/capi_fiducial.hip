@@ -1,7 +1,7 @@
 // ---------------------------------------------------------------------------------------------
 // The default 5x5 Hamming markers (k_fiducial.hip): FiducidalMarkers::createMarkerImage, getMarkerMat, createBoardImage,
 // createBoardImage_ChessBoard, createBoardImage_Frame and the id shuffle behind them (src/arucofidmarkers.cpp:40-61, :214-430),
-// utils/aruco_board_pix2meters.cpp and utils/aruco_selectoptimalmarkers.cpp. The scratch is the handle's d_fiducial.
+// utils/aruco_board_pix2meters.cpp and utils/aruco_selectoptimalmarkers.cpp. The scratch is carved from the handle's arena.
 // ---------------------------------------------------------------------------------------------
 #include <hip/hip_runtime.h>
 
@@ -14,8 +14,6 @@ namespace {
 constexpr int FID_IDS = 1024;          // markers of the family
 constexpr int FID_MAX_SIDE = 16383;    // the largest frame side a handle accepts
 constexpr size_t FID_MAX_STAGE = (size_t)1 << 30;   // bytes of marker images staged for a host destination in one call
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // The cells of a board that carry a marker, row by row, and the image's size. false: outside the limits, or a chessboard that places
 // more markers than it draws ids (CV_Assert at :362).
@@ -76,24 +74,28 @@ int arucohip_fiducial_marker_images(arucohip_handle* h, const int32_t* ids, int 
     if (!images_on_device && is * n > FID_MAX_STAGE)
         return fail(h, ARUCOHIP_E_INVALID, "fiducial_marker_images: more than 2^30 bytes of images for a host destination in one call");
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t o_img = align256((size_t)n * sizeof(int32_t));
-    HIPCHK(h, h->d_fiducial.reserve(o_img + (images_on_device ? 0 : is * n)));
-    uint8_t* b = h->d_fiducial;
+    int32_t* d_ids;
+    uint8_t* d_img;
+    if (const int rc = carve_scratch(h, h, [&](Carver& cv) {
+            d_ids = cv.take<int32_t>((size_t)n);
+            d_img = cv.take<uint8_t>(images_on_device ? 0 : is * n);
+        }))
+        return rc;
     hipStream_t s = h->stream;
-    HIPCHK(h, hipMemcpyAsync(b, ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(d_ids, ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
     const int q = (side - size) / 2;
     const FidLayout L{side, side, size, size, q, 1, 1, size, size, size / 7};
     if (images_on_device) {
-        launch_fid_paint(s, L, (const int32_t*)b, n, images, row_stride, image_stride);
+        launch_fid_paint(s, L, d_ids, n, images, row_stride, image_stride);
         HIPCHK(h, hipGetLastError());
     } else {
-        launch_fid_paint(s, L, (const int32_t*)b, n, b + o_img, rs, is);
+        launch_fid_paint(s, L, d_ids, n, d_img, rs, is);
         HIPCHK(h, hipGetLastError());
         if (n == 1 || image_stride == (size_t)side * row_stride) {
-            HIPCHK(h, hipMemcpy2DAsync(images, row_stride, b + o_img, rs, side, (size_t)side * n, hipMemcpyDeviceToHost, s));
+            HIPCHK(h, hipMemcpy2DAsync(images, row_stride, d_img, rs, side, (size_t)side * n, hipMemcpyDeviceToHost, s));
         } else {
             for (int i = 0; i < n; i++)
-                HIPCHK(h, hipMemcpy2DAsync(images + (size_t)i * image_stride, row_stride, b + o_img + (size_t)i * is, rs, side, side,
+                HIPCHK(h, hipMemcpy2DAsync(images + (size_t)i * image_stride, row_stride, d_img + (size_t)i * is, rs, side, side,
                                            hipMemcpyDeviceToHost, s));
         }
     }
@@ -149,19 +151,24 @@ int arucohip_fiducial_board_image(arucohip_handle* h, int type, int grid_w, int 
     std::vector<int32_t> slots((size_t)grid_w * grid_h, -1);
     for (int k = 0; k < nm; k++) slots[p.cell[k]] = ids[k];
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t rs = ((size_t)p.W + 15) & ~(size_t)15, o_img = align256(slots.size() * sizeof(int32_t));
-    HIPCHK(h, h->d_fiducial.reserve(o_img + (image_on_device ? 0 : rs * p.H)));
-    uint8_t* b = h->d_fiducial;
+    const size_t rs = ((size_t)p.W + 15) & ~(size_t)15;
+    int32_t* d_slots;
+    uint8_t* d_img;
+    if (const int rc = carve_scratch(h, h, [&](Carver& cv) {
+            d_slots = cv.take<int32_t>(slots.size());
+            d_img = cv.take<uint8_t>(image_on_device ? 0 : rs * p.H);
+        }))
+        return rc;
     hipStream_t s = h->stream;
-    HIPCHK(h, hipMemcpyAsync(b, slots.data(), slots.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(d_slots, slots.data(), slots.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     const FidLayout L{p.W, p.H, p.W, p.H, 0, grid_w, grid_h, marker_size, p.pitch, marker_size / 7};
     if (image_on_device) {
-        launch_fid_paint(s, L, (const int32_t*)b, 1, image, row_stride, 0);
+        launch_fid_paint(s, L, d_slots, 1, image, row_stride, 0);
         HIPCHK(h, hipGetLastError());
     } else {
-        launch_fid_paint(s, L, (const int32_t*)b, 1, b + o_img, rs, 0);
+        launch_fid_paint(s, L, d_slots, 1, d_img, rs, 0);
         HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpy2DAsync(image, row_stride, b + o_img, rs, p.W, p.H, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpy2DAsync(image, row_stride, d_img, rs, p.W, p.H, hipMemcpyDeviceToHost, s));
     }
     if (obj) {   // TInfo.objPoints: integer pixel positions as float, minus the integer centre (the panel always, the others on request)
         const bool centre = type == 0 || centered;
@@ -220,10 +227,14 @@ int arucohip_fiducial_distances(arucohip_handle* h, int32_t* dist, int on_device
         launch_fid_distances(s, dist);
         HIPCHK(h, hipGetLastError());
     } else {
-        HIPCHK(h, h->d_fiducial.reserve(bytes));
-        launch_fid_distances(s, (int32_t*)(uint8_t*)h->d_fiducial);
+        int32_t* d_dist;
+        if (const int rc = carve_scratch(h, h, [&](Carver& cv) {
+                d_dist = cv.take<int32_t>((size_t)FID_IDS * FID_IDS);
+            }))
+            return rc;
+        launch_fid_distances(s, d_dist);
         HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(dist, h->d_fiducial, bytes, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(dist, d_dist, bytes, hipMemcpyDeviceToHost, s));
     }
     HIPCHK(h, hipStreamSynchronize(s));
     return ARUCOHIP_OK;
@@ -233,14 +244,16 @@ int arucohip_fiducial_select(arucohip_handle* h, int n_markers, int min_entropy,
     if (!h) return ARUCOHIP_E_INVALID;
     if (n_markers < 1 || n_markers > FID_IDS || !ids_out) return fail(h, ARUCOHIP_E_INVALID, "fiducial_select: n_markers must be 1..1024 and ids_out not NULL");
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t o_res = (size_t)FID_IDS * sizeof(int32_t);
-    HIPCHK(h, h->d_fiducial.reserve(o_res + 4 * sizeof(int32_t)));
-    uint8_t* b = h->d_fiducial;
+    int32_t* d_sel;   // the ids, then the four result words: one array, read back in one copy
+    if (const int rc = carve_scratch(h, h, [&](Carver& cv) {
+            d_sel = cv.take<int32_t>(FID_IDS + 4);
+        }))
+        return rc;
     hipStream_t s = h->stream;
-    launch_fid_select(s, n_markers, min_entropy, (int32_t*)b, (int32_t*)(b + o_res));
+    launch_fid_select(s, n_markers, min_entropy, d_sel, d_sel + FID_IDS);
     HIPCHK(h, hipGetLastError());
     int32_t out[FID_IDS + 4];
-    HIPCHK(h, hipMemcpyAsync(out, b, sizeof(out), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(out, d_sel, sizeof(out), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
     const int32_t* res = out + FID_IDS;
     const int found = std::min(std::max(res[0], 0), n_markers);

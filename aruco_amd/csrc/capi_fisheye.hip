@@ -49,10 +49,14 @@ static int fisheye_points(arucohip_handle* h, const arucohip_fisheye_t* model, c
         return ARUCOHIP_OK;
     }
     const size_t pts = (size_t)n * 2 * sizeof(float);
-    HIPCHK(h, h->d_fisheye.reserve(2 * pts + (size_t)n));
-    float* d_src = (float*)h->d_fisheye.p;
-    float* d_dst = d_src + (size_t)n * 2;
-    uint8_t* d_valid = (uint8_t*)(d_dst + (size_t)n * 2);
+    float *d_src, *d_dst;
+    uint8_t* d_valid;
+    if ((rc = carve_scratch(h, h, [&](Carver& cv) {
+             d_src = cv.take<float>((size_t)n * 2);
+             d_dst = cv.take<float>((size_t)n * 2);
+             d_valid = cv.take<uint8_t>((size_t)n);
+         })))
+        return rc;
     HIPCHK(h, hipMemcpyAsync(d_src, src, pts, hipMemcpyHostToDevice, s));
     launch_fisheye_points(s, cam, d_src, n, undistort, d_dst, d_valid);
     HIPCHK(h, hipGetLastError());
@@ -175,14 +179,18 @@ int arucohip_fisheye_undistort(arucohip_handle* h, const uint8_t* src, int nfram
         h->fmap_w = W, h->fmap_h = H;
         std::memcpy(h->fmap_key, key, sizeof(key));
     }
-    // one staging buffer: the host frames, then the packed result a host caller gets
+    // staged in the arena: the host frames, then the packed result a host caller gets
     const size_t row = (size_t)W * channels;
     const Images in = images(src, nframes, H, row, row_stride, frame_stride, src_on_device), out = images(dst, nframes, H, row, row, row * H, dst_on_device);
-    const size_t staged = src_on_device ? 0 : in.packed_bytes();
-    if (!src_on_device || !dst_on_device) HIPCHK(h, h->d_fisheye_frames.reserve(staged + (dst_on_device ? 0 : out.packed_bytes())));
+    size_t src_at, dst_at;
+    if ((rc = carve_scratch(h, h, [&](Carver& cv) {
+             src_at = cv.take_at(src_on_device ? 0 : in.packed_bytes());
+             dst_at = cv.take_at(dst_on_device ? 0 : out.packed_bytes());
+         })))
+        return rc;
     DevImages sdev, ddev;
-    if ((rc = stage_input(h, s, in, h->d_fisheye_frames, 0, &sdev))) return rc;
-    if ((rc = stage_output(h, out, h->d_fisheye_frames, staged, &ddev))) return rc;
+    if ((rc = stage_input(h, s, in, h->scratch, src_at, &sdev))) return rc;
+    if ((rc = stage_output(h, out, h->scratch, dst_at, &ddev))) return rc;
     launch_remap(s, sdev.p, sdev.row, sdev.frame, W, H, channels, nframes, h->d_fmap_xy, h->d_fmap_f, ddev.p);
     HIPCHK(h, hipGetLastError());
     if ((rc = unstage(h, s, out, ddev))) return rc;
@@ -214,10 +222,13 @@ int arucohip_fisheye_undistort_markers_batch(arucohip_handle* h, int nframes, co
         h->last.ideal = true;       // from the first span on a worker's lists may have changed, whatever happens to the rest of the call
         h->last.board_frames = 0;   // board poses left on the device came from the distorted corners
         arucohip_handle* w = s.w;
-        const size_t drop_bytes = ((size_t)w->cap_frames * sizeof(int32_t) + 255) & ~(size_t)255;
-        HIPCHK(h, w->d_fisheye.reserve(drop_bytes + cam_bytes));
-        int32_t* d_dropped = (int32_t*)w->d_fisheye.p;
-        FisheyeCam* d_cams = (FisheyeCam*)(w->d_fisheye.p + drop_bytes);
+        int32_t* d_dropped;
+        FisheyeCam* d_cams;
+        if (const int e = carve_scratch(w, h, [&](Carver& cv) {
+                d_dropped = cv.take<int32_t>((size_t)w->cap_frames);
+                d_cams = cv.take<FisheyeCam>((size_t)nmodels);
+            }))
+            return e;
         hipStream_t st = w->stream;
         HIPCHK(h, hipMemcpyAsync(d_cams, h->fisheye_cams.data(), cam_bytes, hipMemcpyHostToDevice, st));
         launch_fisheye_markers(st, d_cams, nmodels, s.first, s.count, w->buf, d_dropped);

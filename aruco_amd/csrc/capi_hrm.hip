@@ -1,6 +1,6 @@
 // ---------------------------------------------------------------------------------------------
 // Highly reliable marker dictionaries and boards (k_hrm.hip): HighlyReliableMarkers::createDicitionary and createBoardImage
-// (src/highlyreliablemarkers.cpp:498-608). The scratch is the handle's d_hrm_gen.
+// (src/highlyreliablemarkers.cpp:498-608). The scratch is carved from the handle's arena.
 // ---------------------------------------------------------------------------------------------
 #include <hip/hip_runtime.h>
 
@@ -54,8 +54,6 @@ void hrm_state0(uint32_t seed, uint32_t out[S31]) {
     for (int i = 34; i < 344; i++) r[i] = r[i - 31] + r[i - 3];
     for (int i = 0; i < S31; i++) out[i] = r[313 + i];
 }
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 }  // namespace
 
 extern "C" {
@@ -68,12 +66,17 @@ int arucohip_hrm_create_dictionary(arucohip_handle* h, int n, int dict_size, uin
     if (!codes_out) return fail(h, ARUCOHIP_E_INVALID, "hrm_create_dictionary: NULL codes_out");
     HIPCHK(h, hipSetDevice(h->device));
     const size_t jbytes = (size_t)(HRM_LANE_BITS + 1) * S31 * S31 * sizeof(uint32_t);
-    const size_t o_state = align256(jbytes), o_ctl = o_state + 256, o_code = o_ctl + 256, o_self = o_code + (size_t)HRM_WINDOW * 8,
-                 o_dmin = o_self + HRM_WINDOW, o_dict = o_dmin + HRM_WINDOW, total = o_dict + (size_t)4096 * 4 * sizeof(uint64_t);
-    HIPCHK(h, h->d_hrm_gen.reserve(total));
-    uint8_t* b = h->d_hrm_gen;
-    HrmBufs bufs{(uint32_t*)(b + o_state), (uint32_t*)b, (uint64_t*)(b + o_code), b + o_self, b + o_dmin, (uint64_t*)(b + o_dict),
-                 (HrmCtl*)(b + o_ctl)};
+    HrmBufs bufs;
+    if (const int rc = carve_scratch(h, h, [&](Carver& cv) {
+            bufs.jumps = cv.take<uint32_t>((size_t)(HRM_LANE_BITS + 1) * S31 * S31);
+            bufs.state = cv.take<uint32_t>(S31);
+            bufs.ctl = cv.take<HrmCtl>(1);
+            bufs.code = cv.take<uint64_t>(HRM_WINDOW);
+            bufs.selfd = cv.take<uint8_t>(HRM_WINDOW);
+            bufs.dmin = cv.take<uint8_t>(HRM_WINDOW);
+            bufs.dict = cv.take<uint64_t>((size_t)4096 * 4);
+        }))
+        return rc;
     // J_b = M^(HRM_LANE_CANDS n^2 2^b): lane l starts at J applied for the bits of l; the last one is a whole window
     std::vector<uint32_t> jumps;
     M31 J = m31_pow((uint64_t)HRM_LANE_CANDS * n * n);
@@ -126,10 +129,14 @@ int arucohip_debug_hrm_stream(arucohip_handle* h, uint32_t seed, uint64_t offset
         return fail(h, ARUCOHIP_E_INVALID, "debug_hrm_stream: count must be 0..2^24 and offset + count below 2^48");
     if (count == 0) return ARUCOHIP_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t pbytes = (size_t)HRM_POW_BITS * S31 * S31 * sizeof(uint32_t), o_state = align256(pbytes), o_out = o_state + 256,
-                 total = o_out + (size_t)count * sizeof(uint32_t);
-    HIPCHK(h, h->d_hrm_gen.reserve(total));
-    uint8_t* b = h->d_hrm_gen;
+    const size_t pbytes = (size_t)HRM_POW_BITS * S31 * S31 * sizeof(uint32_t);
+    uint32_t *d_pow2, *d_state, *d_out;
+    if (const int rc = carve_scratch(h, h, [&](Carver& cv) {
+            d_pow2 = cv.take<uint32_t>((size_t)HRM_POW_BITS * S31 * S31);
+            d_state = cv.take<uint32_t>(S31);
+            d_out = cv.take<uint32_t>((size_t)count);
+        }))
+        return rc;
     std::vector<uint32_t> pow2;
     M31 P = m31_pow(1);
     for (int bit = 0; bit < HRM_POW_BITS; bit++) {
@@ -139,11 +146,11 @@ int arucohip_debug_hrm_stream(arucohip_handle* h, uint32_t seed, uint64_t offset
     uint32_t st[S31];
     hrm_state0(seed, st);
     hipStream_t s = h->stream;
-    HIPCHK(h, hipMemcpyAsync(b, pow2.data(), pbytes, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(b + o_state, st, sizeof(st), hipMemcpyHostToDevice, s));
-    launch_hrm_stream(s, (const uint32_t*)(b + o_state), (const uint32_t*)b, offset, count, (uint32_t*)(b + o_out));
+    HIPCHK(h, hipMemcpyAsync(d_pow2, pow2.data(), pbytes, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(d_state, st, sizeof(st), hipMemcpyHostToDevice, s));
+    launch_hrm_stream(s, d_state, d_pow2, offset, count, d_out);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out, b + o_out, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(out, d_out, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
     return ARUCOHIP_OK;
 }
@@ -172,14 +179,19 @@ int arucohip_hrm_board_image(arucohip_handle* h, int n, int count, const uint64_
     for (int i = 0; i < nb; i++)
         if (codes[i] & ~valid) return fail(h, ARUCOHIP_E_INVALID, "hrm_board_image: a code has bits past n * n");
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t stride = ((size_t)W * ch + 15) & ~(size_t)15, o_img = align256((size_t)nb * sizeof(uint64_t)), total = o_img + stride * H;
-    HIPCHK(h, h->d_hrm_gen.reserve(total));
-    uint8_t* b = h->d_hrm_gen;
+    const size_t stride = ((size_t)W * ch + 15) & ~(size_t)15;
+    uint64_t* d_codes;
+    uint8_t* d_img;
+    if (const int rc = carve_scratch(h, h, [&](Carver& cv) {
+            d_codes = cv.take<uint64_t>((size_t)nb);
+            d_img = cv.take<uint8_t>(stride * H);
+        }))
+        return rc;
     hipStream_t s = h->stream;
-    HIPCHK(h, hipMemcpyAsync(b, codes, (size_t)nb * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    launch_hrm_board(s, (const uint64_t*)b, n, grid_w, grid_h, chromatic ? 1 : 0, W, H, ch, stride, b + o_img);
+    HIPCHK(h, hipMemcpyAsync(d_codes, codes, (size_t)nb * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    launch_hrm_board(s, d_codes, n, grid_w, grid_h, chromatic ? 1 : 0, W, H, ch, stride, d_img);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpy2DAsync(image, row_stride, b + o_img, stride, (size_t)W * ch, H, image_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpy2DAsync(image, row_stride, d_img, stride, (size_t)W * ch, H, image_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
     // BC.ids (getId(): sum of 2 << pos) and BC.objPoints, on the host in the reference's float arithmetic
     const unsigned ms = (unsigned)(n + 2) * 20, gap = ms / 5;
     const int sx = grid_w * (int)ms + (grid_w - 1) * (int)gap, sy = grid_h * (int)ms + (grid_h - 1) * (int)gap;

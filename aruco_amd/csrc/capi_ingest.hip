@@ -106,16 +106,21 @@ int arucohip_convert_batch(arucohip_handle* h, const void* src_, const arucohip_
     hipStream_t s = h->stream;
     const bool with_chroma = nv12 && C == 3;
     const size_t staged_frame = luma.packed_frame() + (with_chroma ? chroma.packed_frame() : 0);
-    if (!src_on_device) HIPCHK(h, h->d_ingest_src.reserve((size_t)nframes * staged_frame));
-    if (!dst_on_device) HIPCHK(h, h->d_ingest.reserve(out.packed_bytes()));
+    // the arena holds the raw host frames of the call and the converted frames a host caller gets
+    size_t src_at, dst_at;
+    if ((rc = carve_scratch(h, h, [&](Carver& cv) {
+             src_at = cv.take_at(src_on_device ? 0 : (size_t)nframes * staged_frame);
+             dst_at = cv.take_at(dst_on_device ? 0 : out.packed_bytes());
+         })))
+        return rc;
     DevImages sdev, cdev, ddev;
     FrameFmt sf = f;
-    if ((rc = stage_input(h, s, luma, h->d_ingest_src, 0, &sdev, staged_frame))) return rc;
+    if ((rc = stage_input(h, s, luma, h->scratch, src_at, &sdev, staged_frame))) return rc;
     if (!src_on_device) {
         sf.chroma_offset = 0;   // the staged chroma plane follows the Y plane
-        if (with_chroma && (rc = stage_input(h, s, chroma, h->d_ingest_src, luma.packed_frame(), &cdev, staged_frame))) return rc;
+        if (with_chroma && (rc = stage_input(h, s, chroma, h->scratch, src_at + luma.packed_frame(), &cdev, staged_frame))) return rc;
     }
-    if ((rc = stage_output(h, out, h->d_ingest, 0, &ddev))) return rc;
+    if ((rc = stage_output(h, out, h->scratch, dst_at, &ddev))) return rc;
     launch_ingest(s, sf, sdev.p, sdev.row, sdev.frame, W, H, nframes, C, ddev.p, ddev.row, ddev.frame);
     HIPCHK(h, hipGetLastError());
     if ((rc = unstage(h, s, out, ddev))) return rc;

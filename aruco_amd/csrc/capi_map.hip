@@ -10,15 +10,14 @@
 
 extern "C" {
 
-// The writable ends of what a call uploads or gathers into d_map: the listed ids, and the observation arrays (staging of host
+// The writable ends of what a call uploads or gathers into the arena: the listed ids, and the observation arrays (staging of host
 // arrays, or a batch's gather). d.obs_* are set by the caller, who knows where the observations are.
 struct MapStage {
     int32_t *ids, *obs_frame, *obs_id, *obs_cnt;
     float* obs_corners;
 };
-// d's arrays in `base` for F frames, nboard markers and room for nobs staged observations; returns the bytes.
-static size_t map_layout(MapDev& d, MapStage& w, uint8_t* base, int F, int nboard, size_t nobs) {
-    Carver c{base};
+// d's arrays from `c` for F frames, nboard markers and room for nobs staged observations.
+static void map_layout(MapDev& d, MapStage& w, Carver& c, int F, int nboard, size_t nobs) {
     const size_t N = (size_t)6 * (nboard - 1), f = (size_t)F, nb = (size_t)nboard;
     d.st = c.take<MapState>(1), d.ids = w.ids = c.take<int32_t>(nb);
     d.slot = c.take<int8_t>(f * MAP_MAX_MARKERS), d.fm = c.take<int8_t>(f * MAP_SLOTS), d.fn = c.take<int32_t>(f), d.used = c.take<int32_t>(f);
@@ -31,7 +30,6 @@ static size_t map_layout(MapDev& d, MapStage& w, uint8_t* base, int F, int nboar
     d.obj = c.take<float>(nb * 12);
     w.obs_frame = c.take<int32_t>(nobs), w.obs_id = c.take<int32_t>(nobs), w.obs_corners = c.take<float>(nobs * 8);
     w.obs_cnt = c.take<int32_t>(f);
-    return c.at;
 }
 
 struct MapOut {
@@ -58,7 +56,7 @@ static int map_args(arucohip_handle* h, int nframes, const int32_t* ids, int nbo
 }
 
 // Start values and Levenberg-Marquardt (lm_drive) on observations that are already on the device (d.obs_*), on o's stream and in
-// o's d_map, where d is bound.
+// o's arena, where d is bound.
 static int map_solve(arucohip_handle* o, MapDev d, int32_t* dids, const int32_t* ids, const CamModel& cam, const MapOut& out) {
     const int F = d.nframes, nb = d.nboard;
     hipStream_t s = o->stream;
@@ -128,8 +126,7 @@ int arucohip_board_map(arucohip_handle* h, const int32_t* obs_frame, const int32
     MapDev d{};
     MapStage w;
     const size_t staged = on_device ? 0 : (size_t)nobs;
-    HIPCHK(h, h->d_map.reserve(map_layout(d, w, nullptr, nframes, nboard, staged)));
-    map_layout(d, w, h->d_map, nframes, nboard, staged);
+    if ((rc = carve_scratch(h, h, [&](Carver& c) { map_layout(d, w, c, nframes, nboard, staged); }))) return rc;
     d.nframes = nframes, d.nboard = nboard, d.min_markers = 2, d.nobs = nobs;
     ObsArrays obs;
     if ((rc = stage_obs(h, ObsArrays{obs_frame, obs_id, obs_corners}, nobs, on_device, w.obs_frame, w.obs_id, w.obs_corners, &obs))) return rc;
@@ -153,8 +150,7 @@ int arucohip_board_map_batch(arucohip_handle* h, int nframes, const int32_t* ids
     for (const Span& s : b) stride = std::max(stride, s.w->buf.cap_markers);
     MapDev d{};
     MapStage w;
-    HIPCHK(h, o->d_map.reserve(map_layout(d, w, nullptr, nframes, nboard, (size_t)nframes * stride)));
-    map_layout(d, w, o->d_map, nframes, nboard, (size_t)nframes * stride);
+    if ((rc = carve_scratch(o, h, [&](Carver& c) { map_layout(d, w, c, nframes, nboard, (size_t)nframes * stride); }))) return rc;
     // every worker lays out the markers of the frames it detected, on its own stream
     rc = on_workers(h, b, [&](const Span& s) {
         launch_map_gather(s.w->stream, s.count, s.w->buf, s.first, stride, w.obs_id, w.obs_corners, w.obs_cnt);

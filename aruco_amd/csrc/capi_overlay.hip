@@ -33,7 +33,8 @@ int check_camera(arucohip_handle* h, bool need_K, const float* K, const float* d
 }
 
 // The common part: `slots` marker slots per frame (1 for boards). src / counts: device pointers, or host arrays of `elem` bytes per slot
-// that are staged behind the scratch. build(frames0, nframes, src, counts, recs, prims) enqueues the build kernel of one chunk.
+// that are staged behind the primitive lists in the handle's arena, with host frames behind them, tightly packed.
+// build(frames0, nframes, src, counts, recs, prims) enqueues the build kernel of one chunk.
 template <typename Build>
 int draw(arucohip_handle* h, const Frames& f, const void* src, size_t elem, int slots, const int32_t* counts, int src_on_device, Build build) {
     HIPCHK(h, hipSetDevice(h->device));
@@ -41,22 +42,27 @@ int draw(arucohip_handle* h, const Frames& f, const void* src, size_t elem, int 
     // the scratch holds the primitive lists of a chunk of frames: at most 64 MiB (and 65535 frames, the grid's z limit), at least one frame
     const size_t per_frame = (size_t)slots * (OV_REC_BYTES + OV_PRIM_BYTES);
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)f.im.n, 65535, ((size_t)64 << 20) / per_frame}));
-    const size_t scratch = (size_t)chunk * per_frame;
     const size_t src_bytes = src_on_device ? 0 : (size_t)f.im.n * slots * elem, cnt_bytes = (src_on_device || !counts) ? 0 : (size_t)f.im.n * sizeof(int32_t);
-    HIPCHK(h, h->d_overlay.reserve(scratch + src_bytes + cnt_bytes));
-    uint8_t* base = h->d_overlay;
+    uint8_t *recs, *prims, *d_src, *d_counts;
+    size_t frames_at;
+    if (const int rc = carve_scratch(h, h, [&](Carver& cv) {
+            recs = cv.take<uint8_t>((size_t)chunk * slots * OV_REC_BYTES);
+            prims = cv.take<uint8_t>((size_t)chunk * slots * OV_PRIM_BYTES);
+            d_src = cv.take<uint8_t>(src_bytes);
+            d_counts = cv.take<uint8_t>(cnt_bytes);
+            frames_at = cv.take_at(f.im.on_device ? 0 : f.im.packed_bytes());
+        }))
+        return rc;
     if (!src_on_device) {
-        HIPCHK(h, hipMemcpyAsync(base + scratch, src, src_bytes, hipMemcpyHostToDevice, s));
-        src = base + scratch;
+        HIPCHK(h, hipMemcpyAsync(d_src, src, src_bytes, hipMemcpyHostToDevice, s));
+        src = d_src;
         if (counts) {
-            HIPCHK(h, hipMemcpyAsync(base + scratch + src_bytes, counts, cnt_bytes, hipMemcpyHostToDevice, s));
-            counts = (const int32_t*)(base + scratch + src_bytes);
+            HIPCHK(h, hipMemcpyAsync(d_counts, counts, cnt_bytes, hipMemcpyHostToDevice, s));
+            counts = (const int32_t*)d_counts;
         }
     }
-    if (!f.im.on_device) HIPCHK(h, h->d_overlay_frames.reserve(f.im.packed_bytes()));
     DevImages dev;
-    if (const int rc = stage_input(h, s, f.im, h->d_overlay_frames, 0, &dev)) return rc;
-    void *recs = base, *prims = base + (size_t)chunk * slots * OV_REC_BYTES;
+    if (const int rc = stage_input(h, s, f.im, h->scratch, frames_at, &dev)) return rc;
     for (int f0 = 0; f0 < f.im.n; f0 += chunk) {
         const int nf = std::min(chunk, f.im.n - f0);
         build(s, nf, (const uint8_t*)src + (size_t)f0 * slots * elem, counts ? counts + f0 : nullptr, recs, prims);

@@ -34,11 +34,15 @@ int arucohip_planar_poses(arucohip_handle* h, const arucohip_marker_t* markers, 
         HIPCHK(h, hipStreamSynchronize(s));
         return ARUCOHIP_OK;
     }
-    // d_planar: the results, then the markers (no captured launch reads it: it may grow at any time)
+    // in the arena: the results, then the markers
     const size_t out_bytes = (size_t)n * sizeof(arucohip_planar_poses_t), in_bytes = (size_t)n * sizeof(arucohip_marker_t);
-    HIPCHK(h, h->d_planar.reserve(out_bytes + in_bytes));
-    arucohip_planar_poses_t* d_out = (arucohip_planar_poses_t*)(uint8_t*)h->d_planar;
-    arucohip_marker_t* d_in = (arucohip_marker_t*)((uint8_t*)h->d_planar + out_bytes);
+    arucohip_planar_poses_t* d_out;
+    arucohip_marker_t* d_in;
+    if ((rc = carve_scratch(h, h, [&](Carver& cv) {
+             d_out = cv.take<arucohip_planar_poses_t>((size_t)n);
+             d_in = cv.take<arucohip_marker_t>((size_t)n);
+         })))
+        return rc;
     HIPCHK(h, hipMemcpyAsync(d_in, markers, in_bytes, hipMemcpyHostToDevice, s));
     launch_planar_poses(s, d_in, n, cam, refine, d_out);
     HIPCHK(h, hipGetLastError());
@@ -66,7 +70,7 @@ int arucohip_planar_poses_batch(arucohip_handle* h, int nframes, const float* K,
             cnt[f] = std::max(std::min(cnt[f], s.w->buf.cap_markers), 0);   // what the batch returned: clamped, 0 for a frame it gave up
             if (cnt[f] > cap) return fail(h, ARUCOHIP_E_CAPACITY, "planar_poses_batch: a frame holds more than cap markers");
         }
-    // every worker solves the markers of the frames it detected, on its own stream; host results go through the worker's d_planar
+    // every worker solves the markers of the frames it detected, on its own stream; host results go through the worker's arena
     std::vector<arucohip_planar_poses_t> stage;
     if (!out_on_device) stage.resize((size_t)nframes * cap);
     rc = on_workers(h, b, [&](const Span& s) -> int {
@@ -76,9 +80,13 @@ int arucohip_planar_poses_batch(arucohip_handle* h, int nframes, const float* K,
             launch_planar_poses_list(w->stream, list_frames, s.count, s.first, w->buf, cam, refine, out, cap);
         } else {
             const size_t bytes = (size_t)s.count * cap * sizeof(arucohip_planar_poses_t);
-            HIPCHK(h, w->d_planar.reserve(bytes));
-            launch_planar_poses_list(w->stream, list_frames, s.count, 0, w->buf, cam, refine, (arucohip_planar_poses_t*)(uint8_t*)w->d_planar, cap);
-            HIPCHK(h, hipMemcpyAsync(stage.data() + (size_t)s.first * cap, (uint8_t*)w->d_planar, bytes, hipMemcpyDeviceToHost, w->stream));
+            arucohip_planar_poses_t* d_out;
+            if (const int e = carve_scratch(w, h, [&](Carver& cv) {
+                    d_out = cv.take<arucohip_planar_poses_t>((size_t)s.count * cap);
+                }))
+                return e;
+            launch_planar_poses_list(w->stream, list_frames, s.count, 0, w->buf, cam, refine, d_out, cap);
+            HIPCHK(h, hipMemcpyAsync(stage.data() + (size_t)s.first * cap, d_out, bytes, hipMemcpyDeviceToHost, w->stream));
         }
         return ARUCOHIP_OK;
     });

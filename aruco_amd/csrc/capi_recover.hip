@@ -14,15 +14,13 @@ void arucohip_default_recover(arucohip_recover_t* o) {
     o->max_corner_dist = 10.f, o->max_cell_errors = 3, o->min_markers = 2, o->pose_markers = 0;
 }
 
-// r's arrays and the board (ids, obj) in a worker's d_recover for F frames of cap_markers markers and a board of nboard markers; returns the bytes
-static size_t recover_layout(RecoverBufs& r, int32_t** ids, float** obj, uint8_t* base, int F, int cap_markers, int nboard) {
-    Carver c{base};
+// r's arrays and the board (ids, obj) in a worker's arena for F frames of cap_markers markers and a board of nboard markers
+static void recover_layout(RecoverBufs& r, int32_t** ids, float** obj, Carver& c, int F, int cap_markers, int nboard) {
     const size_t slots = (size_t)F * cap_markers;
     r.base = c.take<int32_t>((size_t)F), r.nrec = c.take<int32_t>((size_t)F), r.recovered = c.take<int32_t>((size_t)F);
     r.status = c.take<uint32_t>(1);
     r.rec = c.take<RecoverRec>(slots), r.rlist = c.take<uint32_t>(slots), r.plist = c.take<uint32_t>(slots);
     *ids = c.take<int32_t>((size_t)nboard), *obj = c.take<float>((size_t)nboard * 12);
-    return c.at;
 }
 
 int arucohip_board_recover_batch(arucohip_handle* h, int nframes, const int32_t* ids, const float* obj, int nboard, int info_type, const float* K,
@@ -78,8 +76,7 @@ int arucohip_board_recover_batch(arucohip_handle* h, int nframes, const int32_t*
         RecoverBufs r;
         int32_t* dids;
         float* dobj;
-        HIPCHK(h, w->d_recover.reserve(recover_layout(r, &dids, &dobj, nullptr, w->cap_frames, capM, nboard)));
-        recover_layout(r, &dids, &dobj, w->d_recover, w->cap_frames, capM, nboard);
+        if (const int e = carve_scratch(w, h, [&](Carver& cv) { recover_layout(r, &dids, &dobj, cv, w->cap_frames, capM, nboard); })) return e;
         a.cells_valid = w->cells_valid ? 1 : 0;
         HIPCHK(h, w->d_board.reserve((size_t)w->cap_frames * (sizeof(arucohip_board_t) + sizeof(float)) + 8192 * sizeof(int32_t)));
         arucohip_board_t* d_boards = w->d_board;

@@ -36,13 +36,25 @@ int check_call(arucohip_handle* h, const Call& c, bool need_K) {
     return check_disjoint(h, "rectify", "dst", c.dst, "src", c.src);
 }
 
+// The one layout of a call in the handle's arena: the plane maps it uploads or computes (n_maps frames; 0: the caller's are on the
+// device), the staged host frames and the images a host caller gets, tightly packed.
+struct Scratch {
+    PlaneMaps m;
+    size_t src_at, dst_at;
+};
+int carve(arucohip_handle* h, const Call& c, int n_maps, Scratch* sc) {
+    return carve_scratch(h, h, [&](Carver& cv) {
+        carve_plane_maps(cv, n_maps, &sc->m);
+        sc->src_at = cv.take_at(c.src.on_device ? 0 : c.src.packed_bytes());
+        sc->dst_at = cv.take_at(c.dst.on_device ? 0 : c.dst.packed_bytes());
+    });
+}
+
 // The resampling of a checked call with device maps: host frames go up, host images come back. Queues only; the caller synchronises.
-int warp(arucohip_handle* h, const Call& c, const double* maps, const int32_t* valid) {
-    const size_t src_bytes = c.src.on_device ? 0 : (c.src.packed_bytes() + 255) & ~(size_t)255;
-    HIPCHK(h, h->d_rectify_frames.reserve(src_bytes + (c.dst.on_device ? 0 : c.dst.packed_bytes())));
+int warp(arucohip_handle* h, const Call& c, const Scratch& sc, const double* maps, const int32_t* valid) {
     DevImages src, dst;
-    if (const int rc = stage_input(h, h->stream, c.src, h->d_rectify_frames, 0, &src)) return rc;
-    if (const int rc = stage_output(h, c.dst, h->d_rectify_frames, src_bytes, &dst)) return rc;
+    if (const int rc = stage_input(h, h->stream, c.src, h->scratch, sc.src_at, &src)) return rc;
+    if (const int rc = stage_output(h, c.dst, h->scratch, sc.dst_at, &dst)) return rc;
     PlaneWarp a;
     std::memset(&a, 0, sizeof(a));
     a.src = src.p, a.row_stride = src.row, a.frame_stride = src.frame;
@@ -70,8 +82,10 @@ int arucohip_warp_plane_batch(arucohip_handle* h, const uint8_t* src, int nframe
     if (!maps) return fail(h, ARUCOHIP_E_INVALID, "rectify: maps is NULL");
     if (const int rc = check_call(h, c, false)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    if (const int rc = stage_plane_maps(h, h->d_rectify, nframes, maps_on_device, &maps, &valid)) return rc;
-    if (const int rc = warp(h, c, maps, valid)) return rc;
+    Scratch sc;
+    if (const int rc = carve(h, c, maps_on_device ? 0 : nframes, &sc)) return rc;
+    if (const int rc = stage_plane_maps(h, sc.m, nframes, maps_on_device, &maps, &valid)) return rc;
+    if (const int rc = warp(h, c, sc, maps, valid)) return rc;
     if (!src_on_device || !maps_on_device || !dst_on_device) HIPCHK(h, hipStreamSynchronize(h->stream));
     return ARUCOHIP_OK;
 }
@@ -115,10 +129,11 @@ int arucohip_board_rectify_batch(arucohip_handle* h, const uint8_t* frames, int 
     if (!window_spans_plane(*win))
         return fail(h, ARUCOHIP_E_INVALID, "rectify: the window's u and v steps are parallel, zero or not finite");
     HIPCHK(h, hipSetDevice(h->device));
-    PlaneMaps m;
-    if (const int rc = plane_maps_of_boards(h, h->d_rectify, launch_plane_maps, boards, boards_on_device, nframes, *win, &m)) return rc;
-    if (const int rc = warp(h, c, m.maps, m.valid)) return rc;
-    if (const int rc = read_plane_maps(h, m, nframes, status, maps_out)) return rc;
+    Scratch sc;
+    if (const int rc = carve(h, c, nframes, &sc)) return rc;
+    if (const int rc = plane_maps_of_boards(h, sc.m, launch_plane_maps, boards, boards_on_device, nframes, *win)) return rc;
+    if (const int rc = warp(h, c, sc, sc.m.maps, sc.m.valid)) return rc;
+    if (const int rc = read_plane_maps(h, sc.m, nframes, status, maps_out)) return rc;
     if (!frames_on_device || !boards_on_device || !dst_on_device || status || maps_out) HIPCHK(h, hipStreamSynchronize(h->stream));
     return ARUCOHIP_OK;
 }

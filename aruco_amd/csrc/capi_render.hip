@@ -75,10 +75,11 @@ struct Scratch {
     float* vertices;
     int32_t* triangles;
     uint8_t* colors;
+    size_t frames_at, masks_at;   // staged host frames and masks
 };
 
 // The common part: `slots` instance slots per frame (cap for markers, 1 for boards). src / counts: device pointers, or host arrays of
-// `elem` bytes per slot that are staged behind the scratch. instances(stream, frames, src, counts, insts) enqueues the front kernel of
+// `elem` bytes per slot that are staged behind the records in the handle's arena, with the host mesh, frames and masks. instances(stream, frames, src, counts, insts) enqueues the front kernel of
 // one chunk.
 template <typename Instances>
 int render(arucohip_handle* h, const Call& c, const RdStyle& rs, const void* src, size_t elem, int slots, const int32_t* counts, int src_on_device,
@@ -91,21 +92,21 @@ int render(arucohip_handle* h, const Call& c, const RdStyle& rs, const void* src
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n, 65535, ((size_t)64 << 20) / per_frame}));
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
+    const bool stage_masks = c.masks.p && !c.masks.on_device;
     Scratch sc;
-    auto layout = [&](uint8_t* base) {
-        Carver cv{base};
-        sc.insts = cv.take<uint8_t>((size_t)chunk * slots * RD_INST_BYTES);
-        sc.verts = cv.take<uint8_t>((size_t)chunk * slots * m.nverts * RD_VERT_BYTES);
-        sc.tris = cv.take<uint8_t>((size_t)chunk * slots * m.ntris * RD_TRI_BYTES);
-        sc.src = cv.take<uint8_t>(src_on_device ? 0 : (size_t)n * slots * elem);
-        sc.counts = cv.take<int32_t>((src_on_device || !counts) ? 0 : (size_t)n);
-        sc.vertices = cv.take<float>(m.on_device ? 0 : (size_t)m.nverts * 3);
-        sc.triangles = cv.take<int32_t>(m.on_device ? 0 : (size_t)m.ntris * 3);
-        sc.colors = cv.take<uint8_t>((m.on_device || !m.colors) ? 0 : (size_t)m.ntris * 3);
-        return cv.at;
-    };
-    HIPCHK(h, h->d_render.reserve(layout(nullptr)));
-    layout(h->d_render);
+    if (const int rc = carve_scratch(h, h, [&](Carver& cv) {
+            sc.insts = cv.take<uint8_t>((size_t)chunk * slots * RD_INST_BYTES);
+            sc.verts = cv.take<uint8_t>((size_t)chunk * slots * m.nverts * RD_VERT_BYTES);
+            sc.tris = cv.take<uint8_t>((size_t)chunk * slots * m.ntris * RD_TRI_BYTES);
+            sc.src = cv.take<uint8_t>(src_on_device ? 0 : (size_t)n * slots * elem);
+            sc.counts = cv.take<int32_t>((src_on_device || !counts) ? 0 : (size_t)n);
+            sc.vertices = cv.take<float>(m.on_device ? 0 : (size_t)m.nverts * 3);
+            sc.triangles = cv.take<int32_t>(m.on_device ? 0 : (size_t)m.ntris * 3);
+            sc.colors = cv.take<uint8_t>((m.on_device || !m.colors) ? 0 : (size_t)m.ntris * 3);
+            sc.frames_at = cv.take_at(c.frames.on_device ? 0 : c.frames.packed_bytes());
+            sc.masks_at = cv.take_at(stage_masks ? c.masks.packed_bytes() : 0);
+        }))
+        return rc;
     if (!src_on_device) {
         HIPCHK(h, hipMemcpyAsync(sc.src, src, (size_t)n * slots * elem, hipMemcpyHostToDevice, s));
         src = sc.src;
@@ -121,13 +122,10 @@ int render(arucohip_handle* h, const Call& c, const RdStyle& rs, const void* src
         if (m.colors) HIPCHK(h, hipMemcpyAsync(sc.colors, m.colors, (size_t)m.ntris * 3, hipMemcpyHostToDevice, s));
         mesh.vertices = sc.vertices, mesh.triangles = sc.triangles, mesh.colors = m.colors ? sc.colors : nullptr;
     }
-    const bool stage_masks = c.masks.p && !c.masks.on_device;
-    const size_t frames_bytes = c.frames.on_device ? 0 : (c.frames.packed_bytes() + 255) & ~(size_t)255;
-    HIPCHK(h, h->d_render_frames.reserve(frames_bytes + (stage_masks ? c.masks.packed_bytes() : 0)));
     DevImages dev, mk = {nullptr, 0, 0};
-    if (const int rc = stage_input(h, s, c.frames, h->d_render_frames, 0, &dev)) return rc;
+    if (const int rc = stage_input(h, s, c.frames, h->scratch, sc.frames_at, &dev)) return rc;
     if (c.masks.p)
-        if (const int rc = stage_input(h, s, c.masks, h->d_render_frames, frames_bytes, &mk)) return rc;
+        if (const int rc = stage_input(h, s, c.masks, h->scratch, sc.masks_at, &mk)) return rc;
     CamModel cam;
     fill_cam(&cam, c.K, c.dist, c.ndist, 0.f, 0);
     // with timing (arucohip_enable_timing) the build and the raster of every chunk are bracketed by events and waited for

@@ -10,7 +10,7 @@
 
 extern "C" {
 
-// The writable ends of what a call uploads or gathers into d_rig: the board, the cameras, and the observation arrays (staging of
+// The writable ends of what a call uploads or gathers into the arena: the board, the cameras, and the observation arrays (staging of
 // host arrays, or a batch's gather). d.obs_* are set by rig_begin from where the observations are (RigObs).
 struct RigStage {
     int32_t* ids;
@@ -19,9 +19,8 @@ struct RigStage {
     int32_t *obs_view, *obs_id, *obs_cnt;
     float* obs_corners;
 };
-// d's arrays in `base` for T instants of C cameras, nboard markers and room for nobs staged observations; returns the bytes.
-static size_t rig_layout(RigDev& d, RigStage& w, uint8_t* base, int T, int C, int nboard, size_t nobs) {
-    Carver c{base};
+// d's arrays from `c` for T instants of C cameras, nboard markers and room for nobs staged observations.
+static void rig_layout(RigDev& d, RigStage& w, Carver& c, int T, int C, int nboard, size_t nobs) {
     const size_t t = (size_t)T, nc = (size_t)C, V = t * nc, N = (size_t)6 * (C - 1), nb = (size_t)nboard;
     d.st = c.take<RigState>(1), w.ids = c.take<int32_t>(nb), w.bobj = c.take<float>(nb * 12);
     d.cams = w.cams = c.take<RigCam>(nc);
@@ -36,13 +35,10 @@ static size_t rig_layout(RigDev& d, RigStage& w, uint8_t* base, int T, int C, in
     d.boards = c.take<arucohip_board_t>(t), d.views_used = c.take<int32_t>(t);
     w.obs_view = c.take<int32_t>(nobs), w.obs_id = c.take<int32_t>(nobs), w.obs_corners = c.take<float>(nobs * 8);
     w.obs_cnt = c.take<int32_t>(V);
-    return c.at;
 }
-// sized, reserved on o (the handle that owns the scratch), then bound there
+// sized, reserved on o (the handle whose arena holds the run), then bound there
 static int rig_reserve(arucohip_handle* h, arucohip_handle* o, RigDev& d, RigStage& w, int T, int C, int nboard, size_t nobs) {
-    HIPCHK(h, o->d_rig.reserve(rig_layout(d, w, nullptr, T, C, nboard, nobs)));
-    rig_layout(d, w, o->d_rig, T, C, nboard, nobs);
-    return ARUCOHIP_OK;
+    return carve_scratch(o, h, [&](Carver& c) { rig_layout(d, w, c, T, C, nboard, nobs); });
 }
 
 // the board and the cameras of a call, checked before anything runs
@@ -81,7 +77,7 @@ struct RigObs {
     int nobs, stride;
 };
 
-// d, bound in o's d_rig, gets the call's numbers and observations, and the board and the cameras go up on o's stream; the solve then
+// d, bound in o's arena, gets the call's numbers and observations, and the board and the cameras go up on o's stream; the solve then
 // starts with the view kernel. A rig pose passes the caller's camera transforms (pose_cams), which go up with the rest, so that nothing
 // waits between the view kernel and the pose kernel; a calibration passes null and computes them.
 static int rig_begin(arucohip_handle* o, RigDev& d, const RigStage& w, int ninstants, int ncams, const BoardDef& b, int min_markers,
@@ -106,7 +102,7 @@ static int rig_begin(arucohip_handle* o, RigDev& d, const RigStage& w, int ninst
     return ARUCOHIP_OK;
 }
 
-// observations given as arrays: staged in h's d_rig unless they are on the device already
+// observations given as arrays: staged in h's arena unless they are on the device already
 static int rig_stage(arucohip_handle* h, const RigStage& w, const int32_t* obs_view, const int32_t* obs_id, const float* obs_corners, int nobs,
                      int on_device, RigObs* obs) {
     ObsArrays at;
@@ -115,7 +111,7 @@ static int rig_stage(arucohip_handle* h, const RigStage& w, const int32_t* obs_v
     return rc;
 }
 
-// the markers of the first nframes frames of the last batch, laid out per view by the workers that hold them (in the owner's d_rig)
+// the markers of the first nframes frames of the last batch, laid out per view by the workers that hold them (in the owner's arena)
 static int rig_gather(arucohip_handle* h, const Batch& b, const RigStage& w, int nframes, int stride, RigObs* obs) {
     *obs = RigObs{nullptr, w.obs_id, w.obs_corners, w.obs_cnt, nframes * stride, stride};
     return on_workers(h, b, [&](const Span& s) {

@@ -108,6 +108,24 @@ struct arucohip_handle {
     bool cells_valid = false;         // buf.cells holds the last batch's cell medians (decode_from_cells; arucohip_debug_cells)
     Mem<uint8_t> d_gray;              // staging for host frames (gray) and the converted BGR frames
     Mem<uint8_t> d_bgr;               // staging for host BGR frames
+    // The call-scratch arena: the device memory an entry point needs for the length of one call, carved by carve_scratch (below).
+    // Every handle has one, chunk workers and lanes too, allocated at the first call that needs it.
+    // - It belongs to the entry point that is running; what it holds is dead to the host when the entry point returns.
+    // - An entry point reserves the arena of a given handle AT MOST ONCE, before it takes any pointer from it: one layout names all it
+    //   needs from that handle (records, staged sources and counts, staged host images, the images a host caller gets back). A call
+    //   spread over workers carves each worker's arena once, on that worker's stream, between fork and join.
+    // - w's arena is used only on w->stream, or on streams forked from it and joined to it again within the call. A call whose every
+    //   side is on the device returns without synchronising, so queued work may still read the arena; the next user is safe because it
+    //   queues on that same stream, and a growing reserve() goes through hipFree, which waits for the device. (A caller who changes
+    //   streams orders them: INTEGRATION.md.)
+    // What is not in it, and why:
+    // - memory a later call reads: d_board (resident board poses, read by ChromaticMask), d_charuco (resident corners), d_hrm (the
+    //   dictionary), d_umap_* / d_fmap_* (cached maps), hc_solver (pinned);
+    // - the detection pipeline's own memory: d_gray, d_bgr, walk_scratch, patches, d_erode, d_canny, d_pyr, d_user_dec, hu_list,
+    //   hu_patches and everything in `held`. The one-frame graph's address check (FrameGraph below) is about d_gray, walk_scratch and
+    //   patches, so nothing else may ever grow them;
+    // - d_charuco_views: the one buffer that lives across a nested entry point, which carves the arena itself.
+    Mem<uint8_t> scratch;
     arucohip_marker_t* wt_out = nullptr;   // set around detect_core by chunk_enqueue: finalize_kernel writes the results there too
     int32_t* wt_n = nullptr;
     int wt_cap = 0;
@@ -120,14 +138,11 @@ struct arucohip_handle {
     Mem<uint16_t> d_umap_f;
     int umap_w = 0, umap_h = 0, umap_nd = -1;
     float umap_K[9] = {}, umap_d[8] = {};
-    Mem<uint8_t> d_undist;            // undistorted frames when the caller wants them on the host
     // fisheye lenses (capi_fisheye.hip): a map slot of its own, so that a fisheye camera never evicts the pinhole map above
     Mem<short2> d_fmap_xy;
     Mem<uint16_t> d_fmap_f;
     int fmap_w = 0, fmap_h = 0;       // fmap_w = 0: none
     double fmap_key[18] = {};         // K (4), D (4), Knew (9), max_angle
-    Mem<uint8_t> d_fisheye;           // scratch of one call: staged points and results, or the models and the dropped counts of a marker call
-    Mem<uint8_t> d_fisheye_frames;    // staged host frames and the remapped frames a host caller gets
     std::vector<FisheyeCam> fisheye_cams;   // the models of the last marker call as they were copied to the workers
     Dictionary hrm;
     Mem<uint64_t> d_hrm;              // hrm.codes on the device
@@ -151,24 +166,11 @@ struct arucohip_handle {
     Mem<arucohip_board_t> d_board;    // batched board results + ids
     uint32_t* zero_block = nullptr;   // counters, gen_cnt, trig_cnt, raw_cnt, ring_cnt: zeroed together at the start of a batch
     size_t zero_words = 0;
-    Mem<double> d_gl;                 // batched GL modelview matrices
-    Mem<uint8_t> d_calib;             // camera calibration: solver state, per-view systems and poses, correspondences (calib_layout)
-    Mem<uint8_t> d_map;               // marker mapping: observations, slot tables, start values, per-frame systems, the reduced system (map_layout)
-    Mem<uint8_t> d_rig;               // camera rigs: observations, view slots, start values, per-view systems, the reduced system, poses (rig_layout)
     Mem<uint8_t> hc_solver{true};     // pinned copy of the state of whichever solver runs (lm_drive), read once per iteration: the calls are synchronous, so one serves all
-    Mem<uint8_t> d_planar;            // arucohip_planar_poses: results and staged markers of one call
-    Mem<uint8_t> d_overlay;           // arucohip_draw_*_batch: primitive lists of one chunk of frames, staged host markers / boards
-    Mem<uint8_t> d_overlay_frames;    // arucohip_draw_*_batch: staged host frames
-    Mem<uint8_t> d_rectify;           // arucohip_warp_plane_batch / arucohip_board_rectify_batch: maps, valid words and staged boards of one call
-    Mem<uint8_t> d_rectify_frames;    // ... and its staged host frames and the images a host caller gets
-    Mem<uint8_t> d_composite;         // arucohip_composite_plane_batch / arucohip_board_composite_batch: maps, valid words and staged boards of one call
-    Mem<uint8_t> d_composite_frames;  // ... and its staged host frames, textures and masks
-    Mem<uint8_t> d_recover;           // arucohip_board_recover_batch: the board, adoption records and work lists of one call (recover_layout)
     // arucohip_charuco_corners_batch (capi_charuco.hip), on the handle the caller holds: the corner records of the last call and their counts stay in
     // d_charuco for the calibration and the pose; the host keeps the layout and the counts
     Mem<uint8_t> d_charuco;           // records [frames][corners], then n_found [frames], then the layout's ids
-    Mem<uint8_t> d_charuco_frames;    // staged host frames of one call
-    Mem<uint8_t> d_charuco_work;      // the consumers' scratch: calibration views and points, poses
+    Mem<uint8_t> d_charuco_views;     // arucohip_charuco_calibrate_batch's gathered views: arucohip_calibrate_camera reads them and carves `scratch` itself
     struct Charuco {
         arucohip_charuco_t layout = {};
         int frames = 0;               // 0: no resident corners
@@ -193,10 +195,7 @@ struct arucohip_handle {
     bool thres_bytes = true;             // buf.thres holds the last batch's byte image (else: tiles + buf.thres_edge, expanded on demand)
     ThrPlan thr_plan_done{};             // the plan the last launch_threshold of this worker executed (arucohip_debug_threshold_plan)
     int thr_plan_planes = 0;             // its planes; 0: none yet, or the last threshold was CANNY
-    Mem<uint8_t> d_em;                   // arucohip_em_fit scratch
-    Mem<uint8_t> d_hrm_gen;              // HRM dictionary / board generation scratch (k_hrm.hip)
     int32_t hrm_stats[4] = {};           // the last arucohip_hrm_create_dictionary: windows, host synchronisations, acceptances, tau decrements
-    Mem<uint8_t> d_fiducial;             // 5x5 marker / board images, distance matrix and selection scratch (k_fiducial.hip)
     // One frame per call (the reference's call shape, arucohip_detect): the chain of ~20 dependent dispatches of a frame is captured once per
     // (geometry, parameters, camera) into a hipGraph and replayed with ONE launch per call; the frame's H2D copy stays outside (its source
     // pointer changes with every call), the results land in the handle's pinned staging inside the graph.
@@ -208,8 +207,8 @@ struct arucohip_handle {
     //   capture and replay; batches that decode from cell medians neither touch nor move buf.patches, and buf.cells is create-time memory;
     // - neither: the other Buffers arrays, zero_block and h_markers are create-time memory (`held`); d_erode, d_canny and the user decoder's
     //   staging and d_pyr belong to configurations that are not graphed; wt_out is set only inside chunk_enqueue, which does not run this path.
-    //   Memory no captured launch reads (d_bgr, undistortion, fisheye maps and scratch, calibration, marker mapping, camera rigs and the pinned solver state, board and GL batches, planar poses, marker recovery, overlays, mesh rendering, plane rectification and compositing, EM, HRM, fiducial generation, ChArUco corners and ChromaticMask scratch) may
-    //   be replaced at any time.
+    //   Memory no captured launch reads may be replaced at any time: the call-scratch arena (`scratch`), d_bgr, the cached undistortion and
+    //   fisheye maps, hc_solver, d_board, d_charuco and d_charuco_views, and what ChromaticMask objects own.
     struct FrameGraph {
         hipGraphExec_t exec = nullptr;
         uint64_t key = 0;          // digest of everything the captured launches carry by value
@@ -235,16 +234,6 @@ struct arucohip_handle {
         int32_t* n_out = nullptr;
     } pend;
     std::string err;
-    // arucohip_convert_batch (capi_ingest.hip): the raw host frames of one call, and the converted frames a host caller gets
-    Mem<uint8_t> d_ingest_src;
-    Mem<uint8_t> d_ingest;
-    // arucohip_export_batch (capi_egress.hip): the host frames of one call, and the exported frames a host caller gets
-    Mem<uint8_t> d_egress_src;
-    Mem<uint8_t> d_egress;
-    // arucohip_render_*_batch (capi_render.hip): instances, transformed vertices and triangle records of one chunk of frames with the staged
-    // host markers / boards and mesh behind them; the staged host frames and masks of one call
-    Mem<uint8_t> d_render;
-    Mem<uint8_t> d_render_frames;
     double render_ms[2] = {};            // with timing: build and raster kernel time summed over render_calls calls (arucohip_render_times)
     int render_calls = 0;
 };
@@ -272,24 +261,41 @@ int take_format(arucohip_handle* h, const arucohip_frame_format_t* fmt, FrameFmt
 int check_frame_format(arucohip_handle* h, const FrameFmt& fmt, int nframes, int W, int H, size_t row_stride, size_t frame_stride);
 
 // A call's scratch, laid out once: take() hands out consecutive 256-byte aligned arrays of `base`. A layout function names every
-// buffer in one take() and returns `at`, the bytes it needs; it runs twice, with a null base to size the memory (every take() is then
-// null) and, after reserve(), with the memory of the handle that owns the scratch to bind the pointers.
+// buffer in one take(); it runs twice, with a null base to size the memory (every take() is then null, and `at` ends as the bytes it
+// needs) and, after reserve(), with the memory of the handle that owns the scratch to bind the pointers.
 struct Carver {
     uint8_t* base;
     size_t at = 0;
+    // the offset of `bytes` more bytes: what stage_input / stage_output take for staged images
+    size_t take_at(size_t bytes) {
+        const size_t here = at;
+        at += (bytes + 255) & ~(size_t)255;
+        return here;
+    }
     template <class T>
     T* take(size_t count) {
-        const size_t here = at;
-        at += (count * sizeof(T) + 255) & ~(size_t)255;
+        const size_t here = take_at(count * sizeof(T));
         return base ? (T*)(base + here) : nullptr;
     }
 };
 
+// The one reservation of w's call-scratch arena (arucohip_handle::scratch) by the entry point that is running: layout(Carver&) takes
+// everything the call needs from w. Errors are reported on h.
+template <class Layout>
+int carve_scratch(arucohip_handle* w, arucohip_handle* h, Layout layout) {
+    Carver size{nullptr};
+    layout(size);
+    HIPCHK(h, w->scratch.reserve(size.at));
+    Carver bind{w->scratch.p};
+    layout(bind);
+    return ARUCOHIP_OK;
+}
+
 // Image batches of the caller (frames_host.h) as the kernels take them. A batch on the device is used where it lies, at the caller's
-// strides. A host batch is staged packed at mem + at, image i at i * staged_frame (0: the images back to back), in the Mem of the
-// entry point it belongs to, which the caller has reserved: stage_input queues the upload on s, stage_output queues nothing, unstage
-// queues the way back of an output or of a batch changed in place (nothing for a device batch). None of them synchronises. These and
-// the checks below are static, so the library's exported symbols stay the C ABI's and the older inline helpers'.
+// strides. A host batch is staged packed at mem + at, image i at i * staged_frame (0: the images back to back), in the arena of the
+// handle the call runs on, at an offset its layout carved (Carver::take_at): stage_input queues the upload on s, stage_output queues
+// nothing, unstage queues the way back of an output or of a batch changed in place (nothing for a device batch). None of them
+// synchronises. These and the checks below are static, so the library's exported symbols stay the C ABI's and the older inline helpers'.
 struct DevImages {
     uint8_t* p;
     size_t row, frame;
@@ -350,30 +356,21 @@ static inline int check_plane_camera(arucohip_handle* h, const char* call, bool 
     return fail(h, ARUCOHIP_E_INVALID, msg.c_str());
 }
 
-// The plane maps of one rectify or composite call, in the scratch of the entry point (d_rectify / d_composite): one 3 x 3 map and
-// one valid word per frame, and the staged boards of a board call.
+// The plane maps of one rectify or composite call, carved by the call's one layout from the arena: one 3 x 3 map and one valid word
+// per frame, and the staged boards of a board call.
 struct PlaneMaps {
     double* maps;
     int32_t* valid;
     arucohip_board_t* boards;
 };
-static inline int reserve_plane_maps(arucohip_handle* h, Mem<uint8_t>& mem, int n, PlaneMaps* m) {
-    auto layout = [&](uint8_t* base) {
-        Carver cv{base};
-        m->maps = cv.take<double>((size_t)n * 9);
-        m->valid = cv.take<int32_t>((size_t)n);
-        m->boards = cv.take<arucohip_board_t>((size_t)n);
-        return cv.at;
-    };
-    HIPCHK(h, mem.reserve(layout(nullptr)));
-    layout(mem);
-    return ARUCOHIP_OK;
+static inline void carve_plane_maps(Carver& cv, int n, PlaneMaps* m) {
+    m->maps = cv.take<double>((size_t)n * 9);
+    m->valid = cv.take<int32_t>((size_t)n);
+    m->boards = cv.take<arucohip_board_t>((size_t)n);
 }
-// the caller's own maps and valid words: where they are on the device, else uploaded on h's stream and *maps / *valid repointed
-static inline int stage_plane_maps(arucohip_handle* h, Mem<uint8_t>& mem, int n, int on_device, const double** maps, const int32_t** valid) {
+// the caller's own maps and valid words: where they are on the device, else uploaded to m on h's stream and *maps / *valid repointed
+static inline int stage_plane_maps(arucohip_handle* h, const PlaneMaps& m, int n, int on_device, const double** maps, const int32_t** valid) {
     if (on_device) return ARUCOHIP_OK;
-    PlaneMaps m;
-    if (const int rc = reserve_plane_maps(h, mem, n, &m)) return rc;
     HIPCHK(h, hipMemcpyAsync(m.maps, *maps, (size_t)n * 9 * sizeof(double), hipMemcpyHostToDevice, h->stream));
     *maps = m.maps;
     if (*valid) {
@@ -383,14 +380,13 @@ static inline int stage_plane_maps(arucohip_handle* h, Mem<uint8_t>& mem, int n,
     return ARUCOHIP_OK;
 }
 // the maps of a board call: host boards go up, `launch` (launch_plane_maps / launch_plane_inverse_maps) writes maps and valid words
-static inline int plane_maps_of_boards(arucohip_handle* h, Mem<uint8_t>& mem, decltype(launch_plane_maps)* launch, const arucohip_board_t* boards,
-                                int boards_on_device, int n, const arucohip_rectify_t& win, PlaneMaps* m) {
-    if (const int rc = reserve_plane_maps(h, mem, n, m)) return rc;
+static inline int plane_maps_of_boards(arucohip_handle* h, const PlaneMaps& m, decltype(launch_plane_maps)* launch, const arucohip_board_t* boards,
+                                int boards_on_device, int n, const arucohip_rectify_t& win) {
     if (!boards_on_device) {
-        HIPCHK(h, hipMemcpyAsync(m->boards, boards, (size_t)n * sizeof(arucohip_board_t), hipMemcpyHostToDevice, h->stream));
-        boards = m->boards;
+        HIPCHK(h, hipMemcpyAsync(m.boards, boards, (size_t)n * sizeof(arucohip_board_t), hipMemcpyHostToDevice, h->stream));
+        boards = m.boards;
     }
-    launch(h->stream, boards, n, win, m->maps, m->valid);
+    launch(h->stream, boards, n, win, m.maps, m.valid);
     HIPCHK(h, hipGetLastError());
     return ARUCOHIP_OK;
 }
@@ -551,7 +547,7 @@ inline int collect_markers(arucohip_handle* h, const Span& s, int cap, arucohip_
 }
 
 // Camera calibration (capi_calib.hip), shared by the pinhole and the fisheye entry points.
-// The views of one run, bound in the d_calib of the handle the run is on: the solver's arrays (d; d.obj / d.img may be the caller's
+// The views of one run, bound in the arena of the handle the run is on: the solver's arrays (d; d.obj / d.img may be the caller's
 // own device arrays), the staging of points and of a batch's gather, each view's offset and count.
 struct CalibViews {
     CalibDev d{};

@@ -197,8 +197,8 @@ def test_single_frame_graph_follows_batches_and_stage_calls_in_between(case, con
 
 def test_single_frame_graph_follows_bgr_batches_and_survives_undistort(monkeypatch):
     """The graph of a BGR frame reads the converted frame in d_gray. A batch of 4 BGR host frames regrows d_gray, so the next detect_bgr
-    must drop the graph and capture again; an undistort of 4 gray frames grows only staging no captured launch reads (d_bgr, d_undist), so
-    the graph is kept. Eager handle (ARUCOHIP_GRAPH=0 at creation) against the default handle, the same calls on both: detect_bgr x3, a
+    must drop the graph and capture again; an undistort of 4 gray frames stages in the handle's call-scratch arena and caches its map,
+    neither of which a captured launch reads, so the graph is kept. Eager handle (ARUCOHIP_GRAPH=0 at creation) against the default handle, the same calls on both: detect_bgr x3, a
     BGR batch of 4, detect_bgr x2, undistort, detect_bgr x2 - identical bytes at every step."""
     from aruco_amd import capi
 
