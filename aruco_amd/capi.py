@@ -256,6 +256,9 @@ class Limits(C.Structure):
                 ("long_walks_per_plane", C.c_int32)]
 
 
+# arucohip_debug_plane_counters: words of a plane's line; [PC_SEGMENTS] = 1 on a handle of the waypoint-segment pipeline
+PLANE_COUNTER_WORDS, PC_SEGMENTS = 36, 35
+
 MARKER_DTYPE = np.dtype([("id", "<i4"), ("corners", "<f4", (8,)), ("ssize", "<f4"), ("has_pose", "<i4"),
                          ("pad_", "<i4"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,))])
 assert MARKER_DTYPE.itemsize == 96 and C.sizeof(Marker) == 96
@@ -274,7 +277,7 @@ SYMBOLS = [
     "arucohip_debug_threshold_batch", "arucohip_debug_threshold_plan", "arucohip_debug_threshold_plane",
     "arucohip_board_detect", "arucohip_calculate_extrinsics", "arucohip_stage_times", "arucohip_stage_name",
     "arucohip_enable_timing", "arucohip_kernel_times", "arucohip_threshold_exec_ms", "arucohip_kernel_name",
-    "arucohip_debug_counters", "arucohip_board_detect_batch",
+    "arucohip_debug_counters", "arucohip_debug_plane_counters", "arucohip_board_detect_batch",
     "arucohip_gl_modelview", "arucohip_ogre_pose", "arucohip_gl_projection", "arucohip_ogre_projection",
     "arucohip_detect_bgr", "arucohip_detect_batch_bgr", "arucohip_bgr_to_gray", "arucohip_set_dictionary",
     "arucohip_set_decoder_callback",
@@ -368,6 +371,7 @@ def load():
     L.arucohip_threshold_exec_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]
     L.arucohip_kernel_name.argtypes = [i]
     L.arucohip_debug_counters.argtypes = [vp, vp]
+    L.arucohip_debug_plane_counters.argtypes = [vp, C.c_int, vp, C.c_int]
     L.arucohip_debug_start_candidates.argtypes = [vp, i, i, vp, i, vp]
     L.arucohip_debug_threshold_batch.argtypes = [vp, vp, i, i, i, C.c_size_t, C.c_size_t, i, i]
     L.arucohip_debug_threshold_plan.argtypes = [vp, vp, i, vp]
@@ -1523,10 +1527,21 @@ class Handle:
     def debug_counters(self):
         c = np.zeros(8, np.uint32)
         self._chk(self.L.arucohip_debug_counters(self.h, _ptr(c)))
-        return {"raw": int(c[4]), "triggers": int(c[0]), "contours": int(c[1]), "points": int(c[2]), "status": int(c[3]),
-                "long_walks": int(c[4]),   # walker mode: [4] = long walks (checkpoint rings handed out)
+        seg = bool(c[5])   # [4] counts what the batch's contour pipeline keeps: waypoint records (segments) or long walks; the other key is None
+        return {"raw": int(c[4]) if seg else None, "triggers": int(c[0]), "contours": int(c[1]), "points": int(c[2]), "status": int(c[3]),
+                "long_walks": None if seg else int(c[4]),   # walker mode: [4] = long walks (checkpoint rings handed out)
                 "late_walks": int(c[6]),   # of them: walks that reached the late generations (borders above 960 points)
                 "side_streams": int(c[7])}   # workers of the batch that own a side stream for those generations (a pipeline lane: 0)
+
+    def debug_plane_counters(self, plane):
+        """arucohip_debug_plane_counters: fill levels and overflow bits of one threshold plane (frame * planes per frame + t) of the last
+        batch, as the kernels left them. The counters keep counting past the capacities: they are the plane's demand."""
+        line = np.zeros(PLANE_COUNTER_WORDS, np.uint32)
+        self._chk(self.L.arucohip_debug_plane_counters(self.h, int(plane), _ptr(line), line.size))
+        seg = bool(line[PC_SEGMENTS])
+        return {"starts": (int(line[0]), int(line[1])), "contours": int(line[2]), "points": int(line[3]), "status": int(line[5]),
+                "late_contours": int(line[6]), "rings": None if seg else (int(line[32]), int(line[33])), "raw": int(line[34]) if seg else None,
+                "segments": seg}
 
     def gl_modelview_batch(self, nframes, cap=64):
         """Marker::glGetModelViewMatrix for every marker of the last batch (device kernel): list per frame of [n][16]."""

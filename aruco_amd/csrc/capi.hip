@@ -221,6 +221,8 @@ static int create_handle(const arucohip_params_t* params, int device, const aruc
     *out = nullptr;
     if (lim->max_width < 32 || lim->max_height < 32 || lim->max_width > 16383 || lim->max_height > 16383 || lim->max_batch < 1 ||
         lim->max_thres_planes < 1 || lim->max_thres_planes > 16 || lim->candidates_per_frame > MAX_CANDS_PER_FRAME || lim->markers_per_frame > 256 ||
+        lim->triggers_per_frame < 1 || lim->contours_per_frame < 1 || lim->points_per_frame < 1 || lim->candidates_per_frame < 1 ||
+        lim->markers_per_frame < 1 /* a zero is a list of no entries, a negative value a huge unsigned capacity */ ||
         (long)lim->max_width * lim->max_height > (1L << 26) /* Quad::key holds a 26-bit raster index */)
         return ARUCOHIP_E_INVALID;
     arucohip_handle* h = new arucohip_handle();
@@ -308,7 +310,8 @@ static int create_handle(const arucohip_params_t* params, int device, const aruc
     ALLOC(b.quads, F * b.cap_quads * sizeof(Quad));
     ALLOC(b.cands, F * b.cap_cands * sizeof(Cand));
     ALLOC(b.ncands, F * sizeof(int32_t));
-    b.cap_flat = (uint32_t)std::min<size_t>(F * (size_t)std::min(b.cap_cands, 96), 65535u * 16u);
+    // 96 candidates per frame on the batch's average, and never less than one frame's own candidate list: a single frame may fill it
+    b.cap_flat = (uint32_t)std::max<size_t>(std::min<size_t>(F * (size_t)std::min(b.cap_cands, 96), 65535u * 16u), (size_t)b.cap_cands);
     ALLOC(b.cand_list, (size_t)b.cap_flat * sizeof(uint32_t));
     ALLOC(b.iM, (size_t)b.cap_flat * 9 * sizeof(double));
     ALLOC(b.hist, (size_t)b.cap_flat * 256 * sizeof(uint16_t));
@@ -1507,8 +1510,30 @@ int arucohip_debug_counters(arucohip_handle* h, uint32_t* out8) {
     out8[0] = (uint32_t)std::min<uint64_t>(ntrig, 0xFFFFFFFFu);   // start candidates after the run rule (all planes)
     const bool seg = r.nspan > 0 && r.span[0].w->buf.seg_mode;
     out8[4] = (uint32_t)std::min<uint64_t>(seg ? nraw : nlong, 0xFFFFFFFFu);   // waypoint records (segment mode) / long walks = checkpoint rings handed out
+    out8[5] = seg ? 1u : 0u;                                      // which of the two [4] counts
     out8[6] = (uint32_t)std::min<uint64_t>(nlate, 0xFFFFFFFFu);   // long walks that reached the late generations (the ones a side stream carries)
     out8[7] = (uint32_t)nside;                                    // side streams among the workers that hold the batch (a pipeline lane: 0)
+    return ARUCOHIP_OK;
+}
+
+// One threshold plane's counters of the last batch as the kernels left them: reads, launches nothing. plane = frame * planes per frame + t.
+int arucohip_debug_plane_counters(arucohip_handle* h0, int plane, uint32_t* out, int cap) {
+    constexpr int WORDS = TRIG_CNT_STRIDE + 4;
+    if (!h0 || !out || plane < 0) return ARUCOHIP_E_INVALID;
+    if (cap < WORDS) return ARUCOHIP_E_CAPACITY;
+    const int nthr = h0->last.nthr;
+    int frame = 0;
+    arucohip_handle* h = h0->last.holder(plane / nthr, &frame);
+    if (!h) return ARUCOHIP_E_INVALID;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t at = ((size_t)frame * nthr + plane % nthr) * TRIG_CNT_STRIDE;
+    uint32_t rings[2] = {}, raw = 0;
+    HIPCHK(h, hipMemcpyAsync(out, h->buf.trig_cnt + at, TRIG_CNT_STRIDE * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(rings, h->buf.ring_cnt + at, sizeof(rings), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&raw, h->buf.raw_cnt + at, sizeof(raw), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    out[TRIG_CNT_STRIDE] = rings[0], out[TRIG_CNT_STRIDE + 1] = rings[1], out[TRIG_CNT_STRIDE + 2] = raw;
+    out[TRIG_CNT_STRIDE + 3] = h->buf.seg_mode ? 1u : 0u;
     return ARUCOHIP_OK;
 }
 

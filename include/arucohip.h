@@ -418,7 +418,26 @@ int arucohip_pyr_down(arucohip_handle* h, const uint8_t* src, int nframes, int w
                       int src_on_device, int levels, uint8_t* dst, int dst_on_device);
 /* After an asynchronous batch: synchronise and report device-side overflow / capacity conditions. */
 int arucohip_batch_status(arucohip_handle* h);
-/* Device lists are finite (arucohip_limits_t), the reference's vectors are not (src/markerdetector.cpp:496-635). When a list overflows
+/* Capacities of the device lists, from arucohip_limits_t (F = frames per worker: max_batch, or ceil(max_batch / ARUCOHIP_STREAMS)). triggers_per_frame,
+ * contours_per_frame, points_per_frame, candidates_per_frame and markers_per_frame must be at least 1 (ARUCOHIP_E_INVALID otherwise),
+ * candidates_per_frame at most 512, markers_per_frame at most 256. The bits are those of the batch status word. Per threshold plane:
+ *   start candidates      max(triggers_per_frame, 8192) / 2 of each kind (outer, hole)                      bit 1  (triggers)
+ *   waypoint records      triggers_per_frame, no minimum (segment pipeline: one small frame per call)        bit 1; a graph cut short may add bit 64
+ *   long-walk rings       min(max(long_walks_per_plane, 64), 65536) of each kind; the walks of one generation share lists of that many
+ *                         entries times the planes rounded up to 8, in up to 8 sublists by plane              bit 1
+ *   border descriptors    contours_per_frame: borders of at most 960 points from slot 0 upwards, longer ones (the late list) from the last slot
+ *                         downwards, in the room the first kind left                                          bit 2  (contours)
+ *   points pool           points_per_frame words (fewer when planes * points_per_frame would pass 2^32 - 16): a border of n points takes n words,
+ *                         on the walker pipeline ceil(n / 16) checkpoint words in front of them as well          bit 4  (points)
+ * Per frame, all its planes together:
+ *   quads                 min(2 * candidates_per_frame, 512): with several threshold planes a frame of more than 512 quads cannot be held by
+ *                         any handle and is always reported                                                   bit 8  (quads)
+ *   candidates            candidates_per_frame (after the near-duplicate removal)                            bit 16 (candidates)
+ *   markers               markers_per_frame                                                                  bit 32 (markers)
+ * Per batch:
+ *   flat decode list      max(F * min(candidates_per_frame, 96), candidates_per_frame): 96 candidates per frame on the batch's average, and one
+ *                         frame alone may always fill its own candidate list; the frames that do not fit are given up whole    bit 16
+ * Device lists are finite (arucohip_limits_t), the reference's vectors are not (src/markerdetector.cpp:496-635). When a list overflows
  * the call returns ARUCOHIP_E_OVERFLOW, but only the frames it happened to are given up: their n_out is -1, every other frame of the batch
  * holds its complete result. arucohip_detect_batch_retry_overflowed takes the arguments of the batch call that returned the code (after it
  * has completed: arucohip_batch_status / _wait for device outputs) and runs the frames with n_out = -1 again, one at a time, on an internal
@@ -519,10 +538,18 @@ int arucohip_debug_threshold_plan(arucohip_handle* h, int32_t* out, int cap, int
 int arucohip_debug_threshold_plane(arucohip_handle* h, int frame, int t, uint8_t* bytes, uint64_t* tiles, uint64_t* tile_bits);
 
 /* Device list fill levels of the last batch: [0] border-start candidates, [1] borders kept, [2] contour points,
- * [3] overflow bits, [4] long walks (waypoint records in segment mode). For sizing arucohip_limits_t. For tests: [6] the long walks that
+ * [3] overflow bits, [4] long walks (waypoint records in segment mode), [5] 1 when the batch ran on the waypoint-segment pipeline, so that [4]
+ * counts waypoint records, else 0. For sizing arucohip_limits_t. For tests: [6] the long walks that
  * reached the late generations (borders of more than 960 points), [7] how many of the workers that hold the batch own a side stream for
  * those generations (a pipeline lane, arucohip_set_pipeline_depth, owns none: its batch runs on one stream). */
 int arucohip_debug_counters(arucohip_handle* h, uint32_t* out8);
+/* Test hook: the counters of ONE threshold plane of the last batch (plane = frame * planes per frame + t), read as the kernels left them; nothing
+ * is launched. The counters keep counting past the capacities, so a generous handle's values are the plane's demand on each list. out, at least 36
+ * words: [0] outer and [1] hole start candidates, [2] borders kept, [3] pool words (points and the checkpoints in front of them), [5] the plane's own
+ * overflow bits (the bits of the batch status word; a frame with a bit on any of its planes is given up), [6] borders of the late list, [32] outer and
+ * [33] hole long walks (checkpoint rings asked for), [34] waypoint records (segment pipeline), [35] 1 when the handle follows borders by waypoint
+ * segments. cap below 36: ARUCOHIP_E_CAPACITY; a plane outside the last batch: ARUCOHIP_E_INVALID. */
+int arucohip_debug_plane_counters(arucohip_handle* h, int plane, uint32_t* out, int cap);
 
 /* Test hook: the pixel-domain corner kernels on corners of the caller's. gray: one host frame with its row stride (kept on the device,
  * at most four times the handle's width); corners_xy: ncorners x,y pairs, refined in place. locked_wsize > 0 runs findCornerMaxima with that
@@ -539,8 +566,8 @@ int arucohip_debug_refine_pixels(arucohip_handle* h, const uint8_t* gray, int wi
  * and nframes choose the kernels exactly as a batch of nframes frames would: one or two frames store the patch, three or more with the built-in 5x5
  * decoder and warp_size 56 keep the cell medians instead. Outputs, each optional, in the order of the quads: iM [n][9] inverse homographies,
  * hist [n][256], thr [n] Otsu thresholds, cells49 [n][49] (written when *paths & 1: the cell medians were kept), patches [n][warp_size^2] (written
- * when *paths & 2: the patches were stored), ids / nrot [n] (id -1: not a marker). n is 1..the flat candidate list (max_batch * min(candidates_per_frame,
- * 96)) and at most candidates_per_frame quads per frame: ARUCOHIP_E_CAPACITY beyond; a frame index outside the call: ARUCOHIP_E_INVALID; the
+ * when *paths & 2: the patches were stored), ids / nrot [n] (id -1: not a marker). n is 1..the capacity of the flat decode list (the formula above
+ * arucohip_detect_batch_retry_overflowed) and at most candidates_per_frame quads per frame: ARUCOHIP_E_CAPACITY beyond; a frame index outside the call: ARUCOHIP_E_INVALID; the
  * caller's decoder (ARUCOHIP_DECODER_USER): ARUCOHIP_E_UNSUPPORTED. Everything is checked before anything runs. Uses the handle's candidate
  * lists: results of the last batch are gone afterwards. */
 int arucohip_debug_decode_quads(arucohip_handle* h, const uint8_t* gray, int nframes, int width, int height, size_t row_stride,

@@ -43,6 +43,22 @@ def test_library_loads_and_host_only_calls():
     assert L.arucohip_stage_name(0).decode() == "Threshold" and L.arucohip_kernel_name(0).decode() == "threshold_kernel"
 
 
+def test_limits_below_one_are_refused_at_creation():
+    """A zero would be a list of no entries and a negative value a huge unsigned capacity: arucohip_create_ex checks every limit before it touches
+    the device, so this needs none."""
+    L = capi.load()
+    p = capi.default_params()
+    for field in ("triggers_per_frame", "contours_per_frame", "points_per_frame", "candidates_per_frame", "markers_per_frame", "max_batch",
+                  "max_thres_planes"):
+        for bad in (0, -1, -(1 << 31)):
+            lim = capi.Limits()
+            L.arucohip_default_limits(C.byref(lim), 640, 480, 2)
+            setattr(lim, field, bad)
+            h = C.c_void_p(1)
+            assert L.arucohip_create_ex(C.byref(p), 0, C.byref(lim), C.byref(h)) == capi.E_INVALID, (field, bad)
+            assert not h.value
+
+
 def test_shim_header_compiles_without_opencv(tmp_path):
     """The C++ shim (reference class API on the C ABI) compiles and links with a plain host compiler."""
     exe = tmp_path / "aruco_simple"

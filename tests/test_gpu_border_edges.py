@@ -85,7 +85,7 @@ def single_frames(env, expected, max_batch, what):
                 assert d["status"] == 0, (what, fmt, fam, i, d)
                 total += len(kept)
                 s = sums.setdefault(fmt, {"long_walks": 0, "late_walks": 0})
-                s["long_walks"] += d["long_walks"]
+                s["long_walks"] += d["raw"] if d["long_walks"] is None else d["long_walks"]
                 s["late_walks"] += d["late_walks"]
         finally:
             hd.close()

@@ -234,11 +234,17 @@ def test_more_than_64_rejected_candidates(scene):
 
 
 def test_a_frame_the_batch_gave_up_stays_given_up(scene):
-    """A one-frame handle's flat candidate list holds 96 entries: the frame with the squares overflows it and comes back with n = -1."""
+    """A handle of 96 candidates a frame (a one-frame handle's flat list held no more, whatever its limits said, until a single frame could fill
+    its own candidate list): the frame with the squares, more than 128 candidates, overflows it and comes back with n = -1."""
+    from aruco_amd import capi
+
     ids, obj = scene["ids"], scene["obj"]
     _, quads = rr.build_frame(ids, obj)
     gray, _ = rr.build_frame(ids, obj, {1: [(3, 3)]}, squares=rr.background_squares(quads))
-    h = make_handle(1)
+    lim = capi.Limits()
+    capi.load().arucohip_default_limits(C.byref(lim), rr.W, rr.H, 1)
+    lim.candidates_per_frame = 96
+    h = make_handle(1, limits=lim)
     try:
         markers, _, first = h.detect_batch_host_tolerant(gray[None], K=KF, marker_size=rr.MARKER_SIZE, retry=False)
         assert markers[0] is None and first[0] == -1

@@ -26,5 +26,5 @@ kt = h.kernel_times()
 c = h.debug_counters()
 tot = sum(kt.values())
 print(json.dumps({"tag": a.tag, "frames": a.frames, "fps_device": round(a.frames / tot * 1e3, 1), "total_ms": round(tot, 3),
-                  "kernel_ms": {k: round(v, 3) for k, v in kt.items()}, "per_frame": {k: v / a.frames for k, v in c.items()},
+                  "kernel_ms": {k: round(v, 3) for k, v in kt.items()}, "per_frame": {k: v / a.frames for k, v in c.items() if v is not None},
                   "markers": float(cnt.float().mean())}))
